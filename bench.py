@@ -20,6 +20,9 @@ value    = whole-job 16 kHz samples per second (sum over GPUs / max-over-ranks t
            Every stream of every rank has its own seeded feature file (1000 + rank*streams + s); after the timed loop
            `--check-streams` streams of the timed output are replayed on the plain-C oracle (checker leg) and
            compared bit for bit: `parity_checked` in the JSON line.
+           `--dump-outputs DIR` writes that same output -- the PCM a caller of the timed path receives from its last timed
+           step -- as DIR/pcm.npy (float32, [streams][frames x 160]; DIR/pcm_rank<r>.npy per rank when N > 1).  Models and
+           features are seeded, so equal arguments give equal inputs and two builds can be compared output for output.
            `--gpus N` without a launcher re-executes itself under `python -m torch.distributed.run` with N ranks;
            `--gpus 2 --share-device` rehearses that path on ONE GPU (both ranks on device 0, gloo control plane).
 roofline = the sample kernel (dominant, >98 % of the step).  SURVEY.md §8(d): not MFMA; the primary bound
@@ -59,6 +62,9 @@ LDS_OPERAND_BYTES_PER_SAMPLE_I8 = 96432 # int8 GRU-A 59 544 + int8 GRU-B 21 912 
 PEAK_FP32_TFLOPS = 157.3                # MI355X_MICROARCH.md: fp32 vector peak
 PEAK_HBM_GBS = 8000.0
 PEAK_LDS_TBS = 150.0
+DUMP_LIMIT_BYTES = 64 << 20             # --dump-outputs: at most this much per run
+SHARE_DEVICE_MAX_RANKS = 4              # --share-device: GPU hosts shared with other work allow six processes on a device at a time; four ranks leave
+                                        # room for the process that started the rehearsal (a test run, a profiler)
 MEASURED_FP32_MUL_ADD_TFLOPS = 66.9      # tools/ubench/peaks.hip (profiles/r04_roofline_measured.json): separately rounded multiply + add, no FMA,
                                         # as PACKED math (v_pk_mul_f32 + v_pk_add_f32: 66.9; scalar v_mul_f32 + v_add_f32: 59.5) -- the VALU-only
                                         # ceiling of the PARITY arithmetic (the kernel also forms exact products on the matrix pipe)
@@ -203,6 +209,16 @@ def cpu_baseline(int8_line=False):
             "unstable": flav[main]["unstable"], "cpu_model": cpu_model(), "flavour": main, "flavours": flav,
             "sample": f"{procs} independent single-threaded processes, each pinned to its own core, x {frames} frames ({frames / 100:.1f} s of audio), "
                       f"warm-up + best of 3, {names[main]}; {cores} usable host cores of {os.cpu_count()} ({cpu_model()})"}
+
+
+def dump_output(dirname, name, arr):
+    """--dump-outputs: DIR/<name>.npy, float32 (exact for int16 PCM); an array over DUMP_LIMIT_BYTES is cut down to a fixed, seeded
+    sample of its rows (streams), the same rows in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    keep = DUMP_LIMIT_BYTES // (4 * arr[0].size)
+    if arr.shape[0] > keep:
+        arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], keep, replace=False))]
+    np.save(os.path.join(dirname, name + ".npy"), arr.astype(np.float32))
 
 
 def kernel_source_hash():
@@ -371,10 +387,11 @@ def _self_launch(a):
     """`python bench.py --gpus N` without a launcher: become N ranks (one per GPU) under torch.distributed.run."""
     import socket
     import subprocess
-    import torch
-    have = torch.cuda.device_count()
-    if have < a.gpus and not a.share_device:
-        raise SystemExit(f"bench.py: --gpus {a.gpus} but only {have} HIP device(s) are visible")
+    if not a.share_device:                                   # (a rehearsal's launcher never opens the GPU: it would hold it open next to its ranks)
+        import torch
+        have = torch.cuda.device_count()
+        if have < a.gpus:
+            raise SystemExit(f"bench.py: --gpus {a.gpus} but only {have} HIP device(s) are visible")
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
@@ -414,8 +431,15 @@ def main():
                     "`value` is the rate at the largest count whose p99 meets the deadline)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of the multi-rank path on ONE GPU: every rank uses device 0 and the control plane is gloo "
-                         "(RCCL cannot put two ranks on one device); the line it prints is a plumbing check, not a scaling number")
+                         "(RCCL cannot put two ranks on one device), at most 4 ranks; the line it prints is a plumbing check, not a scaling number")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the PCM of the last timed step of the headline workload to DIR/pcm.npy (float32; a seeded sample of the streams if "
+                         "all of them exceed 64 MB), so that two builds can be compared output for output")
     a = ap.parse_args()
+    if a.share_device and a.gpus > SHARE_DEVICE_MAX_RANKS:
+        ap.error(f"--share-device takes at most {SHARE_DEVICE_MAX_RANKS} ranks: every rank is one more process on the same device")
+    if a.dump_outputs and a.rt:
+        ap.error("--dump-outputs covers the headline workload, not --rt")
 
     import torch
     import torch.distributed as dist
@@ -442,7 +466,7 @@ def main():
     if a.rt:
         return rt_main(a, world, rank, local, dev)
 
-    def run_workload(n, F, int8, steps, warmup, fast=False, fp16_fc=False, spw=0, densities="", check_streams=8, seed0=1000, skew=0.0):
+    def run_workload(n, F, int8, steps, warmup, fast=False, fp16_fc=False, spw=0, densities="", check_streams=8, seed0=1000, skew=0.0, dump_dir=""):
         """`warmup` untimed + `steps` timed passes of the hot path over n streams x F frames (features / PCM resident in HBM), then the live kernel
         timing and the checker leg; returns the figures of one workload."""
         mk = dict(flavour="int8" if int8 else "float")
@@ -500,6 +524,8 @@ def main():
         ms_frame = float(np.median([k[1] for k in ks]))
         nonzero = int(torch.count_nonzero(d_pcm).item())
         assert nonzero > 0.5 * d_pcm.numel(), "benchmark output is degenerate"
+        if dump_dir:
+            dump_output(dump_dir, "pcm" if world == 1 else f"pcm_rank{rank}", timed_pcm.cpu().numpy())
         # checker leg (rank 0): replay a few streams of the timed region on the plain-C oracle -- the same features fed
         # warmup + steps times in a row from reset -- and compare the last step's PCM bit for bit
         parity_checked = 0
@@ -528,7 +554,8 @@ def main():
                 "envelope": envelope}
 
     n, F = a.streams, a.frames
-    head = run_workload(n, F, a.int8, a.steps, a.warmup, fast=a.fast, fp16_fc=a.fp16_fc, spw=a.spw, densities=a.densities, check_streams=a.check_streams, skew=a.skew)
+    head = run_workload(n, F, a.int8, a.steps, a.warmup, fast=a.fast, fp16_fc=a.fp16_fc, spw=a.spw, densities=a.densities, check_streams=a.check_streams, skew=a.skew,
+                        dump_dir=a.dump_outputs)
     value, ms_sample, ms_frame, parity_checked, samples_per_step, nb_a = (head[k] for k in ("value", "ms_sample", "ms_frame", "parity_checked", "samples_per_step", "nb_a"))
 
     def lds_frac(rec, int8):

@@ -1,5 +1,5 @@
-"""The generated constant tables (tools/gen_tables.py) against the reference's own tables, when the
-reference tree is mounted; otherwise against their closed formulas only."""
+"""The generated constant tables (tools/gen_tables.py) against the reference's own tables -- their values pinned in
+tests/golden/ref_tables_v1.npz (tests/tools/make_golden_tables.py) -- and against their closed formulas."""
 import math
 import os
 import re
@@ -12,29 +12,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_tables  # noqa: E402
 
-REF = "/root/reference/src"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
+
+@pytest.fixture(scope="module")
+def ref_tables():
+    return np.load(os.path.join(ROOT, "tests", "golden", "ref_tables_v1.npz"))
 
 
-def _floats(text):
-    return np.array([float(x) for x in re.findall(r"(-?\d+\.\d+(?:e-?\d+)?)f", text)], np.float32)
+def test_tansig_matches_reference_header(ref_tables):
+    ref = ref_tables["tansig"]
+    assert ref.dtype == np.float32 and ref.size == 201 and np.array_equal(ref, gen_tables.tansig())
 
 
-@needs_ref
-def test_tansig_matches_reference_header():
-    ref = _floats(open(os.path.join(REF, "tansig_table.h")).read())
-    assert ref.size == 201 and np.array_equal(ref, gen_tables.tansig())
-
-
-@needs_ref
-def test_fft_and_dct_tables_match_reference():
-    t = open(os.path.join(REF, "lpcnet_tables.c")).read()
-    br = np.array([int(x) for x in re.findall(r"-?\d+", re.search(r"fft_bitrev\[\d*\]\s*=\s*\{([^}]*)\}", t).group(1))])
-    assert np.array_equal(br, gen_tables.fft_bitrev())
-    tw = _floats(re.search(r"fft_twiddles\[\d*\]\s*=\s*\{(.*?)\};", t, re.S).group(1)).reshape(-1, 2)
-    assert np.array_equal(tw, gen_tables.fft_twiddles())
-    dct = _floats(re.search(r"dct_table\[\d*\]\s*=\s*\{(.*?)\};", t, re.S).group(1))
-    assert np.array_equal(dct, gen_tables.idct_table())
+def test_fft_and_dct_tables_match_reference(ref_tables):
+    assert ref_tables["fft_bitrev"].size == 320 and np.array_equal(ref_tables["fft_bitrev"], gen_tables.fft_bitrev())
+    tw = ref_tables["fft_twiddles"]
+    assert tw.dtype == np.float32 and tw.shape == (320, 2) and np.array_equal(tw, gen_tables.fft_twiddles())
+    dct = ref_tables["dct_table"]
+    assert dct.dtype == np.float32 and dct.size == 324 and np.array_equal(dct, gen_tables.idct_table())
 
 
 def test_headers_are_in_sync_with_generator():

@@ -73,8 +73,8 @@ for fl, suffix in (("f32", ""), ("i8", "_int8"), ("f32_fast", "_fast"), ("i8_fas
 for src, dst in (("bench_single.json", "bench_single_stream.json"), ("bench_f32_fast.json", "bench_n1_fast.json"),
                  ("bench_i8_fast.json", "bench_n1_int8_fast.json"), ("rtf_demo.json", "demo_single_stream_rtf.json"),
                  ("bench_f32_fast_f16.json", "bench_n1_fast_fp16fc.json"), ("bench_i8_fast_f16.json", "bench_n1_int8_fast_fp16fc.json"),
-                 ("bench_rehearsal_2ranks.json", "bench_rehearsal_2ranks_one_gpu.json"), ("bench_rehearsal_8ranks.json", "bench_rehearsal_8ranks_one_gpu.json"),
-                 ("bench_rehearsal_8ranks_int8.json", "bench_rehearsal_8ranks_one_gpu_int8.json"),
+                 ("bench_rehearsal_2ranks.json", "bench_rehearsal_2ranks_one_gpu.json"), ("bench_rehearsal_4ranks.json", "bench_rehearsal_4ranks_one_gpu.json"),
+                 ("bench_rehearsal_4ranks_int8.json", "bench_rehearsal_4ranks_one_gpu_int8.json"),
                  ("bench_rt_f32.json", "bench_rt_f32.json"), ("bench_rt_int8.json", "bench_rt_int8.json"),
                  ("bench_skewed.json", "bench_n1_skewed.json"), ("bench_skewed_int8.json", "bench_n1_skewed_int8.json"),
                  ("bench_denseA_nw32.json", "bench_n1_denseA_nw32.json"), ("bench_denseA_nw36.json", "bench_n1_denseA_nw36.json"),
