@@ -7,6 +7,7 @@
 #include <vector>
 #include "lpcnet_engine.h"
 #include "lpcnet_tables_gen.h"
+#include "sample_variants.h"
 #include "sample_kernel.hip.h"
 #include "frame_kernels.hip.h"
 #include "decode_kernel.hip.h"
@@ -34,22 +35,22 @@ struct DeviceGuard {
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
 
+// GRU-A as dealt to waves and lanes, once per dealing: the model part of the argument block with that image's pointers, and the compiled
+// items-per-lane variant its item arrays are padded to.  PARITY's always exists; FAST has its own for int8 blobs (dealt without candidate heads);
+// the two-group kernel's (float blobs; model_pack.c: lpcn_model_pack_x2) is the only one with the natural-order embedding tables.
+enum { IMG_PARITY, IMG_FAST, IMG_X2, IMG_COUNT };
+struct GruAImage { LpcnSampleArgs args{}; int nw_variant = 0; bool present = false; };
+
 struct lpcn_engine {
     int device = 0;
-    int nw = 0, nw_variant = 0, nb_b = 0;
+    int nw = 0, nb_b = 0;
     bool is_int8 = false;
     bool fc_f16 = false;               // FAST sub-option: fp16 dual FC (lpcn_engine_set_fast(e, 2))
     bool fast = false;                 // FAST arithmetic (lpcn_engine_set_fast): fused / integer accumulation instead of the reference's generic-C order
     float lpc_gamma = 1.f;
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
-    LpcnSampleArgs sargs{};        // model part filled at creation
-    LpcnSampleArgs sargs_fast{};   // the same with the FAST arithmetic's own GRU-A packing (int8 blobs: dealt without candidate heads)
-    bool has_fast_image = false;
-    int nw_variant_fast = 0;
-    LpcnSampleArgs sargs_x2{};     // the same with the two-group kernel's own GRU-A packing (float blobs; model_pack.c: lpcn_model_pack_x2)
-    bool has_x2_image = false;
-    int nw_variant_x2 = 0;
+    GruAImage image[IMG_COUNT];
     LpcnFrameModel fmodel{};
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
@@ -61,6 +62,8 @@ struct lpcn_batch_dev {
     bool S_auto = true;                // streams per workgroup are chosen by the engine (measured on this batch, see autotune_streams_per_wg)
     bool tuned = false;                // ... and have been measured for the current arithmetic flavour
     bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
+    bool no_x2 = false;                // LPCNET_HIP_NO_X2=1 when the batch was created (tools / tests): never the two-group kernel
+    int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
     lpcn_stream_state *d_state = nullptr;
     int *d_fc_base = nullptr;
     float *d_cond_a = nullptr, *d_cond_b = nullptr, *d_lpc = nullptr, *d_cond = nullptr;
@@ -133,6 +136,15 @@ static int upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
     return 0;
 }
 
+// compiled item counts per lane (sample_variants.h), zero-terminated: fp32 items are 4 VGPRs each, int8 items 1 VGPR
+#define LPCN_LIST_ITEM(n) n,
+static const int variants_f32[] = {LPCN_VARIANTS_F32(LPCN_LIST_ITEM) 0};
+static const int variants_i8[] = {LPCN_VARIANTS_I8(LPCN_LIST_ITEM) 0};
+static const int variants_x2[] = {LPCN_VARIANTS_X2(LPCN_LIST_ITEM) 0};
+#undef LPCN_LIST_ITEM
+// the smallest compiled variant that holds nw items per lane (0: none does)
+static int round_up_variant(const int *v, int nw) { for (; *v; ++v) if (nw <= *v) return *v; return 0; }
+
 extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_model_host *m)
 {
     *out = nullptr;
@@ -142,11 +154,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
         return LPCN_E_NODEVICE;
     }
     if (device < 0 || device >= ndev) { snprintf(g_err, sizeof(g_err), "bad device %d (have %d)", device, ndev); return LPCN_E_ARG; }
-    // compiled item counts per lane: fp32 items are 4 VGPRs each, int8 items 1 VGPR
-    static const int variants_f32[] = {24, 28, 30, 32, 36, 40, 48, 64, 80, 96, 0};
-    static const int variants_i8[] = {32, 48, 64, 96, 0};
-    int nwv = 0;
-    for (const int *v = m->is_int8 ? variants_i8 : variants_f32; *v; ++v) if (m->nw <= *v) { nwv = *v; break; }
+    const int nwv = round_up_variant(m->is_int8 ? variants_i8 : variants_f32, m->nw);
     if (!nwv) {
         snprintf(g_err, sizeof(g_err), "GRU-A does not fit the kernel's item variants (needs %d items on one lane, max 96: more than three full rows' worth of blocks on one wave)", m->nw);
         return LPCN_E_MODEL;
@@ -154,15 +162,17 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     DeviceGuard guard(device);
     lpcn_engine *e = new lpcn_engine();
     e->device = device;
-    e->nw = m->nw; e->nw_variant = nwv; e->nb_b = m->nb_b_padded; e->lpc_gamma = m->lpc_gamma;
+    e->nw = m->nw; e->nb_b = m->nb_b_padded; e->lpc_gamma = m->lpc_gamma;
     e->is_int8 = m->is_int8 != 0;
     int rc = 0;
     auto fail = [&](int code) { lpcn_engine_destroy(e); return code; };
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return fail(LPCN_E_HIP);
 
-    LpcnSampleArgs &a = e->sargs;
+    LpcnSampleArgs &a = e->image[IMG_PARITY].args;
     // GRU-A as dealt to waves and lanes (model_pack.c) + the embedding tables in that lane order: everything that depends on the dealing
-    auto upload_gru_a = [&](const lpcn_model_host *mm, LpcnSampleArgs &dst, int nwv_) -> int {
+    auto upload_gru_a = [&](const lpcn_model_host *mm, GruAImage &img, int nwv_) -> int {
+        LpcnSampleArgs &dst = img.args;
+        dst = a;                                               // (what does not depend on the dealing is PARITY's)
         // re-pad the item arrays from the model's nw to the compiled variant
         const size_t item_dw = mm->is_int8 ? 1 : 4;            // dwords per (lane, item)
         const uint32_t *src = mm->is_int8 ? (const uint32_t *)mm->pk_a_wq : (const uint32_t *)mm->pk_a_w;
@@ -196,15 +206,11 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
             UPD(float, emb_exc, mm->pk_emb[2], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
         }
 #undef UPD
+        img.nw_variant = nwv_; img.present = true;
         return 0;
     };
-    if ((rc = upload_gru_a(m, a, nwv))) return fail(rc);
+    if ((rc = upload_gru_a(m, e->image[IMG_PARITY], nwv))) return fail(rc);
 #define UP(T, field, src, count) if ((rc = upload<T>(e, &a.field, src, count))) return fail(rc)
-    if (!m->is_int8) {                                       // the tables in the blob's own [256][1152] order: the start-value pass of the two-group kernel
-        UP(float, emb_nat_sig, m->emb_sig, (size_t)256 * LPCN_ROWS_A);
-        UP(float, emb_nat_pred, m->emb_pred, (size_t)256 * LPCN_ROWS_A);
-        UP(float, emb_nat_exc, m->emb_exc, (size_t)256 * LPCN_ROWS_A);
-    }
     UP(float, a_bias1, m->a_bias + LPCN_ROWS_A, LPCN_ROWS_A);
     UP(float, a_diag, m->a_diag, LPCN_ROWS_A);
     if (m->is_int8) {
@@ -248,17 +254,17 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
         // the two-group kernel (eight float streams per workgroup) runs on its own dealing of GRU-A: chains on waves 0, 1, rows on waves 2..7
         lpcn_model_host mx;
         if (lpcn_model_pack_x2(m, &mx) == 0) {
-            static const int variants_x2[] = {24, 28, 30, 32, 0};
-            int nwx = 0;
-            for (const int *v = variants_x2; *v; ++v) if (mx.nw <= *v) { nwx = *v; break; }
+            const int nwx = round_up_variant(variants_x2, mx.nw);
             mx.pk_b_w = m->pk_b_w; mx.pk_b_start = m->pk_b_start; mx.pk_b_blk = m->pk_b_blk;      // (the check reads GRU-B's packing too: shared)
             const int stx = lpcn_model_selftest(&mx);
             mx.pk_b_w = nullptr; mx.pk_b_start = nullptr; mx.pk_b_blk = nullptr;
             if (nwx && stx == 0) {
-                e->sargs_x2 = e->sargs;
-                rc = upload_gru_a(&mx, e->sargs_x2, nwx);
-                e->nw_variant_x2 = nwx;
-                e->has_x2_image = rc == 0;
+                LpcnSampleArgs &ax = e->image[IMG_X2].args;
+                rc = upload_gru_a(&mx, e->image[IMG_X2], nwx);
+                // ... and the tables in the blob's own [256][1152] order: the start-value pass of the two-group kernel, their only reader
+                if (!rc) rc = upload<float>(e, &ax.emb_nat_sig, m->emb_sig, (size_t)256 * LPCN_ROWS_A);
+                if (!rc) rc = upload<float>(e, &ax.emb_nat_pred, m->emb_pred, (size_t)256 * LPCN_ROWS_A);
+                if (!rc) rc = upload<float>(e, &ax.emb_nat_exc, m->emb_exc, (size_t)256 * LPCN_ROWS_A);
             }
             lpcn_model_release(&mx);
             if (rc) return fail(rc);
@@ -269,14 +275,8 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
         const int pf = getenv("LPCNET_HIP_NO_FAST_IMAGE") ? 1 : lpcn_model_pack_fast(m, &mf);
         if (pf < 0) { snprintf(g_err, sizeof(g_err), "packing the FAST image of GRU-A failed"); return fail(LPCN_E_MODEL); }
         if (pf == 0) {
-            int nwf = 0;
-            for (const int *v = variants_i8; *v; ++v) if (mf.nw <= *v) { nwf = *v; break; }
-            if (nwf) {
-                e->sargs_fast = e->sargs;
-                rc = upload_gru_a(&mf, e->sargs_fast, nwf);
-                e->nw_variant_fast = nwf;
-                e->has_fast_image = rc == 0;
-            }
+            const int nwf = round_up_variant(variants_i8, mf.nw);
+            if (nwf) rc = upload_gru_a(&mf, e->image[IMG_FAST], nwf);
             lpcn_model_release(&mf);
             if (rc) return fail(rc);
         }
@@ -372,34 +372,29 @@ extern "C" int lpcn_engine_set_lpc_gamma(lpcn_engine *e, float gamma)
 // ------------------------------------------------------------------------------------ batches --
 // Streams per workgroup: one workgroup occupies a CU, so a batch runs in ceil(workgroups / CUs) rounds; a round with S
 // interleaved streams costs step[S] (measured us per sample step, tests/tools/gpu_sweep.py).  Pick the cheapest.
-// (measured, us per sample step: tests/tools/gpu_sweep.py, tools/gpu_call_*.sh)
 static int device_cus(const lpcn_engine *e)
 {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) return prop.multiProcessorCount;
     return 256;
 }
-// items per lane of the GRU-A image the engine's current arithmetic runs on
-static int cur_nw_variant(const lpcn_engine *e) { return (e->fast && e->has_fast_image) ? e->nw_variant_fast : e->nw_variant; }
-static bool pack2_available(const lpcn_engine *e) { return e->is_int8 && cur_nw_variant(e) <= 32; }
+// The GRU-A image a launch at S streams per workgroup runs on: the two-group kernel's at eight; else FAST's own where the engine's
+// current arithmetic is FAST and it has one; else PARITY's.
+static const GruAImage &gru_a_image(const lpcn_engine *e, int S) { return e->image[S == 8 ? IMG_X2 : (e->fast && e->image[IMG_FAST].present) ? IMG_FAST : IMG_PARITY]; }
+static bool pack2_available(const lpcn_engine *e) { return e->is_int8 && gru_a_image(e, 4).nw_variant <= 32; }
 // Two groups of four float streams per workgroup, half a step apart (sample_kernel_x2.hip.h): float blobs, PARITY arithmetic, dense GRU-B input
-// matrix, <= 32 items per lane.  b->S == 8 selects it.
-static bool x2_available(const lpcn_engine *e)
+// matrix, <= 32 items per lane.  Eight streams per workgroup select it.
+static bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast; }
+static bool use_pack2(const lpcn_batch_dev *b, int n, int S)
 {
-    const char *off = getenv("LPCNET_HIP_NO_X2");            // tools / tests: "1" = never
-    if (off && *off == '1') return false;
-    return e->has_x2_image && !e->fast;
-}
-static bool use_pack2(const lpcn_engine *e, int n, int S)
-{
-    const char *force = getenv("LPCNET_HIP_PACK2");          // tools / tests: "0" never, "1" whenever the variant exists
     // (S = 4 needs ~92 KB of LDS per workgroup: two do not fit a CU, and the 128-VGPR code alone is slower -- measured 119 vs 137 M)
-    if (S > 2 || !pack2_available(e)) return false;
-    if (force && *force) return *force == '1';
-    return (n + S - 1) / S > device_cus(e);
+    if (S > 2 || !pack2_available(b->e)) return false;
+    if (b->pack2_force >= 0) return b->pack2_force == 1;
+    return (n + S - 1) / S > device_cus(b->e);
 }
-static int auto_streams_per_wg(const lpcn_engine *e, int n)
+static int auto_streams_per_wg(const lpcn_batch_dev *b, int n)
 {
+    const lpcn_engine *e = b->e;
     const int cus = device_cus(e);
     static const float step_f32[3] = {6.5f, 7.6f, 9.9f}, step_i8[3] = {4.4f, 5.5f, 7.3f};
     static const float step_f32_fast[3] = {6.0f, 7.0f, 8.9f}, step_i8_fast[3] = {4.4f, 5.0f, 7.0f};
@@ -412,11 +407,11 @@ static int auto_streams_per_wg(const lpcn_engine *e, int n)
     for (int k = 0; k < 3; ++k) {
         const int S = 1 << k, wgs = (n + S - 1) / S;
         float t;
-        if (use_pack2(e, n, S)) t = (float)((wgs + 2 * cus - 1) / (2 * cus)) * pair[k];
+        if (use_pack2(b, n, S)) t = (float)((wgs + 2 * cus - 1) / (2 * cus)) * pair[k];
         else t = (float)((wgs + cus - 1) / cus) * step[k];
         if (k == 0 || t < best_t) { best = S; best_t = t; }
     }
-    if (x2_available(e)) {                                   // eight streams per workgroup: a round of the two-group kernel (us per sample step)
+    if (x2_available(b)) {                                   // eight streams per workgroup: a round of the two-group kernel (us per sample step)
         static const float step_x2 = 13.9f;
         const int wgs = (n + 7) / 8;
         const float t = (float)((wgs + cus - 1) / cus) * step_x2;
@@ -432,8 +427,10 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     DeviceGuard guard(e->device);
     lpcn_batch_dev *b = new lpcn_batch_dev();
     b->e = e; b->n = n; b->max_chunk = max_chunk;
-    b->S = auto_streams_per_wg(e, n);
-    b->pack2 = use_pack2(e, n, b->S);
+    const char *off = getenv("LPCNET_HIP_NO_X2"), *force = getenv("LPCNET_HIP_PACK2");      // (read once per batch, never on the launch path)
+    b->no_x2 = off && *off == '1'; b->pack2_force = (force && *force) ? *force == '1' : -1;
+    b->S = auto_streams_per_wg(b, n);
+    b->pack2 = use_pack2(b, n, b->S);
     auto fail = [&](int code) { lpcn_batch_dev_destroy(b); return code; };
 #define AL(ptr, bytes) if (hipMalloc((void **)&ptr, (bytes)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", (size_t)(bytes)); return fail(LPCN_E_HIP); }
     AL(b->d_state, sizeof(lpcn_stream_state) * n);
@@ -514,22 +511,21 @@ extern "C" int lpcn_batch_dev_set_state(lpcn_batch_dev *b, int s, const lpcn_str
     HIP_TRY(hipMemcpy(b->d_state + s, host, sizeof(*host), hipMemcpyHostToDevice));
     return 0;
 }
-extern "C" int lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b) { return b->S; }
 // the engine's arithmetic flavour changed: re-run the cost model unless the caller pinned the value
 extern "C" int lpcn_batch_dev_retune(lpcn_batch_dev *b)
 {
-    if (b->S_auto) { b->S = auto_streams_per_wg(b->e, b->n); b->tuned = false; }      // measured again at the next run
-    b->pack2 = use_pack2(b->e, b->n, b->S);
+    if (b->S_auto) { b->S = auto_streams_per_wg(b, b->n); b->tuned = false; }      // measured again at the next run
+    b->pack2 = use_pack2(b, b->n, b->S);
     return 0;
 }
 extern "C" int lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s)
 {
     b->S_auto = s == 0;
-    if (s == 0) { s = auto_streams_per_wg(b->e, b->n); b->tuned = false; }
-    if (s == 8 && !x2_available(b->e)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane, PARITY arithmetic"); return LPCN_E_ARG; }
+    if (s == 0) { s = auto_streams_per_wg(b, b->n); b->tuned = false; }
+    if (s == 8 && !x2_available(b)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane, PARITY arithmetic"); return LPCN_E_ARG; }
     if (s != 1 && s != 2 && s != 4 && s != 8) { snprintf(g_err, sizeof(g_err), "streams per workgroup must be 1, 2, 4 or 8"); return LPCN_E_ARG; }
     b->S = s;
-    b->pack2 = use_pack2(b->e, b->n, b->S);
+    b->pack2 = use_pack2(b, b->n, b->S);
     return 0;
 }
 extern "C" int lpcn_batch_dev_set_frame_len(lpcn_batch_dev *b, int n)
@@ -560,50 +556,77 @@ extern "C" int lpcn_launch_sample_s4(int nw, int is_int8, int flags, int grid, i
 extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x2.hip: two groups of four streams
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
 
-// one chunk of the per-sample kernel; cond_a/cond_b/lpc for the chunk are already in the batch buffers
-static int launch_sample(lpcn_batch_dev *b, hipStream_t st, short *d_pcm, size_t pcm_stride, int n_frames,
-                         int preload, bool fc_from_frames)
+// What a launch works on and the batch does not own for good: a call on part of the batch, on other states or with another S passes another
+// shape; nothing overwrites the batch's settings to steer a launch.
+struct LaunchShape {
+    int n, frame_len;                  // streams in this launch, samples per frame
+    lpcn_stream_state *d_state;        // [n] the states it reads and writes
+    int S;                             // streams per workgroup asked for (plan_sample() decides what the launch gets)
+    bool pack2;                        //   ... and use_pack2() for that S
+};
+static LaunchShape whole_batch(const lpcn_batch_dev *b) { return {b->n, b->frame_len, b->d_state, b->S, b->pack2}; }
+
+// Which sample kernel a launch of n_frames frames per stream gets, on which GRU-A image.  No side effects.
+struct SamplePlan {
+    int S;                             // streams per workgroup the launch runs with
+    bool pack2;
+    const GruAImage *image;            // (with its items-per-lane variant)
+    int lds, grid;                     // dynamic LDS bytes per workgroup, workgroups
+};
+static SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_frames)
 {
-    if (b->S == 8 && !x2_available(b->e)) { b->S = 4; b->pack2 = false; }      // (the arithmetic flavour changed under a pinned value)
-    // (the two-group kernel addresses the launch's conditioning rows with 32-bit byte offsets: launches beyond 4 GB of them -- more than ~9 300 streams x
-    // 100 frames -- run on the four-stream kernel)
-    const int S_keep = b->S;
-    if (b->S == 8 && (unsigned long long)b->n * (unsigned long long)n_frames * LPCN_ROWS_A * 4ull >= (1ull << 32)) b->S = 4;
-    struct SRestore { lpcn_batch_dev *b; int s; ~SRestore() { b->S = s; } } s_restore{b, S_keep};
-    LpcnSampleArgs a = b->S == 8 ? b->e->sargs_x2 : ((b->e->fast && b->e->has_fast_image) ? b->e->sargs_fast : b->e->sargs);
-    a.n_streams = b->n; a.n_frames = n_frames; a.preload = preload; a.frame_len = b->frame_len;
+    const lpcn_engine *e = b->e;
+    SamplePlan p{sh.S, sh.pack2, nullptr, 0, 0};
+    // Eight streams per workgroup become four (a) while the two-group kernel is unavailable (the arithmetic flavour changed under a pinned value) and
+    // (b) for a launch with 4 GB or more of conditioning rows -- more than ~9 300 streams x 100 frames -- which the two-group kernel, addressing them
+    // with 32-bit byte offsets, cannot reach
+    if (sh.S == 8 && (!x2_available(b) || (unsigned long long)sh.n * (unsigned long long)n_frames * LPCN_ROWS_A * 4ull >= (1ull << 32))) { p.S = 4; p.pack2 = false; }
+    p.image = &gru_a_image(e, p.S);
+    p.lds = p.S == 8 ? lpcn_x2_lds_bytes(e->nb_b) : p.S == 1 ? lpcn::Lds<1>::total(e->nb_b, e->is_int8) : p.S == 2 ? lpcn::Lds<2>::total(e->nb_b, e->is_int8) : lpcn::Lds<4>::total(e->nb_b, e->is_int8);
+    p.grid = (sh.n + p.S - 1) / p.S;
+    return p;
+}
+// (what a whole-batch launch of one frame runs with: four while FAST arithmetic is on under a pinned eight)
+extern "C" int lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b) { return plan_sample(b, whole_batch(b), 1).S; }
+
+// one chunk of the per-sample kernel; cond_a/cond_b/lpc for the chunk are already in the batch buffers
+static int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, short *d_pcm, size_t pcm_stride, int n_frames, int preload, bool fc_from_frames)
+{
+    const lpcn_engine *e = b->e;
+    const SamplePlan p = plan_sample(b, sh, n_frames);
+    const int nw = p.image->nw_variant;
+    LpcnSampleArgs a = p.image->args;
+    a.n_streams = sh.n; a.n_frames = n_frames; a.preload = preload; a.frame_len = sh.frame_len;
     a.fc_advance = fc_from_frames ? 1 : 0;
     a.cond_a = b->d_cond_a; a.cond_b = b->d_cond_b; a.lpc = b->d_lpc;
     a.fc_base = fc_from_frames ? b->d_fc_base : nullptr;
     a.pcm = d_pcm; a.pcm_stride = (long long)pcm_stride;
-    a.state = b->d_state; a.dbg = b->d_dbg; a.prof = b->d_prof;
-    a.fc_f16 = (b->e->fast && b->e->fc_f16) ? 1 : 0;
+    a.state = sh.d_state; a.dbg = b->d_dbg; a.prof = b->d_prof;
+    a.fc_f16 = (e->fast && e->fc_f16) ? 1 : 0;
     if (stream_is_capturing(st)) {
         hipLaunchKernelGGL(lpcn_set_args_kernel, dim3(1), dim3(1), 0, st, b->d_args, a);
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemcpyAsync(b->d_args, &a, sizeof(a), hipMemcpyHostToDevice, st));
     }
-    const int i8 = b->e->is_int8 ? 1 : 0;
-    const int fast = (b->e->fast ? 1 : 0) | (b->pack2 ? 2 : 0);
-    const int nwv = cur_nw_variant(b->e);
-    int lds = 0, rc = 0;
-    const int grid = (b->n + b->S - 1) / b->S;
-    switch (b->S) {
-    case 8: lds = lpcn_x2_lds_bytes(b->e->nb_b); rc = lpcn_launch_sample_x2(b->e->nw_variant_x2, grid, lds, st, b->d_args); break;
-    case 1: lds = lpcn::Lds<1>::total(b->e->nb_b, b->e->is_int8); rc = lpcn_launch_sample_s1(nwv, i8, fast, grid, lds, st, b->d_args); break;
-    case 2: lds = lpcn::Lds<2>::total(b->e->nb_b, b->e->is_int8); rc = lpcn_launch_sample_s2(nwv, i8, fast, grid, lds, st, b->d_args); break;
-    default: lds = lpcn::Lds<4>::total(b->e->nb_b, b->e->is_int8); rc = lpcn_launch_sample_s4(nwv, i8, fast, grid, lds, st, b->d_args); break;
+    const int i8 = e->is_int8 ? 1 : 0;
+    const int flags = (e->fast ? 1 : 0) | (p.pack2 ? 2 : 0);
+    int rc = 0;
+    switch (p.S) {
+    case 8: rc = lpcn_launch_sample_x2(nw, p.grid, p.lds, st, b->d_args); break;
+    case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
+    case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
+    default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
     }
+    if (rc == LPCN_NO_SUCH_VARIANT) { snprintf(g_err, sizeof(g_err), "no compiled sample-kernel variant for %d items per lane at %d streams per workgroup", nw, p.S); return LPCN_E_HIP; }
     if (rc) { snprintf(g_err, sizeof(g_err), "sample kernel launch failed: %s", hipGetErrorString((hipError_t)rc)); return LPCN_E_HIP; }
     return 0;
 }
 
-static int launch_frames(lpcn_batch_dev *b, hipStream_t st, const float *d_feat, int feat_stride,
-                         size_t feat_stream_stride, int n_frames)
+static int launch_frames(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, const float *d_feat, int feat_stride, size_t feat_stream_stride, int n_frames)
 {
-    return lpcn_launch_frame_kernels(b->e->fmodel, st, b->n, n_frames, d_feat, feat_stride, feat_stream_stride,
-                                     b->d_state, b->d_fc_base, b->d_cond, b->d_cond_a, b->d_cond_b, b->d_lpc, g_err, sizeof(g_err));
+    return lpcn_launch_frame_kernels(b->e->fmodel, st, sh.n, n_frames, d_feat, feat_stride, feat_stream_stride,
+                                     sh.d_state, b->d_fc_base, b->d_cond, b->d_cond_a, b->d_cond_b, b->d_lpc, g_err, sizeof(g_err));
 }
 
 // Streams per workgroup, measured instead of looked up (the table in auto_streams_per_wg holds THIS model's step
@@ -638,19 +661,17 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
         hipMemsetAsync(b->d_lpc, 0, sizeof(float) * (size_t)b->n * nf * LPCN_LPC_ORDER, st) != hipSuccess ||
         hipMemcpyAsync(b->d_fc_base, fc.data(), sizeof(int) * b->n, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) { snprintf(g_err, sizeof(g_err), "auto-tune: buffer setup failed"); return done(LPCN_E_HIP); }
-    const int keepS = b->S;
-    const bool keepP = b->pack2;
-    int best = keepS;
+    int best = b->S;
     float best_ms = -1.f;
     for (int S = 1; S <= 8; S *= 2) {
-        if (S == 8 && (!x2_available(b->e) || b->n <= 4)) break;
-        b->S = S; b->pack2 = use_pack2(b->e, b->n, S);
+        if (S == 8 && (!x2_available(b) || b->n <= 4)) break;
+        const LaunchShape sh = {b->n, b->frame_len, b->d_state, S, use_pack2(b, b->n, S)};
         float ms = -1.f, ms1 = 0.f;
         for (int pass = 0; pass < 7 && !rc; ++pass) {          // warm-up (1 frame), then three pairs of (1 frame, nf frames): the smallest difference
             const int k = (pass && !(pass & 1)) ? nf : 1;
             float t = 0.f;
             if (hipEventRecord(b->ev[1], st) != hipSuccess) rc = LPCN_E_HIP;
-            if (!rc) rc = launch_sample(b, st, pcm, (size_t)nf * LPCN_FRAME_SIZE, k, 0, true);
+            if (!rc) rc = launch_sample(b, sh, st, pcm, (size_t)nf * LPCN_FRAME_SIZE, k, 0, true);
             if (!rc && (hipEventRecord(b->ev[2], st) != hipSuccess || hipEventSynchronize(b->ev[2]) != hipSuccess ||
                         hipEventElapsedTime(&t, b->ev[1], b->ev[2]) != hipSuccess)) rc = LPCN_E_HIP;
             if (pass & 1) ms1 = t;
@@ -662,8 +683,8 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
     // the measurement ran on the real state: put it back
     if (hipMemcpyAsync(b->d_state, saved, sizeof(lpcn_stream_state) * b->n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) rc = rc ? rc : LPCN_E_HIP;
-    if (rc) { b->S = keepS; b->pack2 = keepP; return done(rc); }
-    b->S = best; b->pack2 = use_pack2(b->e, b->n, best);
+    if (rc) return done(rc);
+    b->S = best; b->pack2 = use_pack2(b, b->n, best);
     return done(0);
 }
 
@@ -680,10 +701,13 @@ extern "C" int lpcn_batch_dev_tune(lpcn_batch_dev *b)
     return order_end(b, st);
 }
 
-// may_tune: the call may measure the streams per workgroup first (allocates, synchronises, launches trial kernels).  Only the
-// host-pointer wrappers pass true; the enqueue-only device-pointer entry points never do, whichever stream they name (ADVICE r4:
-// a NULL hip_stream used to select the engine's own stream AND the measurement).
-static int run_impl(lpcn_batch_dev *b, const float *d_features, int feat_stride, short *d_pcm, int n_frames, int preload, void *hip_stream, bool may_tune)
+// The measurement before the first run of a batch whose value is not pinned (allocates, synchronises, launches trial kernels).  Only the
+// host-pointer entry points call it, on the engine's own stream, and BEFORE they make their launch shape, so that the measuring call itself
+// runs on the measured value; the enqueue-only device-pointer entry points never do, whichever stream they name (a NULL hip_stream
+// used to select the engine's own stream AND the measurement).
+static int tune_if_due(lpcn_batch_dev *b, hipStream_t st) { return (b->S_auto && !b->tuned) ? autotune_streams_per_wg(b, st) : 0; }
+
+static int run_impl(lpcn_batch_dev *b, const LaunchShape &sh, const float *d_features, int feat_stride, short *d_pcm, int n_frames, int preload, void *hip_stream)
 {
     if (n_frames <= 0 || feat_stride < LPCN_NB_FEAT || preload < 0 || preload > LPCN_FRAME_SIZE) {
         snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG;
@@ -693,14 +717,13 @@ static int run_impl(lpcn_batch_dev *b, const float *d_features, int feat_stride,
     float tf = 0.f, ts = 0.f;
     { int rco = order_begin(b, st); if (rco) return rco; }
     if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (the step call's per-stream frame products are stale now)
-    if (b->S_auto && !b->tuned && may_tune && st == b->e->stream) { int rct = autotune_streams_per_wg(b, st); if (rct) return rct; }      // (never inside an enqueue-only call, never on a caller's stream)
     for (int f0 = 0; f0 < n_frames; f0 += b->max_chunk) {
         const int nf = n_frames - f0 < b->max_chunk ? n_frames - f0 : b->max_chunk;
         if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], st));
-        int rc = launch_frames(b, st, d_features + (size_t)f0 * feat_stride, feat_stride, (size_t)n_frames * feat_stride, nf);
+        int rc = launch_frames(b, sh, st, d_features + (size_t)f0 * feat_stride, feat_stride, (size_t)n_frames * feat_stride, nf);
         if (rc) return rc;
         if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
-        rc = launch_sample(b, st, d_pcm + (size_t)f0 * LPCN_FRAME_SIZE, (size_t)n_frames * LPCN_FRAME_SIZE, nf, preload, true);
+        rc = launch_sample(b, sh, st, d_pcm + (size_t)f0 * LPCN_FRAME_SIZE, (size_t)n_frames * LPCN_FRAME_SIZE, nf, preload, true);
         if (rc) return rc;
         if (b->timing) {
             HIP_TRY(hipEventRecord(b->ev[2], st));
@@ -718,7 +741,7 @@ static int run_impl(lpcn_batch_dev *b, const float *d_features, int feat_stride,
 extern "C" int lpcn_batch_dev_run(lpcn_batch_dev *b, const float *d_features, int feat_stride,
                                   short *d_pcm, int n_frames, int preload, void *hip_stream)
 {
-    return run_impl(b, d_features, feat_stride, d_pcm, n_frames, preload, hip_stream, false);
+    return run_impl(b, whole_batch(b), d_features, feat_stride, d_pcm, n_frames, preload, hip_stream);
 }
 
 static int ensure_staging(lpcn_batch_dev *b, size_t feat_floats, size_t pcm_samples)
@@ -751,7 +774,8 @@ extern "C" int lpcn_batch_dev_run_host(lpcn_batch_dev *b, const float *features,
     if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
     HIP_TRY(hipMemcpyAsync(b->d_feat, features, nfeat * sizeof(float), hipMemcpyHostToDevice, st));
     if (preload > 0) HIP_TRY(hipMemcpyAsync(b->d_pcm, pcm, npcm * sizeof(short), hipMemcpyHostToDevice, st));
-    rc = run_impl(b, b->d_feat, feat_stride, b->d_pcm, n_frames, preload, st, true);
+    if ((rc = tune_if_due(b, st))) return rc;
+    rc = run_impl(b, whole_batch(b), b->d_feat, feat_stride, b->d_pcm, n_frames, preload, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, npcm * sizeof(short), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -779,7 +803,8 @@ extern "C" int lpcn_batch_dev_run_single(lpcn_batch_dev *b, const lpcn_stream_st
     }
     memcpy(pin + off_feat, feat, LPCN_NB_FEAT * sizeof(float));
     HIP_TRY(hipMemcpyAsync(b->d_feat, pin + off_feat, LPCN_NB_FEAT * sizeof(float), hipMemcpyHostToDevice, st));
-    rc = run_impl(b, b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, 0, st, true);
+    if ((rc = tune_if_due(b, st))) return rc;
+    rc = run_impl(b, whole_batch(b), b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, 0, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(pin, b->d_state, sizeof(lpcn_stream_state), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(pin + off_pcm, b->d_pcm, LPCN_FRAME_SIZE * sizeof(short), hipMemcpyDeviceToHost, st));
@@ -838,14 +863,12 @@ extern "C" int lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int 
         HIP_TRY(hipMemcpyAsync(b->d_cond_b, pin + off_gb, sizeof(float) * LPCN_ROWS_B * k, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b->d_lpc, pin + off_lpc, sizeof(float) * LPCN_LPC_ORDER * k, hipMemcpyHostToDevice, st));
     }
-    const int keepS = b->S, keep_len = b->frame_len;
-    const bool keepP = b->pack2, keepA = b->S_auto, keepT = b->tuned;
-    b->n = k; b->frame_len = samples ? frame_len : keep_len; b->S = auto_streams_per_wg(b->e, k); b->pack2 = use_pack2(b->e, k, b->S); b->S_auto = false; b->tuned = true;
+    const int S = auto_streams_per_wg(b, k);               // (the table's value for the group's size, never a measurement)
+    const LaunchShape sh = {k, samples ? frame_len : b->frame_len, b->d_state, S, use_pack2(b, k, S)};
     if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);
-    if (kind == LPCN_GROUP_FRAME_SAMPLES) rc = run_impl(b, b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, preload, st, false);      // (S comes from the table for the group's size)
-    else if (kind == LPCN_GROUP_TAIL) rc = launch_sample(b, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, preload, false);
-    else rc = launch_frames(b, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
-    b->n = cap; b->frame_len = keep_len; b->S = keepS; b->pack2 = keepP; b->S_auto = keepA; b->tuned = keepT;
+    if (kind == LPCN_GROUP_FRAME_SAMPLES) rc = run_impl(b, sh, b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, preload, st);
+    else if (kind == LPCN_GROUP_TAIL) rc = launch_sample(b, sh, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, preload, false);
+    else rc = launch_frames(b, sh, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(pin, b->d_state, sz_st * k, hipMemcpyDeviceToHost, st));
     if (samples) HIP_TRY(hipMemcpyAsync(pin + off_pcm, b->d_pcm, sizeof(short) * LPCN_FRAME_SIZE * k, hipMemcpyDeviceToHost, st));
@@ -886,7 +909,8 @@ static int decode_impl(lpcn_batch_dev *b, const unsigned char *d_packets, short 
     hipLaunchKernelGGL(lpcn::decode_kernel, dim3((b->n + 1) / 2), dim3(64), 0, st, b->e->dec, d_packets, b->n, n_packets, b->d_vq_mem,
                        b->d_feat, LPCN_NB_FEAT);
     HIP_TRY(hipGetLastError());
-    return run_impl(b, b->d_feat, LPCN_NB_FEAT, d_pcm, T, 0, st, may_tune);
+    if (may_tune) { int rct = tune_if_due(b, st); if (rct) return rct; }      // (decode_host only: the engine's own stream)
+    return run_impl(b, whole_batch(b), b->d_feat, LPCN_NB_FEAT, d_pcm, T, 0, st);
 }
 extern "C" int lpcn_batch_dev_decode(lpcn_batch_dev *b, const unsigned char *d_packets, short *d_pcm, int n_packets, void *hip_stream)
 {
@@ -928,7 +952,7 @@ extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond
     if (rc) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
-    if (b->S_auto && !b->tuned && (rc = autotune_streams_per_wg(b, st))) return rc;
+    if ((rc = tune_if_due(b, st))) return rc;
     if (preload > 0) HIP_TRY(hipMemcpyAsync(b->d_pcm, pcm, npcm * sizeof(short), hipMemcpyHostToDevice, st));
     for (int f0 = 0; f0 < n_frames; f0 += b->max_chunk) {
         const int nf = n_frames - f0 < b->max_chunk ? n_frames - f0 : b->max_chunk;
@@ -940,7 +964,7 @@ extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond
         HIP_TRY(hipMemcpy2DAsync(b->d_lpc, (size_t)nf * LPCN_LPC_ORDER * 4, lpc + (size_t)f0 * LPCN_LPC_ORDER, (size_t)n_frames * LPCN_LPC_ORDER * 4,
                                  (size_t)nf * LPCN_LPC_ORDER * 4, b->n, hipMemcpyHostToDevice, st));
         if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
-        rc = launch_sample(b, st, b->d_pcm + (size_t)f0 * LPCN_FRAME_SIZE, (size_t)n_frames * LPCN_FRAME_SIZE, nf, preload, false);
+        rc = launch_sample(b, whole_batch(b), st, b->d_pcm + (size_t)f0 * LPCN_FRAME_SIZE, (size_t)n_frames * LPCN_FRAME_SIZE, nf, preload, false);
         if (rc) return rc;
         if (b->timing) {
             HIP_TRY(hipEventRecord(b->ev[2], st));
@@ -968,7 +992,7 @@ extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *fe
     HIP_TRY(hipMemcpyAsync(b->d_feat, features, nfeat * sizeof(float), hipMemcpyHostToDevice, st));
     for (int f0 = 0; f0 < n_frames; f0 += b->max_chunk) {
         const int nf = n_frames - f0 < b->max_chunk ? n_frames - f0 : b->max_chunk;
-        rc = launch_frames(b, st, b->d_feat + (size_t)f0 * feat_stride, feat_stride, (size_t)n_frames * feat_stride, nf);
+        rc = launch_frames(b, whole_batch(b), st, b->d_feat + (size_t)f0 * feat_stride, feat_stride, (size_t)n_frames * feat_stride, nf);
         if (rc) return rc;
         if (cond_a) HIP_TRY(hipMemcpy2DAsync(cond_a + (size_t)f0 * LPCN_ROWS_A, (size_t)n_frames * LPCN_ROWS_A * 4, b->d_cond_a, (size_t)nf * LPCN_ROWS_A * 4,
                                              (size_t)nf * LPCN_ROWS_A * 4, b->n, hipMemcpyDeviceToHost, st));
@@ -1031,7 +1055,7 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
     if (rc) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
-    if (b->S_auto && !b->tuned && (rc = autotune_streams_per_wg(b, st))) return rc;
+    if ((rc = tune_if_due(b, st))) return rc;
 #define ALX(ptr, bytes) if (!(ptr) && hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", (size_t)(bytes)); return LPCN_E_HIP; }
     ALX(b->d_state_tmp, sizeof(lpcn_stream_state) * b->n);
     ALX(b->d_map, sizeof(int) * b->n);
@@ -1048,13 +1072,10 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
     std::vector<int> map;
     std::vector<float> fc((size_t)b->n * LPCN_NB_FEAT);
     std::vector<short> pc((size_t)b->n * LPCN_FRAME_SIZE);
-    const int keep_n = b->n, keep_len = b->frame_len;
-    lpcn_stream_state *const keep_state = b->d_state;
-    auto restore = [&]() { b->n = keep_n; b->frame_len = keep_len; b->d_state = keep_state; };
-    for (int s0 = 0; s0 < keep_n; ++s0) {
+    for (int s0 = 0; s0 < b->n; ++s0) {
         if (done[s0] || mode[s0] == 0) continue;
         map.clear();
-        for (int s = s0; s < keep_n; ++s)
+        for (int s = s0; s < b->n; ++s)
             if (!done[s] && mode[s] == mode[s0] && n_samples[s] == n_samples[s0] && preload[s] == preload[s0]) { map.push_back(s); done[s] = 1; }
         const int cnt = (int)map.size(), N = n_samples[s0], pre = preload[s0], md = mode[s0];
         for (int i = 0; i < cnt; ++i) {
@@ -1064,10 +1085,10 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
         HIP_TRY(hipMemcpyAsync(b->d_map, map.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b->d_feat, fc.data(), sizeof(float) * (size_t)cnt * LPCN_NB_FEAT, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b->d_pcm, pc.data(), sizeof(short) * (size_t)cnt * LPCN_FRAME_SIZE, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)keep_state, (const int *)b->d_map, cnt, 0);
-        b->n = cnt; b->d_state = b->d_state_tmp; b->frame_len = N;
+        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, (const int *)b->d_map, cnt, 0);
+        const LaunchShape sh = {cnt, N, b->d_state_tmp, b->S, b->pack2};      // the compacted group, with the batch's streams per workgroup
         if (md == 1) {
-            rc = launch_frames(b, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
+            rc = launch_frames(b, sh, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
             if (!rc) {      // remember the products per stream (a later tail-only step of the stream uses them)
                 hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (const float *)b->d_cond_a, (const int *)b->d_map, cnt, LPCN_ROWS_A, 1);
                 hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (const float *)b->d_cond_b, (const int *)b->d_map, cnt, LPCN_ROWS_B, 1);
@@ -1078,10 +1099,9 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
             hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (const float *)b->d_keep_b, (const int *)b->d_map, cnt, LPCN_ROWS_B, 0);
             hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_lpc, (const float *)b->d_keep_lpc, (const int *)b->d_map, cnt, LPCN_LPC_ORDER, 0);
         }
-        if (!rc) rc = launch_sample(b, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, pre, md == 1);
-        restore();
+        if (!rc) rc = launch_sample(b, sh, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, pre, md == 1);
         if (rc) return rc;
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, keep_state, (const lpcn_stream_state *)b->d_state_tmp, (const int *)b->d_map, cnt, 1);
+        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, (const int *)b->d_map, cnt, 1);
         if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "per-stream step: kernel launch failed"); return LPCN_E_HIP; }
         HIP_TRY(hipMemcpyAsync(pc.data(), b->d_pcm, sizeof(short) * (size_t)cnt * LPCN_FRAME_SIZE, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

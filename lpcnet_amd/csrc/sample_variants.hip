@@ -2,7 +2,8 @@
 // items per lane (register-resident GRU-A variants) x blob flavour (fp32 / int8) x arithmetic (PARITY / FAST).
 // Split from engine.hip so that the three values build in parallel.
 #include "sample_kernel.hip.h"
-#include <mutex>
+#include "sample_launch.hip.h"
+#include "sample_variants.h"
 
 #ifndef LPCN_S
 #error "compile with -DLPCN_S=1, 2 or 4"
@@ -13,61 +14,39 @@
 template <int NW, bool I8, bool FAST, bool PACK2 = false>
 static int launch(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args)
 {
-    auto k = lpcn::sample_kernel<LPCN_S, NW, I8, FAST, PACK2>;
-    // the dynamic-LDS limit of a variant is raised once per (device, size), not at every launch
-    static std::mutex mu;
-    static int limit[64];                                    // per HIP device: the size already granted
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    {
-        std::lock_guard<std::mutex> g(mu);
-        if (dev < 0 || dev >= 64 || limit[dev] < lds) {
-            hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0 && dev < 64) limit[dev] = lds;
-        }
-    }
-    // (the arguments stay a device-resident block read through scalar loads: passing the struct by value was measured --
-    // 23 more spilled SGPRs, 105.6 vs 107.3 M samples/s on the float kernel, +1.7 % on the int8 one)
-    hipLaunchKernelGGL(k, dim3(grid), dim3(LPCN_WG_THREADS), lds, st, d_args);
-    return (int)hipGetLastError();
+    return lpcn_launch_sample_kernel<lpcn::sample_kernel<LPCN_S, NW, I8, FAST, PACK2>>(grid, lds, st, d_args);
 }
 
 template <bool FAST>
 static int pick(int nw, int is_int8, int pack2, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args)
 {
 #ifdef LPCN_ONLY_BENCH_VARIANT       // tools: compile only the benchmark model's PARITY float kernel (quick assembly listings)
-    if constexpr (FAST) return (int)hipErrorInvalidValue;
+    if constexpr (FAST) return LPCN_NO_SUCH_VARIANT;
 #if LPCN_ONLY_BENCH_VARIANT == 2     // ... the int8 one (32 items per lane, two workgroups per CU; build with -DLPCN_S=2)
-    else return (is_int8 && nw == 32 && pack2) ? launch<32, true, false, (LPCN_S <= 2)>(grid, lds, st, d_args) : (int)hipErrorInvalidValue;
+    else return (is_int8 && nw == 32 && pack2) ? launch<32, true, false, (LPCN_S <= 2)>(grid, lds, st, d_args) : LPCN_NO_SUCH_VARIANT;
 #else
-    else return (!is_int8 && nw == 30) ? launch<30, false, false>(grid, lds, st, d_args) : (int)hipErrorInvalidValue;
+    else return (!is_int8 && nw == 30) ? launch<30, false, false>(grid, lds, st, d_args) : LPCN_NO_SUCH_VARIANT;
 #endif
 #else
+    // one case per compiled items-per-lane variant (sample_variants.h); int8 at 32 items and S <= 2 also has the two-workgroups-per-CU form
+#define LPCN_CASE_I8(n) case n: return (pack2 && n == 32 && LPCN_S <= 2) ? launch<n, true, FAST, (n == 32 && LPCN_S <= 2)>(grid, lds, st, d_args) : launch<n, true, FAST>(grid, lds, st, d_args);
+#define LPCN_CASE_F32(n) case n: return launch<n, false, FAST>(grid, lds, st, d_args);
     if (is_int8) {
         switch (nw) {
-        case 32: return (pack2 && LPCN_S <= 2) ? launch<32, true, FAST, (LPCN_S <= 2)>(grid, lds, st, d_args) : launch<32, true, FAST>(grid, lds, st, d_args);
-        case 48: return launch<48, true, FAST>(grid, lds, st, d_args);
-        case 64: return launch<64, true, FAST>(grid, lds, st, d_args);
-        default: return launch<96, true, FAST>(grid, lds, st, d_args);      // (a row group may list every one of its 96 input blocks: trained, heavy-tailed sparsity)
+        LPCN_VARIANTS_I8(LPCN_CASE_I8)
+        default: return LPCN_NO_SUCH_VARIANT;
         }
     }
     switch (nw) {
-    case 24: return launch<24, false, FAST>(grid, lds, st, d_args);
-    case 28: return launch<28, false, FAST>(grid, lds, st, d_args);
-    case 30: return launch<30, false, FAST>(grid, lds, st, d_args);
-    case 32: return launch<32, false, FAST>(grid, lds, st, d_args);
-    case 36: return launch<36, false, FAST>(grid, lds, st, d_args);
-    case 40: return launch<40, false, FAST>(grid, lds, st, d_args);
-    case 48: return launch<48, false, FAST>(grid, lds, st, d_args);      // (more than 32 items per lane: the items past the 28th are streamed from L2, sample_kernel.hip.h)
-    case 64: return launch<64, false, FAST>(grid, lds, st, d_args);
-    case 80: return launch<80, false, FAST>(grid, lds, st, d_args);
-    default: return launch<96, false, FAST>(grid, lds, st, d_args);      // (a full row: every one of its 96 input blocks)
+    LPCN_VARIANTS_F32(LPCN_CASE_F32)
+    default: return LPCN_NO_SUCH_VARIANT;
     }
+#undef LPCN_CASE_I8
+#undef LPCN_CASE_F32
 #endif
 }
 
-// returns a hipError_t value (0 = launched)
+// returns a hipError_t value (0 = launched) or LPCN_NO_SUCH_VARIANT
 // flags: bit 0 = FAST arithmetic, bit 1 = PACK2 (two workgroups per CU; int8, 32 items per lane only)
 extern "C" int LPCN_CAT(lpcn_launch_sample_s, LPCN_S)(int nw, int is_int8, int flags, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args)
 {

@@ -250,21 +250,28 @@ def test_sharded_batch_in_c(blob_f32, golden, hip_lib):
     b.close(); one.close()
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(densities=(0.07, 0.07, 0.25)), dict(flavour="int8")], ids=["default", "denseA", "int8"])
-def test_streams_per_workgroup_is_measured_not_looked_up(kw, hip_lib):
+@pytest.mark.parametrize("kw,n", [(dict(), 1024), (dict(densities=(0.07, 0.07, 0.25)), 1024), (dict(flavour="int8"), 1024), (dict(), 2560)],
+                         ids=["default", "denseA", "int8", "default2560"])
+def test_streams_per_workgroup_is_measured_not_looked_up(kw, n, hip_lib):
     """the streams-per-workgroup choice must come from THIS model (a denser GRU-A runs another item-count
-    variant with other step times): the engine times S = 1, 2, 4 on the batch itself before its first run.  The chosen
-    value has to be (within noise) the fastest of the three when each is pinned, the states must be untouched by the
-    measurement (bit-exact output afterwards), and a pinned value must stay pinned."""
+    variant with other step times): the engine times S = 1, 2, 4 (8) on the batch itself before its first run.  The chosen
+    value has to be (within noise) the fastest when each is pinned, the states must be untouched by the
+    measurement (bit-exact output afterwards), and a pinned value must stay pinned.  The call that measures runs on the
+    measured value itself, not on the table's (a one-shot user never makes a second call): its kernel time is a pinned batch's at
+    the chosen value -- and where the table says otherwise (2560 float streams: 320 workgroups of eight against 640 of four, two rounds
+    against three, which the table's step times put the other way round than this GPU) nearer to that than to the table's."""
     blob = synth.blob_bytes(synth.make_model(**kw))
-    n, T = 1024, 6
+    T = 6
     feats = distinct_feats(95000, n, T)
     auto = api.LPCNetBatch(n, blob)
+    table = auto.streams_per_workgroup                       # (before the first run: the table's value)
+    auto.enable_timing(True)
     pcm_auto = auto.synthesize(feats)
+    t_first = auto.last_timing()[0]
     chosen = auto.streams_per_workgroup
     auto.close()
     times = {}
-    for S in (1, 2, 4):
+    for S in sorted({1, 2, 4, table, chosen}):
         b = api.LPCNetBatch(n, blob)
         b.streams_per_workgroup = S
         b.enable_timing(True)
@@ -281,7 +288,11 @@ def test_streams_per_workgroup_is_measured_not_looked_up(kw, hip_lib):
             assert np.array_equal(out, pcm_auto)             # the auto-tuned batch produced exactly what a pinned one does
         b.close()
     assert times[chosen] <= 1.15 * min(times.values()), (chosen, times)      # (a perf sanity bound, deliberately loose; the bit-exactness asserts are the gate)
-    pick = [0, 257, 1023]
+    assert t_first <= 1.25 * times[chosen], (table, chosen, t_first, times)      # (one timing against the best of three)
+    if times[table] > 1.05 * times[chosen]:                  # (the table's kernel is measurably another one)
+        assert abs(t_first - times[chosen]) < abs(t_first - times[table]), (table, chosen, t_first, times)
+    print("streams per workgroup: table %d, measured %d; first call %.3f ms; pinned %s" % (table, chosen, t_first, times))
+    pick = [0, 257, n - 1]
     want = orc.synthesize_many(blob, feats[pick])
     assert first_mismatch(pcm_auto[pick], want) is None
 

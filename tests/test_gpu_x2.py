@@ -179,7 +179,7 @@ def test_other_models_on_the_two_group_kernel(kw, hip_lib):
 
 def test_models_the_two_group_kernel_cannot_run_are_refused_or_fall_back(blob_i8, hip_lib):
     """int8 blobs, block-sparse GRU-B and FAST arithmetic keep four (or fewer) streams per workgroup: asking for eight is an error, and a pinned
-    eight falls back when the arithmetic flavour changes under it"""
+    eight falls back while the arithmetic flavour under it is FAST, and only then"""
     b = api.LPCNetBatch(8, blob_i8)
     with pytest.raises(api.LPCNetError):
         b.streams_per_workgroup = 8
@@ -196,9 +196,11 @@ def test_models_the_two_group_kernel_cannot_run_are_refused_or_fall_back(blob_i8
     want = b.synthesize(feats)
     b.reset()
     b.set_fast(True)                                        # FAST has no two-group kernel: the launch falls back to four streams per workgroup
+    assert b.streams_per_workgroup == 4
     fast = b.synthesize(feats)
     assert fast.shape == want.shape and np.any(fast != 0)
-    b.set_fast(False)
+    b.set_fast(False)                                       # ... and the pinned eight is back with PARITY
+    assert b.streams_per_workgroup == 8
     b.reset()
     assert np.array_equal(b.synthesize(feats), want)
     b.close()
