@@ -108,24 +108,9 @@ struct LpcnSampleArgs {
 #endif
 #define LPCN_DBG_STRIDE 1600    // floats per (sample) trace record: hA 384, hB 16, exc,sig,pred,pcm,pred, leader clocks barrier->publish, the tree's own decision; [448..1600) GRU-A pre-activations
 
+#include "sample_common.hip.h"
+
 namespace lpcn {
-
-constexpr int NA = LPCN_N_A, NB = LPCN_N_B, RA = LPCN_ROWS_A, RB = LPCN_ROWS_B;
-
-// pointers fetched from the argument block are generic; tell the compiler they are global memory
-#define LPCN_GLOBAL __attribute__((address_space(1)))
-template <typename T> __device__ __forceinline__ const LPCN_GLOBAL T *as_global(const T *p)
-{
-    return (const LPCN_GLOBAL T *)(uintptr_t)p;
-}
-template <typename T> __device__ __forceinline__ LPCN_GLOBAL T *as_global_rw(T *p)
-{
-    return (LPCN_GLOBAL T *)(uintptr_t)p;
-}
-// Loop-invariant values that hipcc would otherwise hoist out of the 160-sample loop and keep in
-// VGPRs for the whole launch; the weights need that register space.
-#define LPCN_REMAT_V(x) asm volatile("" : "+v"(x))
-#define LPCN_REMAT_S(x) asm volatile("" : "+s"(x))
 
 // ---- LDS carve-up (bytes), all offsets multiples of 16 ---------------------------------------
 #define LPCN_PROD_BLOCKS 48      // single stream per workgroup: blocks of GRU-B whose products the helper waves form (the two assembly loops are generated for this split)
@@ -240,17 +225,6 @@ template <> struct XVec<1> { typedef int type; };
 template <> struct XVec<2> { typedef int type __attribute__((ext_vector_type(2))); };
 template <> struct XVec<4> { typedef int type __attribute__((ext_vector_type(4))); };
 
-// value of lane J of the caller's 16-lane row (DPP row_newbcast); the compiler folds it into the consuming VALU op
-template <int J> __device__ __forceinline__ float row_bcast(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + J, 0xf, 0xf, false));
-}
-template <int J> __device__ __forceinline__ float lpc_chain(float r, float prod)
-{
-    if constexpr (J < LPCN_LPC_ORDER) return lpc_chain<J + 1>(r - row_bcast<J>(prod), prod);
-    else return r;
-}
-
 // PACK2 variants: the register allocation leaves room for 4 waves per SIMD (128 VGPRs per lane), i.e. TWO workgroups per
 // CU, which fill each other's barrier / latency bubbles (measured: a second resident workgroup slows the first by only
 // ~15 %).  Only the int8 kernels with <= 32 items per lane and S <= 2 get there without a scratch access inside the
@@ -326,6 +300,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
     const unsigned char *const sm_bblk = smem + L::bblk;
     const unsigned short *const sm_boff = (const unsigned short *)(smem + L::boff);
     const float *const sm_bw = (const float *)(smem + L::bw);
+    const LeaderCells cells = {sm_lead, sm_idx, sm_thr, sm_pcm};      // the leader's cells (sample_common.hip.h)
 
     const int tid0 = threadIdx.x;
     const int n_streams = Ap->n_streams, n_frames = Ap->n_frames, preload = Ap->preload, frame_len = Ap->frame_len;
@@ -441,21 +416,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
     {
         const int tid = tid0;
         const int nb_b = Ap->nb_b;
-        const auto *t0 = as_global(Ap->tab_tansig), *t1 = as_global(Ap->tab_ulaw2lin), *t2 = as_global(Ap->tab_logit);
-        for (int i = tid; i < 201; i += LPCN_WG_THREADS) ((float *)(smem + L::tansig))[i] = t0[i];
-        for (int i = tid; i < 256; i += LPCN_WG_THREADS) {
-            ((float *)(smem + L::ulaw))[i] = t1[i];
-            ((float *)(smem + L::logit))[i] = t2[i];
-        }
-        const auto *ab1 = as_global(Ap->a_bias1), *adg = as_global(Ap->a_diag);
-        for (int i = tid; i < RA; i += LPCN_WG_THREADS) {
-            ((float *)(smem + L::abias))[2 * i] = ab1[i];          // [row]{bias, diag}: one 8-byte read per row
-            ((float *)(smem + L::abias))[2 * i + 1] = adg[i];
-        }
-        const auto *br = as_global(Ap->b_rec), *bb = as_global(Ap->b_bias);
-        for (int i = tid; i < (I8 ? RB * 4 : NB * RB); i += LPCN_WG_THREADS) ((uint32_t *)(smem + L::brec))[i] = ((const LPCN_GLOBAL uint32_t *)br)[i];   // bit copy (dwords of 4 int8 for I8)
-        for (int i = tid; i < 2 * RB; i += LPCN_WG_THREADS) ((float *)(smem + L::bbias))[i] = bb[i];
-        if (tid < 7) ((int *)(smem + L::bstart))[tid] = as_global(Ap->b_start)[tid];
+        stage_tables<L>(smem, Ap, tid, I8 ? RB * 4 : NB * RB);
         const auto *bk = as_global(Ap->b_blk);
         for (int i = tid; i < 608; i += LPCN_WG_THREADS) {
             const int pblk = i < nb_b ? bk[i] : 0;
@@ -464,6 +425,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
         }
         const auto *bw = as_global(Ap->b_w);
         constexpr int BW_DW = I8 ? 8 : 32;                  // dwords per GRU-B block
+        if constexpr (!FAST && !I8) stage_grub_weights(smem + L::bw, Ap, tid, gb_lds);
+        else
         for (int i = tid; i < (nb_b + (I8 ? 28 : 8)) * BW_DW; i += LPCN_WG_THREADS) {
             int di = i;
             if constexpr (FAST && !I8 && S >= 2) {
@@ -475,20 +438,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                 }
             }
             if constexpr (I8) {
-                // (int8 blobs, dense matrix: a row group is 24 quads of 4 blocks = 3 072 B -- the same bank phase for all six; same cure)
+                // (int8 blobs, dense matrix: a row group is 24 quads of 4 blocks = 3 072 B -- the same bank phase for all six; the cure of stage_grub_weights)
                 if (b_dense) {
-                    if (i < nb_b * BW_DW) di = i + ((0x321100 >> (4 * ((i >> 5) / 24))) & 15) * 32;
+                    if (i < nb_b * BW_DW) di = i + ((LPCN_GRUB_SHIFT >> (4 * ((i >> 5) / 24))) & 15) * 32;
                     else if (i < (nb_b + 4) * BW_DW) di = i + 3 * 32;
-                    else continue;
-                }
-            }
-            if constexpr (!FAST && !I8) {
-                // gb_lds: a wave's weight read fetches 16 B per row from six row groups 12 288 B apart -- the same 32 banks for
-                // every group, a two-way conflict inside each 16-lane service group of ds_read_b128.  Row groups 2, 3 and 5 are
-                // shifted by one more block (128 B = the other half of the banks); the pad blocks behind the matrix absorb it.
-                if (gb_lds) {
-                    if (i < nb_b * BW_DW) di = i + ((0x321100 >> (4 * ((i >> 5) / 96))) & 15) * 32;
-                    else if (i < (nb_b + 5) * BW_DW) di = i + 3 * 32;     // zero blocks behind the shifted last group
                     else continue;
                 }
             }
@@ -513,15 +466,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
             if constexpr (FAST) ((_Float16 *)(smem + L::hBh(Ap->nb_b, I8)))[i] = (_Float16)hv0;
         }
         // leader-lane state (lane s of wave 0 leads stream s); kept in LDS between samples
-        if (tid < S) {
-            const auto *st = &states[stream_of(tid)];
-            sm_idx[tid] = 0;
-            sm_lead[tid * 8 + 0] = 0.f;                                       // pred
-            sm_lead[tid * 8 + 1] = st->deemph_mem;
-            ((int *)sm_lead)[tid * 8 + 2] = st->last_exc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ((uint32_t *)sm_lead)[tid * 8 + 4 + j] = st->rng[j];
-        }
+        if (tid < S) stage_leader_record(cells, tid, &states[stream_of(tid)]);
     }
     __syncthreads();
 
@@ -531,47 +476,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
     //  * wave 1, lane s: the two KISS99 words that become the 8 tree thresholds (src/nnet.c:178-184).
     // LPC predictor state of wave 0: lane 16*s + j holds sample j of stream s's history (j = 0 newest,
     // src/lpcnet.c:252-263) and, per frame, LPC coefficient j.
-    // (lrow/tap are recomputed from the thread id and the coefficient re-read from LDS where needed: every
-    // VGPR that stays live across the GRU-A item loop costs the fp32 engine a spill)
+    // (open_sample, draw_thresholds, draw_sample, finish_sample: sample_common.hip.h)
 #define LPCN_LROW ((tid0 & 63) >> 4)
 #define LPCN_TAP (tid0 & 15)
     float hist = (tid0 < 16 * S) ? states[stream_of(LPCN_LROW)].last_sig[LPCN_TAP] : 0.f;
-    auto row_shr1 = [](float v, float fill) {               // value of the previous lane of the 16-lane row; lane 0 gets `fill`
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-    };
-    // `prod` = this lane's term s_j*a_j of the prediction (tap j); `per_frame`: also (re)write the stream's live flag
-    auto open_sample = [&](const bool live, const float newest, const float prod, const int exc, const bool per_frame) {   // wave 0, lanes < 16*S
-        int t_ = tid0;
-        LPCN_REMAT_V(t_);
-        const int lrow = (t_ & 63) >> 4, tap = t_ & 15;
-        // pred = ((0 - s0*a0) - s1*a1) - ... in tap order (src/lpcnet.c:252): every lane of the row runs the whole chain,
-        // taking product j from lane j of its row through a DPP row broadcast folded into the subtract -- the
-        // broadcast operand does not depend on the chain, so the 16 steps cost only the add latency
-        const float r = lpc_chain<0>(0.f, prod);
-        // mu-law index of the newest sample (even taps) and of the prediction (odd taps) in one pass; tap 0 collects both
-        const int u = lpcn_lin2ulaw((tap & 1) ? r : newest);
-        const int u_pred = __builtin_amdgcn_mov_dpp(u, 0xB1, 0xf, 0xf, true);      // neighbour lane (quad_perm [1,0,3,2])
-        if (tap == 0) {
-            if (live) {
-                sm_lead[lrow * 8 + 0] = r;
-                sm_idx[lrow] = u | (u_pred << 8) | (exc << 16);     // (sig, pred, exc) indices packed into one word per stream
-            } else {
-                sm_idx[lrow] = 0;
-            }
-            if (per_frame) sm_idx[S + lrow] = live ? 1 : 0;
-        }
-    };
-    auto draw_thresholds = [&](const int ls) {
-        int *li = (int *)sm_lead + ls * 8;
-        uint32_t rng[4] = {(uint32_t)li[4], (uint32_t)li[5], (uint32_t)li[6], (uint32_t)li[7]};
-        const uint32_t r0 = lpcn_kiss99(rng), r1 = lpcn_kiss99(rng);
-        li[4] = (int)rng[0]; li[5] = (int)rng[1]; li[6] = (int)rng[2]; li[7] = (int)rng[3];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            sm_thr[ls * 8 + b] = sm_logit[(r0 >> (8 * b)) & 0xFF];
-            sm_thr[ls * 8 + 4 + b] = sm_logit[(r1 >> (8 * b)) & 0xFF];
-        }
-    };
     // The sample loop has no barrier between the leader's work and the next sample's GRU-A: the
     // other waves run ahead into the rows that need no gathered input and pick the new indices
     // up through this flag (LDS operations of one wave complete in order).
@@ -581,62 +489,16 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
     // once the gate stage is done, and they make up most of GRU-A's blocks.  (model_pack.c puts the
     // candidate-only slot of waves 4..7 last, so the rest of the sample simply ends at item bound[2].)
     bool head_ready = false;                                 // wave-uniform: the parked partial sums belong to the sample about to start
-    const uint32_t flag_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)(smem + L::flag);
-    auto publish_indices = [&]() {                           // after the sm_idx writes of the same lane
-        asm volatile("ds_write_b32 %0, %1" :: "v"(flag_addr), "v"(seq) : "memory");
-    };
-    auto wait_indices = [&]() {
-        int v;
-        do {
-            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(flag_addr) : "memory");
-            v = __builtin_amdgcn_readfirstlane(v);
-            if (v != seq) __builtin_amdgcn_s_sleep(1);
-        } while (v != seq);
-    };
+    const uint32_t flag_addr = lds_addr(smem + L::flag);
+    auto wait_indices = [&]() { lds_poll_until<true>(flag_addr, seq); };      // (a binding, not two direct calls: with no by-reference use of seq left, sample_kernel<4,30,0,0> spills one more SGPR)
     // Arrival counter in LDS for hand-offs without a workgroup barrier (FAST float GRU-B on the matrix pipe: every wave bumps it behind its LDS stores -- a wave's
     // LDS operations complete in order -- and only the gate waves wait for all eight)
     int gbseq = 0;                                           // samples handed off so far (identical in every wave)
     const uint32_t arrive_addr = flag_addr + 4;
-    auto lds_arrive = [&]() {                                 // the same counter for hand-offs through LDS: no store round trip to wait for
-        int one = 1;
-        unsigned long long ex;
-        asm volatile("s_mov_b64 %0, exec\n\t"
-                     "s_mov_b64 exec, 1\n\t"
-                     "ds_add_u32 %1, %2\n\t"
-                     "s_mov_b64 exec, %0"
-                     : "=&s"(ex) : "v"(arrive_addr), "v"(one) : "memory");
-    };
-    auto mirror_wait = [&]() {
-        int v;
-        const int want = gbseq * LPCN_WAVES;
-        do {
-            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(arrive_addr) : "memory");
-            v = __builtin_amdgcn_readfirstlane(v);
-            if (v != want) __builtin_amdgcn_s_sleep(1);
-        } while (v != want);
-    };
     // products hand-off (gb_prod): the three producer waves bump a second counter once their blocks are written (a wave's LDS
     // instructions complete in order: the add is behind the stores)
     int prseq = 0;
     const uint32_t prod_cnt_addr = flag_addr + 8;
-    auto prod_arrive = [&]() {
-        int one = 1;
-        unsigned long long ex;
-        asm volatile("s_mov_b64 %0, exec\n\t"
-                     "s_mov_b64 exec, 1\n\t"
-                     "ds_add_u32 %1, %2\n\t"
-                     "s_mov_b64 exec, %0"
-                     : "=&s"(ex) : "v"(prod_cnt_addr), "v"(one) : "memory");
-    };
-    auto prod_wait = [&]() {
-        int v;
-        const int want = prseq * 3;                          // (producers: waves 1..3 of a single-stream workgroup)
-        do {
-            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(prod_cnt_addr) : "memory");
-            v = __builtin_amdgcn_readfirstlane(v);
-            if (v != want) __builtin_amdgcn_s_sleep(1);
-        } while (v != want);
-    };
     if (tid0 == 0) { *(int *)(smem + L::flag) = 0; *(int *)(smem + L::flag + 4) = 0; *(int *)(smem + L::flag + 8) = 0; }
 
 #if LPCN_ENABLE_PROF      // per-phase shader-clock accounting (profiling builds only: it costs VGPRs)
@@ -666,10 +528,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                 sm_lpc[tid] = lp[((size_t)stream_of(tid / LPCN_LPC_ORDER) * nf + f) * LPCN_LPC_ORDER + tid % LPCN_LPC_ORDER];
             if (tid < 16 * S || (tid >= 64 && tid < 64 + S)) {    // wave 0: predictor lanes; wave 1: threshold lanes
                 const int lstream = stream_of(tid < 64 ? LPCN_LROW : tid - 64);
-                const int fc_ref = Ap->fc_base ? as_global(Ap->fc_base)[lstream] : states[lstream].frame_count;
-                int fc = Ap->fc_advance ? fc_ref + f + 1 : fc_ref;
-                if (fc > 1000) fc = 1000;
-                live = fc > LPCN_FEATURES_DELAY;                 // src/lpcnet.c:239-243
+                live = stream_is_live(Ap, states, lstream, f);
             }
             if (preload > 0 && tid < S) {                         // teacher forcing reads the caller's samples
                 const auto *pin = as_global(Ap->pcm) + (size_t)stream_of(tid) * (size_t)Ap->pcm_stride + (size_t)f * LPCN_FRAME_SIZE;
@@ -679,10 +538,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
         __syncthreads();        // sm_lpc visible to the leaders
         ++seq;
         if (tid0 < 16 * S) {
-            open_sample(live, hist, hist * sm_lpc[tid0], ((const int *)sm_lead)[LPCN_LROW * 8 + 2], true);   // sm_lpc is [stream][16] = [lane] for wave 0
-            publish_indices();
+            open_sample<S>(cells, tid0, live, hist, hist * sm_lpc[tid0], ((const int *)sm_lead)[LPCN_LROW * 8 + 2], true);   // sm_lpc is [stream][16] = [lane] for wave 0
+            lds_publish(flag_addr, seq);
         }
-        if (tid0 >= 64 && tid0 < 64 + S && live) draw_thresholds(tid0 - 64);
+        if (tid0 >= 64 && tid0 < 64 + S && live) draw_thresholds(cells, sm_logit, tid0 - 64);
         __syncthreads();
         int live_mask = 0;                                   // bit s: stream s produces samples in this frame
 #pragma unroll
@@ -1297,7 +1156,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                             }
                         }
                     }
-                    lds_arrive();
+                    lds_arrive(arrive_addr);
                 }
             }
             const bool gb_fsplit = FAST && !I8 && b_dense && S <= LPCN_WAVES / 2 && !gb_mfma;
@@ -1478,7 +1337,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                 } else if (gb_mfma) {
 #pragma unroll
                     for (int j = 0; j < NB; ++j) rec = __builtin_fmaf(sm_brec[j * RB + r], sm_hB[s * NB + j], rec);
-                    mirror_wait();                           // all eight waves' partial sums are in LDS
+                    lds_poll_until<true>(arrive_addr, gbseq * LPCN_WAVES);   // all eight waves' partial sums are in LDS
                     const float4 pa = *(const float4 *)(sm_inh + (r * S + s) * 4);
                     zrh = zrh + ((pa.x + pa.y) + (pa.z + pa.w));
                     (void)g; (void)ri;
@@ -1506,7 +1365,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                         asm volatile(
 #include "grub_lds_loop_s1_first.inc"
                             : [z] "+v"(zrh), [wp] "+v"(wp32), [hp] "+v"(hp32) : : LPCN_GRUB_LDS32_CLOBBERS);
-                        prod_wait();
+                        lds_poll_until<true>(prod_cnt_addr, prseq * 3);          // (producers: waves 1..3 of a single-stream workgroup)
                         uint32_t pp32 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)(smem + L::prod(Ap->nb_b, I8) + r * 16);
                         asm volatile(
 #include "grub_prod_loop.inc"
@@ -1601,7 +1460,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                prod_arrive();
+                lds_arrive(prod_cnt_addr);
             } else if (early_wave) {
                 // ---- the head of the next sample's candidate chains (runs in the shadow of GRU-B)
                 run_head();
@@ -1745,83 +1604,32 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, PACK2 ? 4 : 2) void sample_kernel(
             if (tid < 64) __builtin_amdgcn_s_setprio(3);
             if (tid < 16 * S) {
                 const int lrow = (tid & 63) >> 4, tap = tid & 15;
-                // (tried in round 5: the walk by the row's 16 lanes in two dependent steps -- lane c tests the c-th root-to-leaf path of a 4-level
-                // subtree, a ballot names the lane that matched -- a third of the dependent depth, bit-exact, and slower: fp32 123.1 vs 126.3 M,
-                // int8 164.1 vs 170.4 M.  And for int8 blobs at two streams per workgroup: levels 0..6 only with one stream per lane, the last level
+                // (tried in round 5, int8 blobs at two streams per workgroup: levels 0..6 of the tree only with one stream per lane, the last level
                 // evaluated here from an LDS table -- +4.5 % with the tree phase halved, -0.4 % once this wave pays for the extra level)
-                auto walk_tree = [&](int lrow) {             // the sampler's 8 decisions from the 255 ballot bits of stream row lrow
-                    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-                    const u4 *mk = (const u4 *)(sm_mask + lrow * 8);
-                    const u4 qa = mk[0], qb = mk[1], qc = mk[2], qd = mk[3];
-                    auto bit_of = [](unsigned word, int k) { return (int)((word >> (2 * k)) & 1u); };
-                    int val = 0;
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) val = (val << 1) | bit_of(qa[0], (1 << b) | val);        // nodes 1..15
-                    val = (val << 1) | bit_of(qa[1], val);                                               // nodes 16..31
-                    val = (val << 1) | bit_of((val & 16) ? qa[3] : qa[2], val & 15);                     // nodes 32..63
-                    {
-                        const int k = val >> 4;                                                          // nodes 64..127: dwords 4..7
-                        const unsigned lo = (k & 1) ? qb[1] : qb[0], hi = (k & 1) ? qb[3] : qb[2];
-                        val = (val << 1) | bit_of((k & 2) ? hi : lo, val & 15);
-                    }
-                    {
-                        const int k = val >> 4;                                                          // nodes 128..255: dwords 8..15
-                        const unsigned a0 = (k & 1) ? qc[1] : qc[0], a1 = (k & 1) ? qc[3] : qc[2];
-                        const unsigned a2 = (k & 1) ? qd[1] : qd[0], a3 = (k & 1) ? qd[3] : qd[2];
-                        const unsigned b0 = (k & 2) ? a1 : a0, b1 = (k & 2) ? a3 : a2;
-                        val = (val << 1) | bit_of((k & 4) ? b1 : b0, val & 15);
-                    }
-                    return val;
-                };
-                float pcm = 0.f, deemph = 0.f;
-                int exc = 0;                   // (tree_val: the tree's own decision -- teacher forcing overrides exc)
-                if (live) {                                  // (all 16 lanes of a stream's row do the same walk)
-                    const float pred = sm_lead[lrow * 8 + 0];           // (issued together with the mask reads)
-                    deemph = sm_lead[lrow * 8 + 1];
-                    const int val = walk_tree(lrow);
-                    exc = val;
-                    if (smp < preload) {                                        // src/lpcnet.c:256-258
-                        const float x = (float)sm_pcm[lrow * LPCN_FRAME_SIZE + smp];
-                        exc = lpcn_lin2ulaw(x - 0.85f * deemph - pred);
-                        pcm = x - 0.85f * deemph;
-                    } else {
-                        pcm = pred + sm_ulaw[exc];                              // src/lpcnet.c:260
-                    }
-                }
-                {                                            // history shifts by one, the new sample enters at tap 0 (src/lpcnet.c:262-263)
-                    const float shifted = row_shr1(hist, pcm);
-                    hist = live ? shifted : hist;
-                }
-                if (tap == 0 && live) ((int *)sm_lead)[lrow * 8 + 2] = exc;
+                float pcm, deemph;
+                int exc;                       // (teacher forcing overrides the tree's own decision)
+                draw_sample(cells, sm_mask + lrow * 8, sm_ulaw, lrow, tap, live, smp, preload, hist, pcm, deemph, exc);
                 if (tracing_lane0(live)) {
                     LPCN_GLOBAL float *d = as_global_rw(Ap->dbg) + ((size_t)f * LPCN_FRAME_SIZE + smp) * LPCN_DBG_STRIDE + 400;
                     d[1] = (float)(sm_idx[0] & 0xFF); d[2] = (float)((sm_idx[0] >> 8) & 0xFF);
                 }
                 // the next sample's indices first: the other waves are waiting for them
-                if (more) { open_sample(live, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); publish_indices(); }
+                if (more) { open_sample<S>(cells, tid0, live, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); lds_publish(flag_addr, seq); }
                 __builtin_amdgcn_s_setprio(0);
                 if (tracing_lane0(live))
                     as_global_rw(Ap->dbg)[((size_t)f * LPCN_FRAME_SIZE + smp) * LPCN_DBG_STRIDE + 405] = (float)(unsigned)(__builtin_amdgcn_s_memtime() - t_b4);
-                if (tap == 0) {
-                    if (live) {
-                        if (tracing_lane0(true)) {
-                            LPCN_GLOBAL float *d = as_global_rw(Ap->dbg) + ((size_t)f * LPCN_FRAME_SIZE + smp) * LPCN_DBG_STRIDE + 400;
-                            d[0] = (float)exc; d[3] = pcm + 0.85f * deemph; d[4] = pcm - sm_ulaw[exc];
-                            // the tree's own decision (teacher forcing overrides exc) is walked AGAIN here, in the cold trace branch:
-                            // any use of the leader's value this far down (a register, an extra LDS store) cost 17 spilled
-                            // SGPRs in the sample loop and 2.3 % of the float kernel
-                            asm volatile("" ::: "memory");
-                            d[6] = (float)walk_tree(lrow);
-                        }
-                        pcm = pcm + 0.85f * deemph;
-                        sm_lead[lrow * 8 + 1] = pcm;                            // de-emphasis memory
-                        if (smp >= preload) sm_pcm[lrow * LPCN_FRAME_SIZE + smp] = (short)lpcn_round_pcm(pcm);
-                    } else {
-                        sm_pcm[lrow * LPCN_FRAME_SIZE + smp] = 0;
-                    }
+                if (tracing_lane0(live)) {                   // (thread 0 is tap 0 of stream 0)
+                    LPCN_GLOBAL float *d = as_global_rw(Ap->dbg) + ((size_t)f * LPCN_FRAME_SIZE + smp) * LPCN_DBG_STRIDE + 400;
+                    d[0] = (float)exc; d[3] = pcm + 0.85f * deemph; d[4] = pcm - sm_ulaw[exc];
+                    // the tree's own decision (teacher forcing overrides exc) is walked AGAIN here, in the cold trace branch:
+                    // any use of the leader's value this far down (a register, an extra LDS store) cost 17 spilled
+                    // SGPRs in the sample loop and 2.3 % of the float kernel
+                    asm volatile("" ::: "memory");
+                    d[6] = (float)tree_walk(sm_mask + lrow * 8);
                 }
+                finish_sample(cells, lrow, tap, live, smp, preload, pcm, deemph);
             }
-            if (more && tid >= 64 && tid < 64 + S && live) draw_thresholds(tid - 64);
+            if (more && tid >= 64 && tid < 64 + S && live) draw_thresholds(cells, sm_logit, tid - 64);
             if (tracing) {
                 LPCN_GLOBAL float *d = as_global_rw(Ap->dbg) + ((size_t)f * LPCN_FRAME_SIZE + smp) * LPCN_DBG_STRIDE;
                 if (tid < NA) d[tid] = sm_hT[tid * S];

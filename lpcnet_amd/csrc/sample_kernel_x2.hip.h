@@ -135,31 +135,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     // ------------------------------------------------------------------ LDS residents -------
     {
         const int tid = tid0;
-        const int nb_b = Ap->nb_b;
-        const auto *t0 = as_global(Ap->tab_tansig), *t1 = as_global(Ap->tab_ulaw2lin), *t2 = as_global(Ap->tab_logit);
-        for (int i = tid; i < 201; i += LPCN_WG_THREADS) ((float *)(smem + L::tansig))[i] = t0[i];
-        for (int i = tid; i < 256; i += LPCN_WG_THREADS) {
-            ((float *)(smem + L::ulaw))[i] = t1[i];
-            ((float *)(smem + L::logit))[i] = t2[i];
-        }
-        const auto *ab1 = as_global(Ap->a_bias1), *adg = as_global(Ap->a_diag);
-        for (int i = tid; i < RA; i += LPCN_WG_THREADS) {
-            ((float *)(smem + L::abias))[2 * i] = ab1[i];
-            ((float *)(smem + L::abias))[2 * i + 1] = adg[i];
-        }
-        const auto *br = as_global(Ap->b_rec), *bb = as_global(Ap->b_bias);
-        for (int i = tid; i < NB * RB; i += LPCN_WG_THREADS) ((float *)(smem + L::brec))[i] = br[i];
-        for (int i = tid; i < 2 * RB; i += LPCN_WG_THREADS) ((float *)(smem + L::bbias))[i] = bb[i];
-        if (tid < 7) ((int *)(smem + L::bstart))[tid] = as_global(Ap->b_start)[tid];
-        const auto *bwg = as_global(Ap->b_w);
-        // (row groups 2, 3 and 5 shifted by one more block: the six groups' rows then cover both halves of the banks -- see sample_kernel.hip.h)
-        for (int i = tid; i < (nb_b + 8) * 32; i += LPCN_WG_THREADS) {
-            int di;
-            if (i < nb_b * 32) di = i + ((0x321100 >> (4 * ((i >> 5) / 96))) & 15) * 32;
-            else if (i < (nb_b + 5) * 32) di = i + 3 * 32;
-            else continue;
-            ((uint32_t *)(smem + L::bw))[di] = i < nb_b * 32 ? ((const LPCN_GLOBAL uint32_t *)bwg)[i] : 0u;
-        }
+        stage_tables<L>(smem, Ap, tid, NB * RB);
+        stage_grub_weights(smem + L::bw, Ap, tid, true);
         for (int i = tid; i < 2 * S * NA; i += LPCN_WG_THREADS) {
             const int gs = i / NA, n = i % NA, g = gs >> 2, s = gs & 3;
             const float hv0 = states[stream_of(gs)].gru_a[n];
@@ -173,15 +150,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         }
         if (tid < 2 * S) {
             const int g = tid >> 2, s = tid & 3;
-            const auto *st = &states[stream_of(tid)];
             unsigned char *gb = smem + g * L::G_SZ;
-            ((int *)(gb + L::g_idx))[s] = 0;
-            float *ld = (float *)(gb + L::g_lead);
-            ld[s * 8 + 0] = 0.f;
-            ld[s * 8 + 1] = st->deemph_mem;
-            ((int *)ld)[s * 8 + 2] = st->last_exc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ((uint32_t *)ld)[s * 8 + 4 + j] = st->rng[j];
+            stage_leader_record({(float *)(gb + L::g_lead), (int *)(gb + L::g_idx), nullptr, nullptr}, s, &states[stream_of(tid)]);
         }
         if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; fl[2] = 0; }
     }
@@ -202,10 +172,6 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     int chnP = 0, chnQ = 0;                                  // GRU-B phases run so far, per group
     int smpP = 0, smpQ = 0, fP = 0, fQ = 0;                  // position of the group's NEXT P1 sample: sample within the frame, frame
     float lpc_tap = 0.f, prod_old = 0.f;                     // leader lanes: computed behind the tree of a group, used when its sample is finished
-    auto row_shr1 = [](float v, float fill) __attribute__((always_inline)) {               // value of the previous lane of the 16-lane row; lane 0 gets `fill`
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, false));
-    };
-    auto lds_addr = [](const void *ptr) __attribute__((always_inline)) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)(unsigned char *)ptr; };
 
     const int T = n_frames * frame_len;                      // samples per stream in this launch
 #if LPCN_ENABLE_PROF
@@ -236,42 +202,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         float *const hT_p = (float *)(gp + L::g_hT);
         float *const hB_q = (float *)(gq + L::g_hB);
         int *const idx_p = (int *)(gp + L::g_idx);
-        float *const lead_p = (float *)(gp + L::g_lead);
-        float *const thr_p = (float *)(gp + L::g_thr);
         float *const lpc_p = (float *)(gp + L::g_lpc);
         short *const pcm_p = (short *)(gp + L::g_pcm);
+        const LeaderCells cells_p = {(float *)(gp + L::g_lead), idx_p, (float *)(gp + L::g_thr), pcm_p};      // group P's leader cells (sample_common.hip.h)
         const uint32_t flag_p = lds_addr(gp + L::g_flag);
-
-        // prediction + mu-law indices of group P's next sample (wave LW; src/lpcnet.c:252-254), published through idx_p + flag_p
-        auto open_sample = [&](const bool live, const float newest, const float prod, const int exc, const bool per_frame) __attribute__((always_inline)) {
-            int t_ = tid0;
-            LPCN_REMAT_V(t_);
-            const int lrow = (t_ & 63) >> 4, tap = t_ & 15;
-            const float r = lpc_chain<0>(0.f, prod);
-            const int u = lpcn_lin2ulaw((tap & 1) ? r : newest);
-            const int u_pred = __builtin_amdgcn_mov_dpp(u, 0xB1, 0xf, 0xf, true);
-            if (tap == 0) {
-                if (live) {
-                    lead_p[lrow * 8 + 0] = r;
-                    idx_p[lrow] = u | (u_pred << 8) | (exc << 16);
-                } else {
-                    idx_p[lrow] = 0;
-                }
-                if (per_frame) idx_p[S + lrow] = live ? 1 : 0;
-            }
-        };
-        auto publish_indices = [&]() __attribute__((always_inline)) { asm volatile("ds_write_b32 %0, %1" :: "v"(flag_p), "v"(seqP) : "memory"); };
-        auto draw_thresholds = [&](const int ls) __attribute__((always_inline)) {           // src/nnet.c:178-184
-            int *li = (int *)lead_p + ls * 8;
-            uint32_t rng[4] = {(uint32_t)li[4], (uint32_t)li[5], (uint32_t)li[6], (uint32_t)li[7]};
-            const uint32_t r0 = lpcn_kiss99(rng), r1 = lpcn_kiss99(rng);
-            li[4] = (int)rng[0]; li[5] = (int)rng[1]; li[6] = (int)rng[2]; li[7] = (int)rng[3];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                thr_p[ls * 8 + b] = sm_logit[(r0 >> (8 * b)) & 0xFF];
-                thr_p[ls * 8 + 4 + b] = sm_logit[(r1 >> (8 * b)) & 0xFF];
-            }
-        };
 
         // ------------------------------------------------ the leader finishes group P's previous sample --
         if (more) ++seqP;
@@ -281,62 +215,15 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             int t_ = tid0;
             LPCN_REMAT_V(t_);                                // (lane-derived indices are rebuilt here: hoisted out of the loop they are spilled, and a scratch reload on the leader's path is ~0.5 k clk)
             const int lrow = (t_ & 63) >> 4, tap = t_ & 15;
-            auto walk_tree = [&](int lrow_) __attribute__((always_inline)) {                // the sampler's 8 decisions from the 255 ballot bits of stream row lrow_
-                typedef unsigned u4 __attribute__((ext_vector_type(4)));
-                const u4 *mk = (const u4 *)((const unsigned long long *)(gp + L::g_mask) + lrow_ * 8);
-                const u4 qa = mk[0], qb = mk[1], qc = mk[2], qd = mk[3];
-                auto bit_of = [](unsigned word, int k) __attribute__((always_inline)) { return (int)((word >> (2 * k)) & 1u); };
-                int val = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) val = (val << 1) | bit_of(qa[0], (1 << b) | val);
-                val = (val << 1) | bit_of(qa[1], val);
-                val = (val << 1) | bit_of((val & 16) ? qa[3] : qa[2], val & 15);
-                {
-                    const int k = val >> 4;
-                    const unsigned lo = (k & 1) ? qb[1] : qb[0], hi = (k & 1) ? qb[3] : qb[2];
-                    val = (val << 1) | bit_of((k & 2) ? hi : lo, val & 15);
-                }
-                {
-                    const int k = val >> 4;
-                    const unsigned a0 = (k & 1) ? qc[1] : qc[0], a1 = (k & 1) ? qc[3] : qc[2];
-                    const unsigned a2 = (k & 1) ? qd[1] : qd[0], a3 = (k & 1) ? qd[3] : qd[2];
-                    const unsigned b0 = (k & 2) ? a1 : a0, b1_ = (k & 2) ? a3 : a2;
-                    val = (val << 1) | bit_of((k & 4) ? b1_ : b0, val & 15);
-                }
-                return val;
-            };
-            float pcm = 0.f, deemph = 0.f;
-            int exc = 0;
-            if (liveP) {
-                const float pred = lead_p[lrow * 8 + 0];
-                deemph = lead_p[lrow * 8 + 1];
-                exc = walk_tree(lrow);
-                if (smp_done < preload) {                                       // src/lpcnet.c:256-258
-                    const float x = (float)pcm_p[lrow * LPCN_FRAME_SIZE + smp_done];
-                    exc = lpcn_lin2ulaw(x - 0.85f * deemph - pred);
-                    pcm = x - 0.85f * deemph;
-                } else {
-                    pcm = pred + sm_ulaw[exc];                                  // src/lpcnet.c:260
-                }
-            }
-            {
-                const float shifted = row_shr1(histP, pcm);                     // src/lpcnet.c:262-263
-                histP = liveP ? shifted : histP;
-            }
-            if (tap == 0 && liveP) ((int *)lead_p)[lrow * 8 + 2] = exc;
-            if (more) { open_sample(liveP, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); publish_indices(); }
+            float pcm, deemph;
+            int exc;
+            draw_sample(cells_p, (const unsigned long long *)(gp + L::g_mask) + lrow * 8, sm_ulaw, lrow, tap, liveP, smp_done, preload, histP, pcm, deemph, exc);
+            // the next sample's indices first (wave LW publishes them through idx_p + flag_p): the row waves are waiting for them
+            if (more) { open_sample<S>(cells_p, tid0, liveP, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); lds_publish(flag_p, seqP); }
             __builtin_amdgcn_s_setprio(0);
-            if (tap == 0) {
-                if (liveP) {
-                    pcm = pcm + 0.85f * deemph;
-                    lead_p[lrow * 8 + 1] = pcm;
-                    if (smp_done >= preload) pcm_p[lrow * LPCN_FRAME_SIZE + smp_done] = (short)lpcn_round_pcm(pcm);
-                } else {
-                    pcm_p[lrow * LPCN_FRAME_SIZE + smp_done] = 0;
-                }
-            }
+            finish_sample(cells_p, lrow, tap, liveP, smp_done, preload, pcm, deemph);
         }
-        if (more && is_tw_lane && liveP) { int t_ = tid0; LPCN_REMAT_V(t_); draw_thresholds(t_ - 64 * TW); }
+        if (more && is_tw_lane && liveP) { int t_ = tid0; LPCN_REMAT_V(t_); draw_thresholds(cells_p, sm_logit, t_ - 64 * TW); }
 
         // ------------------------------------------------ group P enters a new frame --------------------
         if (new_frame) {
@@ -363,10 +250,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 }
                 if (lw_ || twl_) {
                     const int lstream = stream_of(S * p + (lw_ ? (tid & 63) >> 4 : tid - 64 * TW));
-                    const int fc_ref = Ap->fc_base ? as_global(Ap->fc_base)[lstream] : states[lstream].frame_count;
-                    int fc = Ap->fc_advance ? fc_ref + fP + 1 : fc_ref;
-                    if (fc > 1000) fc = 1000;
-                    liveP = fc > LPCN_FEATURES_DELAY;         // src/lpcnet.c:239-243
+                    liveP = stream_is_live(Ap, states, lstream, fP);
                 }
                 if (preload > 0 && tid < S) {
                     const auto *pin = as_global(Ap->pcm) + (size_t)stream_of(S * p + tid) * (size_t)Ap->pcm_stride + (size_t)fP * LPCN_FRAME_SIZE;
@@ -376,10 +260,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             __syncthreads();                                  // lpc_p visible to the leaders
             ++seqP;
             if (lw_) {
-                open_sample(liveP, histP, histP * lpc_p[tid & 63], ((const int *)lead_p)[((tid & 63) >> 4) * 8 + 2], true);
-                publish_indices();
+                open_sample<S>(cells_p, tid0, liveP, histP, histP * lpc_p[tid & 63], ((const int *)cells_p.lead)[((tid & 63) >> 4) * 8 + 2], true);
+                lds_publish(flag_p, seqP);
             }
-            if (twl_ && liveP) draw_thresholds(tid - 64 * TW);
+            if (twl_ && liveP) draw_thresholds(cells_p, sm_logit, tid - 64 * TW);
             __syncthreads();
             int lm = 0;
 #pragma unroll
@@ -535,15 +419,6 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 *(float4 *)(sm_inh + (r - 2 * NA) * S) = make_float4(g[0], g[1], g[2], g[3]);
             }
         };
-        auto p0_arrive = [&]() __attribute__((always_inline)) {     // the stores above are ahead of this add in the wave's LDS queue
-            int one = 1;
-            unsigned long long ex;
-            asm volatile("s_mov_b64 %0, exec\n\t"
-                         "s_mov_b64 exec, 1\n\t"
-                         "ds_add_u32 %1, %2\n\t"
-                         "s_mov_b64 exec, %0"
-                         : "=&s"(ex) : "v"(p0cnt_p), "v"(one) : "memory");
-        };
         // The two kinds of waves take disjoint paths (so that the 64 registers GRU-B's assembly block names and the 48 loads of the start-value pass in
         // flight never count against each other in the register allocation):
         if (wave < CW) {
@@ -565,7 +440,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 float rec = sm_bbias[RB + r];
 #pragma unroll
                 for (int j = 0; j < NB; ++j) rec = rec + sm_brec[j * RB + r] * hB_q[s * NB + j];
-                uint32_t wp32 = lds_addr(smem + L::bw + (sm_bstart[g6] * 8 + ri) * 16 + ((0x321100 >> (4 * g6)) & 15) * 128);
+                uint32_t wp32 = lds_addr(smem + L::bw + (sm_bstart[g6] * 8 + ri) * 16 + ((LPCN_GRUB_SHIFT >> (4 * g6)) & 15) * 128);
                 uint32_t hp32 = lds_addr(gq + L::g_hA + s * 16);
                 asm volatile(
 #include "grub_lds_loop_s4.inc"
@@ -583,15 +458,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                     const float hnew = sg * hold + (1.f - sg) * hc_i;
                     if ((live_maskQ >> s) & 1) hB_q[s * NB + ln_] = hnew;
                 }
-                {                                            // (the store above is ahead of this add in the wave's LDS queue)
-                    int one = 1;
-                    unsigned long long ex;
-                    asm volatile("s_mov_b64 %0, exec\n\t"
-                                 "s_mov_b64 exec, 1\n\t"
-                                 "ds_add_u32 %1, %2\n\t"
-                                 "s_mov_b64 exec, %0"
-                                 : "=&s"(ex) : "v"(chcnt_q), "v"(one) : "memory");
-                }
+                lds_arrive(chcnt_q);                         // (behind the state store)
                 LPCN_X2_PROF(2);
             }
             // (Round 6 also gave these waves a share of P's start-value pass -- a round of update / reset rows and one of candidate inputs, or the candidate
@@ -624,7 +491,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 issue(0, 0); issue(1, 1); issue(2, 2);
                 LPCN_X2_PROF(2);
                 reduce(0, 0); reduce(1, 1); reduce(2, 2);
-                p0_arrive();
+                lds_arrive(p0cnt_p);                         // (behind the stores of the three rounds)
                 issue(3, 0);
                 if (fifth) issue(4, 1);
             }
@@ -647,14 +514,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         if (p_active) {
             hA_cur = gp + L::g_hA;
             load_negz();
-            {                                                // the start values of the update / reset rows and the candidate inputs come from P0
-                int v;
-                const int want = seqP * NP0;
-                do {
-                    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(p0cnt_p) : "memory");
-                    v = __builtin_amdgcn_readfirstlane(v);
-                } while (v != want);
-            }
+            lds_poll_until<false>(p0cnt_p, seqP * NP0);       // the start values of the update / reset rows and the candidate inputs come from P0
             LPCN_X2_PROF(11);                                // wait for the start-value pass of the four row waves
             // slot 0 becomes the running row: candidate rows start from bias + diag*h -- or from the sums their head has parked --, update / reset
             // rows from their P0 cell; candidate rows further down park bias + diag*h in their own cell
@@ -758,14 +618,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         // while others are still in their (latency-bound) items, instead of all eight saturating the vector units at once behind the barrier.
         if (q_chain) {
             if (!p_active) load_fc();
-            {
-                int v;
-                const int want = chnQ * S;
-                do {
-                    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(chcnt_q) : "memory");
-                    v = __builtin_amdgcn_readfirstlane(v);
-                } while (v != want);
-            }
+            lds_poll_until<false>(chcnt_q, chnQ * S);
             int tid = tid0;
             LPCN_REMAT_V(tid);
             const int node = tid >> 1;

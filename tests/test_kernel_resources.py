@@ -116,8 +116,8 @@ def test_generated_assembly_loops_are_what_the_generator_emits():
     cases = [(["--lds", "1"], "grub_lds_loop_s1.inc"), (["--lds", "2"], "grub_lds_loop_s2.inc"), (["--lds", "4"], "grub_lds_loop_s4.inc"),
              (["--lds", "1", "--blocks", str(96 - prod), "--name", "LPCN_GRUB_LDS32_CLOBBERS"], "grub_lds_loop_s1_first.inc"),
              (["--prod", str(prod)], "grub_prod_loop.inc")]
-    # (round 6: the loops of forms that were measured and not kept -- the scalar-state loop, the product ring of four streams, the int8 loop, two / four
-    # streams per chain wave -- are no longer committed; the generator still emits them for tools/ubench and the record in EXPERIMENTS.md)
+    # (the forms that were measured and not kept -- the scalar-state loop, the product ring of four streams, the int8 loop, two / four streams per
+    # chain wave -- are in EXPERIMENTS.md and the generator's history: it emits exactly these five files)
     for args, name in cases:
         out = subprocess.run([sys.executable, gen] + args, capture_output=True, text=True, check=True).stdout
         assert out == open(os.path.join(csrc, name)).read(), name
