@@ -105,6 +105,35 @@ LPCNET_EXPORT int lpcnet_batch_set_fast(LPCNetBatch *b, int on);
 LPCNET_EXPORT int lpcnet_batch_decode_device(LPCNetBatch *b, const unsigned char *d_packets, short *d_pcm, int n_packets,
                                              void *hip_stream);
 
+/* Feature analysis: lpcnet_compute_single_frame_features (src/lpcnet_enc.c:919; _float: :927) for every stream and frame, on the
+ * device, bit-identical to the reference's generic-C float build:
+ *   pcm [n_streams][n_frames*160] -> features [n_streams][n_frames][feat_stride], feat_stride >= 36, floats 0..35 of a frame written:
+ *   [0..17] cepstrum, [18] pitch, [19] pitch correlation, [20..35] LPC -- what `lpcnet_demo -features` writes and
+ *   lpcnet_batch_synthesize* reads with feat_stride 36.
+ * A batch is n independent LPCNetEncState objects as well: the analysis state (per stream, on the device) is separate from the
+ * synthesis state -- lpcnet_batch_reset does not touch it, lpcnet_batch_analysis_reset is lpcnet_encoder_init on a range of streams.
+ * It is allocated (all zero) by the first analysis call or by lpcnet_batch_analysis_enable; batches that never analyse allocate nothing.
+ * Analysis needs no weights, but the device side of a batch (engine, stream, buffers) is created by lpcnet_batch_load_model: on a
+ * batch without a model every call below returns LPCNET_HIP_E_MODEL with a message.
+ * Host-pointer calls copy in, run, copy out and synchronise (one host thread per shard); any n_frames >= 1. */
+LPCNET_EXPORT int lpcnet_batch_analyze(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_frames);
+LPCNET_EXPORT int lpcnet_batch_analyze_float(LPCNetBatch *b, const float *pcm, float *features, int feat_stride, int n_frames);
+/* Device pointers (d_pcm: shorts, or floats when pcm_is_float != 0), enqueue only, on `hip_stream` (NULL = the batch's own): the same
+ * ordering and capture rules as lpcnet_batch_synthesize_device.  Issued on a stream that is being captured the call executes,
+ * allocates and synchronises nothing, so the analysis state and the kernels' scratch for n_frames per call must exist before the
+ * capture starts (lpcnet_batch_analysis_enable, or an earlier eager call of at least that length): otherwise LPCNET_HIP_E_ARG. */
+LPCNET_EXPORT int lpcnet_batch_analyze_device(LPCNetBatch *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride,
+                                              int n_frames, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_analyze_device_shard(LPCNetBatch *b, int shard, const void *d_pcm, int pcm_is_float, float *d_features,
+                                                    int feat_stride, int n_frames, void *hip_stream);
+/* allocate the analysis state (if absent) and scratch for calls of up to max_frames frames; keeps an existing state */
+LPCNET_EXPORT int lpcnet_batch_analysis_enable(LPCNetBatch *b, int max_frames);
+LPCNET_EXPORT int lpcnet_batch_analysis_reset(LPCNetBatch *b, int first, int count);
+/* raw per-stream analysis state (layout = struct lpcn_analysis_state in lpcnet_amd/csrc/lpcnet_engine.h): snapshot / rollback */
+LPCNET_EXPORT int lpcnet_batch_analysis_state_size(void);
+LPCNET_EXPORT int lpcnet_batch_get_analysis_state(LPCNetBatch *b, int stream, void *out);
+LPCNET_EXPORT int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, const void *in);
+
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);
 LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st);

@@ -98,6 +98,14 @@ def load_library():
     L.lpcnet_batch_set_lpc_gamma.argtypes = [vp, C.c_float]
     L.lpcnet_batch_set_end2end.argtypes = [vp, C.c_int]
     L.lpcnet_batch_set_fast.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_analyze.argtypes = [vp, _i16p, _f32p, C.c_int, C.c_int]
+    L.lpcnet_batch_analyze_float.argtypes = [vp, _f32p, _f32p, C.c_int, C.c_int]
+    L.lpcnet_batch_analyze_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.lpcnet_batch_analyze_device_shard.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp]
+    L.lpcnet_batch_analysis_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_analysis_reset.argtypes = [vp, C.c_int, C.c_int]
+    L.lpcnet_batch_get_analysis_state.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_set_analysis_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_export_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_import_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_streams_per_workgroup.argtypes = [vp, C.c_int]
@@ -371,6 +379,45 @@ class LPCNetBatch:
     def synthesize_device_shard(self, shard: int, d_features_ptr: int, stride: int, d_pcm_ptr: int, n_frames: int, hip_stream: int = 0):
         self._chk(self.L.lpcnet_batch_synthesize_device_shard(self.p, shard, d_features_ptr, stride, d_pcm_ptr, n_frames, hip_stream or None),
                   "synthesize_device_shard")
+
+    # ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ----
+    def analyze(self, pcm: np.ndarray) -> np.ndarray:
+        """pcm (n, T*160) int16 or float32 -> features (n, T, 36) float32: cepstrum [0..17], pitch [18], pitch correlation [19], LPC [20..35]."""
+        pcm = np.asarray(pcm)
+        n, ns = pcm.shape
+        assert n == self.n and ns % LPCNET_FRAME_SIZE == 0 and ns > 0
+        T = ns // LPCNET_FRAME_SIZE
+        feat = np.zeros((n, T, NB_TOTAL_FEATURES), np.float32)
+        if pcm.dtype == np.float32:
+            self._chk(self.L.lpcnet_batch_analyze_float(self.p, np.ascontiguousarray(pcm).reshape(-1), feat.reshape(-1), NB_TOTAL_FEATURES, T), "analyze_float")
+        else:
+            assert pcm.dtype == np.int16, "pcm must be int16 or float32"
+            self._chk(self.L.lpcnet_batch_analyze(self.p, np.ascontiguousarray(pcm).reshape(-1), feat.reshape(-1), NB_TOTAL_FEATURES, T), "analyze")
+        return feat
+
+    def analyze_device(self, d_pcm_ptr: int, pcm_is_float: bool, d_features_ptr: int, stride: int, n_frames: int, hip_stream: int = 0):
+        self._chk(self.L.lpcnet_batch_analyze_device(self.p, d_pcm_ptr, int(bool(pcm_is_float)), d_features_ptr, stride, n_frames, hip_stream or None),
+                  "analyze_device")
+
+    def analyze_device_shard(self, shard: int, d_pcm_ptr: int, pcm_is_float: bool, d_features_ptr: int, stride: int, n_frames: int, hip_stream: int = 0):
+        self._chk(self.L.lpcnet_batch_analyze_device_shard(self.p, shard, d_pcm_ptr, int(bool(pcm_is_float)), d_features_ptr, stride, n_frames,
+                                                           hip_stream or None), "analyze_device_shard")
+
+    def analysis_enable(self, max_frames: int = 1):
+        """allocate the analysis state and the kernels' scratch for calls of up to max_frames frames (needed before a graph capture)"""
+        self._chk(self.L.lpcnet_batch_analysis_enable(self.p, max_frames), "analysis_enable")
+
+    def analysis_reset(self, first=0, count=None):
+        self._chk(self.L.lpcnet_batch_analysis_reset(self.p, first, self.n - first if count is None else count), "analysis_reset")
+
+    def get_analysis_state(self, stream: int) -> bytes:
+        buf = C.create_string_buffer(self.L.lpcnet_batch_analysis_state_size())
+        self._chk(self.L.lpcnet_batch_get_analysis_state(self.p, stream, buf), "get_analysis_state")
+        return buf.raw
+
+    def set_analysis_state(self, stream: int, raw: bytes):
+        assert len(raw) == self.L.lpcnet_batch_analysis_state_size()
+        self._chk(self.L.lpcnet_batch_set_analysis_state(self.p, stream, C.create_string_buffer(raw, len(raw))), "set_analysis_state")
 
     def set_lpc_gamma(self, gamma: float):
         self._chk(self.L.lpcnet_batch_set_lpc_gamma(self.p, gamma), "set_lpc_gamma")

@@ -1063,8 +1063,9 @@ int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
  * device and stream; with a single shard the work runs on the calling thread. */
 typedef struct {
     LPCNetBatch *b; int shard;
-    int kind;                                     /* 0 synthesize(preload), 1 decode */
+    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze */
     const float *features; int feat_stride; short *pcm; int n_frames, preload;
+    const void *an_pcm; int an_is_float; float *an_features;
     const unsigned char *packets; int n_packets;
     int rc; char err[256];
 } shard_job;
@@ -1076,7 +1077,11 @@ static void *shard_worker(void *arg)
     if (j->kind == 0)
         j->rc = lpcn_batch_dev_run_host(s->dev, j->features + (size_t)s->first * j->n_frames * j->feat_stride, j->feat_stride,
                                         j->pcm + (size_t)s->first * j->n_frames * LPCN_FRAME_SIZE, j->n_frames, j->preload);
-    else
+    else if (j->kind == 2) {
+        const size_t o = (size_t)s->first * j->n_frames * LPCN_FRAME_SIZE;
+        j->rc = lpcn_batch_dev_analyze_host(s->dev, j->an_is_float ? (const void *)((const float *)j->an_pcm + o) : (const void *)((const short *)j->an_pcm + o),
+                                            j->an_is_float, j->an_features + (size_t)s->first * j->n_frames * j->feat_stride, j->feat_stride, j->n_frames);
+    } else
         j->rc = lpcn_batch_dev_decode_host(s->dev, j->packets + (size_t)s->first * j->n_packets * 8,
                                            j->pcm + (size_t)s->first * j->n_packets * 4 * LPCN_FRAME_SIZE, j->n_packets);
     if (j->rc) snprintf(j->err, sizeof(j->err), "%s", lpcn_last_error());      /* (the engine's message is thread-local) */
@@ -1242,6 +1247,74 @@ int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st)
     NEED_MODEL(b);
     SHARD_OF(s, b, stream);
     FWD(lpcn_batch_dev_set_state(s->dev, stream - s->first, &st->s));
+}
+
+/* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */
+static int analyze_host(LPCNetBatch *b, const void *pcm, int is_float, float *features, int feat_stride, int n_frames)
+{
+    NEED_MODEL(b);
+    if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_analyze: bad arguments"); return LPCN_E_ARG; }
+    shard_job j;
+    memset(&j, 0, sizeof(j));
+    j.kind = 2; j.an_pcm = pcm; j.an_is_float = is_float; j.an_features = features; j.feat_stride = feat_stride; j.n_frames = n_frames;
+    return run_shards(b, &j);
+}
+int lpcnet_batch_analyze(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_frames)
+{
+    return analyze_host(b, pcm, 0, features, feat_stride, n_frames);
+}
+int lpcnet_batch_analyze_float(LPCNetBatch *b, const float *pcm, float *features, int feat_stride, int n_frames)
+{
+    return analyze_host(b, pcm, 1, features, feat_stride, n_frames);
+}
+int lpcnet_batch_analyze_device_shard(LPCNetBatch *b, int shard, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride,
+                                      int n_frames, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_analyze(b->sh[shard].dev, d_pcm, pcm_is_float, d_features, feat_stride, n_frames, hip_stream));
+}
+int lpcnet_batch_analyze_device(LPCNetBatch *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
+                                void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_analyze_device");
+    return lpcnet_batch_analyze_device_shard(b, 0, d_pcm, pcm_is_float, d_features, feat_stride, n_frames, hip_stream);
+}
+int lpcnet_batch_analysis_enable(LPCNetBatch *b, int max_frames)
+{
+    NEED_MODEL(b);
+    for (int k = 0; k < b->n_shards; k++) { int rc = lpcn_batch_dev_analysis_enable(b->sh[k].dev, max_frames); if (rc) { take_engine_err(); return rc; } }
+    return 0;
+}
+int lpcnet_batch_analysis_reset(LPCNetBatch *b, int first, int count)
+{
+    NEED_MODEL(b);
+    if (first < 0 || count < 0 || first + count > b->n) { set_err("analysis reset range"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {
+        const batch_shard *s = &b->sh[k];
+        const int lo = first > s->first ? first : s->first;
+        const int hi = first + count < s->first + s->count ? first + count : s->first + s->count;
+        if (hi <= lo) continue;
+        int rc = lpcn_batch_dev_analysis_reset(s->dev, lo - s->first, hi - lo);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    return 0;
+}
+int lpcnet_batch_analysis_state_size(void) { return (int)sizeof(lpcn_analysis_state); }
+int lpcnet_batch_get_analysis_state(LPCNetBatch *b, int stream, void *out)
+{
+    NEED_MODEL(b);
+    if (!out) { set_err("lpcnet_batch_get_analysis_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_get_analysis_state(s->dev, stream - s->first, (lpcn_analysis_state *)out));
+}
+int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, const void *in)
+{
+    NEED_MODEL(b);
+    if (!in) { set_err("lpcnet_batch_set_analysis_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_set_analysis_state(s->dev, stream - s->first, (const lpcn_analysis_state *)in));
 }
 
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }

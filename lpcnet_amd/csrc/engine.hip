@@ -11,6 +11,7 @@
 #include "sample_kernel.hip.h"
 #include "frame_kernels.hip.h"
 #include "decode_kernel.hip.h"
+#include "analysis_kernels.hip.h"
 #include <math.h>
 
 static thread_local char g_err[512] = "";
@@ -69,6 +70,12 @@ struct lpcn_batch_dev {
     float *d_cond_a = nullptr, *d_cond_b = nullptr, *d_lpc = nullptr, *d_cond = nullptr;
     float *d_feat = nullptr;           // staging for host-pointer runs / decoded feature vectors
     float *d_vq_mem = nullptr;         // [n][18] VQ memory of the codec path (src/lpcnet_private.h:52)
+    lpcn_analysis_state *d_an_state = nullptr;   // feature analysis (lpcn_batch_dev_analysis_enable): per-stream state, allocated on first use
+    float *d_an_resid = nullptr, *d_an_xc = nullptr, *d_an_fw = nullptr;   //   ... and the kernels' scratch for an_chunk frames per launch
+    int an_chunk = 0;
+    void *d_an_pcm = nullptr;          //   ... and the staging of host-pointer calls (PCM in, features out)
+    float *d_an_feat = nullptr;
+    size_t an_pcm_cap = 0, an_feat_cap = 0;
     lpcn_stream_state *d_state_tmp = nullptr;   // per-stream-arguments step (lpcn_batch_dev_step_host): the compacted group's states
     int *d_map = nullptr;              //   ... and its stream indices
     float *d_keep_a = nullptr, *d_keep_b = nullptr, *d_keep_lpc = nullptr;   //   ... and every stream's most recent frame products
@@ -458,7 +465,8 @@ extern "C" void lpcn_batch_dev_destroy(lpcn_batch_dev *b)
     if (b->h_pin) (void)hipHostFree(b->h_pin);
     if (b->ev_last) (void)hipEventDestroy(b->ev_last);
     void *ptrs[] = {b->d_state, b->d_fc_base, b->d_cond_a, b->d_cond_b, b->d_lpc, b->d_cond, b->d_feat, b->d_pcm, b->d_args, b->d_dbg, b->d_prof,
-                    b->d_vq_mem, b->d_packets, b->d_state_tmp, b->d_map, b->d_keep_a, b->d_keep_b, b->d_keep_lpc};
+                    b->d_vq_mem, b->d_packets, b->d_state_tmp, b->d_map, b->d_keep_a, b->d_keep_b, b->d_keep_lpc,
+                    b->d_an_state, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_an_pcm, b->d_an_feat};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &ev : b->ev) if (ev) (void)hipEventDestroy(ev);
     delete b;
@@ -940,6 +948,127 @@ extern "C" int lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
+
+// ------------------------------------------------------------------------------- feature analysis -----
+// (stream, frame) items per launch of the analysis kernels: bounds their scratch (2.7 KB per item) at 176 MB
+#define LPCN_AN_ITEMS_MAX 65536
+static int analysis_chunk_for(const lpcn_batch_dev *b, int n_frames)
+{
+    int cap = LPCN_AN_ITEMS_MAX / b->n;
+    if (cap < 1) cap = 1;
+    return n_frames < cap ? n_frames : cap;
+}
+
+extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
+{
+    if (max_frames < 1) { snprintf(g_err, sizeof(g_err), "analysis: bad frame count"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    const int chunk = analysis_chunk_for(b, max_frames);
+    if (b->d_an_state && chunk <= b->an_chunk) return 0;
+    { int rcw = wait_all(b); if (rcw) return rcw; }      // the old scratch may still be in use
+    if (!b->d_an_state) {
+        HIP_TRY(hipMalloc((void **)&b->d_an_state, sizeof(lpcn_analysis_state) * (size_t)b->n));
+        HIP_TRY(hipMemset(b->d_an_state, 0, sizeof(lpcn_analysis_state) * (size_t)b->n));      // lpcnet_encoder_init (src/lpcnet_enc.c:471-475)
+    }
+    if (chunk > b->an_chunk) {
+        for (float **p : {&b->d_an_resid, &b->d_an_xc, &b->d_an_fw}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        b->an_chunk = 0;
+        const size_t items = (size_t)b->n * chunk;
+        HIP_TRY(hipMalloc((void **)&b->d_an_resid, sizeof(float) * items * LPCN_FRAME_SIZE));
+        HIP_TRY(hipMalloc((void **)&b->d_an_xc, sizeof(float) * items * 2 * LPCN_PITCH_MAX_PERIOD));
+        HIP_TRY(hipMalloc((void **)&b->d_an_fw, sizeof(float) * items * 2));
+        b->an_chunk = chunk;
+    }
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
+                                      void *hip_stream)
+{
+    if (!d_pcm || !d_features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
+    if (!b->d_an_state || analysis_chunk_for(b, n_frames) > b->an_chunk) {
+        if (stream_is_capturing(st)) {      // (a capture executes nothing and allocates nothing)
+            snprintf(g_err, sizeof(g_err), "analysis state / scratch for %d frames per call must exist before a capture: call lpcnet_batch_analysis_enable first", n_frames);
+            return LPCN_E_ARG;
+        }
+        int rc = lpcn_batch_dev_analysis_enable(b, n_frames);
+        if (rc) return rc;
+    }
+    { int rco = order_begin(b, st); if (rco) return rco; }
+    const int is_float = pcm_is_float ? 1 : 0;
+    const size_t pcm_stride = (size_t)n_frames * LPCN_FRAME_SIZE, feat_stream_stride = (size_t)n_frames * feat_stride;
+    for (int f0 = 0; f0 < n_frames; f0 += b->an_chunk) {
+        const int nf = n_frames - f0 < b->an_chunk ? n_frames - f0 : b->an_chunk;
+        const void *p = is_float ? (const void *)((const float *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE) : (const void *)((const short *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE);
+        int rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, nf, p, is_float, pcm_stride, b->d_an_state, d_features + (size_t)f0 * feat_stride,
+                                              feat_stride, feat_stream_stride, b->d_an_resid, b->d_an_xc, b->d_an_fw, g_err, sizeof(g_err));
+        if (rc) return rc;
+    }
+    return order_end(b, st);
+}
+
+extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames)
+{
+    if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));
+    const size_t nfeat = (size_t)b->n * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
+    if (npcm > b->an_pcm_cap || nfeat > b->an_feat_cap) { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (npcm > b->an_pcm_cap) {
+        if (b->d_an_pcm) (void)hipFree(b->d_an_pcm);
+        b->d_an_pcm = nullptr; b->an_pcm_cap = 0;
+        HIP_TRY(hipMalloc(&b->d_an_pcm, npcm));
+        b->an_pcm_cap = npcm;
+    }
+    if (nfeat > b->an_feat_cap) {
+        if (b->d_an_feat) (void)hipFree(b->d_an_feat);
+        b->d_an_feat = nullptr; b->an_feat_cap = 0;
+        HIP_TRY(hipMalloc((void **)&b->d_an_feat, nfeat * sizeof(float)));
+        b->an_feat_cap = nfeat;
+    }
+    int rc = lpcn_batch_dev_analysis_enable(b, n_frames);
+    if (rc) return rc;
+    hipStream_t st = b->e->stream;
+    if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
+    HIP_TRY(hipMemcpyAsync(b->d_an_pcm, pcm, npcm, hipMemcpyHostToDevice, st));
+    rc = lpcn_batch_dev_analyze(b, b->d_an_pcm, pcm_is_float, b->d_an_feat, LPCN_AN_NB_FEATURES, n_frames, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2DAsync(features, (size_t)feat_stride * sizeof(float), b->d_an_feat, LPCN_AN_NB_FEATURES * sizeof(float),
+                             LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->n * n_frames, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int count)
+{
+    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "analysis reset range"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    if (!b->d_an_state) return lpcn_batch_dev_analysis_enable(b, 1);      // (a fresh state IS the reset state)
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (count) HIP_TRY(hipMemset(b->d_an_state + first, 0, sizeof(lpcn_analysis_state) * (size_t)count));
+    return 0;
+}
+extern "C" int lpcn_batch_dev_get_analysis_state(lpcn_batch_dev *b, int s, lpcn_analysis_state *host)
+{
+    if (s < 0 || s >= b->n || !host) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    if (!b->d_an_state) { int rc = lpcn_batch_dev_analysis_enable(b, 1); if (rc) return rc; }
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    HIP_TRY(hipMemcpy(host, b->d_an_state + s, sizeof(*host), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int s, const lpcn_analysis_state *host)
+{
+    if (s < 0 || s >= b->n || !host) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    if (!b->d_an_state) { int rc = lpcn_batch_dev_analysis_enable(b, 1); if (rc) return rc; }
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    HIP_TRY(hipMemcpy(b->d_an_state + s, host, sizeof(*host), hipMemcpyHostToDevice));
+    return 0;
+}
+
 
 extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond_a, const float *cond_b,
                                             const float *lpc, short *pcm, int n_frames, int preload)

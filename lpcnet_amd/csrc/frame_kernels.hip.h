@@ -380,59 +380,11 @@ __device__ __forceinline__ cpx cmul(cpx a, cpx b) { cpx m; m.r = a.r * b.r - a.i
 __device__ __forceinline__ cpx cadd(cpx a, cpx b) { cpx m; m.r = a.r + b.r; m.i = a.i + b.i; return m; }
 __device__ __forceinline__ cpx csub(cpx a, cpx b) { cpx m; m.r = a.r - b.r; m.i = a.i - b.i; return m; }
 
-constexpr int LPC_WAVES = 4;     // wavefronts (= frames) per workgroup
-
-__global__ __launch_bounds__(64 * LPC_WAVES) void lpc_kernel(LpcnFrameModel M, int n_streams, int n_frames, const float *feat, int feat_stride,
-                                                             size_t feat_stream_stride, lpcn_stream_state *states, float *lpc_out)
+// The radix-4 (m = 1, 4, 16) and radix-5 (m = 64) passes of opus_fft_impl for nfft = 320 (src/kiss_fft.c:111-168, :232-305), in place on F
+// (digit-reversed, scaled input) by one wavefront.  Contains workgroup barriers: every wavefront of the workgroup calls it; F is complete
+// for all lanes on return.  Shared by lpc_kernel and the analysis kernel (analysis_kernels.hip.h).
+__device__ __forceinline__ void fft320_passes(cpx *F, const cpx *TW, const int lane)
 {
-    __shared__ cpx fbuf[LPC_WAVES][320];
-    __shared__ float ex[LPC_WAVES][LPCN_NB_BANDS];
-    __shared__ float xr[LPC_WAVES][164];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const size_t item = (size_t)blockIdx.x * LPC_WAVES + wv;
-    const bool valid = item < (size_t)n_streams * n_frames;
-    const int stream = valid ? (int)(item / n_frames) : 0, t = valid ? (int)(item % n_frames) : 0;
-    const float *c = feat + (size_t)stream * feat_stream_stride + (size_t)t * feat_stride;
-    cpx *F = fbuf[wv];
-    const cpx *TW = (const cpx *)M.tab_tw;
-    static const short band_edge[LPCN_NB_BANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};   // src/freq.c:46-49
-    static const float band_comp[LPCN_NB_BANDS] = {0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.666667f, 0.5f, 0.5f, 0.5f,
-                                                   0.333333f, 0.25f, 0.25f, 0.2f, 0.166667f, 0.173913f};             // src/freq.c:51-53
-    // inverse DCT of the cepstrum (+4 on c0) and 10^x with the band compensation (src/freq.c:230-240, :317-318)
-    if (lane < LPCN_NB_BANDS) {
-        float sum = 0.f;
-        for (int j = 0; j < LPCN_NB_BANDS; ++j) {
-            float cj = c[j];
-            if (j == 0) cj = cj + 4.f;
-            sum = sum + cj * M.tab_idct[lane * LPCN_NB_BANDS + j];
-        }
-        const float e = (float)((double)sum * sqrt(2. / LPCN_NB_BANDS));
-        // pow(10.f, e) in double, then the product with the band compensation rounded to float (src/freq.c:317-318);
-        // lpcn_exp10 is this engine's own correctly rounded 10^e (lpcnet_exp10.h), not the device math library's pow
-        ex[wv][lane] = (float)(lpcn_exp10(e) * (double)band_comp[lane]);
-    }
-    __syncthreads();
-    // band interpolation (src/freq.c:202-215); bin 160 forced to 0 (:286)
-    for (int k = lane; k < 161; k += 64) {
-        float v = 0.f;
-        if (k < 160) {
-            int b = 0;
-            while (b < LPCN_NB_BANDS - 2 && k >= band_edge[b + 1] * 4) ++b;
-            const int size = (band_edge[b + 1] - band_edge[b]) * 4, j = k - band_edge[b] * 4;
-            const float frac = (float)j / (float)size;
-            v = (1.f - frac) * ex[wv][b] + frac * ex[wv][b + 1];
-        }
-        xr[wv][k] = v;
-    }
-    __syncthreads();
-    // Hermitian extension + digit-reversal copy with the 1/320 scale (src/freq.c:260-266, src/kiss_fft.c:579-584)
-    for (int k = lane; k < 320; k += 64) {
-        const float re = k < 161 ? xr[wv][k] : xr[wv][320 - k];
-        const float im = k < 161 ? 0.f : -0.f;
-        cpx v; v.r = 0.0031250000f * re; v.i = 0.0031250000f * im;
-        F[M.tab_bitrev[k]] = v;
-    }
-    __syncthreads();
     // radix-4, m = 1: 80 butterflies with unit twiddles (src/kiss_fft.c:111-131)
     for (int b = lane; b < 80; b += 64) {
         cpx *f = F + 4 * b;
@@ -492,9 +444,56 @@ __global__ __launch_bounds__(64 * LPC_WAVES) void lpc_kernel(LpcnFrameModel M, i
         *F0 = o0; *F1 = csub(s5, s6); *F4 = cadd(s5, s6); *F2 = cadd(s11, s12); *F3 = csub(s11, s12);
     }
     __syncthreads();
+}
+
+// lpc_from_cepstrum (src/freq.c:310-320, without lpc_weighting) by one wavefront: the 16 coefficients are left in lane 0's `lpc` when `active`.
+// c: the 18 cepstral coefficients (c0 without the +4); F [320], ex [18], xr [164]: the wavefront's LDS.  Contains workgroup barriers.
+__device__ __forceinline__ void lpc_from_cepstrum_wave(const LpcnFrameModel &M, const float *c, cpx *F, float *ex, float *xr, const int lane,
+                                                       const bool active, float lpc[LPCN_LPC_ORDER])
+{
+    const cpx *TW = (const cpx *)M.tab_tw;
+    static const short band_edge[LPCN_NB_BANDS] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 20, 24, 28, 34, 40};   // src/freq.c:46-49
+    static const float band_comp[LPCN_NB_BANDS] = {0.8f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.666667f, 0.5f, 0.5f, 0.5f,
+                                                   0.333333f, 0.25f, 0.25f, 0.2f, 0.166667f, 0.173913f};             // src/freq.c:51-53
+    // inverse DCT of the cepstrum (+4 on c0) and 10^x with the band compensation (src/freq.c:230-240, :317-318)
+    if (lane < LPCN_NB_BANDS) {
+        float sum = 0.f;
+        for (int j = 0; j < LPCN_NB_BANDS; ++j) {
+            float cj = c[j];
+            if (j == 0) cj = cj + 4.f;
+            sum = sum + cj * M.tab_idct[lane * LPCN_NB_BANDS + j];
+        }
+        const float e = (float)((double)sum * sqrt(2. / LPCN_NB_BANDS));
+        // pow(10.f, e) in double, then the product with the band compensation rounded to float (src/freq.c:317-318);
+        // lpcn_exp10 is this engine's own correctly rounded 10^e (lpcnet_exp10.h), not the device math library's pow
+        ex[lane] = (float)(lpcn_exp10(e) * (double)band_comp[lane]);
+    }
+    __syncthreads();
+    // band interpolation (src/freq.c:202-215); bin 160 forced to 0 (:286)
+    for (int k = lane; k < 161; k += 64) {
+        float v = 0.f;
+        if (k < 160) {
+            int b = 0;
+            while (b < LPCN_NB_BANDS - 2 && k >= band_edge[b + 1] * 4) ++b;
+            const int size = (band_edge[b + 1] - band_edge[b]) * 4, j = k - band_edge[b] * 4;
+            const float frac = (float)j / (float)size;
+            v = (1.f - frac) * ex[b] + frac * ex[b + 1];
+        }
+        xr[k] = v;
+    }
+    __syncthreads();
+    // Hermitian extension + digit-reversal copy with the 1/320 scale (src/freq.c:260-266, src/kiss_fft.c:579-584)
+    for (int k = lane; k < 320; k += 64) {
+        const float re = k < 161 ? xr[k] : xr[320 - k];
+        const float im = k < 161 ? 0.f : -0.f;
+        cpx v; v.r = 0.0031250000f * re; v.i = 0.0031250000f * im;
+        F[M.tab_bitrev[k]] = v;
+    }
+    __syncthreads();
+    fft320_passes(F, TW, lane);
     // autocorrelation lags 0..16 (reversed read, src/freq.c:268-272), noise floor, lag window, Levinson
-    if (lane == 0 && valid) {
-        float ac[LPCN_LPC_ORDER + 1], lpc[LPCN_LPC_ORDER];
+    if (lane == 0 && active) {
+        float ac[LPCN_LPC_ORDER + 1];
         ac[0] = 320.f * F[0].r;
         for (int k = 1; k <= LPCN_LPC_ORDER; ++k) ac[k] = 320.f * F[320 - k].r;
         ac[0] = (float)((double)ac[0] + ((double)ac[0] * 1e-4 + 320 / 12 / 38.));      // src/freq.c:291
@@ -517,6 +516,25 @@ __global__ __launch_bounds__(64 * LPC_WAVES) void lpc_kernel(LpcnFrameModel M, i
                 if (err < .001f * ac[0]) break;
             }
         }
+    }
+}
+
+constexpr int LPC_WAVES = 4;     // wavefronts (= frames) per workgroup
+
+__global__ __launch_bounds__(64 * LPC_WAVES) void lpc_kernel(LpcnFrameModel M, int n_streams, int n_frames, const float *feat, int feat_stride,
+                                                             size_t feat_stream_stride, lpcn_stream_state *states, float *lpc_out)
+{
+    __shared__ cpx fbuf[LPC_WAVES][320];
+    __shared__ float ex[LPC_WAVES][LPCN_NB_BANDS];
+    __shared__ float xr[LPC_WAVES][164];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t item = (size_t)blockIdx.x * LPC_WAVES + wv;
+    const bool valid = item < (size_t)n_streams * n_frames;
+    const int stream = valid ? (int)(item / n_frames) : 0, t = valid ? (int)(item % n_frames) : 0;
+    const float *c = feat + (size_t)stream * feat_stream_stride + (size_t)t * feat_stride;
+    float lpc[LPCN_LPC_ORDER];
+    lpc_from_cepstrum_wave(M, c, fbuf[wv], ex[wv], xr[wv], lane, valid, lpc);
+    if (lane == 0 && valid) {
         // two-frame delay (src/lpcnet.c:110-112) + LPC_GAMMA weighting of the consumed copy (src/freq.c:299-308)
         lpcn_stream_state *st = &states[stream];
         float g = M.lpc_gamma, gi = g;

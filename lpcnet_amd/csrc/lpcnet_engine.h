@@ -127,6 +127,28 @@ typedef struct lpcn_stream_state {
     int32_t pad[3];
 } lpcn_stream_state;
 
+/* ---- per-stream ANALYSIS state (feature extraction, analysis_kernels.hip.h): the fields of the reference's LPCNetEncState
+ * (src/lpcnet_private.h:55-75) that lpcnet_compute_single_frame_features reads or writes, in the reference's order; all zero after
+ * lpcnet_encoder_init.  Separate from the synthesis state, as LPCNetEncState is from LPCNetState.  An encoder's further fields
+ * (xc[10][257], frame_weight[10], vq_mem, ...) are appended after best_i: no field moves. */
+#define LPCN_AN_OVERLAP         160
+#define LPCN_AN_TRAINING_OFFSET 80
+#define LPCN_PITCH_MIN_PERIOD   32
+#define LPCN_PITCH_MAX_PERIOD   256
+#define LPCN_PITCH_BUF_SIZE     (LPCN_PITCH_MAX_PERIOD + 320)
+#define LPCN_AN_NB_FEATURES     36
+typedef struct lpcn_analysis_state {
+    float analysis_mem[LPCN_AN_OVERLAP];    /* the last 160 pre-emphasised input samples                                       */
+    float mem_preemph;                      /* -0.85f * the last raw input sample                                              */
+    int32_t pcount;                         /* always 0 in single-frame analysis                                               */
+    float pitch_mem[LPCN_LPC_ORDER];        /* = analysis_mem[79 - j]: kept for the layout, the kernels read analysis_mem      */
+    float pitch_filt;                       /* LPC residual of the last sample before the one-tap filter                       */
+    float exc_buf[LPCN_PITCH_BUF_SIZE];     /* [0, 416) live: the last 416 excitation samples; the rest stays zero             */
+    float pitch_max_path[LPCN_PITCH_MAX_PERIOD - LPCN_PITCH_MIN_PERIOD];
+    float pitch_max_path_all;
+    int32_t best_i;
+} lpcn_analysis_state;
+
 /* ---- engine.hip ----------------------------------------------------------------------------- */
 typedef struct lpcn_engine lpcn_engine;      /* one per (process, HIP device, model)            */
 
@@ -202,6 +224,19 @@ int  lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *features, in
  * features [n][feat_stride], pcm [n][160]. */
 int  lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features, int feat_stride, short *pcm,
                               const int *n_samples, const int *preload, const int *mode);
+
+/* Feature analysis (lpcnet_compute_single_frame_features per stream and frame, analysis_kernels.hip.h):
+ *   pcm [n_streams][n_frames*160] shorts (pcm_is_float = 0) or floats -> features [n_streams][n_frames][feat_stride >= 36], floats 0..35.
+ * The analysis state and the kernels' scratch are allocated by lpcn_batch_dev_analysis_enable (max_frames = the longest call that
+ * must not allocate: longer calls grow the scratch) or by the first call; a call on a stream that is being captured allocates nothing
+ * and returns LPCN_E_ARG when something is missing.  lpcn_batch_dev_reset does not touch the analysis state. */
+int  lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames);
+int  lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
+                            void *hip_stream);
+int  lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames);
+int  lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int count);      /* lpcnet_encoder_init */
+int  lpcn_batch_dev_get_analysis_state(lpcn_batch_dev *b, int stream, lpcn_analysis_state *host);
+int  lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int stream, const lpcn_analysis_state *host);
 
 /* Timing of the most recent run: kernel-only milliseconds measured with HIP events on the
  * stream the kernels were launched on (sample kernel, frame kernels). */

@@ -304,3 +304,52 @@ def make_codebooks(seed: int = 5):
     cb3 = (rng.standard_normal((1024, 17)) * 0.25).astype(np.float32)
     cbd = (rng.standard_normal((4096, 18)) * 0.3).astype(np.float32)
     return cb1, cb2, cb3, cbd
+
+
+def make_pcm(stream_seed: int, n_frames: int) -> np.ndarray:
+    """(n_frames*160,) int16: seeded speech-like audio at 16 kHz for the feature analysis (include/lpcnet_batch.h: lpcnet_batch_analyze).
+    A harmonic series whose pitch sweeps from 45 Hz to 650 Hz and back (beyond both ends of the analysis' 62..500 Hz range, so the
+    66 / 510 clamps of the pitch feature are reached) under a slowly moving spectral tilt, an AR(2)-shaped noise part and a DC offset;
+    per 100 frames one stretch of digital silence, one of full-scale alternation (+32767 / -32768), one of loud harmonics that
+    clip and one of a pulse train with a period of exactly 256 samples (the longest lag) -- the inputs on which order-of-summation
+    mistakes show."""
+    rng = np.random.default_rng([stream_seed, 0xA11A])
+    n = n_frames * FRAME_SIZE
+    t = np.arange(n, dtype=np.float64)
+    # pitch: a triangle in log-frequency, period between 150 and 400 frames, random phase
+    period = rng.uniform(150, 400) * FRAME_SIZE
+    tri = np.abs(((t / period + rng.uniform()) % 1.0) * 2.0 - 1.0)
+    f0 = 45.0 * (650.0 / 45.0) ** tri
+    phase = 2 * np.pi * np.cumsum(f0) / 16000.0
+    tilt = 0.55 + 0.35 * np.sin(2 * np.pi * t / (rng.uniform(40, 90) * FRAME_SIZE) + rng.uniform(0, 2 * np.pi))
+    x = np.zeros(n)
+    for h in range(1, 41):
+        x += np.where(h * f0 < 7600.0, tilt ** (h - 1) * np.sin(h * phase + rng.uniform(0, 2 * np.pi)), 0.0)
+    x *= 3000.0 / max(1.0, float(np.sqrt(np.mean(x * x))))
+    # AR(2)-shaped noise: white noise through 1 / (1 - 2 r cos(w) z^-1 + r^2 z^-2), truncated impulse response
+    r, w = rng.uniform(0.90, 0.97), rng.uniform(0.2, 1.2)
+    hh = np.zeros(256)
+    hh[0], hh[1] = 1.0, 2 * r * np.cos(w)
+    for k in range(2, 256):
+        hh[k] = 2 * r * np.cos(w) * hh[k - 1] - r * r * hh[k - 2]
+    noise = np.convolve(rng.standard_normal(n + 255), hh, mode="valid")
+    noise *= rng.uniform(150, 900) / float(np.sqrt(np.mean(noise * noise)))
+    env = 0.6 + 0.4 * np.sin(2 * np.pi * t / (rng.uniform(15, 45) * FRAME_SIZE) + rng.uniform(0, 2 * np.pi))
+    x = env * x + noise + rng.uniform(-400, 400)
+    # per 100 frames: silence, full scale, clipping harmonics (stretches of 3..9 frames at random offsets, sample-aligned on purpose)
+    for blk in range(0, n_frames, 100):
+        for kind in range(4):
+            a = (blk + int(rng.integers(5, 90))) * FRAME_SIZE + int(rng.integers(0, FRAME_SIZE))
+            b = min(n, a + int(rng.integers(3, 10) + (6 if kind == 3 else 0)) * FRAME_SIZE)
+            if a >= n:
+                continue
+            if kind == 0:
+                x[a:b] = 0.0
+            elif kind == 1:
+                x[a:b] = np.where((np.arange(a, b) // int(rng.integers(1, 40))) % 2 == 0, 32767.0, -32768.0)
+            elif kind == 2:
+                x[a:b] *= 14.0
+            else:
+                k = np.arange(b - a) % 256
+                x[a:b] = 9000.0 * np.exp(-k / 12.0) * np.cos(0.9 * k) + 0.05 * x[a:b]
+    return np.clip(np.rint(x), -32768, 32767).astype(np.int16)

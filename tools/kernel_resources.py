@@ -2,6 +2,7 @@
 """Register / scratch accounting of the sample kernel's variants from the compiler's own output (no GPU needed).
 
     python tools/kernel_resources.py [--s 4] [--asm-dir DIR] [--json]
+    python tools/kernel_resources.py --analysis          (the feature-analysis kernels of engine.hip)
 
 Compiles lpcnet_amd/csrc/sample_variants.hip for gfx950 to assembly (device only, same flags as lpcnet_amd/build.py),
 then reports per kernel: VGPR / SGPR counts, spill counts, scratch bytes (the .amdhsa metadata), and how many scratch
@@ -114,12 +115,46 @@ def analyse(asm_path):
     return sorted(out, key=lambda r: (r["S"], r["int8"], r["fast"], r["pack2"], r["NW"]))
 
 
+def engine_kernel_resources(pattern=r"N4lpcn\d+(analysis_[a-z]+_kernel)E", asm_path=None):
+    """Resources of the kernels of engine.hip (frame, decode and ANALYSIS kernels) whose mangled name matches `pattern` (group 1 = the key), from the compiler's
+    metadata: {demangled-ish name: dict(vgpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, max_flat_workgroup_size)}.  No GPU needed."""
+    from lpcnet_amd import build
+    tmp = None
+    if asm_path is None:
+        tmp = tempfile.mkdtemp(prefix="lpcn_engine_asm_")
+        asm_path = os.path.join(tmp, "engine.s")
+    if not os.path.exists(asm_path):
+        subprocess.check_call([build.HIPCC] + build.HIP_FLAGS + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "engine.hip"), "-o", asm_path],
+                              stderr=subprocess.DEVNULL)
+    text = open(asm_path).read()
+    out = {}
+    for rec in re.split(r"\n\s+- \.agpr_count:", text)[1:]:
+        nm = re.search(r"\.name:\s+(\S+)", rec)
+        if not nm:
+            continue
+        m = re.search(pattern, nm.group(1))
+        if not m:
+            continue
+        get = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", rec).group(1))
+        out[m.group(1)] = dict(vgpr=get("vgpr_count"), sgpr=get("sgpr_count"), vgpr_spill=get("vgpr_spill_count"), sgpr_spill=get("sgpr_spill_count"),
+                               scratch=get("private_segment_fixed_size"), lds=get("group_segment_fixed_size"),
+                               max_flat_workgroup_size=get("max_flat_workgroup_size"))
+    if tmp:
+        import shutil
+        shutil.rmtree(tmp, ignore_errors=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", type=int, default=4, help="streams per workgroup: 1, 2, 4, or 8 = the two-group kernel")
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of engine.hip instead")
     a = ap.parse_args()
+    if a.analysis:
+        print(json.dumps(engine_kernel_resources(r"N4lpcn\d+(analysis_[a-z]+_kernel|lpc_kernel)E", os.path.join(a.asm_dir, "engine.s") if a.asm_dir else None), indent=1))
+        return
     d = a.asm_dir or tempfile.mkdtemp(prefix="lpcn_asm_")
     path = os.path.join(d, f"sample_s{a.s}.s")
     if not os.path.exists(path):
