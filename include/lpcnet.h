@@ -5,8 +5,9 @@
  * the reference header (e.g. src/lpcnet_demo.c -synthesis / -decode) links against
  * liblpcnet_hip.so unchanged.  Each declaration cites the reference declaration it replaces.
  * The encoder / feature-extraction / PLC entry points of the reference header are outside this
- * engine's scope and are not exported.  Single-frame feature analysis lives in the
- * batch API instead: lpcnet_batch_analyze* in lpcnet_batch.h.
+ * engine's scope and are not exported.  Feature analysis and the encoder live in the
+ * batch API instead: lpcnet_batch_analyze*, lpcnet_batch_encode*, lpcnet_batch_compute_features* in
+ * lpcnet_batch.h.
  *
  * Differences a caller can observe:
  *   - The trained model is never compiled in.  A state uses the blob given to lpcnet_load_model()

@@ -134,6 +134,37 @@ LPCNET_EXPORT int lpcnet_batch_analysis_state_size(void);
 LPCNET_EXPORT int lpcnet_batch_get_analysis_state(LPCNetBatch *b, int stream, void *out);
 LPCNET_EXPORT int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, const void *in);
 
+/* The encoder of the 1.6 kb/s codec, on the device, bit-identical to the reference's generic-C float build:
+ *   lpcnet_batch_encode*            lpcnet_encode (src/lpcnet_enc.c:882) per stream and packet:
+ *                                   pcm [n_streams][n_packets*640] -> packets [n_streams][n_packets][8], what lpcnet_batch_decode* reads
+ *   lpcnet_batch_compute_features*  lpcnet_compute_features (:895; process_superframe with encode = 0, quantize = 0):
+ *                                   pcm [n_streams][n_packets*640] -> features [n_streams][n_packets*4][feat_stride], feat_stride >= 36
+ * analyze, encode and compute_features act on the SAME per-stream analysis state, as the reference's three entry points act on one
+ * LPCNetEncState, and may be interleaved on a stream: encode and compute_features in any order, and analyze followed by either, give the
+ * reference's result.  One quirk of the reference is not reproduced: lpcnet_compute_single_frame_features never sets pcount, so after a
+ * four-frame call (pcount left at 3) it analyses into features[3] and returns the stale features[0]; lpcnet_batch_analyze keeps behaving
+ * as with pcount = 0.  The state evolves identically either way (no carried field depends on the slot), so a four-frame call after such
+ * an analyze equals the reference again.
+ * The encoder's one further carried field, vq_mem[18], is kept beside the analysis state (all zero when allocated):
+ * lpcnet_batch_analysis_reset (lpcnet_encoder_init) clears it as well, lpcnet_batch_reset touches neither; a snapshot of a stream is its
+ * analysis state plus its vq_mem.
+ * Codebooks: as for lpcnet_batch_decode (lpcnet_hip_set_codebooks or the default file); without them encode returns what decode returns.
+ * compute_features needs none.  A batch without a model returns LPCNET_HIP_E_MODEL.  Host-pointer calls copy in, run, copy out and
+ * synchronise (one host thread per shard); device-pointer calls only enqueue on `hip_stream` (NULL = the batch's own) under the ordering
+ * and capture rules of lpcnet_batch_analyze_device: on a stream that is being captured nothing is executed, allocated or synchronised,
+ * so lpcnet_batch_encoder_enable(max_packets) (state, vq_mem and scratch for calls of up to max_packets packets; implies
+ * lpcnet_batch_analysis_enable(4 * max_packets)) or an earlier eager call of that length must come first: otherwise LPCNET_HIP_E_ARG. */
+LPCNET_EXPORT int lpcnet_batch_encode(LPCNetBatch *b, const short *pcm, unsigned char *packets, int n_packets);
+LPCNET_EXPORT int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_encode_device_shard(LPCNetBatch *b, int shard, const short *d_pcm, unsigned char *d_packets, int n_packets,
+                                                   void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_packets);
+LPCNET_EXPORT int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int feat_stride, int n_packets,
+                                                       void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_encoder_enable(LPCNetBatch *b, int max_packets);
+LPCNET_EXPORT int lpcnet_batch_get_encoder_vq_mem(LPCNetBatch *b, int stream, float *out18);
+LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in18);
+
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);
 LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st);

@@ -106,6 +106,14 @@ def load_library():
     L.lpcnet_batch_analysis_reset.argtypes = [vp, C.c_int, C.c_int]
     L.lpcnet_batch_get_analysis_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_analysis_state.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
+    L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    L.lpcnet_batch_compute_features.argtypes = [vp, _i16p, _f32p, C.c_int, C.c_int]
+    L.lpcnet_batch_compute_features_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
+    L.lpcnet_batch_encoder_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_get_encoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_set_encoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
     L.lpcnet_batch_export_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_import_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_streams_per_workgroup.argtypes = [vp, C.c_int]
@@ -418,6 +426,49 @@ class LPCNetBatch:
     def set_analysis_state(self, stream: int, raw: bytes):
         assert len(raw) == self.L.lpcnet_batch_analysis_state_size()
         self._chk(self.L.lpcnet_batch_set_analysis_state(self.p, stream, C.create_string_buffer(raw, len(raw))), "set_analysis_state")
+
+    def encode(self, pcm: np.ndarray) -> np.ndarray:
+        """pcm (n, P*640) int16 -> packets (n, P, 8) uint8: lpcnet_encode per stream and packet (codebooks: set_codebooks)"""
+        pcm = np.asarray(pcm)
+        n, ns = pcm.shape
+        assert n == self.n and ns % 640 == 0 and ns > 0 and pcm.dtype == np.int16
+        P = ns // 640
+        packets = np.zeros((n, P, 8), np.uint8)
+        self._chk(self.L.lpcnet_batch_encode(self.p, np.ascontiguousarray(pcm).reshape(-1), packets.reshape(-1), P), "encode")
+        return packets
+
+    def encode_device(self, d_pcm_ptr: int, d_packets_ptr: int, n_packets: int, hip_stream: int = 0):
+        self._chk(self.L.lpcnet_batch_encode_device(self.p, d_pcm_ptr, d_packets_ptr, n_packets, hip_stream or None), "encode_device")
+
+    def encode_device_shard(self, shard: int, d_pcm_ptr: int, d_packets_ptr: int, n_packets: int, hip_stream: int = 0):
+        self._chk(self.L.lpcnet_batch_encode_device_shard(self.p, shard, d_pcm_ptr, d_packets_ptr, n_packets, hip_stream or None), "encode_device_shard")
+
+    def compute_features(self, pcm: np.ndarray) -> np.ndarray:
+        """pcm (n, P*640) int16 -> features (n, 4P, 36) float32: lpcnet_compute_features per stream and packet"""
+        pcm = np.asarray(pcm)
+        n, ns = pcm.shape
+        assert n == self.n and ns % 640 == 0 and ns > 0 and pcm.dtype == np.int16
+        P = ns // 640
+        feat = np.zeros((n, 4 * P, NB_TOTAL_FEATURES), np.float32)
+        self._chk(self.L.lpcnet_batch_compute_features(self.p, np.ascontiguousarray(pcm).reshape(-1), feat.reshape(-1), NB_TOTAL_FEATURES, P), "compute_features")
+        return feat
+
+    def compute_features_device(self, d_pcm_ptr: int, d_features_ptr: int, stride: int, n_packets: int, hip_stream: int = 0):
+        self._chk(self.L.lpcnet_batch_compute_features_device(self.p, d_pcm_ptr, d_features_ptr, stride, n_packets, hip_stream or None), "compute_features_device")
+
+    def encoder_enable(self, max_packets: int = 1):
+        """allocate the analysis state, the encoder's vq_mem and the scratch for calls of up to max_packets packets (needed before a graph capture)"""
+        self._chk(self.L.lpcnet_batch_encoder_enable(self.p, max_packets), "encoder_enable")
+
+    def get_encoder_vq_mem(self, stream: int) -> np.ndarray:
+        out = np.zeros(18, np.float32)
+        self._chk(self.L.lpcnet_batch_get_encoder_vq_mem(self.p, stream, out), "get_encoder_vq_mem")
+        return out
+
+    def set_encoder_vq_mem(self, stream: int, mem: np.ndarray):
+        mem = np.ascontiguousarray(mem, np.float32)
+        assert mem.shape == (18,)
+        self._chk(self.L.lpcnet_batch_set_encoder_vq_mem(self.p, stream, mem), "set_encoder_vq_mem")
 
     def set_lpc_gamma(self, gamma: float):
         self._chk(self.L.lpcnet_batch_set_lpc_gamma(self.p, gamma), "set_lpc_gamma")

@@ -11,6 +11,8 @@
 //                             the backward pass -> [18], [19]; the ONLY writer of the per-stream state
 // The first two read the state and the call's PCM only, so every (stream, frame) of a chunk is independent: a frame depends on earlier
 // frames through input samples and through the previous frame's residual (`pitch_filt`), which the second kernel picks up from resid.
+// The first two kernels, the pitch search's half-frame step (an_viterbi_step) and the state hand-over (an_store_state) also serve the
+// four-frame encoder (encode_kernels.hip.h): compute_frame_features is one function for both paths in the reference.
 #pragma once
 #include "lpcnet_log10.h"
 
@@ -210,6 +212,92 @@ __global__ __launch_bounds__(AN_XC_THREADS) void analysis_xcorr_kernel(int n_fra
     }
 }
 
+// One half-frame of the pitch search, the same in process_single_frame (src/lpcnet_enc.c:828-852) and process_superframe (:622-646):
+// the *= .8f pass on the half-frame's cross-correlation (lane i holds lag i, `v`), one Viterbi step over the 224 pitch candidates with
+// weight `fw`, renormalisation.  Leaves the modified cross-correlation in xcw[256], the predecessors in prevs[224], the new path
+// scores in pmp[224] and (max_path_all, best_i) in pmpa / best_i.  Called by all AN_PITCH_THREADS lanes of the workgroup.
+__device__ __forceinline__ void an_viterbi_step(const int i, float v, const float fw, float *xcw, short *prevs, float *pmp, float *red_v, int *red_i,
+                                                float &pmpa, int &best_i)
+{
+    xcw[i] = v;
+    __syncthreads();
+    // the *= .8f pass reads only entries above the one it writes ((255 + i)/2 > i for i < 192): parallel
+    if (i < LPCN_PITCH_MAX_PERIOD - 2 * LPCN_PITCH_MIN_PERIOD) {
+        const float a = xcw[(LPCN_PITCH_MAX_PERIOD + i) / 2], b = xcw[(LPCN_PITCH_MAX_PERIOD + i + 2) / 2];
+        const float c = xcw[(LPCN_PITCH_MAX_PERIOD + i - 1) / 2];
+        const float ab = LPCN_MAX16(a, b);
+        const float xc_half = LPCN_MAX16(ab, c);
+        if (v < xc_half * 1.1f) v = v * .8f;
+    }
+    __syncthreads();
+    xcw[i] = v;
+    // 9 neighbours from -4 upwards, strict >
+    float nv = -1e15f;
+    if (i < AN_PATHS) {
+        float max_prev = pmpa - 6.f;
+        int pp = best_i;
+#pragma unroll
+        for (int j = -4; j <= 4; ++j) {
+            if (i + j >= 0 && i + j < AN_PATHS) {
+                const int aj = j < 0 ? -j : j;
+                const float cand = pmp[i + j] - (.02f * (float)aj) * (float)aj;
+                if (cand > max_prev) { max_prev = cand; pp = i + j; }
+            }
+        }
+        prevs[i] = (short)pp;
+        nv = max_prev + fw * v;
+    }
+    // argmax, the lowest index winning ties, starting from (-1e15f, 0)
+    float bv = nv;
+    int bi = i < AN_PATHS ? i : 0x7fffffff;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const float ov = __shfl_xor(bv, d);
+        const int oi = __shfl_xor(bi, d);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if ((i & 63) == 0) { red_v[i >> 6] = bv; red_i[i >> 6] = bi; }
+    __syncthreads();      // (also: every lane has read its pmp neighbours)
+    bv = red_v[0]; bi = red_i[0];
+#pragma unroll
+    for (int k = 1; k < AN_PITCH_THREADS / 64; ++k) {
+        const float ov = red_v[k];
+        const int oi = red_i[k];
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (!(bv > -1e15f)) { bv = -1e15f; bi = 0; }
+    if (i < AN_PATHS) pmp[i] = nv - bv;        // renormalise
+    pmpa = bv;
+    best_i = bi;
+    __syncthreads();
+}
+
+// The state after T frames of the chunk (what compute_frame_features leaves behind, plus the path scores): everything is read into
+// registers before anything is written.  amb: LPCN_AN_OVERLAP floats of LDS.
+__device__ __forceinline__ void an_store_state(const int i, const int T, const void *pcm, const int is_float, const size_t base, const float *r,
+                                               lpcn_analysis_state *st, const float *pmp, float *amb, const float pmpa, const int best_i)
+{
+    float e0 = 0.f, e1 = 0.f, am = 0.f;
+    e0 = an_exc(r, T * LPCN_FRAME_SIZE - AN_HIST + i, st);
+    if (i + AN_PITCH_THREADS < AN_HIST) e1 = an_exc(r, T * LPCN_FRAME_SIZE - AN_HIST + i + AN_PITCH_THREADS, st);
+    if (i < LPCN_AN_OVERLAP) am = an_preemph(pcm, is_float, base, (T - 1) * LPCN_FRAME_SIZE + i, st);
+    const float last_x = an_pcm(pcm, is_float, base + (size_t)T * LPCN_FRAME_SIZE - 1);
+    const float last_sum = r[T * LPCN_FRAME_SIZE - 1];
+    if (i < LPCN_AN_OVERLAP) amb[i] = am;
+    __syncthreads();
+    st->exc_buf[i] = e0;
+    if (i + AN_PITCH_THREADS < AN_HIST) st->exc_buf[i + AN_PITCH_THREADS] = e1;
+    if (i < LPCN_AN_OVERLAP) st->analysis_mem[i] = am;
+    if (i < LPCN_LPC_ORDER) st->pitch_mem[i] = amb[LPCN_AN_OVERLAP - LPCN_AN_TRAINING_OFFSET - 1 - i];
+    if (i < AN_PATHS) st->pitch_max_path[i] = pmp[i];
+    if (i == 0) {
+        st->mem_preemph = -(0.85f * last_x);
+        st->pitch_filt = last_sum;
+        st->pitch_max_path_all = pmpa;
+        st->best_i = best_i;
+    }
+}
+
 // process_single_frame (src/lpcnet_enc.c:814-870) for every frame of the chunk, and the state the next chunk starts from
 __global__ __launch_bounds__(AN_PITCH_THREADS) void analysis_pitch_kernel(int n_frames, const void *pcm, int is_float, size_t pcm_stream_stride,
                                                                           lpcn_analysis_state *states, const float *resid, const float *xc_in,
@@ -237,60 +325,8 @@ __global__ __launch_bounds__(AN_PITCH_THREADS) void analysis_pitch_kernel(int n_
         fsum = fsum + fw_in[item * 2 + 1];
         const float scale = 2.f / fsum;
         const float fw0 = fw_in[item * 2] * scale, fw1 = fw_in[item * 2 + 1] * scale;
-        for (int sub = 0; sub < 2; ++sub) {
-            float v = xc_in[(item * 2 + sub) * LPCN_PITCH_MAX_PERIOD + i];
-            xcw[sub][i] = v;
-            __syncthreads();
-            // the *= .8f pass (:828-831) reads only entries above the one it writes ((255 + i)/2 > i for i < 192): parallel
-            if (i < LPCN_PITCH_MAX_PERIOD - 2 * LPCN_PITCH_MIN_PERIOD) {
-                const float a = xcw[sub][(LPCN_PITCH_MAX_PERIOD + i) / 2], b = xcw[sub][(LPCN_PITCH_MAX_PERIOD + i + 2) / 2];
-                const float c = xcw[sub][(LPCN_PITCH_MAX_PERIOD + i - 1) / 2];
-                const float ab = LPCN_MAX16(a, b);
-                const float xc_half = LPCN_MAX16(ab, c);
-                if (v < xc_half * 1.1f) v = v * .8f;
-            }
-            __syncthreads();
-            xcw[sub][i] = v;
-            // one Viterbi step over the 224 pitch candidates (:832-847): 9 neighbours from -4 upwards, strict >
-            float nv = -1e15f;
-            if (i < AN_PATHS) {
-                float max_prev = pmpa - 6.f;
-                int pp = best_i;
-#pragma unroll
-                for (int j = -4; j <= 4; ++j) {
-                    if (i + j >= 0 && i + j < AN_PATHS) {
-                        const int aj = j < 0 ? -j : j;
-                        const float cand = pmp[i + j] - (.02f * (float)aj) * (float)aj;
-                        if (cand > max_prev) { max_prev = cand; pp = i + j; }
-                    }
-                }
-                prevs[sub][i] = (short)pp;
-                nv = max_prev + (sub ? fw1 : fw0) * v;
-            }
-            // argmax, the lowest index winning ties, starting from (-1e15f, 0) (:825-826, :843-846)
-            float bv = nv;
-            int bi = i < AN_PATHS ? i : 0x7fffffff;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const float ov = __shfl_xor(bv, d);
-                const int oi = __shfl_xor(bi, d);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if ((i & 63) == 0) { red_v[i >> 6] = bv; red_i[i >> 6] = bi; }
-            __syncthreads();      // (also: every lane has read its pmp neighbours)
-            bv = red_v[0]; bi = red_i[0];
-#pragma unroll
-            for (int k = 1; k < AN_PITCH_THREADS / 64; ++k) {
-                const float ov = red_v[k];
-                const int oi = red_i[k];
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if (!(bv > -1e15f)) { bv = -1e15f; bi = 0; }
-            if (i < AN_PATHS) pmp[i] = nv - bv;        // renormalise (:849)
-            pmpa = bv;
-            best_i = bi;
-            __syncthreads();
-        }
+        for (int sub = 0; sub < 2; ++sub)
+            an_viterbi_step(i, xc_in[(item * 2 + sub) * LPCN_PITCH_MAX_PERIOD + i], sub ? fw1 : fw0, xcw[sub], prevs[sub], pmp, red_v, red_i, pmpa, best_i);
         // backward pass (:858-866)
         if (i == 0) {
             int b = best_i;
@@ -309,28 +345,8 @@ __global__ __launch_bounds__(AN_PITCH_THREADS) void analysis_pitch_kernel(int n_
         }
         __syncthreads();
     }
-    // the state after the chunk: everything is read into registers before anything is written
-    const int T = n_frames;
-    float e0 = 0.f, e1 = 0.f, am = 0.f;
-    e0 = an_exc(r, T * LPCN_FRAME_SIZE - AN_HIST + i, st);
-    if (i + AN_PITCH_THREADS < AN_HIST) e1 = an_exc(r, T * LPCN_FRAME_SIZE - AN_HIST + i + AN_PITCH_THREADS, st);
-    if (i < LPCN_AN_OVERLAP) am = an_preemph(pcm, is_float, base, (T - 1) * LPCN_FRAME_SIZE + i, st);
-    const float last_x = an_pcm(pcm, is_float, base + (size_t)T * LPCN_FRAME_SIZE - 1);
-    const float last_sum = r[T * LPCN_FRAME_SIZE - 1];
     __shared__ float amb[LPCN_AN_OVERLAP];
-    if (i < LPCN_AN_OVERLAP) amb[i] = am;
-    __syncthreads();
-    st->exc_buf[i] = e0;
-    if (i + AN_PITCH_THREADS < AN_HIST) st->exc_buf[i + AN_PITCH_THREADS] = e1;
-    if (i < LPCN_AN_OVERLAP) st->analysis_mem[i] = am;
-    if (i < LPCN_LPC_ORDER) st->pitch_mem[i] = amb[LPCN_AN_OVERLAP - LPCN_AN_TRAINING_OFFSET - 1 - i];
-    if (i < AN_PATHS) st->pitch_max_path[i] = pmp[i];
-    if (i == 0) {
-        st->mem_preemph = -(0.85f * last_x);
-        st->pitch_filt = last_sum;
-        st->pitch_max_path_all = pmpa;
-        st->best_i = best_i;
-    }
+    an_store_state(i, n_frames, pcm, is_float, base, r, st, pmp, amb, pmpa, best_i);
 }
 
 }  // namespace lpcn

@@ -1063,10 +1063,11 @@ int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
  * device and stream; with a single shard the work runs on the calling thread. */
 typedef struct {
     LPCNetBatch *b; int shard;
-    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze */
+    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze, 3 encode, 4 compute_features */
     const float *features; int feat_stride; short *pcm; int n_frames, preload;
     const void *an_pcm; int an_is_float; float *an_features;
     const unsigned char *packets; int n_packets;
+    unsigned char *enc_packets;
     int rc; char err[256];
 } shard_job;
 
@@ -1081,6 +1082,10 @@ static void *shard_worker(void *arg)
         const size_t o = (size_t)s->first * j->n_frames * LPCN_FRAME_SIZE;
         j->rc = lpcn_batch_dev_analyze_host(s->dev, j->an_is_float ? (const void *)((const float *)j->an_pcm + o) : (const void *)((const short *)j->an_pcm + o),
                                             j->an_is_float, j->an_features + (size_t)s->first * j->n_frames * j->feat_stride, j->feat_stride, j->n_frames);
+    } else if (j->kind == 3 || j->kind == 4) {
+        const size_t o = (size_t)s->first * j->n_packets;
+        j->rc = lpcn_batch_dev_encode_host(s->dev, (const short *)j->an_pcm + o * 4 * LPCN_FRAME_SIZE, j->kind == 3 ? j->enc_packets + o * 8 : NULL,
+                                           j->kind == 4 ? j->an_features + o * 4 * j->feat_stride : NULL, j->feat_stride, j->n_packets);
     } else
         j->rc = lpcn_batch_dev_decode_host(s->dev, j->packets + (size_t)s->first * j->n_packets * 8,
                                            j->pcm + (size_t)s->first * j->n_packets * 4 * LPCN_FRAME_SIZE, j->n_packets);
@@ -1315,6 +1320,70 @@ int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, const void *in)
     if (!in) { set_err("lpcnet_batch_set_analysis_state: bad arguments"); return LPCN_E_ARG; }
     SHARD_OF(s, b, stream);
     FWD(lpcn_batch_dev_set_analysis_state(s->dev, stream - s->first, (const lpcn_analysis_state *)in));
+}
+
+/* ---- encoder (lpcnet_encode / lpcnet_compute_features per stream and packet; include/lpcnet_batch.h) ---- */
+int lpcnet_batch_encode(LPCNetBatch *b, const short *pcm, unsigned char *packets, int n_packets)
+{
+    NEED_MODEL(b);
+    if (!pcm || !packets || n_packets < 1) { set_err("lpcnet_batch_encode: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    shard_job j;
+    memset(&j, 0, sizeof(j));
+    j.kind = 3; j.an_pcm = pcm; j.enc_packets = packets; j.n_packets = n_packets;
+    return run_shards(b, &j);
+}
+int lpcnet_batch_encode_device_shard(LPCNetBatch *b, int shard, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    if (!d_pcm || !d_packets || n_packets < 1) { set_err("lpcnet_batch_encode_device: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    FWD(lpcn_batch_dev_encode(b->sh[shard].dev, d_pcm, d_packets, n_packets, hip_stream));
+}
+int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_encode_device");
+    return lpcnet_batch_encode_device_shard(b, 0, d_pcm, d_packets, n_packets, hip_stream);
+}
+int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_packets)
+{
+    NEED_MODEL(b);
+    if (!pcm || !features || n_packets < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_compute_features: bad arguments"); return LPCN_E_ARG; }
+    shard_job j;
+    memset(&j, 0, sizeof(j));
+    j.kind = 4; j.an_pcm = pcm; j.an_features = features; j.feat_stride = feat_stride; j.n_packets = n_packets;
+    return run_shards(b, &j);
+}
+int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int feat_stride, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_compute_features_device");
+    if (!d_pcm || !d_features || n_packets < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_compute_features_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_compute_features(b->sh[0].dev, d_pcm, d_features, feat_stride, n_packets, hip_stream));
+}
+int lpcnet_batch_encoder_enable(LPCNetBatch *b, int max_packets)
+{
+    NEED_MODEL(b);
+    for (int k = 0; k < b->n_shards; k++) { int rc = lpcn_batch_dev_encoder_enable(b->sh[k].dev, max_packets); if (rc) { take_engine_err(); return rc; } }
+    return 0;
+}
+int lpcnet_batch_get_encoder_vq_mem(LPCNetBatch *b, int stream, float *out18)
+{
+    NEED_MODEL(b);
+    if (!out18) { set_err("lpcnet_batch_get_encoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_get_encoder_vq_mem(s->dev, stream - s->first, out18));
+}
+int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in18)
+{
+    NEED_MODEL(b);
+    if (!in18) { set_err("lpcnet_batch_set_encoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_set_encoder_vq_mem(s->dev, stream - s->first, in18));
 }
 
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }

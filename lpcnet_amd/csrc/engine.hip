@@ -12,6 +12,7 @@
 #include "frame_kernels.hip.h"
 #include "decode_kernel.hip.h"
 #include "analysis_kernels.hip.h"
+#include "encode_kernels.hip.h"
 #include <math.h>
 
 static thread_local char g_err[512] = "";
@@ -55,6 +56,7 @@ struct lpcn_engine {
     LpcnFrameModel fmodel{};
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
+    lpcn::EncodeTables enc{};      // encoder: the same codebooks and their transposed copies, refreshed together
 };
 
 struct lpcn_batch_dev {
@@ -76,6 +78,10 @@ struct lpcn_batch_dev {
     void *d_an_pcm = nullptr;          //   ... and the staging of host-pointer calls (PCM in, features out)
     float *d_an_feat = nullptr;
     size_t an_pcm_cap = 0, an_feat_cap = 0;
+    float *d_enc_vq_mem = nullptr;     // encoder (lpcn_batch_dev_encoder_enable): [n][18] vq_mem of LPCNetEncState, beside the analysis state
+    float *d_enc_feat = nullptr, *d_enc_qf3 = nullptr;   //   ... scratch of enc_chunk packets per launch: cepstrum / LPC rows, quantised frame 3 (+ the entry vq_mem)
+    int *d_enc_pk = nullptr;           //   ... and the packets' bit fields
+    int enc_chunk = 0;
     lpcn_stream_state *d_state_tmp = nullptr;   // per-stream-arguments step (lpcn_batch_dev_step_host): the compacted group's states
     int *d_map = nullptr;              //   ... and its stream indices
     float *d_keep_a = nullptr, *d_keep_b = nullptr, *d_keep_lpc = nullptr;   //   ... and every stream's most recent frame products
@@ -335,8 +341,18 @@ extern "C" int lpcn_engine_set_codebooks(lpcn_engine *e, const float *cb1, const
     int rc = 0;
     float pitch[64];
     for (int k = 0; k < 64; ++k) pitch[k] = (float)(pow(2.f, k / 21.) * 32);      // src/lpcnet_dec.c:107 (PITCH_MIN_PERIOD 32)
+    // the encoder's searches read [dimension][entry]; ceps_codebook_diff4 by quarters of 1024 entries (encode_kernels.hip.h)
+    std::vector<float> t1(17 * 1024), t2(17 * 1024), t3(17 * 1024), td(18 * 4096);
+    for (int i = 0; i < 1024; ++i)
+        for (int j = 0; j < 17; ++j) { t1[j * 1024 + i] = cb1[i * 17 + j]; t2[j * 1024 + i] = cb2[i * 17 + j]; t3[j * 1024 + i] = cb3[i * 17 + j]; }
+    for (int i = 0; i < 4096; ++i)
+        for (int j = 0; j < 18; ++j) td[((size_t)(i >> 10) * 18 + j) * 1024 + (i & 1023)] = cb_diff4[i * 18 + j];
     if (e->has_codebooks) {            // a newer codebook version replaces the contents of the buffers already on the device
         HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpy((void *)e->enc.cb1_t, t1.data(), sizeof(float) * t1.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((void *)e->enc.cb2_t, t2.data(), sizeof(float) * t2.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((void *)e->enc.cb3_t, t3.data(), sizeof(float) * t3.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((void *)e->enc.cbd_t, td.data(), sizeof(float) * td.size(), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy((void *)e->dec.cb1, cb1, sizeof(float) * 1024 * 17, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy((void *)e->dec.cb2, cb2, sizeof(float) * 1024 * 17, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy((void *)e->dec.cb3, cb3, sizeof(float) * 1024 * 17, hipMemcpyHostToDevice));
@@ -348,6 +364,11 @@ extern "C" int lpcn_engine_set_codebooks(lpcn_engine *e, const float *cb1, const
     if ((rc = upload<float>(e, &e->dec.cb3, cb3, 1024 * 17))) return rc;
     if ((rc = upload<float>(e, &e->dec.cb_diff4, cb_diff4, 4096 * 18))) return rc;
     if ((rc = upload<float>(e, &e->dec.pitch, pitch, 64))) return rc;
+    if ((rc = upload<float>(e, &e->enc.cb1_t, t1.data(), t1.size()))) return rc;
+    if ((rc = upload<float>(e, &e->enc.cb2_t, t2.data(), t2.size()))) return rc;
+    if ((rc = upload<float>(e, &e->enc.cb3_t, t3.data(), t3.size()))) return rc;
+    if ((rc = upload<float>(e, &e->enc.cbd_t, td.data(), td.size()))) return rc;
+    e->enc.cb1 = e->dec.cb1; e->enc.cb2 = e->dec.cb2; e->enc.cb3 = e->dec.cb3; e->enc.cb_diff4 = e->dec.cb_diff4;
     e->has_codebooks = true;
     return 0;
 }
@@ -466,7 +487,8 @@ extern "C" void lpcn_batch_dev_destroy(lpcn_batch_dev *b)
     if (b->ev_last) (void)hipEventDestroy(b->ev_last);
     void *ptrs[] = {b->d_state, b->d_fc_base, b->d_cond_a, b->d_cond_b, b->d_lpc, b->d_cond, b->d_feat, b->d_pcm, b->d_args, b->d_dbg, b->d_prof,
                     b->d_vq_mem, b->d_packets, b->d_state_tmp, b->d_map, b->d_keep_a, b->d_keep_b, b->d_keep_lpc,
-                    b->d_an_state, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_an_pcm, b->d_an_feat};
+                    b->d_an_state, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_an_pcm, b->d_an_feat,
+                    b->d_enc_vq_mem, b->d_enc_feat, b->d_enc_qf3, b->d_enc_pk};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &ev : b->ev) if (ev) (void)hipEventDestroy(ev);
     delete b;
@@ -925,20 +947,26 @@ extern "C" int lpcn_batch_dev_decode(lpcn_batch_dev *b, const unsigned char *d_p
     return decode_impl(b, d_packets, d_pcm, n_packets, hip_stream, false);
 }
 
+// packet staging of the host-pointer codec calls (decode: in, encode: out)
+static int ensure_packets(lpcn_batch_dev *b, size_t nbytes)
+{
+    if (nbytes <= b->packets_cap) return 0;
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (b->d_packets) (void)hipFree(b->d_packets);
+    b->d_packets = nullptr; b->packets_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_packets, nbytes));
+    b->packets_cap = nbytes;
+    return 0;
+}
+
 extern "C" int lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char *packets, short *pcm, int n_packets)
 {
     if (n_packets <= 0) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     const size_t nbytes = (size_t)b->n * n_packets * 8, npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE;
-    if (nbytes > b->packets_cap) {
-        { int rcw = wait_all(b); if (rcw) return rcw; }
-        if (b->d_packets) (void)hipFree(b->d_packets);
-        b->d_packets = nullptr; b->packets_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_packets, nbytes));
-        b->packets_cap = nbytes;
-    }
-    int rc = ensure_staging(b, 0, npcm);
+    int rc = ensure_packets(b, nbytes);
     if (rc) return rc;
+    if ((rc = ensure_staging(b, 0, npcm))) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
     HIP_TRY(hipMemcpyAsync(b->d_packets, packets, nbytes, hipMemcpyHostToDevice, st));
@@ -959,11 +987,9 @@ static int analysis_chunk_for(const lpcn_batch_dev *b, int n_frames)
     return n_frames < cap ? n_frames : cap;
 }
 
-extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
+// the analysis state (if absent) and the kernels' scratch for `chunk` frames per launch
+static int analysis_alloc(lpcn_batch_dev *b, int chunk)
 {
-    if (max_frames < 1) { snprintf(g_err, sizeof(g_err), "analysis: bad frame count"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    const int chunk = analysis_chunk_for(b, max_frames);
     if (b->d_an_state && chunk <= b->an_chunk) return 0;
     { int rcw = wait_all(b); if (rcw) return rcw; }      // the old scratch may still be in use
     if (!b->d_an_state) {
@@ -980,6 +1006,12 @@ extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
         b->an_chunk = chunk;
     }
     return 0;
+}
+extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
+{
+    if (max_frames < 1) { snprintf(g_err, sizeof(g_err), "analysis: bad frame count"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    return analysis_alloc(b, analysis_chunk_for(b, max_frames));
 }
 
 extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
@@ -1009,12 +1041,9 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
     return order_end(b, st);
 }
 
-extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames)
+// staging of the host-pointer analysis / encoder calls: npcm bytes of PCM in, nfeat floats of features out
+static int ensure_analysis_staging(lpcn_batch_dev *b, size_t npcm, size_t nfeat)
 {
-    if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));
-    const size_t nfeat = (size_t)b->n * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
     if (npcm > b->an_pcm_cap || nfeat > b->an_feat_cap) { int rcw = wait_all(b); if (rcw) return rcw; }
     if (npcm > b->an_pcm_cap) {
         if (b->d_an_pcm) (void)hipFree(b->d_an_pcm);
@@ -1028,8 +1057,18 @@ extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, i
         HIP_TRY(hipMalloc((void **)&b->d_an_feat, nfeat * sizeof(float)));
         b->an_feat_cap = nfeat;
     }
-    int rc = lpcn_batch_dev_analysis_enable(b, n_frames);
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames)
+{
+    if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));
+    const size_t nfeat = (size_t)b->n * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
+    int rc = ensure_analysis_staging(b, npcm, nfeat);
     if (rc) return rc;
+    if ((rc = lpcn_batch_dev_analysis_enable(b, n_frames))) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
     HIP_TRY(hipMemcpyAsync(b->d_an_pcm, pcm, npcm, hipMemcpyHostToDevice, st));
@@ -1048,6 +1087,7 @@ extern "C" int lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int c
     if (!b->d_an_state) return lpcn_batch_dev_analysis_enable(b, 1);      // (a fresh state IS the reset state)
     { int rcw = wait_all(b); if (rcw) return rcw; }
     if (count) HIP_TRY(hipMemset(b->d_an_state + first, 0, sizeof(lpcn_analysis_state) * (size_t)count));
+    if (count && b->d_enc_vq_mem) HIP_TRY(hipMemset(b->d_enc_vq_mem + (size_t)first * LPCN_NB_BANDS, 0, sizeof(float) * LPCN_NB_BANDS * (size_t)count));
     return 0;
 }
 extern "C" int lpcn_batch_dev_get_analysis_state(lpcn_batch_dev *b, int s, lpcn_analysis_state *host)
@@ -1066,6 +1106,140 @@ extern "C" int lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int s, const
     if (!b->d_an_state) { int rc = lpcn_batch_dev_analysis_enable(b, 1); if (rc) return rc; }
     { int rcw = wait_all(b); if (rcw) return rcw; }
     HIP_TRY(hipMemcpy(b->d_an_state + s, host, sizeof(*host), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- encoder -----
+// lpcnet_encode / lpcnet_compute_features per stream and packet (encode_kernels.hip.h).  A chunk is a whole number of packets within the
+// analysis scratch's item bound (at least one packet, whatever the batch size).
+static int encode_chunk_for(const lpcn_batch_dev *b, int n_packets)
+{
+    int cap = LPCN_AN_ITEMS_MAX / b->n / 4;
+    if (cap < 1) cap = 1;
+    return n_packets < cap ? n_packets : cap;
+}
+
+extern "C" int lpcn_batch_dev_encoder_enable(lpcn_batch_dev *b, int max_packets)
+{
+    if (max_packets < 1) { snprintf(g_err, sizeof(g_err), "encoder: bad packet count"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    const int chunk = encode_chunk_for(b, max_packets);
+    int rc = analysis_alloc(b, 4 * chunk);
+    if (rc) return rc;
+    if (b->d_enc_vq_mem && chunk <= b->enc_chunk) return 0;
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (!b->d_enc_vq_mem) {
+        HIP_TRY(hipMalloc((void **)&b->d_enc_vq_mem, sizeof(float) * LPCN_NB_BANDS * (size_t)b->n));
+        HIP_TRY(hipMemset(b->d_enc_vq_mem, 0, sizeof(float) * LPCN_NB_BANDS * (size_t)b->n));
+    }
+    if (chunk > b->enc_chunk) {
+        if (b->d_enc_feat) (void)hipFree(b->d_enc_feat);
+        if (b->d_enc_qf3) (void)hipFree(b->d_enc_qf3);
+        if (b->d_enc_pk) (void)hipFree(b->d_enc_pk);
+        b->d_enc_feat = b->d_enc_qf3 = nullptr; b->d_enc_pk = nullptr; b->enc_chunk = 0;
+        const size_t items = (size_t)b->n * chunk;
+        HIP_TRY(hipMalloc((void **)&b->d_enc_feat, sizeof(float) * items * 4 * LPCN_AN_NB_FEATURES));
+        HIP_TRY(hipMalloc((void **)&b->d_enc_qf3, sizeof(float) * (size_t)b->n * (chunk + 1) * LPCN_NB_BANDS));
+        HIP_TRY(hipMalloc((void **)&b->d_enc_pk, sizeof(int) * items * lpcn::ENC_PK));
+        b->enc_chunk = chunk;
+    }
+    return 0;
+}
+
+// d_packets != NULL: encode; else compute_features into d_features
+static int encode_impl(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_packets, float *d_features, int feat_stride, int n_packets, void *hip_stream)
+{
+    if (!d_pcm || (!d_packets && !d_features) || n_packets < 1 || (!d_packets && feat_stride < LPCN_AN_NB_FEATURES)) {
+        snprintf(g_err, sizeof(g_err), "bad encoder arguments");
+        return LPCN_E_ARG;
+    }
+    if (d_packets && !b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    DeviceGuard guard(b->e->device);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
+    const int want = encode_chunk_for(b, n_packets);
+    if (!b->d_an_state || !b->d_enc_vq_mem || want > b->enc_chunk || 4 * want > b->an_chunk) {
+        if (stream_is_capturing(st)) {      // (a capture executes nothing and allocates nothing)
+            snprintf(g_err, sizeof(g_err), "encoder state / scratch for %d packets per call must exist before a capture: call lpcnet_batch_encoder_enable first", n_packets);
+            return LPCN_E_ARG;
+        }
+        int rc = lpcn_batch_dev_encoder_enable(b, n_packets);
+        if (rc) return rc;
+    }
+    { int rco = order_begin(b, st); if (rco) return rco; }
+    const int chunk = b->enc_chunk < b->an_chunk / 4 ? b->enc_chunk : b->an_chunk / 4;
+    const size_t pcm_stride = (size_t)n_packets * 4 * LPCN_FRAME_SIZE;
+    for (int p0 = 0; p0 < n_packets; p0 += chunk) {
+        const int np = n_packets - p0 < chunk ? n_packets - p0 : chunk;
+        const short *p = d_pcm + (size_t)p0 * 4 * LPCN_FRAME_SIZE;
+        int rc;
+        if (d_packets)
+            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->n, np, p, pcm_stride, b->d_an_state, b->d_enc_feat, LPCN_AN_NB_FEATURES,
+                                            (size_t)np * 4 * LPCN_AN_NB_FEATURES, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_enc_vq_mem, b->d_enc_qf3, b->d_enc_pk,
+                                            d_packets + (size_t)p0 * 8, n_packets, g_err, sizeof(g_err));
+        else
+            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->n, np, p, pcm_stride, b->d_an_state, d_features + (size_t)p0 * 4 * feat_stride, feat_stride,
+                                            (size_t)n_packets * 4 * feat_stride, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_enc_vq_mem, b->d_enc_qf3, b->d_enc_pk,
+                                            nullptr, n_packets, g_err, sizeof(g_err));
+        if (rc) return rc;
+    }
+    return order_end(b, st);
+}
+extern "C" int lpcn_batch_dev_encode(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream)
+{
+    if (!d_packets) { snprintf(g_err, sizeof(g_err), "bad encoder arguments"); return LPCN_E_ARG; }
+    return encode_impl(b, d_pcm, d_packets, nullptr, 0, n_packets, hip_stream);
+}
+extern "C" int lpcn_batch_dev_compute_features(lpcn_batch_dev *b, const short *d_pcm, float *d_features, int feat_stride, int n_packets, void *hip_stream)
+{
+    if (!d_features) { snprintf(g_err, sizeof(g_err), "bad encoder arguments"); return LPCN_E_ARG; }
+    return encode_impl(b, d_pcm, nullptr, d_features, feat_stride, n_packets, hip_stream);
+}
+
+// host pointers: copy in, run, copy out, synchronise.  packets != NULL: encode; else compute_features
+extern "C" int lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, unsigned char *packets, float *features, int feat_stride, int n_packets)
+{
+    if (!pcm || (!packets && !features) || n_packets < 1 || (!packets && feat_stride < LPCN_AN_NB_FEATURES)) {
+        snprintf(g_err, sizeof(g_err), "bad encoder arguments");
+        return LPCN_E_ARG;
+    }
+    if (packets && !b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    DeviceGuard guard(b->e->device);
+    const size_t npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE * sizeof(short);
+    const size_t nfeat = packets ? 0 : (size_t)b->n * n_packets * 4 * LPCN_AN_NB_FEATURES, nbytes = packets ? (size_t)b->n * n_packets * 8 : 0;
+    int rc = ensure_analysis_staging(b, npcm, nfeat);
+    if (rc) return rc;
+    if ((rc = ensure_packets(b, nbytes))) return rc;
+    if ((rc = lpcn_batch_dev_encoder_enable(b, n_packets))) return rc;
+    hipStream_t st = b->e->stream;
+    if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
+    HIP_TRY(hipMemcpyAsync(b->d_an_pcm, pcm, npcm, hipMemcpyHostToDevice, st));
+    rc = encode_impl(b, (const short *)b->d_an_pcm, packets ? b->d_packets : nullptr, packets ? nullptr : b->d_an_feat, LPCN_AN_NB_FEATURES, n_packets, st);
+    if (rc) return rc;
+    if (packets)
+        HIP_TRY(hipMemcpyAsync(packets, b->d_packets, nbytes, hipMemcpyDeviceToHost, st));
+    else
+        HIP_TRY(hipMemcpy2DAsync(features, (size_t)feat_stride * sizeof(float), b->d_an_feat, LPCN_AN_NB_FEATURES * sizeof(float),
+                                 LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->n * n_packets * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_get_encoder_vq_mem(lpcn_batch_dev *b, int s, float *out18)
+{
+    if (s < 0 || s >= b->n || !out18) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    if (!b->d_enc_vq_mem) { int rc = lpcn_batch_dev_encoder_enable(b, 1); if (rc) return rc; }
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    HIP_TRY(hipMemcpy(out18, b->d_enc_vq_mem + (size_t)s * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int lpcn_batch_dev_set_encoder_vq_mem(lpcn_batch_dev *b, int s, const float *in18)
+{
+    if (s < 0 || s >= b->n || !in18) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    if (!b->d_enc_vq_mem) { int rc = lpcn_batch_dev_encoder_enable(b, 1); if (rc) return rc; }
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    HIP_TRY(hipMemcpy(b->d_enc_vq_mem + (size_t)s * LPCN_NB_BANDS, in18, sizeof(float) * LPCN_NB_BANDS, hipMemcpyHostToDevice));
     return 0;
 }
 

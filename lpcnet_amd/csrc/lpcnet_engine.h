@@ -129,8 +129,9 @@ typedef struct lpcn_stream_state {
 
 /* ---- per-stream ANALYSIS state (feature extraction, analysis_kernels.hip.h): the fields of the reference's LPCNetEncState
  * (src/lpcnet_private.h:55-75) that lpcnet_compute_single_frame_features reads or writes, in the reference's order; all zero after
- * lpcnet_encoder_init.  Separate from the synthesis state, as LPCNetEncState is from LPCNetState.  An encoder's further fields
- * (xc[10][257], frame_weight[10], vq_mem, ...) are appended after best_i: no field moves. */
+ * lpcnet_encoder_init.  Separate from the synthesis state, as LPCNetEncState is from LPCNetState.  The encoder (encode_kernels.hip.h)
+ * works on this same record; its vq_mem lives in an array of its own and xc[0..1] / frame_weight[0..1] are read by no path, so the
+ * record does not grow. */
 #define LPCN_AN_OVERLAP         160
 #define LPCN_AN_TRAINING_OFFSET 80
 #define LPCN_PITCH_MIN_PERIOD   32
@@ -237,6 +238,18 @@ int  lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_
 int  lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int count);      /* lpcnet_encoder_init */
 int  lpcn_batch_dev_get_analysis_state(lpcn_batch_dev *b, int stream, lpcn_analysis_state *host);
 int  lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int stream, const lpcn_analysis_state *host);
+
+/* Encoder (lpcnet_encode / lpcnet_compute_features per stream and packet, encode_kernels.hip.h): pcm [n_streams][n_packets*640] shorts ->
+ * packets [n_streams][n_packets][8], or features [n_streams][n_packets*4][feat_stride >= 36].  Both act on the analysis state above; the
+ * encoder's one further carried field, vq_mem[18], is a device array of its own ([n_streams][18], zero on allocation, cleared by
+ * lpcn_batch_dev_analysis_reset where it exists).  lpcn_batch_dev_encoder_enable allocates it, the analysis state and the scratch for calls
+ * of up to max_packets packets; capture rules as for the analysis.  _host: packets != NULL encodes, else features are computed. */
+int  lpcn_batch_dev_encoder_enable(lpcn_batch_dev *b, int max_packets);
+int  lpcn_batch_dev_encode(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream);
+int  lpcn_batch_dev_compute_features(lpcn_batch_dev *b, const short *d_pcm, float *d_features, int feat_stride, int n_packets, void *hip_stream);
+int  lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, unsigned char *packets, float *features, int feat_stride, int n_packets);
+int  lpcn_batch_dev_get_encoder_vq_mem(lpcn_batch_dev *b, int stream, float *out18);
+int  lpcn_batch_dev_set_encoder_vq_mem(lpcn_batch_dev *b, int stream, const float *in18);
 
 /* Timing of the most recent run: kernel-only milliseconds measured with HIP events on the
  * stream the kernels were launched on (sample kernel, frame kernels). */

@@ -3,6 +3,7 @@
 
     python tools/kernel_resources.py [--s 4] [--asm-dir DIR] [--json]
     python tools/kernel_resources.py --analysis          (the feature-analysis kernels of engine.hip)
+    python tools/kernel_resources.py --encode            (the encoder kernels of engine.hip)
 
 Compiles lpcnet_amd/csrc/sample_variants.hip for gfx950 to assembly (device only, same flags as lpcnet_amd/build.py),
 then reports per kernel: VGPR / SGPR counts, spill counts, scratch bytes (the .amdhsa metadata), and how many scratch
@@ -115,6 +116,10 @@ def analyse(asm_path):
     return sorted(out, key=lambda r: (r["S"], r["int8"], r["fast"], r["pack2"], r["NW"]))
 
 
+# the encoder kernels: encode_pitch_kernel is a template (ILb0E = compute_features, ILb1E = encode)
+ENCODE_PATTERN = r"N4lpcn\d+(encode_[a-z_]+_kernel(?:ILb[01]E)?)E"
+
+
 def engine_kernel_resources(pattern=r"N4lpcn\d+(analysis_[a-z]+_kernel)E", asm_path=None):
     """Resources of the kernels of engine.hip (frame, decode and ANALYSIS kernels) whose mangled name matches `pattern` (group 1 = the key), from the compiler's
     metadata: {demangled-ish name: dict(vgpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, max_flat_workgroup_size)}.  No GPU needed."""
@@ -151,7 +156,11 @@ def main():
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of engine.hip instead")
+    ap.add_argument("--encode", action="store_true", help="report the encoder kernels of engine.hip (encode_kernels.hip.h) instead")
     a = ap.parse_args()
+    if a.encode:
+        print(json.dumps(engine_kernel_resources(ENCODE_PATTERN, os.path.join(a.asm_dir, "engine.s") if a.asm_dir else None), indent=1))
+        return
     if a.analysis:
         print(json.dumps(engine_kernel_resources(r"N4lpcn\d+(analysis_[a-z]+_kernel|lpc_kernel)E", os.path.join(a.asm_dir, "engine.s") if a.asm_dir else None), indent=1))
         return
