@@ -127,6 +127,10 @@ LPCNET_EXPORT int lpcnet_hip_set_device(int device);
 /* host-only blob validation (no GPU needed): 0 = loadable (float or int8 flavour), -1 = malformed.
  * info (may be NULL) receives {is_int8, GRU-A blocks, GRU-B blocks, items/lane, padded GRU-B blocks, selftest} */
 LPCNET_EXPORT int lpcnet_hip_check_model(const unsigned char *data, int len, int *info);
+/* Host-only view of the twelve-wave image of GRU-A (the two-group sample kernel at three waves per SIMD): 1 = the model has one, 0 = it does not fit
+ * (the other kernels run it), -1 = malformed blob.  desc: [12 waves][5 segments]{kind 0 none / 1 whole / 2 head / 3 tail, first item, items, blocks of
+ * the rows summed before it}; rows: [12][5][64] GRU-A rows (-1 = none); selftest: 0 = consistent with the blob.  Any of the three may be NULL. */
+LPCNET_EXPORT int lpcnet_hip_x3_image_info(const unsigned char *data, int len, int *desc, int *rows, int *selftest);
 /* release every device resource held for the single-stream API (optional, e.g. before exit); states stay bound and
  * re-create the device side at their next call */
 LPCNET_EXPORT void lpcnet_hip_shutdown(void);

@@ -173,6 +173,11 @@ LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LP
 LPCNET_EXPORT int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int s);      /* 1, 2, 4, 8; 0 = auto.  8 = the two-group kernel (float blobs with a dense GRU-B matrix and
                                                                                         * <= 32 GRU-A items per lane, bit-exact arithmetic): chosen automatically beyond four streams per CU */
 LPCNET_EXPORT int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b);
+/* Which form of the two-group kernel runs at eight streams per workgroup: 0 = eight waves (two per SIMD), 1 = twelve waves (three per SIMD; needs the
+ * model's twelve-wave image: an error without it), -1 = as measured / as the table says.  Both forms produce the same bits.  get: what a launch of the
+ * whole batch runs now (0 / 1). */
+LPCNET_EXPORT int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode);
+LPCNET_EXPORT int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b);
 /* Streams per workgroup are measured on the batch itself (PARITY arithmetic; FAST takes a table value so that its output
  * never depends on timing): lpcnet_batch_tune() does it now, on the engine's own stream (~10 ms).  Without it the first
  * host-pointer call measures; the enqueue-only *_device calls on a caller's stream never do (they use the table value). */

@@ -118,6 +118,9 @@ def load_library():
     L.lpcnet_batch_import_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_streams_per_workgroup.argtypes = [vp, C.c_int]
     L.lpcnet_batch_get_streams_per_workgroup.argtypes = [vp]
+    L.lpcnet_batch_set_twelve_waves.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_get_twelve_waves.argtypes = [vp]
+    L.lpcnet_hip_x3_image_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lpcnet_batch_tune.argtypes = [vp]
     L.lpcnet_batch_enable_timing.argtypes = [vp, C.c_int]
     L.lpcnet_batch_last_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -146,6 +149,13 @@ def check_model(blob: bytes):
     info = (C.c_int * 6)()
     rc = load_library().lpcnet_hip_check_model(blob, len(blob), info)
     return rc, list(info)
+
+
+def x3_image_info(blob: bytes):
+    """Host-only view of a blob's twelve-wave image: (have, desc[12][5][4], rows[12][5][64], selftest); see include/lpcnet.h."""
+    desc, rows, st = (C.c_int * (12 * 5 * 4))(), (C.c_int * (12 * 5 * 64))(), C.c_int(-1)
+    have = load_library().lpcnet_hip_x3_image_info(blob, len(blob), desc, rows, C.byref(st))
+    return have, np.array(desc, np.int32).reshape(12, 5, 4), np.array(rows, np.int32).reshape(12, 5, 64), st.value
 
 
 def last_error() -> str:
@@ -526,6 +536,14 @@ class LPCNetBatch:
     @streams_per_workgroup.setter
     def streams_per_workgroup(self, s):
         self._chk(self.L.lpcnet_batch_set_streams_per_workgroup(self.p, s), "set_streams_per_workgroup")
+
+    @property
+    def twelve_waves(self):
+        return self.L.lpcnet_batch_get_twelve_waves(self.p)
+
+    @twelve_waves.setter
+    def twelve_waves(self, mode):
+        self._chk(self.L.lpcnet_batch_set_twelve_waves(self.p, int(mode)), "set_twelve_waves")
 
     def enable_timing(self, on=True):
         self._chk(self.L.lpcnet_batch_enable_timing(self.p, int(on)), "enable_timing")

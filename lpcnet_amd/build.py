@@ -91,8 +91,9 @@ def build(force=False, verbose=True, prof=False):
     for sv in (1, 2, 4):
         jobs.append([HIPCC] + HIP_FLAGS + pf + extra + [f"-DLPCN_S={sv}", "-c", os.path.join(CSRC, "sample_variants.hip"), "-o", os.path.join(objdir, f"sample_s{sv}.o")])
     jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x2.hip"), "-o", os.path.join(objdir, "sample_x2.o")])
+    jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x3.hip"), "-o", os.path.join(objdir, "sample_x3.o")])
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=5) as ex:
+    with ThreadPoolExecutor(max_workers=6) as ex:
         list(ex.map(run, jobs))
     objs += [j[-1] for j in jobs]
     for c in ("api.c", "model_pack.c"):
@@ -111,7 +112,7 @@ def build_small_registry(verbose=False):
     build (tests/test_gpu_wide.py; select with LPCNET_HIP_LIB).  Test artefact, git-ignored like every built library."""
     build(verbose=verbose)
     objdir0 = os.path.join(HERE, "build")
-    needed = ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "model_pack.o")
+    needed = ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o")
     if not all(os.path.exists(os.path.join(objdir0, f)) for f in needed):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
         build(force=True, verbose=verbose)
     lib = LIB.replace(".so", "_smallreg.so")
@@ -122,7 +123,7 @@ def build_small_registry(verbose=False):
     o = os.path.join(objdir, "api_smallreg.o")
     cmds = [["gcc"] + C_FLAGS + ["-DLPCN_MAX_MODELS=4", "-DLPCN_MAX_RESIDENT=2", f'-DLPCN_SOURCE_HASH="{h_src}-smallreg"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"',
                                  "-c", os.path.join(CSRC, "api.c"), "-o", o],
-            [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o")]
+            [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o")]
             + [o, os.path.join(objdir, "model_pack.o"), "-lpthread", "-lm"]]
     for c in cmds:
         if verbose:

@@ -1388,6 +1388,8 @@ int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in1
 
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }
 int lpcnet_batch_tune(LPCNetBatch *b) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_tune(s->dev)); }
+int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x3(s->dev, mode)); }
+int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x3(b->sh[0].dev) : 0; }
 int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_streams_per_wg(b->sh[0].dev) : 0; }
 int lpcnet_batch_enable_timing(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_enable_timing(s->dev, on)); }
 /* kernel milliseconds of the most recent run: the slowest shard */
@@ -1516,8 +1518,40 @@ int lpcnet_hip_check_model(const unsigned char *data, int len, int *info)
             lpcn_model_release(&f);
         }
     }
+    if (!st) {                                           /* the twelve-wave image, where the model fits it (a model that does not is run by the other kernels) */
+        lpcn_x3_image im;
+        if (lpcn_model_pack_x3(&m, &im) == 0) {
+            const int sf = lpcn_x3_image_selftest(&m, &im);
+            if (sf) st = 300 + sf;
+            lpcn_x3_image_release(&im);
+        }
+    }
     if (info) { info[0] = m.is_int8; info[1] = m.nb_a; info[2] = m.nb_b; info[3] = m.nw; info[4] = m.nb_b_padded; info[5] = st; }
     lpcn_model_release(&m);
     if (st) { set_err("internal error: device packing inconsistent with blob"); return -1; }
     return 0;
+}
+
+/* Host-only view of the twelve-wave image of a blob (sample_kernel_x3.hip.h): returns 1 when the model has one, 0 when it does not fit
+ * (int8, block-sparse GRU-B, an update / reset slot of more than 16 items, a candidate slot of more than 32, no room left), -1 for a
+ * malformed blob.  desc (may be NULL) receives [12 waves][5 segments]{kind, first item, items, blocks summed before it}, rows (may be
+ * NULL) [12][5][64] GRU-A rows, selftest (may be NULL) the code of lpcn_x3_image_selftest. */
+int lpcnet_hip_x3_image_info(const unsigned char *data, int len, int *desc, int *rows, int *selftest)
+{
+    lpcn_model_host m;
+    lpcn_x3_image im;
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return -1; }
+    const int have = lpcn_model_pack_x3(&m, &im) == 0;
+    if (have) {
+        if (selftest) *selftest = lpcn_x3_image_selftest(&m, &im);
+        for (int w = 0; w < LPCN_X3_WAVES; w++)
+            for (int k = 0; k <= LPCN_X3_SEGS; k++) {
+                int *d = desc ? desc + (w * (1 + LPCN_X3_SEGS) + k) * 4 : NULL;
+                if (d) { d[0] = im.kind[w][k]; d[1] = im.first[w][k]; d[2] = im.count[w][k]; d[3] = im.skip[w][k]; }
+                if (rows) memcpy(rows + (w * (1 + LPCN_X3_SEGS) + k) * 64, im.row[w][k], sizeof(int) * 64);
+            }
+        lpcn_x3_image_release(&im);
+    }
+    lpcn_model_release(&m);
+    return have;
 }

@@ -39,8 +39,9 @@ struct DeviceGuard {
 
 // GRU-A as dealt to waves and lanes, once per dealing: the model part of the argument block with that image's pointers, and the compiled
 // items-per-lane variant its item arrays are padded to.  PARITY's always exists; FAST has its own for int8 blobs (dealt without candidate heads);
-// the two-group kernel's (float blobs; model_pack.c: lpcn_model_pack_x2) is the only one with the natural-order embedding tables.
-enum { IMG_PARITY, IMG_FAST, IMG_X2, IMG_COUNT };
+// the two-group kernel's (float blobs; model_pack.c: lpcn_model_pack_x2) is the only one with the natural-order embedding tables; its twelve-wave
+// form runs on an image of its own (lpcn_model_pack_x3: 12 waves x 16 items, candidate slots cut head / tail) and shares those tables.
+enum { IMG_PARITY, IMG_FAST, IMG_X2, IMG_X3, IMG_COUNT };
 struct GruAImage { LpcnSampleArgs args{}; int nw_variant = 0; bool present = false; };
 
 struct lpcn_engine {
@@ -66,6 +67,8 @@ struct lpcn_batch_dev {
     bool tuned = false;                // ... and have been measured for the current arithmetic flavour
     bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
     bool no_x2 = false;                // LPCNET_HIP_NO_X2=1 when the batch was created (tools / tests): never the two-group kernel
+    bool x3 = false;                   // at eight streams per workgroup: the twelve-wave form of the two-group kernel (measured faster on this batch, or asked for)
+    int x3_mode = -1;                  // lpcn_batch_dev_set_x3: 0 never, 1 always, -1 measured (the table's value, the eight-wave form, until then)
     int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
     lpcn_stream_state *d_state = nullptr;
     int *d_fc_base = nullptr;
@@ -282,6 +285,35 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
             lpcn_model_release(&mx);
             if (rc) return fail(rc);
         }
+        // ... and its twelve-wave form on the image of lpcn_model_pack_x3, where the model has one (a model without keeps the eight-wave kernels)
+        lpcn_x3_image im;
+        if (e->image[IMG_X2].present && lpcn_model_pack_x3(m, &im) == 0) {
+            if (lpcn_x3_image_selftest(m, &im) == 0) {
+                GruAImage &img = e->image[IMG_X3];
+                LpcnSampleArgs &ax = img.args;
+                ax = e->image[IMG_X2].args;                    // (the natural-order tables and everything that does not depend on the dealing)
+                int bound[LPCN_X3_WAVES * (1 + LPCN_X3_SEGS)], head[LPCN_X3_WAVES];
+                for (int wv = 0; wv < LPCN_X3_WAVES; ++wv) {
+                    int end = 0;
+                    bound[wv * (1 + LPCN_X3_SEGS)] = 0;
+                    for (int k = 1; k <= LPCN_X3_SEGS; ++k) {     // end of P1 segment k; an absent one ends where it starts
+                        if (im.kind[wv][k] != LPCN_X3_NONE) end = im.first[wv][k] + im.count[wv][k];
+                        bound[wv * (1 + LPCN_X3_SEGS) + k] = end;
+                    }
+                    head[wv] = im.kind[wv][0] != LPCN_X3_NONE ? im.count[wv][0] : 0;
+                }
+                const float *dw = nullptr;
+                rc = upload<float>(e, &dw, im.w, (size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64 * 4);
+                ax.a_w = (const float4 *)dw;
+                if (!rc) rc = upload<uint8_t>(e, &ax.a_blk, im.blk, (size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64);
+                if (!rc) rc = upload<int>(e, &ax.a_row, &im.row[0][0][0], (size_t)LPCN_X3_WAVES * (1 + LPCN_X3_SEGS) * 64);
+                if (!rc) rc = upload<int>(e, &ax.a_bound, bound, LPCN_X3_WAVES * (1 + LPCN_X3_SEGS));
+                if (!rc) rc = upload<int>(e, &ax.a_head, head, LPCN_X3_WAVES);
+                img.nw_variant = LPCN_X3_NW; img.present = rc == 0;
+            }
+            lpcn_x3_image_release(&im);
+            if (rc) return fail(rc);
+        }
     }
     {   // the FAST arithmetic's own GRU-A image where its best dealing is not PARITY's (int8 blobs)
         lpcn_model_host mf;
@@ -413,6 +445,8 @@ static bool pack2_available(const lpcn_engine *e) { return e->is_int8 && gru_a_i
 // Two groups of four float streams per workgroup, half a step apart (sample_kernel_x2.hip.h): float blobs, PARITY arithmetic, dense GRU-B input
 // matrix, <= 32 items per lane.  Eight streams per workgroup select it.
 static bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast; }
+// ... and its twelve-wave form (sample_kernel_x3.hip.h), where the model has the image for it
+static bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && b->e->image[IMG_X3].present; }
 static bool use_pack2(const lpcn_batch_dev *b, int n, int S)
 {
     // (S = 4 needs ~92 KB of LDS per workgroup: two do not fit a CU, and the 128-VGPR code alone is slower -- measured 119 vs 137 M)
@@ -457,6 +491,8 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     b->e = e; b->n = n; b->max_chunk = max_chunk;
     const char *off = getenv("LPCNET_HIP_NO_X2"), *force = getenv("LPCNET_HIP_PACK2");      // (read once per batch, never on the launch path)
     b->no_x2 = off && *off == '1'; b->pack2_force = (force && *force) ? *force == '1' : -1;
+    const char *tw = getenv("LPCNET_HIP_X3");                // tools (profiles of one form under LPCNET_HIP_NO_AUTOTUNE): 1 = the twelve-wave form wherever the model has the image, 0 = never
+    if (tw && *tw) { b->x3_mode = *tw == '1'; b->x3 = b->x3_mode == 1; }
     b->S = auto_streams_per_wg(b, n);
     b->pack2 = use_pack2(b, n, b->S);
     auto fail = [&](int code) { lpcn_batch_dev_destroy(b); return code; };
@@ -544,7 +580,7 @@ extern "C" int lpcn_batch_dev_set_state(lpcn_batch_dev *b, int s, const lpcn_str
 // the engine's arithmetic flavour changed: re-run the cost model unless the caller pinned the value
 extern "C" int lpcn_batch_dev_retune(lpcn_batch_dev *b)
 {
-    if (b->S_auto) { b->S = auto_streams_per_wg(b, b->n); b->tuned = false; }      // measured again at the next run
+    if (b->S_auto) { b->S = auto_streams_per_wg(b, b->n); b->tuned = false; if (b->x3_mode < 0) b->x3 = false; }      // measured again at the next run
     b->pack2 = use_pack2(b, b->n, b->S);
     return 0;
 }
@@ -556,6 +592,15 @@ extern "C" int lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s)
     if (s != 1 && s != 2 && s != 4 && s != 8) { snprintf(g_err, sizeof(g_err), "streams per workgroup must be 1, 2, 4 or 8"); return LPCN_E_ARG; }
     b->S = s;
     b->pack2 = use_pack2(b, b->n, b->S);
+    return 0;
+}
+extern "C" int lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode)
+{
+    if (mode < -1 || mode > 1) { snprintf(g_err, sizeof(g_err), "twelve-wave mode must be -1, 0 or 1"); return LPCN_E_ARG; }
+    if (mode == 1 && !x3_available(b)) { snprintf(g_err, sizeof(g_err), "the twelve-wave kernel needs a float blob that fits 12 waves x 16 items per lane (dense GRU-B matrix), PARITY arithmetic"); return LPCN_E_ARG; }
+    b->x3_mode = mode;
+    b->x3 = mode == 1;                                       // (-1: the eight-wave form until the batch is measured)
+    if (mode < 0 && b->S_auto) b->tuned = false;
     return 0;
 }
 extern "C" int lpcn_batch_dev_set_frame_len(lpcn_batch_dev *b, int n)
@@ -585,6 +630,7 @@ extern "C" int lpcn_launch_sample_s2(int nw, int is_int8, int flags, int grid, i
 extern "C" int lpcn_launch_sample_s4(int nw, int is_int8, int flags, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);
 extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x2.hip: two groups of four streams
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
+extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout)
 
 // What a launch works on and the batch does not own for good: a call on part of the batch, on other states or with another S passes another
 // shape; nothing overwrites the batch's settings to steer a launch.
@@ -593,31 +639,35 @@ struct LaunchShape {
     lpcn_stream_state *d_state;        // [n] the states it reads and writes
     int S;                             // streams per workgroup asked for (plan_sample() decides what the launch gets)
     bool pack2;                        //   ... and use_pack2() for that S
+    bool x3 = false;                   //   ... at eight: the twelve-wave form of the two-group kernel
 };
-static LaunchShape whole_batch(const lpcn_batch_dev *b) { return {b->n, b->frame_len, b->d_state, b->S, b->pack2}; }
+static LaunchShape whole_batch(const lpcn_batch_dev *b) { return {b->n, b->frame_len, b->d_state, b->S, b->pack2, b->x3}; }
 
 // Which sample kernel a launch of n_frames frames per stream gets, on which GRU-A image.  No side effects.
 struct SamplePlan {
     int S;                             // streams per workgroup the launch runs with
     bool pack2;
+    bool x3;                           // eight streams per workgroup on twelve waves
     const GruAImage *image;            // (with its items-per-lane variant)
     int lds, grid;                     // dynamic LDS bytes per workgroup, workgroups
 };
 static SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_frames)
 {
     const lpcn_engine *e = b->e;
-    SamplePlan p{sh.S, sh.pack2, nullptr, 0, 0};
+    SamplePlan p{sh.S, sh.pack2, false, nullptr, 0, 0};
     // Eight streams per workgroup become four (a) while the two-group kernel is unavailable (the arithmetic flavour changed under a pinned value) and
     // (b) for a launch with 4 GB or more of conditioning rows -- more than ~9 300 streams x 100 frames -- which the two-group kernel, addressing them
     // with 32-bit byte offsets, cannot reach
     if (sh.S == 8 && (!x2_available(b) || (unsigned long long)sh.n * (unsigned long long)n_frames * LPCN_ROWS_A * 4ull >= (1ull << 32))) { p.S = 4; p.pack2 = false; }
-    p.image = &gru_a_image(e, p.S);
+    p.x3 = p.S == 8 && sh.x3 && x3_available(b);
+    p.image = p.x3 ? &e->image[IMG_X3] : &gru_a_image(e, p.S);
     p.lds = p.S == 8 ? lpcn_x2_lds_bytes(e->nb_b) : p.S == 1 ? lpcn::Lds<1>::total(e->nb_b, e->is_int8) : p.S == 2 ? lpcn::Lds<2>::total(e->nb_b, e->is_int8) : lpcn::Lds<4>::total(e->nb_b, e->is_int8);
     p.grid = (sh.n + p.S - 1) / p.S;
     return p;
 }
 // (what a whole-batch launch of one frame runs with: four while FAST arithmetic is on under a pinned eight)
 extern "C" int lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b) { return plan_sample(b, whole_batch(b), 1).S; }
+extern "C" int lpcn_batch_dev_x3(const lpcn_batch_dev *b) { return plan_sample(b, whole_batch(b), 1).x3 ? 1 : 0; }
 
 // one chunk of the per-sample kernel; cond_a/cond_b/lpc for the chunk are already in the batch buffers
 static int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, short *d_pcm, size_t pcm_stride, int n_frames, int preload, bool fc_from_frames)
@@ -643,7 +693,7 @@ static int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t s
     const int flags = (e->fast ? 1 : 0) | (p.pack2 ? 2 : 0);
     int rc = 0;
     switch (p.S) {
-    case 8: rc = lpcn_launch_sample_x2(nw, p.grid, p.lds, st, b->d_args); break;
+    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, b->d_args) : lpcn_launch_sample_x2(nw, p.grid, p.lds, st, b->d_args); break;
     case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
     case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
     default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
@@ -692,10 +742,16 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
         hipMemcpyAsync(b->d_fc_base, fc.data(), sizeof(int) * b->n, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) { snprintf(g_err, sizeof(g_err), "auto-tune: buffer setup failed"); return done(LPCN_E_HIP); }
     int best = b->S;
+    bool best_x3 = false;
     float best_ms = -1.f;
-    for (int S = 1; S <= 8; S *= 2) {
+    // the candidates: S = 1, 2, 4, 8 and -- where the model has the image, the choice is the engine's and the batch has more than four streams per CU --
+    // eight on twelve waves (both forms of the two-group kernel produce the same bits: the choice cannot change a result)
+    const bool try_x3 = x3_available(b) && b->x3_mode < 0 && b->n > 4 * device_cus(b->e);
+    for (int c = 0; c < 5; ++c) {
+        const int S = c < 4 ? 1 << c : 8;
         if (S == 8 && (!x2_available(b) || b->n <= 4)) break;
-        const LaunchShape sh = {b->n, b->frame_len, b->d_state, S, use_pack2(b, b->n, S)};
+        if (c == 4 && !try_x3) break;
+        const LaunchShape sh = {b->n, b->frame_len, b->d_state, S, use_pack2(b, b->n, S), c == 4 || (S == 8 && b->x3_mode == 1)};
         float ms = -1.f, ms1 = 0.f;
         for (int pass = 0; pass < 7 && !rc; ++pass) {          // warm-up (1 frame), then three pairs of (1 frame, nf frames): the smallest difference
             const int k = (pass && !(pass & 1)) ? nf : 1;
@@ -708,13 +764,14 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
             else if (pass) { const float d = nf > 1 ? t - ms1 : t; if (ms < 0.f || d < ms) ms = d; }      // nf - 1 frames in steady state
         }
         if (rc) break;
-        if (best_ms < 0.f || ms < best_ms) { best_ms = ms; best = S; }
+        if (best_ms < 0.f || ms < best_ms) { best_ms = ms; best = S; best_x3 = sh.x3; }
     }
     // the measurement ran on the real state: put it back
     if (hipMemcpyAsync(b->d_state, saved, sizeof(lpcn_stream_state) * b->n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) rc = rc ? rc : LPCN_E_HIP;
     if (rc) return done(rc);
     b->S = best; b->pack2 = use_pack2(b, b->n, best);
+    if (b->x3_mode < 0) b->x3 = best_x3;
     return done(0);
 }
 
@@ -894,7 +951,7 @@ extern "C" int lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int 
         HIP_TRY(hipMemcpyAsync(b->d_lpc, pin + off_lpc, sizeof(float) * LPCN_LPC_ORDER * k, hipMemcpyHostToDevice, st));
     }
     const int S = auto_streams_per_wg(b, k);               // (the table's value for the group's size, never a measurement)
-    const LaunchShape sh = {k, samples ? frame_len : b->frame_len, b->d_state, S, use_pack2(b, k, S)};
+    const LaunchShape sh = {k, samples ? frame_len : b->frame_len, b->d_state, S, use_pack2(b, k, S), b->x3_mode == 1};
     if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);
     if (kind == LPCN_GROUP_FRAME_SAMPLES) rc = run_impl(b, sh, b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, preload, st);
     else if (kind == LPCN_GROUP_TAIL) rc = launch_sample(b, sh, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, preload, false);
@@ -1389,7 +1446,7 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
         HIP_TRY(hipMemcpyAsync(b->d_feat, fc.data(), sizeof(float) * (size_t)cnt * LPCN_NB_FEAT, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(b->d_pcm, pc.data(), sizeof(short) * (size_t)cnt * LPCN_FRAME_SIZE, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, (const int *)b->d_map, cnt, 0);
-        const LaunchShape sh = {cnt, N, b->d_state_tmp, b->S, b->pack2};      // the compacted group, with the batch's streams per workgroup
+        const LaunchShape sh = {cnt, N, b->d_state_tmp, b->S, b->pack2, b->x3};      // the compacted group, with the batch's streams per workgroup
         if (md == 1) {
             rc = launch_frames(b, sh, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
             if (!rc) {      // remember the products per stream (a later tail-only step of the stream uses them)

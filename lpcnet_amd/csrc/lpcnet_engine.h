@@ -61,6 +61,16 @@ extern "C" {
 #define LPCN_X2_CHAIN_WAVES 4
 #define LPCN_X2_P0_FIRST 4
 #define LPCN_X2_NW_MAX 32
+/* the twelve-wave form of the two-group kernel (sample_kernel_x3.hip.h): three waves per SIMD, at most LPCN_X3_NW register-resident items per lane.
+ * Waves 0 .. LPCN_X3_CHAIN_WAVES - 1 carry GRU-B's chains, the other eight the candidate heads and the start-value pass; every wave runs up to
+ * LPCN_X3_SEGS row segments in P1.  Wave LPCN_X3_LW leads the streams; it and wave LPCN_X3_FREE carry no head (model_pack.c: lpcn_model_pack_x3). */
+#define LPCN_X3_WAVES 12
+#define LPCN_X3_THREADS (64 * LPCN_X3_WAVES)
+#define LPCN_X3_CHAIN_WAVES 4
+#define LPCN_X3_NW 16
+#define LPCN_X3_SEGS 4
+#define LPCN_X3_LW 4
+#define LPCN_X3_FREE 9
 #define LPCN_DEAL_EH_FAST_I8 0 /* head length of the FAST arithmetic's own image of int8 blobs (model_pack.c: lpcn_model_pack_fast) */
 
 typedef struct lpcn_model_host {
@@ -100,6 +110,21 @@ typedef struct lpcn_model_host {
     float   *pk_emb[3];   /* sig/pred/exc tables re-ordered to [256][3 slots][512 threads] */
 } lpcn_model_host;
 
+/* GRU-A dealt to the twelve waves of sample_kernel_x3 (float blobs).  A wave holds LPCN_X3_NW items per lane: segment 0 -- the HEAD of a candidate
+ * slot (its first blocks, summed onto bias + diag*h one sample ahead and parked in the rows' pre-activation cells; a slot of <= LPCN_X3_NW items
+ * is WHOLE there) -- END-ALIGNED at items [LPCN_X3_NW - count, LPCN_X3_NW), and segments 1 .. LPCN_X3_SEGS, run in P1 from the value the rows' cells hold
+ * (WHOLE update / reset slots: the start value; the TAIL of a candidate slot: its head's partial sums), at items [first, first + count). */
+enum { LPCN_X3_NONE = 0, LPCN_X3_WHOLE = 1, LPCN_X3_HEAD = 2, LPCN_X3_TAIL = 3 };
+typedef struct lpcn_x3_image {
+    float   *w;                                             /* [12 waves][16 items][64 lanes][4] */
+    uint8_t *blk;                                           /* [12][16][64] input block of the item */
+    int32_t  row[LPCN_X3_WAVES][1 + LPCN_X3_SEGS][64];      /* GRU-A row of the lane in the segment, or -1 */
+    int32_t  kind[LPCN_X3_WAVES][1 + LPCN_X3_SEGS];
+    int32_t  first[LPCN_X3_WAVES][1 + LPCN_X3_SEGS];        /* first item of the segment */
+    int32_t  count[LPCN_X3_WAVES][1 + LPCN_X3_SEGS];        /* its items */
+    int32_t  skip[LPCN_X3_WAVES][1 + LPCN_X3_SEGS];         /* blocks of its rows that another segment sums first (TAIL: the head's length) */
+} lpcn_x3_image;
+
 /* model_pack.c -------------------------------------------------------------------------------
  * Parse + validate a DNNw blob exactly like the reference loader does
  * (src/parse_lpcnet_weights.c:53-113, :124-220) and build the packings.  Returns 0, or -1 on a
@@ -108,6 +133,9 @@ int  lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len);
 void lpcn_model_release(lpcn_model_host *m);
 int  lpcn_model_pack_x2(const lpcn_model_host *m, lpcn_model_host *f);     /* 0: f holds the two-group kernel's own GRU-A packing; -1: the model does not fit it */
 int  lpcn_model_pack_fast(const lpcn_model_host *m, lpcn_model_host *f);   /* 1: FAST shares PARITY's image; 0: f holds FAST's own GRU-A packing */
+int  lpcn_model_pack_x3(const lpcn_model_host *m, lpcn_x3_image *im);      /* 0: im holds the twelve-wave image; -1: the model does not fit it (not an error: the other kernels run it) */
+void lpcn_x3_image_release(lpcn_x3_image *im);
+int  lpcn_x3_image_selftest(const lpcn_model_host *m, const lpcn_x3_image *im);      /* 0 = every block of GRU-A exactly once, in its row's order, within the bounds */
 /* re-expand the packings and compare them with the blob (0 = consistent) */
 int  lpcn_model_selftest(const lpcn_model_host *m);
 
@@ -183,6 +211,8 @@ int  lpcn_batch_dev_tune(lpcn_batch_dev *b);              /* measure the streams
 int  lpcn_batch_dev_set_state(lpcn_batch_dev *b, int stream, const lpcn_stream_state *host);
 int  lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s);              /* 1,2,4 (0=auto) */
+int  lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode);                       /* twelve-wave form of the two-group kernel: 0 never, 1 always (needs the image), -1 measured / table */
+int  lpcn_batch_dev_x3(const lpcn_batch_dev *b);                                /* what a whole-batch launch runs now */
 int  lpcn_batch_dev_retune(lpcn_batch_dev *b);                                 /* after lpcn_engine_set_fast: auto value again */
 
 /* Run n_frames frames (frame network + LPC + 160-sample loop each) for every stream.

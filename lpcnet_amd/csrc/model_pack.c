@@ -737,3 +737,175 @@ done:
     free(dense); free(packed); free(seen);
     return rc;
 }
+
+/* ---- the twelve-wave image (sample_kernel_x3.hip.h) ------------------------------------------------------------------------------
+ * Slots as above (row groups sorted by block count, eight to a slot; 6 candidate slots, 12 update / reset slots).  A lane holds only
+ * LPCN_X3_NW items, so a candidate slot of more items is cut in two: the HEAD -- its first LPCN_X3_NW blocks -- runs one sample ahead
+ * on a row wave, from bias + diag*h, and parks its partial sums in the rows' pre-activation cells; the TAIL runs in P1 on another wave
+ * and goes on adding, in order, from those cells (no addition of src/vec.h:347-404 changes its operands or its place).  Update / reset
+ * slots are dealt whole.  Heads go to the row waves that neither lead the streams nor are kept free (slot i, longest first, to
+ * x3_head_wave[i]); tails and update / reset slots, longest first, to the first wave with room (chain waves, then the free row
+ * waves, then the rest), backtracking where that strands a piece.  With the benchmark family 188 of the 192 item positions are taken, so there is
+ * little to choose. */
+static const int x3_head_wave[6] = {5, 6, 7, 8, 10, 11};
+static const int x3_p1_order[LPCN_X3_WAVES] = {0, 1, 2, 3, LPCN_X3_FREE, LPCN_X3_LW, 5, 6, 7, 8, 10, 11};
+
+void lpcn_x3_image_release(lpcn_x3_image *im)
+{
+    free(im->w); free(im->blk);
+    im->w = NULL; im->blk = NULL;
+}
+
+static void x3_fill(const lpcn_model_host *m, lpcn_x3_image *im, const row_group *g8, int w, int seg, int kind, int first, int count, int skip)
+{
+    im->kind[w][seg] = kind; im->first[w][seg] = first; im->count[w][seg] = count; im->skip[w][seg] = skip;
+    for (int q = 0; q < 8; q++) {
+        const row_group *rg = &g8[q];
+        for (int r = 0; r < 8; r++) {
+            const int lane = 8 * q + r;
+            im->row[w][seg][lane] = rg->group * 8 + r;
+            for (int j = skip; j < rg->count && j < skip + count; j++) {
+                const size_t item = ((size_t)w * LPCN_X3_NW + first + (j - skip)) * 64 + lane;
+                const float *blkw = m->a_w + (size_t)(rg->first_block + j) * 32;      /* float block = [in 4][out 8] */
+                for (int c = 0; c < 4; c++) im->w[item * 4 + c] = blkw[c * 8 + r];
+                im->blk[item] = (uint8_t)(rg->pos[j] >> 2);
+            }
+        }
+    }
+}
+
+int lpcn_model_pack_x3(const lpcn_model_host *m, lpcn_x3_image *im)
+{
+    enum { NG = LPCN_ROWS_A / 8, NSLOT = NG / 8, NC = LPCN_N_A / 64 };
+    row_group g[NG], c[NG], z[NG];
+    memset(im, 0, sizeof(*im));
+    if (m->is_int8 || !m->b_dense) return -1;
+    {
+        const int *idx = m->a_idx;
+        int blk = 0, nc = 0, nz = 0;
+        for (int i = 0; i < NG; i++) {
+            row_group t = {i, *idx++, blk, NULL};
+            t.pos = idx; idx += t.count; blk += t.count;
+            if (i * 8 >= 2 * LPCN_N_A) c[nc++] = t; else z[nz++] = t;
+        }
+        qsort(c, (size_t)nc, sizeof(c[0]), cmp_group_desc);
+        qsort(z, (size_t)nz, sizeof(z[0]), cmp_group_desc);
+        memcpy(g, c, sizeof(c[0]) * (size_t)nc);
+        memcpy(g + nc, z, sizeof(z[0]) * (size_t)nz);
+    }
+    int used[LPCN_X3_WAVES] = {0}, nseg[LPCN_X3_WAVES] = {0};
+    /* P1 pieces: {slot, items, blocks summed before it, wave it must avoid} */
+    struct { int slot, items, skip, avoid; } pc[NSLOT], t;
+    int np = 0;
+    for (int s = 0; s < NSLOT; s++) {
+        const int len = g[8 * s].count;
+        if (s < NC) {
+            if (len > 2 * LPCN_X3_NW) return -1;
+            if (len > LPCN_X3_NW) { pc[np].slot = s; pc[np].items = len - LPCN_X3_NW; pc[np].skip = LPCN_X3_NW; pc[np].avoid = x3_head_wave[s]; np++; }
+            used[x3_head_wave[s]] = len < LPCN_X3_NW ? len : LPCN_X3_NW;
+        } else {
+            if (len > LPCN_X3_NW) return -1;
+            if (len > 0) { pc[np].slot = s; pc[np].items = len; pc[np].skip = 0; pc[np].avoid = -1; np++; }      /* (rows without blocks keep their start value) */
+        }
+    }
+    for (int i = 1; i < np; i++)                              /* longest first (stable) */
+        for (int j = i; j > 0 && pc[j].items > pc[j - 1].items; j--) { t = pc[j]; pc[j] = pc[j - 1]; pc[j - 1] = t; }
+    /* first fit, longest piece first, with backtracking (the benchmark family leaves 4 free positions of 192: a greedy fit strands them one by one) */
+    int wave_of[NSLOT], tried[NSLOT], depth = 0;
+    long nodes = 0;
+    for (int i = 0; i < np; i++) tried[i] = 0;
+    while (depth < np) {
+        int k = tried[depth], w = -1;
+        for (; k < LPCN_X3_WAVES; k++) {
+            w = x3_p1_order[k];
+            if (w == pc[depth].avoid || nseg[w] >= LPCN_X3_SEGS || used[w] + pc[depth].items > LPCN_X3_NW) continue;
+            int twin = 0;                                     /* a wave in the state of one already tried at this depth leads to the same dead end */
+            for (int k2 = 0; k2 < k && !twin; k2++) {
+                const int w2 = x3_p1_order[k2];
+                twin = w2 != pc[depth].avoid && used[w2] == used[w] && nseg[w2] == nseg[w] && (w2 < LPCN_X3_CHAIN_WAVES) == (w < LPCN_X3_CHAIN_WAVES);
+            }
+            if (!twin) break;
+        }
+        if (k < LPCN_X3_WAVES && ++nodes < 2000000) {
+            tried[depth] = k + 1; wave_of[depth] = w; used[w] += pc[depth].items; nseg[w]++;
+            if (++depth < np) tried[depth] = 0;
+        } else {
+            if (depth == 0 || nodes >= 2000000) return -1;
+            depth--;
+            used[wave_of[depth]] -= pc[depth].items; nseg[wave_of[depth]]--;
+        }
+    }
+    im->w = (float *)calloc((size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64 * 4, sizeof(float));
+    im->blk = (uint8_t *)calloc((size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64, 1);
+    if (!im->w || !im->blk) { lpcn_x3_image_release(im); return -1; }
+    for (int w = 0; w < LPCN_X3_WAVES; w++)
+        for (int k = 0; k <= LPCN_X3_SEGS; k++)
+            for (int lane = 0; lane < 64; lane++) im->row[w][k][lane] = -1;
+    for (int s = 0; s < NC; s++) {                            /* segment 0: heads, end-aligned */
+        const int len = g[8 * s].count, n = len < LPCN_X3_NW ? len : LPCN_X3_NW;
+        x3_fill(m, im, &g[8 * s], x3_head_wave[s], 0, len > LPCN_X3_NW ? LPCN_X3_HEAD : LPCN_X3_WHOLE, LPCN_X3_NW - n, n, 0);
+    }
+    int cur[LPCN_X3_WAVES] = {0}, at[LPCN_X3_WAVES] = {0};
+    for (int i = 0; i < np; i++) {
+        const int w = wave_of[i];
+        x3_fill(m, im, &g[8 * pc[i].slot], w, 1 + at[w], pc[i].skip ? LPCN_X3_TAIL : LPCN_X3_WHOLE, cur[w], pc[i].items, pc[i].skip);
+        cur[w] += pc[i].items; at[w]++;
+    }
+    return 0;
+}
+
+/* Every block of GRU-A's recurrent matrix sits in exactly one item, the items of a row follow the blob's block order (head before tail),
+ * whatever else a lane holds is zero, and no wave exceeds its bounds.  0 = consistent. */
+int lpcn_x3_image_selftest(const lpcn_model_host *m, const lpcn_x3_image *im)
+{
+    enum { NG = LPCN_ROWS_A / 8 };
+    const int *gpos[NG];
+    int gcount[NG], gfirst[NG], next[LPCN_ROWS_A] = {0}, rc = 0;
+    unsigned char *claimed = (unsigned char *)calloc((size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64, 1);
+    if (!claimed) return 100;
+    {
+        const int *idx = m->a_idx;
+        int blk = 0;
+        for (int i = 0; i < NG; i++) { gcount[i] = *idx++; gpos[i] = idx; gfirst[i] = blk; idx += gcount[i]; blk += gcount[i]; }
+    }
+    /* segments in the order in which a sample runs them: heads (one sample ahead), then P1 */
+    for (int pass = 0; pass < 2 && !rc; pass++)
+        for (int w = 0; w < LPCN_X3_WAVES && !rc; w++) {
+            int end = 0;
+            for (int k = pass ? 1 : 0; k <= (pass ? LPCN_X3_SEGS : 0) && !rc; k++) {
+                const int kind = im->kind[w][k], first = im->first[w][k], count = im->count[w][k];
+                if (kind == LPCN_X3_NONE) { for (int lane = 0; lane < 64; lane++) if (im->row[w][k][lane] >= 0) rc = 1; continue; }
+                if (first < 0 || count < 0 || first + count > LPCN_X3_NW) { rc = 2; break; }
+                if (k == 0) {
+                    if (w < LPCN_X3_CHAIN_WAVES || w == LPCN_X3_LW || kind == LPCN_X3_TAIL || first + count != LPCN_X3_NW) { rc = 3; break; }
+                } else {
+                    if (kind == LPCN_X3_HEAD || first != end || first + count > LPCN_X3_NW - im->count[w][0]) { rc = 4; break; }
+                    end = first + count;
+                }
+                for (int lane = 0; lane < 64 && !rc; lane++) {
+                    const int row = im->row[w][k][lane];
+                    if (row < 0) continue;
+                    if (row >= LPCN_ROWS_A) { rc = 5; break; }
+                    const int candidate = row >= 2 * LPCN_N_A, gi = row >> 3, r = row & 7;
+                    if ((k == 0 && !candidate) || (kind == LPCN_X3_TAIL && !candidate) || (k > 0 && kind == LPCN_X3_WHOLE && candidate)) { rc = 6; break; }
+                    if (next[row] != (im->skip[w][k] < gcount[gi] ? im->skip[w][k] : gcount[gi])) { rc = 7; break; }      /* a head from the row's first block, a tail where its head stopped */
+                    for (int j = 0; j < count; j++) {
+                        const size_t item = ((size_t)w * LPCN_X3_NW + first + j) * 64 + lane;
+                        const float *v = im->w + item * 4;
+                        claimed[item] = 1;
+                        if (next[row] < gcount[gi]) {
+                            const float *blkw = m->a_w + (size_t)(gfirst[gi] + next[row]) * 32;
+                            if (im->blk[item] != gpos[gi][next[row]] >> 2) { rc = 8; break; }
+                            for (int c = 0; c < 4; c++) if (memcmp(&v[c], &blkw[c * 8 + r], 4)) rc = 9;
+                            next[row]++;
+                        } else if (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f) rc = 10;
+                    }
+                }
+            }
+        }
+    for (int row = 0; row < LPCN_ROWS_A && !rc; row++) if (next[row] != gcount[row >> 3]) rc = 11;      /* every block of every row */
+    for (size_t i = 0; i < (size_t)LPCN_X3_WAVES * LPCN_X3_NW * 64 && !rc; i++)
+        if (!claimed[i] && (im->w[4 * i] != 0.f || im->w[4 * i + 1] != 0.f || im->w[4 * i + 2] != 0.f || im->w[4 * i + 3] != 0.f)) rc = 12;
+    free(claimed);
+    return rc;
+}

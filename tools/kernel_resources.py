@@ -24,10 +24,10 @@ sys.path.insert(0, ROOT)
 
 
 def compile_asm(s_value, out_path):
-    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip)"""
+    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip); 12: its twelve-wave form (sample_x3.hip)"""
     from lpcnet_amd import build
-    src = "sample_x2.hip" if s_value == 8 else "sample_variants.hip"
-    cmd = [build.HIPCC] + build.HIP_FLAGS + ([] if s_value == 8 else [f"-DLPCN_S={s_value}"]) + ["--cuda-device-only", "-S", os.path.join(build.CSRC, src), "-o", out_path]
+    src = {8: "sample_x2.hip", 12: "sample_x3.hip"}.get(s_value, "sample_variants.hip")
+    cmd = [build.HIPCC] + build.HIP_FLAGS + ([] if s_value in (8, 12) else [f"-DLPCN_S={s_value}"]) + ["--cuda-device-only", "-S", os.path.join(build.CSRC, src), "-o", out_path]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
 
@@ -36,7 +36,11 @@ def demangle(name):
     if m:
         return dict(S=int(m.group(1)), NW=int(m.group(2)), int8=bool(int(m.group(3))), fast=bool(int(m.group(4))), pack2=bool(int(m.group(5))))
     m = re.match(r"_ZN4lpcn16sample_kernel_x2ILi(\d+)EEE", name)          # eight streams per workgroup (two groups of four)
-    return None if not m else dict(S=8, NW=int(m.group(1)), int8=False, fast=False, pack2=False)
+    if m:
+        return dict(S=8, NW=int(m.group(1)), int8=False, fast=False, pack2=False)
+    if re.match(r"_ZN4lpcn16sample_kernel_x3E", name):                      # ... on twelve waves, 16 items per lane (reported as S = 12)
+        return dict(S=12, NW=16, int8=False, fast=False, pack2=False)
+    return None
 
 
 def analyse(asm_path):
@@ -152,7 +156,7 @@ def engine_kernel_resources(pattern=r"N4lpcn\d+(analysis_[a-z]+_kernel)E", asm_p
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--s", type=int, default=4, help="streams per workgroup: 1, 2, 4, or 8 = the two-group kernel")
+    ap.add_argument("--s", type=int, default=4, help="streams per workgroup: 1, 2, 4, 8 = the two-group kernel, or 12 = its twelve-wave form")
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of engine.hip instead")
