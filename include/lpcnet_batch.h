@@ -165,6 +165,53 @@ LPCNET_EXPORT int lpcnet_batch_encoder_enable(LPCNetBatch *b, int max_packets);
 LPCNET_EXPORT int lpcnet_batch_get_encoder_vq_mem(LPCNetBatch *b, int stream, float *out18);
 LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in18);
 
+/* Packet-loss concealment on the device, bit-identical to the reference's generic-C float build (src/lpcnet_plc.c) in CAUSAL mode.
+ * With lpcnet_batch_plc_enable a batch is, in addition, n independent LPCNetPLCState objects: the `lpcnet` member of stream s is the
+ * stream's synthesis state, the `enc` member its analysis state, everything else is per-stream PLC state.  One step advances every
+ * stream by one 10-ms frame: pcm [n_streams][160] in and out, lost [n_streams] (a HOST array in every form of the call);
+ *   lost[s] == 0: pcm[s] holds the received frame                 -> lpcnet_plc_update(st[s], pcm[s])
+ *   lost[s] != 0: pcm[s] is ignored and receives the concealment  -> lpcnet_plc_conceal(st[s], pcm[s])
+ * The PLC network comes from the same blob as the LPCNet model, as in lpcnet_plc_load_model (src/lpcnet_plc.c:88-97): arrays
+ * plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_* (training_tf2/dump_plc.py).  Its widths are read from the bias lengths (each up to 512).
+ * plc_enable: options = LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER.  LPCNET_PLC_NONCAUSAL returns
+ *   LPCNET_HIP_E_ARG: the reference stops in that mode when FEATURES_DELAY > 0 (src/lpcnet_plc.c:357-361) and this engine's model format has 2.
+ *   A blob without the PLC arrays, or with int8 ones (the float build's arithmetic is what is served), returns LPCNET_HIP_E_MODEL with a
+ *   message; so does every other call below before plc_enable.  It allocates the PLC state, implies lpcnet_batch_analysis_enable(1) and
+ *   performs lpcnet_plc_reset on every stream, which resets the stream's synthesis and analysis states as the reference does (:46-60).
+ * The PLC owns the streams it drives: mixing its steps with lpcnet_batch_synthesize* / _analyze* on the same streams gives what the
+ * same mix gives on the reference's member states, except that a tail step after a foreign frame step uses the PLC's own last products.
+ * plc_step copies in, runs, copies out and synchronises (one host thread per shard).  plc_step_device* only enqueues on `hip_stream`
+ * (NULL = the batch's own) under the ordering rules of lpcnet_batch_analyze_device; `lost` is read before the call returns.  The launch
+ * sequence depends on the loss flags, so on a stream that is being captured the call returns LPCNET_HIP_E_ARG and enqueues nothing.
+ * plc_fec_add(features20 == NULL) is lpcnet_plc_fec_add(st, NULL): one skip.  With a full ring (100 vectors, none consumed) the vector is
+ *   dropped as in the reference and the call returns 1.  fec_add waits for the batch's enqueued work.
+ * get / set_plc_state: one stream's PLC state, both halves (layout = struct lpcn_plc_state_rec in lpcnet_amd/csrc/lpcnet_engine.h); with the
+ *   synthesis state (get / set_raw_state) and the analysis state it is a snapshot a stream can be rolled back to. */
+#ifndef LPCNET_PLC_CAUSAL
+#define LPCNET_PLC_CAUSAL 0
+#define LPCNET_PLC_NONCAUSAL 1
+#define LPCNET_PLC_CODEC 2
+#define LPCNET_PLC_DC_FILTER 4
+#endif
+LPCNET_EXPORT int lpcnet_batch_plc_enable(LPCNetBatch *b, int options);
+LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int first, int count);
+LPCNET_EXPORT int lpcnet_batch_plc_step(LPCNetBatch *b, short *pcm, const unsigned char *lost);
+LPCNET_EXPORT int lpcnet_batch_plc_step_device(LPCNetBatch *b, short *d_pcm, const unsigned char *lost, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_plc_step_device_shard(LPCNetBatch *b, int shard, short *d_pcm, const unsigned char *lost, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_plc_fec_add(LPCNetBatch *b, int stream, const float *features20);
+LPCNET_EXPORT int lpcnet_batch_plc_fec_clear(LPCNetBatch *b, int stream);
+LPCNET_EXPORT int lpcnet_batch_plc_state_size(void);
+LPCNET_EXPORT int lpcnet_batch_get_plc_state(LPCNetBatch *b, int stream, void *out);
+LPCNET_EXPORT int lpcnet_batch_set_plc_state(LPCNetBatch *b, int stream, const void *in);
+/* parity seams: burg_cepstral_analysis (src/freq.c:190-199) of one frame per stream, x [n][160] holding int16 values as the PLC feeds
+ * them -> ceps36 [n][36]; compute_plc_pred (src/lpcnet_plc.c:135-146) on every stream's network state (which advances): in57 [n][57] -> out20 [n][20] */
+LPCNET_EXPORT int lpcnet_batch_plc_burg(LPCNetBatch *b, const float *x, float *ceps36);
+LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20);
+/* the host planner alone, no device (tests): ctl [n][9] ints in and out, fec_op [n] or NULL (1 vector added, 2 NULL skip, 3 clear, 4 two vectors
+ * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
+ * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */
+LPCNET_EXPORT int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary);
+
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);
 LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st);

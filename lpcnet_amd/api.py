@@ -33,6 +33,24 @@ class LPCNetError(RuntimeError):
     pass
 
 
+PLC_CAUSAL, PLC_NONCAUSAL, PLC_CODEC, PLC_DC_FILTER = 0, 1, 2, 4      # include/lpcnet_batch.h
+PLC_SUMMARY = 10
+
+
+def plc_plan(options: int, ctl: np.ndarray, lost, fec_op=None):
+    """The PLC's host planner alone (no device): advances ctl [n][9] int32 in place by one step, returns the step's summary [n][10]"""
+    L = load_library()
+    assert ctl.dtype == np.int32 and ctl.ndim == 2 and ctl.shape[1] == 9 and ctl.flags.c_contiguous
+    n = ctl.shape[0]
+    lost = np.ascontiguousarray(lost, np.uint8)
+    op = None if fec_op is None else np.ascontiguousarray(fec_op, np.uint8)
+    out = np.zeros((n, PLC_SUMMARY), np.int32)
+    rc = L.lpcnet_hip_plc_plan(options, n, ctl.ctypes.data, lost, None if op is None else op.ctypes.data, out.ctypes.data)
+    if rc:
+        raise LPCNetError("plc_plan failed (%d): %s" % (rc, last_error()))
+    return out
+
+
 def load_library():
     """dlopen liblpcnet_hip.so (built by `python -m lpcnet_amd.build`).  Raises if it is absent:
     the product path never falls back to a CPU implementation."""
@@ -106,6 +124,18 @@ def load_library():
     L.lpcnet_batch_analysis_reset.argtypes = [vp, C.c_int, C.c_int]
     L.lpcnet_batch_get_analysis_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_analysis_state.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_plc_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_plc_reset.argtypes = [vp, C.c_int, C.c_int]
+    L.lpcnet_batch_plc_step.argtypes = [vp, _i16p, _u8p]
+    L.lpcnet_batch_plc_step_device.argtypes = [vp, vp, _u8p, vp]
+    L.lpcnet_batch_plc_step_device_shard.argtypes = [vp, C.c_int, vp, _u8p, vp]
+    L.lpcnet_batch_plc_fec_add.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_plc_fec_clear.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_get_plc_state.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_set_plc_state.argtypes = [vp, C.c_int, vp]
+    L.lpcnet_batch_plc_burg.argtypes = [vp, _f32p, _f32p]
+    L.lpcnet_batch_plc_pred.argtypes = [vp, _f32p, _f32p]
+    L.lpcnet_hip_plc_plan.argtypes = [C.c_int, C.c_int, vp, _u8p, vp, vp]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -436,6 +466,71 @@ class LPCNetBatch:
     def set_analysis_state(self, stream: int, raw: bytes):
         assert len(raw) == self.L.lpcnet_batch_analysis_state_size()
         self._chk(self.L.lpcnet_batch_set_analysis_state(self.p, stream, C.create_string_buffer(raw, len(raw))), "set_analysis_state")
+
+    # ---- packet-loss concealment (lpcnet_plc_update / lpcnet_plc_conceal per stream, causal mode; include/lpcnet_batch.h) ----
+    def plc_enable(self, options: int = PLC_CAUSAL):
+        """PLC_CAUSAL or PLC_CODEC, optionally | PLC_DC_FILTER; resets every stream (PLC, synthesis and analysis state)"""
+        self._chk(self.L.lpcnet_batch_plc_enable(self.p, options), "plc_enable")
+
+    def plc_reset(self, first=0, count=None):
+        self._chk(self.L.lpcnet_batch_plc_reset(self.p, first, self.n - first if count is None else count), "plc_reset")
+
+    def plc_step(self, pcm: np.ndarray, lost) -> np.ndarray:
+        """one 10-ms frame of every stream: pcm [n][160] int16 (received frames; rows of lost streams are ignored), lost [n] -> pcm [n][160]"""
+        out = np.ascontiguousarray(pcm, np.int16).copy()
+        lost = np.ascontiguousarray(lost, np.uint8)
+        assert out.shape == (self.n, LPCNET_FRAME_SIZE) and lost.shape == (self.n,)
+        self._chk(self.L.lpcnet_batch_plc_step(self.p, out, lost), "plc_step")
+        return out
+
+    def plc_step_device(self, d_pcm_ptr: int, lost, hip_stream: int = 0, shard=None):
+        """enqueue only: d_pcm [n][160] int16 on the device, in and out; lost stays a host array"""
+        lost = np.ascontiguousarray(lost, np.uint8)
+        if shard is None:
+            assert lost.shape == (self.n,)
+            self._chk(self.L.lpcnet_batch_plc_step_device(self.p, d_pcm_ptr, lost, hip_stream), "plc_step_device")
+        else:
+            self._chk(self.L.lpcnet_batch_plc_step_device_shard(self.p, shard, d_pcm_ptr, lost, hip_stream), "plc_step_device_shard")
+
+    def plc_fec_add(self, stream: int, features=None) -> int:
+        """lpcnet_plc_fec_add: 20 features, or None for one skip; returns 1 when the ring was full and the vector was dropped"""
+        if features is None:
+            rc = self.L.lpcnet_batch_plc_fec_add(self.p, stream, None)
+        else:
+            f = np.ascontiguousarray(features, np.float32)
+            assert f.shape == (20,)
+            rc = self.L.lpcnet_batch_plc_fec_add(self.p, stream, f.ctypes.data)
+        if rc < 0:
+            self._chk(rc, "plc_fec_add")
+        return rc
+
+    def plc_fec_clear(self, stream: int):
+        self._chk(self.L.lpcnet_batch_plc_fec_clear(self.p, stream), "plc_fec_clear")
+
+    def get_plc_state(self, stream: int) -> bytes:
+        buf = C.create_string_buffer(self.L.lpcnet_batch_plc_state_size())
+        self._chk(self.L.lpcnet_batch_get_plc_state(self.p, stream, buf), "get_plc_state")
+        return buf.raw
+
+    def set_plc_state(self, stream: int, raw: bytes):
+        assert len(raw) == self.L.lpcnet_batch_plc_state_size()
+        self._chk(self.L.lpcnet_batch_set_plc_state(self.p, stream, C.create_string_buffer(raw, len(raw))), "set_plc_state")
+
+    def plc_burg(self, x: np.ndarray) -> np.ndarray:
+        """parity seam: burg_cepstral_analysis of one frame per stream, x [n][160] holding int16 values -> [n][36]"""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.shape == (self.n, LPCNET_FRAME_SIZE)
+        out = np.empty((self.n, 36), np.float32)
+        self._chk(self.L.lpcnet_batch_plc_burg(self.p, x, out), "plc_burg")
+        return out
+
+    def plc_pred(self, in57: np.ndarray) -> np.ndarray:
+        """parity seam: compute_plc_pred on every stream's network state (which advances), in57 [n][57] -> [n][20]"""
+        x = np.ascontiguousarray(in57, np.float32)
+        assert x.shape == (self.n, 57)
+        out = np.empty((self.n, 20), np.float32)
+        self._chk(self.L.lpcnet_batch_plc_pred(self.p, x, out), "plc_pred")
+        return out
 
     def encode(self, pcm: np.ndarray) -> np.ndarray:
         """pcm (n, P*640) int16 -> packets (n, P, 8) uint8: lpcnet_encode per stream and packet (codebooks: set_codebooks)"""

@@ -1063,7 +1063,7 @@ int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
  * device and stream; with a single shard the work runs on the calling thread. */
 typedef struct {
     LPCNetBatch *b; int shard;
-    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze, 3 encode, 4 compute_features */
+    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze, 3 encode, 4 compute_features, 5 PLC step */
     const float *features; int feat_stride; short *pcm; int n_frames, preload;
     const void *an_pcm; int an_is_float; float *an_features;
     const unsigned char *packets; int n_packets;
@@ -1086,7 +1086,9 @@ static void *shard_worker(void *arg)
         const size_t o = (size_t)s->first * j->n_packets;
         j->rc = lpcn_batch_dev_encode_host(s->dev, (const short *)j->an_pcm + o * 4 * LPCN_FRAME_SIZE, j->kind == 3 ? j->enc_packets + o * 8 : NULL,
                                            j->kind == 4 ? j->an_features + o * 4 * j->feat_stride : NULL, j->feat_stride, j->n_packets);
-    } else
+    } else if (j->kind == 5)
+        j->rc = lpcn_batch_dev_plc_step_host(s->dev, j->pcm + (size_t)s->first * LPCN_FRAME_SIZE, j->packets + s->first);      /* (packets = the loss flags) */
+    else
         j->rc = lpcn_batch_dev_decode_host(s->dev, j->packets + (size_t)s->first * j->n_packets * 8,
                                            j->pcm + (size_t)s->first * j->n_packets * 4 * LPCN_FRAME_SIZE, j->n_packets);
     if (j->rc) snprintf(j->err, sizeof(j->err), "%s", lpcn_last_error());      /* (the engine's message is thread-local) */
@@ -1252,6 +1254,115 @@ int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st)
     NEED_MODEL(b);
     SHARD_OF(s, b, stream);
     FWD(lpcn_batch_dev_set_state(s->dev, stream - s->first, &st->s));
+}
+
+/* ---- packet-loss concealment (lpcnet_plc_update / lpcnet_plc_conceal per stream, causal mode; include/lpcnet_batch.h) ---- */
+#define NEED_PLC_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_plc_enabled((b)->sh[0].dev)) { set_err("packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; } } while (0)
+int lpcnet_batch_plc_enable(LPCNetBatch *b, int options)
+{
+    NEED_MODEL(b);
+    if ((options & 3) == LPCNET_PLC_NONCAUSAL) { set_err("lpcnet_batch_plc_enable: LPCNET_PLC_NONCAUSAL needs a model without feature delay (src/lpcnet_plc.c:357-361); this engine's model format has FEATURES_DELAY = 2"); return LPCN_E_ARG; }
+    if ((options & 3) == 3 || (options & ~7)) { set_err("lpcnet_batch_plc_enable: options are LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) { int rc = lpcn_batch_dev_plc_enable(b->sh[k].dev, options); if (rc) { take_engine_err(); return rc; } }
+    return 0;
+}
+int lpcnet_batch_plc_reset(LPCNetBatch *b, int first, int count)
+{
+    NEED_PLC_ON(b);
+    if (first < 0 || count < 0 || first + count > b->n) { set_err("PLC reset range"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {
+        const batch_shard *s = &b->sh[k];
+        const int lo = first > s->first ? first : s->first;
+        const int hi = first + count < s->first + s->count ? first + count : s->first + s->count;
+        if (hi <= lo) continue;
+        int rc = lpcn_batch_dev_plc_reset(s->dev, lo - s->first, hi - lo);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    return 0;
+}
+int lpcnet_batch_plc_step(LPCNetBatch *b, short *pcm, const unsigned char *lost)
+{
+    NEED_PLC_ON(b);
+    if (!pcm || !lost) { set_err("lpcnet_batch_plc_step: bad arguments"); return LPCN_E_ARG; }
+    shard_job j; memset(&j, 0, sizeof(j));
+    j.kind = 5; j.pcm = pcm; j.packets = lost;
+    return run_shards(b, &j);
+}
+int lpcnet_batch_plc_step_device_shard(LPCNetBatch *b, int shard, short *d_pcm, const unsigned char *lost, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !d_pcm || !lost) { set_err("lpcnet_batch_plc_step_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_plc_step(b->sh[shard].dev, d_pcm, lost, hip_stream));
+}
+int lpcnet_batch_plc_step_device(LPCNetBatch *b, short *d_pcm, const unsigned char *lost, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_plc_step_device");
+    return lpcnet_batch_plc_step_device_shard(b, 0, d_pcm, lost, hip_stream);
+}
+int lpcnet_batch_plc_fec_add(LPCNetBatch *b, int stream, const float *features20)
+{
+    NEED_PLC_ON(b);
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_plc_fec_add(s->dev, stream - s->first, features20));
+}
+int lpcnet_batch_plc_fec_clear(LPCNetBatch *b, int stream)
+{
+    NEED_PLC_ON(b);
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_plc_fec_clear(s->dev, stream - s->first));
+}
+int lpcnet_batch_plc_state_size(void) { return (int)sizeof(lpcn_plc_state_rec); }
+int lpcnet_batch_get_plc_state(LPCNetBatch *b, int stream, void *out)
+{
+    NEED_PLC_ON(b);
+    if (!out) { set_err("lpcnet_batch_get_plc_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_get_plc_state(s->dev, stream - s->first, (lpcn_plc_state_rec *)out));
+}
+int lpcnet_batch_set_plc_state(LPCNetBatch *b, int stream, const void *in)
+{
+    NEED_PLC_ON(b);
+    if (!in) { set_err("lpcnet_batch_set_plc_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, b, stream);
+    FWD(lpcn_batch_dev_set_plc_state(s->dev, stream - s->first, (const lpcn_plc_state_rec *)in));
+}
+int lpcnet_batch_plc_burg(LPCNetBatch *b, const float *x, float *ceps36)
+{
+    NEED_PLC_ON(b);
+    if (!x || !ceps36) { set_err("lpcnet_batch_plc_burg: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {
+        const batch_shard *s = &b->sh[k];
+        int rc = lpcn_batch_dev_plc_burg_host(s->dev, x + (size_t)s->first * LPCN_FRAME_SIZE, ceps36 + (size_t)s->first * 2 * LPCN_NB_BANDS);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    return 0;
+}
+int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20)
+{
+    NEED_PLC_ON(b);
+    if (!in57 || !out20) { set_err("lpcnet_batch_plc_pred: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {
+        const batch_shard *s = &b->sh[k];
+        int rc = lpcn_batch_dev_plc_pred_host(s->dev, in57 + (size_t)s->first * LPCN_PLC_IN, out20 + (size_t)s->first * LPCN_NB_FEAT);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    return 0;
+}
+/* the planner alone (no device): ctl [n][9] ints in and out (pcm_fill, skip_analysis, blend, loss_count, fec_fill, fec_keep, fec_read, fec_skip,
+ * deferred-queue fill; all zero but pcm_fill = 400 after a reset), fec_op [n] (may be NULL): 1 = a vector was added before the step, 2 = a NULL skip,
+ * 3 = fec_clear, 4 = two vectors; summary [n][10] */
+int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary)
+{
+    if (n < 1 || !ctl || !lost) { set_err("lpcnet_hip_plc_plan: bad arguments"); return LPCN_E_ARG; }
+    lpcn_plc_ctl *c = (lpcn_plc_ctl *)ctl;
+    for (int s = 0; fec_op && s < n; s++) {
+        if (fec_op[s] == 1) (void)lpcn_plc_ctl_fec_add(&c[s], 0);
+        else if (fec_op[s] == 2) (void)lpcn_plc_ctl_fec_add(&c[s], 1);
+        else if (fec_op[s] == 3) c[s].fec_keep = c[s].fec_read = c[s].fec_fill = c[s].fec_skip = 0;
+        else if (fec_op[s] == 4) { (void)lpcn_plc_ctl_fec_add(&c[s], 0); (void)lpcn_plc_ctl_fec_add(&c[s], 0); }
+    }
+    FWD(lpcn_plc_plan(options, n, c, lost, summary));
 }
 
 /* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */

@@ -13,6 +13,8 @@
 #include "decode_kernel.hip.h"
 #include "analysis_kernels.hip.h"
 #include "encode_kernels.hip.h"
+#include "plc_kernels.hip.h"
+#define LPCNET_PLC_CAUSAL_OPT 0      /* LPCNET_PLC_CAUSAL of include/lpcnet.h (2 = LPCNET_PLC_CODEC, | 4 = LPCNET_PLC_DC_FILTER) */
 #include <math.h>
 
 static thread_local char g_err[512] = "";
@@ -58,6 +60,8 @@ struct lpcn_engine {
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
     lpcn::EncodeTables enc{};      // encoder: the same codebooks and their transposed copies, refreshed together
+    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network (plc_present == 1)
+    int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
 };
 
 struct lpcn_batch_dev {
@@ -103,6 +107,7 @@ struct lpcn_batch_dev {
     hipEvent_t ev_last = nullptr;
     hipStream_t last_stream = nullptr;
     bool pending = false;
+    struct lpcn_plc_host *plc = nullptr;      // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
     void *h_pin = nullptr;             // pinned host staging of the single-stream fast path (state | features | pcm)
     bool timing = false;
     float ms_sample = 0.f, ms_frame = 0.f;
@@ -160,6 +165,35 @@ static const int variants_x2[] = {LPCN_VARIANTS_X2(LPCN_LIST_ITEM) 0};
 #undef LPCN_LIST_ITEM
 // the smallest compiled variant that holds nw items per lane (0: none does)
 static int round_up_variant(const int *v, int nw) { for (; *v; ++v) if (nw <= *v) return *v; return 0; }
+
+// the PLC network: the blob's arrays as they are, and for each sparse GRU input matrix the first block of every 8-row group plus the
+// blocks' input positions (the index stream {count, pos...} of src/vec.h:347-360 without its counts)
+static int plc_upload_net(lpcn_engine *e, const lpcn_plc_model *p)
+{
+    lpcn::PlcNet &n = e->plc;
+    n.d1 = p->d1; n.g1 = p->g1; n.g2 = p->g2;
+    int rc = 0;
+#define UPP(field, src, count) if ((rc = upload<float>(e, &n.field, src, (size_t)(count)))) return rc
+    UPP(dense1_w, p->dense1_w, LPCN_PLC_IN * p->d1); UPP(dense1_b, p->dense1_b, p->d1);
+    UPP(gru1_w, p->gru1_w, 32 * (size_t)p->nb1); UPP(gru1_rec, p->gru1_rec, 3 * (size_t)p->g1 * p->g1); UPP(gru1_bias, p->gru1_bias, 6 * p->g1);
+    UPP(gru2_w, p->gru2_w, 32 * (size_t)p->nb2); UPP(gru2_rec, p->gru2_rec, 3 * (size_t)p->g2 * p->g2); UPP(gru2_bias, p->gru2_bias, 6 * p->g2);
+    UPP(out_w, p->out_w, LPCN_NB_FEAT * p->g2); UPP(out_b, p->out_b, LPCN_NB_FEAT);
+    UPP(tansig, lpcn_tansig, 201);
+#undef UPP
+    for (int g = 0; g < 2; ++g) {
+        const int *idx = g ? p->gru2_idx : p->gru1_idx;
+        const int groups = 3 * (g ? p->g2 : p->g1) / 8;
+        std::vector<int> start(groups + 1, 0), pos;
+        for (int r = 0; r < groups; ++r) {
+            const int cnt = *idx++;
+            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++);
+            start[r + 1] = (int)pos.size();
+        }
+        if ((rc = upload<int>(e, g ? &n.gru2_start : &n.gru1_start, start.data(), start.size()))) return rc;
+        if ((rc = upload<int>(e, g ? &n.gru2_pos : &n.gru1_pos, pos.data(), pos.size()))) return rc;
+    }
+    return 0;
+}
 
 extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_model_host *m)
 {
@@ -352,6 +386,8 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     }
     fm.lpc_gamma = m->lpc_gamma;
     fm.end2end = 0;
+    e->plc_present = m->plc.present;
+    if (m->plc.present == 1 && (rc = plc_upload_net(e, &m->plc))) return fail(rc);
     *out = e;
     return 0;
 }
@@ -514,11 +550,13 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     return 0;
 }
 
+static void plc_free(lpcn_batch_dev *b);
 extern "C" void lpcn_batch_dev_destroy(lpcn_batch_dev *b)
 {
     if (!b) return;
     DeviceGuard guard(b->e->device);
     (void)wait_all(b);
+    plc_free(b);
     if (b->h_pin) (void)hipHostFree(b->h_pin);
     if (b->ev_last) (void)hipEventDestroy(b->ev_last);
     void *ptrs[] = {b->d_state, b->d_fc_base, b->d_cond_a, b->d_cond_b, b->d_lpc, b->d_cond, b->d_feat, b->d_pcm, b->d_args, b->d_dbg, b->d_prof,
@@ -1470,6 +1508,572 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
         if (md == 1) for (int i = 0; i < cnt; ++i) b->keep_ok[(size_t)map[i]] = 1;
         for (int i = 0; i < cnt; ++i) memcpy(pcm + (size_t)map[i] * LPCN_FRAME_SIZE, &pc[(size_t)i * LPCN_FRAME_SIZE], sizeof(short) * (size_t)N);
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- packet-loss concealment -----
+// lpcnet_plc_update / lpcnet_plc_conceal in causal mode for every stream (src/lpcnet_plc.c:188-340).  No branch of the
+// reference looks at audio: the options, skip_analysis, blend, pcm_fill, loss_count, the FEC ring positions and fec_skip decide, and they
+// follow from the loss flags and the FEC calls.  So the host keeps that control state, derives every stream's branch for a step without
+// reading anything back, and lists the streams of every phase; the data stays on the device.  A step is one upload of those lists and a
+// fixed order of launches with no host synchronisation between them.
+enum { PLC_T_BURG, PLC_T_PRED, PLC_T_MIX, PLC_T_GROUP, PLC_T_ANALYSIS };
+enum { PLC_G_FRAMES, PLC_G_FRAME_SAMPLES, PLC_G_TAIL };
+struct PlcLaunch {
+    int type = 0, op = 0, off = 0, cnt = 0;
+    // groups: what runs on the compacted streams, where its features and PCM come from and go to
+    int kind = 0, N = LPCN_FRAME_SIZE, preload = 0;
+    int feat_src = 0;          // 0 st->features, 1 + k: entry k of the deferred queue
+    int pcm_src = 0;           // preload source: 0 none, 1 head of the PCM queue, 2 the call's frame at pcm_off
+    int pcm_dst = 0;           // 0 nowhere (the group's compacted PCM is left for a cross-fade), 1 the call's frame at pcm_off
+    int pcm_off = 0;
+    bool scatter = true, keep = false;
+};
+struct PlcPlan { std::vector<int> ctl; std::vector<PlcLaunch> launches; };
+
+struct lpcn_plc_host {
+    int options = 0;
+    bool blending = true, remove_dc = false;
+    std::vector<lpcn_plc_ctl> ctl;
+    lpcn::PlcData D{};
+    short *d_pcm = nullptr, *d_gpcm = nullptr;      // staging of the host-pointer call; the compacted PCM of a group
+    float *d_gfeat = nullptr;                       // the compacted features of a group / the parity seam's output
+    int *d_ident = nullptr;                         // 0 .. n-1
+    int *d_ctl = nullptr, *h_ctl = nullptr;         // the step's lists: device copy and its pinned source
+    size_t ctl_cap = 0;
+    hipEvent_t ev_ctl = nullptr;                    // the upload of the previous step's lists has left h_ctl
+    bool ctl_pending = false;
+    PlcPlan plan;
+};
+
+extern "C" void lpcn_plc_ctl_reset(lpcn_plc_ctl *c)
+{
+    memset(c, 0, sizeof(*c));
+    c->pcm_fill = LPCN_PLC_BUF_SIZE;      // src/lpcnet_plc.c:52-58
+}
+
+// get_fec_or_pred's decision and bookkeeping (src/lpcnet_plc.c:148-168)
+static bool plc_take_fec(lpcn_plc_ctl &c, int *row)
+{
+    if (c.fec_read != c.fec_fill && c.fec_skip == 0) {
+        *row = c.fec_read++;
+        const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
+        c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
+        if (c.fec_keep < 0) c.fec_keep = 0;
+        return true;
+    }
+    if (c.fec_skip > 0) c.fec_skip--;
+    *row = 0;
+    return false;
+}
+
+extern "C" int lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null)      // src/lpcnet_plc.c:109-127
+{
+    if (is_null) { c->fec_skip++; return 0; }
+    int moved = 0;
+    if (c->fec_fill == LPCN_PLC_MAX_FEC) {
+        if (c->fec_keep == 0) return 1;
+        c->fec_fill -= c->fec_keep;
+        c->fec_read -= c->fec_keep;
+        c->fec_keep = 0;
+        moved = 2;
+    }
+    c->fec_fill++;
+    return moved;
+}
+
+static int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
+
+static void plc_emit(PlcPlan &P, int type, int op, const std::vector<int> &recs, int rec_size)
+{
+    if (recs.empty()) return;
+    PlcLaunch L;
+    L.type = type; L.op = op; L.off = (int)P.ctl.size(); L.cnt = (int)recs.size() / rec_size;
+    P.ctl.insert(P.ctl.end(), recs.begin(), recs.end());
+    P.launches.push_back(L);
+}
+static void plc_emit_group(PlcPlan &P, const std::vector<int> &map, int kind, int N, int preload, int feat_src, int pcm_src, int pcm_dst, int pcm_off, bool scatter, bool keep)
+{
+    if (map.empty()) return;
+    PlcLaunch L;
+    L.type = PLC_T_GROUP; L.off = (int)P.ctl.size(); L.cnt = (int)map.size();
+    L.kind = kind; L.N = N; L.preload = preload; L.feat_src = feat_src; L.pcm_src = pcm_src; L.pcm_dst = pcm_dst; L.pcm_off = pcm_off; L.scatter = scatter; L.keep = keep;
+    P.ctl.insert(P.ctl.end(), map.begin(), map.end());
+    P.launches.push_back(L);
+}
+
+// One step of every stream's control state, and the launches it takes.  summary (may be NULL): LPCN_PLC_SUMMARY ints per stream.
+static int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary)
+{
+    using namespace lpcn;
+    const bool blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT, remove_dc = (options & 4) != 0;
+    static const float att_table[10] = {0, 0, -.2, -.2, -.4, -.4, -.8, -.8, -1.6, -1.6};      // src/lpcnet_plc.c:295
+    P.ctl.clear(); P.launches.clear();
+    for (int s = 0; s < n; ++s) {
+        const lpcn_plc_ctl &c = ctl[s];
+        const bool fill_ok = c.pcm_fill == 0 || c.pcm_fill == 80 || c.pcm_fill == 240 || c.pcm_fill == LPCN_PLC_BUF_SIZE;
+        if (!fill_ok || (!lost[s] && c.skip_analysis && !c.blend && c.pcm_fill + LPCN_FRAME_SIZE > LPCN_PLC_BUF_SIZE) || c.fbuf_fill < 0 || c.fbuf_fill > LPCN_PLC_FBUF ||
+            c.fec_keep < 0 || c.fec_keep > c.fec_read || c.fec_read > c.fec_fill || c.fec_fill > LPCN_PLC_MAX_FEC || c.fec_skip < 0 || c.skip_analysis < 0 || c.loss_count < 0) {
+            snprintf(g_err, sizeof(g_err), "stream %d: inconsistent PLC control state", s); return LPCN_E_ARG;
+        }
+    }
+    std::vector<int> flush[LPCN_PLC_FBUF], rpred[3], r160[3], r80[3], rshift[3], fpred, lostmap, dclost;
+    std::vector<int> burg, bpred, fa1, fa2, resetsig, xgrp, xfade, qtail, qappend, post_pred, fa3, qpush, dcrecv;
+    int zero[LPCN_PLC_SUMMARY];
+    for (int s = 0; s < n; ++s) {
+        lpcn_plc_ctl &c = ctl[s];
+        int *sm = summary ? summary + (size_t)s * LPCN_PLC_SUMMARY : zero;
+        memset(sm, 0, sizeof(int) * LPCN_PLC_SUMMARY);
+        if (lost[s]) {                                       // lpcnet_plc_conceal_causal, src/lpcnet_plc.c:296-340
+            sm[0] = 1; sm[1] = c.fbuf_fill;
+            for (int k = 0; k < c.fbuf_fill; ++k) flush[k].push_back(s);
+            c.fbuf_fill = 0;
+            for (int r = 0; c.pcm_fill > 0 && r < 3; ++r) {
+                const int N = c.pcm_fill < LPCN_FRAME_SIZE ? c.pcm_fill : LPCN_FRAME_SIZE;
+                int row = 0;
+                const bool fec = plc_take_fec(c, &row);
+                const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP);
+                const int rec[PLC_PRED_REC] = {s, fl, row, 0, 0, 0};
+                rpred[r].insert(rpred[r].end(), rec, rec + PLC_PRED_REC);
+                (N == LPCN_FRAME_SIZE ? r160 : r80)[r].push_back(s);
+                const int mr[PLC_MIX_REC] = {s, 0, 0};
+                rshift[r].insert(rshift[r].end(), mr, mr + PLC_MIX_REC);
+                c.pcm_fill -= N;
+                c.skip_analysis++;
+                sm[2]++; sm[3] += N; sm[4] += fec ? 1 : 0;
+            }
+            int row = 0;
+            const bool fec = plc_take_fec(c, &row);
+            if (fec) c.loss_count = 0; else c.loss_count++;
+            const float a1 = c.loss_count >= 10 ? att_table[9] : att_table[c.loss_count];
+            const float a2 = c.loss_count >= 10 ? (float)(2 * (c.loss_count - 9)) : 0.f;
+            const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP) | PLC_F_ATT;
+            const int rec[PLC_PRED_REC] = {s, fl, row, float_bits(a1), float_bits(a2), 0};
+            fpred.insert(fpred.end(), rec, rec + PLC_PRED_REC);
+            lostmap.push_back(s);
+            c.blend = 1;
+            sm[4] += fec ? 1 : 0; sm[9] = c.loss_count;
+            const int mr[PLC_MIX_REC] = {s, 0, 0};
+            if (remove_dc) dclost.insert(dclost.end(), mr, mr + PLC_MIX_REC);
+            continue;
+        }
+        // lpcnet_plc_update_causal, src/lpcnet_plc.c:188-290
+        burg.push_back(s);
+        const int mr[PLC_MIX_REC] = {s, 0, 0};
+        if (c.skip_analysis) {
+            if (c.blend) {
+                if (blending) {
+                    const int rec[PLC_PRED_REC] = {s, (2 << PLC_F_RESTORE_SHIFT) | (PLC_IN_BURG << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
+                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
+                    for (int k = 0; k < LPCN_FEATURES_DELAY; ++k) {
+                        const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 0};
+                        std::vector<int> &fa = k ? fa2 : fa1;
+                        fa.insert(fa.end(), fr, fr + PLC_MIX_REC);
+                        if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
+                    }
+                    const int xr[PLC_MIX_REC] = {s, (int)xgrp.size(), 0};
+                    xfade.insert(xfade.end(), xr, xr + PLC_MIX_REC);
+                    xgrp.push_back(s);
+                    sm[5] = 1; sm[8] += LPCN_FEATURES_DELAY;
+                } else {
+                    const int rec[PLC_PRED_REC] = {s, 1 << PLC_F_RESTORE_SHIFT, 0, 0, 0, 0};
+                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
+                    c.fec_read -= LPCN_FEATURES_DELAY;                      // fec_rewind, :170-175
+                    if (c.fec_read < c.fec_keep) c.fec_read = c.fec_keep;
+                    resetsig.insert(resetsig.end(), mr, mr + PLC_MIX_REC);
+                    sm[5] = 2;
+                }
+                qtail.insert(qtail.end(), mr, mr + PLC_MIX_REC);
+                c.pcm_fill = 80;
+                sm[6] = 1;
+            } else {
+                const int qr[PLC_MIX_REC] = {s, c.pcm_fill, 0};
+                qappend.insert(qappend.end(), qr, qr + PLC_MIX_REC);
+                c.pcm_fill += LPCN_FRAME_SIZE;
+                sm[6] = 2;
+            }
+        }
+        if (!c.blend) {
+            const int rec[PLC_PRED_REC] = {s, (PLC_IN_BURG_FEAT << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
+            post_pred.insert(post_pred.end(), rec, rec + PLC_PRED_REC);
+            if (c.fec_skip) c.fec_skip--;
+            else if (c.fec_read < c.fec_fill) c.fec_read++;
+            const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
+            c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
+            if (c.fec_keep < 0) c.fec_keep = 0;
+            sm[7] = 1;
+        }
+        bool append = false;
+        if (c.skip_analysis) {
+            append = blending;
+            c.skip_analysis--;
+        } else {
+            qpush.insert(qpush.end(), mr, mr + PLC_MIX_REC);
+            append = true;
+            sm[6] = 3;
+        }
+        if (append) {
+            const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 1};
+            fa3.insert(fa3.end(), fr, fr + PLC_MIX_REC);
+            if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
+            sm[8]++;
+        }
+        c.loss_count = 0;
+        if (remove_dc) dcrecv.insert(dcrecv.end(), mr, mr + PLC_MIX_REC);
+        c.blend = 0;
+    }
+    // lost streams: flush, the queued samples round by round, the concealed frame
+    for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
+    for (int r = 0; r < 3; ++r) {
+        plc_emit(P, PLC_T_PRED, 0, rpred[r], PLC_PRED_REC);
+        plc_emit_group(P, r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
+        plc_emit_group(P, r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
+        plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, rshift[r], PLC_MIX_REC);
+    }
+    plc_emit_group(P, lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
+    plc_emit(P, PLC_T_PRED, 0, fpred, PLC_PRED_REC);
+    plc_emit_group(P, lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
+    // received streams up to the analysis
+    if (!burg.empty()) { plc_emit(P, PLC_T_BURG, 0, burg, 1); }
+    plc_emit(P, PLC_T_PRED, 0, bpred, PLC_PRED_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa1, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa2, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_RESETSIG, resetsig, PLC_MIX_REC);
+    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 0, 0, false, false);      // into the group's PCM; the states are not written back (the reference's copy / restore)
+    plc_emit(P, PLC_T_MIX, PLC_MIX_XFADE, xfade, PLC_MIX_REC);
+    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QTAIL, qtail, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QAPPEND, qappend, PLC_MIX_REC);
+    { PlcLaunch L; L.type = PLC_T_ANALYSIS; P.launches.push_back(L); }
+    plc_emit(P, PLC_T_PRED, 0, post_pred, PLC_PRED_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa3, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QPUSH, qpush, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_DCRECV, dcrecv, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_DCLOST, dclost, PLC_MIX_REC);
+    return 0;
+}
+
+extern "C" int lpcn_plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary)
+{
+    if (n < 1 || !ctl || !lost || (options & 3) == 1 || (options & 3) == 3 || (options & ~7)) { snprintf(g_err, sizeof(g_err), "bad PLC plan arguments"); return LPCN_E_ARG; }
+    PlcPlan P;
+    return plc_plan(options, n, ctl, lost, P, summary);
+}
+
+extern "C" int lpcn_engine_plc_present(const lpcn_engine *e) { return e->plc_present; }
+extern "C" int lpcn_batch_dev_plc_enabled(const lpcn_batch_dev *b) { return b->plc ? 1 : 0; }
+
+static void plc_free(lpcn_batch_dev *b)
+{
+    lpcn_plc_host *p = b->plc;
+    if (!p) return;
+    void *ptrs[] = {p->D.q, p->D.feat, p->D.net, p->D.dc, p->D.delta, p->D.fec, p->D.fbuf, p->D.lp, p->D.burg, p->D.an, p->d_pcm, p->d_gpcm, p->d_gfeat, p->d_ident, p->d_ctl};
+    for (void *q : ptrs) if (q) (void)hipFree(q);
+    if (p->h_ctl) (void)hipHostFree(p->h_ctl);
+    if (p->ev_ctl) (void)hipEventDestroy(p->ev_ctl);
+    delete p;
+    b->plc = nullptr;
+}
+
+static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(b->e->plc.g1 + b->e->plc.g2); }
+
+// lpcnet_plc_reset (src/lpcnet_plc.c:46-60) on streams [first, first + count): the PLC's own fields, the synthesis state, the analysis state
+static int plc_reset_range(lpcn_batch_dev *b, int first, int count)
+{
+    lpcn_plc_host *p = b->plc;
+    int rc = lpcn_batch_dev_reset(b, first, count);      // (waits for everything enqueued)
+    if (!rc) rc = lpcn_batch_dev_analysis_reset(b, first, count);
+    if (rc || !count) return rc;
+    const size_t G4 = plc_net_floats(b);
+#define ZR(ptr, per) HIP_TRY(hipMemset((ptr) + (size_t)first * (per), 0, sizeof(*(ptr)) * (size_t)count * (per)))
+    ZR(p->D.q, LPCN_PLC_QUEUE); ZR(p->D.feat, LPCN_NB_FEAT); ZR(p->D.net, G4); ZR(p->D.dc, 2); ZR(p->D.delta, 1);
+    ZR(p->D.fec, LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); ZR(p->D.fbuf, LPCN_PLC_FBUF * LPCN_NB_FEAT); ZR(p->D.lp, LPCN_FRAME_SIZE);
+    ZR(p->D.burg, 2 * LPCN_NB_BANDS); ZR(p->D.an, LPCN_AN_NB_FEATURES);
+    ZR(b->d_keep_a, LPCN_ROWS_A); ZR(b->d_keep_b, LPCN_ROWS_B); ZR(b->d_keep_lpc, LPCN_LPC_ORDER);
+#undef ZR
+    for (int s = first; s < first + count; ++s) lpcn_plc_ctl_reset(&p->ctl[s]);
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options)
+{
+    if ((options & 3) == 1 || (options & 3) == 3 || (options & ~7)) { snprintf(g_err, sizeof(g_err), "PLC options: LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER (the non-causal mode needs a model without feature delay)"); return LPCN_E_ARG; }
+    if (b->e->plc_present == 0) { snprintf(g_err, sizeof(g_err), "the model blob has no PLC network (plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_*)"); return LPCN_E_MODEL; }
+    if (b->e->plc_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's PLC network is int8: only the float PLC network is served"); return LPCN_E_MODEL; }
+    if (b->e->plc_present != 1) { snprintf(g_err, sizeof(g_err), "the blob's PLC arrays are incomplete or do not fit together"); return LPCN_E_MODEL; }
+    DeviceGuard guard(b->e->device);
+    int rc = lpcn_batch_dev_analysis_enable(b, 1);
+    if (rc) return rc;
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (!b->plc) {
+        lpcn_plc_host *p = new lpcn_plc_host();
+        b->plc = p;
+        const size_t n = (size_t)b->n, G4 = plc_net_floats(b);
+        auto fail = [&](int code) { plc_free(b); return code; };
+#define ALP(ptr, count) if (hipMalloc((void **)&(ptr), sizeof(*(ptr)) * (count)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipMalloc failed"); return fail(LPCN_E_HIP); }
+        ALP(p->D.q, n * LPCN_PLC_QUEUE); ALP(p->D.feat, n * LPCN_NB_FEAT); ALP(p->D.net, n * G4); ALP(p->D.dc, n * 2); ALP(p->D.delta, n);
+        ALP(p->D.fec, n * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); ALP(p->D.fbuf, n * LPCN_PLC_FBUF * LPCN_NB_FEAT); ALP(p->D.lp, n * LPCN_FRAME_SIZE);
+        ALP(p->D.burg, n * 2 * LPCN_NB_BANDS); ALP(p->D.an, n * LPCN_AN_NB_FEATURES);
+        ALP(p->d_pcm, n * LPCN_FRAME_SIZE); ALP(p->d_gpcm, n * LPCN_FRAME_SIZE); ALP(p->d_gfeat, n * LPCN_NB_FEAT); ALP(p->d_ident, n);
+        p->ctl_cap = 64 * n + 64;
+        ALP(p->d_ctl, p->ctl_cap);
+        if (!b->d_state_tmp) ALP(b->d_state_tmp, n);
+        if (!b->d_keep_a) { ALP(b->d_keep_a, n * LPCN_ROWS_A); ALP(b->d_keep_b, n * LPCN_ROWS_B); ALP(b->d_keep_lpc, n * LPCN_LPC_ORDER); }
+#undef ALP
+        if (hipHostMalloc((void **)&p->h_ctl, sizeof(int) * p->ctl_cap, hipHostMallocDefault) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipHostMalloc failed"); return fail(LPCN_E_HIP); }
+        if (hipEventCreateWithFlags(&p->ev_ctl, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipEventCreate failed"); return fail(LPCN_E_HIP); }
+        std::vector<int> ident(n);
+        for (size_t i = 0; i < n; ++i) ident[i] = (int)i;
+        if (hipMemcpy(p->d_ident, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: upload failed"); return fail(LPCN_E_HIP); }
+        p->ctl.resize(n);
+    }
+    lpcn_plc_host *p = b->plc;
+    p->options = options; p->blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT; p->remove_dc = (options & 4) != 0;
+    return plc_reset_range(b, 0, b->n);
+}
+
+#define NEED_PLC(b) do { if (!(b)->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; } } while (0)
+
+extern "C" int lpcn_batch_dev_plc_reset(lpcn_batch_dev *b, int first, int count)
+{
+    NEED_PLC(b);
+    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "PLC reset range"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    return plc_reset_range(b, first, count);
+}
+
+// a group of streams through the ordinary frame and sample kernels: states, features and PCM gathered by the index map, results scattered back
+static int plc_run_group(lpcn_batch_dev *b, hipStream_t st, const PlcLaunch &L, short *d_pcm)
+{
+    lpcn_plc_host *p = b->plc;
+    const int *map = p->d_ctl + L.off;
+    const int cnt = L.cnt;
+    hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, map, cnt, 0);
+    const LaunchShape sh = {cnt, L.N, b->d_state_tmp, b->S, b->pack2, b->x3};
+    int rc = 0;
+    if (L.kind != PLC_G_TAIL) {
+        const float *src = L.feat_src == 0 ? p->D.feat : p->D.fbuf + (size_t)(L.feat_src - 1) * LPCN_NB_FEAT;
+        const size_t stride = L.feat_src == 0 ? LPCN_NB_FEAT : LPCN_PLC_FBUF * LPCN_NB_FEAT;
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, p->d_gfeat, (size_t)LPCN_NB_FEAT, src, stride, map, cnt, LPCN_NB_FEAT, 0);
+        if ((rc = launch_frames(b, sh, st, p->d_gfeat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1))) return rc;
+        if (L.keep) {      // the stream's most recent frame products (lpcnet->gru_a_condition, gru_b_condition, lpc of the reference's state)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (size_t)LPCN_ROWS_A, (const float *)b->d_cond_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 1);
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (size_t)LPCN_ROWS_B, (const float *)b->d_cond_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 1);
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 1);
+        }
+    } else {
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_cond_a, (size_t)LPCN_ROWS_A, (const float *)b->d_keep_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 0);
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (size_t)LPCN_ROWS_B, (const float *)b->d_keep_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 0);
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 0);
+    }
+    if (L.kind != PLC_G_FRAMES) {
+        if (L.pcm_src == 1)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, (const short *)p->D.q, (size_t)LPCN_PLC_QUEUE, map, cnt, L.N, 0);
+        else if (L.pcm_src == 2)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, (const short *)(d_pcm + L.pcm_off), (size_t)LPCN_FRAME_SIZE, map, cnt, L.N, 0);
+        if ((rc = launch_sample(b, sh, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, 1, L.preload, L.kind != PLC_G_TAIL))) return rc;
+        if (L.pcm_dst == 1)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, d_pcm + L.pcm_off, (size_t)LPCN_FRAME_SIZE, (const short *)p->d_gpcm, (size_t)LPCN_FRAME_SIZE, map, cnt, L.N, 1);
+    }
+    if (L.scatter)
+        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, map, cnt, 1);
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned char *lost, void *hip_stream)
+{
+    NEED_PLC(b);
+    if (!d_pcm || !lost) { snprintf(g_err, sizeof(g_err), "bad PLC step arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    lpcn_plc_host *p = b->plc;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
+    if (stream_is_capturing(st)) {
+        snprintf(g_err, sizeof(g_err), "a PLC step cannot be captured: its launch sequence depends on the loss flags"); return LPCN_E_ARG;
+    }
+    { int rco = order_begin(b, st); if (rco) return rco; }
+    if (p->ctl_pending) { HIP_TRY(hipEventSynchronize(p->ev_ctl)); p->ctl_pending = false; }      // (the previous step's lists have left the pinned buffer: long done)
+    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr);
+    if (rc) return rc;
+    const PlcPlan &P = p->plan;
+    if (P.ctl.size() > p->ctl_cap) { snprintf(g_err, sizeof(g_err), "PLC step: control lists exceed their buffer"); return LPCN_E_HIP; }
+    if (!P.ctl.empty()) {
+        memcpy(p->h_ctl, P.ctl.data(), sizeof(int) * P.ctl.size());
+        HIP_TRY(hipMemcpyAsync(p->d_ctl, p->h_ctl, sizeof(int) * P.ctl.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(p->ev_ctl, st));
+        p->ctl_pending = true;
+    }
+    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's products are the PLC's now)
+    for (const PlcLaunch &L : P.launches) {
+        const int *ctl = p->d_ctl + L.off;
+        switch (L.type) {
+        case PLC_T_BURG:
+            hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(L.cnt), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, ctl, L.cnt, d_pcm, p->D, p->remove_dc ? 1 : 0);
+            break;
+        case PLC_T_PRED:
+            hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(L.cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, L.cnt, p->D, (float *)nullptr);
+            break;
+        case PLC_T_MIX:
+            hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)p->d_gpcm, p->D, b->d_state);
+            break;
+        case PLC_T_GROUP:
+            if ((rc = plc_run_group(b, st, L, d_pcm))) return rc;
+            break;
+        case PLC_T_ANALYSIS:
+            if ((rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, 1, d_pcm, 0, (size_t)LPCN_FRAME_SIZE, b->d_an_state, p->D.an, LPCN_AN_NB_FEATURES,
+                                                   (size_t)LPCN_AN_NB_FEATURES, b->d_an_resid, b->d_an_xc, b->d_an_fw, g_err, sizeof(g_err)))) return rc;
+            break;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC step: kernel launch failed"); return LPCN_E_HIP; }
+    return order_end(b, st);
+}
+
+extern "C" int lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const unsigned char *lost)
+{
+    NEED_PLC(b);
+    if (!pcm || !lost) { snprintf(g_err, sizeof(g_err), "bad PLC step arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    lpcn_plc_host *p = b->plc;
+    hipStream_t st = b->e->stream;
+    int rc = order_begin(b, st);
+    if (rc) return rc;
+    if ((rc = tune_if_due(b, st))) return rc;
+    const size_t bytes = sizeof(short) * (size_t)b->n * LPCN_FRAME_SIZE;
+    HIP_TRY(hipMemcpyAsync(p->d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
+    if ((rc = lpcn_batch_dev_plc_step(b, p->d_pcm, lost, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(pcm, p->d_pcm, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_plc_fec_add(lpcn_batch_dev *b, int s, const float *features20)
+{
+    NEED_PLC(b);
+    if (s < 0 || s >= b->n) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    lpcn_plc_host *p = b->plc;
+    lpcn_plc_ctl &c = p->ctl[s];
+    const int keep = c.fec_keep, fill = c.fec_fill;
+    const int r = lpcn_plc_ctl_fec_add(&c, features20 == nullptr);
+    if (!features20) return 0;
+    if (r == 1) { snprintf(g_err, sizeof(g_err), "stream %d: FEC buffer full", s); return 1; }      // (the reference prints this and drops the vector)
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    float *ring = p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT;
+    if (r == 2) {
+        hipLaunchKernelGGL(lpcn::plc_fec_move_kernel, dim3(1), dim3(256), 0, b->e->stream, ring, keep, fill - keep);
+        HIP_TRY(hipStreamSynchronize(b->e->stream));
+    }
+    HIP_TRY(hipMemcpy(ring + (size_t)(c.fec_fill - 1) * LPCN_NB_FEAT, features20, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_plc_fec_clear(lpcn_batch_dev *b, int s)
+{
+    NEED_PLC(b);
+    if (s < 0 || s >= b->n) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    lpcn_plc_ctl &c = b->plc->ctl[s];
+    c.fec_keep = c.fec_read = c.fec_fill = c.fec_skip = 0;      // src/lpcnet_plc.c:129-131
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int s, lpcn_plc_state_rec *h)
+{
+    NEED_PLC(b);
+    if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    lpcn_plc_host *p = b->plc;
+    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2, G = g1 + g2;
+    memset(h, 0, sizeof(*h));
+    h->ctl = p->ctl[s]; h->g1 = g1; h->g2 = g2;
+#define DN(dst, src, count) HIP_TRY(hipMemcpy(dst, src, sizeof(*(src)) * (size_t)(count), hipMemcpyDeviceToHost))
+    DN(&h->delta, p->D.delta + s, 1); DN(h->dc, p->D.dc + 2 * (size_t)s, 2); DN(h->q, p->D.q + (size_t)s * LPCN_PLC_QUEUE, LPCN_PLC_QUEUE);
+    DN(h->feat, p->D.feat + (size_t)s * LPCN_NB_FEAT, LPCN_NB_FEAT);
+    for (int k = 0; k < 4; ++k) DN(h->net[k], p->D.net + ((size_t)s * 4 + k) * G, G);
+    DN(&h->fec[0][0], p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT, LPCN_PLC_MAX_FEC * LPCN_NB_FEAT);
+    DN(&h->fbuf[0][0], p->D.fbuf + (size_t)s * LPCN_PLC_FBUF * LPCN_NB_FEAT, LPCN_PLC_FBUF * LPCN_NB_FEAT);
+    DN(h->keep_a, b->d_keep_a + (size_t)s * LPCN_ROWS_A, LPCN_ROWS_A); DN(h->keep_b, b->d_keep_b + (size_t)s * LPCN_ROWS_B, LPCN_ROWS_B);
+    DN(h->keep_lpc, b->d_keep_lpc + (size_t)s * LPCN_LPC_ORDER, LPCN_LPC_ORDER);
+#undef DN
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int s, const lpcn_plc_state_rec *h)
+{
+    NEED_PLC(b);
+    if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2, G = g1 + g2;
+    if (h->g1 != g1 || h->g2 != g2) { snprintf(g_err, sizeof(g_err), "PLC state of a %d / %d network on a %d / %d network", h->g1, h->g2, g1, g2); return LPCN_E_ARG; }
+    {   // (the planner's own consistency check, on a copy)
+        lpcn_plc_ctl c = h->ctl;
+        const unsigned char one = 1;
+        PlcPlan P;
+        int rc = plc_plan(b->plc->options, 1, &c, &one, P, nullptr);
+        if (rc) return rc;
+    }
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    lpcn_plc_host *p = b->plc;
+    p->ctl[s] = h->ctl;
+#define UPS(dst, src, count) HIP_TRY(hipMemcpy(dst, src, sizeof(*(dst)) * (size_t)(count), hipMemcpyHostToDevice))
+    UPS(p->D.delta + s, &h->delta, 1); UPS(p->D.dc + 2 * (size_t)s, h->dc, 2); UPS(p->D.q + (size_t)s * LPCN_PLC_QUEUE, h->q, LPCN_PLC_QUEUE);
+    UPS(p->D.feat + (size_t)s * LPCN_NB_FEAT, h->feat, LPCN_NB_FEAT);
+    for (int k = 0; k < 4; ++k) UPS(p->D.net + ((size_t)s * 4 + k) * G, h->net[k], G);
+    UPS(p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT, &h->fec[0][0], LPCN_PLC_MAX_FEC * LPCN_NB_FEAT);
+    UPS(p->D.fbuf + (size_t)s * LPCN_PLC_FBUF * LPCN_NB_FEAT, &h->fbuf[0][0], LPCN_PLC_FBUF * LPCN_NB_FEAT);
+    UPS(b->d_keep_a + (size_t)s * LPCN_ROWS_A, h->keep_a, LPCN_ROWS_A); UPS(b->d_keep_b + (size_t)s * LPCN_ROWS_B, h->keep_b, LPCN_ROWS_B);
+    UPS(b->d_keep_lpc + (size_t)s * LPCN_LPC_ORDER, h->keep_lpc, LPCN_LPC_ORDER);
+#undef UPS
+    return 0;
+}
+
+// parity seam: burg_cepstral_analysis on one frame per stream.  x holds PCM values as the PLC feeds them (x[i] = pcm[i], src/lpcnet_plc.c:206):
+// integers of the int16 range.
+extern "C" int lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, float *ceps36)
+{
+    NEED_PLC(b);
+    if (!x || !ceps36) { snprintf(g_err, sizeof(g_err), "bad arguments"); return LPCN_E_ARG; }
+    const size_t count = (size_t)b->n * LPCN_FRAME_SIZE;
+    std::vector<short> pc(count);
+    for (size_t i = 0; i < count; ++i) {
+        if (!(x[i] >= -32768.f && x[i] <= 32767.f) || x[i] != (float)(int)x[i]) { snprintf(g_err, sizeof(g_err), "plc_burg: samples must be integers of the int16 range"); return LPCN_E_ARG; }
+        pc[i] = (short)(int)x[i];
+    }
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    lpcn_plc_host *p = b->plc;
+    hipStream_t st = b->e->stream;
+    HIP_TRY(hipMemcpy(p->d_pcm, pc.data(), sizeof(short) * count, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(b->n), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, (const int *)p->d_ident, b->n, p->d_pcm, p->D, 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(ceps36, p->D.burg, sizeof(float) * (size_t)b->n * 2 * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// parity seam: compute_plc_pred on every stream's network state (which advances), any 57 inputs
+extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57, float *out20)
+{
+    NEED_PLC(b);
+    if (!in57 || !out20) { snprintf(g_err, sizeof(g_err), "bad arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    lpcn_plc_host *p = b->plc;
+    hipStream_t st = b->e->stream;
+    std::vector<int> recs((size_t)b->n * lpcn::PLC_PRED_REC, 0);
+    if (recs.size() > p->ctl_cap) { snprintf(g_err, sizeof(g_err), "plc_pred: control buffer"); return LPCN_E_HIP; }
+    for (int s = 0; s < b->n; ++s) {
+        const float *in = in57 + (size_t)s * LPCN_PLC_IN;
+        int *r = &recs[(size_t)s * lpcn::PLC_PRED_REC];
+        r[0] = s; r[1] = lpcn::PLC_F_COMPUTE | lpcn::PLC_F_RAW; r[3] = float_bits(in[LPCN_PLC_IN - 1]);
+        HIP_TRY(hipMemcpy(p->D.burg + (size_t)s * 2 * LPCN_NB_BANDS, in, sizeof(float) * 2 * LPCN_NB_BANDS, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->D.an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(p->d_ctl, recs.data(), sizeof(int) * recs.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(b->n), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, (const int *)p->d_ctl, b->n, p->D, p->d_gfeat);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(out20, p->d_gfeat, sizeof(float) * (size_t)b->n * LPCN_NB_FEAT, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -73,6 +73,26 @@ extern "C" {
 #define LPCN_X3_FREE 9
 #define LPCN_DEAL_EH_FAST_I8 0 /* head length of the FAST arithmetic's own image of int8 blobs (model_pack.c: lpcn_model_pack_fast) */
 
+/* ---- the packet-loss concealment's own network (compute_plc_pred, src/lpcnet_plc.c:135-146): dense 57 -> d1 tanh, GRU d1 -> g1,
+ * GRU g1 -> g2, dense g2 -> 20 linear, bound by name like the reference's init_plc_model.  The widths are read from the bias lengths. */
+#define LPCN_PLC_IN       (2 * LPCN_NB_BANDS + LPCN_NB_FEAT + 1)
+#define LPCN_PLC_MAX_UNITS 512
+#define LPCN_PLC_MAX_FEC   100      /* PLC_MAX_FEC, src/lpcnet_private.h:25 */
+#define LPCN_PLC_BUF_SIZE  (LPCN_FEATURES_DELAY * LPCN_FRAME_SIZE + 80)      /* PLC_BUF_SIZE, src/lpcnet_private.h:77 */
+#define LPCN_PLC_QUEUE     (LPCN_PLC_BUF_SIZE + LPCN_FRAME_SIZE)
+#define LPCN_PLC_FBUF      4        /* MAX_FEATURE_BUFFER_SIZE, src/lpcnet_private.h:26 */
+typedef struct lpcn_plc_model {
+    int present;                 /* 0: the blob has no plc_* arrays; 1: float arrays; 2: int8 arrays (not served); -1: incomplete or inconsistent arrays */
+    int d1, g1, g2;              /* dense1 width, GRU widths */
+    int nb1, nb2;                /* 8x4 blocks of the two GRU input matrices */
+    const float *dense1_w, *dense1_b;            /* [57][d1], [d1] */
+    const float *gru1_w, *gru1_rec, *gru1_bias;  /* blocks [nb1][4][8], [g1][3 g1], [2][3 g1] */
+    const int *gru1_idx;
+    const float *gru2_w, *gru2_rec, *gru2_bias;
+    const int *gru2_idx;
+    const float *out_w, *out_b;                  /* [g2][20], [20] */
+} lpcn_plc_model;
+
 typedef struct lpcn_model_host {
     int is_int8;                 /* blob flavour: 0 = float qweights (DISABLE_DOT_PROD), 1 = int8 (DOT_PROD)  */
     int b_dense;                 /* GRU-B input matrix lists every input block for every row group */
@@ -108,6 +128,7 @@ typedef struct lpcn_model_host {
     int32_t *pk_b_start;  /* [6 groups + 1] first block of each group in pk_b_w                */
     uint8_t *pk_b_blk;    /* [nb_b] input block index per block                                */
     float   *pk_emb[3];   /* sig/pred/exc tables re-ordered to [256][3 slots][512 threads] */
+    lpcn_plc_model plc;   /* the PLC network of the same blob, when it has one (pointers into the blob) */
 } lpcn_model_host;
 
 /* GRU-A dealt to the twelve waves of sample_kernel_x3 (float blobs).  A wave holds LPCN_X3_NW items per lane: segment 0 -- the HEAD of a candidate
@@ -280,6 +301,46 @@ int  lpcn_batch_dev_compute_features(lpcn_batch_dev *b, const short *d_pcm, floa
 int  lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, unsigned char *packets, float *features, int feat_stride, int n_packets);
 int  lpcn_batch_dev_get_encoder_vq_mem(lpcn_batch_dev *b, int stream, float *out18);
 int  lpcn_batch_dev_set_encoder_vq_mem(lpcn_batch_dev *b, int stream, const float *in18);
+
+/* Packet-loss concealment (lpcnet_plc_update / lpcnet_plc_conceal in causal mode per stream, plc_kernels.hip.h).
+ * The control state of a stream -- everything src/lpcnet_plc.c:188-340 branches on -- is a function of the loss flags and the FEC calls
+ * alone and lives on the host; samples, features and network states live on the device. */
+typedef struct lpcn_plc_ctl {
+    int32_t pcm_fill, skip_analysis, blend, loss_count;      /* LPCNetPLCState, src/lpcnet_private.h:79-105 */
+    int32_t fec_fill, fec_keep, fec_read, fec_skip;
+    int32_t fbuf_fill;                                        /* feature_buffer_fill of the stream's LPCNetState */
+} lpcn_plc_ctl;
+/* one stream's PLC state as lpcnet_batch_get_plc_state / _set_plc_state carry it: both halves, and the frame products of the synthesis state */
+typedef struct lpcn_plc_state_rec {
+    lpcn_plc_ctl ctl;
+    int32_t g1, g2, delta;
+    double dc[2];                                             /* dc_mem, syn_dc */
+    short q[LPCN_PLC_QUEUE];
+    float feat[LPCN_NB_FEAT];
+    float net[4][2 * LPCN_PLC_MAX_UNITS];                     /* plc_net, plc_copy[0..2]: g1 + g2 floats each */
+    float fec[LPCN_PLC_MAX_FEC][LPCN_NB_FEAT];
+    float fbuf[LPCN_PLC_FBUF][LPCN_NB_FEAT];
+    float keep_a[LPCN_ROWS_A], keep_b[LPCN_ROWS_B], keep_lpc[LPCN_LPC_ORDER];
+} lpcn_plc_state_rec;
+#define LPCN_PLC_SUMMARY 10
+/* The planner alone, without a device: advances ctl[0..n) by one step with the given loss flags and writes per stream
+ * {lost, flushed queue entries, queue rounds, their samples, FEC vectors used, first frame after a loss (1 cross-fade, 2 codec restore),
+ *  queue operation (1 tail, 2 append, 3 push and shift), prediction kept on a received frame, deferred features appended, loss_count after}. */
+int  lpcn_plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary);
+void lpcn_plc_ctl_reset(lpcn_plc_ctl *c);
+int  lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null);     /* host half of lpcnet_plc_fec_add: 0 stored / skipped, 1 dropped (ring full), 2 stored after a compaction */
+int  lpcn_engine_plc_present(const lpcn_engine *e);           /* lpcn_plc_model.present of the engine's blob */
+int  lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options);
+int  lpcn_batch_dev_plc_enabled(const lpcn_batch_dev *b);
+int  lpcn_batch_dev_plc_reset(lpcn_batch_dev *b, int first, int count);
+int  lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned char *lost, void *hip_stream);      /* enqueue only; lost is a host array */
+int  lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const unsigned char *lost);
+int  lpcn_batch_dev_plc_fec_add(lpcn_batch_dev *b, int stream, const float *features20);
+int  lpcn_batch_dev_plc_fec_clear(lpcn_batch_dev *b, int stream);
+int  lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int stream, lpcn_plc_state_rec *host);
+int  lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int stream, const lpcn_plc_state_rec *host);
+int  lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, float *ceps36);
+int  lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57, float *out20);
 
 /* Timing of the most recent run: kernel-only milliseconds measured with HIP events on the
  * stream the kernels were launched on (sample kernel, frame kernels). */

@@ -491,6 +491,57 @@ static int pack_gru_b(lpcn_model_host *m)
     return 0;
 }
 
+/* The PLC network of the blob, bound like the reference's init_plc_model binds it (dense_init / gru_init of
+ * src/parse_lpcnet_weights.c:124-220 with the names training_tf2/dump_plc.py emits) except that the widths come from the bias
+ * lengths.  No plc_* array at all: present = 0 and success.  Some but not all, or sizes that do not fit together: -1 (the caller sets present = -1). */
+static int parse_plc_gru(const blob_rec *rec, int n, const char *name, int n_in, int *units, int *nb, const float **w, const int **idx,
+                         const float **rw, const float **bias, int *is_int8)
+{
+    char key[64];
+    snprintf(key, sizeof(key), "%s_bias", name);
+    const blob_rec *b = blob_find(rec, n, key);
+    if (!b || b->size <= 0 || b->size % (6 * 8 * (int)sizeof(float))) return -1;      /* [2][3 N] floats, N a multiple of 8 */
+    const int N = b->size / (6 * (int)sizeof(float));
+    if (N > LPCN_PLC_MAX_UNITS || (n_in & 3)) return -1;
+    *units = N; *bias = (const float *)b->data;
+    snprintf(key, sizeof(key), "%s_subias", name);
+    if (!blob_need(rec, n, key, sizeof(float) * 6 * (size_t)N)) return -1;
+    snprintf(key, sizeof(key), "%s_weights_idx", name);
+    if (!(*idx = blob_need_idx(rec, n, key, n_in, 3 * N, nb))) return -1;
+    snprintf(key, sizeof(key), "%s_weights", name);
+    const blob_rec *q = blob_find(rec, n, key);
+    if (!q) return -1;
+    if ((size_t)q->size == sizeof(float) * 32 * (size_t)*nb) *is_int8 = 0;
+    else if (q->size == 32 * *nb) *is_int8 = 1;
+    else return -1;
+    *w = (const float *)q->data;
+    snprintf(key, sizeof(key), "%s_recurrent_weights", name);
+    if (!(*rw = (const float *)blob_need(rec, n, key, (*is_int8 ? 1 : sizeof(float)) * 3 * (size_t)N * N))) return -1;
+    return 0;
+}
+
+static int parse_plc(lpcn_plc_model *p, const blob_rec *rec, int n)
+{
+    memset(p, 0, sizeof(*p));
+    int any = 0;
+    for (int i = 0; i < n; i++) if (!strncmp(rec[i].name, "plc_", 4)) any = 1;
+    if (!any) return 0;
+    const blob_rec *b1 = blob_find(rec, n, "plc_dense1_bias");
+    if (!b1 || b1->size <= 0 || b1->size % (4 * (int)sizeof(float))) return -1;
+    p->d1 = b1->size / (int)sizeof(float);
+    if (p->d1 > LPCN_PLC_MAX_UNITS) return -1;
+    p->dense1_b = (const float *)b1->data;
+    if (!(p->dense1_w = (const float *)blob_need(rec, n, "plc_dense1_weights", sizeof(float) * LPCN_PLC_IN * (size_t)p->d1))) return -1;
+    int i8a = 0, i8b = 0;
+    if (parse_plc_gru(rec, n, "plc_gru1", p->d1, &p->g1, &p->nb1, &p->gru1_w, &p->gru1_idx, &p->gru1_rec, &p->gru1_bias, &i8a)) return -1;
+    if (parse_plc_gru(rec, n, "plc_gru2", p->g1, &p->g2, &p->nb2, &p->gru2_w, &p->gru2_idx, &p->gru2_rec, &p->gru2_bias, &i8b)) return -1;
+    if (i8a != i8b) return -1;
+    if (!(p->out_w = (const float *)blob_need(rec, n, "plc_out_weights", sizeof(float) * LPCN_NB_FEAT * (size_t)p->g2))) return -1;
+    if (!(p->out_b = (const float *)blob_need(rec, n, "plc_out_bias", sizeof(float) * LPCN_NB_FEAT))) return -1;
+    p->present = i8a ? 2 : 1;
+    return 0;
+}
+
 int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
 {
     blob_rec rec[64];
@@ -544,6 +595,7 @@ int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
     if (!(m->b_rec = (const float *)blob_need(rec, n, "gru_b_recurrent_weights", q * LPCN_ROWS_B * LPCN_N_B))) return -1;
 
     if (pack_gru_a(m, 0) || pack_gru_b(m)) { lpcn_model_release(m); return -1; }
+    if (parse_plc(&m->plc, rec, n)) { memset(&m->plc, 0, sizeof(m->plc)); m->plc.present = -1; }      /* (the LPCNet model loads as before; lpcnet_batch_plc_enable reports it) */
     return 0;
 }
 

@@ -1,0 +1,394 @@
+// Packet-loss concealment on the device: the data side of lpcnet_plc_update / lpcnet_plc_conceal in causal mode
+// (src/lpcnet_plc.c:188-340) for every stream of a batch, bit for bit like the reference's generic-C float build.  The control side
+// -- which branch a stream takes in this step -- is a function of the loss flags and the FEC calls alone and lives on the host
+// (engine.hip: plc_plan); each kernel here works on the streams the host listed for it:
+//   plc_burg_kernel   DC removal (src/lpcnet_plc.c:196-205) and burg_cepstral_analysis (src/freq.c:156-199) of a received frame
+//   plc_pred_kernel   compute_plc_pred (src/lpcnet_plc.c:135-146) with its input selection (get_fec_or_pred :148-168), the rotation and
+//                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
+//   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
+//   plc_rows_kernel   gather / scatter of rows by an index map: a group of streams runs through the ordinary frame and sample kernels
+// Every sum keeps the reference's order; products and sums are rounded separately (-ffp-contract=off).
+#pragma once
+#include "lpcnet_log10.h"
+#include "lpcnet_plc_tables_gen.h"
+#include "plc_burg.h"
+
+namespace lpcn {
+
+// the PLC network on the device (widths from the blob; the sparse GRU input matrices as the blob has them plus per-row-group starts)
+struct PlcNet {
+    int d1, g1, g2;
+    const float *dense1_w, *dense1_b;
+    const float *gru1_w, *gru1_rec, *gru1_bias;
+    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input position of a block
+    const float *gru2_w, *gru2_rec, *gru2_bias;
+    const int *gru2_start, *gru2_pos;
+    const float *out_w, *out_b;
+    const float *tansig;
+};
+
+// per-stream PLC data (the fields of LPCNetPLCState that hold samples, features and network state; src/lpcnet_private.h:79-105)
+struct PlcData {
+    short *q;            // [n][560] st->pcm
+    float *feat;         // [n][20]  st->features
+    float *net;          // [n][4][g1 + g2]: plc_net, plc_copy[0..2]
+    double *dc;          // [n][2]   dc_mem, syn_dc
+    int *delta;          // [n]      the step's `delta` (src/lpcnet_plc.c:198)
+    float *fec;          // [n][100][20]
+    float *fbuf;         // [n][4][20] the synthesis state's deferred feature queue (src/lpcnet.c:122-144)
+    short *lp;           // [n][160] the step's low-pass samples
+    float *burg;         // [n][36]
+    float *an;           // [n][36]  analysis of the step's frame
+};
+
+constexpr int PLC_BURG_THREADS = 128;
+constexpr int PLC_PRED_THREADS = 256;
+constexpr int PLC_MIX_THREADS = 512;
+constexpr int PLC_PRED_REC = 6;      // ints per record of plc_pred_kernel: stream, flags, FEC row, two float offsets, unused
+constexpr int PLC_MIX_REC = 3;       // ints per record of plc_mix_kernel: stream, a, b
+
+enum { PLC_F_ROT = 1, PLC_F_RESTORE_SHIFT = 1, PLC_F_INPUT_SHIFT = 3, PLC_F_COMPUTE = 32, PLC_F_KEEP = 64, PLC_F_ATT = 128, PLC_F_RAW = 256 };
+enum { PLC_IN_ZEROS = 0, PLC_IN_FEC = 1, PLC_IN_BURG = 2, PLC_IN_BURG_FEAT = 3 };
+enum { PLC_MIX_QTAIL, PLC_MIX_QAPPEND, PLC_MIX_QPUSH, PLC_MIX_QSHIFT, PLC_MIX_FAPPEND, PLC_MIX_RESETSIG, PLC_MIX_DCRECV, PLC_MIX_DCLOST, PLC_MIX_XFADE };
+
+#define LPCN_PLC_DC_CONST 0.003      // src/lpcnet_plc.c:183
+
+// One workgroup per listed stream, wave h on half frame h.  pcm [n][160] is the call's frame: with the DC filter it is rewritten in place.
+__global__ __launch_bounds__(PLC_BURG_THREADS) void plc_burg_kernel(LpcnFrameModel M, const int *map, int cnt, short *pcm, PlcData D, int remove_dc)
+{
+    __shared__ float xin[2][80];
+    __shared__ double cauto[2][LPCN_BURG_ORDER + 1];
+    __shared__ double work[2][LPCN_BURG_WORK];
+    __shared__ float acoef[2][LPCN_BURG_ORDER];
+    __shared__ float gres[2];
+    __shared__ cpx fbuf[2][320];
+    __shared__ float exb[2][LPCN_NB_BANDS], lyb[2][LPCN_NB_BANDS], cepb[2][LPCN_NB_BANDS];
+    if ((int)blockIdx.x >= cnt) return;
+    const int s = map[blockIdx.x];
+    const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
+    short *p = pcm + (size_t)s * LPCN_FRAME_SIZE;
+    if (remove_dc) {
+        // src/lpcnet_plc.c:196-205: serial in double
+        if (threadIdx.x == 0) {
+            double dc_mem = D.dc[2 * s], syn_dc = D.dc[2 * s + 1];
+            dc_mem += syn_dc;
+            D.delta[s] = (int)syn_dc;
+            short *lp = D.lp + (size_t)s * LPCN_FRAME_SIZE;
+            for (int i = 0; i < LPCN_FRAME_SIZE; ++i) {
+                const short l = (short)(int)floor(.5 + dc_mem);
+                dc_mem += LPCN_PLC_DC_CONST * ((double)p[i] - dc_mem);
+                lp[i] = l;
+                p[i] = (short)((int)p[i] - (int)l);
+            }
+            D.dc[2 * s] = dc_mem;
+            D.dc[2 * s + 1] = 0.0;
+        }
+        __syncthreads();
+    }
+    // compute_burg_cepstrum (src/freq.c:156-188) on half h
+    const short *ph = p + h * 80;
+    for (int i = lane; i < LPCN_BURG_LEN; i += 64) xin[h][i] = (float)ph[i + 1] - 0.85f * (float)ph[i];
+    __syncthreads();
+    if (lane <= LPCN_BURG_ORDER) cauto[h][lane] = lpcn_burg_inner(xin[h], xin[h] + lane, LPCN_BURG_LEN - lane);
+    __syncthreads();
+    if (lane == 0) {
+        const float g = lpcn_burg_recursion(acoef[h], xin[h], cauto[h], work[h]);
+        gres[h] = g / 50.f;                          // g /= len - 2*(order-1)
+    }
+    __syncthreads();
+    cpx *F = fbuf[h];
+    for (int k = lane; k < 320; k += 64) {
+        float v = 0.f;
+        if (k == 0) v = 1.f;
+        else if (k <= LPCN_BURG_ORDER) v = (float)((double)(-acoef[h][k - 1]) * lpcn_plc_pow995[k - 1]);
+        cpx z; z.r = 0.0031250000f * v; z.i = 0.0031250000f * 0.f;
+        F[M.tab_bitrev[k]] = z;
+    }
+    __syncthreads();
+    fft320_passes(F, (const cpx *)M.tab_tw, lane);
+    // compute_band_energy_inverse (src/freq.c:60-84), scaling and log10 (:177-179)
+    if (lane < LPCN_NB_BANDS) {
+        float sum = 0.f;
+        if (lane > 0) {
+            const int lo = lpcn_eband5ms[lane - 1] * 4, size = (lpcn_eband5ms[lane] - lpcn_eband5ms[lane - 1]) * 4;
+            for (int j = 0; j < size; ++j) {
+                const float frac = (float)j / (float)size;
+                const cpx X = F[lo + j];
+                float tmp = X.r * X.r;
+                tmp = tmp + X.i * X.i;
+                tmp = (float)(1.0 / ((double)tmp + 1e-9));
+                sum = sum + frac * tmp;
+            }
+        }
+        if (lane < LPCN_NB_BANDS - 1) {
+            const int lo = lpcn_eband5ms[lane] * 4, size = (lpcn_eband5ms[lane + 1] - lpcn_eband5ms[lane]) * 4;
+            for (int j = 0; j < size; ++j) {
+                const float frac = (float)j / (float)size;
+                const cpx X = F[lo + j];
+                float tmp = X.r * X.r;
+                tmp = tmp + X.i * X.i;
+                tmp = (float)(1.0 / ((double)tmp + 1e-9));
+                sum = sum + (1.f - frac) * tmp;
+            }
+        }
+        if (lane == 0 || lane == LPCN_NB_BANDS - 1) sum = sum * 2.f;
+        const float inv_w3 = 1.f / ((320.f * 320.f) * 320.f);
+        sum = (float)((double)sum * ((.45 * (double)gres[h]) * (double)inv_w3));
+        lyb[h][lane] = lpcn_log10f_of_double(1e-2 + (double)sum);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        float logMax = -2.f, follow = -2.f;
+        for (int i = 0; i < LPCN_NB_BANDS; ++i) {
+            float v = lyb[h][i];
+            const float f25 = follow - 2.5f, m8 = logMax - 8.f;
+            const float inner = LPCN_MAX16(f25, v);
+            v = LPCN_MAX16(m8, inner);
+            logMax = LPCN_MAX16(logMax, v);
+            follow = LPCN_MAX16(f25, v);
+            exb[h][i] = v;
+        }
+    }
+    __syncthreads();
+    if (lane < LPCN_NB_BANDS) {
+        float sum = 0.f;
+        for (int j = 0; j < LPCN_NB_BANDS; ++j) sum = sum + exb[h][j] * M.tab_idct[j * LPCN_NB_BANDS + lane];
+        float c = (float)((double)sum * sqrt(2. / LPCN_NB_BANDS));
+        if (lane == 0) c = c - 4.f;
+        cepb[h][lane] = c;
+    }
+    __syncthreads();
+    // burg_cepstral_analysis (src/freq.c:190-199): mean and difference of the halves
+    if (h == 0 && lane < LPCN_NB_BANDS) {
+        const float c0 = cepb[0][lane], c1 = cepb[1][lane];
+        float *o = D.burg + (size_t)s * 2 * LPCN_NB_BANDS;
+        o[lane] = (float)(.5 * (double)(c0 + c1));
+        o[LPCN_NB_BANDS + lane] = c0 - c1;
+    }
+}
+
+// compute_gruB with a zero condition (src/nnet.c:326-372, float build: sparse_sgemv_accum8x4 src/vec.h:347-403, sgemv_accum src/nnet.c:73-86):
+// lane = row, columns in the reference's order.  x [n_in] and hs [N] (the state, replaced) in LDS; zrh / recur [3 N] LDS scratch.
+__device__ __forceinline__ void plc_gru(const int N, const float *W, const int *start, const int *pos, const float *R, const float *bias,
+                                        const float *x, float *hs, float *zrh, float *recur, const float *tansig)
+{
+    const int rows = 3 * N;
+    for (int row = threadIdx.x; row < rows; row += blockDim.x) {
+        float z = bias[row] + 0.f;
+        const int grp = row >> 3, r = row & 7;
+        for (int blk = start[grp]; blk < start[grp + 1]; ++blk) {
+            const float *w = W + (size_t)blk * 32 + r;
+            const float *xp = x + pos[blk];
+            z = z + w[0] * xp[0];
+            z = z + w[8] * xp[1];
+            z = z + w[16] * xp[2];
+            z = z + w[24] * xp[3];
+        }
+        zrh[row] = z;
+        float rc = bias[rows + row];
+        for (int j = 0; j < N; ++j) rc = rc + R[(size_t)j * rows + row] * hs[j];
+        recur[row] = rc;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * N; i += blockDim.x) zrh[i] = lpcn_sigmoid(zrh[i] + recur[i], tansig);
+    __syncthreads();
+    float hn[(LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS];
+#pragma unroll
+    for (int t = 0; t < (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS; ++t) {
+        const int i = threadIdx.x + t * PLC_PRED_THREADS;
+        hn[t] = 0.f;
+        if (i < N) {
+            float hh = zrh[2 * N + i] + recur[2 * N + i] * zrh[N + i];
+            hh = lpcn_tanh(hh, tansig);
+            const float z = zrh[i];
+            hn[t] = z * hs[i] + (1.f - z) * hh;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS; ++t) {
+        const int i = threadIdx.x + t * PLC_PRED_THREADS;
+        if (i < N) hs[i] = hn[t];
+    }
+    __syncthreads();
+}
+
+// One workgroup per record.  flags: PLC_F_ROT rotate plc_copy and store plc_net in plc_copy[0]; restore k (1, 2): plc_net = plc_copy[k];
+// PLC_F_COMPUTE run the network on the selected input; PLC_F_KEEP features = its output (FEC input: features = the FEC vector, the
+// output is discarded); PLC_F_ATT features[0] = MAX16(-10, features[0] + a1 - a2).  PLC_F_RAW (the parity seam): the input is
+// [burg36, an20, a1] as given and the output goes to raw_out [n][20].
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    __shared__ float in[LPCN_PLC_IN + 3];
+    __shared__ float d1[LPCN_PLC_MAX_UNITS], h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
+    __shared__ float zrh[3 * LPCN_PLC_MAX_UNITS], recur[3 * LPCN_PLC_MAX_UNITS];
+    __shared__ float out[LPCN_NB_FEAT];
+    if ((int)blockIdx.x >= cnt) return;
+    const int *rec = ctl + (size_t)blockIdx.x * PLC_PRED_REC;
+    const int s = rec[0], flags = rec[1], fec_row = rec[2];
+    const float a1 = __int_as_float(rec[3]), a2 = __int_as_float(rec[4]);
+    const int G = P.g1 + P.g2;
+    float *net = D.net + (size_t)s * 4 * G;
+    const int restore = (flags >> PLC_F_RESTORE_SHIFT) & 3, input = (flags >> PLC_F_INPUT_SHIFT) & 3;
+    for (int t = threadIdx.x; t < G; t += blockDim.x) {
+        float v0 = net[t];
+        if (flags & PLC_F_ROT) {
+            const float v1 = net[G + t], v2 = net[2 * G + t];
+            net[G + t] = v0; net[2 * G + t] = v1; net[3 * G + t] = v2;
+        }
+        if (restore) { v0 = net[(restore + 1) * G + t]; net[t] = v0; }
+        if (t < P.g1) h1[t] = v0; else h2[t - P.g1] = v0;
+    }
+    if (!(flags & PLC_F_COMPUTE)) return;
+    float *feat = D.feat + (size_t)s * LPCN_NB_FEAT;
+    const float *fec = D.fec + ((size_t)s * LPCN_PLC_MAX_FEC + fec_row) * LPCN_NB_FEAT;
+    if (threadIdx.x < LPCN_PLC_IN) {
+        const int j = threadIdx.x;
+        float v = 0.f;
+        if (input >= PLC_IN_BURG && j < 2 * LPCN_NB_BANDS) v = D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j];
+        if (j >= 2 * LPCN_NB_BANDS && j < LPCN_PLC_IN - 1) {
+            if (input == PLC_IN_FEC) v = fec[j - 2 * LPCN_NB_BANDS];
+            if (input == PLC_IN_BURG_FEAT) v = D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS];
+        }
+        if (j == LPCN_PLC_IN - 1) v = input == PLC_IN_FEC ? -1.f : input == PLC_IN_ZEROS ? 0.f : 1.f;
+        if (flags & PLC_F_RAW) v = j < 2 * LPCN_NB_BANDS ? D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j] : j < LPCN_PLC_IN - 1 ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS] : a1;
+        in[j] = v;
+    }
+    __syncthreads();
+    // _lpcnet_compute_dense (src/nnet.c:122-135), tanh
+    for (int i = threadIdx.x; i < P.d1; i += blockDim.x) {
+        float acc = P.dense1_b[i];
+        for (int j = 0; j < LPCN_PLC_IN; ++j) acc = acc + P.dense1_w[(size_t)j * P.d1 + i] * in[j];
+        d1[i] = lpcn_tanh(acc, P.tansig);
+    }
+    __syncthreads();
+    plc_gru(P.g1, P.gru1_w, P.gru1_start, P.gru1_pos, P.gru1_rec, P.gru1_bias, d1, h1, zrh, recur, P.tansig);
+    plc_gru(P.g2, P.gru2_w, P.gru2_start, P.gru2_pos, P.gru2_rec, P.gru2_bias, h1, h2, zrh, recur, P.tansig);
+    if (threadIdx.x < LPCN_NB_FEAT) {
+        const int i = threadIdx.x;
+        float acc = P.out_b[i];
+        for (int j = 0; j < P.g2; ++j) acc = acc + P.out_w[(size_t)j * LPCN_NB_FEAT + i] * h2[j];
+        if (i == LPCN_NB_FEAT - 1) { const float v = acc + .1f; acc = .5f < v ? .5f : v; }      // MIN16(.5f, out[19]+.1f)
+        out[i] = acc;
+    }
+    for (int t = threadIdx.x; t < G; t += blockDim.x) net[t] = t < P.g1 ? h1[t] : h2[t - P.g1];
+    __syncthreads();
+    if (threadIdx.x < LPCN_NB_FEAT) {
+        const int i = threadIdx.x;
+        float v = 0.f;
+        bool write = false;
+        if (input == PLC_IN_FEC) { v = fec[i]; write = true; }
+        else if (flags & PLC_F_KEEP) { v = out[i]; write = true; }
+        if (write && i == 0 && (flags & PLC_F_ATT)) {
+            v = v + a1;
+            v = v - a2;
+            v = -10.f > v ? -10.f : v;
+        }
+        if (write) feat[i] = v;
+        if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = out[i];
+    }
+}
+
+// Element-wise per-stream operations.  One workgroup per record {stream, a, b}; pcm [n][160] is the call's frame, gpcm the compacted
+// PCM of the group that has just run (row a of it belongs to this record's stream).
+__global__ __launch_bounds__(PLC_MIX_THREADS) void plc_mix_kernel(int op, const int *ctl, int cnt, short *pcm, const short *gpcm, PlcData D, lpcn_stream_state *states)
+{
+    if ((int)blockIdx.x >= cnt) return;
+    const int *rec = ctl + (size_t)blockIdx.x * PLC_MIX_REC;
+    const int s = rec[0], a = rec[1], b = rec[2];
+    const int t = threadIdx.x;
+    short *p = pcm + (size_t)s * LPCN_FRAME_SIZE;
+    short *q = D.q + (size_t)s * LPCN_PLC_QUEUE;
+    switch (op) {
+    case PLC_MIX_QTAIL:           // RNN_COPY(st->pcm, &pcm[80], 80), src/lpcnet_plc.c:249
+        if (t < 80) q[t] = p[80 + t];
+        break;
+    case PLC_MIX_QAPPEND:         // RNN_COPY(&st->pcm[st->pcm_fill], pcm, 160), :252
+        if (t < LPCN_FRAME_SIZE) q[a + t] = p[t];
+        break;
+    case PLC_MIX_QPUSH: {         // st->pcm[400 + i] = pcm[i]; RNN_MOVE(st->pcm, &st->pcm[160], 400), :276-285
+        short v = 0;
+        if (t < LPCN_PLC_BUF_SIZE) v = t + LPCN_FRAME_SIZE < LPCN_PLC_BUF_SIZE ? q[t + LPCN_FRAME_SIZE] : p[t + LPCN_FRAME_SIZE - LPCN_PLC_BUF_SIZE];
+        __syncthreads();
+        if (t < LPCN_PLC_BUF_SIZE) q[t] = v;
+        if (t < LPCN_FRAME_SIZE) q[LPCN_PLC_BUF_SIZE + t] = p[t];
+        break;
+    }
+    case PLC_MIX_QSHIFT: {        // RNN_MOVE(st->pcm, &st->pcm[160], 400), :310
+        short v = 0;
+        if (t < LPCN_PLC_BUF_SIZE) v = q[t + LPCN_FRAME_SIZE];
+        __syncthreads();
+        if (t < LPCN_PLC_BUF_SIZE) q[t] = v;
+        break;
+    }
+    case PLC_MIX_FAPPEND: {       // run_frame_network_deferred (src/lpcnet.c:122-133): a = fill before, b = 0 st->features, 1 the analysed features
+        float *fb = D.fbuf + (size_t)s * LPCN_PLC_FBUF * LPCN_NB_FEAT;
+        float v = 0.f;
+        const bool full = a == LPCN_PLC_FBUF;
+        if (full && t < (LPCN_PLC_FBUF - 1) * LPCN_NB_FEAT) v = fb[t + LPCN_NB_FEAT];
+        __syncthreads();
+        if (full && t < (LPCN_PLC_FBUF - 1) * LPCN_NB_FEAT) fb[t] = v;
+        const int row = full ? LPCN_PLC_FBUF - 1 : a;
+        if (t < LPCN_NB_FEAT) fb[row * LPCN_NB_FEAT + t] = b ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + t] : D.feat[(size_t)s * LPCN_NB_FEAT + t];
+        break;
+    }
+    case PLC_MIX_RESETSIG: {      // lpcnet_reset_signal (src/lpcnet.c:225-232)
+        lpcn_stream_state *st = &states[s];
+        for (int k = t; k < LPCN_N_A; k += blockDim.x) st->gru_a[k] = 0.f;
+        if (t < LPCN_N_B) st->gru_b[t] = 0.f;
+        if (t < LPCN_LPC_ORDER) st->last_sig[t] = 0.f;
+        if (t == 0) { st->deemph_mem = 0.f; st->last_exc = lpcn_lin2ulaw(0.f); }
+        break;
+    }
+    case PLC_MIX_DCRECV:          // pcm[i] += lp[i], :288-292
+        if (t < LPCN_FRAME_SIZE) p[t] = (short)((int)p[t] + (int)D.lp[(size_t)s * LPCN_FRAME_SIZE + t]);
+        break;
+    case PLC_MIX_DCLOST:          // :334-339: serial in double
+        if (t == 0) {
+            double syn_dc = D.dc[2 * s + 1];
+            const int dc = (int)floor(.5 + D.dc[2 * s]);
+            for (int i = 0; i < LPCN_FRAME_SIZE; ++i) {
+                syn_dc += LPCN_PLC_DC_CONST * ((double)p[i] - syn_dc);
+                p[i] = (short)((int)p[i] + dc);
+            }
+            D.dc[2 * s + 1] = syn_dc;
+        }
+        break;
+    case PLC_MIX_XFADE:           // :229-233
+        if (t < 80) {
+            const float w = lpcn_plc_fade[t];
+            const int delta = D.delta[s];
+            const float x0 = w * (float)p[t];
+            const float x1 = (1.f - w) * (float)((int)gpcm[(size_t)a * LPCN_FRAME_SIZE + t] - delta);
+            p[t] = (short)(int)floor(.5 + (double)x0 + (double)x1);
+        }
+        break;
+    }
+}
+
+// rows by an index map: gather dst[i] = src[map[i]], scatter dst[map[i]] = src[i]; strides in elements
+template <typename T>
+__global__ void plc_rows_kernel(T *dst, size_t dst_stride, const T *src, size_t src_stride, const int *map, int cnt, int width, int scatter)
+{
+    const int i = blockIdx.x;
+    if (i >= cnt) return;
+    const T *s = src + (size_t)(scatter ? i : map[i]) * src_stride;
+    T *d = dst + (size_t)(scatter ? map[i] : i) * dst_stride;
+    for (int k = threadIdx.x; k < width; k += blockDim.x) d[k] = s[k];
+}
+
+// lpcnet_plc_fec_add's RNN_MOVE on a full ring (src/lpcnet_plc.c:117-121): rows [keep, keep + rows) of one stream's ring move to the front
+__global__ __launch_bounds__(256) void plc_fec_move_kernel(float *ring, int keep, int rows)
+{
+    const int total = rows * LPCN_NB_FEAT, shift = keep * LPCN_NB_FEAT;
+    for (int base = 0; base < total; base += 256) {
+        const int k = base + threadIdx.x;
+        float v = 0.f;
+        if (k < total) v = ring[k + shift];
+        __syncthreads();
+        if (k < total) ring[k] = v;
+        __syncthreads();
+    }
+}
+
+}  // namespace lpcn
