@@ -22,27 +22,28 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contr
              "-fvisibility=hidden", "-I" + CSRC, "-I" + os.path.join(HERE, "..", "include")]
 C_FLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-std=gnu11", "-Wall", "-fvisibility=hidden", "-DLPCNET_BUILD",
            "-I" + CSRC, "-I" + os.path.join(HERE, "..", "include")]
+CXX_FLAGS = ["-std=c++17" if x == "-std=gnu11" else x for x in C_FLAGS]      # host C++ (plc_plan.cpp: the PLC planner, no device code)
 
 
 def source_hashes(extra_flags=()):
     """(src, dev): sha1 prefixes over every source the library is built from (lpcnet_amd/csrc/*, the public headers, the
     compile flags) and over the DEVICE sources alone (*.hip, *.hip.h, *.inc and the headers they include -- everything in
-    csrc/ except the host C files).  Both are baked into the library (lpcnet_hip_build_info()); `dev` ties a rocprofv3
+    csrc/ except the host C / C++ files).  Both are baked into the library (lpcnet_hip_build_info()); `dev` ties a rocprofv3
     measurement under profiles/ to the kernels it was taken with (bench.py: kernel_source_hash), so a change to host code
     alone does not orphan the profiles."""
     import hashlib
     hs, hd = hashlib.sha1(), hashlib.sha1()
     for f in sorted(os.listdir(CSRC)):
-        if not f.endswith((".h", ".hip", ".inc", ".c")):
+        if not f.endswith((".h", ".hip", ".inc", ".c", ".cpp")):
             continue
         data = f.encode() + open(os.path.join(CSRC, f), "rb").read()
         hs.update(data)
-        if not f.endswith(".c"):
+        if not f.endswith((".c", ".cpp")):
             hd.update(data)
     for f in ("lpcnet.h", "lpcnet_batch.h", "lpcnet_hip_state.h"):
         hs.update(f.encode() + open(os.path.join(HERE, "..", "include", f), "rb").read())
     flags = " ".join(x for x in HIP_FLAGS if not x.startswith("-I")) + " | " + " ".join(extra_flags)
-    hs.update((flags + " | " + " ".join(x for x in C_FLAGS if not x.startswith("-I"))).encode())
+    hs.update((flags + " | " + " ".join(x for x in C_FLAGS + CXX_FLAGS if not x.startswith("-I"))).encode())
     hd.update(flags.encode())
     return hs.hexdigest()[:16], hd.hexdigest()[:16]
 
@@ -102,6 +103,8 @@ def build(force=False, verbose=True, prof=False):
         # carry candidate heads -- are derived from the same macros the kernels are compiled with)
         run(["gcc"] + C_FLAGS + [x for x in extra if x.startswith("-D")] + [f'-DLPCN_SOURCE_HASH="{h_src}"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"', "-c", os.path.join(CSRC, c), "-o", o])
         objs.append(o)
+    objs.append(os.path.join(objdir, "plc_plan.o"))
+    run(["g++"] + CXX_FLAGS + ["-c", os.path.join(CSRC, "plc_plan.cpp"), "-o", objs[-1]])
     run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs + ["-lpthread", "-lm"])
     return lib
 
@@ -112,7 +115,7 @@ def build_small_registry(verbose=False):
     build (tests/test_gpu_wide.py; select with LPCNET_HIP_LIB).  Test artefact, git-ignored like every built library."""
     build(verbose=verbose)
     objdir0 = os.path.join(HERE, "build")
-    needed = ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o")
+    needed = ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
     if not all(os.path.exists(os.path.join(objdir0, f)) for f in needed):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
         build(force=True, verbose=verbose)
     lib = LIB.replace(".so", "_smallreg.so")
@@ -124,7 +127,7 @@ def build_small_registry(verbose=False):
     cmds = [["gcc"] + C_FLAGS + ["-DLPCN_MAX_MODELS=4", "-DLPCN_MAX_RESIDENT=2", f'-DLPCN_SOURCE_HASH="{h_src}-smallreg"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"',
                                  "-c", os.path.join(CSRC, "api.c"), "-o", o],
             [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o")]
-            + [o, os.path.join(objdir, "model_pack.o"), "-lpthread", "-lm"]]
+            + [o, os.path.join(objdir, "model_pack.o"), os.path.join(objdir, "plc_plan.o"), "-lpthread", "-lm"]]
     for c in cmds:
         if verbose:
             print(" ".join(c), flush=True)

@@ -1,9 +1,12 @@
 // Device runtime of the LPCNet HIP engine: model upload, per-batch device buffers, kernel launches.
 // Only the C ABI of lpcnet_engine.h is visible to the C host shell.
+// Device and pinned memory is held by owning types (DevBuf, PinBuf): a buffer is freed when its owner goes and grows in one place
+// (DevBuf::reserve, which first waits for the batch's enqueued work).  Kernels and launch helpers take raw pointers, filled from the owners.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <vector>
 #include "lpcnet_engine.h"
 #include "lpcnet_tables_gen.h"
@@ -14,7 +17,7 @@
 #include "analysis_kernels.hip.h"
 #include "encode_kernels.hip.h"
 #include "plc_kernels.hip.h"
-#define LPCNET_PLC_CAUSAL_OPT 0      /* LPCNET_PLC_CAUSAL of include/lpcnet.h (2 = LPCNET_PLC_CODEC, | 4 = LPCNET_PLC_DC_FILTER) */
+#include "plc_plan.h"
 #include <math.h>
 
 static thread_local char g_err[512] = "";
@@ -37,6 +40,64 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+// Device memory with an owner: the destructor frees, nothing copies.  `cap` counts elements.  What a batch owns goes with `delete b`, inside
+// the DeviceGuard of lpcn_batch_dev_destroy.
+struct lpcn_batch_dev;
+static int wait_all(lpcn_batch_dev *b);
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // exactly `count` elements, optionally zeroed
+    int alloc(size_t count, bool zero = false)
+    {
+        release();
+        if (hipMalloc((void **)&p, count * sizeof(T)) != hipSuccess) { p = nullptr; snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", count * sizeof(T)); return LPCN_E_HIP; }
+        cap = count;
+        if (zero) HIP_TRY(hipMemset(p, 0, count * sizeof(T)));
+        return 0;
+    }
+    // at least `count` elements, contents not kept.  Growing first waits for everything enqueued for the batch, whichever stream it went to:
+    // the old buffer may still be in use.  It happens once per size.
+    int reserve(lpcn_batch_dev *b, size_t count)
+    {
+        if (count <= cap) return 0;
+        const int rc = wait_all(b);
+        return rc ? rc : alloc(count);
+    }
+};
+// Pinned host memory, grown to the bytes its user asks for.  Its users synchronise before they return, so nothing is in flight when it grows.
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int reserve(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; snprintf(g_err, sizeof(g_err), "hipHostMalloc(%zu) failed", bytes); return LPCN_E_HIP; }
+        cap = bytes;
+        return 0;
+    }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
 };
 
 // GRU-A as dealt to waves and lanes, once per dealing: the model part of the argument block with that image's pointers, and the compiled
@@ -64,6 +125,25 @@ struct lpcn_engine {
     int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
 };
 
+// packet-loss concealment of a batch (lpcn_batch_dev_plc_enable): the control state on the host, the data on the device
+struct lpcn_plc_host {
+    int options = 0;
+    bool remove_dc = false;
+    std::vector<lpcn_plc_ctl> ctl;
+    DevBuf<short> q, lp;                            // the arrays of lpcn::PlcData (plc_kernels.hip.h) ...
+    DevBuf<float> feat, net, fec, fbuf, burg, an;
+    DevBuf<double> dc;
+    DevBuf<int> delta;
+    lpcn::PlcData D{};                              // ... and their addresses as the kernels take them
+    DevBuf<short> d_pcm;                            // staging of the host-pointer call
+    DevBuf<int> d_ident;                            // 0 .. n-1
+    DevBuf<int> d_ctl;                              // the step's lists: device copy (its capacity bounds a step's lists) ...
+    PinBuf h_ctl;                                   // ... and its pinned source
+    Event ev_ctl;                                   // the upload of the previous step's lists has left h_ctl
+    bool ctl_pending = false;
+    PlcPlan plan;
+};
+
 struct lpcn_batch_dev {
     lpcn_engine *e = nullptr;
     int n = 0, max_chunk = 0, S = 0, frame_len = LPCN_FRAME_SIZE;
@@ -74,41 +154,40 @@ struct lpcn_batch_dev {
     bool x3 = false;                   // at eight streams per workgroup: the twelve-wave form of the two-group kernel (measured faster on this batch, or asked for)
     int x3_mode = -1;                  // lpcn_batch_dev_set_x3: 0 never, 1 always, -1 measured (the table's value, the eight-wave form, until then)
     int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
-    lpcn_stream_state *d_state = nullptr;
-    int *d_fc_base = nullptr;
-    float *d_cond_a = nullptr, *d_cond_b = nullptr, *d_lpc = nullptr, *d_cond = nullptr;
-    float *d_feat = nullptr;           // staging for host-pointer runs / decoded feature vectors
-    float *d_vq_mem = nullptr;         // [n][18] VQ memory of the codec path (src/lpcnet_private.h:52)
-    lpcn_analysis_state *d_an_state = nullptr;   // feature analysis (lpcn_batch_dev_analysis_enable): per-stream state, allocated on first use
-    float *d_an_resid = nullptr, *d_an_xc = nullptr, *d_an_fw = nullptr;   //   ... and the kernels' scratch for an_chunk frames per launch
+    DevBuf<lpcn_stream_state> d_state;
+    DevBuf<int> d_fc_base;
+    DevBuf<float> d_cond_a, d_cond_b, d_lpc, d_cond;
+    DevBuf<float> d_feat;              // staging for host-pointer runs / decoded feature vectors
+    DevBuf<short> d_pcm;
+    DevBuf<unsigned char> d_packets;   // packet staging of the host-pointer codec calls (decode: in, encode: out)
+    DevBuf<float> d_vq_mem;            // [n][18] VQ memory of the codec path (src/lpcnet_private.h:52)
+    DevBuf<lpcn_analysis_state> d_an_state;      // feature analysis (lpcn_batch_dev_analysis_enable): per-stream state, allocated on first use
+    DevBuf<float> d_an_resid, d_an_xc, d_an_fw;  //   ... and the kernels' scratch for an_chunk frames per launch
     int an_chunk = 0;
-    void *d_an_pcm = nullptr;          //   ... and the staging of host-pointer calls (PCM in, features out)
-    float *d_an_feat = nullptr;
-    size_t an_pcm_cap = 0, an_feat_cap = 0;
-    float *d_enc_vq_mem = nullptr;     // encoder (lpcn_batch_dev_encoder_enable): [n][18] vq_mem of LPCNetEncState, beside the analysis state
-    float *d_enc_feat = nullptr, *d_enc_qf3 = nullptr;   //   ... scratch of enc_chunk packets per launch: cepstrum / LPC rows, quantised frame 3 (+ the entry vq_mem)
-    int *d_enc_pk = nullptr;           //   ... and the packets' bit fields
+    DevBuf<unsigned char> d_an_pcm;    //   ... and the staging of host-pointer calls (PCM in, as bytes; features out)
+    DevBuf<float> d_an_feat;
+    DevBuf<float> d_enc_vq_mem;        // encoder (lpcn_batch_dev_encoder_enable): [n][18] vq_mem of LPCNetEncState, beside the analysis state
+    DevBuf<float> d_enc_feat, d_enc_qf3;         //   ... scratch of enc_chunk packets per launch: cepstrum / LPC rows, quantised frame 3 (+ the entry vq_mem)
+    DevBuf<int> d_enc_pk;              //   ... and the packets' bit fields
     int enc_chunk = 0;
-    lpcn_stream_state *d_state_tmp = nullptr;   // per-stream-arguments step (lpcn_batch_dev_step_host): the compacted group's states
-    int *d_map = nullptr;              //   ... and its stream indices
-    float *d_keep_a = nullptr, *d_keep_b = nullptr, *d_keep_lpc = nullptr;   //   ... and every stream's most recent frame products
+    DevBuf<lpcn_stream_state> d_state_tmp;       // compacted groups (run_group: the per-stream-arguments step, the PLC): the group's states
+    DevBuf<float> d_gfeat;             //   ... features (also the PLC parity seam's output)
+    DevBuf<short> d_gpcm;              //   ... and PCM
+    DevBuf<int> d_map;                 //   ... the index maps of one lpcn_batch_dev_step_host call (the PLC's are part of its control lists)
+    DevBuf<float> d_keep_a, d_keep_b, d_keep_lpc;   //   ... and every stream's most recent frame products
     std::vector<char> keep_ok;         //   ... which exist only for streams whose last frame step went through the step call (mode 1)
-    unsigned char *d_packets = nullptr;
-    size_t packets_cap = 0;
-    short *d_pcm = nullptr;
-    size_t feat_cap = 0, pcm_cap = 0;
-    LpcnSampleArgs *d_args = nullptr;
-    float *d_dbg = nullptr;
-    unsigned long long *d_prof = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf<LpcnSampleArgs> d_args;
+    DevBuf<float> d_dbg;
+    DevBuf<unsigned long long> d_prof;
+    Event ev[3];
     // Ordering across caller streams: the batch's scratch buffers and state are shared by every call, so each enqueue
     // records ev_last on its stream; a call on a DIFFERENT stream first waits for it, and every host-side access
     // (sync, state get/set, reset, destroy, buffer growth) waits for it as well.
-    hipEvent_t ev_last = nullptr;
+    Event ev_last;
     hipStream_t last_stream = nullptr;
     bool pending = false;
-    struct lpcn_plc_host *plc = nullptr;      // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
-    void *h_pin = nullptr;             // pinned host staging of the single-stream fast path (state | features | pcm)
+    std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
+    PinBuf h_pin;                      // pinned host staging of the single-stream fast path and the combined pass: each reserves what it lays out
     bool timing = false;
     float ms_sample = 0.f, ms_frame = 0.f;
 };
@@ -532,40 +611,24 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     b->S = auto_streams_per_wg(b, n);
     b->pack2 = use_pack2(b, n, b->S);
     auto fail = [&](int code) { lpcn_batch_dev_destroy(b); return code; };
-#define AL(ptr, bytes) if (hipMalloc((void **)&ptr, (bytes)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", (size_t)(bytes)); return fail(LPCN_E_HIP); }
-    AL(b->d_state, sizeof(lpcn_stream_state) * n);
-    AL(b->d_fc_base, sizeof(int) * n);
-    AL(b->d_cond_a, sizeof(float) * (size_t)n * max_chunk * LPCN_ROWS_A);
-    AL(b->d_cond_b, sizeof(float) * (size_t)n * max_chunk * LPCN_ROWS_B);
-    AL(b->d_lpc, sizeof(float) * (size_t)n * max_chunk * LPCN_LPC_ORDER);
-    AL(b->d_cond, sizeof(float) * (size_t)n * (max_chunk + 4) * LPCN_COND * 2);
-    AL(b->d_args, sizeof(LpcnSampleArgs));
-    AL(b->d_vq_mem, sizeof(float) * (size_t)n * LPCN_NB_BANDS);
-#undef AL
-    for (auto &ev : b->ev) if (hipEventCreate(&ev) != hipSuccess) return fail(LPCN_E_HIP);
-    if (hipEventCreateWithFlags(&b->ev_last, hipEventDisableTiming) != hipSuccess) return fail(LPCN_E_HIP);
+    const size_t rows = (size_t)n * max_chunk;
+    int rc = 0;
+    if ((rc = b->d_state.alloc(n)) || (rc = b->d_fc_base.alloc(n)) || (rc = b->d_cond_a.alloc(rows * LPCN_ROWS_A)) || (rc = b->d_cond_b.alloc(rows * LPCN_ROWS_B)) ||
+        (rc = b->d_lpc.alloc(rows * LPCN_LPC_ORDER)) || (rc = b->d_cond.alloc((size_t)n * (max_chunk + 4) * LPCN_COND * 2)) || (rc = b->d_args.alloc(1)) ||
+        (rc = b->d_vq_mem.alloc((size_t)n * LPCN_NB_BANDS))) return fail(rc);
+    for (auto &ev : b->ev) if (hipEventCreate(&ev.e) != hipSuccess) return fail(LPCN_E_HIP);
+    if (hipEventCreateWithFlags(&b->ev_last.e, hipEventDisableTiming) != hipSuccess) return fail(LPCN_E_HIP);
     *out = b;
-    int rc = lpcn_batch_dev_reset(b, 0, n);
-    if (rc) return fail(rc);
+    if ((rc = lpcn_batch_dev_reset(b, 0, n))) return fail(rc);
     return 0;
 }
 
-static void plc_free(lpcn_batch_dev *b);
 extern "C" void lpcn_batch_dev_destroy(lpcn_batch_dev *b)
 {
     if (!b) return;
     DeviceGuard guard(b->e->device);
     (void)wait_all(b);
-    plc_free(b);
-    if (b->h_pin) (void)hipHostFree(b->h_pin);
-    if (b->ev_last) (void)hipEventDestroy(b->ev_last);
-    void *ptrs[] = {b->d_state, b->d_fc_base, b->d_cond_a, b->d_cond_b, b->d_lpc, b->d_cond, b->d_feat, b->d_pcm, b->d_args, b->d_dbg, b->d_prof,
-                    b->d_vq_mem, b->d_packets, b->d_state_tmp, b->d_map, b->d_keep_a, b->d_keep_b, b->d_keep_lpc,
-                    b->d_an_state, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_an_pcm, b->d_an_feat,
-                    b->d_enc_vq_mem, b->d_enc_feat, b->d_enc_qf3, b->d_enc_pk};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (auto &ev : b->ev) if (ev) (void)hipEventDestroy(ev);
-    delete b;
+    delete b;                          // (inside the guard: the buffers, events and the PLC's data are freed on the batch's device)
 }
 
 // lpcnet_reset semantics (src/lpcnet.c:174-182): zero everything, last_exc = lin2ulaw(0) = 128,
@@ -585,10 +648,32 @@ static void host_reset_state(lpcn_stream_state *st)
     memcpy(st->rng, c, sizeof(c));
 }
 
+// lpcn_batch_dev_step_host's per-stream frame products are stale after anything else has advanced or rewritten a stream
+static void forget_keep(lpcn_batch_dev *b) { b->keep_ok.assign(b->keep_ok.size(), 0); }
+static int check_range(const lpcn_batch_dev *b, int first, int count, const char *what)
+{
+    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "%s range", what); return LPCN_E_ARG; }
+    return 0;
+}
+// One stream's record of a per-stream device array, `per` elements at buf + s * per, to the host (down) or from it (up), after everything
+// enqueued for the batch.  An array that exists only once its feature is enabled names the call that makes it.
+template <typename T>
+static int stream_rec(lpcn_batch_dev *b, int s, const DevBuf<T> &buf, size_t per, void *down, const void *up, int (*enable)(lpcn_batch_dev *, int) = nullptr)
+{
+    if (s < 0 || s >= b->n || (!down && !up)) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    int rc = (!buf && enable) ? enable(b, 1) : 0;
+    if (!rc) rc = wait_all(b);
+    if (rc) return rc;
+    if (up) HIP_TRY(hipMemcpy(buf + (size_t)s * per, up, sizeof(T) * per, hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemcpy(down, buf + (size_t)s * per, sizeof(T) * per, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
 {
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's per-stream frame products are stale now)
-    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "reset range"); return LPCN_E_ARG; }
+    forget_keep(b);
+    if (check_range(b, first, count, "reset")) return LPCN_E_ARG;
     DeviceGuard guard(b->e->device);
     std::vector<lpcn_stream_state> h(count);
     for (auto &s : h) host_reset_state(&s);
@@ -598,22 +683,11 @@ extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
     return 0;
 }
 
-extern "C" int lpcn_batch_dev_get_state(lpcn_batch_dev *b, int s, lpcn_stream_state *host)
-{
-    if (s < 0 || s >= b->n) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(host, b->d_state + s, sizeof(*host), hipMemcpyDeviceToHost));
-    return 0;
-}
+extern "C" int lpcn_batch_dev_get_state(lpcn_batch_dev *b, int s, lpcn_stream_state *host) { return stream_rec(b, s, b->d_state, 1, host, nullptr); }
 extern "C" int lpcn_batch_dev_set_state(lpcn_batch_dev *b, int s, const lpcn_stream_state *host)
 {
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's per-stream frame products are stale now)
-    if (s < 0 || s >= b->n) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(b->d_state + s, host, sizeof(*host), hipMemcpyHostToDevice));
-    return 0;
+    forget_keep(b);
+    return stream_rec(b, s, b->d_state, 1, nullptr, host);
 }
 // the engine's arithmetic flavour changed: re-run the cost model unless the caller pinned the value
 extern "C" int lpcn_batch_dev_retune(lpcn_batch_dev *b)
@@ -767,18 +841,16 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
     if ((off && *off == '1') || b->n < 2 || b->e->fast) return 0;     // (one stream: one workgroup whatever S is)
     const int nf = 5 < b->max_chunk ? 5 : b->max_chunk;
     int rc = 0;
-    lpcn_stream_state *saved = nullptr;
-    short *pcm = nullptr;                                    // (a buffer of its own: the caller may be holding the staging buffer's address)
-    HIP_TRY(hipMalloc((void **)&saved, sizeof(lpcn_stream_state) * b->n));
-    if (hipMalloc((void **)&pcm, sizeof(short) * (size_t)b->n * nf * LPCN_FRAME_SIZE) != hipSuccess) { (void)hipFree(saved); snprintf(g_err, sizeof(g_err), "auto-tune: hipMalloc failed"); return LPCN_E_HIP; }
-    auto done = [&](int code) { (void)hipFree(saved); (void)hipFree(pcm); return code; };
+    DevBuf<lpcn_stream_state> saved;
+    DevBuf<short> pcm;                                       // (a buffer of its own: the caller may be holding the staging buffer's address)
+    if ((rc = saved.alloc(b->n)) || (rc = pcm.alloc((size_t)b->n * nf * LPCN_FRAME_SIZE))) return rc;
     std::vector<int> fc((size_t)b->n, LPCN_FEATURES_DELAY + 3);                     // every stream live
     if (hipMemcpyAsync(saved, b->d_state, sizeof(lpcn_stream_state) * b->n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipMemsetAsync(b->d_cond_a, 0, sizeof(float) * (size_t)b->n * nf * LPCN_ROWS_A, st) != hipSuccess ||
         hipMemsetAsync(b->d_cond_b, 0, sizeof(float) * (size_t)b->n * nf * LPCN_ROWS_B, st) != hipSuccess ||
         hipMemsetAsync(b->d_lpc, 0, sizeof(float) * (size_t)b->n * nf * LPCN_LPC_ORDER, st) != hipSuccess ||
         hipMemcpyAsync(b->d_fc_base, fc.data(), sizeof(int) * b->n, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { snprintf(g_err, sizeof(g_err), "auto-tune: buffer setup failed"); return done(LPCN_E_HIP); }
+        hipStreamSynchronize(st) != hipSuccess) { snprintf(g_err, sizeof(g_err), "auto-tune: buffer setup failed"); return LPCN_E_HIP; }
     int best = b->S;
     bool best_x3 = false;
     float best_ms = -1.f;
@@ -807,10 +879,10 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
     // the measurement ran on the real state: put it back
     if (hipMemcpyAsync(b->d_state, saved, sizeof(lpcn_stream_state) * b->n, hipMemcpyDeviceToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) rc = rc ? rc : LPCN_E_HIP;
-    if (rc) return done(rc);
+    if (rc) return rc;
     b->S = best; b->pack2 = use_pack2(b, b->n, best);
     if (b->x3_mode < 0) b->x3 = best_x3;
-    return done(0);
+    return 0;
 }
 
 // lpcnet_batch_tune(): measure now, on the engine's own stream (e.g. right after lpcnet_batch_load_model), so that the first
@@ -841,7 +913,7 @@ static int run_impl(lpcn_batch_dev *b, const LaunchShape &sh, const float *d_fea
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     float tf = 0.f, ts = 0.f;
     { int rco = order_begin(b, st); if (rco) return rco; }
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (the step call's per-stream frame products are stale now)
+    forget_keep(b);      // (the step call's per-stream frame products are stale now)
     for (int f0 = 0; f0 < n_frames; f0 += b->max_chunk) {
         const int nf = n_frames - f0 < b->max_chunk ? n_frames - f0 : b->max_chunk;
         if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], st));
@@ -869,22 +941,11 @@ extern "C" int lpcn_batch_dev_run(lpcn_batch_dev *b, const float *d_features, in
     return run_impl(b, whole_batch(b), d_features, feat_stride, d_pcm, n_frames, preload, hip_stream);
 }
 
+// the staging buffers of the host-pointer calls, for at least that many floats of features and samples of PCM
 static int ensure_staging(lpcn_batch_dev *b, size_t feat_floats, size_t pcm_samples)
 {
-    if (feat_floats > b->feat_cap || pcm_samples > b->pcm_cap) { int rcw = wait_all(b); if (rcw) return rcw; }   // the old buffers may still be in use
-    if (feat_floats > b->feat_cap) {
-        if (b->d_feat) (void)hipFree(b->d_feat);
-        b->d_feat = nullptr; b->feat_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_feat, feat_floats * sizeof(float)));
-        b->feat_cap = feat_floats;
-    }
-    if (pcm_samples > b->pcm_cap) {
-        if (b->d_pcm) (void)hipFree(b->d_pcm);
-        b->d_pcm = nullptr; b->pcm_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_pcm, pcm_samples * sizeof(short)));
-        b->pcm_cap = pcm_samples;
-    }
-    return 0;
+    const int rc = b->d_feat.reserve(b, feat_floats);
+    return rc ? rc : b->d_pcm.reserve(b, pcm_samples);
 }
 
 extern "C" int lpcn_batch_dev_run_host(lpcn_batch_dev *b, const float *features, int feat_stride,
@@ -917,11 +978,11 @@ extern "C" int lpcn_batch_dev_run_single(lpcn_batch_dev *b, const lpcn_stream_st
     DeviceGuard guard(b->e->device);
     const size_t off_feat = sizeof(lpcn_stream_state), off_pcm = off_feat + LPCN_NB_FEAT * sizeof(float);
     int rc = ensure_staging(b, LPCN_NB_FEAT, LPCN_FRAME_SIZE);
+    if (!rc) rc = b->h_pin.reserve(off_pcm + LPCN_FRAME_SIZE * sizeof(short));
     if (rc) return rc;
-    if (!b->h_pin) HIP_TRY(hipHostMalloc(&b->h_pin, off_pcm + LPCN_FRAME_SIZE * sizeof(short), hipHostMallocDefault));
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
-    unsigned char *pin = (unsigned char *)b->h_pin;
+    unsigned char *pin = (unsigned char *)b->h_pin.p;
     if (st_in) {
         memcpy(pin, st_in, sizeof(*st_in));
         HIP_TRY(hipMemcpyAsync(b->d_state, pin, sizeof(*st_in), hipMemcpyHostToDevice, st));
@@ -960,16 +1021,16 @@ extern "C" int lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int 
     DeviceGuard guard(b->e->device);
     const int cap = b->n;
     if (k > cap) { snprintf(g_err, sizeof(g_err), "group of %d exceeds the batch's %d streams", k, cap); return LPCN_E_ARG; }
-    int rc = ensure_staging(b, (size_t)cap * LPCN_NB_FEAT, (size_t)cap * LPCN_FRAME_SIZE);
-    if (rc) return rc;
     // pinned staging: states | features | pcm | cond_a | cond_b | lpc, each for `cap` streams
     const size_t sz_st = sizeof(lpcn_stream_state), off_feat = sz_st * cap, off_pcm = off_feat + sizeof(float) * LPCN_NB_FEAT * cap;
     const size_t off_ga = off_pcm + sizeof(short) * LPCN_FRAME_SIZE * cap, off_gb = off_ga + sizeof(float) * LPCN_ROWS_A * cap;
     const size_t off_lpc = off_gb + sizeof(float) * LPCN_ROWS_B * cap, pin_bytes = off_lpc + sizeof(float) * LPCN_LPC_ORDER * cap;
-    if (!b->h_pin) HIP_TRY(hipHostMalloc(&b->h_pin, pin_bytes, hipHostMallocDefault));
+    int rc = ensure_staging(b, (size_t)cap * LPCN_NB_FEAT, (size_t)cap * LPCN_FRAME_SIZE);
+    if (!rc) rc = b->h_pin.reserve(pin_bytes);
+    if (rc) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
-    unsigned char *pin = (unsigned char *)b->h_pin;
+    unsigned char *pin = (unsigned char *)b->h_pin.p;
     for (int i = 0; i < k; ++i) {
         memcpy(pin + sz_st * i, st_in[i], sz_st);
         if (frames) memcpy(pin + off_feat + sizeof(float) * LPCN_NB_FEAT * i, feat[i], sizeof(float) * LPCN_NB_FEAT);
@@ -990,7 +1051,7 @@ extern "C" int lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int 
     }
     const int S = auto_streams_per_wg(b, k);               // (the table's value for the group's size, never a measurement)
     const LaunchShape sh = {k, samples ? frame_len : b->frame_len, b->d_state, S, use_pack2(b, k, S), b->x3_mode == 1};
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);
+    forget_keep(b);
     if (kind == LPCN_GROUP_FRAME_SAMPLES) rc = run_impl(b, sh, b->d_feat, LPCN_NB_FEAT, b->d_pcm, 1, preload, st);
     else if (kind == LPCN_GROUP_TAIL) rc = launch_sample(b, sh, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, preload, false);
     else rc = launch_frames(b, sh, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
@@ -1020,7 +1081,7 @@ extern "C" int lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int 
 // Codec path: 8-byte packets [stream][packet][8] -> 4 frames each.  Device pointers, work only enqueued.
 static int decode_impl(lpcn_batch_dev *b, const unsigned char *d_packets, short *d_pcm, int n_packets, void *hip_stream, bool may_tune)
 {
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's per-stream frame products are stale now)
+    forget_keep(b);
     if (n_packets <= 0) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
     if (!b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
     DeviceGuard guard(b->e->device);
@@ -1042,24 +1103,12 @@ extern "C" int lpcn_batch_dev_decode(lpcn_batch_dev *b, const unsigned char *d_p
     return decode_impl(b, d_packets, d_pcm, n_packets, hip_stream, false);
 }
 
-// packet staging of the host-pointer codec calls (decode: in, encode: out)
-static int ensure_packets(lpcn_batch_dev *b, size_t nbytes)
-{
-    if (nbytes <= b->packets_cap) return 0;
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    if (b->d_packets) (void)hipFree(b->d_packets);
-    b->d_packets = nullptr; b->packets_cap = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_packets, nbytes));
-    b->packets_cap = nbytes;
-    return 0;
-}
-
 extern "C" int lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char *packets, short *pcm, int n_packets)
 {
     if (n_packets <= 0) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     const size_t nbytes = (size_t)b->n * n_packets * 8, npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE;
-    int rc = ensure_packets(b, nbytes);
+    int rc = b->d_packets.reserve(b, nbytes);
     if (rc) return rc;
     if ((rc = ensure_staging(b, 0, npcm))) return rc;
     hipStream_t st = b->e->stream;
@@ -1085,21 +1134,14 @@ static int analysis_chunk_for(const lpcn_batch_dev *b, int n_frames)
 // the analysis state (if absent) and the kernels' scratch for `chunk` frames per launch
 static int analysis_alloc(lpcn_batch_dev *b, int chunk)
 {
-    if (b->d_an_state && chunk <= b->an_chunk) return 0;
-    { int rcw = wait_all(b); if (rcw) return rcw; }      // the old scratch may still be in use
-    if (!b->d_an_state) {
-        HIP_TRY(hipMalloc((void **)&b->d_an_state, sizeof(lpcn_analysis_state) * (size_t)b->n));
-        HIP_TRY(hipMemset(b->d_an_state, 0, sizeof(lpcn_analysis_state) * (size_t)b->n));      // lpcnet_encoder_init (src/lpcnet_enc.c:471-475)
-    }
-    if (chunk > b->an_chunk) {
-        for (float **p : {&b->d_an_resid, &b->d_an_xc, &b->d_an_fw}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        b->an_chunk = 0;
-        const size_t items = (size_t)b->n * chunk;
-        HIP_TRY(hipMalloc((void **)&b->d_an_resid, sizeof(float) * items * LPCN_FRAME_SIZE));
-        HIP_TRY(hipMalloc((void **)&b->d_an_xc, sizeof(float) * items * 2 * LPCN_PITCH_MAX_PERIOD));
-        HIP_TRY(hipMalloc((void **)&b->d_an_fw, sizeof(float) * items * 2));
-        b->an_chunk = chunk;
-    }
+    int rc = 0;
+    if (!b->d_an_state && (rc = b->d_an_state.alloc((size_t)b->n, true))) return rc;      // zeroed: lpcnet_encoder_init (src/lpcnet_enc.c:471-475)
+    if (chunk <= b->an_chunk) return 0;
+    const size_t items = (size_t)b->n * chunk;
+    b->an_chunk = 0;                                         // (until all three have grown)
+    if ((rc = b->d_an_resid.reserve(b, items * LPCN_FRAME_SIZE)) || (rc = b->d_an_xc.reserve(b, items * 2 * LPCN_PITCH_MAX_PERIOD)) ||
+        (rc = b->d_an_fw.reserve(b, items * 2))) return rc;
+    b->an_chunk = chunk;
     return 0;
 }
 extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
@@ -1136,38 +1178,20 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
     return order_end(b, st);
 }
 
-// staging of the host-pointer analysis / encoder calls: npcm bytes of PCM in, nfeat floats of features out
-static int ensure_analysis_staging(lpcn_batch_dev *b, size_t npcm, size_t nfeat)
-{
-    if (npcm > b->an_pcm_cap || nfeat > b->an_feat_cap) { int rcw = wait_all(b); if (rcw) return rcw; }
-    if (npcm > b->an_pcm_cap) {
-        if (b->d_an_pcm) (void)hipFree(b->d_an_pcm);
-        b->d_an_pcm = nullptr; b->an_pcm_cap = 0;
-        HIP_TRY(hipMalloc(&b->d_an_pcm, npcm));
-        b->an_pcm_cap = npcm;
-    }
-    if (nfeat > b->an_feat_cap) {
-        if (b->d_an_feat) (void)hipFree(b->d_an_feat);
-        b->d_an_feat = nullptr; b->an_feat_cap = 0;
-        HIP_TRY(hipMalloc((void **)&b->d_an_feat, nfeat * sizeof(float)));
-        b->an_feat_cap = nfeat;
-    }
-    return 0;
-}
-
 extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames)
 {
     if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));
     const size_t nfeat = (size_t)b->n * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
-    int rc = ensure_analysis_staging(b, npcm, nfeat);
+    int rc = b->d_an_pcm.reserve(b, npcm);
+    if (!rc) rc = b->d_an_feat.reserve(b, nfeat);
     if (rc) return rc;
     if ((rc = lpcn_batch_dev_analysis_enable(b, n_frames))) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
     HIP_TRY(hipMemcpyAsync(b->d_an_pcm, pcm, npcm, hipMemcpyHostToDevice, st));
-    rc = lpcn_batch_dev_analyze(b, b->d_an_pcm, pcm_is_float, b->d_an_feat, LPCN_AN_NB_FEATURES, n_frames, st);
+    rc = lpcn_batch_dev_analyze(b, b->d_an_pcm.p, pcm_is_float, b->d_an_feat, LPCN_AN_NB_FEATURES, n_frames, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(features, (size_t)feat_stride * sizeof(float), b->d_an_feat, LPCN_AN_NB_FEATURES * sizeof(float),
                              LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->n * n_frames, hipMemcpyDeviceToHost, st));
@@ -1177,7 +1201,7 @@ extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, i
 
 extern "C" int lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int count)
 {
-    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "analysis reset range"); return LPCN_E_ARG; }
+    if (check_range(b, first, count, "analysis reset")) return LPCN_E_ARG;
     DeviceGuard guard(b->e->device);
     if (!b->d_an_state) return lpcn_batch_dev_analysis_enable(b, 1);      // (a fresh state IS the reset state)
     { int rcw = wait_all(b); if (rcw) return rcw; }
@@ -1187,21 +1211,11 @@ extern "C" int lpcn_batch_dev_analysis_reset(lpcn_batch_dev *b, int first, int c
 }
 extern "C" int lpcn_batch_dev_get_analysis_state(lpcn_batch_dev *b, int s, lpcn_analysis_state *host)
 {
-    if (s < 0 || s >= b->n || !host) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    if (!b->d_an_state) { int rc = lpcn_batch_dev_analysis_enable(b, 1); if (rc) return rc; }
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(host, b->d_an_state + s, sizeof(*host), hipMemcpyDeviceToHost));
-    return 0;
+    return stream_rec(b, s, b->d_an_state, 1, host, nullptr, lpcn_batch_dev_analysis_enable);
 }
 extern "C" int lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int s, const lpcn_analysis_state *host)
 {
-    if (s < 0 || s >= b->n || !host) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    if (!b->d_an_state) { int rc = lpcn_batch_dev_analysis_enable(b, 1); if (rc) return rc; }
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(b->d_an_state + s, host, sizeof(*host), hipMemcpyHostToDevice));
-    return 0;
+    return stream_rec(b, s, b->d_an_state, 1, nullptr, host, lpcn_batch_dev_analysis_enable);
 }
 
 // ------------------------------------------------------------------------------- encoder -----
@@ -1221,23 +1235,13 @@ extern "C" int lpcn_batch_dev_encoder_enable(lpcn_batch_dev *b, int max_packets)
     const int chunk = encode_chunk_for(b, max_packets);
     int rc = analysis_alloc(b, 4 * chunk);
     if (rc) return rc;
-    if (b->d_enc_vq_mem && chunk <= b->enc_chunk) return 0;
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    if (!b->d_enc_vq_mem) {
-        HIP_TRY(hipMalloc((void **)&b->d_enc_vq_mem, sizeof(float) * LPCN_NB_BANDS * (size_t)b->n));
-        HIP_TRY(hipMemset(b->d_enc_vq_mem, 0, sizeof(float) * LPCN_NB_BANDS * (size_t)b->n));
-    }
-    if (chunk > b->enc_chunk) {
-        if (b->d_enc_feat) (void)hipFree(b->d_enc_feat);
-        if (b->d_enc_qf3) (void)hipFree(b->d_enc_qf3);
-        if (b->d_enc_pk) (void)hipFree(b->d_enc_pk);
-        b->d_enc_feat = b->d_enc_qf3 = nullptr; b->d_enc_pk = nullptr; b->enc_chunk = 0;
-        const size_t items = (size_t)b->n * chunk;
-        HIP_TRY(hipMalloc((void **)&b->d_enc_feat, sizeof(float) * items * 4 * LPCN_AN_NB_FEATURES));
-        HIP_TRY(hipMalloc((void **)&b->d_enc_qf3, sizeof(float) * (size_t)b->n * (chunk + 1) * LPCN_NB_BANDS));
-        HIP_TRY(hipMalloc((void **)&b->d_enc_pk, sizeof(int) * items * lpcn::ENC_PK));
-        b->enc_chunk = chunk;
-    }
+    if (!b->d_enc_vq_mem && (rc = b->d_enc_vq_mem.alloc(LPCN_NB_BANDS * (size_t)b->n, true))) return rc;
+    if (chunk <= b->enc_chunk) return 0;
+    const size_t items = (size_t)b->n * chunk;
+    b->enc_chunk = 0;                                        // (until all three have grown)
+    if ((rc = b->d_enc_feat.reserve(b, items * 4 * LPCN_AN_NB_FEATURES)) || (rc = b->d_enc_qf3.reserve(b, (size_t)b->n * (chunk + 1) * LPCN_NB_BANDS)) ||
+        (rc = b->d_enc_pk.reserve(b, items * lpcn::ENC_PK))) return rc;
+    b->enc_chunk = chunk;
     return 0;
 }
 
@@ -1301,14 +1305,15 @@ extern "C" int lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, u
     DeviceGuard guard(b->e->device);
     const size_t npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE * sizeof(short);
     const size_t nfeat = packets ? 0 : (size_t)b->n * n_packets * 4 * LPCN_AN_NB_FEATURES, nbytes = packets ? (size_t)b->n * n_packets * 8 : 0;
-    int rc = ensure_analysis_staging(b, npcm, nfeat);
+    int rc = b->d_an_pcm.reserve(b, npcm);
+    if (!rc) rc = b->d_an_feat.reserve(b, nfeat);
+    if (!rc) rc = b->d_packets.reserve(b, nbytes);
+    if (!rc) rc = lpcn_batch_dev_encoder_enable(b, n_packets);
     if (rc) return rc;
-    if ((rc = ensure_packets(b, nbytes))) return rc;
-    if ((rc = lpcn_batch_dev_encoder_enable(b, n_packets))) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;      // the staging buffers may still be read by work on a caller stream
     HIP_TRY(hipMemcpyAsync(b->d_an_pcm, pcm, npcm, hipMemcpyHostToDevice, st));
-    rc = encode_impl(b, (const short *)b->d_an_pcm, packets ? b->d_packets : nullptr, packets ? nullptr : b->d_an_feat, LPCN_AN_NB_FEATURES, n_packets, st);
+    rc = encode_impl(b, (const short *)b->d_an_pcm.p, packets ? b->d_packets.p : nullptr, packets ? nullptr : b->d_an_feat.p, LPCN_AN_NB_FEATURES, n_packets, st);
     if (rc) return rc;
     if (packets)
         HIP_TRY(hipMemcpyAsync(packets, b->d_packets, nbytes, hipMemcpyDeviceToHost, st));
@@ -1321,28 +1326,16 @@ extern "C" int lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, u
 
 extern "C" int lpcn_batch_dev_get_encoder_vq_mem(lpcn_batch_dev *b, int s, float *out18)
 {
-    if (s < 0 || s >= b->n || !out18) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    if (!b->d_enc_vq_mem) { int rc = lpcn_batch_dev_encoder_enable(b, 1); if (rc) return rc; }
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(out18, b->d_enc_vq_mem + (size_t)s * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
-    return 0;
+    return stream_rec(b, s, b->d_enc_vq_mem, LPCN_NB_BANDS, out18, nullptr, lpcn_batch_dev_encoder_enable);
 }
 extern "C" int lpcn_batch_dev_set_encoder_vq_mem(lpcn_batch_dev *b, int s, const float *in18)
 {
-    if (s < 0 || s >= b->n || !in18) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    if (!b->d_enc_vq_mem) { int rc = lpcn_batch_dev_encoder_enable(b, 1); if (rc) return rc; }
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    HIP_TRY(hipMemcpy(b->d_enc_vq_mem + (size_t)s * LPCN_NB_BANDS, in18, sizeof(float) * LPCN_NB_BANDS, hipMemcpyHostToDevice));
-    return 0;
+    return stream_rec(b, s, b->d_enc_vq_mem, LPCN_NB_BANDS, nullptr, in18, lpcn_batch_dev_encoder_enable);
 }
-
-
 extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond_a, const float *cond_b,
                                             const float *lpc, short *pcm, int n_frames, int preload)
 {
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's per-stream frame products are stale now)
+    forget_keep(b);
     if (n_frames <= 0 || preload < 0 || preload > LPCN_FRAME_SIZE) { snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE;
@@ -1379,7 +1372,7 @@ extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond
 extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *features, int feat_stride,
                                               float *cond_a, float *cond_b, float *lpc, int n_frames)
 {
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's per-stream frame products are stale now)
+    forget_keep(b);
     if (n_frames <= 0 || feat_stride < LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     const size_t nfeat = (size_t)b->n * n_frames * feat_stride;
@@ -1403,14 +1396,11 @@ extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *fe
     return 0;
 }
 
-// ---- one frame step with PER-STREAM arguments (a batched packet-loss concealment needs it: src/lpcnet_plc.c calls
-// lpcnet_synthesize_impl(N = TRAINING_OFFSET, preload), lpcnet_synthesize_tail_impl(N, preload) and plain frames per
-// stream, depending on which of its streams lost a packet).  mode[s]: 0 = leave the stream alone, 1 = frame network on
-// features[s] + n_samples[s] samples (lpcnet_synthesize_impl, src/lpcnet.c:273-277), 2 = n_samples[s] samples from the
-// products of the stream's most recent frame (lpcnet_synthesize_tail_impl, src/lpcnet.c:235-271); the first preload[s]
-// samples of pcm[s] are imposed (teacher forcing).  Streams with equal (mode, n_samples, preload) form a group; a group is
-// compacted (states gathered by a small kernel, features / PCM on the host side), runs through the ordinary kernels and is
-// scattered back -- the hot kernels stay untouched; this path is meant for occasional use, not for throughput.
+// ---- compacted groups: a subset of the batch's streams through the ordinary frame and sample kernels (the per-stream-arguments step below
+// and the packet-loss concealment, whose streams take different branches in one step).  The streams of a group are named by an index map on
+// the device; their states, their features or kept frame products and their imposed PCM are gathered into dense arrays by small kernels,
+// the launch runs on those with the batch's streams per workgroup, and the results are scattered back by the same map -- the hot kernels
+// stay untouched.  A group runs the sample kernel far below its throughput: this is for occasional use.
 __global__ void lpcn_state_move_kernel(lpcn_stream_state *dst, const lpcn_stream_state *src, const int *map, int count, int scatter)
 {
     const int words = (int)(sizeof(lpcn_stream_state) / 4);
@@ -1420,15 +1410,70 @@ __global__ void lpcn_state_move_kernel(lpcn_stream_state *dst, const lpcn_stream
     uint32_t *d = (uint32_t *)(scatter ? &dst[map[i]] : &dst[i]);
     for (int k = threadIdx.x; k < words; k += blockDim.x) d[k] = s[k];
 }
-__global__ void lpcn_rows_move_kernel(float *dst, const float *src, const int *map, int count, int width, int scatter)
+// the buffers every group uses: the compacted states, features and PCM, and every stream's most recent frame products (zero until a stream has some)
+static int group_alloc(lpcn_batch_dev *b)
 {
-    const int i = blockIdx.x;
-    if (i >= count) return;
-    const float *s = src + (size_t)(scatter ? i : map[i]) * width;
-    float *d = dst + (size_t)(scatter ? map[i] : i) * width;
-    for (int k = threadIdx.x; k < width; k += blockDim.x) d[k] = s[k];
+    if (b->d_keep_lpc) return 0;      // (the last one allocated)
+    const size_t n = (size_t)b->n;
+    int rc = 0;
+    if ((rc = b->d_state_tmp.alloc(n)) || (rc = b->d_gfeat.alloc(n * LPCN_NB_FEAT)) || (rc = b->d_gpcm.alloc(n * LPCN_FRAME_SIZE)) || (rc = b->d_map.alloc(n)) ||
+        (rc = b->d_keep_a.alloc(n * LPCN_ROWS_A, true)) || (rc = b->d_keep_b.alloc(n * LPCN_ROWS_B, true))) return rc;
+    return b->d_keep_lpc.alloc(n * LPCN_LPC_ORDER, true);
 }
 
+// What one group runs (PLC_G_*): FRAMES the frame network alone, FRAME_SAMPLES the frame network and N samples (lpcnet_synthesize_impl,
+// src/lpcnet.c:273-277), TAIL N samples from the products of each stream's most recent kept frame (lpcnet_synthesize_tail_impl, :235-271).
+// Per-stream rows are given as (pointer, stride in elements): stream s's row starts at pointer + s * stride.
+struct GroupRun {
+    const int *map;                    // device: the group's stream indices
+    int cnt, kind, N, preload;         // streams; PLC_G_*; samples per frame and how many of them are imposed
+    const float *feat;                 // kinds with a frame step: every stream's feature vector
+    size_t feat_stride;
+    const short *pcm_src;              // the samples to impose (NULL: none are gathered)
+    size_t pcm_src_stride;
+    short *pcm_dst;                    // where the N samples go (NULL: they stay in the compacted d_gpcm, e.g. for a cross-fade)
+    size_t pcm_dst_stride;
+    bool keep;                         // remember the frame products per stream (lpcnet->gru_a_condition, gru_b_condition, lpc of the reference's state)
+    bool scatter;                      // write the states back (false: a trial run)
+};
+// Enqueues only; the caller checks hipGetLastError() after its groups.
+static int run_group(lpcn_batch_dev *b, hipStream_t st, const GroupRun &g)
+{
+    const int *map = g.map;
+    const int cnt = g.cnt;
+    hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, map, cnt, 0);
+    const LaunchShape sh = {cnt, g.N, b->d_state_tmp, b->S, b->pack2, b->x3};      // the compacted group, with the batch's streams per workgroup
+    int rc = 0;
+    if (g.kind != PLC_G_TAIL) {
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_gfeat, (size_t)LPCN_NB_FEAT, g.feat, g.feat_stride, map, cnt, LPCN_NB_FEAT, 0);
+        if ((rc = launch_frames(b, sh, st, b->d_gfeat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1))) return rc;
+        if (g.keep) {
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (size_t)LPCN_ROWS_A, (const float *)b->d_cond_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 1);
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (size_t)LPCN_ROWS_B, (const float *)b->d_cond_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 1);
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 1);
+        }
+    } else {
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_cond_a, (size_t)LPCN_ROWS_A, (const float *)b->d_keep_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 0);
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (size_t)LPCN_ROWS_B, (const float *)b->d_keep_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 0);
+        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 0);
+    }
+    if (g.kind != PLC_G_FRAMES) {
+        if (g.pcm_src)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, b->d_gpcm, (size_t)LPCN_FRAME_SIZE, g.pcm_src, g.pcm_src_stride, map, cnt, g.N, 0);
+        if ((rc = launch_sample(b, sh, st, b->d_gpcm, (size_t)LPCN_FRAME_SIZE, 1, g.preload, g.kind != PLC_G_TAIL))) return rc;
+        if (g.pcm_dst)
+            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, g.pcm_dst, g.pcm_dst_stride, (const short *)b->d_gpcm, (size_t)LPCN_FRAME_SIZE, map, cnt, g.N, 1);
+    }
+    if (g.scatter)
+        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, map, cnt, 1);
+    return 0;
+}
+
+// ---- one frame step with PER-STREAM arguments (src/lpcnet_plc.c calls lpcnet_synthesize_impl(N = TRAINING_OFFSET, preload),
+// lpcnet_synthesize_tail_impl(N, preload) and plain frames per stream, depending on which of its streams lost a packet).  mode[s]: 0 = leave
+// the stream alone, 1 = frame network on features[s] + n_samples[s] samples, 2 = n_samples[s] samples from the products of the stream's most
+// recent frame; the first preload[s] samples of pcm[s] are imposed (teacher forcing).  Streams with equal (mode, n_samples, preload) form a
+// group.  The call's features and PCM go up once, the groups run one after the other (run_group), the PCM comes back once.
 extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features, int feat_stride, short *pcm,
                                         const int *n_samples, const int *preload, const int *mode)
 {
@@ -1449,346 +1494,70 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
             return LPCN_E_ARG;
         }
     DeviceGuard guard(b->e->device);
-    int rc = ensure_staging(b, (size_t)b->n * LPCN_NB_FEAT, (size_t)b->n * LPCN_FRAME_SIZE);
+    const size_t nfeat = (size_t)(b->n - 1) * feat_stride + LPCN_NB_FEAT, npcm = (size_t)b->n * LPCN_FRAME_SIZE;
+    int rc = ensure_staging(b, nfeat, npcm);
+    if (!rc) rc = group_alloc(b);
     if (rc) return rc;
     hipStream_t st = b->e->stream;
     if ((rc = order_begin(b, st))) return rc;
     if ((rc = tune_if_due(b, st))) return rc;
-#define ALX(ptr, bytes) if (!(ptr) && hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", (size_t)(bytes)); return LPCN_E_HIP; }
-    ALX(b->d_state_tmp, sizeof(lpcn_stream_state) * b->n);
-    ALX(b->d_map, sizeof(int) * b->n);
-    if (!b->d_keep_a) {
-        ALX(b->d_keep_a, sizeof(float) * (size_t)b->n * LPCN_ROWS_A);
-        ALX(b->d_keep_b, sizeof(float) * (size_t)b->n * LPCN_ROWS_B);
-        ALX(b->d_keep_lpc, sizeof(float) * (size_t)b->n * LPCN_LPC_ORDER);
-        HIP_TRY(hipMemsetAsync(b->d_keep_a, 0, sizeof(float) * (size_t)b->n * LPCN_ROWS_A, st));
-        HIP_TRY(hipMemsetAsync(b->d_keep_b, 0, sizeof(float) * (size_t)b->n * LPCN_ROWS_B, st));
-        HIP_TRY(hipMemsetAsync(b->d_keep_lpc, 0, sizeof(float) * (size_t)b->n * LPCN_LPC_ORDER, st));
-    }
-#undef ALX
-    std::vector<char> done((size_t)b->n, 0);
+    struct Group { int off, cnt, mode, N, preload; };      // (off: the group's place in `map`, which holds every group's streams)
+    std::vector<Group> groups;
     std::vector<int> map;
-    std::vector<float> fc((size_t)b->n * LPCN_NB_FEAT);
-    std::vector<short> pc((size_t)b->n * LPCN_FRAME_SIZE);
+    std::vector<char> done((size_t)b->n, 0);
     for (int s0 = 0; s0 < b->n; ++s0) {
         if (done[s0] || mode[s0] == 0) continue;
-        map.clear();
+        const int off = (int)map.size();
         for (int s = s0; s < b->n; ++s)
             if (!done[s] && mode[s] == mode[s0] && n_samples[s] == n_samples[s0] && preload[s] == preload[s0]) { map.push_back(s); done[s] = 1; }
-        const int cnt = (int)map.size(), N = n_samples[s0], pre = preload[s0], md = mode[s0];
-        for (int i = 0; i < cnt; ++i) {
-            memcpy(&fc[(size_t)i * LPCN_NB_FEAT], features + (size_t)map[i] * feat_stride, sizeof(float) * LPCN_NB_FEAT);
-            memcpy(&pc[(size_t)i * LPCN_FRAME_SIZE], pcm + (size_t)map[i] * LPCN_FRAME_SIZE, sizeof(short) * LPCN_FRAME_SIZE);
-        }
-        HIP_TRY(hipMemcpyAsync(b->d_map, map.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b->d_feat, fc.data(), sizeof(float) * (size_t)cnt * LPCN_NB_FEAT, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b->d_pcm, pc.data(), sizeof(short) * (size_t)cnt * LPCN_FRAME_SIZE, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, (const int *)b->d_map, cnt, 0);
-        const LaunchShape sh = {cnt, N, b->d_state_tmp, b->S, b->pack2, b->x3};      // the compacted group, with the batch's streams per workgroup
-        if (md == 1) {
-            rc = launch_frames(b, sh, st, b->d_feat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1);
-            if (!rc) {      // remember the products per stream (a later tail-only step of the stream uses them)
-                hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (const float *)b->d_cond_a, (const int *)b->d_map, cnt, LPCN_ROWS_A, 1);
-                hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (const float *)b->d_cond_b, (const int *)b->d_map, cnt, LPCN_ROWS_B, 1);
-                hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_keep_lpc, (const float *)b->d_lpc, (const int *)b->d_map, cnt, LPCN_LPC_ORDER, 1);
-            }
-        } else {
-            hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_cond_a, (const float *)b->d_keep_a, (const int *)b->d_map, cnt, LPCN_ROWS_A, 0);
-            hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (const float *)b->d_keep_b, (const int *)b->d_map, cnt, LPCN_ROWS_B, 0);
-            hipLaunchKernelGGL(lpcn_rows_move_kernel, dim3(cnt), dim3(64), 0, st, b->d_lpc, (const float *)b->d_keep_lpc, (const int *)b->d_map, cnt, LPCN_LPC_ORDER, 0);
-        }
-        if (!rc) rc = launch_sample(b, sh, st, b->d_pcm, (size_t)LPCN_FRAME_SIZE, 1, pre, md == 1);
-        if (rc) return rc;
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, (const int *)b->d_map, cnt, 1);
-        if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "per-stream step: kernel launch failed"); return LPCN_E_HIP; }
-        HIP_TRY(hipMemcpyAsync(pc.data(), b->d_pcm, sizeof(short) * (size_t)cnt * LPCN_FRAME_SIZE, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        // only now do the group's streams own frame products a later tail-only step may continue from (the flag used to be
-        // set before the sample launch and the state scatter had succeeded)
-        if (md == 1) for (int i = 0; i < cnt; ++i) b->keep_ok[(size_t)map[i]] = 1;
-        for (int i = 0; i < cnt; ++i) memcpy(pcm + (size_t)map[i] * LPCN_FRAME_SIZE, &pc[(size_t)i * LPCN_FRAME_SIZE], sizeof(short) * (size_t)N);
+        groups.push_back({off, (int)map.size() - off, mode[s0], n_samples[s0], preload[s0]});
     }
+    if (groups.empty()) return 0;
+    HIP_TRY(hipMemcpyAsync(b->d_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_feat, features, sizeof(float) * nfeat, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->d_pcm, pcm, sizeof(short) * npcm, hipMemcpyHostToDevice, st));
+    for (const Group &g : groups) {
+        // (only the first N samples of a stream's frame are written: the rest of d_pcm, and the streams of mode 0, go back as they came)
+        const GroupRun r = {b->d_map + g.off, g.cnt, g.mode == 1 ? PLC_G_FRAME_SAMPLES : PLC_G_TAIL, g.N, g.preload, b->d_feat, (size_t)feat_stride,
+                            g.preload > 0 ? b->d_pcm.p : nullptr, (size_t)LPCN_FRAME_SIZE, b->d_pcm, (size_t)LPCN_FRAME_SIZE, g.mode == 1, true};
+        if ((rc = run_group(b, st, r))) return rc;
+    }
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "per-stream step: kernel launch failed"); return LPCN_E_HIP; }
+    HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, sizeof(short) * npcm, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // only now do the streams of the mode-1 groups own frame products a later tail-only step may continue from (the flag used to
+    // be set before the sample launch and the state scatter had succeeded)
+    for (const Group &g : groups)
+        if (g.mode == 1) for (int i = 0; i < g.cnt; ++i) b->keep_ok[(size_t)map[(size_t)g.off + i]] = 1;
     return 0;
 }
 
 // ------------------------------------------------------------------------------- packet-loss concealment -----
-// lpcnet_plc_update / lpcnet_plc_conceal in causal mode for every stream (src/lpcnet_plc.c:188-340).  No branch of the
-// reference looks at audio: the options, skip_analysis, blend, pcm_fill, loss_count, the FEC ring positions and fec_skip decide, and they
-// follow from the loss flags and the FEC calls.  So the host keeps that control state, derives every stream's branch for a step without
-// reading anything back, and lists the streams of every phase; the data stays on the device.  A step is one upload of those lists and a
-// fixed order of launches with no host synchronisation between them.
-enum { PLC_T_BURG, PLC_T_PRED, PLC_T_MIX, PLC_T_GROUP, PLC_T_ANALYSIS };
-enum { PLC_G_FRAMES, PLC_G_FRAME_SAMPLES, PLC_G_TAIL };
-struct PlcLaunch {
-    int type = 0, op = 0, off = 0, cnt = 0;
-    // groups: what runs on the compacted streams, where its features and PCM come from and go to
-    int kind = 0, N = LPCN_FRAME_SIZE, preload = 0;
-    int feat_src = 0;          // 0 st->features, 1 + k: entry k of the deferred queue
-    int pcm_src = 0;           // preload source: 0 none, 1 head of the PCM queue, 2 the call's frame at pcm_off
-    int pcm_dst = 0;           // 0 nowhere (the group's compacted PCM is left for a cross-fade), 1 the call's frame at pcm_off
-    int pcm_off = 0;
-    bool scatter = true, keep = false;
-};
-struct PlcPlan { std::vector<int> ctl; std::vector<PlcLaunch> launches; };
-
-struct lpcn_plc_host {
-    int options = 0;
-    bool blending = true, remove_dc = false;
-    std::vector<lpcn_plc_ctl> ctl;
-    lpcn::PlcData D{};
-    short *d_pcm = nullptr, *d_gpcm = nullptr;      // staging of the host-pointer call; the compacted PCM of a group
-    float *d_gfeat = nullptr;                       // the compacted features of a group / the parity seam's output
-    int *d_ident = nullptr;                         // 0 .. n-1
-    int *d_ctl = nullptr, *h_ctl = nullptr;         // the step's lists: device copy and its pinned source
-    size_t ctl_cap = 0;
-    hipEvent_t ev_ctl = nullptr;                    // the upload of the previous step's lists has left h_ctl
-    bool ctl_pending = false;
-    PlcPlan plan;
-};
-
-extern "C" void lpcn_plc_ctl_reset(lpcn_plc_ctl *c)
-{
-    memset(c, 0, sizeof(*c));
-    c->pcm_fill = LPCN_PLC_BUF_SIZE;      // src/lpcnet_plc.c:52-58
-}
-
-// get_fec_or_pred's decision and bookkeeping (src/lpcnet_plc.c:148-168)
-static bool plc_take_fec(lpcn_plc_ctl &c, int *row)
-{
-    if (c.fec_read != c.fec_fill && c.fec_skip == 0) {
-        *row = c.fec_read++;
-        const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
-        c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
-        if (c.fec_keep < 0) c.fec_keep = 0;
-        return true;
-    }
-    if (c.fec_skip > 0) c.fec_skip--;
-    *row = 0;
-    return false;
-}
-
-extern "C" int lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null)      // src/lpcnet_plc.c:109-127
-{
-    if (is_null) { c->fec_skip++; return 0; }
-    int moved = 0;
-    if (c->fec_fill == LPCN_PLC_MAX_FEC) {
-        if (c->fec_keep == 0) return 1;
-        c->fec_fill -= c->fec_keep;
-        c->fec_read -= c->fec_keep;
-        c->fec_keep = 0;
-        moved = 2;
-    }
-    c->fec_fill++;
-    return moved;
-}
-
-static int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
-
-static void plc_emit(PlcPlan &P, int type, int op, const std::vector<int> &recs, int rec_size)
-{
-    if (recs.empty()) return;
-    PlcLaunch L;
-    L.type = type; L.op = op; L.off = (int)P.ctl.size(); L.cnt = (int)recs.size() / rec_size;
-    P.ctl.insert(P.ctl.end(), recs.begin(), recs.end());
-    P.launches.push_back(L);
-}
-static void plc_emit_group(PlcPlan &P, const std::vector<int> &map, int kind, int N, int preload, int feat_src, int pcm_src, int pcm_dst, int pcm_off, bool scatter, bool keep)
-{
-    if (map.empty()) return;
-    PlcLaunch L;
-    L.type = PLC_T_GROUP; L.off = (int)P.ctl.size(); L.cnt = (int)map.size();
-    L.kind = kind; L.N = N; L.preload = preload; L.feat_src = feat_src; L.pcm_src = pcm_src; L.pcm_dst = pcm_dst; L.pcm_off = pcm_off; L.scatter = scatter; L.keep = keep;
-    P.ctl.insert(P.ctl.end(), map.begin(), map.end());
-    P.launches.push_back(L);
-}
-
-// One step of every stream's control state, and the launches it takes.  summary (may be NULL): LPCN_PLC_SUMMARY ints per stream.
-static int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary)
-{
-    using namespace lpcn;
-    const bool blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT, remove_dc = (options & 4) != 0;
-    static const float att_table[10] = {0, 0, -.2, -.2, -.4, -.4, -.8, -.8, -1.6, -1.6};      // src/lpcnet_plc.c:295
-    P.ctl.clear(); P.launches.clear();
-    for (int s = 0; s < n; ++s) {
-        const lpcn_plc_ctl &c = ctl[s];
-        const bool fill_ok = c.pcm_fill == 0 || c.pcm_fill == 80 || c.pcm_fill == 240 || c.pcm_fill == LPCN_PLC_BUF_SIZE;
-        if (!fill_ok || (!lost[s] && c.skip_analysis && !c.blend && c.pcm_fill + LPCN_FRAME_SIZE > LPCN_PLC_BUF_SIZE) || c.fbuf_fill < 0 || c.fbuf_fill > LPCN_PLC_FBUF ||
-            c.fec_keep < 0 || c.fec_keep > c.fec_read || c.fec_read > c.fec_fill || c.fec_fill > LPCN_PLC_MAX_FEC || c.fec_skip < 0 || c.skip_analysis < 0 || c.loss_count < 0) {
-            snprintf(g_err, sizeof(g_err), "stream %d: inconsistent PLC control state", s); return LPCN_E_ARG;
-        }
-    }
-    std::vector<int> flush[LPCN_PLC_FBUF], rpred[3], r160[3], r80[3], rshift[3], fpred, lostmap, dclost;
-    std::vector<int> burg, bpred, fa1, fa2, resetsig, xgrp, xfade, qtail, qappend, post_pred, fa3, qpush, dcrecv;
-    int zero[LPCN_PLC_SUMMARY];
-    for (int s = 0; s < n; ++s) {
-        lpcn_plc_ctl &c = ctl[s];
-        int *sm = summary ? summary + (size_t)s * LPCN_PLC_SUMMARY : zero;
-        memset(sm, 0, sizeof(int) * LPCN_PLC_SUMMARY);
-        if (lost[s]) {                                       // lpcnet_plc_conceal_causal, src/lpcnet_plc.c:296-340
-            sm[0] = 1; sm[1] = c.fbuf_fill;
-            for (int k = 0; k < c.fbuf_fill; ++k) flush[k].push_back(s);
-            c.fbuf_fill = 0;
-            for (int r = 0; c.pcm_fill > 0 && r < 3; ++r) {
-                const int N = c.pcm_fill < LPCN_FRAME_SIZE ? c.pcm_fill : LPCN_FRAME_SIZE;
-                int row = 0;
-                const bool fec = plc_take_fec(c, &row);
-                const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP);
-                const int rec[PLC_PRED_REC] = {s, fl, row, 0, 0, 0};
-                rpred[r].insert(rpred[r].end(), rec, rec + PLC_PRED_REC);
-                (N == LPCN_FRAME_SIZE ? r160 : r80)[r].push_back(s);
-                const int mr[PLC_MIX_REC] = {s, 0, 0};
-                rshift[r].insert(rshift[r].end(), mr, mr + PLC_MIX_REC);
-                c.pcm_fill -= N;
-                c.skip_analysis++;
-                sm[2]++; sm[3] += N; sm[4] += fec ? 1 : 0;
-            }
-            int row = 0;
-            const bool fec = plc_take_fec(c, &row);
-            if (fec) c.loss_count = 0; else c.loss_count++;
-            const float a1 = c.loss_count >= 10 ? att_table[9] : att_table[c.loss_count];
-            const float a2 = c.loss_count >= 10 ? (float)(2 * (c.loss_count - 9)) : 0.f;
-            const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP) | PLC_F_ATT;
-            const int rec[PLC_PRED_REC] = {s, fl, row, float_bits(a1), float_bits(a2), 0};
-            fpred.insert(fpred.end(), rec, rec + PLC_PRED_REC);
-            lostmap.push_back(s);
-            c.blend = 1;
-            sm[4] += fec ? 1 : 0; sm[9] = c.loss_count;
-            const int mr[PLC_MIX_REC] = {s, 0, 0};
-            if (remove_dc) dclost.insert(dclost.end(), mr, mr + PLC_MIX_REC);
-            continue;
-        }
-        // lpcnet_plc_update_causal, src/lpcnet_plc.c:188-290
-        burg.push_back(s);
-        const int mr[PLC_MIX_REC] = {s, 0, 0};
-        if (c.skip_analysis) {
-            if (c.blend) {
-                if (blending) {
-                    const int rec[PLC_PRED_REC] = {s, (2 << PLC_F_RESTORE_SHIFT) | (PLC_IN_BURG << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
-                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
-                    for (int k = 0; k < LPCN_FEATURES_DELAY; ++k) {
-                        const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 0};
-                        std::vector<int> &fa = k ? fa2 : fa1;
-                        fa.insert(fa.end(), fr, fr + PLC_MIX_REC);
-                        if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
-                    }
-                    const int xr[PLC_MIX_REC] = {s, (int)xgrp.size(), 0};
-                    xfade.insert(xfade.end(), xr, xr + PLC_MIX_REC);
-                    xgrp.push_back(s);
-                    sm[5] = 1; sm[8] += LPCN_FEATURES_DELAY;
-                } else {
-                    const int rec[PLC_PRED_REC] = {s, 1 << PLC_F_RESTORE_SHIFT, 0, 0, 0, 0};
-                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
-                    c.fec_read -= LPCN_FEATURES_DELAY;                      // fec_rewind, :170-175
-                    if (c.fec_read < c.fec_keep) c.fec_read = c.fec_keep;
-                    resetsig.insert(resetsig.end(), mr, mr + PLC_MIX_REC);
-                    sm[5] = 2;
-                }
-                qtail.insert(qtail.end(), mr, mr + PLC_MIX_REC);
-                c.pcm_fill = 80;
-                sm[6] = 1;
-            } else {
-                const int qr[PLC_MIX_REC] = {s, c.pcm_fill, 0};
-                qappend.insert(qappend.end(), qr, qr + PLC_MIX_REC);
-                c.pcm_fill += LPCN_FRAME_SIZE;
-                sm[6] = 2;
-            }
-        }
-        if (!c.blend) {
-            const int rec[PLC_PRED_REC] = {s, (PLC_IN_BURG_FEAT << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
-            post_pred.insert(post_pred.end(), rec, rec + PLC_PRED_REC);
-            if (c.fec_skip) c.fec_skip--;
-            else if (c.fec_read < c.fec_fill) c.fec_read++;
-            const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
-            c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
-            if (c.fec_keep < 0) c.fec_keep = 0;
-            sm[7] = 1;
-        }
-        bool append = false;
-        if (c.skip_analysis) {
-            append = blending;
-            c.skip_analysis--;
-        } else {
-            qpush.insert(qpush.end(), mr, mr + PLC_MIX_REC);
-            append = true;
-            sm[6] = 3;
-        }
-        if (append) {
-            const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 1};
-            fa3.insert(fa3.end(), fr, fr + PLC_MIX_REC);
-            if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
-            sm[8]++;
-        }
-        c.loss_count = 0;
-        if (remove_dc) dcrecv.insert(dcrecv.end(), mr, mr + PLC_MIX_REC);
-        c.blend = 0;
-    }
-    // lost streams: flush, the queued samples round by round, the concealed frame
-    for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
-    for (int r = 0; r < 3; ++r) {
-        plc_emit(P, PLC_T_PRED, 0, rpred[r], PLC_PRED_REC);
-        plc_emit_group(P, r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
-        plc_emit_group(P, r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
-        plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, rshift[r], PLC_MIX_REC);
-    }
-    plc_emit_group(P, lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
-    plc_emit(P, PLC_T_PRED, 0, fpred, PLC_PRED_REC);
-    plc_emit_group(P, lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
-    // received streams up to the analysis
-    if (!burg.empty()) { plc_emit(P, PLC_T_BURG, 0, burg, 1); }
-    plc_emit(P, PLC_T_PRED, 0, bpred, PLC_PRED_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa1, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa2, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_RESETSIG, resetsig, PLC_MIX_REC);
-    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 0, 0, false, false);      // into the group's PCM; the states are not written back (the reference's copy / restore)
-    plc_emit(P, PLC_T_MIX, PLC_MIX_XFADE, xfade, PLC_MIX_REC);
-    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_QTAIL, qtail, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_QAPPEND, qappend, PLC_MIX_REC);
-    { PlcLaunch L; L.type = PLC_T_ANALYSIS; P.launches.push_back(L); }
-    plc_emit(P, PLC_T_PRED, 0, post_pred, PLC_PRED_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa3, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_QPUSH, qpush, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_DCRECV, dcrecv, PLC_MIX_REC);
-    plc_emit(P, PLC_T_MIX, PLC_MIX_DCLOST, dclost, PLC_MIX_REC);
-    return 0;
-}
-
+// lpcnet_plc_update / lpcnet_plc_conceal in causal mode for every stream (src/lpcnet_plc.c:188-340).  The host keeps the control
+// state and plans every step (plc_plan.h: no device needed); the data stays on the device.  A step is one upload of the planner's lists and
+// a fixed order of launches with no host synchronisation between them.
 extern "C" int lpcn_plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary)
 {
     if (n < 1 || !ctl || !lost || (options & 3) == 1 || (options & 3) == 3 || (options & ~7)) { snprintf(g_err, sizeof(g_err), "bad PLC plan arguments"); return LPCN_E_ARG; }
     PlcPlan P;
-    return plc_plan(options, n, ctl, lost, P, summary);
+    return plc_plan(options, n, ctl, lost, P, summary, g_err, sizeof(g_err));
 }
 
 extern "C" int lpcn_engine_plc_present(const lpcn_engine *e) { return e->plc_present; }
 extern "C" int lpcn_batch_dev_plc_enabled(const lpcn_batch_dev *b) { return b->plc ? 1 : 0; }
-
-static void plc_free(lpcn_batch_dev *b)
-{
-    lpcn_plc_host *p = b->plc;
-    if (!p) return;
-    void *ptrs[] = {p->D.q, p->D.feat, p->D.net, p->D.dc, p->D.delta, p->D.fec, p->D.fbuf, p->D.lp, p->D.burg, p->D.an, p->d_pcm, p->d_gpcm, p->d_gfeat, p->d_ident, p->d_ctl};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    if (p->h_ctl) (void)hipHostFree(p->h_ctl);
-    if (p->ev_ctl) (void)hipEventDestroy(p->ev_ctl);
-    delete p;
-    b->plc = nullptr;
-}
-
 static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(b->e->plc.g1 + b->e->plc.g2); }
-
 // lpcnet_plc_reset (src/lpcnet_plc.c:46-60) on streams [first, first + count): the PLC's own fields, the synthesis state, the analysis state
 static int plc_reset_range(lpcn_batch_dev *b, int first, int count)
 {
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     int rc = lpcn_batch_dev_reset(b, first, count);      // (waits for everything enqueued)
     if (!rc) rc = lpcn_batch_dev_analysis_reset(b, first, count);
     if (rc || !count) return rc;
     const size_t G4 = plc_net_floats(b);
-#define ZR(ptr, per) HIP_TRY(hipMemset((ptr) + (size_t)first * (per), 0, sizeof(*(ptr)) * (size_t)count * (per)))
-    ZR(p->D.q, LPCN_PLC_QUEUE); ZR(p->D.feat, LPCN_NB_FEAT); ZR(p->D.net, G4); ZR(p->D.dc, 2); ZR(p->D.delta, 1);
-    ZR(p->D.fec, LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); ZR(p->D.fbuf, LPCN_PLC_FBUF * LPCN_NB_FEAT); ZR(p->D.lp, LPCN_FRAME_SIZE);
-    ZR(p->D.burg, 2 * LPCN_NB_BANDS); ZR(p->D.an, LPCN_AN_NB_FEATURES);
+#define ZR(buf, per) HIP_TRY(hipMemset((buf).p + (size_t)first * (per), 0, sizeof(*(buf).p) * (size_t)count * (per)))
+    ZR(p->q, LPCN_PLC_QUEUE); ZR(p->feat, LPCN_NB_FEAT); ZR(p->net, G4); ZR(p->dc, 2); ZR(p->delta, 1);
+    ZR(p->fec, LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); ZR(p->fbuf, LPCN_PLC_FBUF * LPCN_NB_FEAT); ZR(p->lp, LPCN_FRAME_SIZE);
+    ZR(p->burg, 2 * LPCN_NB_BANDS); ZR(p->an, LPCN_AN_NB_FEATURES);
     ZR(b->d_keep_a, LPCN_ROWS_A); ZR(b->d_keep_b, LPCN_ROWS_B); ZR(b->d_keep_lpc, LPCN_LPC_ORDER);
 #undef ZR
     for (int s = first; s < first + count; ++s) lpcn_plc_ctl_reset(&p->ctl[s]);
@@ -1806,103 +1575,66 @@ extern "C" int lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options)
     if (rc) return rc;
     { int rcw = wait_all(b); if (rcw) return rcw; }
     if (!b->plc) {
-        lpcn_plc_host *p = new lpcn_plc_host();
-        b->plc = p;
-        const size_t n = (size_t)b->n, G4 = plc_net_floats(b);
-        auto fail = [&](int code) { plc_free(b); return code; };
-#define ALP(ptr, count) if (hipMalloc((void **)&(ptr), sizeof(*(ptr)) * (count)) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipMalloc failed"); return fail(LPCN_E_HIP); }
-        ALP(p->D.q, n * LPCN_PLC_QUEUE); ALP(p->D.feat, n * LPCN_NB_FEAT); ALP(p->D.net, n * G4); ALP(p->D.dc, n * 2); ALP(p->D.delta, n);
-        ALP(p->D.fec, n * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); ALP(p->D.fbuf, n * LPCN_PLC_FBUF * LPCN_NB_FEAT); ALP(p->D.lp, n * LPCN_FRAME_SIZE);
-        ALP(p->D.burg, n * 2 * LPCN_NB_BANDS); ALP(p->D.an, n * LPCN_AN_NB_FEATURES);
-        ALP(p->d_pcm, n * LPCN_FRAME_SIZE); ALP(p->d_gpcm, n * LPCN_FRAME_SIZE); ALP(p->d_gfeat, n * LPCN_NB_FEAT); ALP(p->d_ident, n);
-        p->ctl_cap = 64 * n + 64;
-        ALP(p->d_ctl, p->ctl_cap);
-        if (!b->d_state_tmp) ALP(b->d_state_tmp, n);
-        if (!b->d_keep_a) { ALP(b->d_keep_a, n * LPCN_ROWS_A); ALP(b->d_keep_b, n * LPCN_ROWS_B); ALP(b->d_keep_lpc, n * LPCN_LPC_ORDER); }
-#undef ALP
-        if (hipHostMalloc((void **)&p->h_ctl, sizeof(int) * p->ctl_cap, hipHostMallocDefault) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipHostMalloc failed"); return fail(LPCN_E_HIP); }
-        if (hipEventCreateWithFlags(&p->ev_ctl, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipEventCreate failed"); return fail(LPCN_E_HIP); }
+        auto p = std::make_unique<lpcn_plc_host>();      // (a failure below frees what it holds; the batch stays without PLC)
+        const size_t n = (size_t)b->n;
+        if ((rc = p->q.alloc(n * LPCN_PLC_QUEUE)) || (rc = p->feat.alloc(n * LPCN_NB_FEAT)) || (rc = p->net.alloc(n * plc_net_floats(b))) || (rc = p->dc.alloc(n * 2)) ||
+            (rc = p->delta.alloc(n)) || (rc = p->fec.alloc(n * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT)) || (rc = p->fbuf.alloc(n * LPCN_PLC_FBUF * LPCN_NB_FEAT)) ||
+            (rc = p->lp.alloc(n * LPCN_FRAME_SIZE)) || (rc = p->burg.alloc(n * 2 * LPCN_NB_BANDS)) || (rc = p->an.alloc(n * LPCN_AN_NB_FEATURES)) ||
+            (rc = p->d_pcm.alloc(n * LPCN_FRAME_SIZE)) || (rc = p->d_ident.alloc(n)) || (rc = p->d_ctl.alloc(64 * n + 64)) ||
+            (rc = p->h_ctl.reserve(sizeof(int) * p->d_ctl.cap)) || (rc = group_alloc(b))) return rc;
+        p->D = {p->q, p->feat, p->net, p->dc, p->delta, p->fec, p->fbuf, p->lp, p->burg, p->an};
+        if (hipEventCreateWithFlags(&p->ev_ctl.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipEventCreate failed"); return LPCN_E_HIP; }
         std::vector<int> ident(n);
         for (size_t i = 0; i < n; ++i) ident[i] = (int)i;
-        if (hipMemcpy(p->d_ident, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: upload failed"); return fail(LPCN_E_HIP); }
+        if (hipMemcpy(p->d_ident, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: upload failed"); return LPCN_E_HIP; }
         p->ctl.resize(n);
+        b->plc = std::move(p);
     }
-    lpcn_plc_host *p = b->plc;
-    p->options = options; p->blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT; p->remove_dc = (options & 4) != 0;
+    b->plc->options = options; b->plc->remove_dc = (options & 4) != 0;
     return plc_reset_range(b, 0, b->n);
 }
-
 #define NEED_PLC(b) do { if (!(b)->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; } } while (0)
 
 extern "C" int lpcn_batch_dev_plc_reset(lpcn_batch_dev *b, int first, int count)
 {
     NEED_PLC(b);
-    if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "PLC reset range"); return LPCN_E_ARG; }
+    if (check_range(b, first, count, "PLC reset")) return LPCN_E_ARG;
     DeviceGuard guard(b->e->device);
     return plc_reset_range(b, first, count);
 }
 
-// a group of streams through the ordinary frame and sample kernels: states, features and PCM gathered by the index map, results scattered back
-static int plc_run_group(lpcn_batch_dev *b, hipStream_t st, const PlcLaunch &L, short *d_pcm)
+// a group of the plan: its sources and destinations among the PLC's arrays and the call's frame
+static GroupRun plc_group(lpcn_plc_host *p, const PlcLaunch &L, short *d_pcm)
 {
-    lpcn_plc_host *p = b->plc;
-    const int *map = p->d_ctl + L.off;
-    const int cnt = L.cnt;
-    hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, map, cnt, 0);
-    const LaunchShape sh = {cnt, L.N, b->d_state_tmp, b->S, b->pack2, b->x3};
-    int rc = 0;
-    if (L.kind != PLC_G_TAIL) {
-        const float *src = L.feat_src == 0 ? p->D.feat : p->D.fbuf + (size_t)(L.feat_src - 1) * LPCN_NB_FEAT;
-        const size_t stride = L.feat_src == 0 ? LPCN_NB_FEAT : LPCN_PLC_FBUF * LPCN_NB_FEAT;
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, p->d_gfeat, (size_t)LPCN_NB_FEAT, src, stride, map, cnt, LPCN_NB_FEAT, 0);
-        if ((rc = launch_frames(b, sh, st, p->d_gfeat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1))) return rc;
-        if (L.keep) {      // the stream's most recent frame products (lpcnet->gru_a_condition, gru_b_condition, lpc of the reference's state)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (size_t)LPCN_ROWS_A, (const float *)b->d_cond_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 1);
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (size_t)LPCN_ROWS_B, (const float *)b->d_cond_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 1);
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 1);
-        }
-    } else {
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_cond_a, (size_t)LPCN_ROWS_A, (const float *)b->d_keep_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 0);
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (size_t)LPCN_ROWS_B, (const float *)b->d_keep_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 0);
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 0);
-    }
-    if (L.kind != PLC_G_FRAMES) {
-        if (L.pcm_src == 1)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, (const short *)p->D.q, (size_t)LPCN_PLC_QUEUE, map, cnt, L.N, 0);
-        else if (L.pcm_src == 2)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, (const short *)(d_pcm + L.pcm_off), (size_t)LPCN_FRAME_SIZE, map, cnt, L.N, 0);
-        if ((rc = launch_sample(b, sh, st, p->d_gpcm, (size_t)LPCN_FRAME_SIZE, 1, L.preload, L.kind != PLC_G_TAIL))) return rc;
-        if (L.pcm_dst == 1)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, d_pcm + L.pcm_off, (size_t)LPCN_FRAME_SIZE, (const short *)p->d_gpcm, (size_t)LPCN_FRAME_SIZE, map, cnt, L.N, 1);
-    }
-    if (L.scatter)
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, map, cnt, 1);
-    return 0;
+    const bool queued = L.feat_src != 0;      // the features are entry feat_src - 1 of the deferred queue, else st->features
+    return {p->d_ctl + L.off, L.cnt, L.kind, L.N, L.preload,
+            queued ? p->fbuf + (size_t)(L.feat_src - 1) * LPCN_NB_FEAT : p->feat.p, queued ? (size_t)LPCN_PLC_FBUF * LPCN_NB_FEAT : (size_t)LPCN_NB_FEAT,
+            L.pcm_src == 1 ? p->q.p : L.pcm_src == 2 ? d_pcm + L.pcm_off : nullptr, L.pcm_src == 1 ? (size_t)LPCN_PLC_QUEUE : (size_t)LPCN_FRAME_SIZE,
+            L.pcm_dst == 1 ? d_pcm + L.pcm_off : nullptr, (size_t)LPCN_FRAME_SIZE, L.keep, L.scatter};
 }
-
 extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned char *lost, void *hip_stream)
 {
     NEED_PLC(b);
     if (!d_pcm || !lost) { snprintf(g_err, sizeof(g_err), "bad PLC step arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     if (stream_is_capturing(st)) {
         snprintf(g_err, sizeof(g_err), "a PLC step cannot be captured: its launch sequence depends on the loss flags"); return LPCN_E_ARG;
     }
     { int rco = order_begin(b, st); if (rco) return rco; }
     if (p->ctl_pending) { HIP_TRY(hipEventSynchronize(p->ev_ctl)); p->ctl_pending = false; }      // (the previous step's lists have left the pinned buffer: long done)
-    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr);
+    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr, g_err, sizeof(g_err));
     if (rc) return rc;
     const PlcPlan &P = p->plan;
-    if (P.ctl.size() > p->ctl_cap) { snprintf(g_err, sizeof(g_err), "PLC step: control lists exceed their buffer"); return LPCN_E_HIP; }
+    if (P.ctl.size() > p->d_ctl.cap) { snprintf(g_err, sizeof(g_err), "PLC step: control lists exceed their buffer"); return LPCN_E_HIP; }
     if (!P.ctl.empty()) {
-        memcpy(p->h_ctl, P.ctl.data(), sizeof(int) * P.ctl.size());
-        HIP_TRY(hipMemcpyAsync(p->d_ctl, p->h_ctl, sizeof(int) * P.ctl.size(), hipMemcpyHostToDevice, st));
+        memcpy(p->h_ctl.p, P.ctl.data(), sizeof(int) * P.ctl.size());
+        HIP_TRY(hipMemcpyAsync(p->d_ctl, p->h_ctl.p, sizeof(int) * P.ctl.size(), hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(p->ev_ctl, st));
         p->ctl_pending = true;
     }
-    if (!b->keep_ok.empty()) b->keep_ok.assign(b->keep_ok.size(), 0);      // (lpcn_batch_dev_step_host's products are the PLC's now)
+    forget_keep(b);      // (lpcn_batch_dev_step_host's products are the PLC's now)
     for (const PlcLaunch &L : P.launches) {
         const int *ctl = p->d_ctl + L.off;
         switch (L.type) {
@@ -1913,10 +1645,10 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(L.cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, L.cnt, p->D, (float *)nullptr);
             break;
         case PLC_T_MIX:
-            hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)p->d_gpcm, p->D, b->d_state);
+            hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)b->d_gpcm, p->D, b->d_state);
             break;
         case PLC_T_GROUP:
-            if ((rc = plc_run_group(b, st, L, d_pcm))) return rc;
+            if ((rc = run_group(b, st, plc_group(p, L, d_pcm)))) return rc;
             break;
         case PLC_T_ANALYSIS:
             if ((rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, 1, d_pcm, 0, (size_t)LPCN_FRAME_SIZE, b->d_an_state, p->D.an, LPCN_AN_NB_FEATURES,
@@ -1933,7 +1665,7 @@ extern "C" int lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const
     NEED_PLC(b);
     if (!pcm || !lost) { snprintf(g_err, sizeof(g_err), "bad PLC step arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     hipStream_t st = b->e->stream;
     int rc = order_begin(b, st);
     if (rc) return rc;
@@ -1950,7 +1682,7 @@ extern "C" int lpcn_batch_dev_plc_fec_add(lpcn_batch_dev *b, int s, const float 
 {
     NEED_PLC(b);
     if (s < 0 || s >= b->n) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     lpcn_plc_ctl &c = p->ctl[s];
     const int keep = c.fec_keep, fill = c.fec_fill;
     const int r = lpcn_plc_ctl_fec_add(&c, features20 == nullptr);
@@ -1958,7 +1690,7 @@ extern "C" int lpcn_batch_dev_plc_fec_add(lpcn_batch_dev *b, int s, const float 
     if (r == 1) { snprintf(g_err, sizeof(g_err), "stream %d: FEC buffer full", s); return 1; }      // (the reference prints this and drops the vector)
     DeviceGuard guard(b->e->device);
     { int rcw = wait_all(b); if (rcw) return rcw; }
-    float *ring = p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT;
+    float *ring = p->fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT;
     if (r == 2) {
         hipLaunchKernelGGL(lpcn::plc_fec_move_kernel, dim3(1), dim3(256), 0, b->e->stream, ring, keep, fill - keep);
         HIP_TRY(hipStreamSynchronize(b->e->stream));
@@ -1976,55 +1708,49 @@ extern "C" int lpcn_batch_dev_plc_fec_clear(lpcn_batch_dev *b, int s)
     return 0;
 }
 
+// one stream's record, both halves: the device arrays' part field by field, down into *h or up from it
+static int plc_state_copy(lpcn_batch_dev *b, int s, lpcn_plc_state_rec *h, bool up)
+{
+    lpcn_plc_host *p = b->plc.get();
+    const size_t i = (size_t)s, G = (size_t)(b->e->plc.g1 + b->e->plc.g2);
+    const struct { void *dev, *host; size_t bytes; } fields[] = {
+        {p->delta + i, &h->delta, sizeof(int)}, {p->dc + 2 * i, h->dc, sizeof(h->dc)}, {p->q + i * LPCN_PLC_QUEUE, h->q, sizeof(h->q)},
+        {p->feat + i * LPCN_NB_FEAT, h->feat, sizeof(h->feat)},
+        {p->net + (4 * i + 0) * G, h->net[0], sizeof(float) * G}, {p->net + (4 * i + 1) * G, h->net[1], sizeof(float) * G},
+        {p->net + (4 * i + 2) * G, h->net[2], sizeof(float) * G}, {p->net + (4 * i + 3) * G, h->net[3], sizeof(float) * G},
+        {p->fec + i * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT, h->fec, sizeof(h->fec)}, {p->fbuf + i * LPCN_PLC_FBUF * LPCN_NB_FEAT, h->fbuf, sizeof(h->fbuf)},
+        {b->d_keep_a + i * LPCN_ROWS_A, h->keep_a, sizeof(h->keep_a)}, {b->d_keep_b + i * LPCN_ROWS_B, h->keep_b, sizeof(h->keep_b)},
+        {b->d_keep_lpc + i * LPCN_LPC_ORDER, h->keep_lpc, sizeof(h->keep_lpc)}};
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (up) p->ctl[i] = h->ctl;
+    for (const auto &f : fields) HIP_TRY(up ? hipMemcpy(f.dev, f.host, f.bytes, hipMemcpyHostToDevice) : hipMemcpy(f.host, f.dev, f.bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int s, lpcn_plc_state_rec *h)
 {
     NEED_PLC(b);
     if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    DeviceGuard guard(b->e->device);
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    lpcn_plc_host *p = b->plc;
-    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2, G = g1 + g2;
     memset(h, 0, sizeof(*h));
-    h->ctl = p->ctl[s]; h->g1 = g1; h->g2 = g2;
-#define DN(dst, src, count) HIP_TRY(hipMemcpy(dst, src, sizeof(*(src)) * (size_t)(count), hipMemcpyDeviceToHost))
-    DN(&h->delta, p->D.delta + s, 1); DN(h->dc, p->D.dc + 2 * (size_t)s, 2); DN(h->q, p->D.q + (size_t)s * LPCN_PLC_QUEUE, LPCN_PLC_QUEUE);
-    DN(h->feat, p->D.feat + (size_t)s * LPCN_NB_FEAT, LPCN_NB_FEAT);
-    for (int k = 0; k < 4; ++k) DN(h->net[k], p->D.net + ((size_t)s * 4 + k) * G, G);
-    DN(&h->fec[0][0], p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT, LPCN_PLC_MAX_FEC * LPCN_NB_FEAT);
-    DN(&h->fbuf[0][0], p->D.fbuf + (size_t)s * LPCN_PLC_FBUF * LPCN_NB_FEAT, LPCN_PLC_FBUF * LPCN_NB_FEAT);
-    DN(h->keep_a, b->d_keep_a + (size_t)s * LPCN_ROWS_A, LPCN_ROWS_A); DN(h->keep_b, b->d_keep_b + (size_t)s * LPCN_ROWS_B, LPCN_ROWS_B);
-    DN(h->keep_lpc, b->d_keep_lpc + (size_t)s * LPCN_LPC_ORDER, LPCN_LPC_ORDER);
-#undef DN
-    return 0;
+    h->ctl = b->plc->ctl[s]; h->g1 = b->e->plc.g1; h->g2 = b->e->plc.g2;
+    return plc_state_copy(b, s, h, false);
 }
 
 extern "C" int lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int s, const lpcn_plc_state_rec *h)
 {
     NEED_PLC(b);
     if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2, G = g1 + g2;
+    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2;
     if (h->g1 != g1 || h->g2 != g2) { snprintf(g_err, sizeof(g_err), "PLC state of a %d / %d network on a %d / %d network", h->g1, h->g2, g1, g2); return LPCN_E_ARG; }
     {   // (the planner's own consistency check, on a copy)
         lpcn_plc_ctl c = h->ctl;
         const unsigned char one = 1;
         PlcPlan P;
-        int rc = plc_plan(b->plc->options, 1, &c, &one, P, nullptr);
+        int rc = plc_plan(b->plc->options, 1, &c, &one, P, nullptr, g_err, sizeof(g_err));
         if (rc) return rc;
     }
-    DeviceGuard guard(b->e->device);
-    { int rcw = wait_all(b); if (rcw) return rcw; }
-    lpcn_plc_host *p = b->plc;
-    p->ctl[s] = h->ctl;
-#define UPS(dst, src, count) HIP_TRY(hipMemcpy(dst, src, sizeof(*(dst)) * (size_t)(count), hipMemcpyHostToDevice))
-    UPS(p->D.delta + s, &h->delta, 1); UPS(p->D.dc + 2 * (size_t)s, h->dc, 2); UPS(p->D.q + (size_t)s * LPCN_PLC_QUEUE, h->q, LPCN_PLC_QUEUE);
-    UPS(p->D.feat + (size_t)s * LPCN_NB_FEAT, h->feat, LPCN_NB_FEAT);
-    for (int k = 0; k < 4; ++k) UPS(p->D.net + ((size_t)s * 4 + k) * G, h->net[k], G);
-    UPS(p->D.fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT, &h->fec[0][0], LPCN_PLC_MAX_FEC * LPCN_NB_FEAT);
-    UPS(p->D.fbuf + (size_t)s * LPCN_PLC_FBUF * LPCN_NB_FEAT, &h->fbuf[0][0], LPCN_PLC_FBUF * LPCN_NB_FEAT);
-    UPS(b->d_keep_a + (size_t)s * LPCN_ROWS_A, h->keep_a, LPCN_ROWS_A); UPS(b->d_keep_b + (size_t)s * LPCN_ROWS_B, h->keep_b, LPCN_ROWS_B);
-    UPS(b->d_keep_lpc + (size_t)s * LPCN_LPC_ORDER, h->keep_lpc, LPCN_LPC_ORDER);
-#undef UPS
-    return 0;
+    return plc_state_copy(b, s, const_cast<lpcn_plc_state_rec *>(h), true);      // (up: *h is only read)
 }
 
 // parity seam: burg_cepstral_analysis on one frame per stream.  x holds PCM values as the PLC feeds them (x[i] = pcm[i], src/lpcnet_plc.c:206):
@@ -2041,13 +1767,13 @@ extern "C" int lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, f
     }
     DeviceGuard guard(b->e->device);
     { int rcw = wait_all(b); if (rcw) return rcw; }
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     hipStream_t st = b->e->stream;
     HIP_TRY(hipMemcpy(p->d_pcm, pc.data(), sizeof(short) * count, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(b->n), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, (const int *)p->d_ident, b->n, p->d_pcm, p->D, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(ceps36, p->D.burg, sizeof(float) * (size_t)b->n * 2 * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ceps36, p->burg, sizeof(float) * (size_t)b->n * 2 * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2058,22 +1784,22 @@ extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57
     if (!in57 || !out20) { snprintf(g_err, sizeof(g_err), "bad arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
     { int rcw = wait_all(b); if (rcw) return rcw; }
-    lpcn_plc_host *p = b->plc;
+    lpcn_plc_host *p = b->plc.get();
     hipStream_t st = b->e->stream;
     std::vector<int> recs((size_t)b->n * lpcn::PLC_PRED_REC, 0);
-    if (recs.size() > p->ctl_cap) { snprintf(g_err, sizeof(g_err), "plc_pred: control buffer"); return LPCN_E_HIP; }
+    if (recs.size() > p->d_ctl.cap) { snprintf(g_err, sizeof(g_err), "plc_pred: control buffer"); return LPCN_E_HIP; }
     for (int s = 0; s < b->n; ++s) {
         const float *in = in57 + (size_t)s * LPCN_PLC_IN;
         int *r = &recs[(size_t)s * lpcn::PLC_PRED_REC];
         r[0] = s; r[1] = lpcn::PLC_F_COMPUTE | lpcn::PLC_F_RAW; r[3] = float_bits(in[LPCN_PLC_IN - 1]);
-        HIP_TRY(hipMemcpy(p->D.burg + (size_t)s * 2 * LPCN_NB_BANDS, in, sizeof(float) * 2 * LPCN_NB_BANDS, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(p->D.an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->burg + (size_t)s * 2 * LPCN_NB_BANDS, in, sizeof(float) * 2 * LPCN_NB_BANDS, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(p->d_ctl, recs.data(), sizeof(int) * recs.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(b->n), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, (const int *)p->d_ctl, b->n, p->D, p->d_gfeat);
+    hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(b->n), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, (const int *)p->d_ctl, b->n, p->D, b->d_gfeat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(out20, p->d_gfeat, sizeof(float) * (size_t)b->n * LPCN_NB_FEAT, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out20, b->d_gfeat, sizeof(float) * (size_t)b->n * LPCN_NB_FEAT, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2083,12 +1809,8 @@ extern "C" int lpcn_batch_dev_debug_trace(lpcn_batch_dev *b, int n_samples, floa
     DeviceGuard guard(b->e->device);
     if (host_out == nullptr) {
         { int rcw = wait_all(b); if (rcw) return rcw; }
-        if (b->d_dbg) { (void)hipFree(b->d_dbg); b->d_dbg = nullptr; }
-        if (n_samples > 0) {
-            HIP_TRY(hipMalloc((void **)&b->d_dbg, sizeof(float) * (size_t)n_samples * LPCN_DBG_STRIDE));
-            HIP_TRY(hipMemset(b->d_dbg, 0, sizeof(float) * (size_t)n_samples * LPCN_DBG_STRIDE));
-        }
-        return 0;
+        b->d_dbg.release();
+        return n_samples > 0 ? b->d_dbg.alloc((size_t)n_samples * LPCN_DBG_STRIDE, true) : 0;
     }
     if (!b->d_dbg) { snprintf(g_err, sizeof(g_err), "trace not enabled"); return LPCN_E_ARG; }
     { int rcw = wait_all(b); if (rcw) return rcw; }
@@ -2100,7 +1822,7 @@ extern "C" int lpcn_batch_dev_debug_trace(lpcn_batch_dev *b, int n_samples, floa
 extern "C" int lpcn_batch_dev_profile(lpcn_batch_dev *b, unsigned long long *out)
 {
     DeviceGuard guard(b->e->device);
-    if (!b->d_prof) HIP_TRY(hipMalloc((void **)&b->d_prof, 96 * sizeof(unsigned long long)));
+    if (!b->d_prof) { int rca = b->d_prof.alloc(96); if (rca) return rca; }
     { int rcw = wait_all(b); if (rcw) return rcw; }
     if (!out) { HIP_TRY(hipMemset(b->d_prof, 0, 96 * sizeof(unsigned long long))); return 0; }
     HIP_TRY(hipMemcpy(out, b->d_prof, 96 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -2113,17 +1835,15 @@ extern "C" int lpcn_debug_exp10(int device, const float *x, double *out, size_t 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { snprintf(g_err, sizeof(g_err), "no such HIP device"); return LPCN_E_NODEVICE; }
     DeviceGuard guard(device);
-    float *dx = nullptr;
-    double *dy = nullptr;
-    HIP_TRY(hipMalloc((void **)&dx, n * sizeof(float)));
-    if (hipMalloc((void **)&dy, n * sizeof(double)) != hipSuccess) { (void)hipFree(dx); snprintf(g_err, sizeof(g_err), "hipMalloc failed"); return LPCN_E_HIP; }
+    DevBuf<float> dx;
+    DevBuf<double> dy;
     int rc = 0;
+    if ((rc = dx.alloc(n)) || (rc = dy.alloc(n))) return rc;
     if (hipMemcpy(dx, x, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = LPCN_E_HIP;
     if (!rc) {
-        hipLaunchKernelGGL(lpcn::exp10_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)dx, dy, n);
+        hipLaunchKernelGGL(lpcn::exp10_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (const float *)dx, dy.p, n);
         if (hipGetLastError() != hipSuccess || hipMemcpy(out, dy, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = LPCN_E_HIP;
     }
-    (void)hipFree(dx); (void)hipFree(dy);
     if (rc) snprintf(g_err, sizeof(g_err), "exp10 test kernel failed");
     return rc;
 }
@@ -2177,11 +1897,10 @@ extern "C" int lpcn_debug_arith_identities(int device, const float *a, const flo
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { snprintf(g_err, sizeof(g_err), "no such HIP device"); return LPCN_E_NODEVICE; }
     if (!n || n % 64) { snprintf(g_err, sizeof(g_err), "operand count must be a positive multiple of 64"); return LPCN_E_ARG; }
     DeviceGuard guard(device);
-    float *d_in = nullptr;
-    uint32_t *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_in, 2 * n * sizeof(float)));
-    if (hipMalloc((void **)&d_out, 16 * n * sizeof(uint32_t)) != hipSuccess) { (void)hipFree(d_in); snprintf(g_err, sizeof(g_err), "hipMalloc failed"); return LPCN_E_HIP; }
+    DevBuf<float> d_in;
+    DevBuf<uint32_t> d_out;
     int rc = 0;
+    if ((rc = d_in.alloc(2 * n)) || (rc = d_out.alloc(16 * n))) return rc;
     if (hipMemcpy(d_in, a, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_in + n, b, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = LPCN_E_HIP;
     if (!rc) {
@@ -2192,7 +1911,6 @@ extern "C" int lpcn_debug_arith_identities(int device, const float *a, const flo
         for (int k = 0; k < 4 && !rc; ++k)
             if (hipMemcpy(dst[k], d_out + (size_t)k * 4 * n, 4 * n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = LPCN_E_HIP;
     }
-    (void)hipFree(d_in); (void)hipFree(d_out);
     if (rc) snprintf(g_err, sizeof(g_err), "arithmetic identity test kernel failed");
     return rc;
 }
@@ -2224,15 +1942,14 @@ extern "C" int lpcn_debug_quant_sweep(int device, unsigned long long *out3)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { snprintf(g_err, sizeof(g_err), "no such HIP device"); return LPCN_E_NODEVICE; }
     DeviceGuard guard(device);
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 3 * sizeof(unsigned long long)));
-    int rc = 0;
+    DevBuf<unsigned long long> d;
+    int rc = d.alloc(3);
+    if (rc) return rc;
     if (hipMemset(d, 0, 3 * sizeof(unsigned long long)) != hipSuccess) rc = LPCN_E_HIP;
     if (!rc) {
-        hipLaunchKernelGGL(lpcn_quant_sweep_kernel, dim3(65536), dim3(256), 0, 0, d);      // 2^16 x 2^8 threads x 2^8 patterns
+        hipLaunchKernelGGL(lpcn_quant_sweep_kernel, dim3(65536), dim3(256), 0, 0, d.p);      // 2^16 x 2^8 threads x 2^8 patterns
         if (hipGetLastError() != hipSuccess || hipMemcpy(out3, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) rc = LPCN_E_HIP;
     }
-    (void)hipFree(d);
     if (rc) snprintf(g_err, sizeof(g_err), "quantisation sweep kernel failed");
     return rc;
 }

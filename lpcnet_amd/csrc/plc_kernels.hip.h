@@ -1,7 +1,7 @@
 // Packet-loss concealment on the device: the data side of lpcnet_plc_update / lpcnet_plc_conceal in causal mode
 // (src/lpcnet_plc.c:188-340) for every stream of a batch, bit for bit like the reference's generic-C float build.  The control side
 // -- which branch a stream takes in this step -- is a function of the loss flags and the FEC calls alone and lives on the host
-// (engine.hip: plc_plan); each kernel here works on the streams the host listed for it:
+// (plc_plan.cpp: plc_plan); each kernel here works on the streams the host listed for it:
 //   plc_burg_kernel   DC removal (src/lpcnet_plc.c:196-205) and burg_cepstral_analysis (src/freq.c:156-199) of a received frame
 //   plc_pred_kernel   compute_plc_pred (src/lpcnet_plc.c:135-146) with its input selection (get_fec_or_pred :148-168), the rotation and
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
@@ -12,6 +12,7 @@
 #include "lpcnet_log10.h"
 #include "lpcnet_plc_tables_gen.h"
 #include "plc_burg.h"
+#include "plc_records.h"      // record sizes, flags and operation codes of the control lists (shared with the host planner)
 
 namespace lpcn {
 
@@ -44,13 +45,6 @@ struct PlcData {
 constexpr int PLC_BURG_THREADS = 128;
 constexpr int PLC_PRED_THREADS = 256;
 constexpr int PLC_MIX_THREADS = 512;
-constexpr int PLC_PRED_REC = 6;      // ints per record of plc_pred_kernel: stream, flags, FEC row, two float offsets, unused
-constexpr int PLC_MIX_REC = 3;       // ints per record of plc_mix_kernel: stream, a, b
-
-enum { PLC_F_ROT = 1, PLC_F_RESTORE_SHIFT = 1, PLC_F_INPUT_SHIFT = 3, PLC_F_COMPUTE = 32, PLC_F_KEEP = 64, PLC_F_ATT = 128, PLC_F_RAW = 256 };
-enum { PLC_IN_ZEROS = 0, PLC_IN_FEC = 1, PLC_IN_BURG = 2, PLC_IN_BURG_FEAT = 3 };
-enum { PLC_MIX_QTAIL, PLC_MIX_QAPPEND, PLC_MIX_QPUSH, PLC_MIX_QSHIFT, PLC_MIX_FAPPEND, PLC_MIX_RESETSIG, PLC_MIX_DCRECV, PLC_MIX_DCLOST, PLC_MIX_XFADE };
-
 #define LPCN_PLC_DC_CONST 0.003      // src/lpcnet_plc.c:183
 
 // One workgroup per listed stream, wave h on half frame h.  pcm [n][160] is the call's frame: with the DC filter it is rewritten in place.

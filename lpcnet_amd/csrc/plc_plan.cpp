@@ -1,0 +1,209 @@
+// The host half of the packet-loss concealment (plc_plan.h): no device, no HIP.
+#include <stdio.h>
+#include <string.h>
+#include "plc_plan.h"
+using namespace lpcn;
+#define LPCNET_PLC_CAUSAL_OPT 0      /* LPCNET_PLC_CAUSAL of include/lpcnet.h (2 = LPCNET_PLC_CODEC, | 4 = LPCNET_PLC_DC_FILTER) */
+
+extern "C" void lpcn_plc_ctl_reset(lpcn_plc_ctl *c)
+{
+    memset(c, 0, sizeof(*c));
+    c->pcm_fill = LPCN_PLC_BUF_SIZE;      // src/lpcnet_plc.c:52-58
+}
+
+// get_fec_or_pred's decision and bookkeeping (src/lpcnet_plc.c:148-168)
+static bool plc_take_fec(lpcn_plc_ctl &c, int *row)
+{
+    if (c.fec_read != c.fec_fill && c.fec_skip == 0) {
+        *row = c.fec_read++;
+        const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
+        c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
+        if (c.fec_keep < 0) c.fec_keep = 0;
+        return true;
+    }
+    if (c.fec_skip > 0) c.fec_skip--;
+    *row = 0;
+    return false;
+}
+
+extern "C" int lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null)      // src/lpcnet_plc.c:109-127
+{
+    if (is_null) { c->fec_skip++; return 0; }
+    int moved = 0;
+    if (c->fec_fill == LPCN_PLC_MAX_FEC) {
+        if (c->fec_keep == 0) return 1;
+        c->fec_fill -= c->fec_keep;
+        c->fec_read -= c->fec_keep;
+        c->fec_keep = 0;
+        moved = 2;
+    }
+    c->fec_fill++;
+    return moved;
+}
+
+static void plc_emit(PlcPlan &P, int type, int op, const std::vector<int> &recs, int rec_size)
+{
+    if (recs.empty()) return;
+    PlcLaunch L;
+    L.type = type; L.op = op; L.off = (int)P.ctl.size(); L.cnt = (int)recs.size() / rec_size;
+    P.ctl.insert(P.ctl.end(), recs.begin(), recs.end());
+    P.launches.push_back(L);
+}
+static void plc_emit_group(PlcPlan &P, const std::vector<int> &map, int kind, int N, int preload, int feat_src, int pcm_src, int pcm_dst, int pcm_off, bool scatter, bool keep)
+{
+    if (map.empty()) return;
+    PlcLaunch L;
+    L.type = PLC_T_GROUP; L.off = (int)P.ctl.size(); L.cnt = (int)map.size();
+    L.kind = kind; L.N = N; L.preload = preload; L.feat_src = feat_src; L.pcm_src = pcm_src; L.pcm_dst = pcm_dst; L.pcm_off = pcm_off; L.scatter = scatter; L.keep = keep;
+    P.ctl.insert(P.ctl.end(), map.begin(), map.end());
+    P.launches.push_back(L);
+}
+
+int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len)
+{
+    const bool blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT, remove_dc = (options & 4) != 0;
+    static const float att_table[10] = {0, 0, -.2, -.2, -.4, -.4, -.8, -.8, -1.6, -1.6};      // src/lpcnet_plc.c:295
+    P.ctl.clear(); P.launches.clear();
+    for (int s = 0; s < n; ++s) {
+        const lpcn_plc_ctl &c = ctl[s];
+        const bool fill_ok = c.pcm_fill == 0 || c.pcm_fill == 80 || c.pcm_fill == 240 || c.pcm_fill == LPCN_PLC_BUF_SIZE;
+        if (!fill_ok || (!lost[s] && c.skip_analysis && !c.blend && c.pcm_fill + LPCN_FRAME_SIZE > LPCN_PLC_BUF_SIZE) || c.fbuf_fill < 0 || c.fbuf_fill > LPCN_PLC_FBUF ||
+            c.fec_keep < 0 || c.fec_keep > c.fec_read || c.fec_read > c.fec_fill || c.fec_fill > LPCN_PLC_MAX_FEC || c.fec_skip < 0 || c.skip_analysis < 0 || c.loss_count < 0) {
+            snprintf(err, err_len, "stream %d: inconsistent PLC control state", s); return LPCN_E_ARG;
+        }
+    }
+    std::vector<int> flush[LPCN_PLC_FBUF], rpred[3], r160[3], r80[3], rshift[3], fpred, lostmap, dclost;
+    std::vector<int> burg, bpred, fa1, fa2, resetsig, xgrp, xfade, qtail, qappend, post_pred, fa3, qpush, dcrecv;
+    int zero[LPCN_PLC_SUMMARY];
+    for (int s = 0; s < n; ++s) {
+        lpcn_plc_ctl &c = ctl[s];
+        int *sm = summary ? summary + (size_t)s * LPCN_PLC_SUMMARY : zero;
+        memset(sm, 0, sizeof(int) * LPCN_PLC_SUMMARY);
+        if (lost[s]) {                                       // lpcnet_plc_conceal_causal, src/lpcnet_plc.c:296-340
+            sm[0] = 1; sm[1] = c.fbuf_fill;
+            for (int k = 0; k < c.fbuf_fill; ++k) flush[k].push_back(s);
+            c.fbuf_fill = 0;
+            for (int r = 0; c.pcm_fill > 0 && r < 3; ++r) {
+                const int N = c.pcm_fill < LPCN_FRAME_SIZE ? c.pcm_fill : LPCN_FRAME_SIZE;
+                int row = 0;
+                const bool fec = plc_take_fec(c, &row);
+                const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP);
+                const int rec[PLC_PRED_REC] = {s, fl, row, 0, 0, 0};
+                rpred[r].insert(rpred[r].end(), rec, rec + PLC_PRED_REC);
+                (N == LPCN_FRAME_SIZE ? r160 : r80)[r].push_back(s);
+                const int mr[PLC_MIX_REC] = {s, 0, 0};
+                rshift[r].insert(rshift[r].end(), mr, mr + PLC_MIX_REC);
+                c.pcm_fill -= N;
+                c.skip_analysis++;
+                sm[2]++; sm[3] += N; sm[4] += fec ? 1 : 0;
+            }
+            int row = 0;
+            const bool fec = plc_take_fec(c, &row);
+            if (fec) c.loss_count = 0; else c.loss_count++;
+            const float a1 = c.loss_count >= 10 ? att_table[9] : att_table[c.loss_count];
+            const float a2 = c.loss_count >= 10 ? (float)(2 * (c.loss_count - 9)) : 0.f;
+            const int fl = PLC_F_ROT | ((fec ? PLC_IN_FEC : PLC_IN_ZEROS) << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | (fec ? 0 : PLC_F_KEEP) | PLC_F_ATT;
+            const int rec[PLC_PRED_REC] = {s, fl, row, float_bits(a1), float_bits(a2), 0};
+            fpred.insert(fpred.end(), rec, rec + PLC_PRED_REC);
+            lostmap.push_back(s);
+            c.blend = 1;
+            sm[4] += fec ? 1 : 0; sm[9] = c.loss_count;
+            const int mr[PLC_MIX_REC] = {s, 0, 0};
+            if (remove_dc) dclost.insert(dclost.end(), mr, mr + PLC_MIX_REC);
+            continue;
+        }
+        // lpcnet_plc_update_causal, src/lpcnet_plc.c:188-290
+        burg.push_back(s);
+        const int mr[PLC_MIX_REC] = {s, 0, 0};
+        if (c.skip_analysis) {
+            if (c.blend) {
+                if (blending) {
+                    const int rec[PLC_PRED_REC] = {s, (2 << PLC_F_RESTORE_SHIFT) | (PLC_IN_BURG << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
+                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
+                    for (int k = 0; k < LPCN_FEATURES_DELAY; ++k) {
+                        const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 0};
+                        std::vector<int> &fa = k ? fa2 : fa1;
+                        fa.insert(fa.end(), fr, fr + PLC_MIX_REC);
+                        if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
+                    }
+                    const int xr[PLC_MIX_REC] = {s, (int)xgrp.size(), 0};
+                    xfade.insert(xfade.end(), xr, xr + PLC_MIX_REC);
+                    xgrp.push_back(s);
+                    sm[5] = 1; sm[8] += LPCN_FEATURES_DELAY;
+                } else {
+                    const int rec[PLC_PRED_REC] = {s, 1 << PLC_F_RESTORE_SHIFT, 0, 0, 0, 0};
+                    bpred.insert(bpred.end(), rec, rec + PLC_PRED_REC);
+                    c.fec_read -= LPCN_FEATURES_DELAY;                      // fec_rewind, :170-175
+                    if (c.fec_read < c.fec_keep) c.fec_read = c.fec_keep;
+                    resetsig.insert(resetsig.end(), mr, mr + PLC_MIX_REC);
+                    sm[5] = 2;
+                }
+                qtail.insert(qtail.end(), mr, mr + PLC_MIX_REC);
+                c.pcm_fill = 80;
+                sm[6] = 1;
+            } else {
+                const int qr[PLC_MIX_REC] = {s, c.pcm_fill, 0};
+                qappend.insert(qappend.end(), qr, qr + PLC_MIX_REC);
+                c.pcm_fill += LPCN_FRAME_SIZE;
+                sm[6] = 2;
+            }
+        }
+        if (!c.blend) {
+            const int rec[PLC_PRED_REC] = {s, (PLC_IN_BURG_FEAT << PLC_F_INPUT_SHIFT) | PLC_F_COMPUTE | PLC_F_KEEP, 0, 0, 0, 0};
+            post_pred.insert(post_pred.end(), rec, rec + PLC_PRED_REC);
+            if (c.fec_skip) c.fec_skip--;
+            else if (c.fec_read < c.fec_fill) c.fec_read++;
+            const int k = c.fec_read - LPCN_FEATURES_DELAY - 1;
+            c.fec_keep = c.fec_keep > k ? c.fec_keep : k;
+            if (c.fec_keep < 0) c.fec_keep = 0;
+            sm[7] = 1;
+        }
+        bool append = false;
+        if (c.skip_analysis) {
+            append = blending;
+            c.skip_analysis--;
+        } else {
+            qpush.insert(qpush.end(), mr, mr + PLC_MIX_REC);
+            append = true;
+            sm[6] = 3;
+        }
+        if (append) {
+            const int fr[PLC_MIX_REC] = {s, c.fbuf_fill, 1};
+            fa3.insert(fa3.end(), fr, fr + PLC_MIX_REC);
+            if (c.fbuf_fill < LPCN_PLC_FBUF) c.fbuf_fill++;
+            sm[8]++;
+        }
+        c.loss_count = 0;
+        if (remove_dc) dcrecv.insert(dcrecv.end(), mr, mr + PLC_MIX_REC);
+        c.blend = 0;
+    }
+    // lost streams: flush, the queued samples round by round, the concealed frame
+    for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
+    for (int r = 0; r < 3; ++r) {
+        plc_emit(P, PLC_T_PRED, 0, rpred[r], PLC_PRED_REC);
+        plc_emit_group(P, r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
+        plc_emit_group(P, r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
+        plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, rshift[r], PLC_MIX_REC);
+    }
+    plc_emit_group(P, lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
+    plc_emit(P, PLC_T_PRED, 0, fpred, PLC_PRED_REC);
+    plc_emit_group(P, lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
+    // received streams up to the analysis
+    if (!burg.empty()) { plc_emit(P, PLC_T_BURG, 0, burg, 1); }
+    plc_emit(P, PLC_T_PRED, 0, bpred, PLC_PRED_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa1, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa2, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_RESETSIG, resetsig, PLC_MIX_REC);
+    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 0, 0, false, false);      // into the group's PCM; the states are not written back (the reference's copy / restore)
+    plc_emit(P, PLC_T_MIX, PLC_MIX_XFADE, xfade, PLC_MIX_REC);
+    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QTAIL, qtail, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QAPPEND, qappend, PLC_MIX_REC);
+    { PlcLaunch L; L.type = PLC_T_ANALYSIS; P.launches.push_back(L); }
+    plc_emit(P, PLC_T_PRED, 0, post_pred, PLC_PRED_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa3, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_QPUSH, qpush, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_DCRECV, dcrecv, PLC_MIX_REC);
+    plc_emit(P, PLC_T_MIX, PLC_MIX_DCLOST, dclost, PLC_MIX_REC);
+    return 0;
+}

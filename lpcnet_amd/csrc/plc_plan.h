@@ -1,0 +1,31 @@
+// Packet-loss concealment, host half: lpcnet_plc_update / lpcnet_plc_conceal in causal mode for every stream (src/lpcnet_plc.c:188-340;
+// DESIGN.md §4.4).  No branch of the reference looks at audio: the options, skip_analysis, blend, pcm_fill, loss_count, the FEC ring positions
+// and fec_skip decide, and they follow from the loss flags and the FEC calls.  So the host keeps that control state (lpcn_plc_ctl), derives
+// every stream's branch for a step without reading anything back, and lists the streams of every phase; the data stays on the device.  Plain
+// C++: nothing here needs a device (lpcn_plc_ctl_reset and lpcn_plc_ctl_fec_add of lpcnet_engine.h are defined beside the planner).
+#pragma once
+#include <stddef.h>
+#include <string.h>
+#include <vector>
+#include "lpcnet_engine.h"
+#include "plc_records.h"
+
+enum { PLC_T_BURG, PLC_T_PRED, PLC_T_MIX, PLC_T_GROUP, PLC_T_ANALYSIS };
+enum { PLC_G_FRAMES, PLC_G_FRAME_SAMPLES, PLC_G_TAIL };
+struct PlcLaunch {
+    int type = 0, op = 0, off = 0, cnt = 0;
+    // groups: what runs on the compacted streams, where its features and PCM come from and go to
+    int kind = 0, N = LPCN_FRAME_SIZE, preload = 0;
+    int feat_src = 0;          // 0 st->features, 1 + k: entry k of the deferred queue
+    int pcm_src = 0;           // preload source: 0 none, 1 head of the PCM queue, 2 the call's frame at pcm_off
+    int pcm_dst = 0;           // 0 nowhere (the group's compacted PCM is left for a cross-fade), 1 the call's frame at pcm_off
+    int pcm_off = 0;
+    bool scatter = true, keep = false;
+};
+struct PlcPlan { std::vector<int> ctl; std::vector<PlcLaunch> launches; };
+
+inline int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
+
+// One step of every stream's control state, and the launches it takes.  summary (may be NULL): LPCN_PLC_SUMMARY ints per stream.
+// Returns 0, or LPCN_E_ARG with the message in err.
+int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len);
