@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the LPCNet synthesis hot path on MI355X (driver contract: one JSON line on rank 0).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: it sets up (model, engine, streams-per-workgroup measurement, features), warms up,
+times the K steps, writes the timed output if `--dump-outputs` says so and prints the line.  `--full` adds everything else described below -- the
+checker leg (`parity_checked`, the FAST envelope), the live kernel timing behind `roofline`, `also`, `rt` and `cpu_baseline` -- after the timed
+steps, so that `value` and `ms_per_step` are the same measurement with and without it; `--check-streams`, `--no-extras` and `--no-cpu-baseline` trim
+a full run.  (`--rt` is a line of its own and does not look at `--full`.)
 
 step     = one pass of the hot path (frame network + LPC + 160-sample loop per frame) over one
            batch of synthetic feature frames: STREAMS streams x FRAMES frames per GPU, features and
@@ -10,14 +16,14 @@ step     = one pass of the hot path (frame network + LPC + 160-sample loop per f
            streams per CU (256 CUs x 8), so BASELINE.json config 2's 1024 streams fill only half of its stream slots; the
            1024-stream figure of the same build rides along as `also.config2_1024_streams` (four streams per CU, the
            round-5 kernel).  Weak scaling: every GPU gets its own streams.
-also     = (N = 1) the same step with BASELINE config 4's int8 GRU weights (`also.int8_parity`, bit-exact against the reference's
+also     = (--full, N = 1) the same step with BASELINE config 4's int8 GRU weights (`also.int8_parity`, bit-exact against the reference's
            generic int8 build) and config 2's 1024 streams, each oracle-checked like the headline.
-rt       = (N = 1) the half of the metric that is a DEADLINE: frame-at-a-time synthesis at the stream counts that bracket the 10-ms
+rt       = (--full, N = 1) the half of the metric that is a DEADLINE: frame-at-a-time synthesis at the stream counts that bracket the 10-ms
            frame period (`rt.probe`), host wall time AND device time of every step; `realtime_streams_sustained` is the largest
            measured count whose p99.9 step stays under 10 ms.
 value    = whole-job 16 kHz samples per second (sum over GPUs / max-over-ranks time);
            concurrent real-time streams = value / 16000.
-           Every stream of every rank has its own seeded feature file (1000 + rank*streams + s); after the timed loop
+           Every stream of every rank has its own seeded feature file (1000 + rank*streams + s); with --full, after the timed loop,
            `--check-streams` streams of the timed output are replayed on the plain-C oracle (checker leg) and
            compared bit for bit: `parity_checked` in the JSON line.
            `--dump-outputs DIR` writes that same output -- the PCM a caller of the timed path receives from its last timed
@@ -25,7 +31,7 @@ value    = whole-job 16 kHz samples per second (sum over GPUs / max-over-ranks t
            features are seeded, so equal arguments give equal inputs and two builds can be compared output for output.
            `--gpus N` without a launcher re-executes itself under `python -m torch.distributed.run` with N ranks;
            `--gpus 2 --share-device` rehearses that path on ONE GPU (both ranks on device 0, gloo control plane).
-roofline = the sample kernel (dominant, >98 % of the step).  SURVEY.md §8(d): not MFMA; the primary bound
+roofline = (--full) the sample kernel (dominant, >98 % of the step).  SURVEY.md §8(d): not MFMA; the primary bound
            is on-chip operand bandwidth, so `achieved` = algorithmic operand bytes per stream-sample
            (286 704 B fp32 / 96 432 B int8: every weight and table entry once per sample) x samples per
            launch / launch time, against the 150 TB/s LDS peak; the fp32-VALU flop fraction (129 698 flop
@@ -34,7 +40,7 @@ roofline = the sample kernel (dominant, >98 % of the step).  SURVEY.md §8(d): n
            (profiles/, FETCH_SIZE x2 + WRITE_SIZE; it cannot be collected from inside the process) and
            `hbm` = that traffic over the live launch time against the 8 TB/s peak.  Launch time is
            measured live with HIP events on the stream the kernel runs on.
-cpu_baseline = the reference's own AVX2 builds (oracle/_ref, `kind: reference`): A-f = float (-DDISABLE_DOT_PROD, the
+cpu_baseline = (--full) the reference's own AVX2 builds (oracle/_ref, `kind: reference`): A-f = float (-DDISABLE_DOT_PROD, the
            arithmetic the fp32 line is compared with) and A-i = int8, the reference's default x86 build; `value`
            is A-f for the fp32 line and A-i for the --int8 line, both are listed under `flavours`.  If the
            prebuilt libraries are absent: the plain-C oracle (`kind: port`).  Timed here on the host cores over a
@@ -408,9 +414,13 @@ def main():
     ap.add_argument("--streams", type=int, default=STREAMS_PER_GPU, help="streams per GPU")
     ap.add_argument("--frames", type=int, default=FRAMES_PER_STEP, help="frames per step")
     ap.add_argument("--spw", type=int, default=0, help="streams per workgroup (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="the default command without its `also` (1024 streams, int8 weights) and `rt` (real-time probe) records")
-    ap.add_argument("--check-streams", type=int, default=8, help="streams of the timed output replayed on the CPU oracle (0 = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check and measure everything else the line can carry: the timed output against the CPU oracle "
+                         "(`parity_checked`; --fast: the envelope check), the live kernel timing behind `roofline`, the `also` (1024 streams, int8 weights) "
+                         "and `rt` (real-time probe) records of the default workload and the CPU baseline.  Without it: set up, warm up, time, print")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the `also` (1024 streams, int8 weights) and `rt` (real-time probe) records")
+    ap.add_argument("--check-streams", type=int, default=8, help="--full / --rt: streams of the timed output replayed on the CPU oracle (0 = none)")
     ap.add_argument("--fast", action="store_true",
                     help="FAST arithmetic (fused multiply-add / int32 accumulation like the reference's AVX2 builds): a separate, "
                          "non-bit-exact flavour; the headline is the default PARITY arithmetic")
@@ -467,8 +477,8 @@ def main():
         return rt_main(a, world, rank, local, dev)
 
     def run_workload(n, F, int8, steps, warmup, fast=False, fp16_fc=False, spw=0, densities="", check_streams=8, seed0=1000, skew=0.0, dump_dir=""):
-        """`warmup` untimed + `steps` timed passes of the hot path over n streams x F frames (features / PCM resident in HBM), then the live kernel
-        timing and the checker leg; returns the figures of one workload."""
+        """`warmup` untimed + `steps` timed passes of the hot path over n streams x F frames (features / PCM resident in HBM), then (--full) the live
+        kernel timing and the checker leg; returns the figures of one workload."""
         mk = dict(flavour="int8" if int8 else "float")
         if densities:
             mk["densities"] = tuple(float(x) for x in densities.split(","))
@@ -479,6 +489,8 @@ def main():
         if fast:
             batch.set_fast(2 if fp16_fc else 1)
             check_streams = 0                                # FAST is validated teacher-forced (tests/test_gpu_fast.py), not bit for bit
+        if not a.full:
+            check_streams = 0                                # a plain run checks nothing
         if spw:
             batch.streams_per_workgroup = spw
         else:
@@ -512,16 +524,18 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if a.share_device else dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        # live kernel timing for the roofline: HIP events around the sample kernel on its own stream
-        batch.enable_timing(True)
-        ks = []
-        for _ in range(3):
-            step()
-            torch.cuda.synchronize()
-            ks.append(batch.last_timing())
-        batch.enable_timing(False)
-        ms_sample = float(np.median([k[0] for k in ks]))
-        ms_frame = float(np.median([k[1] for k in ks]))
+        ms_sample = ms_frame = None
+        if a.full:
+            # live kernel timing for the roofline: HIP events around the sample kernel on its own stream
+            batch.enable_timing(True)
+            ks = []
+            for _ in range(3):
+                step()
+                torch.cuda.synchronize()
+                ks.append(batch.last_timing())
+            batch.enable_timing(False)
+            ms_sample = float(np.median([k[0] for k in ks]))
+            ms_frame = float(np.median([k[1] for k in ks]))
         nonzero = int(torch.count_nonzero(d_pcm).item())
         assert nonzero > 0.5 * d_pcm.numel(), "benchmark output is degenerate"
         if dump_dir:
@@ -542,7 +556,7 @@ def main():
         spw_used = batch.streams_per_workgroup
         batch.close()
         envelope = None
-        if fast and rank == 0 and a.check_streams > 0:       # FAST: its own check on a few streams of this very batch (their feature files), teacher-forced
+        if fast and a.full and rank == 0 and a.check_streams > 0:       # FAST: its own check on a few streams of this very batch (their feature files), teacher-forced
             kk = min(4, n)
             pick = sorted({(i * n) // kk for i in range(kk)})
             ek, eda, edb = fast_envelope_check(blob, np.ascontiguousarray(feats[pick]), int8, fp16_fc, spw_used, local)
@@ -561,10 +575,10 @@ def main():
     def lds_frac(rec, int8):
         return rec["samples_per_step"] / (rec["ms_sample"] * 1e-3) * (LDS_OPERAND_BYTES_PER_SAMPLE_I8 if int8 else LDS_OPERAND_BYTES_PER_SAMPLE) / 1e9 / (PEAK_LDS_TBS * 1e3)
 
-    # ---- (N = 1, the default command only) what else the metric and BASELINE's configs name: config 2's 1024 streams, config 4's int8 weights, the deadline
+    # ---- (--full, N = 1, the default workload only) what else the metric and BASELINE's configs name: config 2's 1024 streams, config 4's int8 weights, the deadline
     also, rt = None, None
-    default_cmd = world == 1 and not (a.fast or a.int8 or a.densities or a.spw or a.skew) and (n, F) == (STREAMS_PER_GPU, FRAMES_PER_STEP) and not a.no_extras
-    if default_cmd:
+    default_cmd = world == 1 and not (a.fast or a.int8 or a.densities or a.spw or a.skew) and (n, F) == (STREAMS_PER_GPU, FRAMES_PER_STEP)
+    if a.full and default_cmd and not a.no_extras:
         also = {}
         r1 = run_workload(CONFIG2_STREAMS, F, False, max(a.steps // 2, 2), 1, check_streams=a.check_streams, seed0=3000)
         also["config2_1024_streams"] = {"value": r1["value"], "unit": "samples/s", "ms_per_step": r1["ms_per_step"], "launch_ms": r1["ms_sample"], "frac": lds_frac(r1, False),
@@ -586,10 +600,10 @@ def main():
               "over_deadline_steps": best["over_deadline_steps"] if best else None, "device_ms_max": best["device_ms_max"] if best else None,
               "parity_checked": best["parity_checked"] if best else 0, "probe": probe}
 
-    if world > 1:
-        dist.barrier()                                       # the last collective: rank 0's CPU baseline below (~90 s) must not leave the other ranks inside one (VERDICT r3)
-    if rank == 0:
-        x2 = head["streams_per_workgroup"] == 8
+    x2 = head["streams_per_workgroup"] == 8
+
+    def roofline_record():
+        """--full: the `roofline` record of the headline workload, from the live launch time of its sample kernel"""
         launch_flop = samples_per_step * FLOP_PER_SAMPLE
         achieved_tflops = launch_flop / (ms_sample * 1e-3) / 1e12
         kernel_rate = samples_per_step / (ms_sample * 1e-3)
@@ -614,6 +628,30 @@ def main():
                     break
                 except Exception:
                     traffic = None
+        return {"bound": "lds_operand_bandwidth", "kernel": "lpcn::sample_kernel_x2" if x2 else "lpcn::sample_kernel",
+                "achieved": op_gbs, "peak": PEAK_LDS_TBS * 1e3, "unit": "GB/s",
+                "frac": op_gbs / (PEAK_LDS_TBS * 1e3), "traffic": traffic, "traffic_source": traffic_src,
+                "launch_ms": ms_sample, "frame_kernels_ms": ms_frame,
+                "operand_bytes_per_sample": op_bytes,
+                "note": "algorithmic operand bytes (each weight/table entry once per stream-sample); the engine keeps "
+                        "GRU-A weights in VGPRs and shares every LDS read among the workgroup's streams, so realised LDS bytes are lower; "
+                        "`traffic` comes from the rocprofv3 PMC passes recorded under profiles/ (it cannot be collected from inside the "
+                        "process) and is null unless that file was measured with these very kernel sources",
+                "kernel_source_hash": khash, "library_build_info": api.build_info(),
+                "library_matches_sources": api.build_info().get("dev") == khash,
+                "valu_fp32": {"achieved_TFLOPs": achieved_tflops, "peak_TFLOPs": PEAK_FP32_TFLOPS,
+                              "frac": achieved_tflops / PEAK_FP32_TFLOPS, "flop_per_sample": FLOP_PER_SAMPLE,
+                              "measured_packed_mul_add_no_fma_TFLOPs": MEASURED_FP32_MUL_ADD_TFLOPS,
+                              "frac_of_measured_no_fma": achieved_tflops / MEASURED_FP32_MUL_ADD_TFLOPS},
+                "l2_gather": {"achieved_GBs": kernel_rate * L2_BYTES_PER_SAMPLE / 1e9, "bytes_per_sample": L2_BYTES_PER_SAMPLE,
+                              "note": "embedding rows + frame products, L2 -> CU; the tables stay L2-resident, this is not HBM traffic"},
+                "hbm": None if traffic is None else {"achieved_GBs": traffic / (ms_sample * 1e-3) / 1e9, "peak_GBs": PEAK_HBM_GBS,
+                                                     "frac": traffic / (ms_sample * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                                                     "note": "measured PMC traffic per launch / live launch time: HBM is not a bound of this kernel"}}
+
+    if world > 1:
+        dist.barrier()                                       # the last collective: rank 0's CPU baseline below (~90 s) must not leave the other ranks inside one (VERDICT r3)
+    if rank == 0:
         out = {
             "metric": "16 kHz samples/sec & concurrent real-time streams, 1/2/4/8 MI355X",
             "value": value, "unit": "samples/s",
@@ -636,34 +674,16 @@ def main():
                        "gru_a_skew": a.skew, "gru_a_items_per_lane": int(api.check_model(head["blob"])[1][3]),
                        "streams_per_gpu": n, "frames_per_step": F, "streams_per_workgroup": head["streams_per_workgroup"],
                        "sharding": f"{world} x {n} independent streams, no data-path collective"},
-            "roofline": {"bound": "lds_operand_bandwidth", "kernel": "lpcn::sample_kernel_x2" if x2 else "lpcn::sample_kernel",
-                         "achieved": op_gbs, "peak": PEAK_LDS_TBS * 1e3, "unit": "GB/s",
-                         "frac": op_gbs / (PEAK_LDS_TBS * 1e3), "traffic": traffic, "traffic_source": traffic_src,
-                         "launch_ms": ms_sample, "frame_kernels_ms": ms_frame,
-                         "operand_bytes_per_sample": op_bytes,
-                         "note": "algorithmic operand bytes (each weight/table entry once per stream-sample); the engine keeps "
-                                 "GRU-A weights in VGPRs and shares every LDS read among the workgroup's streams, so realised LDS bytes are lower; "
-                                 "`traffic` comes from the rocprofv3 PMC passes recorded under profiles/ (it cannot be collected from inside the "
-                                 "process) and is null unless that file was measured with these very kernel sources",
-                         "kernel_source_hash": khash, "library_build_info": api.build_info(),
-                         "library_matches_sources": api.build_info().get("dev") == khash,
-                         "valu_fp32": {"achieved_TFLOPs": achieved_tflops, "peak_TFLOPs": PEAK_FP32_TFLOPS,
-                                       "frac": achieved_tflops / PEAK_FP32_TFLOPS, "flop_per_sample": FLOP_PER_SAMPLE,
-                                       "measured_packed_mul_add_no_fma_TFLOPs": MEASURED_FP32_MUL_ADD_TFLOPS,
-                                       "frac_of_measured_no_fma": achieved_tflops / MEASURED_FP32_MUL_ADD_TFLOPS},
-                         "l2_gather": {"achieved_GBs": kernel_rate * L2_BYTES_PER_SAMPLE / 1e9, "bytes_per_sample": L2_BYTES_PER_SAMPLE,
-                                       "note": "embedding rows + frame products, L2 -> CU; the tables stay L2-resident, this is not HBM traffic"},
-                         "hbm": None if traffic is None else {"achieved_GBs": traffic / (ms_sample * 1e-3) / 1e9, "peak_GBs": PEAK_HBM_GBS,
-                                                              "frac": traffic / (ms_sample * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                                                              "note": "measured PMC traffic per launch / live launch time: HBM is not a bound of this kernel"}},
         }
+        if a.full:
+            out["roofline"] = roofline_record()
         if also is not None:
             out["also"] = also
         if rt is not None:
             out["rt"] = rt
         if a.share_device:
             out["rehearsal"] = "all ranks on device 0, gloo control plane: a plumbing check of the multi-rank path, not a scaling number"
-        if not a.no_cpu_baseline:                            # (N > 1: rank 0 only, behind the timed region; the other ranks wait at the final barrier)
+        if a.full and not a.no_cpu_baseline:                 # (N > 1: rank 0 only, behind the timed region; the other ranks wait at the final barrier)
             try:
                 out["cpu_baseline"] = cpu_baseline(a.int8)
             except Exception as e:  # the baseline must never take the GPU number down with it

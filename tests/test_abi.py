@@ -181,7 +181,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(tmp_path):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    common = ["--steps", "2", "--warmup", "1", "--streams", "256", "--frames", "10", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--streams", "256", "--frames", "10", "--no-cpu-baseline"]
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path / "one")] + common,
                         capture_output=True, text=True, env=env, timeout=900)
     assert r1.returncode == 0, r1.stderr[-2000:]
@@ -219,7 +219,7 @@ def test_bench_four_rank_shape_rehearsed_on_one_gpu(flag):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-device", "--steps", "2", "--warmup", "1",
-                        "--streams", "1024", "--no-cpu-baseline"] + flag, capture_output=True, text=True, env=env, timeout=1500)      # (configs 3 / 4: 1024 per rank; the bench's default is 2048 per GPU since round 6)
+                        "--streams", "1024", "--full", "--no-cpu-baseline"] + flag, capture_output=True, text=True, env=env, timeout=1500)      # (configs 3 / 4: 1024 per rank; the bench's default is 2048 per GPU since round 6)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -1,4 +1,4 @@
-"""The JSON lines bench.py prints (GPU box): the default command's extra records and the real-time mode (the code that produces the
+"""The JSON lines bench.py prints (GPU box): the plain run's line, the extra records of `--full` and the real-time mode (the code that produces the
 real-time claim ran in no test, and the driver's line carried neither the measured sustained-stream figure nor BASELINE config 4's weights)."""
 import json
 import os
@@ -34,10 +34,21 @@ def test_rt_mode_is_oracle_checked_and_carries_both_clocks():
     assert d["realtime_streams_sustained"] == 256
 
 
+def test_plain_line_carries_the_headline_and_nothing_that_takes_a_run_of_its_own():
+    """`python bench.py --gpus 1 --steps K --warmup W`: set up, warm up, time, print -- the headline fields of the full line, on the same kernel, and none of the
+    records that `--full` measures after the timed steps"""
+    d = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert d["metric"].startswith("16 kHz samples/sec") and d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["streams_per_gpu"] == 2048 and d["config"]["streams_per_workgroup"] == 8
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 / (2048 * 25 * 160) - 1.0) < 1e-9      # one step = 2048 streams x 25 frames x 160 samples
+    assert d["parity_checked"] == 0 and d["realtime_streams_sustained"] is None
+    assert not {"roofline", "also", "rt", "cpu_baseline", "envelope"} & set(d)
+
+
 def test_default_line_shape_with_its_also_and_rt_records(monkeypatch):
-    """the driver's command (`python bench.py`, here with fewer steps and without the CPU baseline): headline on the two-group kernel, `also` (BASELINE config 2's
+    """`python bench.py --full` (here with fewer steps and without the CPU baseline): headline on the two-group kernel, `also` (BASELINE config 2's
     1024 streams, config 4's int8 weights), `rt` (measured sustained stream count), each oracle-checked"""
-    d = run_bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = run_bench(["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     assert d["n_gpus"] == 1 and d["parity_checked"] == 8 and d["config"]["streams_per_gpu"] == 2048
     assert d["config"]["streams_per_workgroup"] == 8 and d["roofline"]["kernel"] == "lpcn::sample_kernel_x2"
     assert d["roofline"]["frac"] > 0.2 and d["roofline"]["library_matches_sources"]
@@ -54,7 +65,7 @@ def test_default_line_shape_with_its_also_and_rt_records(monkeypatch):
 def test_fast_line_carries_its_envelope_check():
     """a FAST (not bit-exact) line says what it WAS checked against: the teacher-forced deviation from the PARITY engine on streams of the
     batch, inside the reference's own AVX2-vs-generic-C envelope"""
-    d = run_bench(["--fast", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
+    d = run_bench(["--fast", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
     assert d["parity_checked"] == 0 and d["envelope_checked"] == 4 and d["config"]["arithmetic"] == "fast"
     assert 0 <= d["envelope"]["max_gru_a_deviation"] < 1e-4 and 0 <= d["envelope"]["max_gru_b_deviation"] < 1e-4
 

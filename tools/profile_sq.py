@@ -4,7 +4,7 @@
     python tools/profile_sq.py [--int8] [--tag r02] [--extra "<bench.py flags>"]
 
 rocprofv3 --pmc passes (at most 8 SQ counters each, --kernel-trace only: never mixed with other trace
-domains) around `python bench.py --steps 2 --warmup 1 --no-cpu-baseline`, one pass per counter group; the
+domains) around `python bench.py --steps 2 --warmup 1`, one pass per counter group; the
 counters actually present on the box are taken from `rocprofv3 -L`.  Output: gpurun_out/sq/<tag>_sq_<flavour>.csv
 (one row per counter: sum over the sample kernel's dispatches / number of dispatches) which
 tools/profile_summarize.py copies into profiles/.
@@ -63,7 +63,7 @@ def main():
         open(os.path.join(out_dir, "counters_available.txt"), "w").write(txt)
     rows = collections.OrderedDict()
     ndisp = 0
-    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"] + (["--int8"] if a.int8 else []) + a.extra.split()
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"] + (["--int8"] if a.int8 else []) + a.extra.split()
     for gi, group in enumerate(WISH):
         ctrs = [c for c in group if have is None or len(have) < 1000 or re.search(r"\b" + c + r"\b", have)]
         if not ctrs:
@@ -90,7 +90,7 @@ def main():
                 ndisp = cnt[c]
     path = os.path.join(out_dir, f"{a.tag}_sq_{fl}.csv")
     with open(path, "w") as o:
-        o.write(f"# rocprofv3 --pmc <<=8 SQ counters per pass> --kernel-trace -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras{' --int8' if a.int8 else ''} {a.extra}\n")
+        o.write(f"# rocprofv3 --pmc <<=8 SQ counters per pass> --kernel-trace -- python bench.py --steps 2 --warmup 1{' --int8' if a.int8 else ''} {a.extra}\n")
         o.write(f"# lpcn::sample_kernel*, per-dispatch average over {ndisp} dispatches (bench.py's workload: 2048 streams x 25 frames x 160 samples per dispatch unless --streams says otherwise); SQ_*_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles\n")
         o.write("counter,value_per_dispatch\n")
         for k, v in rows.items():

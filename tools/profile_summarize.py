@@ -45,7 +45,7 @@ for fl, suffix in (("f32", ""), ("i8", "_int8"), ("f32_fast", "_fast"), ("i8_fas
             rows.append((k, len(full), sum(full), sum(full) / len(full), min(full), max(full), len(v) - len(full)))
         tot = sum(r[2] for r in rows) or 1
         with open(os.path.join(DST, f"{RND}_kernel_stats{suffix}.csv"), "w") as o:
-            o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras" + (" --int8" if fl == "i8" else "")
+            o.write("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1" + (" --int8" if fl == "i8" else "")
                     + " (LPCNET_HIP_NO_AUTOTUNE=1); per kernel the workload's launches only (Dropped = shorter launches left out)\n")
             o.write('"Name","Calls","TotalDurationNs","AverageNs","Percentage","MinNs","MaxNs","Dropped"\n')
             for k, n, t, avg, mn, mx, dropped in sorted(rows, key=lambda r: -r[2]):
@@ -55,7 +55,7 @@ for fl, suffix in (("f32", ""), ("i8", "_int8"), ("f32_fast", "_fast"), ("i8_fas
     fe, wr = counter_avg(f"fetch_{fl}", "FETCH_SIZE"), counter_avg(f"write_{fl}", "WRITE_SIZE")
     if fe and wr:
         with open(os.path.join(DST, f"{RND}_pmc_hbm_summary{suffix}.csv"), "w") as o:
-            o.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+            o.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), python bench.py --steps 3 --warmup 1"
                     + {"f32": "", "i8": " --int8", "f32_fast": " --fast", "i8_fast": " --int8 --fast --spw 2"}[fl] + ", MI355X\n")
             o.write("# workload per launch: 2048 streams x 25 frames x 160 samples; values are per-dispatch averages in KB as reported\n")
             o.write("kernel,dispatches,FETCH_SIZE_KB_avg,WRITE_SIZE_KB_avg\n")
