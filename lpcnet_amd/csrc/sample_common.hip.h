@@ -163,14 +163,16 @@ __device__ __forceinline__ int tree_walk(const unsigned long long *mask_row)
 
 // Leader lanes, once the tree of sample `smp` of the frame has been evaluated: the excitation (walked, or forced from the caller's
 // PCM while smp < preload), the sample before de-emphasis, the history shift.  Out: pcm, deemph, exc for open_sample / finish_sample.
-__device__ __forceinline__ void draw_sample(const LeaderCells &c, const unsigned long long *mask_row, const float *ulaw_tab, const int lrow, const int tap,
-                                            const bool live, const int smp, const int preload, float &hist, float &pcm, float &deemph, int &exc)
+// `walked()` returns the tree's 8 decisions; the two forms below bind it.
+template <class Walked>
+__device__ __forceinline__ void draw_sample_with(const LeaderCells &c, const Walked walked, const float *ulaw_tab, const int lrow, const int tap,
+                                                 const bool live, const int smp, const int preload, float &hist, float &pcm, float &deemph, int &exc)
 {
     pcm = 0.f; deemph = 0.f; exc = 0;
     if (live) {                                  // (all 16 lanes of a stream's row do the same walk)
         const float pred = c.lead[lrow * 8 + 0];           // (issued together with the mask reads)
         deemph = c.lead[lrow * 8 + 1];
-        exc = tree_walk(mask_row);
+        exc = walked();
         if (smp < preload) {                                        // src/lpcnet.c:256-258
             const float x = (float)c.pcm[lrow * LPCN_FRAME_SIZE + smp];
             exc = lpcn_lin2ulaw(x - 0.85f * deemph - pred);
@@ -184,6 +186,18 @@ __device__ __forceinline__ void draw_sample(const LeaderCells &c, const unsigned
         hist = live ? shifted : hist;
     }
     if (tap == 0 && live) ((int *)c.lead)[lrow * 8 + 2] = exc;
+}
+// the tree as 255 ballot bits per stream (every node evaluated): the leader walks them
+__device__ __forceinline__ void draw_sample(const LeaderCells &c, const unsigned long long *mask_row, const float *ulaw_tab, const int lrow, const int tap,
+                                            const bool live, const int smp, const int preload, float &hist, float &pcm, float &deemph, int &exc)
+{
+    draw_sample_with(c, [&]() { return tree_walk(mask_row); }, ulaw_tab, lrow, tap, live, smp, preload, hist, pcm, deemph, exc);
+}
+// the tree already walked by the wave that evaluated it (tree_stages.h): one cell per stream holds the 8 decisions
+__device__ __forceinline__ void draw_sample_walked(const LeaderCells &c, const int *walked_cell, const float *ulaw_tab, const int lrow, const int tap,
+                                                   const bool live, const int smp, const int preload, float &hist, float &pcm, float &deemph, int &exc)
+{
+    draw_sample_with(c, [&]() { return *walked_cell & 0xFF; }, ulaw_tab, lrow, tap, live, smp, preload, hist, pcm, deemph, exc);
 }
 // ... and behind the next sample's indices (the other waves are waiting for those): de-emphasis and the PCM store
 // (src/lpcnet.c:264-269); start-up frames produce zeros

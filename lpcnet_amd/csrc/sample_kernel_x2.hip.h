@@ -9,8 +9,8 @@
 // The sample of a group is the four phases P1 (GRU-A rows) | P2 (gates) | P3 (GRU-B chains, candidate heads of the next sample) |
 // P4 (tree); the workgroup runs HALF-STEPS of two intervals and two barriers:
 //
-//      interval A:  P3 of the one group (its GRU-B chains on waves 0..3, its candidate heads on the head waves)
-//                   followed, on every wave, by P1 of the OTHER group, then P4 (the tree) of the first one   | barrier
+//      interval A:  P3 of the one group (its GRU-B chains on waves 0..3, its candidate heads on the head waves) and, on each chain
+//                   wave, P4 of its stream (the tree in two stages, tree_stages.h), followed, on every wave, by P1 of the OTHER group   | barrier
 //      interval B:  P2 of that other group                                                                   | barrier, the groups swap roles
 //
 // so a wave is never short of work that does not depend on the chain it has just fed: the leader / gather latency of one group's
@@ -23,10 +23,11 @@
 // Scope: float blobs, PARITY arithmetic, dense GRU-B input matrix, <= 32 items per lane.  Everything else runs on the four-stream kernel.
 #pragma once
 #include "sample_kernel.hip.h"
+#include "tree_stages.h"
 
 namespace lpcn {
 
-#define LPCN_X2_LW 4            // the wave that leads the streams (tree walk, LPC predictor, mu-law): a head wave (model_pack.c gives it the shortest candidate slot) -- waves 0..3 start GRU-B's chains at once
+#define LPCN_X2_LW 4            // the wave that leads the streams (LPC predictor, mu-law): a head wave (model_pack.c gives it the shortest candidate slot) -- waves 0..3 start GRU-B's chains at once
 #define LPCN_X2_TW 0            // the wave that draws the KISS99 thresholds: a chain wave -- they have the most slack at barrier 1 (wave 0 / 1 / 3 / 5 / 6: 149.5 / 148.9 / 145.0 / 147.4 / 143.5 M; leader on wave 5 / 7: 139.3 / 138.2 M against 146.7 M on wave 4, round 6)
 #define LPCN_X2_HG 10           // head items a row wave runs before it polls the leader's indices for the start-value pass (6 / 10 / 14 / 18: 145.0 / 146.7 / 146.2 / 144.3 M)
 
@@ -40,7 +41,7 @@ struct LdsX2 {
     static constexpr int g_hB    = g_prec + NA * S * 4;             // [4][16]
     static constexpr int g_idx   = g_hB + S * NB * 4;               // [4] packed indices, [4] live flags
     static constexpr int g_thr   = g_idx + S * 16;                  // [4][8]
-    static constexpr int g_mask  = g_thr + S * 32;                  // [4][8] u64
+    static constexpr int g_mask  = g_thr + S * 32;                  // [4] i32: the streams' walked tree values (the region keeps the size of the [4][8] u64 ballots the twelve-wave kernel stores here)
     static constexpr int g_lead  = g_mask + S * 64;                 // [4][8]
     static constexpr int g_flag  = g_lead + S * 32;                 // [4] i32
     static constexpr int g_condb = g_flag + 16;                     // [4][48]
@@ -61,6 +62,46 @@ struct LdsX2 {
     static constexpr int total(int nb_b) { return bw + (nb_b + 8) * 128; }
     __host__ __device__ static constexpr int ha_off(int p) { return p * HA_STRIDE + (p >> 2) * 16; }
 };
+
+// ---- the dual-FC tree of ONE stream on ONE wave, in two stages (tree_stages.h; src/nnet.c:163-214) ----
+// A lane is one (node, channel) of the stage: its row of the dual FC comes from L2 (64 B of weights, bias, factor -- no table in LDS),
+// the 16 state values from the wave's own stream.  The reference's order per node and channel: sum = bias, sum += w[j] * h[j] for j = 0..15 with
+// separately rounded products and sums (src/nnet.c:194-199), tanh, * factor, channel 0 + channel 1, threshold[level] < sum.
+typedef float tree_f4 __attribute__((ext_vector_type(4)));
+struct TreeRow { tree_f4 w[NB / 4]; float bias, factor; };
+template <int STAGE>
+__device__ __forceinline__ TreeRow tree_row_load(const LPCN_GLOBAL float *fc_w, const LPCN_GLOBAL float *fc_b, const LPCN_GLOBAL float *fc_f, const int lane, const int prefix)
+{
+    const int node = lpcn_tree_node(STAGE, lpcn_tree_lane_local(STAGE, lane), prefix), chan = lane & 1;      // 1..255
+    const auto *wp = (const LPCN_GLOBAL tree_f4 *)(fc_w + (node * 2 + chan) * NB);      // (64-byte rows of an allocation of their own)
+    TreeRow r;
+#pragma unroll
+    for (int j = 0; j < NB / 4; ++j) r.w[j] = wp[j];
+    r.bias = fc_b[chan * 256 + node];
+    r.factor = fc_f[chan * 256 + node];
+    return r;
+}
+// the stage's decisions (wave-uniform): the ballot over its nodes, walked from the stage's first node
+template <int STAGE>
+__device__ __forceinline__ int tree_stage_walk(const TreeRow &r, const float *h_s, const float *thr_s, const float *tansig, const int lane)
+{
+    const float4 *hp = (const float4 *)h_s;
+    float sum = r.bias;
+#pragma unroll
+    for (int j = 0; j < NB / 4; ++j) {
+        const float4 hv = hp[j];
+        const tree_f4 wv = r.w[j];
+        sum = sum + wv[0] * hv.x;
+        sum = sum + wv[1] * hv.y;
+        sum = sum + wv[2] * hv.z;
+        sum = sum + wv[3] * hv.w;
+    }
+    const float v = r.factor * lpcn_tanh(sum, tansig);
+    const float vo = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));      // the other channel (quad_perm [1,0,3,2])
+    const float lg = v + vo;
+    const unsigned long long m = __ballot(thr_s[lpcn_tree_level(STAGE, lpcn_tree_lane_local(STAGE, lane))] < lg) & lpcn_tree_stage_mask(STAGE);
+    return lpcn_tree_stage_walk(m, STAGE == 0 ? LPCN_TREE_TOP : LPCN_TREE_LEVELS - LPCN_TREE_TOP);
+}
 
 template <int NW>
 __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const LpcnSampleArgs *__restrict__ Ap)
@@ -153,7 +194,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             unsigned char *gb = smem + g * L::G_SZ;
             stage_leader_record({(float *)(gb + L::g_lead), (int *)(gb + L::g_idx), nullptr, nullptr}, s, &states[stream_of(tid)]);
         }
-        if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; fl[2] = 0; }
+        if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; }
     }
     __syncthreads();
 
@@ -169,7 +210,6 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     bool liveP = false, liveQ = false;                       // per lane: leader lanes (their stream), threshold lanes
     int live_maskP = 0, live_maskQ = 0;                      // bit s: stream s of the group produces samples in its current frame
     int seqP = 0, seqQ = 0;                                  // samples opened so far, per group (identical in every wave)
-    int chnP = 0, chnQ = 0;                                  // GRU-B phases run so far, per group
     int smpP = 0, smpQ = 0, fP = 0, fQ = 0;                  // position of the group's NEXT P1 sample: sample within the frame, frame
     float lpc_tap = 0.f, prod_old = 0.f;                     // leader lanes: computed behind the tree of a group, used when its sample is finished
 
@@ -180,7 +220,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
 #endif
     // per-phase shader-clock accounting of workgroup 0 (profiling builds only), clk summed over the half-steps of the launch:
     // 0 leader / thresholds / frame boundary, 1 GRU-B mat-vec, 2 GRU-B gates, 3 candidate heads, 4 P1 start values (wait for the indices, gather, cond),
-    // 5 P1 items, 6 P1 close, 7 wait at barrier 1, 8 dual-FC prefetch + GRU-A gate stage, 9 tree, 10 wait at barrier 2
+    // 5 P1 items, 6 P1 close, 7 wait at barrier 1, 8 GRU-A gate stage, 9 tree (chain waves: both stages and the walk, behind the gates), 10 wait at barrier 2
     unsigned long long *const prof = Ap->prof;
     unsigned long long pt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
     const bool profiling = prof != nullptr && blockIdx.x == 0;
@@ -217,7 +257,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             const int lrow = (t_ & 63) >> 4, tap = t_ & 15;
             float pcm, deemph;
             int exc;
-            draw_sample(cells_p, (const unsigned long long *)(gp + L::g_mask) + lrow * 8, sm_ulaw, lrow, tap, liveP, smp_done, preload, histP, pcm, deemph, exc);
+            draw_sample_walked(cells_p, (const int *)(gp + L::g_mask) + lrow, sm_ulaw, lrow, tap, liveP, smp_done, preload, histP, pcm, deemph, exc);
             // the next sample's indices first (wave LW publishes them through idx_p + flag_p): the row waves are waiting for them
             if (more) { open_sample<S>(cells_p, tid0, liveP, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); lds_publish(flag_p, seqP); }
             __builtin_amdgcn_s_setprio(0);
@@ -316,21 +356,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             return (float *)(r < 2 * NA ? smem + L::pre_ur + r * (S * 4) : gb + L::g_prec + (r - 2 * NA) * (S * 4));
         };
 
-        const int lane = tid0 & 63;
         const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-        // this lane's dual-FC row (node = tid >> 1, channel = tid & 1) for group Q's tree, fetched behind the wave's items of P (it lands while the slots are closed)
-        float fcw[NB], fcb = 0.f, fcf = 0.f;
-        auto load_fc = [&]() __attribute__((always_inline)) {
-            int t_ = tid0;
-            LPCN_REMAT_V(t_);
-            const int node_ = t_ >> 1, chan_ = t_ & 1;
-            const auto *fcw_ptr = fc_w_s + node_ * 2 * NB + chan_ * NB;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) fcw[j] = fcw_ptr[j];
-            fcb = fc_b_s[chan_ * 256 + node_]; fcf = fc_f_s[chan_ * 256 + node_];
-        };
-        const uint32_t chcnt_q = lds_addr(gq + L::g_flag) + 8;   // arrival counter of Q's GRU-B chains (the tree of a wave must not start before all four have written their state)
-        if (q_chain) ++chnQ;
 
         // Order of an interval on one wave (round 6, third form.  The first ran P3 of Q, then all of P1 of P, and every wave then sat ~4 k clk behind
         // its own embedding gather; the second issued each wave's gather before Q's chain / heads and the 60 values in flight pushed GRU-A's weights
@@ -447,6 +473,9 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                     : [z] "+v"(zrh), [wp] "+v"(wp32), [hp] "+v"(hp32) : : LPCN_GRUB_LDS_CLOBBERS);
                 __builtin_amdgcn_s_setprio(0);
                 LPCN_X2_PROF(1);
+                // P4 of stream s, stage 1: the rows of the tree's top levels are the same every sample; fetched here, behind the assembly block (nothing extra is live
+                // across it), they land under the gates
+                const TreeRow top = tree_row_load<0>(fc_w_s, fc_b_s, fc_f_s, ln_, 0);
                 // gates: rows [0,16) update, [16,32) reset, [32,48) candidate (src/nnet.c:362-371)
                 const int ln = ln_ & 15;
                 const float sg = lpcn_sigmoid(zrh + rec, sm_tansig);
@@ -458,8 +487,20 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                     const float hnew = sg * hold + (1.f - sg) * hc_i;
                     if ((live_maskQ >> s) & 1) hB_q[s * NB + ln_] = hnew;
                 }
-                lds_arrive(chcnt_q);                         // (behind the state store)
                 LPCN_X2_PROF(2);
+                // ---- P4 of group Q: the dual-FC tree of stream s, on the wave that has just produced its state (src/nnet.c:163-214) ----
+                // Round 8.  Until then all eight waves evaluated all 255 nodes x 2 channels of the four streams (one node-channel per lane, the products on the
+                // matrix pipe) behind their items and the leader walked 255 ballot bits: 1.5 k clk on every wave for 8 nodes the result needs.  Here the stream's
+                // own wave speculates over the top five levels, walks its ballot as scalar bit tests, fetches the rows of the 7-node subtree under the node
+                // reached and does the same for the last three levels: 38 node evaluations per stream, none on the row waves, and the leader reads 8 bits.
+                // The state is read back from the cells this wave has just written (a wave's LDS operations complete in order: no counter, and no wave waits
+                // for another stream's chain).  Streams that are not live, clamped copies and teacher-forced samples run the same code; the leader ignores the value.
+                const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
+                int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
+                const TreeRow sub = tree_row_load<1>(fc_w_s, fc_b_s, fc_f_s, ln_, val);
+                val = (val << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) | tree_stage_walk<1>(sub, hB_q + s * NB, thr_s, sm_tansig, ln_);
+                if (ln_ == 0) ((int *)(gq + L::g_mask))[s] = val;      // read by the leader behind barriers 1 and 2
+                LPCN_X2_PROF(9);
             }
             // (Round 6 also gave these waves a share of P's start-value pass -- a round of update / reset rows and one of candidate inputs, or the candidate
             // inputs alone, issued above the gates: 144.0 / 145.7 vs 147.0 M.  With only the barrier waits instrumented the chain waves have 1.3-2.2 k clk
@@ -598,7 +639,6 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 }
             };
             run_items(run_items, std::integral_constant<int, 0>{});
-            if (q_chain) load_fc();
             LPCN_X2_PROF(5);
             // close whichever slot is still open; slots that start exactly at the end have no items
             if (b1 >= jend) {
@@ -613,68 +653,12 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             }
             LPCN_X2_PROF(6);
         }
-        // ------------------------------------------------------------ P4 of group Q: dual-FC tree, all nodes at once (src/nnet.c:163-214) --
-        // Round 6: the tree runs on each wave BEHIND its own part of interval A, in front of the barrier -- a wave that is done early evaluates its nodes
-        // while others are still in their (latency-bound) items, instead of all eight saturating the vector units at once behind the barrier.
-        if (q_chain) {
-            if (!p_active) load_fc();
-            lds_poll_until<false>(chcnt_q, chnQ * S);
-            int tid = tid0;
-            LPCN_REMAT_V(tid);
-            const int node = tid >> 1;
-            const int node_level = node > 0 ? 31 - __clz(node) : 0;
-            const float *const thr_q = (const float *)(gq + L::g_thr);
-            unsigned long long *const mask_q = (unsigned long long *)(gq + L::g_mask);
-            // the node's 16 products for all four streams from the matrix pipe, four columns at a time, like a GRU-A item: lane k of a quad holds stream k's
-            // state, v_mfma_f32_4x4x1 with C = -0.0 returns (stream k's value) x (this lane's weight) in register k, rounded once; the sums stay in the
-            // reference's order as packed adds over stream pairs (src/nnet.c:194-199) -- 16 MFMA + 32 packed adds instead of 64 multiplies + 64 adds
-            // (146.7 -> 148.3 M samples/s)
-            float sums[S];
-            {
-                typedef float f4 __attribute__((ext_vector_type(4)));
-                typedef float f2 __attribute__((ext_vector_type(2)));
-                float hs[NB];
-                const float4 *hp = (const float4 *)(hB_q + (tid & 3) * NB);
-#pragma unroll
-                for (int qd = 0; qd < NB / 4; ++qd) { const float4 v4 = hp[qd]; hs[4 * qd] = v4.x; hs[4 * qd + 1] = v4.y; hs[4 * qd + 2] = v4.z; hs[4 * qd + 3] = v4.w; }
-                load_negz();
-                f2 s01 = {fcb, fcb}, s23 = {fcb, fcb};
-#pragma unroll
-                for (int jb = 0; jb < NB; jb += 4) {
-                    f4 pv[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) pv[c] = __builtin_amdgcn_mfma_f32_4x4x1f32(hs[jb + c], fcw[jb + c], negz, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        s01 = s01 + __builtin_shufflevector(pv[c], pv[c], 0, 1);
-                        s23 = s23 + __builtin_shufflevector(pv[c], pv[c], 2, 3);
-                    }
-                }
-                sums[0] = s01[0]; sums[1] = s01[1]; sums[2] = s23[0]; sums[3] = s23[1];
-            }
-            // the four streams stage by stage -- four table lookups in flight, the masks stored at the end (a store per stream makes every stream a basic block
-            // of its own, and the compiler then runs them one behind the other)
-            float vq[S], thq[S];
-            unsigned long long mq[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) { vq[s] = lpcn_tanh(sums[s], sm_tansig); thq[s] = thr_q[s * 8 + node_level]; }
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const float v = fcf * vq[s];
-                const float vo = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-                const float lg = v + vo;
-                mq[s] = __ballot(thq[s] < lg) & (wave == 0 ? 0x5555555555555554ull : 0x5555555555555555ull);
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int s = 0; s < S; ++s) mask_q[s * 8 + wave] = mq[s];
-            }
-            // wave LW: the prediction terms of Q's next sample that do not involve the sample about to be drawn (src/lpcnet.c:252,262)
-            if (is_lw) {
-                lpc_tap = ((const float *)(gq + L::g_lpc))[tid & 63];
-                prod_old = row_shr1(histQ, 0.f) * lpc_tap;
-            }
+        // wave LW: the prediction terms of Q's next sample that do not involve the sample about to be drawn (src/lpcnet.c:252,262)
+        if (q_chain && is_lw) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            lpc_tap = ((const float *)(gq + L::g_lpc))[t_ & 63];
+            prod_old = row_shr1(histQ, 0.f) * lpc_tap;
         }
         LPCN_X2_PROF(9);
         __syncthreads();                                                       // B1
@@ -726,7 +710,6 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         { const bool t = liveP; liveP = liveQ; liveQ = t; }
         { const int t = live_maskP; live_maskP = live_maskQ; live_maskQ = t; }
         { const int t = seqP; seqP = seqQ; seqQ = t; }
-        { const int t = chnP; chnP = chnQ; chnQ = t; }
         { const int t = smpP; smpP = smpQ; smpQ = t; }
         { const int t = fP; fP = fQ; fQ = t; }
         asm volatile("; LPCN_SAMPLE_LOOP_END" ::: "memory");
