@@ -10,7 +10,8 @@
 // P4 (tree); the workgroup runs HALF-STEPS of two intervals and two barriers:
 //
 //      interval A:  P3 of the one group (its GRU-B chains on waves 0..3, its candidate heads on the head waves) and, on each chain
-//                   wave, P4 of its stream (the tree in two stages, tree_stages.h), followed, on every wave, by P1 of the OTHER group   | barrier
+//                   wave, stage 1 of its stream's P4 (the tree in two stages, tree_stages.h), followed, on every wave, by P1 of the OTHER
+//                   group; stage 2 of the four streams' trees is one pass of row wave LPCN_X2_S2W behind its items                      | barrier
 //      interval B:  P2 of that other group                                                                   | barrier, the groups swap roles
 //
 // so a wave is never short of work that does not depend on the chain it has just fed: the leader / gather latency of one group's
@@ -29,6 +30,8 @@ namespace lpcn {
 
 #define LPCN_X2_LW 4            // the wave that leads the streams (LPC predictor, mu-law): a head wave (model_pack.c gives it the shortest candidate slot) -- waves 0..3 start GRU-B's chains at once
 #define LPCN_X2_TW 0            // the wave that draws the KISS99 thresholds: a chain wave -- they have the most slack at barrier 1 (wave 0 / 1 / 3 / 5 / 6: 149.5 / 148.9 / 145.0 / 147.4 / 143.5 M; leader on wave 5 / 7: 139.3 / 138.2 M against 146.7 M on wave 4, round 6)
+#define LPCN_X2_S2W 7           // the row wave that runs stage 2 of the four streams' trees in one pass (never the leader's: it has the least slack at barrier 1)
+#define LPCN_X2_S2_LEAD 2       // ... and how many of its P1 items from the end it polls the streams' prefixes and issues the loads of its rows (2 / 4 / 8: 171.8 / 171.3 / 170.2 M; at least 1)
 #define LPCN_X2_HG 10           // head items a row wave runs before it polls the leader's indices for the start-value pass (6 / 10 / 14 / 18: 145.0 / 146.7 / 146.2 / 144.3 M)
 
 struct LdsX2 {
@@ -42,6 +45,7 @@ struct LdsX2 {
     static constexpr int g_idx   = g_hB + S * NB * 4;               // [4] packed indices, [4] live flags
     static constexpr int g_thr   = g_idx + S * 16;                  // [4][8]
     static constexpr int g_mask  = g_thr + S * 32;                  // [4] i32: the streams' walked tree values (the region keeps the size of the [4][8] u64 ballots the twelve-wave kernel stores here)
+    static constexpr int g_pfx   = g_mask + S * 4;                  // [4] i32: (sample sequence number << LPCN_TREE_TOP) | stage 1's walk, published by the streams' chain waves for the stage-2 wave
     static constexpr int g_lead  = g_mask + S * 64;                 // [4][8]
     static constexpr int g_flag  = g_lead + S * 32;                 // [4] i32
     static constexpr int g_condb = g_flag + 16;                     // [4][48]
@@ -69,10 +73,8 @@ struct LdsX2 {
 // separately rounded products and sums (src/nnet.c:194-199), tanh, * factor, channel 0 + channel 1, threshold[level] < sum.
 typedef float tree_f4 __attribute__((ext_vector_type(4)));
 struct TreeRow { tree_f4 w[NB / 4]; float bias, factor; };
-template <int STAGE>
-__device__ __forceinline__ TreeRow tree_row_load(const LPCN_GLOBAL float *fc_w, const LPCN_GLOBAL float *fc_b, const LPCN_GLOBAL float *fc_f, const int lane, const int prefix)
+__device__ __forceinline__ TreeRow tree_row_load_node(const LPCN_GLOBAL float *fc_w, const LPCN_GLOBAL float *fc_b, const LPCN_GLOBAL float *fc_f, const int node, const int chan)
 {
-    const int node = lpcn_tree_node(STAGE, lpcn_tree_lane_local(STAGE, lane), prefix), chan = lane & 1;      // 1..255
     const auto *wp = (const LPCN_GLOBAL tree_f4 *)(fc_w + (node * 2 + chan) * NB);      // (64-byte rows of an allocation of their own)
     TreeRow r;
 #pragma unroll
@@ -81,9 +83,18 @@ __device__ __forceinline__ TreeRow tree_row_load(const LPCN_GLOBAL float *fc_w, 
     r.factor = fc_f[chan * 256 + node];
     return r;
 }
-// the stage's decisions (wave-uniform): the ballot over its nodes, walked from the stage's first node
 template <int STAGE>
-__device__ __forceinline__ int tree_stage_walk(const TreeRow &r, const float *h_s, const float *thr_s, const float *tansig, const int lane)
+__device__ __forceinline__ TreeRow tree_row_load(const LPCN_GLOBAL float *fc_w, const LPCN_GLOBAL float *fc_b, const LPCN_GLOBAL float *fc_f, const int lane, const int prefix)
+{
+    return tree_row_load_node(fc_w, fc_b, fc_f, lpcn_tree_node(STAGE, lpcn_tree_lane_local(STAGE, lane), prefix), lane & 1);      // node 1..255
+}
+// the four streams' stage 2 in one pass (tree_stages.h, packed mapping): lane 16 f + l is local lane l of stream f, `prefix` its stream's
+__device__ __forceinline__ TreeRow tree_row_load_packed(const LPCN_GLOBAL float *fc_w, const LPCN_GLOBAL float *fc_b, const LPCN_GLOBAL float *fc_f, const int lane, const int prefix)
+{
+    return tree_row_load_node(fc_w, fc_b, fc_f, lpcn_tree_packed_node(lane, prefix), lane & 1);
+}
+// the decisions of the lanes' nodes: `h_s` the 16 state values of the lane's stream, `thr` the threshold of its node's level
+__device__ __forceinline__ unsigned long long tree_node_ballot(const TreeRow &r, const float *h_s, const float *thr, const float *tansig)
 {
     const float4 *hp = (const float4 *)h_s;
     float sum = r.bias;
@@ -99,7 +110,13 @@ __device__ __forceinline__ int tree_stage_walk(const TreeRow &r, const float *h_
     const float v = r.factor * lpcn_tanh(sum, tansig);
     const float vo = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));      // the other channel (quad_perm [1,0,3,2])
     const float lg = v + vo;
-    const unsigned long long m = __ballot(thr_s[lpcn_tree_level(STAGE, lpcn_tree_lane_local(STAGE, lane))] < lg) & lpcn_tree_stage_mask(STAGE);
+    return __ballot(*thr < lg);
+}
+// the stage's decisions (wave-uniform): the ballot over its nodes, walked from the stage's first node
+template <int STAGE>
+__device__ __forceinline__ int tree_stage_walk(const TreeRow &r, const float *h_s, const float *thr_s, const float *tansig, const int lane)
+{
+    const unsigned long long m = tree_node_ballot(r, h_s, thr_s + lpcn_tree_level(STAGE, lpcn_tree_lane_local(STAGE, lane)), tansig) & lpcn_tree_stage_mask(STAGE);
     return lpcn_tree_stage_walk(m, STAGE == 0 ? LPCN_TREE_TOP : LPCN_TREE_LEVELS - LPCN_TREE_TOP);
 }
 
@@ -195,6 +212,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             stage_leader_record({(float *)(gb + L::g_lead), (int *)(gb + L::g_idx), nullptr, nullptr}, s, &states[stream_of(tid)]);
         }
         if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; }
+        if (tid < 2 * S) ((int *)(smem + (tid >> 2) * L::G_SZ + L::g_pfx))[tid & 3] = 0;      // (no sample has sequence number 0)
     }
     __syncthreads();
 
@@ -220,7 +238,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
 #endif
     // per-phase shader-clock accounting of workgroup 0 (profiling builds only), clk summed over the half-steps of the launch:
     // 0 leader / thresholds / frame boundary, 1 GRU-B mat-vec, 2 GRU-B gates, 3 candidate heads, 4 P1 start values (wait for the indices, gather, cond),
-    // 5 P1 items, 6 P1 close, 7 wait at barrier 1, 8 GRU-A gate stage, 9 tree (chain waves: both stages and the walk, behind the gates), 10 wait at barrier 2
+    // 5 P1 items, 6 P1 close, 7 wait at barrier 1, 8 GRU-A gate stage, 9 tree (chain waves: stage 1 and its walk, behind the gates; wave LPCN_X2_S2W: stage 2 of the four streams, behind the close), 10 wait at barrier 2
     unsigned long long *const prof = Ap->prof;
     unsigned long long pt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
     const bool profiling = prof != nullptr && blockIdx.x == 0;
@@ -488,18 +506,19 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                     if ((live_maskQ >> s) & 1) hB_q[s * NB + ln_] = hnew;
                 }
                 LPCN_X2_PROF(2);
-                // ---- P4 of group Q: the dual-FC tree of stream s, on the wave that has just produced its state (src/nnet.c:163-214) ----
+                // ---- P4 of group Q, stage 1: the dual-FC tree of stream s, on the wave that has just produced its state (src/nnet.c:163-214) ----
                 // Round 8.  Until then all eight waves evaluated all 255 nodes x 2 channels of the four streams (one node-channel per lane, the products on the
-                // matrix pipe) behind their items and the leader walked 255 ballot bits: 1.5 k clk on every wave for 8 nodes the result needs.  Here the stream's
-                // own wave speculates over the top five levels, walks its ballot as scalar bit tests, fetches the rows of the 7-node subtree under the node
-                // reached and does the same for the last three levels: 38 node evaluations per stream, none on the row waves, and the leader reads 8 bits.
+                // matrix pipe) behind their items and the leader walked 255 ballot bits: 1.5 k clk on every wave for 8 nodes the result needs.  Since then the
+                // stream's own wave speculates over the top five levels and walks its ballot as scalar bit tests; the 7-node subtree under the node reached
+                // is evaluated the same way for the last three levels: 38 node evaluations per stream and the leader reads 8 bits.
                 // The state is read back from the cells this wave has just written (a wave's LDS operations complete in order: no counter, and no wave waits
                 // for another stream's chain).  Streams that are not live, clamped copies and teacher-forced samples run the same code; the leader ignores the value.
+                // Round 9: the chain waves are the pole of the interval, so stage 2 is not theirs any more.  The wave publishes its five decided bits under the
+                // sample's sequence number -- one word, behind its state stores, so whoever reads the tag of this sample reads this sample's prefix and state --
+                // and goes on to P1; wave LPCN_X2_S2W runs stage 2 of all four streams in one pass (below, behind its items).
                 const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
-                int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
-                const TreeRow sub = tree_row_load<1>(fc_w_s, fc_b_s, fc_f_s, ln_, val);
-                val = (val << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) | tree_stage_walk<1>(sub, hB_q + s * NB, thr_s, sm_tansig, ln_);
-                if (ln_ == 0) ((int *)(gq + L::g_mask))[s] = val;      // read by the leader behind barriers 1 and 2
+                const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
+                if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
                 LPCN_X2_PROF(9);
             }
             // (Round 6 also gave these waves a share of P's start-value pass -- a round of update / reset rows and one of candidate inputs, or the candidate
@@ -550,6 +569,29 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             if (p0_wave) { reduce(3, 0); if (fifth) reduce(4, 1); }
             LPCN_X2_PROF(3);
         }
+
+        // ---------------------------------------------------------------- P4 of group Q, stage 2, first part (wave LPCN_X2_S2W) ----
+        // Four streams in one pass: lane 16 f + l is local lane l of stream f (tree_stages.h, packed mapping).  Each lane reads its stream's cell until all
+        // four carry this sample's sequence number, then fetches the row of its node in the subtree its stream's prefix names (4 global_load_dwordx4 +
+        // 2 dwords per lane).  This happens LPCN_X2_S2_LEAD items before the end of the wave's P1 items: the rows land under those, and the chains
+        // have published by then -- in front of the items the wave would wait ~1.2 k clk for them (the row waves open their items while the chain
+        // waves are still in their gates) and become the pole itself.
+        static_assert(LPCN_X2_S2W > LPCN_X2_LW && LPCN_X2_S2W < LPCN_WAVES && LPCN_TREE_FIELDS == S && LPCN_X2_S2_LEAD >= 1, "stage 2 runs on a row wave other than the leader's, one field per stream");
+        const bool s2_wave = q_chain && wave == LPCN_X2_S2W;      // (wave-uniform)
+        TreeRow sub = {};
+        int pfx = 0;
+        auto s2_open = [&]() __attribute__((always_inline)) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            const uint32_t cell = lds_addr(gq + L::g_pfx) + (uint32_t)lpcn_tree_packed_field(t_ & 63) * 4u;
+            do {
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pfx) : "v"(cell) : "memory");
+            } while (__ballot((pfx >> LPCN_TREE_TOP) != seqQ) != 0ull);
+            pfx &= (1 << LPCN_TREE_TOP) - 1;
+            sub = tree_row_load_packed(fc_w_s, fc_b_s, fc_f_s, t_ & 63, pfx);
+        };
+        const bool s2_in_items = s2_wave && p_active && b3 > 0;      // (a wave without items, a half-step without P1: in front of the barrier's work)
+        if (s2_wave && !s2_in_items) s2_open();
 
         // ---------------------------------------------------------------- 5: P1 of group P ----
         if (p_active) {
@@ -617,16 +659,20 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             LPCN_REMAT_S(b2);
             LPCN_REMAT_S(b3);
             // All tests below are wave-uniform scalar branches; an ordinary item falls through every one of them.
-            int nextb = b1;
+            int s2_at = s2_in_items ? (jend > LPCN_X2_S2_LEAD ? jend - LPCN_X2_S2_LEAD : 0) : NW + 1;      // stage 2 of Q's trees opens in front of this item
+            LPCN_REMAT_S(s2_at);
+            int nextb = b1 < s2_at ? b1 : s2_at;
             LPCN_REMAT_S(nextb);
             auto item = [&](const int j) __attribute__((always_inline)) -> bool {           // false: this wave has no more items
                 if (__builtin_expect(j >= jend, 0)) return false;
                 if (j + PF < NW) fetch_h(j + PF);
-                if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty): ONE compare per item against the next one
+                if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty) and the stage-2 wave's opening: ONE compare per item against the next one
                     if (j == b1) row_swap(0, 1);
                     if (j == b2) row_swap(1, 2);
+                    if (j == s2_at) s2_open();
                     __builtin_amdgcn_s_waitcnt(0xC07F);
                     nextb = b1 > j ? b1 : (b2 > j ? b2 : NW);
+                    if (s2_at > j && s2_at < nextb) nextb = s2_at;
                 }
                 mac(j);
                 return true;
@@ -652,6 +698,21 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 row_store(2);
             }
             LPCN_X2_PROF(6);
+        }
+        // ---------------------------------------------------------------- P4 of group Q, stage 2, second part ----
+        // Behind the close of the items: the state and the thresholds of the lane's stream, one 64-bit ballot, four three-level walks over its 16-bit
+        // fields (scalar); lane 16 f stores stream f's 8 bits for the leader, which reads them behind barriers 1 and 2.  In a group with fewer than four
+        // streams the unused fields belong to clamped copies: valid rows, values nobody reads.
+        if (s2_wave) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            const int ln = t_ & 63, f = lpcn_tree_packed_field(ln);
+            const unsigned long long m = tree_node_ballot(sub, hB_q + f * NB, (const float *)(gq + L::g_thr) + f * 8 + lpcn_tree_packed_level(ln), sm_tansig) & lpcn_tree_packed_mask();
+            int walks = 0;
+#pragma unroll
+            for (int k = 0; k < S; ++k) walks |= lpcn_tree_packed_walk(m, k) << (8 * k);
+            if ((ln & (LPCN_TREE_FIELD_LANES - 1)) == 0)
+                ((int *)(gq + L::g_mask))[f] = (pfx << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) | ((walks >> (8 * f)) & ((1 << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) - 1));
         }
         // wave LW: the prediction terms of Q's next sample that do not involve the sample about to be drawn (src/lpcnet.c:252,262)
         if (q_chain && is_lw) {

@@ -39,3 +39,27 @@ LPCN_HD constexpr int lpcn_tree_stage_walk(const unsigned long long ballot, cons
     for (int b = 0; b < levels; ++b) val = (val << 1) | (int)((ballot >> (2 * ((1 << b) | val))) & 1ull);
     return val;
 }
+
+// ---- stage 2 of FOUR streams in one pass of one wave (round 9): the wave is four 16-lane FIELDS, field f = lane >> 4 belongs to stream f of
+// the group and is a stage-2 wave cut to 16 lanes -- local lane l = lane & 15 is (local node l >> 1, channel l & 1), the 7 nodes of the subtree
+// under the node stream f's own prefix names; lanes 0, 1 of a field evaluate the subtree's first node again (a valid row, masked off).  The
+// 64-bit ballot is four 16-bit stage ballots, each walked like a stage-2 ballot (tests/test_tree_stages_packed.py).
+#define LPCN_TREE_FIELD_LANES 16
+#define LPCN_TREE_FIELDS 4
+LPCN_HD constexpr int lpcn_tree_packed_field(const int lane) { return lane / LPCN_TREE_FIELD_LANES; }
+LPCN_HD constexpr int lpcn_tree_packed_local(const int lane) { return lpcn_tree_lane_local(1, lane % LPCN_TREE_FIELD_LANES); }      // 1..7
+LPCN_HD constexpr int lpcn_tree_packed_level(const int lane) { return lpcn_tree_level(1, lpcn_tree_packed_local(lane)); }
+LPCN_HD constexpr int lpcn_tree_packed_node(const int lane, const int prefix) { return lpcn_tree_node(1, lpcn_tree_packed_local(lane), prefix); }      // prefix: the lane's field's
+// ballot bits that count: the stage-2 mask in every field
+LPCN_HD constexpr unsigned long long lpcn_tree_packed_mask()
+{
+    unsigned long long m = 0;
+    for (int f = 0; f < LPCN_TREE_FIELDS; ++f) m |= lpcn_tree_stage_mask(1) << (LPCN_TREE_FIELD_LANES * f);
+    return m;
+}
+// the walk over field f of the packed ballot: the last LPCN_TREE_LEVELS - LPCN_TREE_TOP decisions of stream f
+LPCN_HD constexpr int lpcn_tree_packed_walk(const unsigned long long ballot, const int field)
+{
+    return lpcn_tree_stage_walk((ballot >> (LPCN_TREE_FIELD_LANES * field)) & ((1ull << LPCN_TREE_FIELD_LANES) - 1), LPCN_TREE_LEVELS - LPCN_TREE_TOP);
+}
+static_assert(2 * lpcn_tree_stage_nodes(1) + 2 <= LPCN_TREE_FIELD_LANES && LPCN_TREE_FIELDS * LPCN_TREE_FIELD_LANES == 64, "a stage-2 subtree fits a 16-lane field");
