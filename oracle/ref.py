@@ -49,6 +49,9 @@ class RefLib:
                                              C.POINTER(C.c_int), _u32p]
         lib.ref_get_logit_table.argtypes = [vp, _f32p]
         lib.ref_synthesize_impl.argtypes = [vp, _f32p, _i16p, C.c_int, C.c_int]
+        if hasattr(lib, "ref_synthesize_tail"):          # (absent from a library built before the hook existed)
+            lib.ref_synthesize_tail.argtypes = [vp, _f32p, _f32p, _f32p, _i16p, C.c_int, C.c_int]
+            lib.ref_synthesize_tail.restype = None
         lib.ref_run_frame_network.argtypes = [vp, _f32p, _f32p, _f32p, _f32p]
         lib.ref_run_sample_network.argtypes = [vp, _f32p, _f32p, C.c_int, C.c_int, C.c_int]
         lib.ref_run_sample_network.restype = C.c_int

@@ -86,6 +86,17 @@ void ref_run_frame_network(LPCNetState *st, const float *features, float *cond_a
     run_frame_network(st, cond_a, cond_b, lpc, features);        /* src/lpcnet.c:82 */
 }
 
+/* the tail alone on frame products supplied by the caller (the counterpart of the engine's lpcnet_batch_run_tail and of the
+ * oracle's orc_synthesize_tail): the products are put where run_frame_network leaves them, the loop is the reference's */
+void ref_synthesize_tail(LPCNetState *st, const float *cond_a, const float *cond_b, const float *lpc,
+                         short *output, int N, int preload)
+{
+    memcpy(st->gru_a_condition, cond_a, sizeof(st->gru_a_condition));
+    memcpy(st->gru_b_condition, cond_b, sizeof(st->gru_b_condition));
+    memcpy(st->lpc, lpc, sizeof(st->lpc));
+    lpcnet_synthesize_tail_impl(st, output, N, preload);         /* src/lpcnet.c:235 */
+}
+
 int ref_run_sample_network(LPCNetState *st, const float *cond_a, const float *cond_b,
                            int last_exc, int last_sig, int pred)
 {

@@ -64,6 +64,17 @@ def test_scalar_known_answers(golden, oracle_lib):
     assert np.array_equal(np.array([L.orc_logit_table(i) for i in range(256)], np.float32), golden["logit_table"])
 
 
+def test_lin2ulaw_where_the_loud_families_drive_it(golden, oracle_lib):
+    """golden_v1's table clamps (its sweep runs to +-40000) but ends there; the loud families (tests/tools/loud_inputs.py) call the
+    conversion with up to 2e6, and cross the clamp thresholds near +-32768: the reference's answers for those arguments"""
+    import os
+    loud = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_loud_v1.npz"))
+    assert np.abs(golden["ulaw_x"]).max() < 5e4 < 1e6 < np.abs(loud["ulaw_x"]).max()
+    got = np.array([oracle_lib.orc_lin2ulaw(float(x)) for x in loud["ulaw_x"]], np.int32)
+    assert np.array_equal(got, loud["lin2ulaw"])
+    assert set(got[np.abs(loud["ulaw_x"]) > 4e4].tolist()) == {0, 255} and 1 in got and 254 in got
+
+
 def test_kiss99(golden, oracle_lib):
     rng = np.zeros(4, np.uint32)
     oracle_lib.orc_kiss99_srand(rng, b"LPCNet", 6)
