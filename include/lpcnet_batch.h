@@ -165,7 +165,8 @@ LPCNET_EXPORT int lpcnet_batch_encoder_enable(LPCNetBatch *b, int max_packets);
 LPCNET_EXPORT int lpcnet_batch_get_encoder_vq_mem(LPCNetBatch *b, int stream, float *out18);
 LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in18);
 
-/* Packet-loss concealment on the device, bit-identical to the reference's generic-C float build (src/lpcnet_plc.c) in CAUSAL mode.
+/* Packet-loss concealment on the device, bit-identical to the reference's generic-C builds (src/lpcnet_plc.c) in CAUSAL mode: the float build
+ * (DISABLE_DOT_PROD) for a float blob, the int8 build (DOT_PROD, the reference's default) for an int8 blob.
  * With lpcnet_batch_plc_enable a batch is, in addition, n independent LPCNetPLCState objects: the `lpcnet` member of stream s is the
  * stream's synthesis state, the `enc` member its analysis state, everything else is per-stream PLC state.  One step advances every
  * stream by one 10-ms frame: pcm [n_streams][160] in and out, lost [n_streams] (a HOST array in every form of the call);
@@ -173,10 +174,12 @@ LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, co
  *   lost[s] != 0: pcm[s] is ignored and receives the concealment  -> lpcnet_plc_conceal(st[s], pcm[s])
  * The PLC network comes from the same blob as the LPCNet model, as in lpcnet_plc_load_model (src/lpcnet_plc.c:88-97): arrays
  * plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_* (training_tf2/dump_plc.py).  Its widths are read from the bias lengths (each up to 512).
+ * It is served in the flavour of its blob, which is what one dump of the reference produces: float GRU arrays with a float LPCNet model,
+ * int8 GRU arrays with an int8 one (src/vec.h:274-339 without USE_SU_BIAS: per 8x4 block one exact integer sum, one rounded float add).
  * plc_enable: options = LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER.  LPCNET_PLC_NONCAUSAL returns
  *   LPCNET_HIP_E_ARG: the reference stops in that mode when FEATURES_DELAY > 0 (src/lpcnet_plc.c:357-361) and this engine's model format has 2.
- *   A blob without the PLC arrays, or with int8 ones (the float build's arithmetic is what is served), returns LPCNET_HIP_E_MODEL with a
- *   message; so does every other call below before plc_enable.  It allocates the PLC state, implies lpcnet_batch_analysis_enable(1) and
+ *   A blob without the PLC arrays, with incomplete or inconsistent ones, or with a mix no reference build has -- int8 PLC arrays beside a float
+ *   LPCNet model, float PLC arrays beside an int8 one -- returns LPCNET_HIP_E_MODEL with a message; so does every other call below before plc_enable.  It allocates the PLC state, implies lpcnet_batch_analysis_enable(1) and
  *   performs lpcnet_plc_reset on every stream, which resets the stream's synthesis and analysis states as the reference does (:46-60).
  * The PLC owns the streams it drives: mixing its steps with lpcnet_batch_synthesize* / _analyze* on the same streams gives what the
  * same mix gives on the reference's member states, except that a tail step after a foreign frame step uses the PLC's own last products.
@@ -194,6 +197,7 @@ LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, co
 #define LPCNET_PLC_DC_FILTER 4
 #endif
 LPCNET_EXPORT int lpcnet_batch_plc_enable(LPCNetBatch *b, int options);
+LPCNET_EXPORT int lpcnet_batch_plc_flavour(const LPCNetBatch *b);      /* 0: the float PLC network runs, 1: the int8 one; LPCNET_HIP_E_MODEL before plc_enable */
 LPCNET_EXPORT int lpcnet_batch_plc_reset(LPCNetBatch *b, int first, int count);
 LPCNET_EXPORT int lpcnet_batch_plc_step(LPCNetBatch *b, short *pcm, const unsigned char *lost);
 LPCNET_EXPORT int lpcnet_batch_plc_step_device(LPCNetBatch *b, short *d_pcm, const unsigned char *lost, void *hip_stream);
@@ -211,6 +215,10 @@ LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float
  * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
  * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */
 LPCNET_EXPORT int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary);
+/* a blob's PLC network as the loader sees it, no device: info[7] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or inconsistent),
+ * servable (plc_enable accepts the blob), dense width, GRU widths, 8x4 blocks of the two GRU input matrices}.  Returns 0, LPCNET_HIP_E_ARG without
+ * `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
+LPCNET_EXPORT int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info);
 
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);

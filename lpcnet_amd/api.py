@@ -125,6 +125,7 @@ def load_library():
     L.lpcnet_batch_get_analysis_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_analysis_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_plc_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_plc_flavour.argtypes = [vp]
     L.lpcnet_batch_plc_reset.argtypes = [vp, C.c_int, C.c_int]
     L.lpcnet_batch_plc_step.argtypes = [vp, _i16p, _u8p]
     L.lpcnet_batch_plc_step_device.argtypes = [vp, vp, _u8p, vp]
@@ -136,6 +137,7 @@ def load_library():
     L.lpcnet_batch_plc_burg.argtypes = [vp, _f32p, _f32p]
     L.lpcnet_batch_plc_pred.argtypes = [vp, _f32p, _f32p]
     L.lpcnet_hip_plc_plan.argtypes = [C.c_int, C.c_int, vp, _u8p, vp, vp]
+    L.lpcnet_hip_plc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -179,6 +181,14 @@ def check_model(blob: bytes):
     info = (C.c_int * 6)()
     rc = load_library().lpcnet_hip_check_model(blob, len(blob), info)
     return rc, list(info)
+
+
+def plc_model_info(blob: bytes):
+    """Host-only view of a blob's PLC network: dict(present, servable, d1, g1, g2, nb1, nb2); see include/lpcnet_batch.h."""
+    info = (C.c_int * 7)()
+    if load_library().lpcnet_hip_plc_model_info(blob, len(blob), info) != 0:
+        raise LPCNetError("plc_model_info: " + last_error())
+    return dict(zip(("present", "servable", "d1", "g1", "g2", "nb1", "nb2"), list(info)))
 
 
 def x3_image_info(blob: bytes):
@@ -471,6 +481,13 @@ class LPCNetBatch:
     def plc_enable(self, options: int = PLC_CAUSAL):
         """PLC_CAUSAL or PLC_CODEC, optionally | PLC_DC_FILTER; resets every stream (PLC, synthesis and analysis state)"""
         self._chk(self.L.lpcnet_batch_plc_enable(self.p, options), "plc_enable")
+
+    def plc_flavour(self) -> int:
+        """0: the float PLC network runs, 1: the int8 one (the flavour of the batch's blob)"""
+        rc = self.L.lpcnet_batch_plc_flavour(self.p)
+        if rc < 0:
+            self._chk(rc, "plc_flavour")
+        return rc
 
     def plc_reset(self, first=0, count=None):
         self._chk(self.L.lpcnet_batch_plc_reset(self.p, first, self.n - first if count is None else count), "plc_reset")

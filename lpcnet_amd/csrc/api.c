@@ -1266,6 +1266,11 @@ int lpcnet_batch_plc_enable(LPCNetBatch *b, int options)
     for (int k = 0; k < b->n_shards; k++) { int rc = lpcn_batch_dev_plc_enable(b->sh[k].dev, options); if (rc) { take_engine_err(); return rc; } }
     return 0;
 }
+int lpcnet_batch_plc_flavour(const LPCNetBatch *b)
+{
+    NEED_PLC_ON(b);
+    FWD(lpcn_batch_dev_plc_flavour(b->sh[0].dev));
+}
 int lpcnet_batch_plc_reset(LPCNetBatch *b, int first, int count)
 {
     NEED_PLC_ON(b);
@@ -1596,6 +1601,20 @@ int lpcnet_hip_quant_sweep_device(unsigned long long *out3)
 {
     if (!out3) { set_err("lpcnet_hip_quant_sweep_device: bad arguments"); return LPCN_E_ARG; }
     FWD(lpcn_debug_quant_sweep(single_stream_device(), out3));
+}
+
+/* Host-only view of a blob's PLC network (no GPU needed): info[0..6] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
+ * inconsistent), servable (the arrays are in the blob's own flavour: lpcnet_batch_plc_enable accepts the blob), d1, g1, g2, blocks of the
+ * two GRU input matrices}.  Returns 0, LPCN_E_ARG without `info`, LPCN_E_MODEL when the blob does not load as an LPCNet model at all. */
+int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info)
+{
+    lpcn_model_host m;
+    if (!info) { set_err("lpcnet_hip_plc_model_info: bad arguments"); return LPCN_E_ARG; }
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return LPCN_E_MODEL; }
+    info[0] = m.plc.present; info[1] = lpcn_plc_servable(&m);
+    info[2] = m.plc.d1; info[3] = m.plc.g1; info[4] = m.plc.g2; info[5] = m.plc.nb1; info[6] = m.plc.nb2;
+    lpcn_model_release(&m);
+    return 0;
 }
 
 /* Host-only model check (no GPU needed): parses the blob with the loader's rules, builds the device

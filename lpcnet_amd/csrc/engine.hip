@@ -121,8 +121,10 @@ struct lpcn_engine {
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
     lpcn::EncodeTables enc{};      // encoder: the same codebooks and their transposed copies, refreshed together
-    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network (plc_present == 1)
+    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network (float blobs; int8 blobs: its widths only)
+    lpcn::PlcNetQ plcq{};          //   ... an int8 blob's (plc_pred_i8_kernel)
     int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
+    bool plc_servable = false;     //   ... and whether it is in the blob's own flavour (lpcn_plc_servable): uploaded only then
 };
 
 // packet-loss concealment of a batch (lpcn_batch_dev_plc_enable): the control state on the host, the data on the device
@@ -268,6 +270,39 @@ static int plc_upload_net(lpcn_engine *e, const lpcn_plc_model *p)
             for (int k = 0; k < cnt; ++k) pos.push_back(*idx++);
             start[r + 1] = (int)pos.size();
         }
+        if ((rc = upload<int>(e, g ? &n.gru2_start : &n.gru1_start, start.data(), start.size()))) return rc;
+        if ((rc = upload<int>(e, g ? &n.gru2_pos : &n.gru1_pos, pos.data(), pos.size()))) return rc;
+    }
+    return 0;
+}
+
+// the int8 PLC network (plc_pred_i8_kernel): the float arrays as they are (`bias` -- the generic-C build never reads `subias`), the GRU input
+// blocks as the blob has them -- [block][8 rows][4 cols] int8 is one dword per (row, block) already -- with the row groups' first blocks and the
+// blocks' input dwords, and the recurrent weights block-major (model_pack.c: lpcn_plc_pack_rec_i8)
+static int plc_upload_net_i8(lpcn_engine *e, const lpcn_plc_model *p)
+{
+    lpcn::PlcNetQ &n = e->plcq;
+    n.d1 = e->plc.d1 = p->d1; n.g1 = e->plc.g1 = p->g1; n.g2 = e->plc.g2 = p->g2;
+    int rc = 0;
+#define UPP(field, src, count) if ((rc = upload<float>(e, &n.field, src, (size_t)(count)))) return rc
+    UPP(dense1_w, p->dense1_w, LPCN_PLC_IN * p->d1); UPP(dense1_b, p->dense1_b, p->d1);
+    UPP(gru1_bias, p->gru1_bias, 6 * p->g1); UPP(gru2_bias, p->gru2_bias, 6 * p->g2);
+    UPP(out_w, p->out_w, LPCN_NB_FEAT * p->g2); UPP(out_b, p->out_b, LPCN_NB_FEAT);
+    UPP(tansig, lpcn_tansig, 201);
+#undef UPP
+    for (int g = 0; g < 2; ++g) {
+        const int *idx = g ? p->gru2_idx : p->gru1_idx;
+        const int N = g ? p->g2 : p->g1, nb = g ? p->nb2 : p->nb1, groups = 3 * N / 8;
+        std::vector<int> start(groups + 1, 0), pos;
+        for (int r = 0; r < groups; ++r) {
+            const int cnt = *idx++;
+            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++ >> 2);
+            start[r + 1] = (int)pos.size();
+        }
+        std::vector<int32_t> rec((size_t)3 * N * N / 4);
+        lpcn_plc_pack_rec_i8((const signed char *)(g ? p->gru2_rec : p->gru1_rec), N, rec.data());
+        if ((rc = upload<int>(e, g ? &n.gru2_w : &n.gru1_w, g ? p->gru2_w : p->gru1_w, (size_t)8 * nb))) return rc;      // (32 bytes per block)
+        if ((rc = upload<int>(e, g ? &n.gru2_rec : &n.gru1_rec, rec.data(), rec.size()))) return rc;
         if ((rc = upload<int>(e, g ? &n.gru2_start : &n.gru1_start, start.data(), start.size()))) return rc;
         if ((rc = upload<int>(e, g ? &n.gru2_pos : &n.gru1_pos, pos.data(), pos.size()))) return rc;
     }
@@ -466,7 +501,8 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     fm.lpc_gamma = m->lpc_gamma;
     fm.end2end = 0;
     e->plc_present = m->plc.present;
-    if (m->plc.present == 1 && (rc = plc_upload_net(e, &m->plc))) return fail(rc);
+    e->plc_servable = lpcn_plc_servable(m) != 0;
+    if (e->plc_servable && (rc = m->is_int8 ? plc_upload_net_i8(e, &m->plc) : plc_upload_net(e, &m->plc))) return fail(rc);
     *out = e;
     return 0;
 }
@@ -1545,6 +1581,17 @@ extern "C" int lpcn_plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsign
 
 extern "C" int lpcn_engine_plc_present(const lpcn_engine *e) { return e->plc_present; }
 extern "C" int lpcn_batch_dev_plc_enabled(const lpcn_batch_dev *b) { return b->plc ? 1 : 0; }
+extern "C" int lpcn_batch_dev_plc_flavour(const lpcn_batch_dev *b)
+{
+    if (!b->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; }
+    return b->e->is_int8 ? 1 : 0;
+}
+// compute_plc_pred in the flavour of the engine's blob: the same records and data, the float or the int8 network
+static void launch_plc_pred(lpcn_batch_dev *b, hipStream_t st, const int *ctl, int cnt, float *raw_out)
+{
+    if (b->e->is_int8) hipLaunchKernelGGL(lpcn::plc_pred_i8_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plcq, ctl, cnt, b->plc->D, raw_out);
+    else hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, cnt, b->plc->D, raw_out);
+}
 static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(b->e->plc.g1 + b->e->plc.g2); }
 // lpcnet_plc_reset (src/lpcnet_plc.c:46-60) on streams [first, first + count): the PLC's own fields, the synthesis state, the analysis state
 static int plc_reset_range(lpcn_batch_dev *b, int first, int count)
@@ -1568,8 +1615,9 @@ extern "C" int lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options)
 {
     if ((options & 3) == 1 || (options & 3) == 3 || (options & ~7)) { snprintf(g_err, sizeof(g_err), "PLC options: LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER (the non-causal mode needs a model without feature delay)"); return LPCN_E_ARG; }
     if (b->e->plc_present == 0) { snprintf(g_err, sizeof(g_err), "the model blob has no PLC network (plc_dense1_*, plc_gru1_*, plc_gru2_*, plc_out_*)"); return LPCN_E_MODEL; }
-    if (b->e->plc_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's PLC network is int8: only the float PLC network is served"); return LPCN_E_MODEL; }
-    if (b->e->plc_present != 1) { snprintf(g_err, sizeof(g_err), "the blob's PLC arrays are incomplete or do not fit together"); return LPCN_E_MODEL; }
+    if (b->e->plc_present != 1 && b->e->plc_present != 2) { snprintf(g_err, sizeof(g_err), "the blob's PLC arrays are incomplete or do not fit together"); return LPCN_E_MODEL; }
+    if (b->e->plc_present == 2 && !b->e->plc_servable) { snprintf(g_err, sizeof(g_err), "the blob's PLC network is int8 but its LPCNet model is float: a PLC network is served in its blob's own flavour"); return LPCN_E_MODEL; }
+    if (!b->e->plc_servable) { snprintf(g_err, sizeof(g_err), "the blob's PLC network is float but its LPCNet model is int8: a PLC network is served in its blob's own flavour"); return LPCN_E_MODEL; }
     DeviceGuard guard(b->e->device);
     int rc = lpcn_batch_dev_analysis_enable(b, 1);
     if (rc) return rc;
@@ -1642,7 +1690,7 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(L.cnt), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, ctl, L.cnt, d_pcm, p->D, p->remove_dc ? 1 : 0);
             break;
         case PLC_T_PRED:
-            hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(L.cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, L.cnt, p->D, (float *)nullptr);
+            launch_plc_pred(b, st, ctl, L.cnt, nullptr);
             break;
         case PLC_T_MIX:
             hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)b->d_gpcm, p->D, b->d_state);
@@ -1796,7 +1844,7 @@ extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57
         HIP_TRY(hipMemcpy(p->an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(p->d_ctl, recs.data(), sizeof(int) * recs.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(b->n), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, (const int *)p->d_ctl, b->n, p->D, b->d_gfeat.p);
+    launch_plc_pred(b, st, p->d_ctl, b->n, b->d_gfeat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(out20, b->d_gfeat, sizeof(float) * (size_t)b->n * LPCN_NB_FEAT, hipMemcpyDeviceToHost));

@@ -82,11 +82,12 @@ extern "C" {
 #define LPCN_PLC_QUEUE     (LPCN_PLC_BUF_SIZE + LPCN_FRAME_SIZE)
 #define LPCN_PLC_FBUF      4        /* MAX_FEATURE_BUFFER_SIZE, src/lpcnet_private.h:26 */
 typedef struct lpcn_plc_model {
-    int present;                 /* 0: the blob has no plc_* arrays; 1: float arrays; 2: int8 arrays (not served); -1: incomplete or inconsistent arrays */
+    int present;                 /* 0: the blob has no plc_* arrays; 1: float arrays; 2: int8 arrays (DOT_PROD: GRU weights signed char, blocks [8][4]); -1: incomplete or
+                                  * inconsistent arrays.  Served in the blob's own flavour only (lpcn_plc_servable) */
     int d1, g1, g2;              /* dense1 width, GRU widths */
     int nb1, nb2;                /* 8x4 blocks of the two GRU input matrices */
     const float *dense1_w, *dense1_b;            /* [57][d1], [d1] */
-    const float *gru1_w, *gru1_rec, *gru1_bias;  /* blocks [nb1][4][8], [g1][3 g1], [2][3 g1] */
+    const float *gru1_w, *gru1_rec, *gru1_bias;  /* blocks [nb1][4][8], [g1][3 g1], [2][3 g1]; present == 2: signed char blocks [nb1][8][4], [3 g1 / 8][g1 / 4][8][4] */
     const int *gru1_idx;
     const float *gru2_w, *gru2_rec, *gru2_bias;
     const int *gru2_idx;
@@ -159,6 +160,8 @@ void lpcn_x3_image_release(lpcn_x3_image *im);
 int  lpcn_x3_image_selftest(const lpcn_model_host *m, const lpcn_x3_image *im);      /* 0 = every block of GRU-A exactly once, in its row's order, within the bounds */
 /* re-expand the packings and compare them with the blob (0 = consistent) */
 int  lpcn_model_selftest(const lpcn_model_host *m);
+int  lpcn_plc_servable(const lpcn_model_host *m);                           /* 1: the blob's PLC network is in the blob's own flavour (float / int8) */
+void lpcn_plc_pack_rec_i8(const signed char *rec, int N, int32_t *out);     /* int8 recurrent weights of a PLC GRU, one dword per (row, block): out [N / 4][3 N] */
 
 /* ---- per-stream state as the device keeps it (AoS, one record per stream) ------------------ */
 typedef struct lpcn_stream_state {
@@ -332,6 +335,7 @@ int  lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null);     /* host half of lpc
 int  lpcn_engine_plc_present(const lpcn_engine *e);           /* lpcn_plc_model.present of the engine's blob */
 int  lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options);
 int  lpcn_batch_dev_plc_enabled(const lpcn_batch_dev *b);
+int  lpcn_batch_dev_plc_flavour(const lpcn_batch_dev *b);     /* 0 float network, 1 int8; LPCN_E_MODEL before plc_enable */
 int  lpcn_batch_dev_plc_reset(lpcn_batch_dev *b, int first, int count);
 int  lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned char *lost, void *hip_stream);      /* enqueue only; lost is a host array */
 int  lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const unsigned char *lost);

@@ -542,6 +542,25 @@ static int parse_plc(lpcn_plc_model *p, const blob_rec *rec, int n)
     return 0;
 }
 
+/* The engine serves a PLC network in the flavour of its blob, as one dump of the reference produces it: float arrays with a float
+ * LPCNet model, int8 arrays (DOT_PROD) with an int8 one.  No reference build runs either mix. */
+int lpcn_plc_servable(const lpcn_model_host *m)
+{
+    return (m->plc.present == 1 && !m->is_int8) || (m->plc.present == 2 && m->is_int8);
+}
+
+/* int8 recurrent weights of a PLC GRU for plc_pred_i8_kernel: the blob has [3 N / 8 row groups][N / 4 blocks][8 rows][4 cols]
+ * (src/vec.h:274-304), so the four weights of (row, block) are one dword already; the kernel walks a row's blocks with one lane per
+ * row, so the dwords go block-major, out [N / 4][3 N]: a wave's lanes read consecutive dwords. */
+void lpcn_plc_pack_rec_i8(const signed char *rec, int N, int32_t *out)
+{
+    const int rows = 3 * N, nblk = N / 4;
+    for (int g = 0; g < rows / 8; g++)
+        for (int j = 0; j < nblk; j++)
+            for (int r = 0; r < 8; r++)
+                memcpy(&out[(size_t)j * rows + g * 8 + r], rec + (((size_t)g * nblk + j) * 8 + r) * 4, 4);
+}
+
 int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
 {
     blob_rec rec[64];

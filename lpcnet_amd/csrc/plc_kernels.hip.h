@@ -1,15 +1,18 @@
 // Packet-loss concealment on the device: the data side of lpcnet_plc_update / lpcnet_plc_conceal in causal mode
-// (src/lpcnet_plc.c:188-340) for every stream of a batch, bit for bit like the reference's generic-C float build.  The control side
+// (src/lpcnet_plc.c:188-340) for every stream of a batch, bit for bit like the reference's generic-C build of the blob's flavour (float, or
+// int8 DOT_PROD: only the PLC network's two GRUs differ, plc_pred_i8_kernel).  The control side
 // -- which branch a stream takes in this step -- is a function of the loss flags and the FEC calls alone and lives on the host
 // (plc_plan.cpp: plc_plan); each kernel here works on the streams the host listed for it:
 //   plc_burg_kernel   DC removal (src/lpcnet_plc.c:196-205) and burg_cepstral_analysis (src/freq.c:156-199) of a received frame
 //   plc_pred_kernel   compute_plc_pred (src/lpcnet_plc.c:135-146) with its input selection (get_fec_or_pred :148-168), the rotation and
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
+//   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs
 //   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
 //   plc_rows_kernel   gather / scatter of rows by an index map: a group of streams runs through the ordinary frame and sample kernels
 // Every sum keeps the reference's order; products and sums are rounded separately (-ffp-contract=off).
 #pragma once
 #include "lpcnet_log10.h"
+#include "quant_i8.hip.h"           // quant_s8, QS, QS1: the int8 arithmetic's quantisation and scales
 #include "lpcnet_plc_tables_gen.h"
 #include "plc_burg.h"
 #include "plc_records.h"      // record sizes, flags and operation codes of the control lists (shared with the host planner)
@@ -258,6 +261,151 @@ __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, co
     __syncthreads();
     plc_gru(P.g1, P.gru1_w, P.gru1_start, P.gru1_pos, P.gru1_rec, P.gru1_bias, d1, h1, zrh, recur, P.tansig);
     plc_gru(P.g2, P.gru2_w, P.gru2_start, P.gru2_pos, P.gru2_rec, P.gru2_bias, h1, h2, zrh, recur, P.tansig);
+    if (threadIdx.x < LPCN_NB_FEAT) {
+        const int i = threadIdx.x;
+        float acc = P.out_b[i];
+        for (int j = 0; j < P.g2; ++j) acc = acc + P.out_w[(size_t)j * LPCN_NB_FEAT + i] * h2[j];
+        if (i == LPCN_NB_FEAT - 1) { const float v = acc + .1f; acc = .5f < v ? .5f : v; }      // MIN16(.5f, out[19]+.1f)
+        out[i] = acc;
+    }
+    for (int t = threadIdx.x; t < G; t += blockDim.x) net[t] = t < P.g1 ? h1[t] : h2[t - P.g1];
+    __syncthreads();
+    if (threadIdx.x < LPCN_NB_FEAT) {
+        const int i = threadIdx.x;
+        float v = 0.f;
+        bool write = false;
+        if (input == PLC_IN_FEC) { v = fec[i]; write = true; }
+        else if (flags & PLC_F_KEEP) { v = out[i]; write = true; }
+        if (write && i == 0 && (flags & PLC_F_ATT)) {
+            v = v + a1;
+            v = v - a2;
+            v = -10.f > v ? -10.f : v;
+        }
+        if (write) feat[i] = v;
+        if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = out[i];
+    }
+}
+
+// ---- the int8 (DOT_PROD) PLC network: compute_plc_pred of the reference's generic-C int8 build.  The dense layers are float there too; the GRUs
+// run sparse_sgemv_accum8x4 / sgemv_accum8x4 of src/vec.h:274-339 (USE_SU_BIAS undefined: they start from `bias`): per row out *= 128*127, then for
+// each 8x4 block in list order the exact integer sum of four int8 products is added with ONE rounded float add, then out *= 1/128/127.  The inputs
+// of a product are quantised once, (signed char)(int)floor(.5 + 127 x) (quant_s8, quant_i8.hip.h).
+struct PlcNetQ {
+    int d1, g1, g2;
+    const float *dense1_w, *dense1_b;
+    const int *gru1_w, *gru1_rec;                // [blocks][8 rows] and [g1 / 4][3 g1] dwords: the four int8 weights of (row, block)
+    const float *gru1_bias;
+    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input DWORD (position / 4) of a block
+    const int *gru2_w, *gru2_rec;
+    const float *gru2_bias;
+    const int *gru2_start, *gru2_pos;
+    const float *out_w, *out_b;
+    const float *tansig;
+};
+
+constexpr int PLC_Q_UNITS_PER_LANE = (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS;
+
+// compute_gruB on quantised inputs.  One lane per UNIT: it runs the unit's three gate rows (z, r, h: rows i, N + i, 2 N + i), so no pre-activation
+// leaves the lane -- the input product row after row (each row group has its own block list), the recurrent product as three independent add chains
+// on one LDS dword per block.  Units beyond the workgroup size take a second pass (t = 1).  xq [M / 4] and sq [N / 4]: the input and the old state as packed int8, four per dword; hs [N] the
+// state (replaced); nq (may be null) receives the new state quantised, the next layer's input.  All in LDS.
+__device__ __forceinline__ void plc_gru_i8(const int N, const int *W, const int *start, const int *pos, const int *R, const float *bias,
+                                           const int *xq, const int *sq, float *hs, unsigned char *nq, const float *tansig)
+{
+    const int rows = 3 * N, nblk = N >> 2;
+    float hn[PLC_Q_UNITS_PER_LANE];
+#pragma unroll
+    for (int t = 0; t < PLC_Q_UNITS_PER_LANE; ++t) {
+        const int i = threadIdx.x + t * PLC_PRED_THREADS;
+        hn[t] = 0.f;
+        if (i < N) {
+            float zrh[3], rc[3];
+#pragma unroll
+            for (int g = 0; g < 3; ++g) {
+                const int row = g * N + i, grp = row >> 3, r = row & 7;
+                float a = bias[row] + 0.f;
+                a = a * QS;
+                for (int blk = start[grp]; blk < start[grp + 1]; ++blk)
+                    a = a + (float)__builtin_amdgcn_sdot4(W[(size_t)blk * 8 + r], xq[pos[blk]], 0, false);
+                zrh[g] = a * QS1;
+                rc[g] = bias[rows + row] * QS;
+            }
+            for (int j = 0; j < nblk; ++j) {
+                const int x = sq[j];
+                const int *w = R + (size_t)j * rows + i;
+                rc[0] = rc[0] + (float)__builtin_amdgcn_sdot4(w[0], x, 0, false);
+                rc[1] = rc[1] + (float)__builtin_amdgcn_sdot4(w[N], x, 0, false);
+                rc[2] = rc[2] + (float)__builtin_amdgcn_sdot4(w[2 * N], x, 0, false);
+            }
+            const float z = lpcn_sigmoid(zrh[0] + rc[0] * QS1, tansig);
+            const float rg = lpcn_sigmoid(zrh[1] + rc[1] * QS1, tansig);
+            float hh = zrh[2] + (rc[2] * QS1) * rg;
+            hh = lpcn_tanh(hh, tansig);
+            hn[t] = z * hs[i] + (1.f - z) * hh;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < PLC_Q_UNITS_PER_LANE; ++t) {
+        const int i = threadIdx.x + t * PLC_PRED_THREADS;
+        if (i < N) {
+            hs[i] = hn[t];
+            if (nq) nq[i] = (unsigned char)quant_s8(hn[t]);
+        }
+    }
+    __syncthreads();
+}
+
+// plc_pred_kernel for an int8 PLC network: the same records, flags and per-stream data (the network state is float in both builds); only the two
+// GRUs differ.  The control parts repeat plc_pred_kernel's, which stays as it is.
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    __shared__ float in[LPCN_PLC_IN + 3];
+    __shared__ float h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
+    __shared__ int xq[LPCN_PLC_MAX_UNITS / 4], s1q[LPCN_PLC_MAX_UNITS / 4], s2q[LPCN_PLC_MAX_UNITS / 4];      // a layer's input, the two old states: packed int8
+    __shared__ float out[LPCN_NB_FEAT];
+    if ((int)blockIdx.x >= cnt) return;
+    const int *rec = ctl + (size_t)blockIdx.x * PLC_PRED_REC;
+    const int s = rec[0], flags = rec[1], fec_row = rec[2];
+    const float a1 = __int_as_float(rec[3]), a2 = __int_as_float(rec[4]);
+    const int G = P.g1 + P.g2;
+    float *net = D.net + (size_t)s * 4 * G;
+    const int restore = (flags >> PLC_F_RESTORE_SHIFT) & 3, input = (flags >> PLC_F_INPUT_SHIFT) & 3;
+    for (int t = threadIdx.x; t < G; t += blockDim.x) {
+        float v0 = net[t];
+        if (flags & PLC_F_ROT) {
+            const float v1 = net[G + t], v2 = net[2 * G + t];
+            net[G + t] = v0; net[2 * G + t] = v1; net[3 * G + t] = v2;
+        }
+        if (restore) { v0 = net[(restore + 1) * G + t]; net[t] = v0; }
+        if (t < P.g1) { h1[t] = v0; ((unsigned char *)s1q)[t] = (unsigned char)quant_s8(v0); }
+        else { h2[t - P.g1] = v0; ((unsigned char *)s2q)[t - P.g1] = (unsigned char)quant_s8(v0); }
+    }
+    if (!(flags & PLC_F_COMPUTE)) return;
+    float *feat = D.feat + (size_t)s * LPCN_NB_FEAT;
+    const float *fec = D.fec + ((size_t)s * LPCN_PLC_MAX_FEC + fec_row) * LPCN_NB_FEAT;
+    if (threadIdx.x < LPCN_PLC_IN) {
+        const int j = threadIdx.x;
+        float v = 0.f;
+        if (input >= PLC_IN_BURG && j < 2 * LPCN_NB_BANDS) v = D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j];
+        if (j >= 2 * LPCN_NB_BANDS && j < LPCN_PLC_IN - 1) {
+            if (input == PLC_IN_FEC) v = fec[j - 2 * LPCN_NB_BANDS];
+            if (input == PLC_IN_BURG_FEAT) v = D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS];
+        }
+        if (j == LPCN_PLC_IN - 1) v = input == PLC_IN_FEC ? -1.f : input == PLC_IN_ZEROS ? 0.f : 1.f;
+        if (flags & PLC_F_RAW) v = j < 2 * LPCN_NB_BANDS ? D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j] : j < LPCN_PLC_IN - 1 ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS] : a1;
+        in[j] = v;
+    }
+    __syncthreads();
+    // _lpcnet_compute_dense (src/nnet.c:122-135), tanh: float in both builds; its output is read as GRU 1's quantised input only
+    for (int i = threadIdx.x; i < P.d1; i += blockDim.x) {
+        float acc = P.dense1_b[i];
+        for (int j = 0; j < LPCN_PLC_IN; ++j) acc = acc + P.dense1_w[(size_t)j * P.d1 + i] * in[j];
+        ((unsigned char *)xq)[i] = (unsigned char)quant_s8(lpcn_tanh(acc, P.tansig));
+    }
+    __syncthreads();
+    plc_gru_i8(P.g1, P.gru1_w, P.gru1_start, P.gru1_pos, P.gru1_rec, P.gru1_bias, xq, s1q, h1, (unsigned char *)xq, P.tansig);
+    plc_gru_i8(P.g2, P.gru2_w, P.gru2_start, P.gru2_pos, P.gru2_rec, P.gru2_bias, xq, s2q, h2, nullptr, P.tansig);
     if (threadIdx.x < LPCN_NB_FEAT) {
         const int i = threadIdx.x;
         float acc = P.out_b[i];

@@ -109,6 +109,7 @@ struct LpcnSampleArgs {
 #define LPCN_DBG_STRIDE 1600    // floats per (sample) trace record: hA 384, hB 16, exc,sig,pred,pcm,pred, leader clocks barrier->publish, the tree's own decision; [448..1600) GRU-A pre-activations
 
 #include "sample_common.hip.h"
+#include "quant_i8.hip.h"
 
 namespace lpcn {
 
@@ -177,19 +178,7 @@ template <int SEL> __device__ __forceinline__ float fmac_quad(float acc, const f
     return acc;
 }
 
-// int8 (DOT_PROD) arithmetic of the reference's generic-C build, src/vec.h:274-339:
-//   x_q = (signed char)(int)floor(.5 + 127*x)   (float product, double sum)
-//   out = out*(128*127);  out += (w0*x0 + w1*x1 + w2*x2 + w3*x3) per block (exact integer);  out *= 1/128/127
-constexpr float QS = 128.f * 127.f, QS1 = 1.f / 128.f / 127.f;
-__device__ __forceinline__ int quant_s8(float x)
-{
-    const float t = 127.f * x;
-    // floor(.5 + t) as ONE instruction, v_cvt_rpi_i32_f32 (round to nearest, ties toward +infinity): == (int)floor(.5 + (double)t) for every finite t
-    // (lpcnet_hip_quant_sweep_device: all 2^32 bit patterns on the device)
-    int q;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(q) : "v"(t));
-    return q & 0xFF;
-}
+// (QS, QS1 and quant_s8 -- the int8 arithmetic's scales and re-quantisation -- live in quant_i8.hip.h, shared with the PLC network)
 // Integer dot products converted to float.  v_dot4_i32_i8 with a literal-zero accumulator saves the
 // v_mov the compiler's v_dot4c selection needs, but the hazard recogniser cannot see inside inline
 // asm: gfx90a+ requires 3 wait states between a DOT write and a different VALU op reading the
