@@ -188,6 +188,14 @@ LPCNET_EXPORT int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, co
  * sequence depends on the loss flags, so on a stream that is being captured the call returns LPCNET_HIP_E_ARG and enqueues nothing.
  * plc_fec_add(features20 == NULL) is lpcnet_plc_fec_add(st, NULL): one skip.  With a full ring (100 vectors, none consumed) the vector is
  *   dropped as in the reference and the call returns 1.  fec_add waits for the batch's enqueued work.
+ * plc_fec_feed is every stream's FEC traffic in one call and one launch per shard.  Per stream s it is lpcnet_plc_fec_clear(st[s]) if clear[s],
+ *   then skip[s] calls of lpcnet_plc_fec_add(st[s], NULL), then lpcnet_plc_fec_add(st[s], v) for the stream's count[s] vectors in order.  count,
+ *   skip, clear and dropped are host arrays [n_streams] (skip, clear, dropped may be NULL) and are read / written before the call returns;
+ *   features is packed [sum(count)][20], stream 0's vectors first.  dropped[s] receives how many of the stream's vectors the reference would
+ *   drop with "FEC buffer full" (always the tail of its list); the call returns 1 if any were and 0 otherwise, LPCNET_HIP_E_ARG for a negative
+ *   count (nothing has changed then).  plc_fec_feed uploads, enqueues and synchronises (one host thread per shard).  plc_fec_feed_device*
+ *   takes a device pointer and only enqueues on `hip_stream`, like plc_step_device: no wait for enqueued work, LPCNET_HIP_E_ARG on a capturing
+ *   stream (the launch depends on the rings' positions, which the host keeps).  The _shard form covers that shard's streams, in arrays and packing.
  * get / set_plc_state: one stream's PLC state, both halves (layout = struct lpcn_plc_state_rec in lpcnet_amd/csrc/lpcnet_engine.h); with the
  *   synthesis state (get / set_raw_state) and the analysis state it is a snapshot a stream can be rolled back to. */
 #ifndef LPCNET_PLC_CAUSAL
@@ -204,6 +212,11 @@ LPCNET_EXPORT int lpcnet_batch_plc_step_device(LPCNetBatch *b, short *d_pcm, con
 LPCNET_EXPORT int lpcnet_batch_plc_step_device_shard(LPCNetBatch *b, int shard, short *d_pcm, const unsigned char *lost, void *hip_stream);
 LPCNET_EXPORT int lpcnet_batch_plc_fec_add(LPCNetBatch *b, int stream, const float *features20);
 LPCNET_EXPORT int lpcnet_batch_plc_fec_clear(LPCNetBatch *b, int stream);
+LPCNET_EXPORT int lpcnet_batch_plc_fec_feed(LPCNetBatch *b, const float *features, const int *count, const int *skip, const unsigned char *clear, int *dropped);
+LPCNET_EXPORT int lpcnet_batch_plc_fec_feed_device(LPCNetBatch *b, const float *d_features, const int *count, const int *skip, const unsigned char *clear,
+                                                   int *dropped, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_plc_fec_feed_device_shard(LPCNetBatch *b, int shard, const float *d_features, const int *count, const int *skip,
+                                                         const unsigned char *clear, int *dropped, void *hip_stream);
 LPCNET_EXPORT int lpcnet_batch_plc_state_size(void);
 LPCNET_EXPORT int lpcnet_batch_get_plc_state(LPCNetBatch *b, int stream, void *out);
 LPCNET_EXPORT int lpcnet_batch_set_plc_state(LPCNetBatch *b, int stream, const void *in);
@@ -215,6 +228,10 @@ LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float
  * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
  * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */
 LPCNET_EXPORT int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary);
+/* plc_fec_feed's planner alone, no device (tests): ctl [n][9] in and out, count [n], skip / clear [n] or NULL, dropped [n] or NULL; rec [n][8] out,
+ * one record per stream that stores something: {stream, first row of the packed vectors, rows a, ring row they go to, first ring row moved to the
+ * front, rows moved, rows b appended after the move, ring row they go to}.  Returns the number of records, or LPCNET_HIP_E_ARG. */
+LPCNET_EXPORT int lpcnet_hip_plc_fec_feed_plan(int n, int *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped);
 /* a blob's PLC network as the loader sees it, no device: info[7] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or inconsistent),
  * servable (plc_enable accepts the blob), dense width, GRU widths, 8x4 blocks of the two GRU input matrices}.  Returns 0, LPCNET_HIP_E_ARG without
  * `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */

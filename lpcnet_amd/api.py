@@ -51,6 +51,33 @@ def plc_plan(options: int, ctl: np.ndarray, lost, fec_op=None):
     return out
 
 
+PLC_FEED_REC = 8
+
+
+def plc_fec_feed_plan(ctl: np.ndarray, count, skip=None, clear=None):
+    """plc_fec_feed's host planner alone (no device): advances the ring positions of ctl [n][9] int32 in place and returns (records [k][8]: stream,
+    first row of the packed vectors, rows a, their ring row, first ring row moved to the front, rows moved, rows b, their ring row; dropped [n])"""
+    L = load_library()
+    assert ctl.dtype == np.int32 and ctl.ndim == 2 and ctl.shape[1] == 9 and ctl.flags.c_contiguous
+    n = ctl.shape[0]
+    count, skip, clear = _feed_args(n, count, skip, clear)
+    rec = np.zeros((n, PLC_FEED_REC), np.int32)
+    dropped = np.zeros(n, np.int32)
+    rc = L.lpcnet_hip_plc_fec_feed_plan(n, ctl.ctypes.data, count.ctypes.data, None if skip is None else skip.ctypes.data,
+                                        None if clear is None else clear.ctypes.data, rec.ctypes.data, dropped.ctypes.data)
+    if rc < 0:
+        raise LPCNetError("plc_fec_feed_plan failed (%d): %s" % (rc, last_error()))
+    return rec[:rc].copy(), dropped
+
+
+def _feed_args(n, count, skip, clear):
+    count = np.ascontiguousarray(count, np.int32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.int32)
+    clear = None if clear is None else np.ascontiguousarray(clear, np.uint8)
+    assert count.shape == (n,) and (skip is None or skip.shape == (n,)) and (clear is None or clear.shape == (n,))
+    return count, skip, clear
+
+
 def load_library():
     """dlopen liblpcnet_hip.so (built by `python -m lpcnet_amd.build`).  Raises if it is absent:
     the product path never falls back to a CPU implementation."""
@@ -132,6 +159,10 @@ def load_library():
     L.lpcnet_batch_plc_step_device_shard.argtypes = [vp, C.c_int, vp, _u8p, vp]
     L.lpcnet_batch_plc_fec_add.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_plc_fec_clear.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_plc_fec_feed.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_plc_fec_feed_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_plc_fec_feed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.lpcnet_hip_plc_fec_feed_plan.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_get_plc_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_plc_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_plc_burg.argtypes = [vp, _f32p, _f32p]
@@ -523,6 +554,38 @@ class LPCNetBatch:
 
     def plc_fec_clear(self, stream: int):
         self._chk(self.L.lpcnet_batch_plc_fec_clear(self.p, stream), "plc_fec_clear")
+
+    def plc_fec_feed(self, features, count, skip=None, clear=None) -> np.ndarray:
+        """every stream's FEC traffic in one call: per stream lpcnet_plc_fec_clear if clear[s], skip[s] skips, then its count[s] vectors.  features is
+        [sum(count)][20] float32, stream 0's vectors first, or a list of per-stream [k][20] arrays.  Returns dropped [n]: how many of each stream's
+        vectors (the last ones) found the ring full"""
+        count, skip, clear = _feed_args(self.n, count, skip, clear)
+        if isinstance(features, (list, tuple)):
+            assert len(features) == self.n
+            rows = [np.asarray(f, np.float32).reshape(-1, 20) for f in features]
+            assert [len(r) for r in rows] == count.tolist()
+            features = np.concatenate(rows) if rows else np.zeros((0, 20), np.float32)
+        f = np.ascontiguousarray(features, np.float32).reshape(-1, 20)
+        assert (count < 0).any() or f.shape[0] == int(count.sum())
+        dropped = np.zeros(self.n, np.int32)
+        rc = self.L.lpcnet_batch_plc_fec_feed(self.p, f.ctypes.data, count.ctypes.data, None if skip is None else skip.ctypes.data,
+                                              None if clear is None else clear.ctypes.data, dropped.ctypes.data)
+        if rc < 0:
+            self._chk(rc, "plc_fec_feed")
+        return dropped
+
+    def plc_fec_feed_device(self, d_features_ptr: int, count, skip=None, clear=None, hip_stream: int = 0, shard=None) -> np.ndarray:
+        """enqueue only: d_features [sum(count)][20] float32 on the device; count, skip, clear stay host arrays (of the shard's streams with shard=k).
+        Returns dropped, as plc_fec_feed does"""
+        n = self.n if shard is None else self.shards[shard][1]
+        count, skip, clear = _feed_args(n, count, skip, clear)
+        dropped = np.zeros(n, np.int32)
+        args = (d_features_ptr, count.ctypes.data, None if skip is None else skip.ctypes.data, None if clear is None else clear.ctypes.data,
+                dropped.ctypes.data, hip_stream)
+        rc = self.L.lpcnet_batch_plc_fec_feed_device(self.p, *args) if shard is None else self.L.lpcnet_batch_plc_fec_feed_device_shard(self.p, shard, *args)
+        if rc < 0:
+            self._chk(rc, "plc_fec_feed_device")
+        return dropped
 
     def get_plc_state(self, stream: int) -> bytes:
         buf = C.create_string_buffer(self.L.lpcnet_batch_plc_state_size())

@@ -1063,11 +1063,12 @@ int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
  * device and stream; with a single shard the work runs on the calling thread. */
 typedef struct {
     LPCNetBatch *b; int shard;
-    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze, 3 encode, 4 compute_features, 5 PLC step */
+    int kind;                                     /* 0 synthesize(preload), 1 decode, 2 analyze, 3 encode, 4 compute_features, 5 PLC step, 6 FEC feed */
     const float *features; int feat_stride; short *pcm; int n_frames, preload;
     const void *an_pcm; int an_is_float; float *an_features;
     const unsigned char *packets; int n_packets;
     unsigned char *enc_packets;
+    const int *fec_count, *fec_skip, *fec_vec0; int *fec_dropped;      /* FEC feed: fec_vec0[k] = shard k's first row of the packed vectors; packets = clear */
     int rc; char err[256];
 } shard_job;
 
@@ -1088,6 +1089,10 @@ static void *shard_worker(void *arg)
                                            j->kind == 4 ? j->an_features + o * 4 * j->feat_stride : NULL, j->feat_stride, j->n_packets);
     } else if (j->kind == 5)
         j->rc = lpcn_batch_dev_plc_step_host(s->dev, j->pcm + (size_t)s->first * LPCN_FRAME_SIZE, j->packets + s->first);      /* (packets = the loss flags) */
+    else if (j->kind == 6)
+        j->rc = lpcn_batch_dev_plc_fec_feed_host(s->dev, j->features ? j->features + (size_t)j->fec_vec0[j->shard] * LPCN_NB_FEAT : NULL, j->fec_count + s->first,
+                                                 j->fec_skip ? j->fec_skip + s->first : NULL, j->packets ? j->packets + s->first : NULL,
+                                                 j->fec_dropped ? j->fec_dropped + s->first : NULL);
     else
         j->rc = lpcn_batch_dev_decode_host(s->dev, j->packets + (size_t)s->first * j->n_packets * 8,
                                            j->pcm + (size_t)s->first * j->n_packets * 4 * LPCN_FRAME_SIZE, j->n_packets);
@@ -1104,7 +1109,8 @@ static int run_shards(LPCNetBatch *b, const shard_job *proto)
     for (int k = 1; k < b->n_shards; k++) started[k] = pthread_create(&th[k], NULL, shard_worker, &job[k]) == 0;
     shard_worker(&job[0]);
     for (int k = 1; k < b->n_shards; k++) { if (started[k]) pthread_join(th[k], NULL); else shard_worker(&job[k]); }
-    for (int k = 0; k < b->n_shards; k++) if (job[k].rc) { set_err(job[k].err); return job[k].rc; }
+    for (int k = 0; k < b->n_shards; k++) if (job[k].rc < 0) { set_err(job[k].err); return job[k].rc; }
+    for (int k = 0; k < b->n_shards; k++) if (job[k].rc) { set_err(job[k].err); return job[k].rc; }      /* (an FEC feed's 1: vectors were dropped) */
     return 0;
 }
 
@@ -1317,6 +1323,40 @@ int lpcnet_batch_plc_fec_clear(LPCNetBatch *b, int stream)
     SHARD_OF(s, b, stream);
     FWD(lpcn_batch_dev_plc_fec_clear(s->dev, stream - s->first));
 }
+/* every stream's FEC traffic in one call (include/lpcnet_batch.h) */
+int lpcnet_batch_plc_fec_feed(LPCNetBatch *b, const float *features, const int *count, const int *skip, const unsigned char *clear, int *dropped)
+{
+    NEED_PLC_ON(b);
+    if (!count) { set_err("lpcnet_batch_plc_fec_feed: bad arguments"); return LPCN_E_ARG; }
+    int vec0[LPCN_MAX_SHARDS];
+    long long total = 0;
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard's rings change) */
+        const batch_shard *s = &b->sh[k];
+        vec0[k] = (int)total;
+        for (int i = s->first; i < s->first + s->count; i++) {
+            if (count[i] < 0 || (skip && skip[i] < 0)) { set_err("lpcnet_batch_plc_fec_feed: negative count"); return LPCN_E_ARG; }
+            if ((total += count[i]) > 0x7fffffff) { set_err("lpcnet_batch_plc_fec_feed: more than 2^31 - 1 vectors"); return LPCN_E_ARG; }
+        }
+    }
+    if (total && !features) { set_err("lpcnet_batch_plc_fec_feed: bad arguments"); return LPCN_E_ARG; }
+    shard_job j; memset(&j, 0, sizeof(j));
+    j.kind = 6; j.features = features; j.fec_count = count; j.fec_skip = skip; j.packets = clear; j.fec_dropped = dropped; j.fec_vec0 = vec0;
+    return run_shards(b, &j);
+}
+int lpcnet_batch_plc_fec_feed_device_shard(LPCNetBatch *b, int shard, const float *d_features, const int *count, const int *skip, const unsigned char *clear,
+                                           int *dropped, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !count) { set_err("lpcnet_batch_plc_fec_feed_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_plc_fec_feed(b->sh[shard].dev, d_features, count, skip, clear, dropped, hip_stream));
+}
+int lpcnet_batch_plc_fec_feed_device(LPCNetBatch *b, const float *d_features, const int *count, const int *skip, const unsigned char *clear, int *dropped,
+                                     void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_plc_fec_feed_device");
+    return lpcnet_batch_plc_fec_feed_device_shard(b, 0, d_features, count, skip, clear, dropped, hip_stream);
+}
 int lpcnet_batch_plc_state_size(void) { return (int)sizeof(lpcn_plc_state_rec); }
 int lpcnet_batch_get_plc_state(LPCNetBatch *b, int stream, void *out)
 {
@@ -1368,6 +1408,15 @@ int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost,
         else if (fec_op[s] == 4) { (void)lpcn_plc_ctl_fec_add(&c[s], 0); (void)lpcn_plc_ctl_fec_add(&c[s], 0); }
     }
     FWD(lpcn_plc_plan(options, n, c, lost, summary));
+}
+/* the FEC feed's planner alone (no device): ctl as above, count [n], skip / clear [n] or NULL, rec [n][8] out (one record per stream that stores
+ * something: stream, first source row, rows a, their ring row, move-from row, rows moved, rows b, their ring row), dropped [n] or NULL.  Returns
+ * the number of records. */
+int lpcnet_hip_plc_fec_feed_plan(int n, int *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped)
+{
+    const int rc = lpcn_plc_fec_feed_plan(n, (lpcn_plc_ctl *)ctl, count, skip, clear, rec, dropped);
+    if (rc < 0) take_engine_err();
+    return rc;
 }
 
 /* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */

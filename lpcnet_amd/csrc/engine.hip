@@ -144,6 +144,10 @@ struct lpcn_plc_host {
     Event ev_ctl;                                   // the upload of the previous step's lists has left h_ctl
     bool ctl_pending = false;
     PlcPlan plan;
+    DevBuf<int> d_feed;                             // a batched FEC feed's records (their pinned source: h_ctl past the step's lists, so that a feed
+    Event ev_feed;                                  //   and a step never wait for each other's upload) and "the previous feed's have left it"
+    bool feed_pending = false;
+    DevBuf<float> d_feed_src;                       //   ... and the host-pointer call's packed vectors, grown to the largest call
 };
 
 struct lpcn_batch_dev {
@@ -1629,9 +1633,9 @@ extern "C" int lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options)
             (rc = p->delta.alloc(n)) || (rc = p->fec.alloc(n * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT)) || (rc = p->fbuf.alloc(n * LPCN_PLC_FBUF * LPCN_NB_FEAT)) ||
             (rc = p->lp.alloc(n * LPCN_FRAME_SIZE)) || (rc = p->burg.alloc(n * 2 * LPCN_NB_BANDS)) || (rc = p->an.alloc(n * LPCN_AN_NB_FEATURES)) ||
             (rc = p->d_pcm.alloc(n * LPCN_FRAME_SIZE)) || (rc = p->d_ident.alloc(n)) || (rc = p->d_ctl.alloc(64 * n + 64)) ||
-            (rc = p->h_ctl.reserve(sizeof(int) * p->d_ctl.cap)) || (rc = group_alloc(b))) return rc;
+            (rc = p->d_feed.alloc(lpcn::PLC_FEED_REC * n)) || (rc = p->h_ctl.reserve(sizeof(int) * (p->d_ctl.cap + p->d_feed.cap))) || (rc = group_alloc(b))) return rc;
         p->D = {p->q, p->feat, p->net, p->dc, p->delta, p->fec, p->fbuf, p->lp, p->burg, p->an};
-        if (hipEventCreateWithFlags(&p->ev_ctl.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipEventCreate failed"); return LPCN_E_HIP; }
+        if (hipEventCreateWithFlags(&p->ev_ctl.e, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&p->ev_feed.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: hipEventCreate failed"); return LPCN_E_HIP; }
         std::vector<int> ident(n);
         for (size_t i = 0; i < n; ++i) ident[i] = (int)i;
         if (hipMemcpy(p->d_ident, ident.data(), sizeof(int) * n, hipMemcpyHostToDevice) != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC: upload failed"); return LPCN_E_HIP; }
@@ -1754,6 +1758,65 @@ extern "C" int lpcn_batch_dev_plc_fec_clear(lpcn_batch_dev *b, int s)
     lpcn_plc_ctl &c = b->plc->ctl[s];
     c.fec_keep = c.fec_read = c.fec_fill = c.fec_skip = 0;      // src/lpcnet_plc.c:129-131
     return 0;
+}
+
+// lpcnet_plc_fec_clear / lpcnet_plc_fec_add for every stream in one call (plc_plan.h: plc_fec_feed_plan): the host plans every ring's rows from
+// the control state, the records go up through the pinned list buffer and one launch moves the vectors.  Enqueue only; count, skip, clear and
+// dropped are host arrays, d_features the packed vectors on the device.  Returns 1 when a vector was dropped ("FEC buffer full").
+extern "C" int lpcn_plc_fec_feed_plan(int n, lpcn_plc_ctl *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped)
+{
+    if (n < 1 || !ctl || !count || !rec) { snprintf(g_err, sizeof(g_err), "bad FEC feed plan arguments"); return LPCN_E_ARG; }
+    return plc_fec_feed_plan(n, ctl, count, skip, clear, rec, dropped, nullptr, g_err, sizeof(g_err));
+}
+
+extern "C" int lpcn_batch_dev_plc_fec_feed(lpcn_batch_dev *b, const float *d_features, const int *count, const int *skip, const unsigned char *clear,
+                                           int *dropped, void *hip_stream)
+{
+    NEED_PLC(b);
+    bool vectors = false;
+    for (int s = 0; count && s < b->n; ++s) vectors |= count[s] > 0;
+    if (!count || (vectors && !d_features)) { snprintf(g_err, sizeof(g_err), "bad FEC feed arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    lpcn_plc_host *p = b->plc.get();
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
+    if (stream_is_capturing(st)) {
+        snprintf(g_err, sizeof(g_err), "an FEC feed cannot be captured: its launch depends on the rings' positions"); return LPCN_E_ARG;
+    }
+    if (p->feed_pending) { HIP_TRY(hipEventSynchronize(p->ev_feed)); p->feed_pending = false; }      // (the previous feed's records have left the pinned buffer)
+    int *h_rec = (int *)p->h_ctl.p + p->d_ctl.cap, any = 0;
+    const int n_rec = plc_fec_feed_plan(b->n, p->ctl.data(), count, skip, clear, h_rec, dropped, &any, g_err, sizeof(g_err));
+    if (n_rec < 0) return n_rec;
+    if (any) snprintf(g_err, sizeof(g_err), "FEC buffer full");      // (the reference prints this and drops the vector)
+    if (n_rec == 0) return any;
+    { int rco = order_begin(b, st); if (rco) return rco; }
+    HIP_TRY(hipMemcpyAsync(p->d_feed, h_rec, sizeof(int) * lpcn::PLC_FEED_REC * (size_t)n_rec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(p->ev_feed, st));
+    p->feed_pending = true;
+    hipLaunchKernelGGL(lpcn::plc_fec_feed_kernel, dim3(n_rec), dim3(lpcn::PLC_FEED_THREADS), 0, st, (const int *)p->d_feed, n_rec, d_features, p->D.fec);
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "FEC feed: kernel launch failed"); return LPCN_E_HIP; }
+    { int rco = order_end(b, st); if (rco) return rco; }
+    return any;
+}
+
+extern "C" int lpcn_batch_dev_plc_fec_feed_host(lpcn_batch_dev *b, const float *features, const int *count, const int *skip, const unsigned char *clear, int *dropped)
+{
+    NEED_PLC(b);
+    if (!count) { snprintf(g_err, sizeof(g_err), "bad FEC feed arguments"); return LPCN_E_ARG; }
+    size_t total = 0;
+    for (int s = 0; s < b->n; ++s) {
+        if (count[s] < 0) { snprintf(g_err, sizeof(g_err), "FEC feed: stream %d has a negative count", s); return LPCN_E_ARG; }
+        total += (size_t)count[s];
+    }
+    if (total && !features) { snprintf(g_err, sizeof(g_err), "bad FEC feed arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    lpcn_plc_host *p = b->plc.get();
+    hipStream_t st = b->e->stream;
+    int rc = p->d_feed_src.reserve(b, total * LPCN_NB_FEAT);
+    if (rc) return rc;
+    if (total) HIP_TRY(hipMemcpyAsync(p->d_feed_src, features, sizeof(float) * total * LPCN_NB_FEAT, hipMemcpyHostToDevice, st));
+    if ((rc = lpcn_batch_dev_plc_fec_feed(b, p->d_feed_src, count, skip, clear, dropped, st)) < 0) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
 }
 
 // one stream's record, both halves: the device arrays' part field by field, down into *h or up from it

@@ -341,6 +341,12 @@ int  lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned cha
 int  lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const unsigned char *lost);
 int  lpcn_batch_dev_plc_fec_add(lpcn_batch_dev *b, int stream, const float *features20);
 int  lpcn_batch_dev_plc_fec_clear(lpcn_batch_dev *b, int stream);
+/* every stream's FEC traffic in one call: clear[s], then skip[s] NULL adds, then count[s] vectors of the packed [sum(count)][20] features (host arrays
+ * [n]; skip, clear, dropped may be NULL).  0, or 1 when vectors were dropped (dropped[s]: how many, the tail of the stream's list).  The device form only
+ * enqueues (not on a capturing stream); _plan is the planner alone: ctl in and out, rec [n][8] out, returns the number of records. */
+int  lpcn_batch_dev_plc_fec_feed(lpcn_batch_dev *b, const float *d_features, const int *count, const int *skip, const unsigned char *clear, int *dropped, void *hip_stream);
+int  lpcn_batch_dev_plc_fec_feed_host(lpcn_batch_dev *b, const float *features, const int *count, const int *skip, const unsigned char *clear, int *dropped);
+int  lpcn_plc_fec_feed_plan(int n, lpcn_plc_ctl *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped);
 int  lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int stream, lpcn_plc_state_rec *host);
 int  lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int stream, const lpcn_plc_state_rec *host);
 int  lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, float *ceps36);

@@ -533,4 +533,32 @@ __global__ __launch_bounds__(256) void plc_fec_move_kernel(float *ring, int keep
     }
 }
 
+// A batched FEC feed (plc_plan.h: plc_fec_feed_plan): one workgroup per record {stream, first source row, a, ring row, move-from row, rows
+// moved, b, ring row}.  `a` rows of the packed source go into the stream's ring; then, if the call compacts the ring, rows [from, from + rows)
+// move to the front -- the rows just appended among them, so the move waits for them -- and `b` more rows follow.  The move overlaps itself
+// and is staged through LDS whole.  Ring rows are 80 bytes from a 16-byte-aligned base, so the move goes in float4; the source is the caller's
+// pointer with whatever alignment it has and a record copies a few rows of it, in single floats.
+constexpr int PLC_FEED_THREADS = 256;
+__global__ __launch_bounds__(PLC_FEED_THREADS) void plc_fec_feed_kernel(const int *recs, int cnt, const float *src, float *fec)
+{
+    __shared__ float4 stage[LPCN_PLC_MAX_FEC * LPCN_NB_FEAT / 4];
+    if ((int)blockIdx.x >= cnt) return;
+    const int *rec = recs + (size_t)blockIdx.x * PLC_FEED_REC;
+    const int s = rec[0], a = rec[2], at_a = rec[3], from = rec[4], rows = rec[5], b = rec[6], at_b = rec[7];
+    const int t = threadIdx.x;
+    float *ring = fec + (size_t)s * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT;
+    const float *v = src + (size_t)rec[1] * LPCN_NB_FEAT;
+    for (int k = t; k < a * LPCN_NB_FEAT; k += PLC_FEED_THREADS) ring[at_a * LPCN_NB_FEAT + k] = v[k];
+    if (rows > 0) {      // (the record's choice: the whole workgroup takes it)
+        __syncthreads();
+        const float4 *in4 = (const float4 *)(ring + from * LPCN_NB_FEAT);
+        float4 *out4 = (float4 *)ring;
+        for (int k = t; k < rows * (LPCN_NB_FEAT / 4); k += PLC_FEED_THREADS) stage[k] = in4[k];
+        __syncthreads();
+        for (int k = t; k < rows * (LPCN_NB_FEAT / 4); k += PLC_FEED_THREADS) out4[k] = stage[k];
+        __syncthreads();
+    }
+    for (int k = t; k < b * LPCN_NB_FEAT; k += PLC_FEED_THREADS) ring[at_b * LPCN_NB_FEAT + k] = v[a * LPCN_NB_FEAT + k];      // (b > 0 after a move of no rows: keep == 100)
+}
+
 }  // namespace lpcn

@@ -41,6 +41,46 @@ extern "C" int lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null)      // src/lp
     return moved;
 }
 
+int plc_fec_feed_plan(int n, lpcn_plc_ctl *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped, int *any_dropped,
+                      char *err, size_t err_len)
+{
+    long long total = 0;
+    for (int s = 0; s < n; ++s) {      // (everything is checked before anything changes)
+        const lpcn_plc_ctl &c = ctl[s];
+        if (count[s] < 0 || (skip && skip[s] < 0)) { snprintf(err, err_len, "FEC feed: stream %d has a negative count", s); return LPCN_E_ARG; }
+        if (c.fec_keep < 0 || c.fec_keep > c.fec_read || c.fec_read > c.fec_fill || c.fec_fill > LPCN_PLC_MAX_FEC || c.fec_skip < 0 ||
+            (skip && skip[s] > 0x7fffffff - c.fec_skip)) {
+            snprintf(err, err_len, "stream %d: inconsistent PLC control state", s); return LPCN_E_ARG;
+        }
+        if ((total += count[s]) > 0x7fffffff) { snprintf(err, err_len, "FEC feed: more than 2^31 - 1 vectors"); return LPCN_E_ARG; }
+    }
+    int n_rec = 0, off = 0, any = 0;
+    for (int s = 0; s < n; ++s) {
+        lpcn_plc_ctl &c = ctl[s];
+        if (clear && clear[s]) c.fec_keep = c.fec_read = c.fec_fill = c.fec_skip = 0;      // src/lpcnet_plc.c:130-132
+        if (skip) c.fec_skip += skip[s];
+        int left = count[s];
+        const int room = LPCN_PLC_MAX_FEC - c.fec_fill, a = left < room ? left : room, at_a = c.fec_fill;
+        c.fec_fill += a; left -= a;
+        int from = 0, rows = 0, b = 0, at_b = 0;
+        if (left > 0 && c.fec_keep > 0) {      // the ring is full and has rows to give up: :116-125, once
+            from = c.fec_keep; rows = LPCN_PLC_MAX_FEC - from; at_b = rows;
+            b = left < from ? left : from;
+            c.fec_read -= from; c.fec_keep = 0; c.fec_fill = rows + b;
+            left -= b;
+        }
+        if (dropped) dropped[s] = left;      // "FEC buffer full", :117-120
+        any |= left > 0;
+        if (a + b > 0) {
+            const int r[PLC_FEED_REC] = {s, off, a, at_a, from, rows, b, at_b};
+            memcpy(rec + (size_t)n_rec++ * PLC_FEED_REC, r, sizeof(r));
+        }
+        off += count[s];
+    }
+    if (any_dropped) *any_dropped = any;
+    return n_rec;
+}
+
 static void plc_emit(PlcPlan &P, int type, int op, const std::vector<int> &recs, int rec_size)
 {
     if (recs.empty()) return;

@@ -29,3 +29,14 @@ inline int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
 // One step of every stream's control state, and the launches it takes.  summary (may be NULL): LPCN_PLC_SUMMARY ints per stream.
 // Returns 0, or LPCN_E_ARG with the message in err.
 int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len);
+
+// A batched FEC feed (lpcnet_batch_plc_fec_feed): per stream lpcnet_plc_fec_clear if clear[s], skip[s] NULL adds, then count[s] vectors through
+// lpcnet_plc_fec_add (src/lpcnet_plc.c:111-132), planned from the ring positions alone.  A stream's vectors are rows [off, off + count[s]) of the
+// packed source, off the sum of the counts before it.  The ring takes a = min(count, 100 - fill) rows at row fill; if vectors remain and
+// keep > 0 the one compaction a call can cause follows (rows [keep, 100) to the front: keep grows in steps, not in adds), then up to keep more
+// rows; the rest -- always the tail of the stream's list -- is dropped.  One record of PLC_FEED_REC ints per stream that stores something, in
+// stream order: {stream, off, a, fill, keep, 100 - keep, b, 100 - keep}, the last four 0 without a compaction.  skip and clear may be NULL,
+// dropped too ([n] otherwise).  Returns the number of records, or LPCN_E_ARG (negative count or skip, a total beyond INT_MAX, ring positions
+// out of order) with ctl untouched; *any_dropped (may be NULL) says whether a vector was dropped.
+int plc_fec_feed_plan(int n, lpcn_plc_ctl *ctl, const int *count, const int *skip, const unsigned char *clear, int *rec, int *dropped, int *any_dropped,
+                      char *err, size_t err_len);

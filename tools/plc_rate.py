@@ -10,6 +10,15 @@ drains, are listed one by one).  Each random-loss figure is the median, minimum 
 share of steps that had no lost stream at all.  Beside them: one frame of analyze_device on the same batch, the cost the loss-free step is
 compared with.  --int8 builds the int8 test model (int8 sample kernels and the int8 PLC network) instead of the float one.  One process; the tool stops at the first failure.  Run it under a time limit:
     timeout -k 10 900 python tools/plc_rate.py profiles/plc_rate.json
+
+    python tools/plc_rate.py --fec K [--fec-loop] OUT.json [streams]       (profiles/plc_rate_fec.json holds the runs made for the record)
+
+With --fec K every stream is given K redundancy vectors before each step, in LPCNET_PLC_CODEC mode with 5 % random loss: one
+lpcnet_batch_plc_fec_feed_device on the caller's stream, then the step, timed together and apart with HIP events.  Every stream's ring fills at
+the same step (100 / K steps after the reset) and from then on every feed compacts every ring, so the steps are reported in two windows: while
+the rings fill, and with full rings.  Beside them: the step without any FEC traffic, and the host-pointer feed (lpcnet_batch_plc_fec_feed,
+which uploads and synchronises) by the host's clock.  --fec-loop feeds through the per-stream lpcnet_batch_plc_fec_add instead, one call per
+vector, and times loop + step by the host's clock: what the batched feed replaces.
 """
 import json
 import os
@@ -93,6 +102,95 @@ def measure(out_path, n, int8=False):
         f.write("\n")
 
 
+def fec_windows(K, steps, warm):
+    """step ranges while every ring still fills and after every ring is full (each stream gets K vectors per step from a reset)"""
+    return dict(rings_filling=(warm, min(steps, 95 // K)), rings_full=(min(steps, -(-100 // K) + 10), steps))
+
+
+def measure_fec(out_path, n, K, loop=False, int8=False):
+    import time
+    import torch
+    import plc_synth
+    from lpcnet_amd import api, synth
+    dev = torch.device("cuda:0")
+    b = api.LPCNetBatch(n, synth.blob_bytes(plc_synth.make_model_with_plc(flavour="int8" if int8 else "float")))
+    b.plc_enable(api.PLC_CODEC)
+    b.tune()
+    T = 100
+    base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
+    frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
+    d = torch.zeros((n, 160), dtype=torch.int16, device=dev)
+    rng = np.random.default_rng(7)
+    vec_h = (rng.standard_normal((n * K, 20)) * 0.5).astype(np.float32)
+    vec_h[:, 0] -= 3.0
+    vec = torch.from_numpy(vec_h).to(dev)
+    count = np.full(n, K, np.int32)
+    s = torch.cuda.Stream()
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), streams=n, options="LPCNET_PLC_CODEC", flavour="int8" if int8 else "float",
+                  vectors_per_stream_and_step=K, loss=0.05, feed="per-stream lpcnet_batch_plc_fec_add loop" if loop else "lpcnet_batch_plc_fec_feed_device")
+    steps, warm = (-(-100 // K) + 40, 10) if loop else (-(-100 // K) + 130, 30)
+    with torch.cuda.stream(s):
+        if not loop:
+            ms = []
+            for t in range(30 + 60):
+                d.copy_(frames[t % T])
+                m = step_ms(torch, b, d, (rng.uniform(size=n) < 0.05).astype(np.uint8), s)
+                if t >= 30:
+                    ms.append(m)
+            result["step_without_fec"] = stats(ms)
+            print(json.dumps(result["step_without_fec"]), flush=True)
+            b.plc_reset()
+        rows = []
+        for t in range(steps):
+            lost = (rng.uniform(size=n) < 0.05).astype(np.uint8)
+            d.copy_(frames[t % T])
+            if loop:
+                s.synchronize()
+                t0 = time.perf_counter()
+                for i in range(n):
+                    for k in range(K):
+                        b.plc_fec_add(i, vec_h[i * K + k])
+                t1 = time.perf_counter()
+                b.plc_step_device(d.data_ptr(), lost, s.cuda_stream)
+                s.synchronize()
+                rows.append(((t1 - t0) * 1e3, (time.perf_counter() - t0) * 1e3, 0))
+            else:
+                a, m, e = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                a.record(s)
+                dropped = b.plc_fec_feed_device(vec.data_ptr(), count, hip_stream=s.cuda_stream)
+                m.record(s)
+                b.plc_step_device(d.data_ptr(), lost, s.cuda_stream)
+                e.record(s)
+                e.synchronize()
+                rows.append((a.elapsed_time(m), a.elapsed_time(e), int(dropped.sum())))
+        for name, (lo, hi) in fec_windows(K, steps, warm).items():
+            if hi - lo >= 10:
+                w = rows[lo:hi]
+                result[name] = dict(first_step=lo, feed=stats([r[0] for r in w]), feed_and_step=stats([r[1] for r in w]), dropped_vectors_per_step=float(np.mean([r[2] for r in w])))
+                print(name, json.dumps(result[name]), flush=True)
+        if not loop:          # the host-pointer form with full rings: upload, enqueue, synchronise
+            hs = []
+            for t in range(25):
+                s.synchronize()
+                t0 = time.perf_counter()
+                b.plc_fec_feed(vec_h, count)
+                hs.append((time.perf_counter() - t0) * 1e3)
+            result["host_pointer_feed_rings_full_host_clock"] = stats(hs[5:])
+            print(json.dumps(result["host_pointer_feed_rings_full_host_clock"]), flush=True)
+    b.sync()
+    b.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x != "--int8"]
+    args = [x for x in sys.argv[1:] if x not in ("--int8", "--fec-loop")]
+    if "--fec" in args:
+        i = args.index("--fec")
+        K = int(args[i + 1])
+        del args[i:i + 2]
+        measure_fec(args[0], int(args[1]) if len(args) > 1 else 8192, K, loop="--fec-loop" in sys.argv[1:], int8="--int8" in sys.argv[1:])
+        sys.exit(0)
     measure(args[0], int(args[1]) if len(args) > 1 else 8192, int8="--int8" in sys.argv[1:])
