@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import plc_model as pm  # noqa: E402
 import plc_synth  # noqa: E402
+from plc_run import run  # noqa: E402
 from lpcnet_amd import api, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -34,29 +35,6 @@ def pcm_in(gold):
 
 
 B = pm.BLOCK          # the fixture checks output per block of 10 frames (plc_model.block_crc)
-
-
-def run(b, pcm, lost, t0=0, t1=None, ops=None, vec=None, streams=None):
-    """steps frames [t0, t1) of the given streams' inputs (default: stream i of the batch = stream i of the fixture) -> [n][t1 - t0][160]"""
-    streams = list(range(b.n)) if streams is None else streams
-    t1 = pcm.shape[1] if t1 is None else t1
-    out = np.zeros((b.n, t1 - t0, 160), np.int16)
-    for t in range(t0, t1):
-        if ops is not None:
-            for i, s in enumerate(streams):
-                op = int(ops[t, s])
-                if op in (1, 4):
-                    for k in range(2 if op == 4 else 1):
-                        b.plc_fec_add(i, vec[t, s, k])
-                elif op == 2:
-                    b.plc_fec_add(i, None)
-                elif op == 3:
-                    b.plc_fec_clear(i)
-        lo = np.ascontiguousarray(lost[streams, t])
-        frame = np.ascontiguousarray(pcm[streams, t])
-        frame[lo != 0] = 0
-        out[:, t - t0] = b.plc_step(frame, lo)
-    return out
 
 
 def test_refusals(blob_f32, blob_plc, hip_lib):
@@ -233,6 +211,33 @@ def test_device_pointer_step_and_capture_refusal(gold, blob_plc, pcm_in, hip_lib
         d.add_(0)                                     # (the capture stays usable and is not empty)
     b.sync()
     b.close()
+
+
+def test_device_pointer_step_on_eight_streams_per_workgroup(gold, blob_plc, pcm_in, hip_lib):
+    """the enqueue-only step on a caller's stream with the form pinned (the test above runs whatever tune() measured): the two-group kernel"""
+    import torch
+    lost = pm.loss_patterns()
+    n, T = 12, 40
+    b = api.LPCNetBatch(n, blob_plc)
+    b.streams_per_workgroup = 8
+    b.twelve_waves = 0
+    b.plc_enable(api.PLC_CODEC)
+    d = torch.zeros((n, 160), dtype=torch.int16, device=torch.device("cuda:0"))
+    s = torch.cuda.Stream()
+    out = np.zeros((n, T, 160), np.int16)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        for t in range(T):
+            frame = np.ascontiguousarray(pcm_in[:n, t])
+            frame[lost[:n, t] != 0] = 0
+            d.copy_(torch.from_numpy(frame))
+            b.plc_step_device(d.data_ptr(), lost[:n, t], s.cuda_stream)
+            out[:, t] = d.cpu().numpy()
+    assert b.streams_per_workgroup == 8 and b.twelve_waves == 0
+    b.sync()
+    b.close()
+    bad = np.argwhere(pm.block_crc(out) != gold["pcm_crc"][1][:n, :T // B])
+    assert bad.size == 0, "first differing (stream, block of %d frames) %s of %d" % (B, bad[:6].tolist(), len(bad))
 
 
 def test_a_batch_without_plc_is_as_before(blob_plc, hip_lib):

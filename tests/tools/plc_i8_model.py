@@ -6,7 +6,8 @@
     out *= 1/128/127 -- float32 at every rounding point.  The fixture (tests/golden/golden_plc_i8_v1.npz) pins it to the reference at 128 / 16 / 16;
   * blob_256_i8: the int8 counterpart of plc_model.blob_256 (widths 128 / 256 / 256); blob_wide_i8: widths 128 / 512 / 264, beyond the 256 lanes of
     the kernel's workgroup; model_with_plc: an LPCNet model of one flavour with a small PLC network of another (or the same);
-  * blob_sparse_i8: a 128 / 16 / 16 int8 blob whose GRU 1 input matrix misses whole 8x4 blocks (a row group without any, one with a single block).
+  * blob_sparse_i8: a 128 / 16 / 16 int8 blob whose GRU 1 input matrix misses whole 8x4 blocks (a row group without any, one with a single block);
+  * pred_traces: several streams' input traces through either restatement, one process per stream (the widest networks take ~0.6 s per step).
 """
 import os
 import sys
@@ -118,14 +119,7 @@ def blob_sparse_i8(seed=555):
     return synth.blob_bytes(m)
 
 
-def group_counts(idx, groups):
-    """block counts per row group of an index stream {count, positions...}"""
-    out, p = [], 0
-    for _ in range(groups):
-        out.append(int(idx[p]))
-        p += 1 + out[-1]
-    assert p == len(idx)
-    return out
+group_counts = pm.group_counts
 
 
 class PlcNetNumpyI8:
@@ -178,3 +172,20 @@ class PlcNetNumpyI8:
         v = f32(out[19] + f32(0.1))
         out[19] = f32(0.5) if f32(0.5) < v else v
         return out
+
+
+def _trace_worker(args):
+    blob, int8, xs = args
+    net = (PlcNetNumpyI8 if int8 else pm.PlcNetNumpy)(blob)
+    return np.stack([net.pred(x) for x in xs])
+
+
+def pred_traces(blob, int8, xs):
+    """xs [n][steps][57]: every stream's own input trace through a fresh restatement of the blob's PLC network (float or int8) -> [n][steps][20].
+    The streams run in a pool of processes (spawned, so a parent that already initialised HIP is not forked), one each"""
+    import multiprocessing as mp
+    jobs = [(blob, int8, np.ascontiguousarray(x)) for x in xs]
+    if len(jobs) == 1:
+        return np.stack([_trace_worker(jobs[0])])
+    with mp.get_context("spawn").Pool(min(len(jobs), 8)) as pool:
+        return np.stack(pool.map(_trace_worker, jobs))

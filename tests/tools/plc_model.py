@@ -105,17 +105,32 @@ def fec_loss_patterns(n=N_STREAMS, n_frames=T):
     return L
 
 
-def blob_256(seed=777):
-    """the LPCNet test model with a 128 / 256 / 256 PLC network (the trained PLC model's GRU width, training_tf2/lpcnet_plc.py:65)"""
-    m = synth.make_model()
+def blob_widths(d1, g1, g2, flavour="float", seed=777, block_density=None):
+    """the LPCNet test model of `flavour` with a d1 / g1 / g2 PLC network in the same flavour; block_density as in plc_synth._gru (both GRUs)"""
+    m = synth.make_model(flavour=flavour)
     rng = np.random.default_rng(seed)
-    m.add("plc_dense1_weights", (rng.standard_normal((57, 128)) * 0.1).astype(f32), synth.WEIGHT_TYPE_FLOAT)
-    m.add("plc_dense1_bias", (rng.standard_normal(128) * 0.05).astype(f32), synth.WEIGHT_TYPE_FLOAT)
-    plc_synth._gru(m, "plc_gru1", rng, 128, 256, "float")
-    plc_synth._gru(m, "plc_gru2", rng, 256, 256, "float")
-    m.add("plc_out_weights", (rng.standard_normal((256, 20)) * 0.08).astype(f32), synth.WEIGHT_TYPE_FLOAT)
+    m.add("plc_dense1_weights", (rng.standard_normal((57, d1)) * 0.1).astype(f32), synth.WEIGHT_TYPE_FLOAT)
+    m.add("plc_dense1_bias", (rng.standard_normal(d1) * 0.05).astype(f32), synth.WEIGHT_TYPE_FLOAT)
+    plc_synth._gru(m, "plc_gru1", rng, d1, g1, flavour, block_density)
+    plc_synth._gru(m, "plc_gru2", rng, g1, g2, flavour, block_density)
+    m.add("plc_out_weights", (rng.standard_normal((g2, 20)) * 0.08).astype(f32), synth.WEIGHT_TYPE_FLOAT)
     m.add("plc_out_bias", (rng.standard_normal(20) * 0.2).astype(f32), synth.WEIGHT_TYPE_FLOAT)
     return synth.blob_bytes(m)
+
+
+def blob_256(seed=777):
+    """the LPCNet test model with a 128 / 256 / 256 PLC network (the trained PLC model's GRU width, training_tf2/lpcnet_plc.py:65)"""
+    return blob_widths(128, 256, 256, "float", seed)
+
+
+def group_counts(idx, groups):
+    """block counts per row group of an index stream {count, positions...}"""
+    out, p = [], 0
+    for _ in range(groups):
+        out.append(int(idx[p]))
+        p += 1 + out[-1]
+    assert p == len(idx)
+    return out
 
 
 def blob_arrays(blob):
@@ -328,8 +343,8 @@ def burg_frames():
     return np.stack([np.asarray(x, f32) for x in fr])
 
 
-def pred_inputs(n_steps=40):
-    rng = np.random.default_rng(0x9ED)
+def pred_inputs(n_steps=40, seed=0x9ED):
+    rng = np.random.default_rng(seed)
     x = (rng.standard_normal((n_steps, 57)) * 1.5).astype(f32)
     x[::5] = 0
     x[:, 56] = rng.choice([-1.0, 0.0, 1.0], n_steps).astype(f32)

@@ -10,9 +10,24 @@ from lpcnet_amd import synth
 PLC_IN, PLC_D1, PLC_G1, PLC_G2, NB_FEATURES = 2 * 18 + 20 + 1, 128, 16, 16, 20
 
 
-def _gru(m, name, rng, n_in, n, flavour):
+def block_mask(n_in, n, density):
+    """[n_in / 4][3 n / 8] bool, seeded by the shape alone: which 4 x 8 blocks of a GRU input matrix stay -- each with probability `density`,
+    except that the middle row group keeps none, and from 24 row groups on neither do the first and the last"""
+    rng = np.random.default_rng([n_in, n, 0xB10C])
+    groups = 3 * n // 8
+    mask = rng.uniform(size=(n_in // 4, groups)) < density
+    mask[:, [groups // 2] + ([0, groups - 1] if groups >= 24 else [])] = False
+    return mask
+
+
+def _gru(m, name, rng, n_in, n, flavour, block_density=None):
+    """block_density (optional): keep only the blocks of block_mask(n_in, n, block_density) in the input matrix; the others leave the index list.
+    The default draws and emits exactly what it always did: a dense list"""
     f32 = np.float32
     W, Q = synth._quantize_matrix((rng.standard_normal((n_in, 3 * n)) * 0.08).astype(f32))
+    if block_density is not None:
+        keep = np.repeat(np.repeat(block_mask(n_in, n, block_density), 4, axis=0), 8, axis=1)
+        W, Q = W * keep, Q * keep
     W0, Wq, idx = synth._sparse_blocks(W, Q)
     m.add(name + "_weights", W0 if flavour == "float" else Wq, synth.WEIGHT_TYPE_QWEIGHT)
     m.add(name + "_weights_idx", idx, synth.WEIGHT_TYPE_INT)
