@@ -228,6 +228,14 @@ LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float
  * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
  * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */
 LPCNET_EXPORT int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary);
+/* the planner alone with lanes, no device (tests).  `ctl`, `lost`, `fec_op`, `summary`: as lpcnet_hip_plc_plan.
+ * launch[k] = {type (0 Burg analysis, 1 prediction, 2 element-wise operation, 3 group, 4 the frame analysis), op, lane, slot, cnt, offset of its
+ * records in lists, ints per record, kind (0 frame network, 1 frame network and samples, 2 samples), N, preload}; `lists` receives the control
+ * lists.  With lanes == 1 these are the launches and lists of a PLC step today; launches of different lanes in front of the type-4 launch name
+ * disjoint streams, a group works in rows [slot, slot + cnt) of n, and the rows of different lanes are disjoint.  Returns the number of
+ * launches, or LPCNET_HIP_E_ARG (lanes outside 1 .. 4, an array too short: ctl is unchanged then). */
+LPCNET_EXPORT int lpcnet_hip_plc_plan_lanes(int options, int n, int lanes, int *ctl, const unsigned char *lost, const unsigned char *fec_op,
+                                            int *summary, int *launch, int launch_cap, int *lists, int lists_cap);
 /* plc_fec_feed's planner alone, no device (tests): ctl [n][9] in and out, count [n], skip / clear [n] or NULL, dropped [n] or NULL; rec [n][8] out,
  * one record per stream that stores something: {stream, first row of the packed vectors, rows a, ring row they go to, first ring row moved to the
  * front, rows moved, rows b appended after the move, ring row they go to}.  Returns the number of records, or LPCNET_HIP_E_ARG. */
@@ -250,6 +258,20 @@ LPCNET_EXPORT int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b);
  * whole batch runs now (0 / 1). */
 LPCNET_EXPORT int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode);
 LPCNET_EXPORT int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b);
+/* The group schedule: how the compacted groups of a PLC step or a per-stream step (lpcnet_batch_synthesize_step) are launched.  Off by default.
+ * form: 0 = groups launch in the batch's form (default), 1 = in the cost table's form for the group's own size -- while the streams per
+ *   workgroup are not pinned and the arithmetic is bit-exact, where every form gives the same samples; a pinned value and FAST keep the batch's form.
+ * lanes: 1 (default) .. 4: groups that name disjoint streams are enqueued on up to three streams of the batch's own beside the caller's and
+ *   joined into the caller's stream before the call returns or reaches a launch on the whole batch: the ordering rules above do not change.
+ * LPCNET_HIP_E_ARG otherwise, with the setting unchanged.  Waits for enqueued work.  Every shard gets the same setting; the output does not
+ * depend on it. */
+LPCNET_EXPORT int lpcnet_batch_set_group_schedule(LPCNetBatch *b, int form, int lanes);
+LPCNET_EXPORT int lpcnet_batch_get_group_schedule(const LPCNetBatch *b, int *form, int *lanes);
+/* streams per workgroup a group of cnt streams (1 .. the streams of shard 0) launches with under the present settings (no device work) */
+LPCNET_EXPORT int lpcnet_batch_group_form(const LPCNetBatch *b, int cnt);
+/* the groups of the most recent plc_step / synthesize_step of shard 0:
+ * rec[k] = {lane, slot, cnt, kind, N, preload, streams per workgroup, workgroups}; returns their number (at most `cap` are written) */
+LPCNET_EXPORT int lpcnet_batch_last_groups(const LPCNetBatch *b, int *rec, int cap);
 /* Streams per workgroup are measured on the batch itself (PARITY arithmetic; FAST takes a table value so that its output
  * never depends on timing): lpcnet_batch_tune() does it now, on the engine's own stream (~10 ms).  Without it the first
  * host-pointer call measures; the enqueue-only *_device calls on a caller's stream never do (they use the table value). */

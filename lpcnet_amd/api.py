@@ -51,6 +51,28 @@ def plc_plan(options: int, ctl: np.ndarray, lost, fec_op=None):
     return out
 
 
+PLC_LANES_REC = 10
+
+
+def plc_plan_lanes(options: int, ctl: np.ndarray, lost, lanes: int, fec_op=None):
+    """The PLC's host planner with lanes (no device): advances ctl [n][9] int32 in place by one step and returns (summary [n][10], launches [k][10]:
+    type, op, lane, slot, cnt, offset of its records in the lists, ints per record, kind, N, preload; the control lists)"""
+    L = load_library()
+    assert ctl.dtype == np.int32 and ctl.ndim == 2 and ctl.shape[1] == 9 and ctl.flags.c_contiguous
+    n = ctl.shape[0]
+    lost = np.ascontiguousarray(lost, np.uint8)
+    op = None if fec_op is None else np.ascontiguousarray(fec_op, np.uint8)
+    out = np.zeros((n, PLC_SUMMARY), np.int32)
+    launch = np.zeros((128, PLC_LANES_REC), np.int32)
+    lists = np.zeros(64 * n + 64, np.int32)
+    k = L.lpcnet_hip_plc_plan_lanes(options, n, lanes, ctl.ctypes.data, lost, None if op is None else op.ctypes.data, out.ctypes.data,
+                                    launch.ctypes.data, launch.shape[0], lists.ctypes.data, lists.size)
+    if k < 0:
+        raise LPCNetError("plc_plan_lanes failed (%d): %s" % (k, last_error()))
+    used = max([0] + [int(r[5] + r[4] * r[6]) for r in launch[:k]])
+    return out, launch[:k].copy(), lists[:used].copy()
+
+
 PLC_FEED_REC = 8
 
 
@@ -168,6 +190,11 @@ def load_library():
     L.lpcnet_batch_plc_burg.argtypes = [vp, _f32p, _f32p]
     L.lpcnet_batch_plc_pred.argtypes = [vp, _f32p, _f32p]
     L.lpcnet_hip_plc_plan.argtypes = [C.c_int, C.c_int, vp, _u8p, vp, vp]
+    L.lpcnet_hip_plc_plan_lanes.argtypes = [C.c_int, C.c_int, C.c_int, vp, _u8p, vp, vp, vp, C.c_int, vp, C.c_int]
+    L.lpcnet_batch_set_group_schedule.argtypes = [vp, C.c_int, C.c_int]
+    L.lpcnet_batch_get_group_schedule.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lpcnet_batch_group_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_last_groups.argtypes = [vp, vp, C.c_int]
     L.lpcnet_hip_plc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -719,6 +746,35 @@ class LPCNetBatch:
     @twelve_waves.setter
     def twelve_waves(self, mode):
         self._chk(self.L.lpcnet_batch_set_twelve_waves(self.p, int(mode)), "set_twelve_waves")
+
+    @property
+    def group_schedule(self):
+        """(form, lanes): how the compacted groups of a PLC step / synthesize_step launch (include/lpcnet_batch.h); (0, 1) = off"""
+        f, l = C.c_int(), C.c_int()
+        self._chk(self.L.lpcnet_batch_get_group_schedule(self.p, C.byref(f), C.byref(l)), "get_group_schedule")
+        return f.value, l.value
+
+    @group_schedule.setter
+    def group_schedule(self, form_lanes):
+        form, lanes = form_lanes
+        self._chk(self.L.lpcnet_batch_set_group_schedule(self.p, int(form), int(lanes)), "set_group_schedule")
+
+    def group_form(self, cnt: int) -> int:
+        """streams per workgroup a group of cnt streams launches with under the present settings"""
+        rc = self.L.lpcnet_batch_group_form(self.p, int(cnt))
+        if rc < 0:
+            self._chk(rc, "group_form")
+        return rc
+
+    def last_groups(self) -> np.ndarray:
+        """[k][8] int32 {lane, slot, cnt, kind, N, preload, streams per workgroup, workgroups}: the groups of the most recent plc_step / synthesize_step of shard 0"""
+        k = self.L.lpcnet_batch_last_groups(self.p, None, 0)
+        if k < 0:
+            self._chk(k, "last_groups")
+        out = np.zeros((k, 8), np.int32)
+        if k:
+            self.L.lpcnet_batch_last_groups(self.p, out.ctypes.data, k)
+        return out
 
     def enable_timing(self, on=True):
         self._chk(self.L.lpcnet_batch_enable_timing(self.p, int(on)), "enable_timing")

@@ -1409,6 +1409,28 @@ int lpcnet_hip_plc_plan(int options, int n, int *ctl, const unsigned char *lost,
     }
     FWD(lpcn_plc_plan(options, n, c, lost, summary));
 }
+/* the same with lanes: the launches and the control lists come back as well (include/lpcnet_batch.h) */
+int lpcnet_hip_plc_plan_lanes(int options, int n, int lanes, int *ctl, const unsigned char *lost, const unsigned char *fec_op, int *summary,
+                              int *launch, int launch_cap, int *lists, int lists_cap)
+{
+    char err[256] = "";
+    if (n < 1 || !ctl || !lost) { set_err("lpcnet_hip_plc_plan_lanes: bad arguments"); return LPCN_E_ARG; }
+    if (lanes < 1 || lanes > 4) { set_err("lpcnet_hip_plc_plan_lanes: lanes must be 1 .. 4"); return LPCN_E_ARG; }      /* (before fec_op changes ctl) */
+    lpcn_plc_ctl *c = (lpcn_plc_ctl *)ctl;
+    lpcn_plc_ctl *before = (lpcn_plc_ctl *)malloc(sizeof(*c) * (size_t)n);
+    if (!before) { set_err("lpcnet_hip_plc_plan_lanes: out of memory"); return LPCN_E_ARG; }
+    memcpy(before, c, sizeof(*c) * (size_t)n);
+    for (int s = 0; fec_op && s < n; s++) {
+        if (fec_op[s] == 1) (void)lpcn_plc_ctl_fec_add(&c[s], 0);
+        else if (fec_op[s] == 2) (void)lpcn_plc_ctl_fec_add(&c[s], 1);
+        else if (fec_op[s] == 3) c[s].fec_keep = c[s].fec_read = c[s].fec_fill = c[s].fec_skip = 0;
+        else if (fec_op[s] == 4) { (void)lpcn_plc_ctl_fec_add(&c[s], 0); (void)lpcn_plc_ctl_fec_add(&c[s], 0); }
+    }
+    const int rc = lpcn_plc_plan_lanes(options, n, lanes, c, lost, summary, launch, launch_cap, lists, lists_cap, err, sizeof(err));
+    if (rc < 0) { memcpy(c, before, sizeof(*c) * (size_t)n); set_err(err); }
+    free(before);
+    return rc;
+}
 /* the FEC feed's planner alone (no device): ctl as above, count [n], skip / clear [n] or NULL, rec [n][8] out (one record per stream that stores
  * something: stream, first source row, rows a, their ring row, move-from row, rows moved, rows b, their ring row), dropped [n] or NULL.  Returns
  * the number of records. */
@@ -1554,6 +1576,30 @@ int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in1
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }
 int lpcnet_batch_tune(LPCNetBatch *b) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_tune(s->dev)); }
 int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x3(s->dev, mode)); }
+int lpcnet_batch_set_group_schedule(LPCNetBatch *b, int form, int lanes)
+{
+    NEED_MODEL(b);
+    if (form < 0 || form > 1 || lanes < 1 || lanes > 4) { set_err("lpcnet_batch_set_group_schedule: form must be 0 or 1 and lanes 1 .. 4"); return LPCN_E_ARG; }      /* (no shard changes) */
+    EACH_SHARD(lpcn_batch_dev_set_group_schedule(s->dev, form, lanes));
+}
+int lpcnet_batch_get_group_schedule(const LPCNetBatch *b, int *form, int *lanes)
+{
+    NEED_MODEL(b);
+    FWD(lpcn_batch_dev_get_group_schedule(b->sh[0].dev, form, lanes));
+}
+int lpcnet_batch_group_form(const LPCNetBatch *b, int cnt)
+{
+    NEED_MODEL(b);
+    const int rc = lpcn_batch_dev_group_form(b->sh[0].dev, cnt);
+    if (rc < 0) take_engine_err();
+    return rc;
+}
+int lpcnet_batch_last_groups(const LPCNetBatch *b, int *rec, int cap)
+{
+    NEED_MODEL(b);
+    if (cap < 0 || (cap && !rec)) { set_err("lpcnet_batch_last_groups: bad arguments"); return LPCN_E_ARG; }
+    return lpcn_batch_dev_last_groups(b->sh[0].dev, rec, cap);
+}
 int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x3(b->sh[0].dev) : 0; }
 int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_streams_per_wg(b->sh[0].dev) : 0; }
 int lpcnet_batch_enable_timing(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_enable_timing(s->dev, on)); }

@@ -91,6 +91,14 @@ struct PinBuf {
         return 0;
     }
 };
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;
@@ -182,7 +190,14 @@ struct lpcn_batch_dev {
     DevBuf<int> d_map;                 //   ... the index maps of one lpcn_batch_dev_step_host call (the PLC's are part of its control lists)
     DevBuf<float> d_keep_a, d_keep_b, d_keep_lpc;   //   ... and every stream's most recent frame products
     std::vector<char> keep_ok;         //   ... which exist only for streams whose last frame step went through the step call (mode 1)
-    DevBuf<LpcnSampleArgs> d_args;
+    DevBuf<LpcnSampleArgs> d_args;     // one record per sample launch of a step (a whole-batch launch uses record 0) ...
+    int args_next = 0;                 //   ... and the next free one of the step being enqueued
+    // the group schedule (lpcn_batch_dev_set_group_schedule; default off: every group launches in the batch's form, on the caller's stream)
+    int sched_form = 0, sched_lanes = 1;
+    Stream side[PLC_MAX_LANES - 1];    // lanes 1 .. 3: created when the schedule is first set with more than one lane
+    Event ev_fork, ev_join[PLC_MAX_LANES - 1];
+    struct GroupRec { int v[8]; };     // {lane, slot, cnt, kind, N, preload, streams per workgroup, workgroups}
+    std::vector<GroupRec> last_groups; // the groups of the most recent PLC step / per-stream step
     DevBuf<float> d_dbg;
     DevBuf<unsigned long long> d_prof;
     Event ev[3];
@@ -654,7 +669,7 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     const size_t rows = (size_t)n * max_chunk;
     int rc = 0;
     if ((rc = b->d_state.alloc(n)) || (rc = b->d_fc_base.alloc(n)) || (rc = b->d_cond_a.alloc(rows * LPCN_ROWS_A)) || (rc = b->d_cond_b.alloc(rows * LPCN_ROWS_B)) ||
-        (rc = b->d_lpc.alloc(rows * LPCN_LPC_ORDER)) || (rc = b->d_cond.alloc((size_t)n * (max_chunk + 4) * LPCN_COND * 2)) || (rc = b->d_args.alloc(1)) ||
+        (rc = b->d_lpc.alloc(rows * LPCN_LPC_ORDER)) || (rc = b->d_cond.alloc((size_t)n * (max_chunk + 4) * LPCN_COND * 2)) || (rc = b->d_args.alloc((size_t)(n > PLC_MAX_GROUPS ? n : PLC_MAX_GROUPS))) ||
         (rc = b->d_vq_mem.alloc((size_t)n * LPCN_NB_BANDS))) return fail(rc);
     for (auto &ev : b->ev) if (hipEventCreate(&ev.e) != hipSuccess) return fail(LPCN_E_HIP);
     if (hipEventCreateWithFlags(&b->ev_last.e, hipEventDisableTiming) != hipSuccess) return fail(LPCN_E_HIP);
@@ -792,6 +807,8 @@ struct LaunchShape {
     int S;                             // streams per workgroup asked for (plan_sample() decides what the launch gets)
     bool pack2;                        //   ... and use_pack2() for that S
     bool x3 = false;                   //   ... at eight: the twelve-wave form of the two-group kernel
+    int slot = 0;                      // first row of the per-stream scratch arrays (frame products, conditioning, frame counts) the launch works in
+    int arg = 0;                       // its record of d_args
 };
 static LaunchShape whole_batch(const lpcn_batch_dev *b) { return {b->n, b->frame_len, b->d_state, b->S, b->pack2, b->x3}; }
 
@@ -830,25 +847,28 @@ static int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t s
     LpcnSampleArgs a = p.image->args;
     a.n_streams = sh.n; a.n_frames = n_frames; a.preload = preload; a.frame_len = sh.frame_len;
     a.fc_advance = fc_from_frames ? 1 : 0;
-    a.cond_a = b->d_cond_a; a.cond_b = b->d_cond_b; a.lpc = b->d_lpc;
-    a.fc_base = fc_from_frames ? b->d_fc_base : nullptr;
+    a.cond_a = b->d_cond_a + (size_t)sh.slot * LPCN_ROWS_A; a.cond_b = b->d_cond_b + (size_t)sh.slot * LPCN_ROWS_B; a.lpc = b->d_lpc + (size_t)sh.slot * LPCN_LPC_ORDER;
+    a.fc_base = fc_from_frames ? b->d_fc_base + sh.slot : nullptr;
     a.pcm = d_pcm; a.pcm_stride = (long long)pcm_stride;
     a.state = sh.d_state; a.dbg = b->d_dbg; a.prof = b->d_prof;
     a.fc_f16 = (e->fast && e->fc_f16) ? 1 : 0;
+    if ((size_t)sh.arg >= b->d_args.cap) { snprintf(g_err, sizeof(g_err), "sample launch: the step's launches exceed their argument records"); return LPCN_E_HIP; }
+    LpcnSampleArgs *d_args = b->d_args + sh.arg;
+    // (d_dbg / d_prof are one buffer per batch: the trace and the phase profile are meaningful with one lane only)
     if (stream_is_capturing(st)) {
-        hipLaunchKernelGGL(lpcn_set_args_kernel, dim3(1), dim3(1), 0, st, b->d_args, a);
+        hipLaunchKernelGGL(lpcn_set_args_kernel, dim3(1), dim3(1), 0, st, d_args, a);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemcpyAsync(b->d_args, &a, sizeof(a), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_args, &a, sizeof(a), hipMemcpyHostToDevice, st));
     }
     const int i8 = e->is_int8 ? 1 : 0;
     const int flags = (e->fast ? 1 : 0) | (p.pack2 ? 2 : 0);
     int rc = 0;
     switch (p.S) {
-    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, b->d_args) : lpcn_launch_sample_x2(nw, p.grid, p.lds, st, b->d_args); break;
-    case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
-    case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
-    default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, b->d_args); break;
+    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, d_args) : lpcn_launch_sample_x2(nw, p.grid, p.lds, st, d_args); break;
+    case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, d_args); break;
+    case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, d_args); break;
+    default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, d_args); break;
     }
     if (rc == LPCN_NO_SUCH_VARIANT) { snprintf(g_err, sizeof(g_err), "no compiled sample-kernel variant for %d items per lane at %d streams per workgroup", nw, p.S); return LPCN_E_HIP; }
     if (rc) { snprintf(g_err, sizeof(g_err), "sample kernel launch failed: %s", hipGetErrorString((hipError_t)rc)); return LPCN_E_HIP; }
@@ -858,7 +878,8 @@ static int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t s
 static int launch_frames(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, const float *d_feat, int feat_stride, size_t feat_stream_stride, int n_frames)
 {
     return lpcn_launch_frame_kernels(b->e->fmodel, st, sh.n, n_frames, d_feat, feat_stride, feat_stream_stride,
-                                     sh.d_state, b->d_fc_base, b->d_cond, b->d_cond_a, b->d_cond_b, b->d_lpc, g_err, sizeof(g_err));
+                                     sh.d_state, b->d_fc_base + sh.slot, b->d_cond + (size_t)sh.slot * LPCN_COND, b->d_cond_a + (size_t)sh.slot * LPCN_ROWS_A,
+                                     b->d_cond_b + (size_t)sh.slot * LPCN_ROWS_B, b->d_lpc + (size_t)sh.slot * LPCN_LPC_ORDER, g_err, sizeof(g_err));
 }
 
 // Streams per workgroup, measured instead of looked up (the table in auto_streams_per_wg holds THIS model's step
@@ -1439,17 +1460,8 @@ extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *fe
 // ---- compacted groups: a subset of the batch's streams through the ordinary frame and sample kernels (the per-stream-arguments step below
 // and the packet-loss concealment, whose streams take different branches in one step).  The streams of a group are named by an index map on
 // the device; their states, their features or kept frame products and their imposed PCM are gathered into dense arrays by small kernels,
-// the launch runs on those with the batch's streams per workgroup, and the results are scattered back by the same map -- the hot kernels
-// stay untouched.  A group runs the sample kernel far below its throughput: this is for occasional use.
-__global__ void lpcn_state_move_kernel(lpcn_stream_state *dst, const lpcn_stream_state *src, const int *map, int count, int scatter)
-{
-    const int words = (int)(sizeof(lpcn_stream_state) / 4);
-    const int i = blockIdx.x;
-    if (i >= count) return;
-    const uint32_t *s = (const uint32_t *)(scatter ? &src[i] : &src[map[i]]);
-    uint32_t *d = (uint32_t *)(scatter ? &dst[map[i]] : &dst[i]);
-    for (int k = threadIdx.x; k < words; k += blockDim.x) d[k] = s[k];
-}
+// the launch runs on those in the batch's form -- or, under the group schedule, the cost table's form for the group's size (group_shape) -- and
+// the results are scattered back by the same map: the hot kernels stay untouched.  A group runs the sample kernel far below its throughput.
 // the buffers every group uses: the compacted states, features and PCM, and every stream's most recent frame products (zero until a stream has some)
 static int group_alloc(lpcn_batch_dev *b)
 {
@@ -1475,38 +1487,125 @@ struct GroupRun {
     size_t pcm_dst_stride;
     bool keep;                         // remember the frame products per stream (lpcnet->gru_a_condition, gru_b_condition, lpc of the reference's state)
     bool scatter;                      // write the states back (false: a trial run)
+    int slot = 0, lane = 0;            // the group's rows of the group buffers: [slot, slot + cnt); the lane it was dealt to (for lpcn_batch_dev_last_groups)
 };
-// Enqueues only; the caller checks hipGetLastError() after its groups.
+// The form a compacted group of cnt streams launches in.  Under the group schedule's `form`, with the batch's streams per workgroup chosen by
+// the engine and PARITY arithmetic (every form gives the same bits there; FAST's output depends on the form), the cost table's form for cnt
+// streams -- a table look-up, never a measurement -- and the twelve-wave form only where the batch already runs it at eight; else the batch's.
+static LaunchShape group_shape(const lpcn_batch_dev *b, int cnt, int N, int slot)
+{
+    if (b->sched_form && b->S_auto && !b->e->fast) {
+        const int S = auto_streams_per_wg(b, cnt);
+        return {cnt, N, b->d_state_tmp + slot, S, use_pack2(b, cnt, S), S == 8 && b->S == 8 && b->x3, slot, 0};
+    }
+    return {cnt, N, b->d_state_tmp + slot, b->S, b->pack2, b->x3, slot, 0};
+}
+static bool aligned16(const void *p, size_t stride_bytes) { return ((uintptr_t)p | (uintptr_t)stride_bytes) % 16 == 0; }
+// Enqueues only; the caller checks hipGetLastError() after its groups.  One gather launch, the frame and sample kernels on rows
+// [slot, slot + cnt) of the group buffers, one scatter launch.
 static int run_group(lpcn_batch_dev *b, hipStream_t st, const GroupRun &g)
 {
-    const int *map = g.map;
     const int cnt = g.cnt;
-    hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state_tmp, (const lpcn_stream_state *)b->d_state, map, cnt, 0);
-    const LaunchShape sh = {cnt, g.N, b->d_state_tmp, b->S, b->pack2, b->x3};      // the compacted group, with the batch's streams per workgroup
+    if (g.slot < 0 || cnt < 1 || g.slot + cnt > b->n) { snprintf(g_err, sizeof(g_err), "group rows [%d, %d) outside the batch", g.slot, g.slot + cnt); return LPCN_E_ARG; }
+    LaunchShape sh = group_shape(b, cnt, g.N, g.slot);
+    sh.arg = b->args_next;
+    const SamplePlan sp = plan_sample(b, sh, 1);
+    b->last_groups.push_back({{g.lane, g.slot, cnt, g.kind, g.N, g.preload, sp.S, sp.grid}});
+    const bool frames = g.kind != PLC_G_TAIL, samples = g.kind != PLC_G_FRAMES;
+    short *gpcm = b->d_gpcm + (size_t)g.slot * LPCN_FRAME_SIZE;
+    lpcn::GroupRows r{};
+    r.map = g.map; r.cnt = cnt;
+    r.states = b->d_state; r.gstates = sh.d_state;
+    r.gfeat = b->d_gfeat + (size_t)g.slot * LPCN_NB_FEAT;
+    r.keep_a = b->d_keep_a; r.keep_b = b->d_keep_b; r.keep_lpc = b->d_keep_lpc;
+    r.cond_a = b->d_cond_a + (size_t)g.slot * LPCN_ROWS_A; r.cond_b = b->d_cond_b + (size_t)g.slot * LPCN_ROWS_B; r.lpc = b->d_lpc + (size_t)g.slot * LPCN_LPC_ORDER;
+    r.gpcm = gpcm; r.N = g.N;
+    lpcn::GroupRows in = r;
+    if (frames) { in.feat = g.feat; in.feat_stride = g.feat_stride; in.feat_vec = aligned16(g.feat, g.feat_stride * sizeof(float)); }
+    in.keep = frames ? 0 : 1;
+    if (samples && g.pcm_src) { in.pcm = const_cast<short *>(g.pcm_src); in.pcm_stride = g.pcm_src_stride; in.pcm_vec = aligned16(g.pcm_src, g.pcm_src_stride * sizeof(short)); }
+    hipLaunchKernelGGL(lpcn::group_gather_kernel, dim3(cnt), dim3(lpcn::PLC_GROUP_THREADS), 0, st, in);
     int rc = 0;
-    if (g.kind != PLC_G_TAIL) {
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_gfeat, (size_t)LPCN_NB_FEAT, g.feat, g.feat_stride, map, cnt, LPCN_NB_FEAT, 0);
-        if ((rc = launch_frames(b, sh, st, b->d_gfeat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1))) return rc;
-        if (g.keep) {
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_keep_a, (size_t)LPCN_ROWS_A, (const float *)b->d_cond_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 1);
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_b, (size_t)LPCN_ROWS_B, (const float *)b->d_cond_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 1);
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 1);
-        }
-    } else {
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(256), 0, st, b->d_cond_a, (size_t)LPCN_ROWS_A, (const float *)b->d_keep_a, (size_t)LPCN_ROWS_A, map, cnt, LPCN_ROWS_A, 0);
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_cond_b, (size_t)LPCN_ROWS_B, (const float *)b->d_keep_b, (size_t)LPCN_ROWS_B, map, cnt, LPCN_ROWS_B, 0);
-        hipLaunchKernelGGL(lpcn::plc_rows_kernel<float>, dim3(cnt), dim3(64), 0, st, b->d_lpc, (size_t)LPCN_LPC_ORDER, (const float *)b->d_keep_lpc, (size_t)LPCN_LPC_ORDER, map, cnt, LPCN_LPC_ORDER, 0);
+    if (frames && (rc = launch_frames(b, sh, st, r.gfeat, LPCN_NB_FEAT, (size_t)LPCN_NB_FEAT, 1))) return rc;
+    if (samples) {
+        if ((rc = launch_sample(b, sh, st, gpcm, (size_t)LPCN_FRAME_SIZE, 1, g.preload, frames))) return rc;
+        b->args_next++;
     }
-    if (g.kind != PLC_G_FRAMES) {
-        if (g.pcm_src)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, b->d_gpcm, (size_t)LPCN_FRAME_SIZE, g.pcm_src, g.pcm_src_stride, map, cnt, g.N, 0);
-        if ((rc = launch_sample(b, sh, st, b->d_gpcm, (size_t)LPCN_FRAME_SIZE, 1, g.preload, g.kind != PLC_G_TAIL))) return rc;
-        if (g.pcm_dst)
-            hipLaunchKernelGGL(lpcn::plc_rows_kernel<short>, dim3(cnt), dim3(64), 0, st, g.pcm_dst, g.pcm_dst_stride, (const short *)b->d_gpcm, (size_t)LPCN_FRAME_SIZE, map, cnt, g.N, 1);
-    }
-    if (g.scatter)
-        hipLaunchKernelGGL(lpcn_state_move_kernel, dim3(cnt), dim3(256), 0, st, b->d_state, (const lpcn_stream_state *)b->d_state_tmp, map, cnt, 1);
+    lpcn::GroupRows out = r;
+    if (samples && g.pcm_dst) { out.pcm = g.pcm_dst; out.pcm_stride = g.pcm_dst_stride; out.pcm_vec = aligned16(g.pcm_dst, g.pcm_dst_stride * sizeof(short)); }
+    out.keep = frames && g.keep ? 1 : 0;
+    out.state_back = g.scatter ? 1 : 0;
+    if (out.pcm || out.keep || out.state_back)
+        hipLaunchKernelGGL(lpcn::group_scatter_kernel, dim3(cnt), dim3(lpcn::PLC_GROUP_THREADS), 0, st, out);
     return 0;
+}
+// The lanes of a step: lane 0 is the caller's stream, lanes 1 .. are the batch's own streams.  lanes_fork lets them start after what the caller's
+// stream holds so far (the step's uploads); lanes_join makes the caller's stream wait for every lane that was given work.
+struct Lanes {
+    hipStream_t st[PLC_MAX_LANES];
+    bool used[PLC_MAX_LANES] = {false, false, false, false};
+    bool forked = false;
+};
+static int lanes_use(lpcn_batch_dev *b, Lanes &ln, int lane, hipStream_t *out)
+{
+    if (lane < 0 || lane >= b->sched_lanes) { snprintf(g_err, sizeof(g_err), "lane %d of %d", lane, b->sched_lanes); return LPCN_E_ARG; }
+    if (lane > 0 && !ln.used[lane]) {
+        if (!ln.forked) { HIP_TRY(hipEventRecord(b->ev_fork, ln.st[0])); ln.forked = true; }
+        HIP_TRY(hipStreamWaitEvent(ln.st[lane], b->ev_fork, 0));
+        ln.used[lane] = true;
+    }
+    *out = ln.st[lane];
+    return 0;
+}
+static Lanes lanes_begin(lpcn_batch_dev *b, hipStream_t st)
+{
+    Lanes ln;
+    ln.st[0] = st;
+    for (int l = 1; l < PLC_MAX_LANES; ++l) ln.st[l] = b->side[l - 1];
+    return ln;
+}
+static int lanes_join(lpcn_batch_dev *b, Lanes &ln)
+{
+    for (int l = 1; l < PLC_MAX_LANES; ++l)
+        if (ln.used[l]) {
+            HIP_TRY(hipEventRecord(b->ev_join[l - 1], ln.st[l]));
+            HIP_TRY(hipStreamWaitEvent(ln.st[0], b->ev_join[l - 1], 0));
+            ln.used[l] = false;
+        }
+    ln.forked = false;
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_set_group_schedule(lpcn_batch_dev *b, int form, int lanes)
+{
+    if (form < 0 || form > 1 || lanes < 1 || lanes > PLC_MAX_LANES) { snprintf(g_err, sizeof(g_err), "group schedule: form must be 0 or 1 and lanes 1 .. %d", PLC_MAX_LANES); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    { int rcw = wait_all(b); if (rcw) return rcw; }
+    if (lanes > 1 && !b->ev_fork.e) {
+        // (each handle is made once: a call that failed part-way is completed by the next one)
+        for (auto &sd : b->side) if (!sd.s && hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking) != hipSuccess) { snprintf(g_err, sizeof(g_err), "group schedule: hipStreamCreate failed"); return LPCN_E_HIP; }
+        for (auto &ev : b->ev_join) if (!ev.e && hipEventCreateWithFlags(&ev.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "group schedule: hipEventCreate failed"); return LPCN_E_HIP; }
+        if (hipEventCreateWithFlags(&b->ev_fork.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "group schedule: hipEventCreate failed"); return LPCN_E_HIP; }
+    }
+    b->sched_form = form; b->sched_lanes = lanes;
+    return 0;
+}
+extern "C" int lpcn_batch_dev_get_group_schedule(const lpcn_batch_dev *b, int *form, int *lanes)
+{
+    if (form) *form = b->sched_form;
+    if (lanes) *lanes = b->sched_lanes;
+    return 0;
+}
+extern "C" int lpcn_batch_dev_group_form(const lpcn_batch_dev *b, int cnt)
+{
+    if (cnt < 1 || cnt > b->n) { snprintf(g_err, sizeof(g_err), "group form: 1 .. %d streams", b->n); return LPCN_E_ARG; }
+    return plan_sample(b, group_shape(b, cnt, LPCN_FRAME_SIZE, 0), 1).S;
+}
+extern "C" int lpcn_batch_dev_last_groups(const lpcn_batch_dev *b, int *rec, int cap)
+{
+    const int k = (int)b->last_groups.size();
+    for (int i = 0; rec && i < k && i < cap; ++i) memcpy(rec + (size_t)i * 8, b->last_groups[(size_t)i].v, sizeof(int) * 8);
+    return k;
 }
 
 // ---- one frame step with PER-STREAM arguments (src/lpcnet_plc.c calls lpcnet_synthesize_impl(N = TRAINING_OFFSET, preload),
@@ -1556,12 +1655,21 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
     HIP_TRY(hipMemcpyAsync(b->d_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_feat, features, sizeof(float) * nfeat, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b->d_pcm, pcm, sizeof(short) * npcm, hipMemcpyHostToDevice, st));
+    b->args_next = 0; b->last_groups.clear();
+    Lanes ln = lanes_begin(b, st);
+    int next_lane = 0;
     for (const Group &g : groups) {
         // (only the first N samples of a stream's frame are written: the rest of d_pcm, and the streams of mode 0, go back as they came)
+        // The groups hold disjoint streams: with more than one lane they are dealt round-robin, each in the rows of its own place in the map.
+        const int lane = next_lane, slot = b->sched_lanes > 1 ? g.off : 0;
+        next_lane = (next_lane + 1) % b->sched_lanes;
+        hipStream_t lst = st;
+        if ((rc = lanes_use(b, ln, lane, &lst))) return rc;
         const GroupRun r = {b->d_map + g.off, g.cnt, g.mode == 1 ? PLC_G_FRAME_SAMPLES : PLC_G_TAIL, g.N, g.preload, b->d_feat, (size_t)feat_stride,
-                            g.preload > 0 ? b->d_pcm.p : nullptr, (size_t)LPCN_FRAME_SIZE, b->d_pcm, (size_t)LPCN_FRAME_SIZE, g.mode == 1, true};
-        if ((rc = run_group(b, st, r))) return rc;
+                            g.preload > 0 ? b->d_pcm.p : nullptr, (size_t)LPCN_FRAME_SIZE, b->d_pcm, (size_t)LPCN_FRAME_SIZE, g.mode == 1, true, slot, lane};
+        if ((rc = run_group(b, lst, r))) { (void)lanes_join(b, ln); return rc; }
     }
+    if ((rc = lanes_join(b, ln))) return rc;
     if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "per-stream step: kernel launch failed"); return LPCN_E_HIP; }
     HIP_TRY(hipMemcpyAsync(pcm, b->d_pcm, sizeof(short) * npcm, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1662,7 +1770,7 @@ static GroupRun plc_group(lpcn_plc_host *p, const PlcLaunch &L, short *d_pcm)
     return {p->d_ctl + L.off, L.cnt, L.kind, L.N, L.preload,
             queued ? p->fbuf + (size_t)(L.feat_src - 1) * LPCN_NB_FEAT : p->feat.p, queued ? (size_t)LPCN_PLC_FBUF * LPCN_NB_FEAT : (size_t)LPCN_NB_FEAT,
             L.pcm_src == 1 ? p->q.p : L.pcm_src == 2 ? d_pcm + L.pcm_off : nullptr, L.pcm_src == 1 ? (size_t)LPCN_PLC_QUEUE : (size_t)LPCN_FRAME_SIZE,
-            L.pcm_dst == 1 ? d_pcm + L.pcm_off : nullptr, (size_t)LPCN_FRAME_SIZE, L.keep, L.scatter};
+            L.pcm_dst == 1 ? d_pcm + L.pcm_off : nullptr, (size_t)LPCN_FRAME_SIZE, L.keep, L.scatter, L.slot, L.lane};
 }
 extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const unsigned char *lost, void *hip_stream)
 {
@@ -1676,7 +1784,7 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
     }
     { int rco = order_begin(b, st); if (rco) return rco; }
     if (p->ctl_pending) { HIP_TRY(hipEventSynchronize(p->ev_ctl)); p->ctl_pending = false; }      // (the previous step's lists have left the pinned buffer: long done)
-    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr, g_err, sizeof(g_err));
+    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr, g_err, sizeof(g_err), b->sched_lanes);
     if (rc) return rc;
     const PlcPlan &P = p->plan;
     if (P.ctl.size() > p->d_ctl.cap) { snprintf(g_err, sizeof(g_err), "PLC step: control lists exceed their buffer"); return LPCN_E_HIP; }
@@ -1687,8 +1795,15 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
         p->ctl_pending = true;
     }
     forget_keep(b);      // (lpcn_batch_dev_step_host's products are the PLC's now)
+    b->args_next = 0; b->last_groups.clear();
+    // Lanes run side by side from here -- the lists are up -- to the join in front of the analysis; from there on everything is on the caller's stream.
+    Lanes ln = lanes_begin(b, st);
+    const hipStream_t caller = st;
     for (const PlcLaunch &L : P.launches) {
         const int *ctl = p->d_ctl + L.off;
+        if (L.type == PLC_T_ANALYSIS) rc = lanes_join(b, ln);
+        if (!rc) rc = lanes_use(b, ln, L.lane, &st);      // (st: the launch's lane from here on)
+        if (rc) { (void)lanes_join(b, ln); return rc; }
         switch (L.type) {
         case PLC_T_BURG:
             hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(L.cnt), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, ctl, L.cnt, d_pcm, p->D, p->remove_dc ? 1 : 0);
@@ -1697,10 +1812,10 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             launch_plc_pred(b, st, ctl, L.cnt, nullptr);
             break;
         case PLC_T_MIX:
-            hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)b->d_gpcm, p->D, b->d_state);
+            hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)b->d_gpcm + (size_t)L.slot * LPCN_FRAME_SIZE, p->D, b->d_state);
             break;
         case PLC_T_GROUP:
-            if ((rc = run_group(b, st, plc_group(p, L, d_pcm)))) return rc;
+            if ((rc = run_group(b, st, plc_group(p, L, d_pcm)))) { (void)lanes_join(b, ln); return rc; }
             break;
         case PLC_T_ANALYSIS:
             if ((rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, 1, d_pcm, 0, (size_t)LPCN_FRAME_SIZE, b->d_an_state, p->D.an, LPCN_AN_NB_FEATURES,
@@ -1708,8 +1823,9 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             break;
         }
     }
+    if ((rc = lanes_join(b, ln))) return rc;      // (a plan always has its analysis launch: nothing is left to join)
     if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "PLC step: kernel launch failed"); return LPCN_E_HIP; }
-    return order_end(b, st);
+    return order_end(b, caller);
 }
 
 extern "C" int lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const unsigned char *lost)

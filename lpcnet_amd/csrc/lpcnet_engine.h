@@ -330,6 +330,14 @@ typedef struct lpcn_plc_state_rec {
  * {lost, flushed queue entries, queue rounds, their samples, FEC vectors used, first frame after a loss (1 cross-fade, 2 codec restore),
  *  queue operation (1 tail, 2 append, 3 push and shift), prediction kept on a received frame, deferred features appended, loss_count after}. */
 int  lpcn_plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary);
+/* ... with lanes (plc_plan.cpp): launch [.][10] and the control lists out; returns the number of launches, or LPCN_E_ARG with the message in err */
+int  lpcn_plc_plan_lanes(int options, int n, int lanes, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary, int *launch, int launch_cap,
+                         int *lists, int lists_cap, char *err, size_t err_len);
+/* The group schedule of a batch (include/lpcnet_batch.h: lpcnet_batch_set_group_schedule): form 0 / 1, lanes 1 .. 4 */
+int  lpcn_batch_dev_set_group_schedule(lpcn_batch_dev *b, int form, int lanes);
+int  lpcn_batch_dev_get_group_schedule(const lpcn_batch_dev *b, int *form, int *lanes);
+int  lpcn_batch_dev_group_form(const lpcn_batch_dev *b, int cnt);             /* streams per workgroup of a group of cnt streams */
+int  lpcn_batch_dev_last_groups(const lpcn_batch_dev *b, int *rec, int cap);  /* [.][8] of the most recent PLC / per-stream step; returns their number */
 void lpcn_plc_ctl_reset(lpcn_plc_ctl *c);
 int  lpcn_plc_ctl_fec_add(lpcn_plc_ctl *c, int is_null);     /* host half of lpcnet_plc_fec_add: 0 stored / skipped, 1 dropped (ring full), 2 stored after a compaction */
 int  lpcn_engine_plc_present(const lpcn_engine *e);           /* lpcn_plc_model.present of the engine's blob */

@@ -8,7 +8,9 @@
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
 //   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs
 //   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
-//   plc_rows_kernel   gather / scatter of rows by an index map: a group of streams runs through the ordinary frame and sample kernels
+//   plc_rows_kernel   gather / scatter of rows by an index map
+//   group_gather_kernel, group_scatter_kernel   everything a compacted group of streams takes in and gives back, in one launch each: the group
+//                     runs through the ordinary frame and sample kernels
 // Every sum keeps the reference's order; products and sums are rounded separately (-ffp-contract=off).
 #pragma once
 #include "lpcnet_log10.h"
@@ -518,6 +520,9 @@ __global__ void plc_rows_kernel(T *dst, size_t dst_stride, const T *src, size_t 
     T *d = dst + (size_t)(scatter ? map[i] : i) * dst_stride;
     for (int k = threadIdx.x; k < width; k += blockDim.x) d[k] = s[k];
 }
+// (no caller in the engine since the group kernels below took over run_group's rows; the two forms stay compiled for tools and the resource test)
+template __global__ void plc_rows_kernel<float>(float *, size_t, const float *, size_t, const int *, int, int, int);
+template __global__ void plc_rows_kernel<short>(short *, size_t, const short *, size_t, const int *, int, int, int);
 
 // lpcnet_plc_fec_add's RNN_MOVE on a full ring (src/lpcnet_plc.c:117-121): rows [keep, keep + rows) of one stream's ring move to the front
 __global__ __launch_bounds__(256) void plc_fec_move_kernel(float *ring, int keep, int rows)
@@ -559,6 +564,77 @@ __global__ __launch_bounds__(PLC_FEED_THREADS) void plc_fec_feed_kernel(const in
         __syncthreads();
     }
     for (int k = t; k < b * LPCN_NB_FEAT; k += PLC_FEED_THREADS) ring[at_b * LPCN_NB_FEAT + k] = v[a * LPCN_NB_FEAT + k];      // (b > 0 after a move of no rows: keep == 100)
+}
+
+// A compacted group's rows in and out, one launch each way and one workgroup per stream of the group (engine.hip: run_group).  Row i of the
+// group's arrays belongs to stream map[i].  In: the state record, then what the group's kind needs -- the 20 features of a frame step, or the
+// kept frame products (1152 + 48 + 16 floats) a tail group continues from -- and the N samples to impose.  Out: the N samples, the state
+// unless the run was a trial, and the frame products where the group keeps them.  State records are 3592 bytes, so 8-byte aligned: they move
+// in int2.  The engine's own rows (products, the group's features and PCM, the PCM queue) are 16-byte aligned and move in float4 / int4; a
+// caller's features or PCM move that way only where the engine found pointer and stride aligned (feat_vec, pcm_vec), else one element at a time.
+constexpr int PLC_GROUP_THREADS = 256;
+struct GroupRows {
+    const int *map;
+    int cnt;
+    lpcn_stream_state *states, *gstates;       // every stream's record; the group's
+    const float *feat;                         // gather: every stream's features (NULL: none)
+    size_t feat_stride;
+    float *gfeat;
+    float *keep_a, *keep_b, *keep_lpc;         // every stream's kept frame products ...
+    float *cond_a, *cond_b, *lpc;              // ... and the group's rows of the frame products
+    short *pcm;                                // gather: the samples to impose; scatter: where the N samples go (NULL: nothing moves)
+    size_t pcm_stride;
+    short *gpcm;
+    int N;
+    int feat_vec, pcm_vec;
+    int keep;                                  // gather: the kept products come in; scatter: the group's products are kept
+    int state_back;                            // scatter: the states go back
+};
+static_assert(sizeof(lpcn_stream_state) % sizeof(int2) == 0, "state records move in int2");
+template <typename V>
+__device__ inline void group_copy(void *dst, const void *src, int count, int t)
+{
+    for (int k = t; k < count; k += PLC_GROUP_THREADS) ((V *)dst)[k] = ((const V *)src)[k];
+}
+__device__ inline void group_copy_pcm(short *dst, const short *src, int N, int vec, int t)
+{
+    const int n8 = vec ? N / 8 : 0;
+    group_copy<int4>(dst, src, n8, t);
+    for (int k = 8 * n8 + t; k < N; k += PLC_GROUP_THREADS) dst[k] = src[k];
+}
+__device__ inline void group_copy_products(float *da, float *db, float *dl, const float *sa, const float *sb, const float *sl, int t)
+{
+    group_copy<float4>(da, sa, LPCN_ROWS_A / 4, t);
+    group_copy<float4>(db, sb, LPCN_ROWS_B / 4, t);
+    group_copy<float4>(dl, sl, LPCN_LPC_ORDER / 4, t);
+}
+__global__ __launch_bounds__(PLC_GROUP_THREADS) void group_gather_kernel(GroupRows g)
+{
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (i >= g.cnt) return;
+    const size_t s = (size_t)g.map[i];
+    group_copy<int2>(&g.gstates[i], &g.states[s], (int)(sizeof(lpcn_stream_state) / sizeof(int2)), t);
+    if (g.feat) {
+        const float *f = g.feat + s * g.feat_stride;
+        float *d = g.gfeat + (size_t)i * LPCN_NB_FEAT;
+        if (g.feat_vec) group_copy<float4>(d, f, LPCN_NB_FEAT / 4, t);
+        else group_copy<float>(d, f, LPCN_NB_FEAT, t);
+    }
+    if (g.keep)
+        group_copy_products(g.cond_a + (size_t)i * LPCN_ROWS_A, g.cond_b + (size_t)i * LPCN_ROWS_B, g.lpc + (size_t)i * LPCN_LPC_ORDER,
+                            g.keep_a + s * LPCN_ROWS_A, g.keep_b + s * LPCN_ROWS_B, g.keep_lpc + s * LPCN_LPC_ORDER, t);
+    if (g.pcm) group_copy_pcm(g.gpcm + (size_t)i * LPCN_FRAME_SIZE, g.pcm + s * g.pcm_stride, g.N, g.pcm_vec, t);
+}
+__global__ __launch_bounds__(PLC_GROUP_THREADS) void group_scatter_kernel(GroupRows g)
+{
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (i >= g.cnt) return;
+    const size_t s = (size_t)g.map[i];
+    if (g.pcm) group_copy_pcm(g.pcm + s * g.pcm_stride, g.gpcm + (size_t)i * LPCN_FRAME_SIZE, g.N, g.pcm_vec, t);
+    if (g.state_back) group_copy<int2>(&g.states[s], &g.gstates[i], (int)(sizeof(lpcn_stream_state) / sizeof(int2)), t);
+    if (g.keep)
+        group_copy_products(g.keep_a + s * LPCN_ROWS_A, g.keep_b + s * LPCN_ROWS_B, g.keep_lpc + s * LPCN_LPC_ORDER,
+                            g.cond_a + (size_t)i * LPCN_ROWS_A, g.cond_b + (size_t)i * LPCN_ROWS_B, g.lpc + (size_t)i * LPCN_LPC_ORDER, t);
 }
 
 }  // namespace lpcn

@@ -99,8 +99,9 @@ static void plc_emit_group(PlcPlan &P, const std::vector<int> &map, int kind, in
     P.launches.push_back(L);
 }
 
-int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len)
+int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len, int lanes)
 {
+    if (lanes < 1 || lanes > PLC_MAX_LANES) { snprintf(err, err_len, "PLC plan: lanes must be 1 .. %d", PLC_MAX_LANES); return LPCN_E_ARG; }
     const bool blending = (options & 3) == LPCNET_PLC_CAUSAL_OPT, remove_dc = (options & 4) != 0;
     static const float att_table[10] = {0, 0, -.2, -.2, -.4, -.4, -.8, -.8, -1.6, -1.6};      // src/lpcnet_plc.c:295
     P.ctl.clear(); P.launches.clear();
@@ -112,7 +113,10 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
             snprintf(err, err_len, "stream %d: inconsistent PLC control state", s); return LPCN_E_ARG;
         }
     }
-    std::vector<int> flush[LPCN_PLC_FBUF], rpred[3], r160[3], r80[3], rshift[3], fpred, lostmap, dclost;
+    // the lost streams' lists, per chain: chain c holds the streams that take c queue rounds in this step (one lane: everything is chain 0)
+    struct LostChain { std::vector<int> flush[LPCN_PLC_FBUF], rpred[3], r160[3], r80[3], rshift[3], fpred, lostmap; };
+    LostChain chain[4];
+    std::vector<int> dclost;
     std::vector<int> burg, bpred, fa1, fa2, resetsig, xgrp, xfade, qtail, qappend, post_pred, fa3, qpush, dcrecv;
     int zero[LPCN_PLC_SUMMARY];
     for (int s = 0; s < n; ++s) {
@@ -121,6 +125,11 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
         memset(sm, 0, sizeof(int) * LPCN_PLC_SUMMARY);
         if (lost[s]) {                                       // lpcnet_plc_conceal_causal, src/lpcnet_plc.c:296-340
             sm[0] = 1; sm[1] = c.fbuf_fill;
+            int rounds = 0;
+            for (int left = c.pcm_fill; left > 0 && rounds < 3; ++rounds) left -= left < LPCN_FRAME_SIZE ? left : LPCN_FRAME_SIZE;
+            LostChain &ch = chain[lanes > 1 ? rounds : 0];
+            std::vector<int> *const flush = ch.flush, *const rpred = ch.rpred, *const r160 = ch.r160, *const r80 = ch.r80, *const rshift = ch.rshift;
+            std::vector<int> &fpred = ch.fpred, &lostmap = ch.lostmap;
             for (int k = 0; k < c.fbuf_fill; ++k) flush[k].push_back(s);
             c.fbuf_fill = 0;
             for (int r = 0; c.pcm_fill > 0 && r < 3; ++r) {
@@ -217,17 +226,23 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
         if (remove_dc) dcrecv.insert(dcrecv.end(), mr, mr + PLC_MIX_REC);
         c.blend = 0;
     }
-    // lost streams: flush, the queued samples round by round, the concealed frame
-    for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
-    for (int r = 0; r < 3; ++r) {
-        plc_emit(P, PLC_T_PRED, 0, rpred[r], PLC_PRED_REC);
-        plc_emit_group(P, r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
-        plc_emit_group(P, r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
-        plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, rshift[r], PLC_MIX_REC);
+    // lost streams, chain by chain: flush, the queued samples round by round, the concealed frame
+    size_t chain_first[5];
+    for (int c = 0; c < 4; ++c) {
+        const LostChain &ch = chain[c];
+        chain_first[c] = P.launches.size();
+        for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, ch.flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
+        for (int r = 0; r < 3; ++r) {
+            plc_emit(P, PLC_T_PRED, 0, ch.rpred[r], PLC_PRED_REC);
+            plc_emit_group(P, ch.r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
+            plc_emit_group(P, ch.r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
+            plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, ch.rshift[r], PLC_MIX_REC);
+        }
+        plc_emit_group(P, ch.lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
+        plc_emit(P, PLC_T_PRED, 0, ch.fpred, PLC_PRED_REC);
+        plc_emit_group(P, ch.lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
     }
-    plc_emit_group(P, lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
-    plc_emit(P, PLC_T_PRED, 0, fpred, PLC_PRED_REC);
-    plc_emit_group(P, lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
+    chain_first[4] = P.launches.size();
     // received streams up to the analysis
     if (!burg.empty()) { plc_emit(P, PLC_T_BURG, 0, burg, 1); }
     plc_emit(P, PLC_T_PRED, 0, bpred, PLC_PRED_REC);
@@ -239,6 +254,27 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
     plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
     plc_emit(P, PLC_T_MIX, PLC_MIX_QTAIL, qtail, PLC_MIX_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_QAPPEND, qappend, PLC_MIX_REC);
+    if (lanes > 1) {
+        // the chains onto the lanes: by the sample steps they take, longest first, each onto the lane with the least so far (lane 0 starts with the
+        // received streams' chain); then one range of group rows per lane, as long as the lane's largest group -- the lanes hold disjoint streams,
+        // so the ranges fit the n rows
+        auto steps = [&](size_t first, size_t last) { int t = 0; for (size_t k = first; k < last; ++k) if (P.launches[k].type == PLC_T_GROUP && P.launches[k].kind != PLC_G_FRAMES) t += P.launches[k].N; return t; };
+        int load[PLC_MAX_LANES] = {steps(chain_first[4], P.launches.size())}, cost[4];
+        bool dealt[4] = {false, false, false, false};
+        for (int c = 0; c < 4; ++c) cost[c] = steps(chain_first[c], chain_first[c + 1]);
+        for (int pass = 0; pass < 4; ++pass) {
+            int c = -1, l = 0;
+            for (int k = 0; k < 4; ++k) if (!dealt[k] && chain_first[k + 1] > chain_first[k] && (c < 0 || cost[k] > cost[c])) c = k;
+            if (c < 0) break;
+            for (int k = 1; k < lanes; ++k) if (load[k] < load[l]) l = k;
+            for (size_t k = chain_first[c]; k < chain_first[c + 1]; ++k) P.launches[k].lane = l;
+            load[l] += cost[c]; dealt[c] = true;
+        }
+        int rows[PLC_MAX_LANES] = {0, 0, 0, 0}, base[PLC_MAX_LANES];
+        for (const PlcLaunch &L : P.launches) if (L.type == PLC_T_GROUP && L.cnt > rows[L.lane]) rows[L.lane] = L.cnt;
+        for (int l = 0, at = 0; l < PLC_MAX_LANES; ++l) { base[l] = at; at += rows[l]; }
+        for (PlcLaunch &L : P.launches) L.slot = base[L.lane];
+    }
     { PlcLaunch L; L.type = PLC_T_ANALYSIS; P.launches.push_back(L); }
     plc_emit(P, PLC_T_PRED, 0, post_pred, PLC_PRED_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa3, PLC_MIX_REC);
@@ -246,4 +282,30 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
     plc_emit(P, PLC_T_MIX, PLC_MIX_DCRECV, dcrecv, PLC_MIX_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_DCLOST, dclost, PLC_MIX_REC);
     return 0;
+}
+
+// The planner with lanes as plain arrays (lpcnet_hip_plc_plan_lanes of include/lpcnet_batch.h): launch[k] = {type, op, lane, slot, cnt, offset of its
+// records in lists, ints per record, kind, N, preload}.  Returns the number of launches, or LPCN_E_ARG (message in err) when the arguments or the
+// control state are bad or an output array is too short.
+extern "C" int lpcn_plc_plan_lanes(int options, int n, int lanes, lpcn_plc_ctl *ctl, const unsigned char *lost, int *summary, int *launch, int launch_cap,
+                                   int *lists, int lists_cap, char *err, size_t err_len)
+{
+    if (n < 1 || !ctl || !lost || !launch || !lists || launch_cap < 0 || lists_cap < 0 || (options & 3) == 1 || (options & 3) == 3 || (options & ~7)) {
+        snprintf(err, err_len, "bad PLC plan arguments"); return LPCN_E_ARG;
+    }
+    PlcPlan P;
+    std::vector<lpcn_plc_ctl> before(ctl, ctl + n);
+    const int rc = plc_plan(options, n, ctl, lost, P, summary, err, err_len, lanes);
+    if (rc) return rc;
+    if (P.launches.size() > (size_t)launch_cap || P.ctl.size() > (size_t)lists_cap) {
+        memcpy(ctl, before.data(), sizeof(lpcn_plc_ctl) * (size_t)n);      // (nothing has happened)
+        snprintf(err, err_len, "PLC plan: %zu launches and %zu list entries do not fit the arrays given", P.launches.size(), P.ctl.size()); return LPCN_E_ARG;
+    }
+    for (size_t k = 0; k < P.launches.size(); ++k) {
+        const PlcLaunch &L = P.launches[k];
+        const int r[PLC_LANES_REC] = {L.type, L.op, L.lane, L.slot, L.cnt, L.off, plc_rec_size(L), L.kind, L.N, L.preload};
+        memcpy(launch + k * PLC_LANES_REC, r, sizeof(r));
+    }
+    if (!P.ctl.empty()) memcpy(lists, P.ctl.data(), sizeof(int) * P.ctl.size());
+    return (int)P.launches.size();
 }

@@ -21,14 +21,28 @@ struct PlcLaunch {
     int pcm_dst = 0;           // 0 nowhere (the group's compacted PCM is left for a cross-fade), 1 the call's frame at pcm_off
     int pcm_off = 0;
     bool scatter = true, keep = false;
+    // the group schedule (plc_plan's `lanes` > 1): launches of different lanes before PLC_T_ANALYSIS name disjoint streams and may run side by side;
+    // a group works in rows [slot, slot + cnt) of the engine's group buffers, and the slot ranges of different lanes are disjoint
+    int lane = 0, slot = 0;
 };
 struct PlcPlan { std::vector<int> ctl; std::vector<PlcLaunch> launches; };
+constexpr int PLC_MAX_LANES = 4;
+constexpr int PLC_LANES_REC = 10;      // ints per launch of lpcn_plc_plan_lanes
+// most groups one step can plan: per chain of lost streams (one per number of queue rounds, 0 .. 3) the flushes, two groups a round, the tail and the
+// concealed half; the received streams' trial and teacher-forced halves
+constexpr int PLC_MAX_GROUPS = 4 * (LPCN_PLC_FBUF + 2 * 3 + 2) + 2;
 
 inline int float_bits(float f) { int i; memcpy(&i, &f, 4); return i; }
 
 // One step of every stream's control state, and the launches it takes.  summary (may be NULL): LPCN_PLC_SUMMARY ints per stream.
 // Returns 0, or LPCN_E_ARG with the message in err.
-int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len);
+// lanes == 1: one chain of launches, in the order a single stream runs them.  lanes 2 .. PLC_MAX_LANES: the lost streams are split by the number of
+// queue rounds they take in this step into up to four chains, each with its own flush, prediction, round, shift, tail and concealed-half launches, and
+// the chains are dealt to the lanes, longest first, onto the lane with the least work so far; the received streams' chain stays on lane 0, and so does
+// everything from PLC_T_ANALYSIS on.  Every stream sees the launches of the one-lane plan, in their order, all in one lane.
+int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, PlcPlan &P, int *summary, char *err, size_t err_len, int lanes = 1);
+// ints per record of a launch's list
+inline int plc_rec_size(const PlcLaunch &L) { return L.type == PLC_T_PRED ? lpcn::PLC_PRED_REC : L.type == PLC_T_MIX ? lpcn::PLC_MIX_REC : L.type == PLC_T_ANALYSIS ? 0 : 1; }
 
 // A batched FEC feed (lpcnet_batch_plc_fec_feed): per stream lpcnet_plc_fec_clear if clear[s], skip[s] NULL adds, then count[s] vectors through
 // lpcnet_plc_fec_add (src/lpcnet_plc.c:111-132), planned from the ring positions alone.  A stream's vectors are rows [off, off + count[s]) of the

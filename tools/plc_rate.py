@@ -19,6 +19,14 @@ the same step (100 / K steps after the reset) and from then on every feed compac
 the rings fill, and with full rings.  Beside them: the step without any FEC traffic, and the host-pointer feed (lpcnet_batch_plc_fec_feed,
 which uploads and synchronises) by the host's clock.  --fec-loop feeds through the per-stream lpcnet_batch_plc_fec_add instead, one call per
 vector, and times loop + step by the host's clock: what the batched feed replaces.
+
+    python tools/plc_rate.py [--int8] [--schedule FORM,LANES]... --ab OUT.json [streams]       (profiles/plc_rate_schedule.json, plc_rate_schedule_int8.json)
+
+The group schedule (lpcnet_batch_set_group_schedule).  --schedule FORM,LANES alone sets it for any of the runs above.  --ab compares: ONE batch in one
+process, the schedule switched between blocks of steps -- off, then each --schedule given (default 1,1 0,2 0,4 1,4), round after round -- so that
+every variant sees the same clocks, the same state history and the same loss flags' statistics.  Per loss pattern (0 %, 5 %, 20 % random loss, the
+outage and its recovery) it prints every variant's median over all its blocks, the medians of its single blocks, and the ratio to the off median;
+the spread between the off blocks' medians is the noise a ratio has to beat.  The steps are timed like the runs above.
 """
 import json
 import os
@@ -44,7 +52,81 @@ def stats(ms):
     return dict(median_ms=float(np.median(ms)), min_ms=float(np.min(ms)), max_ms=float(np.max(ms)), steps=len(ms))
 
 
-def measure(out_path, n, int8=False):
+def measure_ab(out_path, n, schedules, int8=False, rounds=4, block=12):
+    import torch
+    import plc_synth
+    from lpcnet_amd import api, synth
+    dev = torch.device("cuda:0")
+    b = api.LPCNetBatch(n, synth.blob_bytes(plc_synth.make_model_with_plc(flavour="int8" if int8 else "float")))
+    b.plc_enable(api.PLC_CAUSAL)
+    b.tune()
+    T = 100
+    base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
+    frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
+    d = torch.zeros((n, 160), dtype=torch.int16, device=dev)
+    s = torch.cuda.Stream()
+    rng = np.random.default_rng(7)
+    variants = [(0, 1)] + [v for v in schedules if v != (0, 1)]
+    name = lambda v: "off" if v == (0, 1) else "form %d, lanes %d" % v
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), streams=n, options="LPCNET_PLC_CAUSAL", flavour="int8" if int8 else "float",
+                  streams_per_workgroup=b.streams_per_workgroup, rounds=rounds, steps_per_block=block, group_form_of={},
+                  note="one batch, one process; the schedule alternates between blocks of steps; ratio = median / the off median of the same pattern", patterns=[])
+    b.group_schedule = (1, 1)
+    result["group_form_of"] = {str(c): b.group_form(c) for c in (n // 20, n // 5, n) if c >= 1}
+    b.group_schedule = (0, 1)
+
+    def report(pattern, blocks):
+        off = float(np.median(np.concatenate(blocks[(0, 1)])))
+        row = dict(pattern=pattern, variants=[])
+        for v in variants:
+            med = float(np.median(np.concatenate(blocks[v])))
+            row["variants"].append(dict(schedule=name(v), form=v[0], lanes=v[1], median_ms=med, block_medians_ms=[float(np.median(x)) for x in blocks[v]], ratio_to_off=med / off))
+        bm = row["variants"][0]["block_medians_ms"]
+        row["off_block_spread"] = (max(bm) - min(bm)) / off
+        print(json.dumps(row), flush=True)
+        result["patterns"].append(row)
+
+    with torch.cuda.stream(s):
+        t = 0
+        for p in (0.0, 0.05, 0.20):
+            b.group_schedule = (0, 1)
+            b.plc_reset()
+            blocks = {v: [] for v in variants}
+            for _ in range(30):
+                d.copy_(frames[t % T]); step_ms(torch, b, d, (rng.uniform(size=n) < p).astype(np.uint8), s); t += 1
+            for _ in range(rounds):
+                for v in variants:
+                    b.group_schedule = v
+                    ms = []
+                    for _ in range(block):
+                        d.copy_(frames[t % T]); ms.append(step_ms(torch, b, d, (rng.uniform(size=n) < p).astype(np.uint8), s)); t += 1
+                    blocks[v].append(ms)
+            report("random loss %g %%" % (100 * p), blocks)
+        # the outage: every stream loses the same 10 frames, then receives again; the 10 steps of the outage and the 6 after it, where the PCM queue drains
+        out_b, rec_b = {v: [] for v in variants}, {v: [] for v in variants}
+        for _ in range(rounds):
+            for v in variants:
+                b.group_schedule = (0, 1)
+                b.plc_reset()
+                for k in range(12):
+                    d.copy_(frames[k]); step_ms(torch, b, d, np.zeros(n, np.uint8), s)
+                b.group_schedule = v
+                seq = []
+                for k in range(12, 12 + 10 + 6):
+                    d.copy_(frames[k % T]); seq.append(step_ms(torch, b, d, np.full(n, 1 if k < 22 else 0, np.uint8), s))
+                out_b[v].append(seq[:10]); rec_b[v].append(seq[10:])
+        report("outage: every stream lost, 10 frames", out_b)
+        report("recovery: the 6 frames after the outage", rec_b)
+    b.group_schedule = (0, 1)
+    b.sync()
+    b.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+def measure(out_path, n, int8=False, schedule=None):
     import torch
     import plc_synth
     from lpcnet_amd import api, synth
@@ -53,6 +135,8 @@ def measure(out_path, n, int8=False):
     b.plc_enable(api.PLC_CAUSAL)
     assert b.plc_flavour() == int(int8)
     b.tune()
+    if schedule:
+        b.group_schedule = schedule
     T = 100
     base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
     frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
@@ -61,7 +145,7 @@ def measure(out_path, n, int8=False):
     s = torch.cuda.Stream()
     rng = np.random.default_rng(7)
     result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), streams=n, options="LPCNET_PLC_CAUSAL", flavour="int8" if int8 else "float",
-                  streams_per_workgroup=b.L.lpcnet_batch_get_streams_per_workgroup(b.p), random_loss=[], burst=None)
+                  streams_per_workgroup=b.L.lpcnet_batch_get_streams_per_workgroup(b.p), group_schedule=list(b.group_schedule), random_loss=[], burst=None)
     with torch.cuda.stream(s):
         for p in (0.0, 0.05, 0.20):
             b.plc_reset()
@@ -107,7 +191,7 @@ def fec_windows(K, steps, warm):
     return dict(rings_filling=(warm, min(steps, 95 // K)), rings_full=(min(steps, -(-100 // K) + 10), steps))
 
 
-def measure_fec(out_path, n, K, loop=False, int8=False):
+def measure_fec(out_path, n, K, loop=False, int8=False, schedule=None):
     import time
     import torch
     import plc_synth
@@ -116,6 +200,8 @@ def measure_fec(out_path, n, K, loop=False, int8=False):
     b = api.LPCNetBatch(n, synth.blob_bytes(plc_synth.make_model_with_plc(flavour="int8" if int8 else "float")))
     b.plc_enable(api.PLC_CODEC)
     b.tune()
+    if schedule:
+        b.group_schedule = schedule
     T = 100
     base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
     frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
@@ -186,11 +272,21 @@ def measure_fec(out_path, n, K, loop=False, int8=False):
 
 
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x not in ("--int8", "--fec-loop")]
+    args = [x for x in sys.argv[1:] if x not in ("--int8", "--fec-loop", "--ab")]
+    schedules = []
+    while "--schedule" in args:
+        i = args.index("--schedule")
+        form, lanes = (int(x) for x in args[i + 1].split(","))
+        schedules.append((form, lanes))
+        del args[i:i + 2]
+    if "--ab" in sys.argv[1:]:
+        measure_ab(args[0], int(args[1]) if len(args) > 1 else 8192, schedules or [(1, 1), (0, 2), (0, 4), (1, 4)], int8="--int8" in sys.argv[1:])
+        sys.exit(0)
+    schedule = schedules[-1] if schedules else None
     if "--fec" in args:
         i = args.index("--fec")
         K = int(args[i + 1])
         del args[i:i + 2]
-        measure_fec(args[0], int(args[1]) if len(args) > 1 else 8192, K, loop="--fec-loop" in sys.argv[1:], int8="--int8" in sys.argv[1:])
+        measure_fec(args[0], int(args[1]) if len(args) > 1 else 8192, K, loop="--fec-loop" in sys.argv[1:], int8="--int8" in sys.argv[1:], schedule=schedule)
         sys.exit(0)
-    measure(args[0], int(args[1]) if len(args) > 1 else 8192, int8="--int8" in sys.argv[1:])
+    measure(args[0], int(args[1]) if len(args) > 1 else 8192, int8="--int8" in sys.argv[1:], schedule=schedule)
