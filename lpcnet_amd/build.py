@@ -24,6 +24,11 @@ C_FLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-std=gnu11", "-Wall", "-fvisibi
            "-I" + CSRC, "-I" + os.path.join(HERE, "..", "include")]
 CXX_FLAGS = ["-std=c++17" if x == "-std=gnu11" else x for x in C_FLAGS]      # host C++ (plc_plan.cpp: the PLC planner, no device code)
 
+# The engine's host runtime, one unit per subsystem (engine_core.h is what they share; each kernel header belongs to one unit) ...
+ENGINE_UNITS = ("engine", "engine_synth", "engine_codec", "engine_plc", "engine_probe")
+# ... and every object of the library except api.o, which build_small_registry() replaces
+OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS) + ("sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
+
 
 def source_hashes(extra_flags=()):
     """(src, dev): sha1 prefixes over every source the library is built from (lpcnet_amd/csrc/*, the public headers, the
@@ -80,32 +85,28 @@ def build(force=False, verbose=True, prof=False):
         return lib
     objdir = os.path.join(HERE, "build_" + suffix if suffix else ("build_prof" if prof else "build"))
     os.makedirs(objdir, exist_ok=True)
-    objs = []
 
     def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    # engine.hip + the sample kernel's variants, one translation unit per streams-per-workgroup value: built in parallel
-    jobs = [([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "engine.hip"), "-o", os.path.join(objdir, "engine.o")])]
+    # the engine's units + the sample kernel's variants, one translation unit per streams-per-workgroup value: built in parallel
+    jobs = [[HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, u + ".hip"), "-o", os.path.join(objdir, u + ".o")] for u in ENGINE_UNITS]
     for sv in (1, 2, 4):
         jobs.append([HIPCC] + HIP_FLAGS + pf + extra + [f"-DLPCN_S={sv}", "-c", os.path.join(CSRC, "sample_variants.hip"), "-o", os.path.join(objdir, f"sample_s{sv}.o")])
     jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x2.hip"), "-o", os.path.join(objdir, "sample_x2.o")])
     jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x3.hip"), "-o", os.path.join(objdir, "sample_x3.o")])
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=6) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), 16, len(os.sched_getaffinity(0)))) as ex:
         list(ex.map(run, jobs))
-    objs += [j[-1] for j in jobs]
     for c in ("api.c", "model_pack.c"):
         o = os.path.join(objdir, c[:-2] + ".o")
         # (the -D switches of an experiment reach the host C files too: lpcnet_engine.h's dealing defaults -- e.g. which waves of an int8 blob may
         # carry candidate heads -- are derived from the same macros the kernels are compiled with)
         run(["gcc"] + C_FLAGS + [x for x in extra if x.startswith("-D")] + [f'-DLPCN_SOURCE_HASH="{h_src}"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"', "-c", os.path.join(CSRC, c), "-o", o])
-        objs.append(o)
-    objs.append(os.path.join(objdir, "plc_plan.o"))
-    run(["g++"] + CXX_FLAGS + ["-c", os.path.join(CSRC, "plc_plan.cpp"), "-o", objs[-1]])
-    run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs + ["-lpthread", "-lm"])
+    run(["g++"] + CXX_FLAGS + ["-c", os.path.join(CSRC, "plc_plan.cpp"), "-o", os.path.join(objdir, "plc_plan.o")])
+    run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("api.o",) + OBJECTS] + ["-lpthread", "-lm"])
     return lib
 
 
@@ -115,8 +116,7 @@ def build_small_registry(verbose=False):
     build (tests/test_gpu_wide.py; select with LPCNET_HIP_LIB).  Test artefact, git-ignored like every built library."""
     build(verbose=verbose)
     objdir0 = os.path.join(HERE, "build")
-    needed = ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
-    if not all(os.path.exists(os.path.join(objdir0, f)) for f in needed):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
+    if not all(os.path.exists(os.path.join(objdir0, f)) for f in OBJECTS):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
         build(force=True, verbose=verbose)
     lib = LIB.replace(".so", "_smallreg.so")
     h_src, h_dev = source_hashes()
@@ -126,8 +126,7 @@ def build_small_registry(verbose=False):
     o = os.path.join(objdir, "api_smallreg.o")
     cmds = [["gcc"] + C_FLAGS + ["-DLPCN_MAX_MODELS=4", "-DLPCN_MAX_RESIDENT=2", f'-DLPCN_SOURCE_HASH="{h_src}-smallreg"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"',
                                  "-c", os.path.join(CSRC, "api.c"), "-o", o],
-            [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("engine.o", "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o")]
-            + [o, os.path.join(objdir, "model_pack.o"), os.path.join(objdir, "plc_plan.o"), "-lpthread", "-lm"]]
+            [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [o] + [os.path.join(objdir, f) for f in OBJECTS] + ["-lpthread", "-lm"]]
     for c in cmds:
         if verbose:
             print(" ".join(c), flush=True)

@@ -15,6 +15,7 @@
 // four-frame encoder (encode_kernels.hip.h): compute_frame_features is one function for both paths in the reference.
 #pragma once
 #include "lpcnet_log10.h"
+#include "spectral.hip.h"
 
 namespace lpcn {
 
@@ -23,8 +24,6 @@ constexpr int AN_XC_THREADS = 320;      // cross-correlation: 256 lag lanes + on
 constexpr int AN_PITCH_THREADS = 256;
 constexpr int AN_HIST = LPCN_PITCH_MAX_PERIOD + LPCN_FRAME_SIZE;      // live part of exc_buf in single-frame analysis (416 of 576)
 constexpr int AN_PATHS = LPCN_PITCH_MAX_PERIOD - LPCN_PITCH_MIN_PERIOD;
-
-#define LPCN_MAX16(a, b) ((a) > (b) ? (a) : (b))      // the reference's MAX16 (src/arch.h), same operand roles
 
 __device__ __forceinline__ float an_pcm(const void *pcm, const int is_float, const size_t i)
 {
@@ -352,7 +351,7 @@ __global__ __launch_bounds__(AN_PITCH_THREADS) void analysis_pitch_kernel(int n_
 }  // namespace lpcn
 
 // the three launches of one chunk (n_frames <= the scratch buffers' capacity)
-static inline int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
+int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
                                                size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride,
                                                size_t feat_stream_stride, float *d_resid, float *d_xc, float *d_fw, char *err, size_t errlen)
 {

@@ -9,14 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "lpcnet_engine.h"
+#include "kernel_params.h"
 
 namespace lpcn {
-
-struct DecodeTables {
-    const float *cb1, *cb2, *cb3;     // [1024][17] each (ceps_codebook1..3)
-    const float *cb_diff4;            // [4096][18]
-    const float *pitch;               // [64] = (float)(pow(2.f, k/21.)*32), evaluated by the host libm (src/lpcnet_dec.c:107)
-};
 
 __device__ __forceinline__ unsigned dec_bits(const unsigned long long word, int &pos, const int n)
 {

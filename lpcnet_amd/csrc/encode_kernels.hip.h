@@ -29,12 +29,6 @@ constexpr int ENC_END_IPW = 4;                 // (stream, packet) items per wav
 constexpr int ENC_MID_IPW = 2;                 //   ... vq_mid (78 KB)
 constexpr int ENC_PK = 4;                      // ints per packet of the scratch record: [0] pitch | modulation | corr_id (11 bits), [1] c0_id + 64, [2] vq_end (30 bits)
 
-struct EncodeTables {
-    const float *cb1, *cb2, *cb3, *cb_diff4;   // row-major, the decode kernel's copies
-    const float *cb1_t, *cb2_t, *cb3_t;        // [17][1024]
-    const float *cbd_t;                        // [4][18][1024]: quarter q holds entries 1024 q ..
-};
-
 // (int)v as the reference's x86 build converts (cvttsd2si): out of range and NaN give INT_MIN
 __device__ __forceinline__ int enc_int(const double v) { return (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : (int)0x80000000; }
 __device__ __forceinline__ int enc_imax(const int a, const int b) { return a > b ? a : b; }
@@ -475,7 +469,7 @@ static inline int lpcn_encode_ipw(size_t items, int ipw_max)
 
 // the launches of one chunk of n_packets packets (4 * n_packets <= the analysis scratch's frames).  d_packets != NULL: lpcnet_encode, five
 // launches, cepstrum / LPC into the scratch rows d_feat (stride 36); else lpcnet_compute_features, three launches, d_feat is the caller's.
-static inline int lpcn_launch_encode_kernels(const LpcnFrameModel &M, const lpcn::EncodeTables &T, hipStream_t st, int n, int n_packets, const short *d_pcm,
+int lpcn_launch_encode_kernels(const LpcnFrameModel &M, const lpcn::EncodeTables &T, hipStream_t st, int n, int n_packets, const short *d_pcm,
                                              size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride, size_t feat_stream_stride,
                                              float *d_resid, float *d_xc, float *d_fw, float *d_vq_mem, float *d_qf3, int *d_pk, unsigned char *d_packets,
                                              int packets_per_stream, char *err, size_t errlen)

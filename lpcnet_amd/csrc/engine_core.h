@@ -1,0 +1,280 @@
+// What the units of the engine's host runtime share (engine.hip, engine_synth.hip, engine_codec.hip, engine_plc.hip, engine_probe.hip): the
+// error macro, the owning buffer types, the engine and batch records and the helpers more than one unit calls.  C++ only: the C host
+// shell sees lpcnet_engine.h alone.  The seam between units is host functions; each kernel header belongs to one unit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <memory>
+#include <vector>
+#include "lpcnet_engine.h"
+#include "sample_kernel.hip.h"
+#include "kernel_params.h"
+#include "plc_plan.h"
+
+// The calling thread's last error message (engine.hip; lpcn_last_error).  __thread: no dynamic initialiser, so every unit reaches it directly; a
+// thread_local declared extern goes through the C++ wrapper and its weak init hook, whose address test fails in a shared library.
+extern __attribute__((visibility("hidden"))) __thread char g_err[512];
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess) {                                                               \
+            snprintf(g_err, sizeof(g_err), "%s:%d: %s -> %s", __FILE__, __LINE__, #expr,      \
+                     hipGetErrorString(_e));                                                  \
+            return LPCN_E_HIP;                                                                \
+        }                                                                                     \
+    } while (0)
+
+// Every entry point selects the engine's device and restores the caller's current device on return.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != dev) (void)hipSetDevice(dev); else prev = -1; }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+// Device memory with an owner: the destructor frees, nothing copies.  `cap` counts elements.  What a batch owns goes with `delete b`, inside
+// the DeviceGuard of lpcn_batch_dev_destroy.
+struct lpcn_batch_dev;
+int wait_all(lpcn_batch_dev *b);
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // exactly `count` elements, optionally zeroed
+    int alloc(size_t count, bool zero = false)
+    {
+        release();
+        if (hipMalloc((void **)&p, count * sizeof(T)) != hipSuccess) { p = nullptr; snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", count * sizeof(T)); return LPCN_E_HIP; }
+        cap = count;
+        if (zero) HIP_TRY(hipMemset(p, 0, count * sizeof(T)));
+        return 0;
+    }
+    // at least `count` elements, contents not kept.  Growing first waits for everything enqueued for the batch, whichever stream it went to:
+    // the old buffer may still be in use.  It happens once per size.
+    int reserve(lpcn_batch_dev *b, size_t count)
+    {
+        if (count <= cap) return 0;
+        const int rc = wait_all(b);
+        return rc ? rc : alloc(count);
+    }
+};
+// Pinned host memory, grown to the bytes its user asks for.  Its users synchronise before they return, so nothing is in flight when it grows.
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int reserve(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; snprintf(g_err, sizeof(g_err), "hipHostMalloc(%zu) failed", bytes); return LPCN_E_HIP; }
+        cap = bytes;
+        return 0;
+    }
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+// GRU-A as dealt to waves and lanes, once per dealing: the model part of the argument block with that image's pointers, and the compiled
+// items-per-lane variant its item arrays are padded to.  PARITY's always exists; FAST has its own for int8 blobs (dealt without candidate heads);
+// the two-group kernel's (float blobs; model_pack.c: lpcn_model_pack_x2) is the only one with the natural-order embedding tables; its twelve-wave
+// form runs on an image of its own (lpcn_model_pack_x3: 12 waves x 16 items, candidate slots cut head / tail) and shares those tables.
+enum { IMG_PARITY, IMG_FAST, IMG_X2, IMG_X3, IMG_COUNT };
+struct GruAImage { LpcnSampleArgs args{}; int nw_variant = 0; bool present = false; };
+
+struct lpcn_engine {
+    int device = 0;
+    int nw = 0, nb_b = 0;
+    bool is_int8 = false;
+    bool fc_f16 = false;               // FAST sub-option: fp16 dual FC (lpcn_engine_set_fast(e, 2))
+    bool fast = false;                 // FAST arithmetic (lpcn_engine_set_fast): fused / integer accumulation instead of the reference's generic-C order
+    float lpc_gamma = 1.f;
+    hipStream_t stream = nullptr;
+    std::vector<void *> allocs;
+    GruAImage image[IMG_COUNT];
+    LpcnFrameModel fmodel{};
+    lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
+    bool has_codebooks = false;
+    lpcn::EncodeTables enc{};      // encoder: the same codebooks and their transposed copies, refreshed together
+    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network (float blobs; int8 blobs: its widths only)
+    lpcn::PlcNetQ plcq{};          //   ... an int8 blob's (plc_pred_i8_kernel)
+    int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
+    bool plc_servable = false;     //   ... and whether it is in the blob's own flavour (lpcn_plc_servable): uploaded only then
+};
+
+// packet-loss concealment of a batch (lpcn_batch_dev_plc_enable): the control state on the host, the data on the device
+struct lpcn_plc_host {
+    int options = 0;
+    bool remove_dc = false;
+    std::vector<lpcn_plc_ctl> ctl;
+    DevBuf<short> q, lp;                            // the arrays of lpcn::PlcData (kernel_params.h) ...
+    DevBuf<float> feat, net, fec, fbuf, burg, an;
+    DevBuf<double> dc;
+    DevBuf<int> delta;
+    lpcn::PlcData D{};                              // ... and their addresses as the kernels take them
+    DevBuf<short> d_pcm;                            // staging of the host-pointer call
+    DevBuf<int> d_ident;                            // 0 .. n-1
+    DevBuf<int> d_ctl;                              // the step's lists: device copy (its capacity bounds a step's lists) ...
+    PinBuf h_ctl;                                   // ... and its pinned source
+    Event ev_ctl;                                   // the upload of the previous step's lists has left h_ctl
+    bool ctl_pending = false;
+    PlcPlan plan;
+    DevBuf<int> d_feed;                             // a batched FEC feed's records (their pinned source: h_ctl past the step's lists, so that a feed
+    Event ev_feed;                                  //   and a step never wait for each other's upload) and "the previous feed's have left it"
+    bool feed_pending = false;
+    DevBuf<float> d_feed_src;                       //   ... and the host-pointer call's packed vectors, grown to the largest call
+};
+
+struct lpcn_batch_dev {
+    lpcn_engine *e = nullptr;
+    int n = 0, max_chunk = 0, S = 0, frame_len = LPCN_FRAME_SIZE;
+    bool S_auto = true;                // streams per workgroup are chosen by the engine (measured on this batch, see autotune_streams_per_wg)
+    bool tuned = false;                // ... and have been measured for the current arithmetic flavour
+    bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
+    bool no_x2 = false;                // LPCNET_HIP_NO_X2=1 when the batch was created (tools / tests): never the two-group kernel
+    bool x3 = false;                   // at eight streams per workgroup: the twelve-wave form of the two-group kernel (measured faster on this batch, or asked for)
+    int x3_mode = -1;                  // lpcn_batch_dev_set_x3: 0 never, 1 always, -1 measured (the table's value, the eight-wave form, until then)
+    int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
+    DevBuf<lpcn_stream_state> d_state;
+    DevBuf<int> d_fc_base;
+    DevBuf<float> d_cond_a, d_cond_b, d_lpc, d_cond;
+    DevBuf<float> d_feat;              // staging for host-pointer runs / decoded feature vectors
+    DevBuf<short> d_pcm;
+    DevBuf<unsigned char> d_packets;   // packet staging of the host-pointer codec calls (decode: in, encode: out)
+    DevBuf<float> d_vq_mem;            // [n][18] VQ memory of the codec path (src/lpcnet_private.h:52)
+    DevBuf<lpcn_analysis_state> d_an_state;      // feature analysis (lpcn_batch_dev_analysis_enable): per-stream state, allocated on first use
+    DevBuf<float> d_an_resid, d_an_xc, d_an_fw;  //   ... and the kernels' scratch for an_chunk frames per launch
+    int an_chunk = 0;
+    DevBuf<unsigned char> d_an_pcm;    //   ... and the staging of host-pointer calls (PCM in, as bytes; features out)
+    DevBuf<float> d_an_feat;
+    DevBuf<float> d_enc_vq_mem;        // encoder (lpcn_batch_dev_encoder_enable): [n][18] vq_mem of LPCNetEncState, beside the analysis state
+    DevBuf<float> d_enc_feat, d_enc_qf3;         //   ... scratch of enc_chunk packets per launch: cepstrum / LPC rows, quantised frame 3 (+ the entry vq_mem)
+    DevBuf<int> d_enc_pk;              //   ... and the packets' bit fields
+    int enc_chunk = 0;
+    DevBuf<lpcn_stream_state> d_state_tmp;       // compacted groups (run_group: the per-stream-arguments step, the PLC): the group's states
+    DevBuf<float> d_gfeat;             //   ... features (also the PLC parity seam's output)
+    DevBuf<short> d_gpcm;              //   ... and PCM
+    DevBuf<int> d_map;                 //   ... the index maps of one lpcn_batch_dev_step_host call (the PLC's are part of its control lists)
+    DevBuf<float> d_keep_a, d_keep_b, d_keep_lpc;   //   ... and every stream's most recent frame products
+    std::vector<char> keep_ok;         //   ... which exist only for streams whose last frame step went through the step call (mode 1)
+    DevBuf<LpcnSampleArgs> d_args;     // one record per sample launch of a step (a whole-batch launch uses record 0) ...
+    int args_next = 0;                 //   ... and the next free one of the step being enqueued
+    // the group schedule (lpcn_batch_dev_set_group_schedule; default off: every group launches in the batch's form, on the caller's stream)
+    int sched_form = 0, sched_lanes = 1;
+    Stream side[PLC_MAX_LANES - 1];    // lanes 1 .. 3: created when the schedule is first set with more than one lane
+    Event ev_fork, ev_join[PLC_MAX_LANES - 1];
+    struct GroupRec { int v[8]; };     // {lane, slot, cnt, kind, N, preload, streams per workgroup, workgroups}
+    std::vector<GroupRec> last_groups; // the groups of the most recent PLC step / per-stream step
+    DevBuf<float> d_dbg;
+    DevBuf<unsigned long long> d_prof;
+    Event ev[3];
+    // Ordering across caller streams: the batch's scratch buffers and state are shared by every call, so each enqueue
+    // records ev_last on its stream; a call on a DIFFERENT stream first waits for it, and every host-side access
+    // (sync, state get/set, reset, destroy, buffer growth) waits for it as well.
+    Event ev_last;
+    hipStream_t last_stream = nullptr;
+    bool pending = false;
+    std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
+    PinBuf h_pin;                      // pinned host staging of the single-stream fast path and the combined pass: each reserves what it lays out
+    bool timing = false;
+    float ms_sample = 0.f, ms_frame = 0.f;
+};
+
+// What a launch works on and the batch does not own for good: a call on part of the batch, on other states or with another S passes another
+// shape; nothing overwrites the batch's settings to steer a launch.
+struct LaunchShape {
+    int n, frame_len;                  // streams in this launch, samples per frame
+    lpcn_stream_state *d_state;        // [n] the states it reads and writes
+    int S;                             // streams per workgroup asked for (plan_sample() decides what the launch gets)
+    bool pack2;                        //   ... and use_pack2() for that S
+    bool x3 = false;                   //   ... at eight: the twelve-wave form of the two-group kernel
+    int slot = 0;                      // first row of the per-stream scratch arrays (frame products, conditioning, frame counts) the launch works in
+    int arg = 0;                       // its record of d_args
+};
+
+// Which sample kernel a launch of n_frames frames per stream gets, on which GRU-A image.  No side effects.
+struct SamplePlan {
+    int S;                             // streams per workgroup the launch runs with
+    bool pack2;
+    bool x3;                           // eight streams per workgroup on twelve waves
+    const GruAImage *image;            // (with its items-per-lane variant)
+    int lds, grid;                     // dynamic LDS bytes per workgroup, workgroups
+};
+SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_frames);
+
+// The GRU-A image a launch at S streams per workgroup runs on: the two-group kernel's at eight; else FAST's own where the engine's
+// current arithmetic is FAST and it has one; else PARITY's.
+inline const GruAImage &gru_a_image(const lpcn_engine *e, int S) { return e->image[S == 8 ? IMG_X2 : (e->fast && e->image[IMG_FAST].present) ? IMG_FAST : IMG_PARITY]; }
+// Two groups of four float streams per workgroup, half a step apart (sample_kernel_x2.hip.h): float blobs, PARITY arithmetic, dense GRU-B input
+// matrix, <= 32 items per lane.  Eight streams per workgroup select it.
+inline bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast; }
+// ... and its twelve-wave form (sample_kernel_x3.hip.h), where the model has the image for it
+inline bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && b->e->image[IMG_X3].present; }
+
+// engine.hip: ordering across caller streams, argument checks, the cost table
+bool stream_is_capturing(hipStream_t st);
+int order_begin(lpcn_batch_dev *b, hipStream_t st);
+int order_end(lpcn_batch_dev *b, hipStream_t st);
+void forget_keep(lpcn_batch_dev *b);
+int check_range(const lpcn_batch_dev *b, int first, int count, const char *what);
+int device_cus(const lpcn_engine *e);
+bool use_pack2(const lpcn_batch_dev *b, int n, int S);
+int auto_streams_per_wg(const lpcn_batch_dev *b, int n);
+// engine_synth.hip: staging, the tuner, the sample and frame launches (frame_kernels.hip.h)
+int ensure_staging(lpcn_batch_dev *b, size_t feat_floats, size_t pcm_samples);
+int tune_if_due(lpcn_batch_dev *b, hipStream_t st);
+int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, short *d_pcm, size_t pcm_stride, int n_frames, int preload, bool fc_from_frames);
+int launch_frames(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, const float *d_feat, int feat_stride, size_t feat_stream_stride, int n_frames);
+int lpcn_launch_frame_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const float *d_feat,
+                              int feat_stride, size_t feat_stream_stride, lpcn_stream_state *d_state, int *d_fc_base,
+                              float *d_cond, float *d_cond_a, float *d_cond_b, float *d_lpc, char *err, size_t errlen);
+// engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)
+int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
+                                 size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride,
+                                 size_t feat_stream_stride, float *d_resid, float *d_xc, float *d_fw, char *err, size_t errlen);
+int lpcn_launch_encode_kernels(const LpcnFrameModel &M, const lpcn::EncodeTables &T, hipStream_t st, int n, int n_packets, const short *d_pcm,
+                               size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride, size_t feat_stream_stride,
+                               float *d_resid, float *d_xc, float *d_fw, float *d_vq_mem, float *d_qf3, int *d_pk, unsigned char *d_packets,
+                               int packets_per_stream, char *err, size_t errlen);
+
+// One stream's record of a per-stream device array, `per` elements at buf + s * per, to the host (down) or from it (up), after everything
+// enqueued for the batch.  An array that exists only once its feature is enabled names the call that makes it.
+template <typename T>
+int stream_rec(lpcn_batch_dev *b, int s, const DevBuf<T> &buf, size_t per, void *down, const void *up, int (*enable)(lpcn_batch_dev *, int) = nullptr)
+{
+    if (s < 0 || s >= b->n || (!down && !up)) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    int rc = (!buf && enable) ? enable(b, 1) : 0;
+    if (!rc) rc = wait_all(b);
+    if (rc) return rc;
+    if (up) HIP_TRY(hipMemcpy(buf + (size_t)s * per, up, sizeof(T) * per, hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemcpy(down, buf + (size_t)s * per, sizeof(T) * per, hipMemcpyDeviceToHost));
+    return 0;
+}

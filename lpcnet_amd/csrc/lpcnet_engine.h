@@ -4,7 +4,7 @@
  * Layers:
  *   api.c (C)          public include/lpcnet.h + include/lpcnet_batch.h entry points
  *   model_pack.c (C)   DNNw blob -> validated host model + device-friendly packings
- *   engine.hip (HIP)   device memory, uploads, kernel launches  <-- declared here
+ *   engine*.hip (HIP)  device memory, uploads, kernel launches  <-- declared here (engine_core.h: what the units share)
  */
 #ifndef LPCNET_ENGINE_H
 #define LPCNET_ENGINE_H
@@ -202,7 +202,7 @@ typedef struct lpcn_analysis_state {
     int32_t best_i;
 } lpcn_analysis_state;
 
-/* ---- engine.hip ----------------------------------------------------------------------------- */
+/* ---- engine*.hip ---------------------------------------------------------------------------- */
 typedef struct lpcn_engine lpcn_engine;      /* one per (process, HIP device, model)            */
 
 /* All functions return 0 on success or a negative LPCN_E_* code; the message of the last failure
@@ -223,11 +223,11 @@ int  lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n_streams, 
 void lpcn_batch_dev_destroy(lpcn_batch_dev *b);
 int  lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count);           /* lpcnet_reset   */
 int  lpcn_batch_dev_get_state(lpcn_batch_dev *b, int stream, lpcn_stream_state *host);
-/* k independent streams with their callers' POD states in ONE pass and one synchronisation (engine.hip): frame network + samples,
+/* k independent streams with their callers' POD states in ONE pass and one synchronisation (engine_synth.hip): frame network + samples,
  * samples from the callers' frame products, or the frame network alone */
-#define LPCN_GROUP_FRAME_SAMPLES 0
-#define LPCN_GROUP_TAIL          1
-#define LPCN_GROUP_FRAMES        2
+#define LPCN_GROUP_FRAMES        0
+#define LPCN_GROUP_FRAME_SAMPLES 1
+#define LPCN_GROUP_TAIL          2
 int  lpcn_batch_dev_run_group(lpcn_batch_dev *b, int k, int kind, int frame_len, int preload, const lpcn_stream_state *const *st_in,
                               const float *const *feat, short *const *pcm, lpcn_stream_state *const *st_out,
                               float *const *ga, float *const *gb, float *const *lpc);
@@ -274,7 +274,7 @@ int  lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond_a, const 
 int  lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *features, int feat_stride,
                                     float *cond_a, float *cond_b, float *lpc, int n_frames);
 
-/* One frame step with per-stream arguments (host pointers, see engine.hip): mode[s] 0 = skip, 1 = frame network + n_samples[s]
+/* One frame step with per-stream arguments (host pointers, see engine_plc.hip): mode[s] 0 = skip, 1 = frame network + n_samples[s]
  * samples, 2 = n_samples[s] samples from the stream's most recent frame products; preload[s] leading samples of pcm[s] imposed.
  * features [n][feat_stride], pcm [n][160]. */
 int  lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features, int feat_stride, short *pcm,
@@ -374,8 +374,8 @@ int  lpcn_batch_dev_profile(lpcn_batch_dev *b, unsigned long long *out);
 /* test seam: this engine's own 10^x (lpcnet_exp10.h) evaluated on the device for host arrays */
 int  lpcn_debug_exp10(int device, const float *x, double *out, size_t n);
 /* test seam: v_mfma_f32_4x4x1 with C = -0.0 against v_mul_f32, and the halves of v_pk_mul_f32 / v_pk_add_f32 against the scalar
- * instructions, as bit patterns (engine.hip: lpcn_arith_identity_kernel); n = operand count, a multiple of 64; outputs [n][4] each */
-/* test seam: v_cvt_rpi_i32_f32 against (int)floor(.5 + (double)t) on all 2^32 bit patterns (engine.hip: lpcn_quant_sweep_kernel);
+ * instructions, as bit patterns (engine_probe.hip: lpcn_arith_identity_kernel); n = operand count, a multiple of 64; outputs [n][4] each */
+/* test seam: v_cvt_rpi_i32_f32 against (int)floor(.5 + (double)t) on all 2^32 bit patterns (engine_probe.hip: lpcn_quant_sweep_kernel);
  * out3 = {mismatches among finite |t| < 2^31, mismatches with |t| <= 127.5, one mismatching pattern} */
 int  lpcn_debug_quant_sweep(int device, unsigned long long *out3);
 int  lpcn_debug_arith_identities(int device, const float *a, const float *b, uint32_t *out_mfma, uint32_t *out_mul,

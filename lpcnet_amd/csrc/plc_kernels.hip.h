@@ -8,11 +8,11 @@
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
 //   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs
 //   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
-//   plc_rows_kernel   gather / scatter of rows by an index map
 //   group_gather_kernel, group_scatter_kernel   everything a compacted group of streams takes in and gives back, in one launch each: the group
 //                     runs through the ordinary frame and sample kernels
 // Every sum keeps the reference's order; products and sums are rounded separately (-ffp-contract=off).
 #pragma once
+#include "spectral.hip.h"
 #include "lpcnet_log10.h"
 #include "quant_i8.hip.h"           // quant_s8, QS, QS1: the int8 arithmetic's quantisation and scales
 #include "lpcnet_plc_tables_gen.h"
@@ -20,32 +20,6 @@
 #include "plc_records.h"      // record sizes, flags and operation codes of the control lists (shared with the host planner)
 
 namespace lpcn {
-
-// the PLC network on the device (widths from the blob; the sparse GRU input matrices as the blob has them plus per-row-group starts)
-struct PlcNet {
-    int d1, g1, g2;
-    const float *dense1_w, *dense1_b;
-    const float *gru1_w, *gru1_rec, *gru1_bias;
-    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input position of a block
-    const float *gru2_w, *gru2_rec, *gru2_bias;
-    const int *gru2_start, *gru2_pos;
-    const float *out_w, *out_b;
-    const float *tansig;
-};
-
-// per-stream PLC data (the fields of LPCNetPLCState that hold samples, features and network state; src/lpcnet_private.h:79-105)
-struct PlcData {
-    short *q;            // [n][560] st->pcm
-    float *feat;         // [n][20]  st->features
-    float *net;          // [n][4][g1 + g2]: plc_net, plc_copy[0..2]
-    double *dc;          // [n][2]   dc_mem, syn_dc
-    int *delta;          // [n]      the step's `delta` (src/lpcnet_plc.c:198)
-    float *fec;          // [n][100][20]
-    float *fbuf;         // [n][4][20] the synthesis state's deferred feature queue (src/lpcnet.c:122-144)
-    short *lp;           // [n][160] the step's low-pass samples
-    float *burg;         // [n][36]
-    float *an;           // [n][36]  analysis of the step's frame
-};
 
 constexpr int PLC_BURG_THREADS = 128;
 constexpr int PLC_PRED_THREADS = 256;
@@ -292,19 +266,6 @@ __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, co
 // run sparse_sgemv_accum8x4 / sgemv_accum8x4 of src/vec.h:274-339 (USE_SU_BIAS undefined: they start from `bias`): per row out *= 128*127, then for
 // each 8x4 block in list order the exact integer sum of four int8 products is added with ONE rounded float add, then out *= 1/128/127.  The inputs
 // of a product are quantised once, (signed char)(int)floor(.5 + 127 x) (quant_s8, quant_i8.hip.h).
-struct PlcNetQ {
-    int d1, g1, g2;
-    const float *dense1_w, *dense1_b;
-    const int *gru1_w, *gru1_rec;                // [blocks][8 rows] and [g1 / 4][3 g1] dwords: the four int8 weights of (row, block)
-    const float *gru1_bias;
-    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input DWORD (position / 4) of a block
-    const int *gru2_w, *gru2_rec;
-    const float *gru2_bias;
-    const int *gru2_start, *gru2_pos;
-    const float *out_w, *out_b;
-    const float *tansig;
-};
-
 constexpr int PLC_Q_UNITS_PER_LANE = (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS;
 
 // compute_gruB on quantised inputs.  One lane per UNIT: it runs the unit's three gate rows (z, r, h: rows i, N + i, 2 N + i), so no pre-activation
@@ -510,20 +471,6 @@ __global__ __launch_bounds__(PLC_MIX_THREADS) void plc_mix_kernel(int op, const 
     }
 }
 
-// rows by an index map: gather dst[i] = src[map[i]], scatter dst[map[i]] = src[i]; strides in elements
-template <typename T>
-__global__ void plc_rows_kernel(T *dst, size_t dst_stride, const T *src, size_t src_stride, const int *map, int cnt, int width, int scatter)
-{
-    const int i = blockIdx.x;
-    if (i >= cnt) return;
-    const T *s = src + (size_t)(scatter ? i : map[i]) * src_stride;
-    T *d = dst + (size_t)(scatter ? map[i] : i) * dst_stride;
-    for (int k = threadIdx.x; k < width; k += blockDim.x) d[k] = s[k];
-}
-// (no caller in the engine since the group kernels below took over run_group's rows; the two forms stay compiled for tools and the resource test)
-template __global__ void plc_rows_kernel<float>(float *, size_t, const float *, size_t, const int *, int, int, int);
-template __global__ void plc_rows_kernel<short>(short *, size_t, const short *, size_t, const int *, int, int, int);
-
 // lpcnet_plc_fec_add's RNN_MOVE on a full ring (src/lpcnet_plc.c:117-121): rows [keep, keep + rows) of one stream's ring move to the front
 __global__ __launch_bounds__(256) void plc_fec_move_kernel(float *ring, int keep, int rows)
 {
@@ -566,30 +513,13 @@ __global__ __launch_bounds__(PLC_FEED_THREADS) void plc_fec_feed_kernel(const in
     for (int k = t; k < b * LPCN_NB_FEAT; k += PLC_FEED_THREADS) ring[at_b * LPCN_NB_FEAT + k] = v[a * LPCN_NB_FEAT + k];      // (b > 0 after a move of no rows: keep == 100)
 }
 
-// A compacted group's rows in and out, one launch each way and one workgroup per stream of the group (engine.hip: run_group).  Row i of the
+// A compacted group's rows in and out, one launch each way and one workgroup per stream of the group (engine_plc.hip: run_group).  Row i of the
 // group's arrays belongs to stream map[i].  In: the state record, then what the group's kind needs -- the 20 features of a frame step, or the
 // kept frame products (1152 + 48 + 16 floats) a tail group continues from -- and the N samples to impose.  Out: the N samples, the state
 // unless the run was a trial, and the frame products where the group keeps them.  State records are 3592 bytes, so 8-byte aligned: they move
 // in int2.  The engine's own rows (products, the group's features and PCM, the PCM queue) are 16-byte aligned and move in float4 / int4; a
 // caller's features or PCM move that way only where the engine found pointer and stride aligned (feat_vec, pcm_vec), else one element at a time.
 constexpr int PLC_GROUP_THREADS = 256;
-struct GroupRows {
-    const int *map;
-    int cnt;
-    lpcn_stream_state *states, *gstates;       // every stream's record; the group's
-    const float *feat;                         // gather: every stream's features (NULL: none)
-    size_t feat_stride;
-    float *gfeat;
-    float *keep_a, *keep_b, *keep_lpc;         // every stream's kept frame products ...
-    float *cond_a, *cond_b, *lpc;              // ... and the group's rows of the frame products
-    short *pcm;                                // gather: the samples to impose; scatter: where the N samples go (NULL: nothing moves)
-    size_t pcm_stride;
-    short *gpcm;
-    int N;
-    int feat_vec, pcm_vec;
-    int keep;                                  // gather: the kept products come in; scatter: the group's products are kept
-    int state_back;                            // scatter: the states go back
-};
 static_assert(sizeof(lpcn_stream_state) % sizeof(int2) == 0, "state records move in int2");
 template <typename V>
 __device__ inline void group_copy(void *dst, const void *src, int count, int t)

@@ -231,16 +231,16 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
     for (int c = 0; c < 4; ++c) {
         const LostChain &ch = chain[c];
         chain_first[c] = P.launches.size();
-        for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, ch.flush[k], PLC_G_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
+        for (int k = 0; k < LPCN_PLC_FBUF; ++k) plc_emit_group(P, ch.flush[k], LPCN_GROUP_FRAMES, LPCN_FRAME_SIZE, 0, 1 + k, 0, 0, 0, true, false);
         for (int r = 0; r < 3; ++r) {
             plc_emit(P, PLC_T_PRED, 0, ch.rpred[r], PLC_PRED_REC);
-            plc_emit_group(P, ch.r160[r], PLC_G_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
-            plc_emit_group(P, ch.r80[r], PLC_G_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
+            plc_emit_group(P, ch.r160[r], LPCN_GROUP_FRAME_SAMPLES, LPCN_FRAME_SIZE, LPCN_FRAME_SIZE, 0, 1, 0, 0, true, true);
+            plc_emit_group(P, ch.r80[r], LPCN_GROUP_FRAME_SAMPLES, 80, 80, 0, 1, 0, 0, true, true);
             plc_emit(P, PLC_T_MIX, PLC_MIX_QSHIFT, ch.rshift[r], PLC_MIX_REC);
         }
-        plc_emit_group(P, ch.lostmap, PLC_G_TAIL, 80, 0, 0, 0, 1, 0, true, false);
+        plc_emit_group(P, ch.lostmap, LPCN_GROUP_TAIL, 80, 0, 0, 0, 1, 0, true, false);
         plc_emit(P, PLC_T_PRED, 0, ch.fpred, PLC_PRED_REC);
-        plc_emit_group(P, ch.lostmap, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
+        plc_emit_group(P, ch.lostmap, LPCN_GROUP_FRAME_SAMPLES, 80, 0, 0, 0, 1, 80, true, true);
     }
     chain_first[4] = P.launches.size();
     // received streams up to the analysis
@@ -249,16 +249,16 @@ int plc_plan(int options, int n, lpcn_plc_ctl *ctl, const unsigned char *lost, P
     plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa1, PLC_MIX_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_FAPPEND, fa2, PLC_MIX_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_RESETSIG, resetsig, PLC_MIX_REC);
-    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 0, 0, 0, 0, 0, false, false);      // into the group's PCM; the states are not written back (the reference's copy / restore)
+    plc_emit_group(P, xgrp, LPCN_GROUP_FRAME_SAMPLES, 80, 0, 0, 0, 0, 0, false, false);      // into the group's PCM; the states are not written back (the reference's copy / restore)
     plc_emit(P, PLC_T_MIX, PLC_MIX_XFADE, xfade, PLC_MIX_REC);
-    plc_emit_group(P, xgrp, PLC_G_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
+    plc_emit_group(P, xgrp, LPCN_GROUP_FRAME_SAMPLES, 80, 80, 0, 2, 0, 0, true, true);
     plc_emit(P, PLC_T_MIX, PLC_MIX_QTAIL, qtail, PLC_MIX_REC);
     plc_emit(P, PLC_T_MIX, PLC_MIX_QAPPEND, qappend, PLC_MIX_REC);
     if (lanes > 1) {
         // the chains onto the lanes: by the sample steps they take, longest first, each onto the lane with the least so far (lane 0 starts with the
         // received streams' chain); then one range of group rows per lane, as long as the lane's largest group -- the lanes hold disjoint streams,
         // so the ranges fit the n rows
-        auto steps = [&](size_t first, size_t last) { int t = 0; for (size_t k = first; k < last; ++k) if (P.launches[k].type == PLC_T_GROUP && P.launches[k].kind != PLC_G_FRAMES) t += P.launches[k].N; return t; };
+        auto steps = [&](size_t first, size_t last) { int t = 0; for (size_t k = first; k < last; ++k) if (P.launches[k].type == PLC_T_GROUP && P.launches[k].kind != LPCN_GROUP_FRAMES) t += P.launches[k].N; return t; };
         int load[PLC_MAX_LANES] = {steps(chain_first[4], P.launches.size())}, cost[4];
         bool dealt[4] = {false, false, false, false};
         for (int c = 0; c < 4; ++c) cost[c] = steps(chain_first[c], chain_first[c + 1]);

@@ -11,7 +11,6 @@
 #include "plc_records.h"
 
 enum { PLC_T_BURG, PLC_T_PRED, PLC_T_MIX, PLC_T_GROUP, PLC_T_ANALYSIS };
-enum { PLC_G_FRAMES, PLC_G_FRAME_SAMPLES, PLC_G_TAIL };
 struct PlcLaunch {
     int type = 0, op = 0, off = 0, cnt = 0;
     // groups: what runs on the compacted streams, where its features and PCM come from and go to

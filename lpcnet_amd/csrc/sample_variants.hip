@@ -1,6 +1,6 @@
 // Instantiations of the persistent sample kernel for ONE streams-per-workgroup value (compile with -DLPCN_S=1|2|4):
 // items per lane (register-resident GRU-A variants) x blob flavour (fp32 / int8) x arithmetic (PARITY / FAST).
-// Split from engine.hip so that the three values build in parallel.
+// Units of their own beside the engine's so that the three values build in parallel.
 #include "sample_kernel.hip.h"
 #include "sample_launch.hip.h"
 #include "sample_variants.h"

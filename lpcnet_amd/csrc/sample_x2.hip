@@ -10,7 +10,7 @@ static int launch_x2(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_
     return lpcn_launch_sample_kernel<lpcn::sample_kernel_x2<NW>>(grid, lds, st, d_args);
 }
 
-// returns a hipError_t value (0 = launched) or LPCN_NO_SUCH_VARIANT, which fails the caller's launch like any HIP error (engine.hip: launch_sample)
+// returns a hipError_t value (0 = launched) or LPCN_NO_SUCH_VARIANT, which fails the caller's launch like any HIP error (engine_synth.hip: launch_sample)
 extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args)
 {
     switch (nw) {

@@ -1,6 +1,6 @@
 """Batched packet-loss concealment on EVERY form of the sample kernel and at outage scale.
 
-Every group of a PLC step (run_group, engine.hip) launches with the batch's own streams per workgroup, two-workgroups-per-CU choice and twelve-wave
+Every group of a PLC step (run_group, engine_plc.hip) launches with the batch's own streams per workgroup, two-workgroups-per-CU choice and twelve-wave
 choice.  A batch of at most one stream per CU picks one stream per workgroup, so tests/test_gpu_plc.py and tests/test_gpu_plc_i8.py compare the
 concealment on that form alone; the service shape runs eight.  Here the forms are pinned (as tests/test_gpu_loud.py pins them) and the same
 fixtures decide: the reference's own output in tests/golden/golden_plc_v1.npz (generic-C float build) and golden_plc_i8_v1.npz (generic-C int8

@@ -2,8 +2,8 @@
 """Register / scratch accounting of the sample kernel's variants from the compiler's own output (no GPU needed).
 
     python tools/kernel_resources.py [--s 4] [--asm-dir DIR] [--json]
-    python tools/kernel_resources.py --analysis          (the feature-analysis kernels of engine.hip)
-    python tools/kernel_resources.py --encode            (the encoder kernels of engine.hip)
+    python tools/kernel_resources.py --analysis          (the feature-analysis kernels of the engine's units)
+    python tools/kernel_resources.py --encode            (the encoder kernels of the engine's units)
 
 Compiles lpcnet_amd/csrc/sample_variants.hip for gfx950 to assembly (device only, same flags as lpcnet_amd/build.py),
 then reports per kernel: VGPR / SGPR counts, spill counts, scratch bytes (the .amdhsa metadata), and how many scratch
@@ -18,6 +18,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -125,17 +126,20 @@ ENCODE_PATTERN = r"N4lpcn\d+(encode_[a-z_]+_kernel(?:ILb[01]E)?)E"
 
 
 def engine_kernel_resources(pattern=r"N4lpcn\d+(analysis_[a-z]+_kernel)E", asm_path=None):
-    """Resources of the kernels of engine.hip (frame, decode and ANALYSIS kernels) whose mangled name matches `pattern` (group 1 = the key), from the compiler's
-    metadata: {demangled-ish name: dict(vgpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, max_flat_workgroup_size)}.  No GPU needed."""
+    """Resources of the kernels of the engine's units (build.ENGINE_UNITS: frame, decode, analysis, encoder, PLC and probe kernels) whose mangled name
+    matches `pattern` (group 1 = the key), from the compiler's metadata: {demangled-ish name: dict(vgpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds,
+    max_flat_workgroup_size)}.  asm_path caches the first unit's assembly; the other units' go beside it as <unit>.s.  No GPU needed."""
     from lpcnet_amd import build
     tmp = None
     if asm_path is None:
         tmp = tempfile.mkdtemp(prefix="lpcn_engine_asm_")
         asm_path = os.path.join(tmp, "engine.s")
-    if not os.path.exists(asm_path):
-        subprocess.check_call([build.HIPCC] + build.HIP_FLAGS + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "engine.hip"), "-o", asm_path],
-                              stderr=subprocess.DEVNULL)
-    text = open(asm_path).read()
+    paths = [asm_path] + [os.path.join(os.path.dirname(asm_path), u + ".s") for u in build.ENGINE_UNITS[1:]]
+    jobs = [[build.HIPCC] + build.HIP_FLAGS + ["--cuda-device-only", "-S", os.path.join(build.CSRC, u + ".hip"), "-o", p]
+            for u, p in zip(build.ENGINE_UNITS, paths) if not os.path.exists(p)]
+    with ThreadPoolExecutor(max_workers=len(paths)) as ex:
+        list(ex.map(lambda cmd: subprocess.check_call(cmd, stderr=subprocess.DEVNULL), jobs))
+    text = "".join(open(p).read() for p in paths)
     out = {}
     for rec in re.split(r"\n\s+- \.agpr_count:", text)[1:]:
         nm = re.search(r"\.name:\s+(\S+)", rec)
@@ -159,8 +163,8 @@ def main():
     ap.add_argument("--s", type=int, default=4, help="streams per workgroup: 1, 2, 4, 8 = the two-group kernel, or 12 = its twelve-wave form")
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--json", action="store_true")
-    ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of engine.hip instead")
-    ap.add_argument("--encode", action="store_true", help="report the encoder kernels of engine.hip (encode_kernels.hip.h) instead")
+    ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of the engine's units instead")
+    ap.add_argument("--encode", action="store_true", help="report the encoder kernels of the engine's units (encode_kernels.hip.h) instead")
     a = ap.parse_args()
     if a.encode:
         print(json.dumps(engine_kernel_resources(ENCODE_PATTERN, os.path.join(a.asm_dir, "engine.s") if a.asm_dir else None), indent=1))
