@@ -11,7 +11,7 @@
 //
 //      interval A:  P3 of the one group (its GRU-B chains on waves 0..3, its candidate heads on the head waves) and, on each chain
 //                   wave, stage 1 of its stream's P4 (the tree in two stages, tree_stages.h), followed, on every wave, by P1 of the OTHER
-//                   group; stage 2 of the four streams' trees is one pass of row wave LPCN_X2_S2W behind its items                      | barrier
+//                   group; stage 2 of the four streams' trees is one pass of wave LPCN_X2_S2W behind its items                          | barrier
 //      interval B:  P2 of that other group                                                                   | barrier, the groups swap roles
 //
 // so a wave is never short of work that does not depend on the chain it has just fed: the leader / gather latency of one group's
@@ -25,13 +25,14 @@
 #pragma once
 #include "sample_kernel.hip.h"
 #include "tree_stages.h"
+#include "slot_plan.h"
 
 namespace lpcn {
 
 #define LPCN_X2_LW 4            // the wave that leads the streams (LPC predictor, mu-law): a head wave (model_pack.c gives it the shortest candidate slot) -- waves 0..3 start GRU-B's chains at once
 #define LPCN_X2_TW 0            // the wave that draws the KISS99 thresholds: a chain wave -- they have the most slack at barrier 1 (wave 0 / 1 / 3 / 5 / 6: 149.5 / 148.9 / 145.0 / 147.4 / 143.5 M; leader on wave 5 / 7: 139.3 / 138.2 M against 146.7 M on wave 4, round 6)
-#define LPCN_X2_S2W 7           // the row wave that runs stage 2 of the four streams' trees in one pass (never the leader's: it has the least slack at barrier 1)
-#define LPCN_X2_S2_LEAD 2       // ... and how many of its P1 items from the end it polls the streams' prefixes and issues the loads of its rows (2 / 4 / 8: 171.8 / 171.3 / 170.2 M; at least 1)
+#define LPCN_X2_S2W 1           // the wave that runs stage 2 of the four streams' trees in one pass: any but the leader's (it has the least slack at barrier 1).  Wave 0 / 1 / 5 / 7: 168.4 / 175.6 / 173.5 / 175.0 M (round 10; chain wave 1 has the fewest items of the waves that do not draw the thresholds)
+#define LPCN_X2_S2_LEAD 2       // ... and how many of its P1 items from the end it polls the streams' prefixes and issues the loads of its rows (on row wave 7, round 9: 2 / 4 / 8: 171.8 / 171.3 / 170.2 M; on wave 1, round 10: 1 / 2 / 4: 175.8 / 175.6 / 175.5 M, a tie; at least 1)
 #define LPCN_X2_HG 10           // head items a row wave runs before it polls the leader's indices for the start-value pass (6 / 10 / 14 / 18: 145.0 / 146.7 / 146.2 / 144.3 M)
 
 struct LdsX2 {
@@ -186,9 +187,9 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     const bool has2 = (has_slot & 4) != 0;
     const int hl = __builtin_amdgcn_readfirstlane(as_global(Ap->a_head)[tid0 >> 6]);
     const bool early_wave = hl > 0;                          // wave-uniform: this wave computes the head of its candidate slot one sample ahead
-    // wave-uniform: no row of this wave starts from bias + diag*h formed in P1 -- slot 0 continues from its head's partial sums (or holds update / reset rows only), slots 1, 2
-    // hold no candidate rows: the slot start is then ONE cell read (the row waves of the benchmark model's dealing)
-    const bool plain_start = __builtin_amdgcn_readfirstlane(((early_wave || __ballot(row_reg[0] >= 2 * NA) == 0ull) && __ballot(row_reg[1] >= 2 * NA || row_reg[2] >= 2 * NA) == 0ull) ? 1 : 0) != 0;
+    // wave-uniform: what the slot start and the close of P1 do on this wave (slot_plan.h)
+    auto any_row = [&](const int k, const int lo, const int hi) __attribute__((always_inline)) { return __ballot(row_reg[k] >= lo && row_reg[k] < hi) != 0ull ? 1 << k : 0; };
+    int plan = __builtin_amdgcn_readfirstlane(lpcn_slot_plan(any_row(0, 0, RA) | any_row(1, 0, RA) | any_row(2, 0, RA), any_row(0, 2 * NA, RA) | any_row(1, 2 * NA, RA) | any_row(2, 2 * NA, RA), b1, b2, b3, hl));
 
     // ------------------------------------------------------------------ LDS residents -------
     {
@@ -515,7 +516,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 // for another stream's chain).  Streams that are not live, clamped copies and teacher-forced samples run the same code; the leader ignores the value.
                 // Round 9: the chain waves are the pole of the interval, so stage 2 is not theirs any more.  The wave publishes its five decided bits under the
                 // sample's sequence number -- one word, behind its state stores, so whoever reads the tag of this sample reads this sample's prefix and state --
-                // and goes on to P1; wave LPCN_X2_S2W runs stage 2 of all four streams in one pass (below, behind its items).
+                // and goes on to P1; wave LPCN_X2_S2W runs stage 2 of all four streams in one pass (below, behind its items).  Round 10: that wave may be a chain
+                // wave again -- ONE of them, the one with the fewest items, for all four streams: its own prefix it has published itself, earlier in program order.
                 const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
                 const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
                 if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
@@ -575,8 +577,9 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         // four carry this sample's sequence number, then fetches the row of its node in the subtree its stream's prefix names (4 global_load_dwordx4 +
         // 2 dwords per lane).  This happens LPCN_X2_S2_LEAD items before the end of the wave's P1 items: the rows land under those, and the chains
         // have published by then -- in front of the items the wave would wait ~1.2 k clk for them (the row waves open their items while the chain
-        // waves are still in their gates) and become the pole itself.
-        static_assert(LPCN_X2_S2W > LPCN_X2_LW && LPCN_X2_S2W < LPCN_WAVES && LPCN_TREE_FIELDS == S && LPCN_X2_S2_LEAD >= 1, "stage 2 runs on a row wave other than the leader's, one field per stream");
+        // waves are still in their gates) and become the pole itself.  (`sub` is loaded here, behind the chain waves' block: a chain wave that hosts the pass
+        // never holds stage 1's rows and stage 2's at once.)
+        static_assert(LPCN_X2_S2W != LPCN_X2_LW && LPCN_X2_S2W >= 0 && LPCN_X2_S2W < LPCN_WAVES && LPCN_TREE_FIELDS == S && LPCN_X2_S2_LEAD >= 1, "stage 2 runs on any wave but the leader's, one field per stream");
         const bool s2_wave = q_chain && wave == LPCN_X2_S2W;      // (wave-uniform)
         TreeRow sub = {};
         int pfx = 0;
@@ -599,10 +602,18 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             load_negz();
             lds_poll_until<false>(p0cnt_p, seqP * NP0);       // the start values of the update / reset rows and the candidate inputs come from P0
             LPCN_X2_PROF(11);                                // wait for the start-value pass of the four row waves
-            // slot 0 becomes the running row: candidate rows start from bias + diag*h -- or from the sums their head has parked --, update / reset
-            // rows from their P0 cell; candidate rows further down park bias + diag*h in their own cell
+            // a slot becomes the running row: candidate rows start from bias + diag*h -- or from the sums their head has parked --, update / reset
+            // rows from their P0 cell; candidate rows further down park bias + diag*h in their own cell.  Which slot, and which slots need
+            // bias + diag*h at all: slot_plan.h.  (Round 10 also measured this start without slot 0's cell read where all its rows are unparked
+            // candidates -- chain waves 2 and 3 of the benchmark model -- and as one loop over the slots that serves the plain waves too:
+            // 174.9 and 173.2 against 175.6 M.  Less work, slower; EXPERIMENTS.md.)
+            LPCN_REMAT_S(plan);
+            const bool plain_start = lpcn_slot_plain_start(plan);
+            // wave-uniform: no row of this wave starts from bias + diag*h formed in P1 (the row waves of the benchmark model's dealing): the slot start is
+            // then ONE cell read, of the first slot that has items -- the slots in front of it are not walked through
+            const int first = lpcn_slot_first(plan);
             if (plain_start) {
-                int r = LPCN_ROW(0);
+                int r = first == 0 ? LPCN_ROW(0) : first == 1 ? LPCN_ROW(1) : LPCN_ROW(2);
                 LPCN_REMAT_V(r);
                 r = r < 0 ? 0 : r;
                 const float *c = pre_cell(r, gp);
@@ -611,6 +622,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             } else {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
+                if (k > 0 && !lpcn_slot_forms_start(plan, k)) continue;      // (wave-uniform: update / reset rows are picked up from their cell, an empty slot needs nothing)
                 int r = LPCN_ROW(k);
                 LPCN_REMAT_V(r);
                 const bool live_row = r >= 0;
@@ -619,7 +631,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 const int n = candidate ? r - 2 * NA : 0;
                 const float bias = sm_abias[2 * r], diag = sm_abias[2 * r + 1];
                 float *c = pre_cell(r, gp);
-                const bool parked = k == 0 && early_wave;
+                const bool parked = lpcn_slot_parked(plan, k);
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
                     const float bv = bias + diag * hT_p[n * S + s];
@@ -661,14 +673,15 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             // All tests below are wave-uniform scalar branches; an ordinary item falls through every one of them.
             int s2_at = s2_in_items ? (jend > LPCN_X2_S2_LEAD ? jend - LPCN_X2_S2_LEAD : 0) : NW + 1;      // stage 2 of Q's trees opens in front of this item
             LPCN_REMAT_S(s2_at);
-            int nextb = b1 < s2_at ? b1 : s2_at;
+            int nextb = first >= 1 ? (first >= 2 || b2 <= 0 ? NW : b2) : b1;      // (the slots in front of the one the start has opened have no items)
+            if (s2_at < nextb) nextb = s2_at;
             LPCN_REMAT_S(nextb);
             auto item = [&](const int j) __attribute__((always_inline)) -> bool {           // false: this wave has no more items
                 if (__builtin_expect(j >= jend, 0)) return false;
                 if (j + PF < NW) fetch_h(j + PF);
                 if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty) and the stage-2 wave's opening: ONE compare per item against the next one
-                    if (j == b1) row_swap(0, 1);
-                    if (j == b2) row_swap(1, 2);
+                    if (lpcn_slot_moves(plan, 1, j, b1)) row_swap(0, 1);
+                    if (lpcn_slot_moves(plan, 2, j, b2)) row_swap(1, 2);
                     if (j == s2_at) s2_open();
                     __builtin_amdgcn_s_waitcnt(0xC07F);
                     nextb = b1 > j ? b1 : (b2 > j ? b2 : NW);
@@ -686,17 +699,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             };
             run_items(run_items, std::integral_constant<int, 0>{});
             LPCN_X2_PROF(5);
-            // close whichever slot is still open; slots that start exactly at the end have no items
-            if (b1 >= jend) {
-                row_swap(0, 1);
-                row_swap(1, 2);
-                row_store(2);
-            } else if (b2 >= jend) {
-                row_swap(1, 2);
-                row_store(2);
-            } else {
-                row_store(2);
-            }
+            // close: the slot the last item belongs to is stored; the slots behind it have no items and their cells hold their values already
+            if (lpcn_slot_last(plan) == 0) row_store(0);
+            else if (lpcn_slot_last(plan) == 1) row_store(1);
+            else row_store(2);
             LPCN_X2_PROF(6);
         }
         // ---------------------------------------------------------------- P4 of group Q, stage 2, second part ----

@@ -107,6 +107,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--int8", action="store_true")
     ap.add_argument("--x2", action="store_true", help="the two-group kernel's dealing (LPCN_DEAL_FORCE_X2, 2048 streams, eight per workgroup); candidate slots move too")
+    ap.add_argument("--keep-candidates", action="store_true", help="with --x2: move update / reset slots only (the candidate slots stay where the dealing puts them)")
     ap.add_argument("--start", default="", help="comma-separated start map instead of the model's dealing")
     a = ap.parse_args()
     global X2
@@ -120,7 +121,7 @@ def main():
         base = max(bench(wv, a.int8), bench(wv, a.int8))
     print("model's dealing:", " ".join(("c" if c else "") + f"{n}:{w}" for c, n, w in slots), "-> %.2f M" % base, flush=True)
     best, best_v = list(wv), base
-    zr = [i for i, s in enumerate(slots) if not s[0] or X2]
+    zr = [i for i, s in enumerate(slots) if not s[0] or (X2 and not a.keep_candidates)]
     for rnd in range(a.rounds):
         improved = False
         cands = []
