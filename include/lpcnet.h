@@ -131,6 +131,11 @@ LPCNET_EXPORT int lpcnet_hip_check_model(const unsigned char *data, int len, int
  * (the other kernels run it), -1 = malformed blob.  desc: [12 waves][5 segments]{kind 0 none / 1 whole / 2 head / 3 tail, first item, items, blocks of
  * the rows summed before it}; rows: [12][5][64] GRU-A rows (-1 = none); selftest: 0 = consistent with the blob.  Any of the three may be NULL. */
 LPCNET_EXPORT int lpcnet_hip_x3_image_info(const unsigned char *data, int len, int *desc, int *rows, int *selftest);
+/* Host-only view of the two-group kernel's wide image of GRU-A (its streamed variants, lpcnet_batch_set_two_group_streaming): 1 = the model gets one
+ * (a float blob with a dense GRU-B matrix and 33 .. 96 items per lane in the two-group dealing), 0 = it does not, -1 = malformed blob.
+ * info[21] (may be NULL) = {fits, items per lane, compiled variant, register-resident items of that variant, self-test code (0 = consistent),
+ * items of waves 0..7, candidate-head items of waves 0..7}. */
+LPCNET_EXPORT int lpcnet_hip_x2_wide_info(const unsigned char *data, int len, int *info);
 /* release every device resource held for the single-stream API (optional, e.g. before exit); states stay bound and
  * re-create the device side at their next call */
 LPCNET_EXPORT void lpcnet_hip_shutdown(void);

@@ -251,13 +251,24 @@ LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LP
 
 /* Tuning / introspection */
 LPCNET_EXPORT int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int s);      /* 1, 2, 4, 8; 0 = auto.  8 = the two-group kernel (float blobs with a dense GRU-B matrix and
-                                                                                        * <= 32 GRU-A items per lane, bit-exact arithmetic): chosen automatically beyond four streams per CU */
+                                                                                        * <= 32 GRU-A items per lane, bit-exact arithmetic): chosen automatically beyond four streams per CU.
+                                                                                        * Models of 33 .. 96 items per lane: after lpcnet_batch_set_two_group_streaming(b, 1) */
 LPCNET_EXPORT int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b);
 /* Which form of the two-group kernel runs at eight streams per workgroup: 0 = eight waves (two per SIMD), 1 = twelve waves (three per SIMD; needs the
  * model's twelve-wave image: an error without it), -1 = as measured / as the table says.  Both forms produce the same bits.  get: what a launch of the
  * whole batch runs now (0 / 1). */
 LPCNET_EXPORT int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode);
 LPCNET_EXPORT int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b);
+/* The two-group kernel for models of 33 .. 96 GRU-A items per lane (heavy-tailed, trained-like sparsity): its streamed variants keep 24 items of a
+ * lane in registers and fetch the others from L2 every sample.  Off by default; a batch that does not ask behaves as before.  on = 1 waits for
+ * enqueued work, uploads the model's wide image once, and from then on this batch treats eight streams per workgroup like any two-group model: the
+ * value may be pinned, lpcnet_batch_tune and the first host-pointer call measure it, the group schedule may answer it.  The cost table alone never
+ * chooses eight for such a model.  Same bits as the four-stream kernel.  FAST arithmetic under a pinned eight runs at four, as always; the
+ * twelve-wave form stays unavailable.  on = 0 puts the batch back on the four-stream kernel (LPCNET_HIP_E_ARG while eight is pinned).
+ * A model that has the ordinary two-group image: returns 0 and changes nothing.  int8 blobs, a block-sparse GRU-B matrix, more than 96 items:
+ * LPCNET_HIP_E_MODEL with a message, setting unchanged.  LPCNET_HIP_X2_STREAMED=1, read when a batch is created, switches it on where the model allows. */
+LPCNET_EXPORT int lpcnet_batch_set_two_group_streaming(LPCNetBatch *b, int on);
+LPCNET_EXPORT int lpcnet_batch_get_two_group_streaming(const LPCNetBatch *b);
 /* The group schedule: how the compacted groups of a PLC step or a per-stream step (lpcnet_batch_synthesize_step) are launched.  Off by default.
  * form: 0 = groups launch in the batch's form (default), 1 = in the cost table's form for the group's own size -- while the streams per
  *   workgroup are not pinned and the arithmetic is bit-exact, where every form gives the same samples; a pinned value and FAST keep the batch's form.

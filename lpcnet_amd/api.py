@@ -210,6 +210,9 @@ def load_library():
     L.lpcnet_batch_get_streams_per_workgroup.argtypes = [vp]
     L.lpcnet_batch_set_twelve_waves.argtypes = [vp, C.c_int]
     L.lpcnet_batch_get_twelve_waves.argtypes = [vp]
+    L.lpcnet_batch_set_two_group_streaming.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_get_two_group_streaming.argtypes = [vp]
+    L.lpcnet_hip_x2_wide_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_hip_x3_image_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lpcnet_batch_tune.argtypes = [vp]
     L.lpcnet_batch_enable_timing.argtypes = [vp, C.c_int]
@@ -254,6 +257,15 @@ def x3_image_info(blob: bytes):
     desc, rows, st = (C.c_int * (12 * 5 * 4))(), (C.c_int * (12 * 5 * 64))(), C.c_int(-1)
     have = load_library().lpcnet_hip_x3_image_info(blob, len(blob), desc, rows, C.byref(st))
     return have, np.array(desc, np.int32).reshape(12, 5, 4), np.array(rows, np.int32).reshape(12, 5, 64), st.value
+
+
+def x2_wide_info(blob: bytes):
+    """Host-only view of a blob's wide two-group image (the streamed variants of the two-group kernel; include/lpcnet.h): dict(fits -- 1, 0, or -1
+    for a malformed blob --, items, variant, resident, selftest, b3[8], head[8])."""
+    info = (C.c_int * 21)()
+    rc = load_library().lpcnet_hip_x2_wide_info(blob, len(blob), info)
+    v = list(info)
+    return dict(fits=rc, items=v[1], variant=v[2], resident=v[3], selftest=v[4], b3=v[5:13], head=v[13:21])
 
 
 def last_error() -> str:
@@ -746,6 +758,15 @@ class LPCNetBatch:
     @twelve_waves.setter
     def twelve_waves(self, mode):
         self._chk(self.L.lpcnet_batch_set_twelve_waves(self.p, int(mode)), "set_twelve_waves")
+
+    @property
+    def two_group_streaming(self):
+        """the two-group kernel's streamed variants for this batch (models of 33 .. 96 items per lane; include/lpcnet_batch.h); off by default"""
+        return bool(self.L.lpcnet_batch_get_two_group_streaming(self.p))
+
+    @two_group_streaming.setter
+    def two_group_streaming(self, on):
+        self._chk(self.L.lpcnet_batch_set_two_group_streaming(self.p, 1 if on else 0), "set_two_group_streaming")
 
     @property
     def group_schedule(self):

@@ -27,7 +27,7 @@ CXX_FLAGS = ["-std=c++17" if x == "-std=gnu11" else x for x in C_FLAGS]      # h
 # The engine's host runtime, one unit per subsystem (engine_core.h is what they share; each kernel header belongs to one unit) ...
 ENGINE_UNITS = ("engine", "engine_synth", "engine_codec", "engine_plc", "engine_probe")
 # ... and every object of the library except api.o, which build_small_registry() replaces
-OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS) + ("sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
+OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS) + ("sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x2w.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
 
 
 def source_hashes(extra_flags=()):
@@ -95,8 +95,8 @@ def build(force=False, verbose=True, prof=False):
     jobs = [[HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, u + ".hip"), "-o", os.path.join(objdir, u + ".o")] for u in ENGINE_UNITS]
     for sv in (1, 2, 4):
         jobs.append([HIPCC] + HIP_FLAGS + pf + extra + [f"-DLPCN_S={sv}", "-c", os.path.join(CSRC, "sample_variants.hip"), "-o", os.path.join(objdir, f"sample_s{sv}.o")])
-    jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x2.hip"), "-o", os.path.join(objdir, "sample_x2.o")])
-    jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, "sample_x3.hip"), "-o", os.path.join(objdir, "sample_x3.o")])
+    for u in ("sample_x2", "sample_x2w", "sample_x3"):
+        jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, u + ".hip"), "-o", os.path.join(objdir, u + ".o")])
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, len(os.sched_getaffinity(0)))) as ex:
         list(ex.map(run, jobs))

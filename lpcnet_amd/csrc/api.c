@@ -25,6 +25,7 @@
 #include "lpcnet.h"
 #include "lpcnet_batch.h"
 #include "lpcnet_engine.h"
+#include "sample_variants.h"
 
 #define LPCN_MAGIC 0x4C50434Eu   /* "LPCN" */
 
@@ -1576,6 +1577,9 @@ int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in1
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }
 int lpcnet_batch_tune(LPCNetBatch *b) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_tune(s->dev)); }
 int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x3(s->dev, mode)); }
+/* (every shard holds the same model: a refusal comes from the first shard, before anything has changed) */
+int lpcnet_batch_set_two_group_streaming(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x2_streamed(s->dev, on)); }
+int lpcnet_batch_get_two_group_streaming(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x2_streamed(b->sh[0].dev) : 0; }
 int lpcnet_batch_set_group_schedule(LPCNetBatch *b, int form, int lanes)
 {
     NEED_MODEL(b);
@@ -1755,6 +1759,44 @@ int lpcnet_hip_check_model(const unsigned char *data, int len, int *info)
     lpcn_model_release(&m);
     if (st) { set_err("internal error: device packing inconsistent with blob"); return -1; }
     return 0;
+}
+
+/* Host-only view of the two-group kernel's WIDE image of a blob (sample_kernel_x2.hip.h, the streamed variants of sample_x2w.hip): returns 1 when the
+ * model gets one -- a float blob with a dense GRU-B input matrix and 33 .. 96 items per lane in the two-group dealing --, 0 when it does not (the
+ * ordinary image serves it, or no two-group kernel runs it), -1 for a malformed blob.  info[21] (may be NULL) = {fits, items per lane of the
+ * two-group dealing (0 for int8 blobs), compiled variant, register-resident items of that variant, self-test code, items of waves 0..7 in P1 (b3),
+ * candidate-head items of waves 0..7}; variant, resident items and self-test code are -1 without an image. */
+int lpcnet_hip_x2_wide_info(const unsigned char *data, int len, int *info)
+{
+    static const int variants[] = {
+#define LPCN_LIST_ITEM(n) n,
+        LPCN_VARIANTS_X2W(LPCN_LIST_ITEM)
+#undef LPCN_LIST_ITEM
+        0};
+    lpcn_model_host m, f;
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return -1; }
+    int out[21];
+    memset(out, 0, sizeof(out));
+    out[2] = out[3] = out[4] = -1;
+    int have = lpcn_model_pack_x2_wide(&m, &f) == 0;
+    if (have) {
+        out[1] = f.nw;
+        for (int w = 0; w < LPCN_WAVES; w++) { out[5 + w] = f.pk_a_bound[w][LPCN_MAX_SLOTS]; out[5 + LPCN_WAVES + w] = f.pk_a_head[w]; }
+        for (const int *v = variants; *v && out[2] < 0; v++) if (f.nw <= *v) out[2] = *v;
+        out[3] = LPCN_X2W_NR;
+        f.pk_b_w = m.pk_b_w; f.pk_b_start = m.pk_b_start; f.pk_b_blk = m.pk_b_blk;      /* (the check reads GRU-B's packing too: shared) */
+        out[4] = lpcn_model_selftest(&f);
+        f.pk_b_w = NULL; f.pk_b_start = NULL; f.pk_b_blk = NULL;
+        lpcn_model_release(&f);
+        have = m.b_dense && out[2] > 0 && out[4] == 0;
+    } else if (!m.is_int8 && lpcn_model_pack_x2(&m, &f) == 0) {      /* (the ordinary image: its item count, for the caller's information) */
+        out[1] = f.nw;
+        lpcn_model_release(&f);
+    }
+    out[0] = have;
+    if (info) memcpy(info, out, sizeof(out));
+    lpcn_model_release(&m);
+    return have;
 }
 
 /* Host-only view of the twelve-wave image of a blob (sample_kernel_x3.hip.h): returns 1 when the model has one, 0 when it does not fit

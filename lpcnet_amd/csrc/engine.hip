@@ -56,6 +56,7 @@ static int upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
 static const int variants_f32[] = {LPCN_VARIANTS_F32(LPCN_LIST_ITEM) 0};
 static const int variants_i8[] = {LPCN_VARIANTS_I8(LPCN_LIST_ITEM) 0};
 static const int variants_x2[] = {LPCN_VARIANTS_X2(LPCN_LIST_ITEM) 0};
+static const int variants_x2w[] = {LPCN_VARIANTS_X2W(LPCN_LIST_ITEM) 0};
 #undef LPCN_LIST_ITEM
 // the smallest compiled variant that holds nw items per lane (0: none does)
 static int round_up_variant(const int *v, int nw) { for (; *v; ++v) if (nw <= *v) return *v; return 0; }
@@ -122,6 +123,58 @@ static int plc_upload_net_i8(lpcn_engine *e, const lpcn_plc_model *p)
     return 0;
 }
 
+// GRU-A as dealt to waves and lanes (model_pack.c) + the embedding tables in that lane order: everything that depends on the dealing.  `a`: the
+// PARITY image's block, for what does not
+static int upload_gru_a(lpcn_engine *e, const LpcnSampleArgs &a, const lpcn_model_host *mm, GruAImage &img, int nwv_)
+{
+    LpcnSampleArgs &dst = img.args;
+    dst = a;                                               // (what does not depend on the dealing is PARITY's)
+    // re-pad the item arrays from the model's nw to the compiled variant
+    const size_t item_dw = mm->is_int8 ? 1 : 4;            // dwords per (lane, item)
+    const uint32_t *src = mm->is_int8 ? (const uint32_t *)mm->pk_a_wq : (const uint32_t *)mm->pk_a_w;
+    std::vector<uint32_t> w((size_t)LPCN_WAVES * nwv_ * 64 * item_dw, 0u);
+    std::vector<uint8_t> b((size_t)LPCN_WAVES * nwv_ * 64, 0);
+    for (int wv = 0; wv < LPCN_WAVES; ++wv)
+        for (int j = 0; j < mm->nw; ++j) {
+            // the early head of slot 0, [nw - head, nw) in the model, stays end-aligned in the compiled variant's item array
+            const int jd = j >= mm->nw - mm->pk_a_head[wv] ? j + (nwv_ - mm->nw) : j;
+            memcpy(&w[((size_t)wv * nwv_ + jd) * 64 * item_dw], &src[((size_t)wv * mm->nw + j) * 64 * item_dw], 64 * item_dw * 4);
+            memcpy(&b[((size_t)wv * nwv_ + jd) * 64], &mm->pk_a_blk[((size_t)wv * mm->nw + j) * 64], 64);
+        }
+    const uint32_t *d = nullptr;
+    int rc_ = 0;
+    if ((rc_ = upload<uint32_t>(e, &d, w.data(), w.size()))) return rc_;
+    dst.a_w = (const float4 *)d;
+    if ((rc_ = upload<uint8_t>(e, &dst.a_blk, b.data(), b.size()))) return rc_;
+    int bound[LPCN_WAVES * 4], allh[LPCN_WAVES * 3];
+    for (int wv = 0; wv < LPCN_WAVES; ++wv) {
+        for (int k = 0; k < 4; ++k) bound[wv * 4 + k] = mm->pk_a_bound[wv][k];
+        for (int k = 0; k < 3; ++k) allh[wv * 3 + k] = mm->pk_a_allh[wv][k];
+    }
+#define UPD(T, field, srcp, count) if ((rc_ = upload<T>(e, &dst.field, srcp, count))) return rc_
+    UPD(int, a_row, mm->pk_a_row, LPCN_WAVES * 3 * 64);
+    UPD(int, a_bound, bound, LPCN_WAVES * 4);
+    UPD(int, a_allh, allh, LPCN_WAVES * 3);
+    UPD(int, a_head, mm->pk_a_head, LPCN_WAVES);
+    if (mm->pk_emb[0]) {                                  // (the two-group kernel's image has no lane-ordered tables)
+        UPD(float, emb_sig, mm->pk_emb[0], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
+        UPD(float, emb_pred, mm->pk_emb[1], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
+        UPD(float, emb_exc, mm->pk_emb[2], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
+    }
+#undef UPD
+    img.nw_variant = nwv_; img.present = true;
+    return 0;
+}
+
+// the embedding tables in the blob's own [256][1152] order: the start-value pass of the two-group kernel, their only reader
+static int upload_nat_tables(lpcn_engine *e, LpcnSampleArgs &ax, const float *sig, const float *pred, const float *exc)
+{
+    int rc = upload<float>(e, &ax.emb_nat_sig, sig, (size_t)256 * LPCN_ROWS_A);
+    if (!rc) rc = upload<float>(e, &ax.emb_nat_pred, pred, (size_t)256 * LPCN_ROWS_A);
+    if (!rc) rc = upload<float>(e, &ax.emb_nat_exc, exc, (size_t)256 * LPCN_ROWS_A);
+    return rc;
+}
+
 extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_model_host *m)
 {
     *out = nullptr;
@@ -146,47 +199,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return fail(LPCN_E_HIP);
 
     LpcnSampleArgs &a = e->image[IMG_PARITY].args;
-    // GRU-A as dealt to waves and lanes (model_pack.c) + the embedding tables in that lane order: everything that depends on the dealing
-    auto upload_gru_a = [&](const lpcn_model_host *mm, GruAImage &img, int nwv_) -> int {
-        LpcnSampleArgs &dst = img.args;
-        dst = a;                                               // (what does not depend on the dealing is PARITY's)
-        // re-pad the item arrays from the model's nw to the compiled variant
-        const size_t item_dw = mm->is_int8 ? 1 : 4;            // dwords per (lane, item)
-        const uint32_t *src = mm->is_int8 ? (const uint32_t *)mm->pk_a_wq : (const uint32_t *)mm->pk_a_w;
-        std::vector<uint32_t> w((size_t)LPCN_WAVES * nwv_ * 64 * item_dw, 0u);
-        std::vector<uint8_t> b((size_t)LPCN_WAVES * nwv_ * 64, 0);
-        for (int wv = 0; wv < LPCN_WAVES; ++wv)
-            for (int j = 0; j < mm->nw; ++j) {
-                // the early head of slot 0, [nw - head, nw) in the model, stays end-aligned in the compiled variant's item array
-                const int jd = j >= mm->nw - mm->pk_a_head[wv] ? j + (nwv_ - mm->nw) : j;
-                memcpy(&w[((size_t)wv * nwv_ + jd) * 64 * item_dw], &src[((size_t)wv * mm->nw + j) * 64 * item_dw], 64 * item_dw * 4);
-                memcpy(&b[((size_t)wv * nwv_ + jd) * 64], &mm->pk_a_blk[((size_t)wv * mm->nw + j) * 64], 64);
-            }
-        const uint32_t *d = nullptr;
-        int rc_ = 0;
-        if ((rc_ = upload<uint32_t>(e, &d, w.data(), w.size()))) return rc_;
-        dst.a_w = (const float4 *)d;
-        if ((rc_ = upload<uint8_t>(e, &dst.a_blk, b.data(), b.size()))) return rc_;
-        int bound[LPCN_WAVES * 4], allh[LPCN_WAVES * 3];
-        for (int wv = 0; wv < LPCN_WAVES; ++wv) {
-            for (int k = 0; k < 4; ++k) bound[wv * 4 + k] = mm->pk_a_bound[wv][k];
-            for (int k = 0; k < 3; ++k) allh[wv * 3 + k] = mm->pk_a_allh[wv][k];
-        }
-#define UPD(T, field, srcp, count) if ((rc_ = upload<T>(e, &dst.field, srcp, count))) return rc_
-        UPD(int, a_row, mm->pk_a_row, LPCN_WAVES * 3 * 64);
-        UPD(int, a_bound, bound, LPCN_WAVES * 4);
-        UPD(int, a_allh, allh, LPCN_WAVES * 3);
-        UPD(int, a_head, mm->pk_a_head, LPCN_WAVES);
-        if (mm->pk_emb[0]) {                                  // (the two-group kernel's image has no lane-ordered tables)
-            UPD(float, emb_sig, mm->pk_emb[0], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
-            UPD(float, emb_pred, mm->pk_emb[1], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
-            UPD(float, emb_exc, mm->pk_emb[2], (size_t)256 * LPCN_MAX_SLOTS * LPCN_WG_THREADS);
-        }
-#undef UPD
-        img.nw_variant = nwv_; img.present = true;
-        return 0;
-    };
-    if ((rc = upload_gru_a(m, e->image[IMG_PARITY], nwv))) return fail(rc);
+    if ((rc = upload_gru_a(e, a, m, e->image[IMG_PARITY], nwv))) return fail(rc);
 #define UP(T, field, src, count) if ((rc = upload<T>(e, &a.field, src, count))) return fail(rc)
     UP(float, a_bias1, m->a_bias + LPCN_ROWS_A, LPCN_ROWS_A);
     UP(float, a_diag, m->a_diag, LPCN_ROWS_A);
@@ -236,15 +249,26 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
             const int stx = lpcn_model_selftest(&mx);
             mx.pk_b_w = nullptr; mx.pk_b_start = nullptr; mx.pk_b_blk = nullptr;
             if (nwx && stx == 0) {
-                LpcnSampleArgs &ax = e->image[IMG_X2].args;
-                rc = upload_gru_a(&mx, e->image[IMG_X2], nwx);
-                // ... and the tables in the blob's own [256][1152] order: the start-value pass of the two-group kernel, their only reader
-                if (!rc) rc = upload<float>(e, &ax.emb_nat_sig, m->emb_sig, (size_t)256 * LPCN_ROWS_A);
-                if (!rc) rc = upload<float>(e, &ax.emb_nat_pred, m->emb_pred, (size_t)256 * LPCN_ROWS_A);
-                if (!rc) rc = upload<float>(e, &ax.emb_nat_exc, m->emb_exc, (size_t)256 * LPCN_ROWS_A);
+                rc = upload_gru_a(e, a, &mx, e->image[IMG_X2], nwx);
+                if (!rc) rc = upload_nat_tables(e, e->image[IMG_X2].args, m->emb_sig, m->emb_pred, m->emb_exc);
             }
             lpcn_model_release(&mx);
             if (rc) return fail(rc);
+        } else {
+            // more than 32 items per lane: the STREAMED variants' image (lpcn_model_pack_x2_wide) is dealt and checked here, on the host, and kept
+            // with a copy of the tables; the first batch that asks (lpcn_batch_dev_set_x2_streamed) uploads it as IMG_X2
+            auto wh = std::make_unique<X2WideHost>();
+            if (lpcn_model_pack_x2_wide(m, &wh->mx) == 0) {
+                wh->packed = true;
+                wh->mx.pk_b_w = m->pk_b_w; wh->mx.pk_b_start = m->pk_b_start; wh->mx.pk_b_blk = m->pk_b_blk;
+                const int stw = lpcn_model_selftest(&wh->mx);
+                wh->mx.pk_b_w = nullptr; wh->mx.pk_b_start = nullptr; wh->mx.pk_b_blk = nullptr;
+                if (stw == 0 && round_up_variant(variants_x2w, wh->mx.nw)) {
+                    const float *src[3] = {m->emb_sig, m->emb_pred, m->emb_exc};
+                    for (int t = 0; t < 3; ++t) wh->emb[t].assign(src[t], src[t] + (size_t)256 * LPCN_ROWS_A);
+                    e->x2w_host = std::move(wh);
+                }
+            }
         }
         // ... and its twelve-wave form on the image of lpcn_model_pack_x3, where the model has one (a model without keeps the eight-wave kernels)
         lpcn_x3_image im;
@@ -282,7 +306,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
         if (pf < 0) { snprintf(g_err, sizeof(g_err), "packing the FAST image of GRU-A failed"); return fail(LPCN_E_MODEL); }
         if (pf == 0) {
             const int nwf = round_up_variant(variants_i8, mf.nw);
-            if (nwf) rc = upload_gru_a(&mf, e->image[IMG_FAST], nwf);
+            if (nwf) rc = upload_gru_a(e, a, &mf, e->image[IMG_FAST], nwf);
             lpcn_model_release(&mf);
             if (rc) return fail(rc);
         }
@@ -429,7 +453,9 @@ int auto_streams_per_wg(const lpcn_batch_dev *b, int n)
         else t = (float)((wgs + cus - 1) / cus) * step[k];
         if (k == 0 || t < best_t) { best = S; best_t = t; }
     }
-    if (x2_available(b)) {                                   // eight streams per workgroup: a round of the two-group kernel (us per sample step)
+    // (a wide image -- the streamed variants, a batch's opt-in -- is never the table's choice: at 2 048 streams eight against four was +17.3 % on
+    // the 36-item model and -2.8 % at skew 0.1, EXPERIMENTS.md round 11 -- one sign per model; lpcnet_batch_tune and a pinned value select it)
+    if (x2_available(b) && !e->x2_wide) {                    // eight streams per workgroup: a round of the two-group kernel (us per sample step)
         static const float step_x2 = 13.9f;
         const int wgs = (n + 7) / 8;
         const float t = (float)((wgs + cus - 1) / cus) * step_x2;
@@ -452,6 +478,8 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     b->S = auto_streams_per_wg(b, n);
     b->pack2 = use_pack2(b, n, b->S);
     auto fail = [&](int code) { lpcn_batch_dev_destroy(b); return code; };
+    const char *xs = getenv("LPCNET_HIP_X2_STREAMED");       // tools (bench.py on a trained-like model): the streamed two-group variants where the model allows, silently not where it does not
+    if (xs && *xs == '1' && (e->x2w_host || e->x2_wide)) { const int rcs = lpcn_batch_dev_set_x2_streamed(b, 1); if (rcs) return fail(rcs); }
     const size_t rows = (size_t)n * max_chunk;
     int rc = 0;
     if ((rc = b->d_state.alloc(n)) || (rc = b->d_fc_base.alloc(n)) || (rc = b->d_cond_a.alloc(rows * LPCN_ROWS_A)) || (rc = b->d_cond_b.alloc(rows * LPCN_ROWS_B)) ||
@@ -527,12 +555,40 @@ extern "C" int lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s)
 {
     b->S_auto = s == 0;
     if (s == 0) { s = auto_streams_per_wg(b, b->n); b->tuned = false; }
-    if (s == 8 && !x2_available(b)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane, PARITY arithmetic"); return LPCN_E_ARG; }
+    if (s == 8 && !x2_available(b)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane (33 .. 96: lpcnet_batch_set_two_group_streaming first), PARITY arithmetic"); return LPCN_E_ARG; }
     if (s != 1 && s != 2 && s != 4 && s != 8) { snprintf(g_err, sizeof(g_err), "streams per workgroup must be 1, 2, 4 or 8"); return LPCN_E_ARG; }
     b->S = s;
     b->pack2 = use_pack2(b, b->n, b->S);
     return 0;
 }
+// The streamed variants of the two-group kernel for THIS batch (float blobs of 33 .. 96 items per lane; off by default).  On: the engine's wide image
+// is uploaded once, as IMG_X2, and the batch treats eight streams per workgroup like any two-group model -- pinned, measured, or the group
+// schedule's answer; off: the batch is back on the four-stream kernel (the image stays).  A model with an ordinary two-group image: nothing to do.
+extern "C" int lpcn_batch_dev_set_x2_streamed(lpcn_batch_dev *b, int on)
+{
+    lpcn_engine *e = b->e;
+    if (e->image[IMG_X2].present && !e->x2_wide) return 0;
+    if (e->is_int8) { snprintf(g_err, sizeof(g_err), "two-group streaming: int8 blobs have no two-group kernel"); return LPCN_E_MODEL; }
+    if (!e->image[IMG_PARITY].args.b_dense) { snprintf(g_err, sizeof(g_err), "two-group streaming: the two-group kernel needs a dense GRU-B input matrix"); return LPCN_E_MODEL; }
+    if (!e->x2_wide && !e->x2w_host) { snprintf(g_err, sizeof(g_err), "two-group streaming: the model has no two-group image (more than %d items per lane, or switched off when the engine was created)", LPCN_X2W_NW_MAX); return LPCN_E_MODEL; }
+    if (!on && b->x2_streamed && !b->S_auto && b->S == 8) { snprintf(g_err, sizeof(g_err), "two-group streaming: eight streams per workgroup are pinned; pin another value first"); return LPCN_E_ARG; }
+    if ((on != 0) == b->x2_streamed) return 0;
+    DeviceGuard guard(e->device);
+    { const int rcw = wait_all(b); if (rcw) return rcw; }
+    if (on && !e->x2_wide) {
+        X2WideHost &wh = *e->x2w_host;
+        GruAImage img;
+        int rc = upload_gru_a(e, e->image[IMG_PARITY].args, &wh.mx, img, round_up_variant(variants_x2w, wh.mx.nw));
+        if (!rc) rc = upload_nat_tables(e, img.args, wh.emb[0].data(), wh.emb[1].data(), wh.emb[2].data());
+        if (rc) return rc;                                   // (what was uploaded goes with the engine)
+        e->image[IMG_X2] = img;
+        e->x2_wide = true;
+        e->x2w_host.reset();
+    }
+    b->x2_streamed = on != 0;
+    return lpcn_batch_dev_retune(b);                         // (the engine's choice is made again, and measured again at the next run; a pinned value stays)
+}
+extern "C" int lpcn_batch_dev_x2_streamed(const lpcn_batch_dev *b) { return b->x2_streamed ? 1 : 0; }
 extern "C" int lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode)
 {
     if (mode < -1 || mode > 1) { snprintf(g_err, sizeof(g_err), "twelve-wave mode must be -1, 0 or 1"); return LPCN_E_ARG; }

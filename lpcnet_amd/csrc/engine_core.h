@@ -109,6 +109,18 @@ struct Event {
 enum { IMG_PARITY, IMG_FAST, IMG_X2, IMG_X3, IMG_COUNT };
 struct GruAImage { LpcnSampleArgs args{}; int nw_variant = 0; bool present = false; };
 
+// The two-group kernel's wide image (more than 32 items per lane: the streamed variants) as dealt when the engine was created, on the host, with a
+// copy of the blob's embedding tables, until a batch asks for it (lpcn_batch_dev_set_x2_streamed uploads it and drops this)
+struct X2WideHost {
+    lpcn_model_host mx{};
+    bool packed = false;
+    std::vector<float> emb[3];
+    X2WideHost() = default;
+    X2WideHost(const X2WideHost &) = delete;
+    X2WideHost &operator=(const X2WideHost &) = delete;
+    ~X2WideHost() { if (packed) lpcn_model_release(&mx); }
+};
+
 struct lpcn_engine {
     int device = 0;
     int nw = 0, nb_b = 0;
@@ -119,6 +131,8 @@ struct lpcn_engine {
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
     GruAImage image[IMG_COUNT];
+    bool x2_wide = false;              // image[IMG_X2] is the wide image: only batches that asked for it run on it (lpcn_batch_dev::x2_streamed)
+    std::unique_ptr<X2WideHost> x2w_host;         //   ... not uploaded yet
     LpcnFrameModel fmodel{};
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
@@ -159,6 +173,7 @@ struct lpcn_batch_dev {
     bool tuned = false;                // ... and have been measured for the current arithmetic flavour
     bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
     bool no_x2 = false;                // LPCNET_HIP_NO_X2=1 when the batch was created (tools / tests): never the two-group kernel
+    bool x2_streamed = false;          // lpcn_batch_dev_set_x2_streamed: this batch may run the two-group kernel's streamed variants (a wide image)
     bool x3 = false;                   // at eight streams per workgroup: the twelve-wave form of the two-group kernel (measured faster on this batch, or asked for)
     int x3_mode = -1;                  // lpcn_batch_dev_set_x3: 0 never, 1 always, -1 measured (the table's value, the eight-wave form, until then)
     int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
@@ -233,8 +248,8 @@ SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_fra
 // current arithmetic is FAST and it has one; else PARITY's.
 inline const GruAImage &gru_a_image(const lpcn_engine *e, int S) { return e->image[S == 8 ? IMG_X2 : (e->fast && e->image[IMG_FAST].present) ? IMG_FAST : IMG_PARITY]; }
 // Two groups of four float streams per workgroup, half a step apart (sample_kernel_x2.hip.h): float blobs, PARITY arithmetic, dense GRU-B input
-// matrix, <= 32 items per lane.  Eight streams per workgroup select it.
-inline bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast; }
+// matrix, <= 32 items per lane -- or up to 96 on its streamed variants, for the batches that opted in.  Eight streams per workgroup select it.
+inline bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast && (!b->e->x2_wide || b->x2_streamed); }
 // ... and its twelve-wave form (sample_kernel_x3.hip.h), where the model has the image for it
 inline bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && b->e->image[IMG_X3].present; }
 

@@ -17,6 +17,7 @@ extern "C" int lpcn_launch_sample_s1(int nw, int is_int8, int flags, int grid, i
 extern "C" int lpcn_launch_sample_s2(int nw, int is_int8, int flags, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);
 extern "C" int lpcn_launch_sample_s4(int nw, int is_int8, int flags, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);
 extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x2.hip: two groups of four streams
+extern "C" int lpcn_launch_sample_x2w(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);     // sample_x2w.hip: its streamed variants (more than 32 items per lane)
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
 extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout)
 
@@ -67,7 +68,7 @@ int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, shor
     const int flags = (e->fast ? 1 : 0) | (p.pack2 ? 2 : 0);
     int rc = 0;
     switch (p.S) {
-    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, d_args) : lpcn_launch_sample_x2(nw, p.grid, p.lds, st, d_args); break;
+    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, d_args) : (nw > LPCN_X2_NW_MAX ? lpcn_launch_sample_x2w : lpcn_launch_sample_x2)(nw, p.grid, p.lds, st, d_args); break;
     case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, d_args); break;
     case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, d_args); break;
     default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, d_args); break;

@@ -61,6 +61,10 @@ extern "C" {
 #define LPCN_X2_CHAIN_WAVES 4
 #define LPCN_X2_P0_FIRST 4
 #define LPCN_X2_NW_MAX 32
+/* ... its streamed variants (a batch's opt-in, lpcn_batch_dev_set_x2_streamed): up to LPCN_X2W_NW_MAX items per lane, of which the first LPCN_X2W_NR
+ * are register-resident and the others come from L2 every sample (model_pack.c: lpcn_model_pack_x2_wide) */
+#define LPCN_X2W_NW_MAX 96
+#define LPCN_X2W_NR 24
 /* the twelve-wave form of the two-group kernel (sample_kernel_x3.hip.h): three waves per SIMD, at most LPCN_X3_NW register-resident items per lane.
  * Waves 0 .. LPCN_X3_CHAIN_WAVES - 1 carry GRU-B's chains, the other eight the candidate heads and the start-value pass; every wave runs up to
  * LPCN_X3_SEGS row segments in P1.  Wave LPCN_X3_LW leads the streams; it and wave LPCN_X3_FREE carry no head (model_pack.c: lpcn_model_pack_x3). */
@@ -154,6 +158,7 @@ typedef struct lpcn_x3_image {
 int  lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len);
 void lpcn_model_release(lpcn_model_host *m);
 int  lpcn_model_pack_x2(const lpcn_model_host *m, lpcn_model_host *f);     /* 0: f holds the two-group kernel's own GRU-A packing; -1: the model does not fit it */
+int  lpcn_model_pack_x2_wide(const lpcn_model_host *m, lpcn_model_host *f); /* the same for LPCN_X2_NW_MAX < items per lane <= LPCN_X2W_NW_MAX (the streamed variants); -1: int8, fewer, more */
 int  lpcn_model_pack_fast(const lpcn_model_host *m, lpcn_model_host *f);   /* 1: FAST shares PARITY's image; 0: f holds FAST's own GRU-A packing */
 int  lpcn_model_pack_x3(const lpcn_model_host *m, lpcn_x3_image *im);      /* 0: im holds the twelve-wave image; -1: the model does not fit it (not an error: the other kernels run it) */
 void lpcn_x3_image_release(lpcn_x3_image *im);
@@ -235,6 +240,8 @@ int  lpcn_batch_dev_tune(lpcn_batch_dev *b);              /* measure the streams
 int  lpcn_batch_dev_set_state(lpcn_batch_dev *b, int stream, const lpcn_stream_state *host);
 int  lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s);              /* 1,2,4 (0=auto) */
+int  lpcn_batch_dev_set_x2_streamed(lpcn_batch_dev *b, int on);                /* the two-group kernel's streamed variants for this batch (33 .. 96 items per lane); 0 also where the model has the ordinary image */
+int  lpcn_batch_dev_x2_streamed(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode);                       /* twelve-wave form of the two-group kernel: 0 never, 1 always (needs the image), -1 measured / table */
 int  lpcn_batch_dev_x3(const lpcn_batch_dev *b);                                /* what a whole-batch launch runs now */
 int  lpcn_batch_dev_retune(lpcn_batch_dev *b);                                 /* after lpcn_engine_set_fast: auto value again */

@@ -649,6 +649,20 @@ int lpcn_model_pack_x2(const lpcn_model_host *m, lpcn_model_host *f)
     return 0;
 }
 
+/* The same dealing for the two-group kernel's STREAMED variants: float blobs with more than LPCN_X2_NW_MAX and at most LPCN_X2W_NW_MAX items on a
+ * lane.  Returns -1 for int8 blobs and for models of at most LPCN_X2_NW_MAX items, which the ordinary image serves. */
+int lpcn_model_pack_x2_wide(const lpcn_model_host *m, lpcn_model_host *f)
+{
+    if (m->is_int8) return -1;
+    *f = *m;
+    f->pk_a_w = NULL; f->pk_a_wq = NULL; f->pk_a_blk = NULL; f->pk_a_row = NULL;
+    f->pk_b_w = NULL; f->pk_b_wq = NULL; f->pk_b_start = NULL; f->pk_b_blk = NULL;
+    for (int i = 0; i < 3; i++) f->pk_emb[i] = NULL;
+    const int rc = pack_gru_a(f, 2);
+    if (rc || f->nw <= LPCN_X2_NW_MAX || f->nw > LPCN_X2W_NW_MAX) { lpcn_model_release(f); return -1; }
+    return 0;
+}
+
 void lpcn_model_release(lpcn_model_host *m)
 {
     free(m->pk_a_w); free(m->pk_a_wq); free(m->pk_b_wq); free(m->pk_a_blk); free(m->pk_a_row);

@@ -21,7 +21,10 @@
 // conditioning (1152 x 4 floats per group and frame) is read from L2 by the lanes that need it (one row = one dword per stream and
 // sample) instead of living in LDS: 152.7 KB of the CU's 160.
 //
-// Scope: float blobs, PARITY arithmetic, dense GRU-B input matrix, <= 32 items per lane.  Everything else runs on the four-stream kernel.
+// Scope: float blobs, PARITY arithmetic, dense GRU-B input matrix.  Up to 32 items per lane are register-resident (sample_x2.hip); the variants
+// above that (sample_x2w.hip: 48 / 64 / 80 / 96, a batch's opt-in -- lpcnet_batch_set_two_group_streaming) keep the first 24 items of a lane in
+// registers and STREAM the others from the L2-resident item array, the four-stream kernel's mechanism (sample_kernel.hip.h).  Everything else
+// runs on the four-stream kernel.
 #pragma once
 #include "sample_kernel.hip.h"
 #include "tree_stages.h"
@@ -149,8 +152,16 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     asm volatile("" : "+s"(emb_nat_sig), "+s"(emb_nat_pred), "+s"(emb_nat_exc));
 
     // ------------------------------------------------------------------ resident weights ----
-    float4 w[NW];
-    uint32_t offp[(NW + 1) / 2];
+    // More than 32 items per lane (heavy-tailed, trained-like sparsity): the first NR stay in VGPRs, the others are re-fetched from L2 every sample,
+    // WSD - 1 items ahead of their use, into a ring of WSD register quads; their block indices come with them, one byte per lane and item,
+    // WSOD - 1 items ahead of the state read they address.  Only a wave with more than NR items, or with a candidate head (heads sit end-aligned,
+    // at items [NW - head, NW): all streamed), ever executes a streamed item.  All of it is compiled out of the resident variants.
+    constexpr int NR = NW > LPCN_X2_NW_MAX ? LPCN_X2W_NR : NW;
+    constexpr int WSD = 4, WSOD = 8;
+    float4 w[NR];
+    float4 ws[NR < NW ? WSD : 1] = {};
+    uint32_t offp[(NR + 1) / 2];
+    int wso[NR < NW ? WSOD : 1] = {};
     int row_reg[3];
 #define LPCN_ROW(k) (row_reg[k])
     {
@@ -160,14 +171,14 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         const auto *ab = as_global(Ap->a_blk);
         const auto *aw = (const LPCN_GLOBAL float *)as_global(Ap->a_w);
 #pragma unroll
-        for (int j = 0; j < NW; ++j) {
+        for (int j = 0; j < NR; ++j) {
             const auto *v = aw + (base + (size_t)j * 64) * 4;
             w[j] = make_float4(v[0], v[1], v[2], v[3]);
         }
 #pragma unroll
-        for (int j = 0; j < NW; j += 2) {
+        for (int j = 0; j < NR; j += 2) {
             const int p0 = ab[base + (size_t)j * 64];
-            const int p1 = (j + 1 < NW) ? ab[base + (size_t)(j + 1) * 64] : 0;
+            const int p1 = (j + 1 < NR) ? ab[base + (size_t)(j + 1) * 64] : 0;
             offp[j >> 1] = (uint32_t)(L::ha_off(p0) + lane_sel) | ((uint32_t)(L::ha_off(p1) + lane_sel) << 16);
         }
         const auto *ar = as_global(Ap->a_row);
@@ -182,6 +193,9 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
     asm volatile("" : "+s"(fc_w_s), "+s"(fc_b_s), "+s"(fc_f_s));
     const LPCN_GLOBAL float *cond_a_s = as_global(Ap->cond_a);
     asm volatile("" : "+s"(cond_a_s));
+    const LPCN_GLOBAL char *aw_s = (const LPCN_GLOBAL char *)as_global(Ap->a_w);       // item array, for the streamed items (NR < NW)
+    const LPCN_GLOBAL uint8_t *ab_s = as_global(Ap->a_blk);                             // ... and their block indices
+    if constexpr (NR < NW) asm volatile("" : "+s"(aw_s), "+s"(ab_s));
     const int has_slot = __builtin_amdgcn_readfirstlane((__ballot(row_reg[0] >= 0) != 0ull ? 1 : 0) | (__ballot(row_reg[1] >= 0) != 0ull ? 2 : 0) |
                                                         (__ballot(row_reg[2] >= 0) != 0ull ? 4 : 0));
     const bool has2 = (has_slot & 4) != 0;
@@ -337,12 +351,52 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         constexpr int PF = 2;                                // (state blocks fetched 1 / 2 / 3 / 4 items ahead: 150.0 / 151.0 / 149.6 / 148.0 M)
         float4 hq[PF + 1] = {};
         const unsigned char *hA_cur = gp + L::g_hA;           // state blocks of the group whose items are running
+        // streamed item j's block index / weights -> their ring slots: ONE scalar base each plus a 32-bit lane offset rebuilt from the thread id (no
+        // per-item scalar base, no 64-bit per-lane pointer held across the loop); j is a constant after unrolling, in [NR, NW) -- the wave's own part
+        // of a_blk / a_w
+        auto fetch_o = [&](const int j) __attribute__((always_inline)) {
+            if constexpr (NR < NW) {
+                uint32_t bo = (uint32_t)tid0;
+                LPCN_REMAT_V(bo);
+                bo = (bo >> 6) * (uint32_t)(NW * 64) + (bo & 63u) + (uint32_t)j * 64u;
+                wso[(j >= NR ? j - NR : 0) % WSOD] = ab_s[bo];
+            }
+        };
+        auto fetch_w = [&](const int j) __attribute__((always_inline)) {
+            if constexpr (NR < NW) {
+                uint32_t wo = (uint32_t)tid0;
+                LPCN_REMAT_V(wo);
+                wo = (wo >> 6) * (uint32_t)(NW * 1024) + (wo & 63u) * 16u + (uint32_t)j * 1024u;
+                const LPCN_GLOBAL float *v = (const LPCN_GLOBAL float *)(aw_s + wo);
+                ws[(j >= NR ? j - NR : 0) % WSD] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        };
         auto fetch_h = [&](const int j) __attribute__((always_inline)) {
+            if constexpr (NR < NW) {
+                uint32_t off;
+                if (j >= NR) {                               // a streamed item: the offset of its state block from its index byte
+                    uint32_t pb = (uint32_t)wso[(j >= NR ? j - NR : 0) % WSOD], ls = (uint32_t)tid0;
+                    LPCN_REMAT_V(ls);
+                    off = pb * (uint32_t)L::HA_STRIDE + (pb >> 2) * 16u + (ls & 3u) * 16u;
+                } else {
+                    uint32_t pk = offp[(j < NR ? j : 0) >> 1];
+                    LPCN_REMAT_V(pk);
+                    off = (j & 1) ? (pk >> 16) : (pk & 0xFFFFu);
+                }
+                hq[j % (PF + 1)] = *(const float4 *)(hA_cur + off);
+            } else {
             uint32_t pk = offp[j >> 1];
             LPCN_REMAT_V(pk);
             const uint32_t off = (j & 1) ? (pk >> 16) : (pk & 0xFFFFu);
             hq[j % (PF + 1)] = *(const float4 *)(hA_cur + off);
+            }
         };
+        auto wsel = [&](const int j) __attribute__((always_inline)) -> float4 {      // item j's weights: resident or from the ring
+            if constexpr (NR < NW) return j < NR ? w[j < NR ? j : 0] : ws[(j >= NR ? j - NR : 0) % WSD];
+            else return w[j];
+        };
+        // What an item of either chain issues in front of its products, in this order: the index byte of the item WSOD - 1 ahead, the state block of the
+        // item PF ahead, the weights of the item WSD - 1 ahead -- the first and the last only where they name a streamed item of [NR, NW).
         typedef float negz_t __attribute__((ext_vector_type(4)));
         negz_t negz = {-0.f, -0.f, -0.f, -0.f};
         auto load_negz = [&]() __attribute__((always_inline)) { negz = (negz_t){-0.f, -0.f, -0.f, -0.f}; asm volatile("" : "+v"(negz)); };
@@ -354,7 +408,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             typedef float f2 __attribute__((ext_vector_type(2)));
             const float4 hv = hq[j % (PF + 1)];
             const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
-            const float wk[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
+            const float4 wv = wsel(j);
+            const float wk[4] = {wv.x, wv.y, wv.z, wv.w};
             f2 a01 = {acc[0], acc[1]}, a23 = {acc[2], acc[3]};
             f4 pv[4];
             // (the four products of an item are issued back to back into four result tuples, then the sums.  Round 6 tried to software-pipeline the
@@ -400,6 +455,18 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             if constexpr (j < je) {
                 if constexpr (j + PF < NW) fetch_h(j + PF);
                 if (j >= e0) { asm volatile(""); mac(j); }   // (every step issues the same LDS read whether its item runs or not: exact wait counts)
+                self(self, std::integral_constant<int, j + 1>{}, jend_c);
+            }
+        };
+        // ... of a streamed variant: every step issues the same loads of streamed items, too.  (A lambda of its own: the one above, naming the ring's
+        // fetches only in discarded statements, still captured them, and the resident variants' code came out differently.)
+        auto head_step_s = [&](auto self, auto jc, auto jend_c) __attribute__((always_inline)) -> void {
+            constexpr int j = decltype(jc)::value, je = decltype(jend_c)::value;
+            if constexpr (j < je) {
+                if constexpr (j + WSOD - 1 >= NR && j + WSOD - 1 < NW) fetch_o(j + WSOD - 1);
+                if constexpr (j + PF < NW) fetch_h(j + PF);
+                if constexpr (j + WSD - 1 >= NR && j + WSD - 1 < NW) fetch_w(j + WSD - 1);
+                if (j >= e0) { asm volatile(""); mac(j); }
                 self(self, std::integral_constant<int, j + 1>{}, jend_c);
             }
         };
@@ -540,8 +607,15 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
 #pragma unroll
                     for (int s = 0; s < S; ++s) acc[s] = bias + diag * hT_q[n * S + s];
                 }
+                // (a streamed variant's chain primes both rings from its first step: the index bytes before the state reads that need them)
+#pragma unroll
+                for (int j = J0; j < J0 + WSOD - 1; ++j) if (NR < NW && j >= NR && j < NW) fetch_o(j);
 #pragma unroll
                 for (int j = 0; j < PF; ++j) if (J0 + j < NW) fetch_h(J0 + j);
+#pragma unroll
+                for (int j = J0; j < J0 + WSD - 1; ++j) if (NR < NW && j >= NR && j < NW) fetch_w(j);
+                if constexpr (NR < NW) head_step_s(head_step_s, std::integral_constant<int, J0>{}, std::integral_constant<int, JM>{});
+                else
                 head_step(head_step, std::integral_constant<int, J0>{}, std::integral_constant<int, JM>{});
             }
             LPCN_X2_PROF(3);
@@ -559,6 +633,8 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             }
             LPCN_X2_PROF(4);
             if (do_heads) {
+                if constexpr (NR < NW) head_step_s(head_step_s, std::integral_constant<int, JM>{}, std::integral_constant<int, NW>{});
+                else
                 head_step(head_step, std::integral_constant<int, JM>{}, std::integral_constant<int, NW>{});
                 int r = LPCN_ROW(0);
                 LPCN_REMAT_V(r);
@@ -677,8 +753,10 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             if (s2_at < nextb) nextb = s2_at;
             LPCN_REMAT_S(nextb);
             auto item = [&](const int j) __attribute__((always_inline)) -> bool {           // false: this wave has no more items
-                if (__builtin_expect(j >= jend, 0)) return false;
+                if (__builtin_expect(j >= jend, 0)) return false;      // (a wave with b3 <= NR items returns here before it reaches a streamed one)
+                if constexpr (NR < NW) { if (j + WSOD - 1 >= NR && j + WSOD - 1 < NW) fetch_o(j + WSOD - 1); }      // (j is a constant after unrolling)
                 if (j + PF < NW) fetch_h(j + PF);
+                if constexpr (NR < NW) { if (j + WSD - 1 >= NR && j + WSD - 1 < NW) fetch_w(j + WSD - 1); }
                 if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty) and the stage-2 wave's opening: ONE compare per item against the next one
                     if (lpcn_slot_moves(plan, 1, j, b1)) row_swap(0, 1);
                     if (lpcn_slot_moves(plan, 2, j, b2)) row_swap(1, 2);

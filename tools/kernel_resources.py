@@ -2,6 +2,7 @@
 """Register / scratch accounting of the sample kernel's variants from the compiler's own output (no GPU needed).
 
     python tools/kernel_resources.py [--s 4] [--asm-dir DIR] [--json]
+    python tools/kernel_resources.py --s 8 --wide        (the two-group kernel's streamed variants, sample_x2w.hip)
     python tools/kernel_resources.py --analysis          (the feature-analysis kernels of the engine's units)
     python tools/kernel_resources.py --encode            (the encoder kernels of the engine's units)
 
@@ -24,10 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def compile_asm(s_value, out_path):
-    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip); 12: its twelve-wave form (sample_x3.hip)"""
+def compile_asm(s_value, out_path, wide=False):
+    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip; wide: its streamed variants, sample_x2w.hip);
+    12: its twelve-wave form (sample_x3.hip)"""
     from lpcnet_amd import build
-    src = {8: "sample_x2.hip", 12: "sample_x3.hip"}.get(s_value, "sample_variants.hip")
+    src = {8: "sample_x2w.hip" if wide else "sample_x2.hip", 12: "sample_x3.hip"}.get(s_value, "sample_variants.hip")
     cmd = [build.HIPCC] + build.HIP_FLAGS + ([] if s_value in (8, 12) else [f"-DLPCN_S={s_value}"]) + ["--cuda-device-only", "-S", os.path.join(build.CSRC, src), "-o", out_path]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
@@ -161,6 +163,7 @@ def engine_kernel_resources(pattern=r"N4lpcn\d+(analysis_[a-z]+_kernel)E", asm_p
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--s", type=int, default=4, help="streams per workgroup: 1, 2, 4, 8 = the two-group kernel, or 12 = its twelve-wave form")
+    ap.add_argument("--wide", action="store_true", help="with --s 8: the streamed variants for more than 32 items per lane (sample_x2w.hip)")
     ap.add_argument("--asm-dir", default=None)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--analysis", action="store_true", help="report the feature-analysis kernels (and lpc_kernel) of the engine's units instead")
@@ -173,9 +176,10 @@ def main():
         print(json.dumps(engine_kernel_resources(r"N4lpcn\d+(analysis_[a-z]+_kernel|lpc_kernel)E", os.path.join(a.asm_dir, "engine.s") if a.asm_dir else None), indent=1))
         return
     d = a.asm_dir or tempfile.mkdtemp(prefix="lpcn_asm_")
-    path = os.path.join(d, f"sample_s{a.s}.s")
+    wide = a.wide and a.s == 8
+    path = os.path.join(d, f"sample_s{a.s}{'w' if wide else ''}.s")
     if not os.path.exists(path):
-        compile_asm(a.s, path)
+        compile_asm(a.s, path, wide)
     rows = analyse(path)
     if a.json:
         print(json.dumps(rows, indent=1))
