@@ -8,7 +8,7 @@
  * offsets): with this definition the unmodified src/lpcnet_plc.c compiles and links against liblpcnet_hip.so
  * (integration/lpcnet_private_hip.h, integration/Makefile target plc, tests/test_demo_integration.py).
  *
- * api.c defines the state it really uses and statically asserts that every member below sits where this header says.
+ * lpcnet_amd/csrc/api_internal.h defines the state it really uses and statically asserts that every member below sits where this header says.
  * Members the engine adds are prefixed hip_; the sizes are the fixed architecture of the default model
  * (the reference's generated nnet_data.h: GRU_A_STATE_SIZE 384, GRU_B_STATE_SIZE 16, FEATURE_CONV1_STATE_SIZE 168,
  * FEATURE_CONV2_STATE_SIZE 256, FEATURES_DELAY 2; src/freq.h: LPC_ORDER 16; include/lpcnet.h: NB_FEATURES 20). */

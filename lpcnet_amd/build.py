@@ -26,14 +26,18 @@ CXX_FLAGS = ["-std=c++17" if x == "-std=gnu11" else x for x in C_FLAGS]      # h
 
 # The engine's host runtime, one unit per subsystem (engine_core.h is what they share; each kernel header belongs to one unit) ...
 ENGINE_UNITS = ("engine", "engine_synth", "engine_codec", "engine_plc", "engine_probe")
-# ... and every object of the library except api.o, which build_small_registry() replaces
-OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS) + ("sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x2w.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
+# ... the C host shell, one unit per API surface (api_internal.h / api_shards.h are what they share); api_stream holds the model registry ...
+API_UNITS = ("api_core", "api_stream", "api_batch", "api_tools")
+REGISTRY_UNIT = "api_stream"
+# ... and every object of the library except the registry's, which build_small_registry() replaces
+OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS + tuple(u for u in API_UNITS if u != REGISTRY_UNIT)) + (
+    "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x2w.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
 
 
 def source_hashes(extra_flags=()):
     """(src, dev): sha1 prefixes over every source the library is built from (lpcnet_amd/csrc/*, the public headers, the
     compile flags) and over the DEVICE sources alone (*.hip, *.hip.h, *.inc and the headers they include -- everything in
-    csrc/ except the host C / C++ files).  Both are baked into the library (lpcnet_hip_build_info()); `dev` ties a rocprofv3
+    csrc/ except the host C / C++ files and the shell's own headers, api_*.h).  Both are baked into the library (lpcnet_hip_build_info()); `dev` ties a rocprofv3
     measurement under profiles/ to the kernels it was taken with (bench.py: kernel_source_hash), so a change to host code
     alone does not orphan the profiles."""
     import hashlib
@@ -43,7 +47,7 @@ def source_hashes(extra_flags=()):
             continue
         data = f.encode() + open(os.path.join(CSRC, f), "rb").read()
         hs.update(data)
-        if not f.endswith((".c", ".cpp")):
+        if not (f.endswith((".c", ".cpp")) or (f.startswith("api_") and f.endswith(".h"))):
             hd.update(data)
     for f in ("lpcnet.h", "lpcnet_batch.h", "lpcnet_hip_state.h"):
         hs.update(f.encode() + open(os.path.join(HERE, "..", "include", f), "rb").read())
@@ -100,32 +104,30 @@ def build(force=False, verbose=True, prof=False):
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, len(os.sched_getaffinity(0)))) as ex:
         list(ex.map(run, jobs))
-    for c in ("api.c", "model_pack.c"):
-        o = os.path.join(objdir, c[:-2] + ".o")
+    for u in API_UNITS + ("model_pack",):
         # (the -D switches of an experiment reach the host C files too: lpcnet_engine.h's dealing defaults -- e.g. which waves of an int8 blob may
-        # carry candidate heads -- are derived from the same macros the kernels are compiled with)
-        run(["gcc"] + C_FLAGS + [x for x in extra if x.startswith("-D")] + [f'-DLPCN_SOURCE_HASH="{h_src}"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"', "-c", os.path.join(CSRC, c), "-o", o])
+        # carry candidate heads -- are derived from the same macros the kernels are compiled with; the hashes go to the unit that publishes them)
+        hashes = [f'-DLPCN_SOURCE_HASH="{h_src}"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"'] if u == "api_core" else []
+        run(["gcc"] + C_FLAGS + [x for x in extra if x.startswith("-D")] + hashes + ["-c", os.path.join(CSRC, u + ".c"), "-o", os.path.join(objdir, u + ".o")])
     run(["g++"] + CXX_FLAGS + ["-c", os.path.join(CSRC, "plc_plan.cpp"), "-o", os.path.join(objdir, "plc_plan.o")])
-    run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in ("api.o",) + OBJECTS] + ["-lpthread", "-lm"])
+    run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [os.path.join(objdir, f) for f in (REGISTRY_UNIT + ".o",) + OBJECTS] + ["-lpthread", "-lm"])
     return lib
 
 
 def build_small_registry(verbose=False):
-    """liblpcnet_hip_smallreg.so: the same objects with a model registry of 4 slots / 2 resident device sides (api.c rebuilt with
-    -DLPCN_MAX_MODELS=4 -DLPCN_MAX_RESIDENT=2), so that tests reach the eviction paths that need > 256 distinct models in the product
-    build (tests/test_gpu_wide.py; select with LPCNET_HIP_LIB).  Test artefact, git-ignored like every built library."""
+    """liblpcnet_hip_smallreg.so: the same objects with a model registry of 4 slots / 2 resident device sides (the registry's unit alone
+    rebuilt with -DLPCN_MAX_MODELS=4 -DLPCN_MAX_RESIDENT=2), so that tests reach the eviction paths that need > 256 distinct models in
+    the product build (tests/test_gpu_wide.py; select with LPCNET_HIP_LIB).  Test artefact, git-ignored like every built library.  It
+    carries the hashes of the library it shares its other objects with."""
     build(verbose=verbose)
-    objdir0 = os.path.join(HERE, "build")
-    if not all(os.path.exists(os.path.join(objdir0, f)) for f in OBJECTS):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
-        build(force=True, verbose=verbose)
     lib = LIB.replace(".so", "_smallreg.so")
-    h_src, h_dev = source_hashes()
-    if baked_hashes(lib) == (h_src + "-smallreg", h_dev):
+    if baked_hashes(lib) == source_hashes():
         return lib
     objdir = os.path.join(HERE, "build")
-    o = os.path.join(objdir, "api_smallreg.o")
-    cmds = [["gcc"] + C_FLAGS + ["-DLPCN_MAX_MODELS=4", "-DLPCN_MAX_RESIDENT=2", f'-DLPCN_SOURCE_HASH="{h_src}-smallreg"', f'-DLPCN_DEVICE_SOURCE_HASH="{h_dev}"',
-                                 "-c", os.path.join(CSRC, "api.c"), "-o", o],
+    if not all(os.path.exists(os.path.join(objdir, f)) for f in OBJECTS):      # (a prebuilt library whose hash matches skips the compile: its objects may be absent -- ADVICE r5)
+        build(force=True, verbose=verbose)
+    o = os.path.join(objdir, REGISTRY_UNIT + "_smallreg.o")
+    cmds = [["gcc"] + C_FLAGS + ["-DLPCN_MAX_MODELS=4", "-DLPCN_MAX_RESIDENT=2", "-c", os.path.join(CSRC, REGISTRY_UNIT + ".c"), "-o", o],
             [HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + [o] + [os.path.join(objdir, f) for f in OBJECTS] + ["-lpthread", "-lm"]]
     for c in cmds:
         if verbose:

@@ -1,0 +1,546 @@
+/* C host shell of the LPCNet HIP engine, batch half: every entry point of include/lpcnet_batch.h that takes an LPCNetBatch, on top of the
+ * device runtime declared in lpcnet_engine.h.  Which streams a shard owns and how one call fans out over the shards is api_shards.h. */
+#include "api_internal.h"
+
+LPCNetBatch *lpcnet_batch_create_sharded(int n_streams, const int *devices, int n_devices)
+{
+    if (n_streams <= 0 || !devices || n_devices <= 0 || n_devices > LPCN_MAX_SHARDS) { set_err("lpcnet_batch_create_sharded: bad arguments"); return NULL; }
+    for (int k = 0; k < n_devices; k++) if (devices[k] < 0) { set_err("lpcnet_batch_create_sharded: bad device"); return NULL; }
+    LPCNetBatch *b = (LPCNetBatch *)calloc(1, sizeof(*b));
+    if (!b) return NULL;
+    b->n = n_streams;
+    b->n_shards = shard_partition(n_streams, n_devices, b->at);      /* (more devices than streams: the last ones stay without a shard) */
+    for (int k = 0; k < b->n_shards; k++) b->sh[k].device = devices[k];
+    return b;
+}
+
+LPCNetBatch *lpcnet_batch_create(int n_streams, int device)
+{
+    if (n_streams <= 0 || device < 0) { set_err("lpcnet_batch_create: bad arguments"); return NULL; }
+    return lpcnet_batch_create_sharded(n_streams, &device, 1);
+}
+
+void lpcnet_batch_destroy(LPCNetBatch *b)
+{
+    if (!b) return;
+    for (int k = 0; k < b->n_shards; k++) {
+        if (b->sh[k].dev) lpcn_batch_dev_destroy(b->sh[k].dev);
+        if (b->sh[k].engine) lpcn_engine_destroy(b->sh[k].engine);
+    }
+    free(b);
+}
+
+int lpcnet_batch_streams(const LPCNetBatch *b) { return b->n; }
+int lpcnet_batch_shards(const LPCNetBatch *b) { return b ? b->n_shards : 0; }
+
+int lpcnet_batch_shard_info(const LPCNetBatch *b, int shard, int *first, int *count, int *device)
+{
+    if (!b || shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    if (first) *first = b->at[shard].first;
+    if (count) *count = b->at[shard].count;
+    if (device) *device = b->sh[shard].device;
+    return 0;
+}
+
+#define BATCH_CHUNK_FRAMES 100       /* frame products are staged per chunk: 100 frames = 1 s of audio */
+
+int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
+{
+    lpcn_model_host m;
+    if (!b) { set_err("lpcnet_batch_load_model: bad arguments"); return -1; }
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return -1; }
+    lpcn_engine *e[LPCN_MAX_SHARDS] = {0};
+    lpcn_batch_dev *d[LPCN_MAX_SHARDS] = {0};
+    int rc = 0;
+    for (int k = 0; k < b->n_shards && !rc; k++) {          /* the model is replicated on every shard's device */
+        rc = lpcn_engine_create(&e[k], b->sh[k].device, &m);
+        if (!rc) rc = lpcn_batch_dev_create(&d[k], e[k], b->at[k].count, BATCH_CHUNK_FRAMES);
+    }
+    lpcn_model_release(&m);
+    if (rc) {
+        take_engine_err();
+        for (int k = 0; k < b->n_shards; k++) { if (d[k]) lpcn_batch_dev_destroy(d[k]); if (e[k]) lpcn_engine_destroy(e[k]); }
+        return -1;
+    }
+    for (int k = 0; k < b->n_shards; k++) {
+        if (b->sh[k].dev) lpcn_batch_dev_destroy(b->sh[k].dev);
+        if (b->sh[k].engine) lpcn_engine_destroy(b->sh[k].engine);
+        b->sh[k].engine = e[k]; b->sh[k].dev = d[k]; b->sh[k].cb_version = 0;
+    }
+    return 0;
+}
+
+#define NEED_MODEL(b) do { if (!(b) || !(b)->n_shards || !(b)->sh[0].dev) { set_err("batch has no model (lpcnet_batch_load_model)"); return LPCN_E_MODEL; } } while (0)
+#define NEED_ONE_SHARD(b, what) do { if ((b)->n_shards != 1) { set_err(what ": device pointers belong to one device; use the _shard form on a sharded batch"); return LPCN_E_ARG; } } while (0)
+
+/* ---- one call over the shards (api_shards.h).  Shard after shard on the calling thread, stopping at the first that fails: `call` on every shard
+ * `s` that holds some of the streams [first, first + count) -- [lfirst, lfirst + lcount) of its own; the shard's streams are `at` -- ... */
+#define EACH_SHARD_IN(first, count, call) do { for (int k_ = -1, lfirst, lcount; shard_next_in(b->at, b->n_shards, first, count, &k_, &lfirst, &lcount); ) { \
+    batch_shard *s = &b->sh[k_]; const shard_span at = b->at[k_]; (void)at; int rc_ = (call); if (rc_) { take_engine_err(); return rc_; } } return 0; } while (0)
+#define EACH_SHARD(call) EACH_SHARD_IN(0, b->n, call)
+/* ... or all shards at once, one host thread per shard, each on its own device and stream; with a single shard the work runs on the
+ * calling thread.  These calls hand each shard its streams' part of the caller's arrays: an argument struct and a per-shard function stand next to
+ * each such entry point. */
+static int run_shards(LPCNetBatch *b, shard_fn fn, void *args)
+{
+    char err[SHARD_ERR_LEN];
+    const int rc = shards_run(b->n_shards, 1, fn, lpcn_last_error, args, err);      /* (the engine's message is thread-local) */
+    if (rc) set_err(err);
+    return rc;
+}
+
+int lpcnet_batch_reset(LPCNetBatch *b, int first, int count)
+{
+    NEED_MODEL(b);
+    if (first < 0 || count < 0 || first + count > b->n) { set_err("reset range"); return LPCN_E_ARG; }
+    EACH_SHARD_IN(first, count, lpcn_batch_dev_reset(s->dev, lfirst, lcount));
+}
+
+typedef struct { LPCNetBatch *b; const float *features; int feat_stride; short *pcm; int n_frames, preload; } synth_args;
+static int synth_shard(void *args, int k)
+{
+    const synth_args *a = (const synth_args *)args;
+    const size_t o = (size_t)a->b->at[k].first * a->n_frames;
+    return lpcn_batch_dev_run_host(a->b->sh[k].dev, a->features + o * a->feat_stride, a->feat_stride, a->pcm + o * LPCN_FRAME_SIZE, a->n_frames, a->preload);
+}
+int lpcnet_batch_synthesize_preload(LPCNetBatch *b, const float *features, int feat_stride, short *pcm, int n_frames, int preload)
+{
+    NEED_MODEL(b);
+    synth_args a = {b, features, feat_stride, pcm, n_frames, preload};
+    return run_shards(b, synth_shard, &a);
+}
+
+/* one frame step with per-stream arguments (see include/lpcnet_batch.h); shards run one after the other */
+int lpcnet_batch_synthesize_step(LPCNetBatch *b, const float *features, int feat_stride, short *pcm,
+                                 const int *n_samples, const int *preload, const int *mode)
+{
+    NEED_MODEL(b);
+    if (!features || !pcm || !n_samples || !preload || !mode) { set_err("lpcnet_batch_synthesize_step: bad arguments"); return LPCN_E_ARG; }
+    EACH_SHARD(lpcn_batch_dev_step_host(s->dev, features + (size_t)at.first * feat_stride, feat_stride, pcm + (size_t)at.first * LPCN_FRAME_SIZE,
+                                        n_samples + at.first, preload + at.first, mode + at.first));
+}
+
+int lpcnet_batch_synthesize(LPCNetBatch *b, const float *features, int feat_stride, short *pcm, int n_frames)
+{
+    return lpcnet_batch_synthesize_preload(b, features, feat_stride, pcm, n_frames, 0);
+}
+
+int lpcnet_batch_synthesize_device_shard(LPCNetBatch *b, int shard, const float *d_features, int feat_stride, short *d_pcm,
+                                         int n_frames, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_run(b->sh[shard].dev, d_features, feat_stride, d_pcm, n_frames, 0, hip_stream));
+}
+
+int lpcnet_batch_synthesize_device(LPCNetBatch *b, const float *d_features, int feat_stride, short *d_pcm, int n_frames, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_synthesize_device");
+    return lpcnet_batch_synthesize_device_shard(b, 0, d_features, feat_stride, d_pcm, n_frames, hip_stream);
+}
+
+int lpcnet_batch_sync(LPCNetBatch *b) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_sync(s->dev)); }
+
+/* the device copies of the VQ codebooks follow lpcnet_hip_set_codebooks() */
+static int batch_codebooks(LPCNetBatch *b)
+{
+    int version, rc = 0;
+    const float *const *cb = codebooks_rdlock(&version);
+    if (!cb[0]) { set_err("lpcnet_batch_decode: no VQ codebooks installed (lpcnet_hip_set_codebooks)"); rc = LPCN_E_MODEL; }
+    for (int k = 0; !rc && k < b->n_shards; k++)
+        if (b->sh[k].cb_version != version) {
+            rc = lpcn_engine_set_codebooks(b->sh[k].engine, cb[0], cb[1], cb[2], cb[3]);
+            if (rc) take_engine_err(); else b->sh[k].cb_version = version;
+        }
+    codebooks_unlock();
+    return rc;
+}
+
+typedef struct { LPCNetBatch *b; const unsigned char *packets; short *pcm; int n_packets; } decode_args;
+static int decode_shard(void *args, int k)
+{
+    const decode_args *a = (const decode_args *)args;
+    const size_t o = (size_t)a->b->at[k].first * a->n_packets;
+    return lpcn_batch_dev_decode_host(a->b->sh[k].dev, a->packets + o * 8, a->pcm + o * 4 * LPCN_FRAME_SIZE, a->n_packets);
+}
+/* packets [n][n_packets][8] (host) -> pcm [n][n_packets*640]; unpacking, VQ lookup and interpolation run on the device */
+int lpcnet_batch_decode(LPCNetBatch *b, const unsigned char *packets, short *pcm, int n_packets)
+{
+    NEED_MODEL(b);
+    if (n_packets <= 0) { set_err("lpcnet_batch_decode: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    decode_args a = {b, packets, pcm, n_packets};
+    return run_shards(b, decode_shard, &a);
+}
+
+/* the same with device pointers, enqueued on the caller's stream (NULL = the batch's own) */
+int lpcnet_batch_decode_device(LPCNetBatch *b, const unsigned char *d_packets, short *d_pcm, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_decode_device");
+    if (n_packets <= 0) { set_err("lpcnet_batch_decode_device: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    FWD(lpcn_batch_dev_decode(b->sh[0].dev, d_packets, d_pcm, n_packets, hip_stream));
+}
+
+/* LPC_GAMMA of the model (a #define of the reference's generated nnet_data.h, not in the blob); default 1 */
+int lpcnet_batch_set_lpc_gamma(LPCNetBatch *b, float gamma) { NEED_MODEL(b); EACH_SHARD(lpcn_engine_set_lpc_gamma(s->engine, gamma)); }
+/* END2END models (LPC from the network's reflection coefficients); a #define of the reference, not in the blob */
+int lpcnet_batch_set_end2end(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_engine_set_end2end(s->engine, on)); }
+
+/* arithmetic flavour: 0 = PARITY (default, bit-identical to the reference's generic-C build), 1 = FAST (what the
+ * reference's own SIMD builds do: fused multiply-add / int32 block accumulation; validated teacher-forced) */
+static int set_fast_shard(batch_shard *s, int on) { const int rc = lpcn_engine_set_fast(s->engine, on); return rc ? rc : lpcn_batch_dev_retune(s->dev); }
+int lpcnet_batch_set_fast(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(set_fast_shard(s, on)); }
+
+/* the shard `sv` that owns a stream, and the stream's index `iv` within it */
+#define SHARD_OF(sv, iv, b, stream) int iv; const int k_##sv = shard_of((b)->at, (b)->n_shards, stream, &iv); \
+    if (k_##sv < 0) { set_err("stream index"); return LPCN_E_ARG; } batch_shard *sv = &(b)->sh[k_##sv]
+
+int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st)
+{
+    NEED_MODEL(b);
+    SHARD_OF(s, i, b, stream);
+    if (st->magic != LPCN_MAGIC) { st->magic = LPCN_MAGIC; st->model_id = -1; }
+    FWD(lpcn_batch_dev_get_state(s->dev, i, &st->s));
+}
+
+int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st)
+{
+    NEED_MODEL(b);
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_state(s->dev, i, &st->s));
+}
+
+/* ---- packet-loss concealment (lpcnet_plc_update / lpcnet_plc_conceal per stream, causal mode; include/lpcnet_batch.h) ---- */
+#define NEED_PLC_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_plc_enabled((b)->sh[0].dev)) { set_err("packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; } } while (0)
+int lpcnet_batch_plc_enable(LPCNetBatch *b, int options)
+{
+    NEED_MODEL(b);
+    if ((options & 3) == LPCNET_PLC_NONCAUSAL) { set_err("lpcnet_batch_plc_enable: LPCNET_PLC_NONCAUSAL needs a model without feature delay (src/lpcnet_plc.c:357-361); this engine's model format has FEATURES_DELAY = 2"); return LPCN_E_ARG; }
+    if ((options & 3) == 3 || (options & ~7)) { set_err("lpcnet_batch_plc_enable: options are LPCNET_PLC_CAUSAL or LPCNET_PLC_CODEC, optionally | LPCNET_PLC_DC_FILTER"); return LPCN_E_ARG; }
+    EACH_SHARD(lpcn_batch_dev_plc_enable(s->dev, options));
+}
+int lpcnet_batch_plc_flavour(const LPCNetBatch *b)
+{
+    NEED_PLC_ON(b);
+    FWD(lpcn_batch_dev_plc_flavour(b->sh[0].dev));
+}
+int lpcnet_batch_plc_reset(LPCNetBatch *b, int first, int count)
+{
+    NEED_PLC_ON(b);
+    if (first < 0 || count < 0 || first + count > b->n) { set_err("PLC reset range"); return LPCN_E_ARG; }
+    EACH_SHARD_IN(first, count, lpcn_batch_dev_plc_reset(s->dev, lfirst, lcount));
+}
+typedef struct { LPCNetBatch *b; short *pcm; const unsigned char *lost; } plc_step_args;
+static int plc_step_shard(void *args, int k)
+{
+    const plc_step_args *a = (const plc_step_args *)args;
+    const int f = a->b->at[k].first;
+    return lpcn_batch_dev_plc_step_host(a->b->sh[k].dev, a->pcm + (size_t)f * LPCN_FRAME_SIZE, a->lost + f);
+}
+int lpcnet_batch_plc_step(LPCNetBatch *b, short *pcm, const unsigned char *lost)
+{
+    NEED_PLC_ON(b);
+    if (!pcm || !lost) { set_err("lpcnet_batch_plc_step: bad arguments"); return LPCN_E_ARG; }
+    plc_step_args a = {b, pcm, lost};
+    return run_shards(b, plc_step_shard, &a);
+}
+int lpcnet_batch_plc_step_device_shard(LPCNetBatch *b, int shard, short *d_pcm, const unsigned char *lost, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !d_pcm || !lost) { set_err("lpcnet_batch_plc_step_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_plc_step(b->sh[shard].dev, d_pcm, lost, hip_stream));
+}
+int lpcnet_batch_plc_step_device(LPCNetBatch *b, short *d_pcm, const unsigned char *lost, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_plc_step_device");
+    return lpcnet_batch_plc_step_device_shard(b, 0, d_pcm, lost, hip_stream);
+}
+int lpcnet_batch_plc_fec_add(LPCNetBatch *b, int stream, const float *features20)
+{
+    NEED_PLC_ON(b);
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_plc_fec_add(s->dev, i, features20));
+}
+int lpcnet_batch_plc_fec_clear(LPCNetBatch *b, int stream)
+{
+    NEED_PLC_ON(b);
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_plc_fec_clear(s->dev, i));
+}
+typedef struct { LPCNetBatch *b; const float *features; const int *count, *skip; const unsigned char *clear; int *dropped; const int *vec0; } fec_feed_args;
+static int fec_feed_shard(void *args, int k)      /* (vec0[k]: shard k's first row of the packed vectors) */
+{
+    const fec_feed_args *a = (const fec_feed_args *)args;
+    const int f = a->b->at[k].first;
+    return lpcn_batch_dev_plc_fec_feed_host(a->b->sh[k].dev, a->features ? a->features + (size_t)a->vec0[k] * LPCN_NB_FEAT : NULL, a->count + f,
+                                            a->skip ? a->skip + f : NULL, a->clear ? a->clear + f : NULL, a->dropped ? a->dropped + f : NULL);
+}
+/* every stream's FEC traffic in one call (include/lpcnet_batch.h) */
+int lpcnet_batch_plc_fec_feed(LPCNetBatch *b, const float *features, const int *count, const int *skip, const unsigned char *clear, int *dropped)
+{
+    NEED_PLC_ON(b);
+    if (!count) { set_err("lpcnet_batch_plc_fec_feed: bad arguments"); return LPCN_E_ARG; }
+    int vec0[LPCN_MAX_SHARDS];
+    long long total = 0;
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard's rings change) */
+        vec0[k] = (int)total;
+        for (int i = b->at[k].first; i < b->at[k].first + b->at[k].count; i++) {
+            if (count[i] < 0 || (skip && skip[i] < 0)) { set_err("lpcnet_batch_plc_fec_feed: negative count"); return LPCN_E_ARG; }
+            if ((total += count[i]) > 0x7fffffff) { set_err("lpcnet_batch_plc_fec_feed: more than 2^31 - 1 vectors"); return LPCN_E_ARG; }
+        }
+    }
+    if (total && !features) { set_err("lpcnet_batch_plc_fec_feed: bad arguments"); return LPCN_E_ARG; }
+    fec_feed_args a = {b, features, count, skip, clear, dropped, vec0};
+    return run_shards(b, fec_feed_shard, &a);
+}
+int lpcnet_batch_plc_fec_feed_device_shard(LPCNetBatch *b, int shard, const float *d_features, const int *count, const int *skip, const unsigned char *clear,
+                                           int *dropped, void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !count) { set_err("lpcnet_batch_plc_fec_feed_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_plc_fec_feed(b->sh[shard].dev, d_features, count, skip, clear, dropped, hip_stream));
+}
+int lpcnet_batch_plc_fec_feed_device(LPCNetBatch *b, const float *d_features, const int *count, const int *skip, const unsigned char *clear, int *dropped,
+                                     void *hip_stream)
+{
+    NEED_PLC_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_plc_fec_feed_device");
+    return lpcnet_batch_plc_fec_feed_device_shard(b, 0, d_features, count, skip, clear, dropped, hip_stream);
+}
+int lpcnet_batch_plc_state_size(void) { return (int)sizeof(lpcn_plc_state_rec); }
+int lpcnet_batch_get_plc_state(LPCNetBatch *b, int stream, void *out)
+{
+    NEED_PLC_ON(b);
+    if (!out) { set_err("lpcnet_batch_get_plc_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_get_plc_state(s->dev, i, (lpcn_plc_state_rec *)out));
+}
+int lpcnet_batch_set_plc_state(LPCNetBatch *b, int stream, const void *in)
+{
+    NEED_PLC_ON(b);
+    if (!in) { set_err("lpcnet_batch_set_plc_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_plc_state(s->dev, i, (const lpcn_plc_state_rec *)in));
+}
+int lpcnet_batch_plc_burg(LPCNetBatch *b, const float *x, float *ceps36)
+{
+    NEED_PLC_ON(b);
+    if (!x || !ceps36) { set_err("lpcnet_batch_plc_burg: bad arguments"); return LPCN_E_ARG; }
+    EACH_SHARD(lpcn_batch_dev_plc_burg_host(s->dev, x + (size_t)at.first * LPCN_FRAME_SIZE, ceps36 + (size_t)at.first * 2 * LPCN_NB_BANDS));
+}
+int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20)
+{
+    NEED_PLC_ON(b);
+    if (!in57 || !out20) { set_err("lpcnet_batch_plc_pred: bad arguments"); return LPCN_E_ARG; }
+    EACH_SHARD(lpcn_batch_dev_plc_pred_host(s->dev, in57 + (size_t)at.first * LPCN_PLC_IN, out20 + (size_t)at.first * LPCN_NB_FEAT));
+}
+/* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */
+typedef struct { LPCNetBatch *b; const void *pcm; int is_float; float *features; int feat_stride, n_frames; } analyze_args;
+static int analyze_shard(void *args, int k)
+{
+    const analyze_args *a = (const analyze_args *)args;
+    const size_t o = (size_t)a->b->at[k].first * a->n_frames, op = o * LPCN_FRAME_SIZE;
+    return lpcn_batch_dev_analyze_host(a->b->sh[k].dev, a->is_float ? (const void *)((const float *)a->pcm + op) : (const void *)((const short *)a->pcm + op),
+                                       a->is_float, a->features + o * a->feat_stride, a->feat_stride, a->n_frames);
+}
+static int analyze_host(LPCNetBatch *b, const void *pcm, int is_float, float *features, int feat_stride, int n_frames)
+{
+    NEED_MODEL(b);
+    if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_analyze: bad arguments"); return LPCN_E_ARG; }
+    analyze_args a = {b, pcm, is_float, features, feat_stride, n_frames};
+    return run_shards(b, analyze_shard, &a);
+}
+int lpcnet_batch_analyze(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_frames)
+{
+    return analyze_host(b, pcm, 0, features, feat_stride, n_frames);
+}
+int lpcnet_batch_analyze_float(LPCNetBatch *b, const float *pcm, float *features, int feat_stride, int n_frames)
+{
+    return analyze_host(b, pcm, 1, features, feat_stride, n_frames);
+}
+int lpcnet_batch_analyze_device_shard(LPCNetBatch *b, int shard, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride,
+                                      int n_frames, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_analyze(b->sh[shard].dev, d_pcm, pcm_is_float, d_features, feat_stride, n_frames, hip_stream));
+}
+int lpcnet_batch_analyze_device(LPCNetBatch *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
+                                void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_analyze_device");
+    return lpcnet_batch_analyze_device_shard(b, 0, d_pcm, pcm_is_float, d_features, feat_stride, n_frames, hip_stream);
+}
+int lpcnet_batch_analysis_enable(LPCNetBatch *b, int max_frames) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_analysis_enable(s->dev, max_frames)); }
+int lpcnet_batch_analysis_reset(LPCNetBatch *b, int first, int count)
+{
+    NEED_MODEL(b);
+    if (first < 0 || count < 0 || first + count > b->n) { set_err("analysis reset range"); return LPCN_E_ARG; }
+    EACH_SHARD_IN(first, count, lpcn_batch_dev_analysis_reset(s->dev, lfirst, lcount));
+}
+int lpcnet_batch_analysis_state_size(void) { return (int)sizeof(lpcn_analysis_state); }
+int lpcnet_batch_get_analysis_state(LPCNetBatch *b, int stream, void *out)
+{
+    NEED_MODEL(b);
+    if (!out) { set_err("lpcnet_batch_get_analysis_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_get_analysis_state(s->dev, i, (lpcn_analysis_state *)out));
+}
+int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, const void *in)
+{
+    NEED_MODEL(b);
+    if (!in) { set_err("lpcnet_batch_set_analysis_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_analysis_state(s->dev, i, (const lpcn_analysis_state *)in));
+}
+
+typedef struct { LPCNetBatch *b; const short *pcm; unsigned char *packets; float *features; int feat_stride, n_packets; } encode_args;      /* packets or features */
+static int encode_shard(void *args, int k)
+{
+    const encode_args *a = (const encode_args *)args;
+    const size_t o = (size_t)a->b->at[k].first * a->n_packets;
+    return lpcn_batch_dev_encode_host(a->b->sh[k].dev, a->pcm + o * 4 * LPCN_FRAME_SIZE, a->packets ? a->packets + o * 8 : NULL,
+                                      a->features ? a->features + o * 4 * a->feat_stride : NULL, a->feat_stride, a->n_packets);
+}
+/* ---- encoder (lpcnet_encode / lpcnet_compute_features per stream and packet; include/lpcnet_batch.h) ---- */
+int lpcnet_batch_encode(LPCNetBatch *b, const short *pcm, unsigned char *packets, int n_packets)
+{
+    NEED_MODEL(b);
+    if (!pcm || !packets || n_packets < 1) { set_err("lpcnet_batch_encode: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    encode_args a = {b, pcm, packets, NULL, 0, n_packets};
+    return run_shards(b, encode_shard, &a);
+}
+int lpcnet_batch_encode_device_shard(LPCNetBatch *b, int shard, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    if (!d_pcm || !d_packets || n_packets < 1) { set_err("lpcnet_batch_encode_device: bad arguments"); return LPCN_E_ARG; }
+    int rc = batch_codebooks(b);
+    if (rc) return rc;
+    FWD(lpcn_batch_dev_encode(b->sh[shard].dev, d_pcm, d_packets, n_packets, hip_stream));
+}
+int lpcnet_batch_encode_device(LPCNetBatch *b, const short *d_pcm, unsigned char *d_packets, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_encode_device");
+    return lpcnet_batch_encode_device_shard(b, 0, d_pcm, d_packets, n_packets, hip_stream);
+}
+int lpcnet_batch_compute_features(LPCNetBatch *b, const short *pcm, float *features, int feat_stride, int n_packets)
+{
+    NEED_MODEL(b);
+    if (!pcm || !features || n_packets < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_compute_features: bad arguments"); return LPCN_E_ARG; }
+    encode_args a = {b, pcm, NULL, features, feat_stride, n_packets};
+    return run_shards(b, encode_shard, &a);
+}
+int lpcnet_batch_compute_features_device(LPCNetBatch *b, const short *d_pcm, float *d_features, int feat_stride, int n_packets, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_compute_features_device");
+    if (!d_pcm || !d_features || n_packets < 1 || feat_stride < LPCN_AN_NB_FEATURES) { set_err("lpcnet_batch_compute_features_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_compute_features(b->sh[0].dev, d_pcm, d_features, feat_stride, n_packets, hip_stream));
+}
+int lpcnet_batch_encoder_enable(LPCNetBatch *b, int max_packets) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_encoder_enable(s->dev, max_packets)); }
+int lpcnet_batch_get_encoder_vq_mem(LPCNetBatch *b, int stream, float *out18)
+{
+    NEED_MODEL(b);
+    if (!out18) { set_err("lpcnet_batch_get_encoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_get_encoder_vq_mem(s->dev, i, out18));
+}
+int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in18)
+{
+    NEED_MODEL(b);
+    if (!in18) { set_err("lpcnet_batch_set_encoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_encoder_vq_mem(s->dev, i, in18));
+}
+
+int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }
+int lpcnet_batch_tune(LPCNetBatch *b) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_tune(s->dev)); }
+int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x3(s->dev, mode)); }
+/* (every shard holds the same model: a refusal comes from the first shard, before anything has changed) */
+int lpcnet_batch_set_two_group_streaming(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x2_streamed(s->dev, on)); }
+int lpcnet_batch_get_two_group_streaming(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x2_streamed(b->sh[0].dev) : 0; }
+int lpcnet_batch_set_group_schedule(LPCNetBatch *b, int form, int lanes)
+{
+    NEED_MODEL(b);
+    if (form < 0 || form > 1 || lanes < 1 || lanes > 4) { set_err("lpcnet_batch_set_group_schedule: form must be 0 or 1 and lanes 1 .. 4"); return LPCN_E_ARG; }      /* (no shard changes) */
+    EACH_SHARD(lpcn_batch_dev_set_group_schedule(s->dev, form, lanes));
+}
+int lpcnet_batch_get_group_schedule(const LPCNetBatch *b, int *form, int *lanes)
+{
+    NEED_MODEL(b);
+    FWD(lpcn_batch_dev_get_group_schedule(b->sh[0].dev, form, lanes));
+}
+int lpcnet_batch_group_form(const LPCNetBatch *b, int cnt)
+{
+    NEED_MODEL(b);
+    const int rc = lpcn_batch_dev_group_form(b->sh[0].dev, cnt);
+    if (rc < 0) take_engine_err();
+    return rc;
+}
+int lpcnet_batch_last_groups(const LPCNetBatch *b, int *rec, int cap)
+{
+    NEED_MODEL(b);
+    if (cap < 0 || (cap && !rec)) { set_err("lpcnet_batch_last_groups: bad arguments"); return LPCN_E_ARG; }
+    return lpcn_batch_dev_last_groups(b->sh[0].dev, rec, cap);
+}
+int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x3(b->sh[0].dev) : 0; }
+int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_streams_per_wg(b->sh[0].dev) : 0; }
+int lpcnet_batch_enable_timing(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_enable_timing(s->dev, on)); }
+/* kernel milliseconds of the most recent run: the slowest shard */
+int lpcnet_batch_last_timing(LPCNetBatch *b, float *ms_s, float *ms_f)
+{
+    NEED_MODEL(b);
+    float bs = 0.f, bf = 0.f;
+    for (int k = 0; k < b->n_shards; k++) {
+        float a = 0.f, c = 0.f;
+        lpcn_batch_dev_last_timing(b->sh[k].dev, &a, &c);
+        if (a > bs) bs = a;
+        if (c > bf) bf = c;
+    }
+    if (ms_s) *ms_s = bs;
+    if (ms_f) *ms_f = bf;
+    return 0;
+}
+
+int lpcnet_batch_run_tail(LPCNetBatch *b, const float *cond_a, const float *cond_b, const float *lpc, short *pcm, int n_frames, int preload)
+{
+    NEED_MODEL(b);
+    const size_t per = (size_t)n_frames;                /* (per stream: frames) */
+    EACH_SHARD(lpcn_batch_dev_run_tail_host(s->dev, cond_a + at.first * per * LPCN_ROWS_A, cond_b + at.first * per * LPCN_ROWS_B, lpc + at.first * per * LPCN_LPC_ORDER,
+                                            pcm + at.first * per * LPCN_FRAME_SIZE, n_frames, preload));
+}
+
+int lpcnet_batch_run_frames(LPCNetBatch *b, const float *features, int feat_stride, float *cond_a, float *cond_b, float *lpc, int n_frames)
+{
+    NEED_MODEL(b);
+    const size_t per = (size_t)n_frames;                /* (per stream: frames) */
+    EACH_SHARD(lpcn_batch_dev_run_frames_host(s->dev, features + at.first * per * feat_stride, feat_stride, cond_a ? cond_a + at.first * per * LPCN_ROWS_A : NULL,
+                                              cond_b ? cond_b + at.first * per * LPCN_ROWS_B : NULL, lpc ? lpc + at.first * per * LPCN_LPC_ORDER : NULL, n_frames));
+}
+
+int lpcnet_batch_state_size(void) { return (int)sizeof(lpcn_stream_state); }
+int lpcnet_batch_get_raw_state(LPCNetBatch *b, int stream, void *out)
+{
+    NEED_MODEL(b);
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_get_state(s->dev, i, (lpcn_stream_state *)out));
+}
+int lpcnet_batch_set_raw_state(LPCNetBatch *b, int stream, const void *in)
+{
+    NEED_MODEL(b);
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_state(s->dev, i, (const lpcn_stream_state *)in));
+}
+int lpcnet_batch_debug_trace(LPCNetBatch *b, int n_samples, float *host_out) { NEED_MODEL(b); FWD(lpcn_batch_dev_debug_trace(b->sh[0].dev, n_samples, host_out)); }
+int lpcnet_batch_profile(LPCNetBatch *b, unsigned long long *out) { NEED_MODEL(b); FWD(lpcn_batch_dev_profile(b->sh[0].dev, out)); }

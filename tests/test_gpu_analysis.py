@@ -124,6 +124,11 @@ def test_2048_streams_at_once_and_a_sharded_batch(blob_f32, hip_lib):
     assert len(sh.shards) == 2
     got = np.concatenate([sh.analyze(pcm[:301, :160 * 2]), sh.analyze(pcm[:301, 160 * 2:])], axis=1)
     assert same(got, out[:301])
+    edge = sh.shards[1][0]
+    sh.analysis_reset(edge - 2, 4)                                                # two streams on either side of the shard boundary restart
+    again = sh.analyze(pcm[:301, :160 * 2])
+    assert same(again[edge - 2:edge + 2], out[edge - 2:edge + 2, :2])
+    assert not same(again[edge - 3], out[edge - 3, :2]) and not same(again[edge + 2], out[edge + 2, :2])      # their neighbours went on
     sh.close()
 
 

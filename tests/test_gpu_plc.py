@@ -183,6 +183,28 @@ def test_reset_and_rollback(gold, blob_plc, pcm_in, hip_lib):
     b.close()
 
 
+def test_reset_across_a_shard_boundary(gold, blob_plc, pcm_in, hip_lib):
+    """the reset half of test_reset_and_rollback on two shards of two streams each: plc_reset(1, 2) takes the last stream of the first shard and
+    the first stream of the second"""
+    lost = pm.loss_patterns()
+    streams = [3, 6, 7, 9]
+    b = api.LPCNetBatch(4, blob_plc, devices=[0, 0])
+    assert b.shards == [(0, 2, 0), (2, 2, 0)]
+    b.plc_enable(api.PLC_CAUSAL | api.PLC_DC_FILTER)
+    head = run(b, pcm_in, lost, 0, 40, streams=streams)
+    b.plc_reset(1, 2)                                 # streams 1, 2 of the batch start over; 0 and 3 go on
+    tail = run(b, pcm_in[:, 40:], lost[:, 40:], 0, 50, streams=streams)
+    b.close()
+    fresh = api.LPCNetBatch(4, blob_plc)
+    fresh.plc_enable(api.PLC_CAUSAL | api.PLC_DC_FILTER)
+    new = run(fresh, pcm_in[:, 40:], lost[:, 40:], 0, 50, streams=streams)
+    fresh.close()
+    assert np.array_equal(tail[1:3], new[1:3])
+    want = gold["pcm_crc"][2]
+    got = pm.block_crc(np.concatenate([head, tail], axis=1))
+    assert np.array_equal(got[0], want[3, :9]) and np.array_equal(got[3], want[9, :9]) and np.array_equal(got[1, :4], want[6, :4])
+
+
 def test_device_pointer_step_and_capture_refusal(gold, blob_plc, pcm_in, hip_lib):
     import torch
     dev = torch.device("cuda:0")

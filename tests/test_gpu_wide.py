@@ -250,6 +250,32 @@ def test_sharded_batch_in_c(blob_f32, golden, hip_lib):
     b.close(); one.close()
 
 
+def test_sharded_batch_calls_that_run_shard_after_shard(blob_f32, hip_lib):
+    """The host-pointer calls whose shards run in turn hand every shard its own part of the caller's arrays: 5 streams as shards of 3 and 2
+    on one device, 3 frames (two start-up frames and the first live one), bit for bit against the plain-C oracle.  The per-stream step with
+    N = 40 on every stream against orc_synthesize with N; the frame network and the sample loop as two calls per frame against synthesize."""
+    n, T, N = 5, 3, 40
+    feats = distinct_feats(7400, n, T)
+    om = orc.OracleModel(blob_f32)
+    b = api.LPCNetBatch(n, blob_f32, devices=[0, 0])
+    assert b.shards == [(0, 3, 0), (3, 2, 0)]
+    ost = [om.new_state() for _ in range(n)]
+    for t in range(T):
+        got = b.synthesize_step(np.ascontiguousarray(feats[:, t]), np.zeros((n, 160), np.int16), [N] * n, [0] * n, [1] * n)
+        for s in range(n):
+            ref = np.zeros(160, np.int16)
+            ost[s].L.orc_synthesize(ost[s].p, np.ascontiguousarray(feats[s, t, :20]), ref, N, 0)
+            assert np.array_equal(got[s, :N], ref[:N]), (t, s)
+    assert got[:, :N].any(axis=1).all()                      # (the third frame is live on every stream)
+    b.reset()
+    want = np.stack([om.new_state().synthesize(feats[s]) for s in range(n)])
+    for t in range(T):
+        ca, cb, lp = b.run_frames(np.ascontiguousarray(feats[:, t:t + 1]))
+        assert np.array_equal(b.run_tail(ca, cb, lp), want[:, t * 160:(t + 1) * 160]), t
+    assert want[:, 2 * 160:].any(axis=1).all()
+    b.close()
+
+
 @pytest.mark.parametrize("kw,n", [(dict(), 1024), (dict(densities=(0.07, 0.07, 0.25)), 1024), (dict(flavour="int8"), 1024), (dict(), 2560)],
                          ids=["default", "denseA", "int8", "default2560"])
 def test_streams_per_workgroup_is_measured_not_looked_up(kw, n, hip_lib):
@@ -300,7 +326,7 @@ def test_streams_per_workgroup_is_measured_not_looked_up(kw, n, hip_lib):
 def test_legacy_api_combines_concurrent_callers(blob_f32, hip_lib):
     """VERDICT r3 (missing 4): the reference is re-entrant per state -- N threads with N LPCNetStates scale over N cores.  The
     engine's drop-in lpcnet_synthesize used to serialise all states of a model behind one 1-stream batch.  Now concurrent
-    callers are combined into one multi-stream pass (api.c: comb_synthesize): 64 threads x 50 frames, one state each, every
+    callers are combined into one multi-stream pass (api_stream.c: dispatch / comb_run): 64 threads x 50 frames, one state each, every
     thread's PCM must be the oracle's bit for bit, and the aggregate rate must be a large multiple of one thread's."""
     import threading, time
     n, T = 64, 50
