@@ -100,7 +100,9 @@ LPCNET_EXPORT int lpcnet_batch_set_end2end(LPCNetBatch *b, int on);
  * definition: the oracle restates it (oracle/lpcnet_oracle.c: orc_mdense_f16_path -- binary16 weights and GRU-B state, fp32
  * sums, both v_dot2 rounding orders) and replays every tree decision of the engine from the traced GRU-B state against the
  * reference RNG's thresholds, within a 2e-4 x max(1, |logit|) band (tests/test_gpu_fast.py::
- * test_fp16_dual_fc_against_the_oracle_restatement; fewer than 1 % of the decisions may fall inside the band). */
+ * test_fp16_dual_fc_against_the_oracle_restatement; fewer than 1 % of the decisions may fall inside the band).
+ * Both FAST flavours run at up to four streams per workgroup; FAST = 1 runs the two-group kernel (eight) for a batch that asked with
+ * lpcnet_batch_set_fast_two_group. */
 LPCNET_EXPORT int lpcnet_batch_set_fast(LPCNetBatch *b, int on);
 LPCNET_EXPORT int lpcnet_batch_decode_device(LPCNetBatch *b, const unsigned char *d_packets, short *d_pcm, int n_packets,
                                              void *hip_stream);
@@ -252,7 +254,9 @@ LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LP
 /* Tuning / introspection */
 LPCNET_EXPORT int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int s);      /* 1, 2, 4, 8; 0 = auto.  8 = the two-group kernel (float blobs with a dense GRU-B matrix and
                                                                                         * <= 32 GRU-A items per lane, bit-exact arithmetic): chosen automatically beyond four streams per CU.
-                                                                                        * Models of 33 .. 96 items per lane: after lpcnet_batch_set_two_group_streaming(b, 1) */
+                                                                                        * Models of 33 .. 96 items per lane: after lpcnet_batch_set_two_group_streaming(b, 1).
+                                                                                        * FAST fp32 arithmetic: after lpcnet_batch_set_fast_two_group(b, 1); without it a pinned
+                                                                                        * eight runs at four while FAST is on */
 LPCNET_EXPORT int lpcnet_batch_get_streams_per_workgroup(const LPCNetBatch *b);
 /* Which form of the two-group kernel runs at eight streams per workgroup: 0 = eight waves (two per SIMD), 1 = twelve waves (three per SIMD; needs the
  * model's twelve-wave image: an error without it), -1 = as measured / as the table says.  Both forms produce the same bits.  get: what a launch of the
@@ -263,12 +267,24 @@ LPCNET_EXPORT int lpcnet_batch_get_twelve_waves(const LPCNetBatch *b);
  * lane in registers and fetch the others from L2 every sample.  Off by default; a batch that does not ask behaves as before.  on = 1 waits for
  * enqueued work, uploads the model's wide image once, and from then on this batch treats eight streams per workgroup like any two-group model: the
  * value may be pinned, lpcnet_batch_tune and the first host-pointer call measure it, the group schedule may answer it.  The cost table alone never
- * chooses eight for such a model.  Same bits as the four-stream kernel.  FAST arithmetic under a pinned eight runs at four, as always; the
- * twelve-wave form stays unavailable.  on = 0 puts the batch back on the four-stream kernel (LPCNET_HIP_E_ARG while eight is pinned).
+ * chooses eight for such a model.  Same bits as the four-stream kernel.  FAST arithmetic under a pinned eight runs at four (the streamed variants have no
+ * FAST form, lpcnet_batch_set_fast_two_group refuses such a model); the twelve-wave form stays unavailable.  on = 0 puts the batch back on the four-stream kernel (LPCNET_HIP_E_ARG while eight is pinned).
  * A model that has the ordinary two-group image: returns 0 and changes nothing.  int8 blobs, a block-sparse GRU-B matrix, more than 96 items:
  * LPCNET_HIP_E_MODEL with a message, setting unchanged.  LPCNET_HIP_X2_STREAMED=1, read when a batch is created, switches it on where the model allows. */
 LPCNET_EXPORT int lpcnet_batch_set_two_group_streaming(LPCNetBatch *b, int on);
 LPCNET_EXPORT int lpcnet_batch_get_two_group_streaming(const LPCNetBatch *b);
+/* The two-group kernel under FAST fp32 arithmetic (lpcnet_batch_set_fast(b, 1)): GRU-A's items accumulate on the matrix pipe, every activation is the
+ * hardware exp2 / rcp, the sampling tree's terms are fused; GRU-B's chains keep their separately rounded sums.  Off by default; a batch that does not
+ * ask behaves as before (FAST runs at up to four streams per workgroup, a pinned eight at four).  on = 1 waits for enqueued work and sets the switch
+ * on every shard; it may be set while PARITY is active and takes effect whenever FAST = 1 is on: eight streams per workgroup may then be pinned, and
+ * the cost table picks eight at exactly the stream counts where it does under PARITY (beyond four streams per CU) -- FAST is never measured, so its
+ * output stays a function of the stream count and this switch, not of timing.  Under PARITY and under FAST = 2 (fp16 dual FC) nothing that runs
+ * changes; the twelve-wave form is never chosen under FAST.  Not the bits of the four-stream FAST kernel (another summation order): inside the same
+ * teacher-forced envelope (tests/test_gpu_x2_fast.py).  on = 0 puts the batch back (LPCNET_HIP_E_ARG while FAST is on and eight is pinned).
+ * int8 blobs, a block-sparse GRU-B matrix, a model whose two-group image is the wide one (33 .. 96 items per lane) or absent: LPCNET_HIP_E_MODEL with
+ * a message, setting unchanged.  LPCNET_HIP_X2_FAST=1, read when a batch is created, switches it on where the model allows. */
+LPCNET_EXPORT int lpcnet_batch_set_fast_two_group(LPCNetBatch *b, int on);
+LPCNET_EXPORT int lpcnet_batch_get_fast_two_group(const LPCNetBatch *b);
 /* The group schedule: how the compacted groups of a PLC step or a per-stream step (lpcnet_batch_synthesize_step) are launched.  Off by default.
  * form: 0 = groups launch in the batch's form (default), 1 = in the cost table's form for the group's own size -- while the streams per
  *   workgroup are not pinned and the arithmetic is bit-exact, where every form gives the same samples; a pinned value and FAST keep the batch's form.

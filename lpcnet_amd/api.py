@@ -212,6 +212,8 @@ def load_library():
     L.lpcnet_batch_get_twelve_waves.argtypes = [vp]
     L.lpcnet_batch_set_two_group_streaming.argtypes = [vp, C.c_int]
     L.lpcnet_batch_get_two_group_streaming.argtypes = [vp]
+    L.lpcnet_batch_set_fast_two_group.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_get_fast_two_group.argtypes = [vp]
     L.lpcnet_hip_x2_wide_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_hip_x3_image_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lpcnet_batch_tune.argtypes = [vp]
@@ -767,6 +769,15 @@ class LPCNetBatch:
     @two_group_streaming.setter
     def two_group_streaming(self, on):
         self._chk(self.L.lpcnet_batch_set_two_group_streaming(self.p, 1 if on else 0), "set_two_group_streaming")
+
+    @property
+    def fast_two_group(self):
+        """the two-group kernel under FAST fp32 arithmetic for this batch (set_fast(1); include/lpcnet_batch.h); off by default"""
+        return bool(self.L.lpcnet_batch_get_fast_two_group(self.p))
+
+    @fast_two_group.setter
+    def fast_two_group(self, on):
+        self._chk(self.L.lpcnet_batch_set_fast_two_group(self.p, 1 if on else 0), "set_fast_two_group")
 
     @property
     def group_schedule(self):

@@ -31,7 +31,7 @@ API_UNITS = ("api_core", "api_stream", "api_batch", "api_tools")
 REGISTRY_UNIT = "api_stream"
 # ... and every object of the library except the registry's, which build_small_registry() replaces
 OBJECTS = tuple(u + ".o" for u in ENGINE_UNITS + tuple(u for u in API_UNITS if u != REGISTRY_UNIT)) + (
-    "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x2w.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
+    "sample_s1.o", "sample_s2.o", "sample_s4.o", "sample_x2.o", "sample_x2f.o", "sample_x2w.o", "sample_x3.o", "model_pack.o", "plc_plan.o")
 
 
 def source_hashes(extra_flags=()):
@@ -99,7 +99,7 @@ def build(force=False, verbose=True, prof=False):
     jobs = [[HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, u + ".hip"), "-o", os.path.join(objdir, u + ".o")] for u in ENGINE_UNITS]
     for sv in (1, 2, 4):
         jobs.append([HIPCC] + HIP_FLAGS + pf + extra + [f"-DLPCN_S={sv}", "-c", os.path.join(CSRC, "sample_variants.hip"), "-o", os.path.join(objdir, f"sample_s{sv}.o")])
-    for u in ("sample_x2", "sample_x2w", "sample_x3"):
+    for u in ("sample_x2", "sample_x2f", "sample_x2w", "sample_x3"):
         jobs.append([HIPCC] + HIP_FLAGS + pf + extra + ["-c", os.path.join(CSRC, u + ".hip"), "-o", os.path.join(objdir, u + ".o")])
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=min(len(jobs), 16, len(os.sched_getaffinity(0)))) as ex:

@@ -470,6 +470,8 @@ int lpcnet_batch_set_twelve_waves(LPCNetBatch *b, int mode) { NEED_MODEL(b); EAC
 /* (every shard holds the same model: a refusal comes from the first shard, before anything has changed) */
 int lpcnet_batch_set_two_group_streaming(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x2_streamed(s->dev, on)); }
 int lpcnet_batch_get_two_group_streaming(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x2_streamed(b->sh[0].dev) : 0; }
+int lpcnet_batch_set_fast_two_group(LPCNetBatch *b, int on) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_x2_fast(s->dev, on)); }
+int lpcnet_batch_get_fast_two_group(const LPCNetBatch *b) { return b && b->n_shards && b->sh[0].dev ? lpcn_batch_dev_x2_fast(b->sh[0].dev) : 0; }
 int lpcnet_batch_set_group_schedule(LPCNetBatch *b, int form, int lanes)
 {
     NEED_MODEL(b);

@@ -459,6 +459,17 @@ int auto_streams_per_wg(const lpcn_batch_dev *b, int n)
         static const float step_x2 = 13.9f;
         const int wgs = (n + 7) / 8;
         const float t = (float)((wgs + cus - 1) / cus) * step_x2;
+        // (FAST, a batch that opted in -- lpcn_batch_dev_set_x2_fast: eight at exactly the stream counts where PARITY gets eight, so the comparison is
+        // PARITY's; the FAST form of the kernel has no step time of its own in this table)
+        if (e->fast) {
+            float t_par = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                const int S = 1 << k, w = (n + S - 1) / S;
+                const float tk = (float)((w + cus - 1) / cus) * step_f32[k];
+                if (k == 0 || tk < t_par) t_par = tk;
+            }
+            if (t < t_par) best = 8;
+        } else
         if (t < best_t) { best = 8; best_t = t; }
     }
     return best;
@@ -480,6 +491,8 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     auto fail = [&](int code) { lpcn_batch_dev_destroy(b); return code; };
     const char *xs = getenv("LPCNET_HIP_X2_STREAMED");       // tools (bench.py on a trained-like model): the streamed two-group variants where the model allows, silently not where it does not
     if (xs && *xs == '1' && (e->x2w_host || e->x2_wide)) { const int rcs = lpcn_batch_dev_set_x2_streamed(b, 1); if (rcs) return fail(rcs); }
+    const char *xf = getenv("LPCNET_HIP_X2_FAST");           // tools (bench.py --fast): the two-group kernel under FAST fp32 arithmetic where the model allows, silently not where it does not
+    if (xf && *xf == '1' && x2_fast_servable(e)) { const int rcf = lpcn_batch_dev_set_x2_fast(b, 1); if (rcf) return fail(rcf); }
     const size_t rows = (size_t)n * max_chunk;
     int rc = 0;
     if ((rc = b->d_state.alloc(n)) || (rc = b->d_fc_base.alloc(n)) || (rc = b->d_cond_a.alloc(rows * LPCN_ROWS_A)) || (rc = b->d_cond_b.alloc(rows * LPCN_ROWS_B)) ||
@@ -555,7 +568,7 @@ extern "C" int lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s)
 {
     b->S_auto = s == 0;
     if (s == 0) { s = auto_streams_per_wg(b, b->n); b->tuned = false; }
-    if (s == 8 && !x2_available(b)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane (33 .. 96: lpcnet_batch_set_two_group_streaming first), PARITY arithmetic"); return LPCN_E_ARG; }
+    if (s == 8 && !x2_available(b)) { snprintf(g_err, sizeof(g_err), "eight streams per workgroup need a float blob with a dense GRU-B matrix and <= 32 items per lane (33 .. 96: lpcnet_batch_set_two_group_streaming first), PARITY arithmetic (FAST fp32: lpcnet_batch_set_fast_two_group first)"); return LPCN_E_ARG; }
     if (s != 1 && s != 2 && s != 4 && s != 8) { snprintf(g_err, sizeof(g_err), "streams per workgroup must be 1, 2, 4 or 8"); return LPCN_E_ARG; }
     b->S = s;
     b->pack2 = use_pack2(b, b->n, b->S);
@@ -589,6 +602,23 @@ extern "C" int lpcn_batch_dev_set_x2_streamed(lpcn_batch_dev *b, int on)
     return lpcn_batch_dev_retune(b);                         // (the engine's choice is made again, and measured again at the next run; a pinned value stays)
 }
 extern "C" int lpcn_batch_dev_x2_streamed(const lpcn_batch_dev *b) { return b->x2_streamed ? 1 : 0; }
+// The two-group kernel under FAST fp32 arithmetic for THIS batch (off by default).  On: while the engine's flavour is FAST without the fp16 dual FC,
+// eight streams per workgroup are available to the batch -- pinned, or the cost table's answer at the stream counts where PARITY gets eight (never a
+// measurement: FAST is not timed); under PARITY and under the fp16 dual FC nothing that runs changes.  Needs the ordinary two-group image.
+extern "C" int lpcn_batch_dev_set_x2_fast(lpcn_batch_dev *b, int on)
+{
+    lpcn_engine *e = b->e;
+    if (e->is_int8) { snprintf(g_err, sizeof(g_err), "FAST two-group: int8 blobs have no two-group kernel"); return LPCN_E_MODEL; }
+    if (!e->image[IMG_PARITY].args.b_dense) { snprintf(g_err, sizeof(g_err), "FAST two-group: the two-group kernel needs a dense GRU-B input matrix"); return LPCN_E_MODEL; }
+    if (!x2_fast_servable(e)) { snprintf(g_err, sizeof(g_err), "FAST two-group: the model has no register-resident two-group image (more than %d items per lane, or switched off when the engine was created)", LPCN_X2_NW_MAX); return LPCN_E_MODEL; }
+    if (!on && b->x2_fast && x2_fast_active(b) && !b->S_auto && b->S == 8) { snprintf(g_err, sizeof(g_err), "FAST two-group: eight streams per workgroup are pinned under FAST arithmetic; pin another value first"); return LPCN_E_ARG; }
+    if ((on != 0) == b->x2_fast) return 0;
+    DeviceGuard guard(e->device);
+    { const int rcw = wait_all(b); if (rcw) return rcw; }
+    b->x2_fast = on != 0;
+    return lpcn_batch_dev_retune(b);                         // (the table's choice is made again; a pinned value stays)
+}
+extern "C" int lpcn_batch_dev_x2_fast(const lpcn_batch_dev *b) { return b->x2_fast ? 1 : 0; }
 extern "C" int lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode)
 {
     if (mode < -1 || mode > 1) { snprintf(g_err, sizeof(g_err), "twelve-wave mode must be -1, 0 or 1"); return LPCN_E_ARG; }

@@ -174,6 +174,7 @@ struct lpcn_batch_dev {
     bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
     bool no_x2 = false;                // LPCNET_HIP_NO_X2=1 when the batch was created (tools / tests): never the two-group kernel
     bool x2_streamed = false;          // lpcn_batch_dev_set_x2_streamed: this batch may run the two-group kernel's streamed variants (a wide image)
+    bool x2_fast = false;              // lpcn_batch_dev_set_x2_fast: this batch may run the two-group kernel under FAST fp32 arithmetic (sample_x2f.hip)
     bool x3 = false;                   // at eight streams per workgroup: the twelve-wave form of the two-group kernel (measured faster on this batch, or asked for)
     int x3_mode = -1;                  // lpcn_batch_dev_set_x3: 0 never, 1 always, -1 measured (the table's value, the eight-wave form, until then)
     int pack2_force = -1;              // LPCNET_HIP_PACK2 when the batch was created (tools / tests): 0 never, 1 whenever the variant exists, -1 unset
@@ -249,9 +250,12 @@ SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_fra
 inline const GruAImage &gru_a_image(const lpcn_engine *e, int S) { return e->image[S == 8 ? IMG_X2 : (e->fast && e->image[IMG_FAST].present) ? IMG_FAST : IMG_PARITY]; }
 // Two groups of four float streams per workgroup, half a step apart (sample_kernel_x2.hip.h): float blobs, PARITY arithmetic, dense GRU-B input
 // matrix, <= 32 items per lane -- or up to 96 on its streamed variants, for the batches that opted in.  Eight streams per workgroup select it.
-inline bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && !b->e->fast && (!b->e->x2_wide || b->x2_streamed); }
-// ... and its twelve-wave form (sample_kernel_x3.hip.h), where the model has the image for it
-inline bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && b->e->image[IMG_X3].present; }
+// FAST fp32 arithmetic (not its fp16 dual FC) has the kernel too, on the ordinary image only and for the batches that opted in (x2_fast).
+inline bool x2_fast_servable(const lpcn_engine *e) { return !e->is_int8 && e->image[IMG_X2].present && !e->x2_wide; }      // (the register-resident variants)
+inline bool x2_fast_active(const lpcn_batch_dev *b) { return b->x2_fast && b->e->fast && !b->e->fc_f16 && !b->e->x2_wide; }
+inline bool x2_available(const lpcn_batch_dev *b) { return !b->no_x2 && b->e->image[IMG_X2].present && (!b->e->fast || x2_fast_active(b)) && (!b->e->x2_wide || b->x2_streamed); }
+// ... and its twelve-wave form (sample_kernel_x3.hip.h), where the model has the image for it; never under FAST
+inline bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && !b->e->fast && b->e->image[IMG_X3].present; }
 
 // engine.hip: ordering across caller streams, argument checks, the cost table
 bool stream_is_capturing(hipStream_t st);

@@ -18,6 +18,7 @@ extern "C" int lpcn_launch_sample_s2(int nw, int is_int8, int flags, int grid, i
 extern "C" int lpcn_launch_sample_s4(int nw, int is_int8, int flags, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);
 extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x2.hip: two groups of four streams
 extern "C" int lpcn_launch_sample_x2w(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);     // sample_x2w.hip: its streamed variants (more than 32 items per lane)
+extern "C" int lpcn_launch_sample_x2f(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);     // sample_x2f.hip: its register-resident variants with FAST fp32 arithmetic
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
 extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout)
 
@@ -27,7 +28,8 @@ SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_fra
 {
     const lpcn_engine *e = b->e;
     SamplePlan p{sh.S, sh.pack2, false, nullptr, 0, 0};
-    // Eight streams per workgroup become four (a) while the two-group kernel is unavailable (the arithmetic flavour changed under a pinned value) and
+    // Eight streams per workgroup become four (a) while the two-group kernel is unavailable (the arithmetic flavour changed under a pinned value and the
+    // batch has not asked for the kernel's FAST form, or the flavour is FAST with the fp16 dual FC) and
     // (b) for a launch with 4 GB or more of conditioning rows -- more than ~9 300 streams x 100 frames -- which the two-group kernel, addressing them
     // with 32-bit byte offsets, cannot reach
     if (sh.S == 8 && (!x2_available(b) || (unsigned long long)sh.n * (unsigned long long)n_frames * LPCN_ROWS_A * 4ull >= (1ull << 32))) { p.S = 4; p.pack2 = false; }
@@ -37,7 +39,7 @@ SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_fra
     p.grid = (sh.n + p.S - 1) / p.S;
     return p;
 }
-// (what a whole-batch launch of one frame runs with: four while FAST arithmetic is on under a pinned eight)
+// (what a whole-batch launch of one frame runs with: four while FAST arithmetic is on under a pinned eight, unless the batch opted in -- x2_fast)
 extern "C" int lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b) { return plan_sample(b, whole_batch(b), 1).S; }
 extern "C" int lpcn_batch_dev_x3(const lpcn_batch_dev *b) { return plan_sample(b, whole_batch(b), 1).x3 ? 1 : 0; }
 
@@ -68,7 +70,7 @@ int launch_sample(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, shor
     const int flags = (e->fast ? 1 : 0) | (p.pack2 ? 2 : 0);
     int rc = 0;
     switch (p.S) {
-    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, d_args) : (nw > LPCN_X2_NW_MAX ? lpcn_launch_sample_x2w : lpcn_launch_sample_x2)(nw, p.grid, p.lds, st, d_args); break;
+    case 8: rc = p.x3 ? lpcn_launch_sample_x3(p.grid, p.lds, st, d_args) : (e->fast ? lpcn_launch_sample_x2f : nw > LPCN_X2_NW_MAX ? lpcn_launch_sample_x2w : lpcn_launch_sample_x2)(nw, p.grid, p.lds, st, d_args); break;
     case 1: rc = lpcn_launch_sample_s1(nw, i8, flags, p.grid, p.lds, st, d_args); break;
     case 2: rc = lpcn_launch_sample_s2(nw, i8, flags, p.grid, p.lds, st, d_args); break;
     default: rc = lpcn_launch_sample_s4(nw, i8, flags, p.grid, p.lds, st, d_args); break;
@@ -95,7 +97,7 @@ int launch_frames(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, cons
 // LPCNET_HIP_NO_AUTOTUNE=1 keeps the table value.
 // Round 4: (a) the FAST flavour is never timed -- its float kernels switch GRU-B's algorithm with S (matrix-pipe GEMM at S >= 2,
 // fused DPP chains at S = 1: different summation orders), so a measured S would make FAST output depend on timing noise;
-// it takes the table's value, a pure function of (blob kind, stream count, device).  (b) the measurement is the best of
+// it takes the table's value, a pure function of (blob kind, stream count, device, the batch's FAST two-group opt-in).  (b) the measurement is the best of
 // three timing pairs.  (c) it never runs inside the enqueue-only device-pointer calls on a caller's stream (those take the
 // table's value unless lpcnet_batch_tune() has been called): it allocates, synchronises and would break stream capture.
 static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)

@@ -242,6 +242,8 @@ int  lpcn_batch_dev_streams_per_wg(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_set_streams_per_wg(lpcn_batch_dev *b, int s);              /* 1,2,4 (0=auto) */
 int  lpcn_batch_dev_set_x2_streamed(lpcn_batch_dev *b, int on);                /* the two-group kernel's streamed variants for this batch (33 .. 96 items per lane); 0 also where the model has the ordinary image */
 int  lpcn_batch_dev_x2_streamed(const lpcn_batch_dev *b);
+int  lpcn_batch_dev_set_x2_fast(lpcn_batch_dev *b, int on);                    /* the two-group kernel under FAST fp32 arithmetic for this batch (ordinary two-group image only; LPCN_E_MODEL otherwise) */
+int  lpcn_batch_dev_x2_fast(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_set_x3(lpcn_batch_dev *b, int mode);                       /* twelve-wave form of the two-group kernel: 0 never, 1 always (needs the image), -1 measured / table */
 int  lpcn_batch_dev_x3(const lpcn_batch_dev *b);                                /* what a whole-batch launch runs now */
 int  lpcn_batch_dev_retune(lpcn_batch_dev *b);                                 /* after lpcn_engine_set_fast: auto value again */

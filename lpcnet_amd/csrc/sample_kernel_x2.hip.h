@@ -23,7 +23,8 @@
 //
 // Scope: float blobs, PARITY arithmetic, dense GRU-B input matrix.  Up to 32 items per lane are register-resident (sample_x2.hip); the variants
 // above that (sample_x2w.hip: 48 / 64 / 80 / 96, a batch's opt-in -- lpcnet_batch_set_two_group_streaming) keep the first 24 items of a lane in
-// registers and STREAM the others from the L2-resident item array, the four-stream kernel's mechanism (sample_kernel.hip.h).  Everything else
+// registers and STREAM the others from the L2-resident item array, the four-stream kernel's mechanism (sample_kernel.hip.h).  FAST fp32 arithmetic
+// (a batch's opt-in -- lpcnet_batch_set_fast_two_group) has instantiations of the register-resident variants (sample_x2f.hip).  Everything else
 // runs on the four-stream kernel.
 #pragma once
 #include "sample_kernel.hip.h"
@@ -97,7 +98,9 @@ __device__ __forceinline__ TreeRow tree_row_load_packed(const LPCN_GLOBAL float 
 {
     return tree_row_load_node(fc_w, fc_b, fc_f, lpcn_tree_packed_node(lane, prefix), lane & 1);
 }
-// the decisions of the lanes' nodes: `h_s` the 16 state values of the lane's stream, `thr` the threshold of its node's level
+// the decisions of the lanes' nodes: `h_s` the 16 state values of the lane's stream, `thr` the threshold of its node's level.  FAST: every term a fused
+// multiply-add and the hardware tanh (act_tanh<true>), as in the four-stream kernel's FAST tree
+template <bool FAST = false>
 __device__ __forceinline__ unsigned long long tree_node_ballot(const TreeRow &r, const float *h_s, const float *thr, const float *tansig)
 {
     const float4 *hp = (const float4 *)h_s;
@@ -106,30 +109,42 @@ __device__ __forceinline__ unsigned long long tree_node_ballot(const TreeRow &r,
     for (int j = 0; j < NB / 4; ++j) {
         const float4 hv = hp[j];
         const tree_f4 wv = r.w[j];
+        if constexpr (FAST) {
+            sum = __builtin_fmaf(wv[0], hv.x, sum);
+            sum = __builtin_fmaf(wv[1], hv.y, sum);
+            sum = __builtin_fmaf(wv[2], hv.z, sum);
+            sum = __builtin_fmaf(wv[3], hv.w, sum);
+        } else {
         sum = sum + wv[0] * hv.x;
         sum = sum + wv[1] * hv.y;
         sum = sum + wv[2] * hv.z;
         sum = sum + wv[3] * hv.w;
+        }
     }
-    const float v = r.factor * lpcn_tanh(sum, tansig);
+    const float v = r.factor * act_tanh<FAST>(sum, tansig);
     const float vo = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));      // the other channel (quad_perm [1,0,3,2])
     const float lg = v + vo;
     return __ballot(*thr < lg);
 }
 // the stage's decisions (wave-uniform): the ballot over its nodes, walked from the stage's first node
-template <int STAGE>
+template <int STAGE, bool FAST = false>
 __device__ __forceinline__ int tree_stage_walk(const TreeRow &r, const float *h_s, const float *thr_s, const float *tansig, const int lane)
 {
-    const unsigned long long m = tree_node_ballot(r, h_s, thr_s + lpcn_tree_level(STAGE, lpcn_tree_lane_local(STAGE, lane)), tansig) & lpcn_tree_stage_mask(STAGE);
+    const unsigned long long m = tree_node_ballot<FAST>(r, h_s, thr_s + lpcn_tree_level(STAGE, lpcn_tree_lane_local(STAGE, lane)), tansig) & lpcn_tree_stage_mask(STAGE);
     return lpcn_tree_stage_walk(m, STAGE == 0 ? LPCN_TREE_TOP : LPCN_TREE_LEVELS - LPCN_TREE_TOP);
 }
 
-template <int NW>
+// FAST (lpcnet_batch_set_fast 1 with lpcnet_batch_set_fast_two_group; register-resident variants only, sample_x2f.hip): the same schedule with the
+// arithmetic of the reference's SIMD builds where it is cheaper -- a GRU-A item accumulates on the matrix pipe (the running sums are the MFMA's C
+// operand: no product tuples, no packed adds), every activation is the hardware exp2 / rcp, the tree's terms are fused.  GRU-B's chains, the start
+// values, the gate arithmetic around the activations and the leader are the PARITY statements.
+template <int NW, bool FAST = false>
 __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const LpcnSampleArgs *__restrict__ Ap)
 {
     using L = LdsX2;
     constexpr int S = 4;
     constexpr int LW = LPCN_X2_LW, TW = LPCN_X2_TW;
+    static_assert(!FAST || NW <= LPCN_X2_NW_MAX, "FAST arithmetic: the register-resident variants only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *const sm_pre_ur = (float *)(smem + L::pre_ur);
     float *const sm_inh = (float *)(smem + L::inh);
@@ -399,10 +414,11 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
         // item PF ahead, the weights of the item WSD - 1 ahead -- the first and the last only where they name a streamed item of [NR, NW).
         typedef float negz_t __attribute__((ext_vector_type(4)));
         negz_t negz = {-0.f, -0.f, -0.f, -0.f};
-        auto load_negz = [&]() __attribute__((always_inline)) { negz = (negz_t){-0.f, -0.f, -0.f, -0.f}; asm volatile("" : "+v"(negz)); };
+        auto load_negz = [&]() __attribute__((always_inline)) { if constexpr (!FAST) { negz = (negz_t){-0.f, -0.f, -0.f, -0.f}; asm volatile("" : "+v"(negz)); } };
         // one item = (this lane's row) x (one 4-wide input block) for the four streams of a group: the products of a column from ONE
         // v_mfma_f32_4x4x1 with C = -0.0 (bit for bit the separately rounded product), the sums as v_pk_add_f32 over stream pairs, columns
-        // 0..3 in order (src/vec.h:355-401)
+        // 0..3 in order (src/vec.h:355-401).  FAST: the running sums of the four streams are the C operand -- four dependent v_mfma_f32_4x4x1, each the fused
+        // multiply-adds of one column, and nothing else (sample_kernel.hip.h, "FAST: the quad broadcast as a 4x4 outer product on the matrix pipe")
         auto mac = [&](const int j) __attribute__((always_inline)) {
             typedef float f4 __attribute__((ext_vector_type(4)));
             typedef float f2 __attribute__((ext_vector_type(2)));
@@ -410,6 +426,12 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             const float hk[4] = {hv.x, hv.y, hv.z, hv.w};
             const float4 wv = wsel(j);
             const float wk[4] = {wv.x, wv.y, wv.z, wv.w};
+            if constexpr (FAST) {
+                f4 av = {acc[0], acc[1], acc[2], acc[3]};
+#pragma unroll
+                for (int c = 0; c < 4; ++c) av = __builtin_amdgcn_mfma_f32_4x4x1f32(hk[c], wk[c], av, 0, 0, 0);
+                acc[0] = av[0]; acc[1] = av[1]; acc[2] = av[2]; acc[3] = av[3];
+            } else {
             f2 a01 = {acc[0], acc[1]}, a23 = {acc[2], acc[3]};
             f4 pv[4];
             // (the four products of an item are issued back to back into four result tuples, then the sums.  Round 6 tried to software-pipeline the
@@ -424,6 +446,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 a23 = a23 + __builtin_shufflevector(pv[c], pv[c], 2, 3);
             }
             acc[0] = a01[0]; acc[1] = a01[1]; acc[2] = a23[0]; acc[3] = a23[1];
+            }
         };
         // pre-activation cell of GRU-A row r: update / reset rows share one copy, candidate rows have one per group
         auto pre_cell = [&](const int r, unsigned char *gb) __attribute__((always_inline)) -> float * {
@@ -564,9 +587,9 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 const TreeRow top = tree_row_load<0>(fc_w_s, fc_b_s, fc_f_s, ln_, 0);
                 // gates: rows [0,16) update, [16,32) reset, [32,48) candidate (src/nnet.c:362-371)
                 const int ln = ln_ & 15;
-                const float sg = lpcn_sigmoid(zrh + rec, sm_tansig);
+                const float sg = act_sigmoid<FAST>(zrh + rec, sm_tansig);
                 const float r_gate = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((16 + ln) << 2, __builtin_bit_cast(int, sg)));
-                const float hc = lpcn_tanh(zrh + rec * r_gate, sm_tansig);
+                const float hc = act_tanh<FAST>(zrh + rec * r_gate, sm_tansig);
                 const float hc_i = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((32 + ln) << 2, __builtin_bit_cast(int, hc)));
                 if (ln_ < NB) {
                     const float hold = hB_q[s * NB + ln_];
@@ -586,7 +609,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 // and goes on to P1; wave LPCN_X2_S2W runs stage 2 of all four streams in one pass (below, behind its items).  Round 10: that wave may be a chain
                 // wave again -- ONE of them, the one with the fewest items, for all four streams: its own prefix it has published itself, earlier in program order.
                 const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
-                const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
+                const int val = tree_stage_walk<0, FAST>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
                 if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
                 LPCN_X2_PROF(9);
             }
@@ -791,7 +814,7 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
             int t_ = tid0;
             LPCN_REMAT_V(t_);
             const int ln = t_ & 63, f = lpcn_tree_packed_field(ln);
-            const unsigned long long m = tree_node_ballot(sub, hB_q + f * NB, (const float *)(gq + L::g_thr) + f * 8 + lpcn_tree_packed_level(ln), sm_tansig) & lpcn_tree_packed_mask();
+            const unsigned long long m = tree_node_ballot<FAST>(sub, hB_q + f * NB, (const float *)(gq + L::g_thr) + f * 8 + lpcn_tree_packed_level(ln), sm_tansig) & lpcn_tree_packed_mask();
             int walks = 0;
 #pragma unroll
             for (int k = 0; k < S; ++k) walks |= lpcn_tree_packed_walk(m, k) << (8 * k);
@@ -826,11 +849,11 @@ __global__ __launch_bounds__(LPCN_WG_THREADS, 2) void sample_kernel_x2(const Lpc
                 hold[k] = hT_p[i];
             }
 #pragma unroll
-            for (int k = 0; k < NQ; ++k) { z[k] = lpcn_sigmoid(z[k], sm_tansig); rg[k] = lpcn_sigmoid(rg[k], sm_tansig); }
+            for (int k = 0; k < NQ; ++k) { z[k] = act_sigmoid<FAST>(z[k], sm_tansig); rg[k] = act_sigmoid<FAST>(rg[k], sm_tansig); }
 #pragma unroll
             for (int k = 0; k < NQ; ++k) a[k] = a[k] * rg[k] + sm_inh[tid + k * LPCN_WG_THREADS];
 #pragma unroll
-            for (int k = 0; k < NQ; ++k) a[k] = lpcn_tanh(a[k], sm_tansig);
+            for (int k = 0; k < NQ; ++k) a[k] = act_tanh<FAST>(a[k], sm_tansig);
             // item i = tid + 512 k is (neuron (tid >> 2) + 128 k, stream tid & 3): the stream is the lane's own for all three, and the block-ordered copy's address
             // advances by a constant (32 blocks of 64 B + 8 pads of 16 B per 128 neurons)
             const unsigned ut = (unsigned)tid;

@@ -2,6 +2,7 @@
 """Register / scratch accounting of the sample kernel's variants from the compiler's own output (no GPU needed).
 
     python tools/kernel_resources.py [--s 4] [--asm-dir DIR] [--json]
+    python tools/kernel_resources.py --s 8               (the two-group kernel: sample_x2.hip, then its FAST instantiations, sample_x2f.hip)
     python tools/kernel_resources.py --s 8 --wide        (the two-group kernel's streamed variants, sample_x2w.hip)
     python tools/kernel_resources.py --analysis          (the feature-analysis kernels of the engine's units)
     python tools/kernel_resources.py --encode            (the encoder kernels of the engine's units)
@@ -25,11 +26,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def compile_asm(s_value, out_path, wide=False):
-    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip; wide: its streamed variants, sample_x2w.hip);
-    12: its twelve-wave form (sample_x3.hip)"""
+def compile_asm(s_value, out_path, wide=False, fast=False):
+    """s_value 1 / 2 / 4: sample_variants.hip with -DLPCN_S; 8: the two-group kernel (sample_x2.hip; wide: its streamed variants, sample_x2w.hip;
+    fast: its FAST instantiations, sample_x2f.hip); 12: its twelve-wave form (sample_x3.hip)"""
     from lpcnet_amd import build
-    src = {8: "sample_x2w.hip" if wide else "sample_x2.hip", 12: "sample_x3.hip"}.get(s_value, "sample_variants.hip")
+    src = {8: "sample_x2w.hip" if wide else "sample_x2f.hip" if fast else "sample_x2.hip", 12: "sample_x3.hip"}.get(s_value, "sample_variants.hip")
     cmd = [build.HIPCC] + build.HIP_FLAGS + ([] if s_value in (8, 12) else [f"-DLPCN_S={s_value}"]) + ["--cuda-device-only", "-S", os.path.join(build.CSRC, src), "-o", out_path]
     subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
 
@@ -38,9 +39,9 @@ def demangle(name):
     m = re.match(r"_ZN4lpcn13sample_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)EEE", name)
     if m:
         return dict(S=int(m.group(1)), NW=int(m.group(2)), int8=bool(int(m.group(3))), fast=bool(int(m.group(4))), pack2=bool(int(m.group(5))))
-    m = re.match(r"_ZN4lpcn16sample_kernel_x2ILi(\d+)EEE", name)          # eight streams per workgroup (two groups of four)
+    m = re.match(r"_ZN4lpcn16sample_kernel_x2ILi(\d+)ELb(\d)EEE", name)    # eight streams per workgroup (two groups of four), PARITY / FAST
     if m:
-        return dict(S=8, NW=int(m.group(1)), int8=False, fast=False, pack2=False)
+        return dict(S=8, NW=int(m.group(1)), int8=False, fast=bool(int(m.group(2))), pack2=False)
     if re.match(r"_ZN4lpcn16sample_kernel_x3E", name):                      # ... on twelve waves, 16 items per lane (reported as S = 12)
         return dict(S=12, NW=16, int8=False, fast=False, pack2=False)
     return None
@@ -181,6 +182,12 @@ def main():
     if not os.path.exists(path):
         compile_asm(a.s, path, wide)
     rows = analyse(path)
+    if a.s == 8 and not wide:                                # ... and the FAST instantiations of the same variants, a translation unit of their own
+        path_f = os.path.join(d, "sample_s8f.s")
+        if not os.path.exists(path_f):
+            compile_asm(8, path_f, fast=True)
+        rows += analyse(path_f)
+        path += " + " + path_f
     if a.json:
         print(json.dumps(rows, indent=1))
         return
