@@ -331,6 +331,43 @@ LPCNET_EXPORT int lpcnet_hip_arith_identities_device(const float *a, const float
  * (int)floor(.5 + 127 x) with the sum in double (src/vec.h:311-316): this runs both over ALL 2^32 float bit patterns on the device.
  * out3 = {mismatches among finite |t| < 2^31, mismatches inside the reachable |t| <= 127.5, one mismatching pattern}. */
 LPCNET_EXPORT int lpcnet_hip_quant_sweep_device(unsigned long long *out3);
+/* Streams that come and go.  A batch is a CAPACITY of n streams; of shard k's count_k streams the first active_k are ACTIVE, 0 <= active_k <=
+ * count_k (default: all).  A batch that never calls lpcnet_batch_set_active runs exactly what it ran before these functions existed.
+ * set_active: active[k] for every shard (n_shards must equal lpcnet_batch_shards(b)); host-only, no wait, no device work: it takes effect for
+ *   calls enqueued after it, calls already enqueued keep the count they were enqueued with.  A count beyond its shard's streams is
+ *   LPCNET_HIP_E_ARG and no shard has changed.  get_active returns the number of shards, active_streams the sum of the counts.
+ * Which calls follow the prefix: every call that ADVANCES streams acts on the active streams only -- the host-pointer, device-pointer and _shard
+ *   forms of synthesize, synthesize_preload, synthesize_step, decode, analyze(_float), encode, compute_features, plc_step and plc_fec_feed, and
+ *   the parity seams run_tail / run_frames / plc_burg / plc_pred.  Array layouts do not change: host arrays stay [n_streams][...], a shard's device
+ *   arrays [count_k][...]; the rows of inactive streams are neither read nor written, and every byte of an inactive stream's states stays as it
+ *   was (synthesis, decoder VQ, analysis, encoder VQ and PLC states, the PLC's control state, the kept frame products and whether they exist).
+ *   lost[s], clear[s], skip[s] and mode[s] / n_samples[s] / preload[s] of an inactive stream are ignored; dropped[s] is written 0; a non-zero
+ *   count[s] of an inactive stream in plc_fec_feed* is LPCNET_HIP_E_ARG with nothing changed (the packed array would be ambiguous).
+ *   A shard with active_k == 0 launches nothing and the call returns 0.
+ * Per-stream maintenance calls work on ANY stream of the capacity, active or not -- that is how a joining stream is prepared: reset,
+ *   analysis_reset, plc_reset, get / set_*_state, get / set_*_vq_mem, export / import_state, plc_fec_add / plc_fec_clear, copy_streams.
+ * The sample kernel's form on a prefix: with active_k == count_k what the batch runs anyway (a measured value and the twelve-wave form
+ *   included).  With active_k < count_k a pinned streams-per-workgroup value holds; otherwise the launch takes the cost table's form for
+ *   active_k streams, as lpcnet_batch_group_form answers for a group; the twelve-wave form is never used and nothing is measured inside a call
+ *   (lpcnet_batch_tune keeps measuring the full capacity).  PARITY gives the same bits in every form.  FAST output is a function of the ACTIVE
+ *   count and the batch's switches: it equals what a batch of active_k streams with those switches gives.
+ * copy_streams: stream src[i] -> stream dst[i], i < m: EVERYTHING the batch keeps per stream that is allocated at the time of the call -- the
+ *   synthesis state, the decoder's and the encoder's VQ memory, the analysis state, the kept frame products and whether they exist, every
+ *   per-stream array of the PLC and its control state.  All dst distinct, no stream in both lists (a source may feed several destinations),
+ *   every index inside the capacity: else LPCNET_HIP_E_ARG and nothing has changed.  Pairs inside one shard: one upload of the pair list and ONE
+ *   launch per shard, only enqueued on hip_stream (NULL = the batch's own; on a sharded batch it must be NULL) under the ordering rules of
+ *   lpcnet_batch_analyze_device; LPCNET_HIP_E_ARG on a capturing stream.  The host halves (PLC control state, the products' flag) are copied
+ *   when the call is made, which is when the planners of the steps run too: call order is the order.  Pairs ACROSS shards go through pinned
+ *   host memory and synchronise both shards: an occasional operation, not one for every step.
+ * A stream leaves by copying the last active stream of its shard into its slot and lowering the count; a stream joins by reset (and
+ *   analysis_reset / plc_reset where used) of the slot at the count and raising it.  lpcnet_amd/roster.py (StreamRoster) keeps that book. */
+LPCNET_EXPORT int lpcnet_batch_set_active(LPCNetBatch *b, const int *active, int n_shards);
+LPCNET_EXPORT int lpcnet_batch_get_active(const LPCNetBatch *b, int *active, int cap);
+LPCNET_EXPORT int lpcnet_batch_active_streams(const LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_copy_streams(LPCNetBatch *b, const int *src, const int *dst, int m, void *hip_stream);
+/* the decoder's per-stream VQ memory (float[18]; zero after lpcnet_batch_reset): with it a per-stream snapshot covers every state of a stream */
+LPCNET_EXPORT int lpcnet_batch_get_decoder_vq_mem(LPCNetBatch *b, int stream, float *out18);
+LPCNET_EXPORT int lpcnet_batch_set_decoder_vq_mem(LPCNetBatch *b, int stream, const float *in18);
 /* raw per-stream state record (layout = struct lpcn_stream_state in lpcnet_amd/csrc/lpcnet_engine.h) */
 LPCNET_EXPORT int lpcnet_batch_state_size(void);
 LPCNET_EXPORT int lpcnet_batch_get_raw_state(LPCNetBatch *b, int stream, void *out);

@@ -204,6 +204,12 @@ def load_library():
     L.lpcnet_batch_encoder_enable.argtypes = [vp, C.c_int]
     L.lpcnet_batch_get_encoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
     L.lpcnet_batch_set_encoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_get_decoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_set_decoder_vq_mem.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_set_active.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+    L.lpcnet_batch_get_active.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+    L.lpcnet_batch_active_streams.argtypes = [vp]
+    L.lpcnet_batch_copy_streams.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_export_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_import_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_streams_per_workgroup.argtypes = [vp, C.c_int]
@@ -695,6 +701,48 @@ class LPCNetBatch:
         mem = np.ascontiguousarray(mem, np.float32)
         assert mem.shape == (18,)
         self._chk(self.L.lpcnet_batch_set_encoder_vq_mem(self.p, stream, mem), "set_encoder_vq_mem")
+
+    def get_decoder_vq_mem(self, stream: int) -> np.ndarray:
+        out = np.zeros(18, np.float32)
+        self._chk(self.L.lpcnet_batch_get_decoder_vq_mem(self.p, stream, out), "get_decoder_vq_mem")
+        return out
+
+    def set_decoder_vq_mem(self, stream: int, mem: np.ndarray):
+        mem = np.ascontiguousarray(mem, np.float32)
+        assert mem.shape == (18,)
+        self._chk(self.L.lpcnet_batch_set_decoder_vq_mem(self.p, stream, mem), "set_decoder_vq_mem")
+
+    # ---- streams that come and go (include/lpcnet_batch.h: lpcnet_batch_set_active, lpcnet_batch_copy_streams; lpcnet_amd/roster.py keeps the book) ----
+    @property
+    def active(self):
+        """the active prefix: an int for an unsharded batch, a list with one count per shard otherwise.  Calls that advance streams work on the
+        first `active` streams of every shard; array shapes stay (n, ...) and the other rows are neither read nor written"""
+        k = self.L.lpcnet_batch_shards(self.p)
+        arr = (C.c_int * k)()
+        rc = self.L.lpcnet_batch_get_active(self.p, arr, k)
+        if rc < 0:
+            self._chk(rc, "get_active")
+        return arr[0] if k == 1 else list(arr)
+
+    @active.setter
+    def active(self, counts):
+        counts = [int(counts)] if np.isscalar(counts) else [int(c) for c in counts]
+        arr = (C.c_int * len(counts))(*counts)
+        self._chk(self.L.lpcnet_batch_set_active(self.p, arr, len(counts)), "set_active")
+
+    @property
+    def active_streams(self) -> int:
+        rc = self.L.lpcnet_batch_active_streams(self.p)
+        if rc < 0:
+            self._chk(rc, "active_streams")
+        return rc
+
+    def copy_streams(self, src, dst, hip_stream: int = 0):
+        """stream src[i] -> stream dst[i]: everything the batch keeps per stream, on the device (one launch per shard, only enqueued; pairs across
+        shards go through the host and synchronise).  All dst distinct, no stream in both lists"""
+        src, dst = np.ascontiguousarray(src, np.int32).reshape(-1), np.ascontiguousarray(dst, np.int32).reshape(-1)
+        assert src.size == dst.size
+        self._chk(self.L.lpcnet_batch_copy_streams(self.p, src.ctypes.data, dst.ctypes.data, int(src.size), hip_stream or None), "copy_streams")
 
     def set_lpc_gamma(self, gamma: float):
         self._chk(self.L.lpcnet_batch_set_lpc_gamma(self.p, gamma), "set_lpc_gamma")

@@ -1,6 +1,7 @@
 /* C host shell of the LPCNet HIP engine, batch half: every entry point of include/lpcnet_batch.h that takes an LPCNetBatch, on top of the
  * device runtime declared in lpcnet_engine.h.  Which streams a shard owns and how one call fans out over the shards is api_shards.h. */
 #include "api_internal.h"
+#include "api_roster.h"
 
 LPCNetBatch *lpcnet_batch_create_sharded(int n_streams, const int *devices, int n_devices)
 {
@@ -290,8 +291,11 @@ int lpcnet_batch_plc_fec_feed(LPCNetBatch *b, const float *features, const int *
     long long total = 0;
     for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard's rings change) */
         vec0[k] = (int)total;
+        const int active = lpcn_batch_dev_active(b->sh[k].dev);
         for (int i = b->at[k].first; i < b->at[k].first + b->at[k].count; i++) {
-            if (count[i] < 0 || (skip && skip[i] < 0)) { set_err("lpcnet_batch_plc_fec_feed: negative count"); return LPCN_E_ARG; }
+            const int inactive = i >= b->at[k].first + active;      /* (its skip and clear are ignored; vectors for it would make the packed array ambiguous) */
+            if (inactive && count[i] != 0) { set_err("lpcnet_batch_plc_fec_feed: a stream beyond its shard's active prefix has a count"); return LPCN_E_ARG; }
+            if (count[i] < 0 || (!inactive && skip && skip[i] < 0)) { set_err("lpcnet_batch_plc_fec_feed: negative count"); return LPCN_E_ARG; }
             if ((total += count[i]) > 0x7fffffff) { set_err("lpcnet_batch_plc_fec_feed: more than 2^31 - 1 vectors"); return LPCN_E_ARG; }
         }
     }
@@ -462,6 +466,75 @@ int lpcnet_batch_set_encoder_vq_mem(LPCNetBatch *b, int stream, const float *in1
     if (!in18) { set_err("lpcnet_batch_set_encoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
     SHARD_OF(s, i, b, stream);
     FWD(lpcn_batch_dev_set_encoder_vq_mem(s->dev, i, in18));
+}
+
+int lpcnet_batch_get_decoder_vq_mem(LPCNetBatch *b, int stream, float *out18)
+{
+    NEED_MODEL(b);
+    if (!out18) { set_err("lpcnet_batch_get_decoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_get_decoder_vq_mem(s->dev, i, out18));
+}
+int lpcnet_batch_set_decoder_vq_mem(LPCNetBatch *b, int stream, const float *in18)
+{
+    NEED_MODEL(b);
+    if (!in18) { set_err("lpcnet_batch_set_decoder_vq_mem: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_set_decoder_vq_mem(s->dev, i, in18));
+}
+
+/* ---- streams that come and go (include/lpcnet_batch.h): the active prefix of every shard and the device-side stream copies; which pair lists
+ * are valid and how they split over the shards is api_roster.h ---- */
+int lpcnet_batch_set_active(LPCNetBatch *b, const int *active, int n_shards)
+{
+    NEED_MODEL(b);
+    if (!active || n_shards != b->n_shards) { set_err("lpcnet_batch_set_active: one count per shard (lpcnet_batch_shards)"); return LPCN_E_ARG; }
+    for (int k = 0; k < n_shards; k++)       /* (checked for every shard before any shard changes) */
+        if (active[k] < 0 || active[k] > b->at[k].count) { set_err("lpcnet_batch_set_active: a count outside 0 .. the shard's streams"); return LPCN_E_ARG; }
+    for (int k = 0; k < n_shards; k++) { const int rc = lpcn_batch_dev_set_active(b->sh[k].dev, active[k]); if (rc) { take_engine_err(); return rc; } }
+    return 0;
+}
+int lpcnet_batch_get_active(const LPCNetBatch *b, int *active, int cap)
+{
+    NEED_MODEL(b);
+    for (int k = 0; active && k < b->n_shards && k < cap; k++) active[k] = lpcn_batch_dev_active(b->sh[k].dev);
+    return b->n_shards;
+}
+int lpcnet_batch_active_streams(const LPCNetBatch *b)
+{
+    NEED_MODEL(b);
+    int sum = 0;
+    for (int k = 0; k < b->n_shards; k++) sum += lpcn_batch_dev_active(b->sh[k].dev);
+    return sum;
+}
+int lpcnet_batch_copy_streams(LPCNetBatch *b, const int *src, const int *dst, int m, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (m < 0 || (m && (!src || !dst))) { set_err("lpcnet_batch_copy_streams: bad arguments"); return LPCN_E_ARG; }
+    if (hip_stream && b->n_shards != 1) { set_err("lpcnet_batch_copy_streams: a sharded batch copies on its shards' own streams (hip_stream must be NULL)"); return LPCN_E_ARG; }
+    if (!m) return 0;
+    /* scratch: the marks of the check, then the split's four lists */
+    unsigned char *mark = (unsigned char *)malloc((size_t)b->n + 4 * (size_t)m * sizeof(int) + sizeof(int));
+    if (!mark) { set_err("lpcnet_batch_copy_streams: out of memory"); return LPCN_E_ARG; }
+    int rc = roster_check(b->at, b->n_shards, src, dst, m, mark);
+    if (rc) {
+        set_err("lpcnet_batch_copy_streams: every index must lie inside the batch, all destinations be distinct and no stream be both a source and a destination");
+        free(mark);
+        return LPCN_E_ARG;
+    }
+    int *lsrc = (int *)(mark + ((size_t)b->n + sizeof(int) - 1) / sizeof(int) * sizeof(int)), *ldst = lsrc + m, *xsrc = ldst + m, *xdst = xsrc + m;
+    int first[LPCN_MAX_SHARDS + 1];
+    const int nx = roster_split(b->at, b->n_shards, src, dst, m, first, lsrc, ldst, xsrc, xdst);
+    for (int k = 0; k < b->n_shards && !rc; k++)         /* one upload and one launch per shard, only enqueued */
+        if (first[k + 1] > first[k]) rc = lpcn_batch_dev_copy_streams(b->sh[k].dev, lsrc + first[k], ldst + first[k], first[k + 1] - first[k], hip_stream);
+    for (int i = 0; i < nx && !rc; i++) {                /* across shards: through the host, both shards synchronised */
+        int ls = 0, ld = 0;
+        const int ks = shard_of(b->at, b->n_shards, xsrc[i], &ls), kd = shard_of(b->at, b->n_shards, xdst[i], &ld);
+        rc = lpcn_batch_dev_copy_stream_across(b->sh[ks].dev, ls, b->sh[kd].dev, ld);
+    }
+    if (rc) take_engine_err();
+    free(mark);
+    return rc;
 }
 
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }

@@ -481,7 +481,7 @@ extern "C" int lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n
     if (!e || n <= 0 || max_chunk <= 0) { snprintf(g_err, sizeof(g_err), "bad batch arguments"); return LPCN_E_ARG; }
     DeviceGuard guard(e->device);
     lpcn_batch_dev *b = new lpcn_batch_dev();
-    b->e = e; b->n = n; b->max_chunk = max_chunk;
+    b->e = e; b->n = n; b->active = n; b->max_chunk = max_chunk;
     const char *off = getenv("LPCNET_HIP_NO_X2"), *force = getenv("LPCNET_HIP_PACK2");      // (read once per batch, never on the launch path)
     b->no_x2 = off && *off == '1'; b->pack2_force = (force && *force) ? *force == '1' : -1;
     const char *tw = getenv("LPCNET_HIP_X3");                // tools (profiles of one form under LPCNET_HIP_NO_AUTOTUNE): 1 = the twelve-wave form wherever the model has the image, 0 = never
@@ -531,7 +531,9 @@ static void host_reset_state(lpcn_stream_state *st)
 }
 
 // lpcn_batch_dev_step_host's per-stream frame products are stale after anything else has advanced or rewritten a stream
-void forget_keep(lpcn_batch_dev *b) { b->keep_ok.assign(b->keep_ok.size(), 0); }
+// (an inactive stream keeps its products and their flag: nothing advanced it)
+void forget_keep(lpcn_batch_dev *b) { for (size_t s = 0; s < b->keep_ok.size() && s < (size_t)b->active; ++s) b->keep_ok[s] = 0; }
+void forget_keep_all(lpcn_batch_dev *b) { b->keep_ok.assign(b->keep_ok.size(), 0); }
 int check_range(const lpcn_batch_dev *b, int first, int count, const char *what)
 {
     if (first < 0 || count < 0 || first + count > b->n) { snprintf(g_err, sizeof(g_err), "%s range", what); return LPCN_E_ARG; }
@@ -540,7 +542,7 @@ int check_range(const lpcn_batch_dev *b, int first, int count, const char *what)
 
 extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
 {
-    forget_keep(b);
+    forget_keep_all(b);
     if (check_range(b, first, count, "reset")) return LPCN_E_ARG;
     DeviceGuard guard(b->e->device);
     std::vector<lpcn_stream_state> h(count);
@@ -554,7 +556,7 @@ extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
 extern "C" int lpcn_batch_dev_get_state(lpcn_batch_dev *b, int s, lpcn_stream_state *host) { return stream_rec(b, s, b->d_state, 1, host, nullptr); }
 extern "C" int lpcn_batch_dev_set_state(lpcn_batch_dev *b, int s, const lpcn_stream_state *host)
 {
-    forget_keep(b);
+    forget_keep_all(b);
     return stream_rec(b, s, b->d_state, 1, nullptr, host);
 }
 // the engine's arithmetic flavour changed: re-run the cost model unless the caller pinned the value
@@ -641,6 +643,15 @@ extern "C" int lpcn_batch_dev_last_timing(lpcn_batch_dev *b, float *ms_sample, f
     if (ms_frame) *ms_frame = b->ms_frame;
     return 0;
 }
+// The active prefix: host-only, no wait, no device work.  Calls enqueued before keep the count they were enqueued with (every launch takes its
+// size as a value when it is enqueued); what follows works on streams [0, active).
+extern "C" int lpcn_batch_dev_set_active(lpcn_batch_dev *b, int active)
+{
+    if (active < 0 || active > b->n) { snprintf(g_err, sizeof(g_err), "active streams: 0 .. %d", b->n); return LPCN_E_ARG; }
+    b->active = active;
+    return 0;
+}
+extern "C" int lpcn_batch_dev_active(const lpcn_batch_dev *b) { return b->active; }
 extern "C" int lpcn_batch_dev_sync(lpcn_batch_dev *b)
 {
     DeviceGuard guard(b->e->device);

@@ -36,6 +36,7 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
                                       void *hip_stream)
 {
     if (!d_pcm || !d_features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     if (!b->d_an_state || analysis_chunk_for(b, n_frames) > b->an_chunk) {
@@ -52,7 +53,7 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
     for (int f0 = 0; f0 < n_frames; f0 += b->an_chunk) {
         const int nf = n_frames - f0 < b->an_chunk ? n_frames - f0 : b->an_chunk;
         const void *p = is_float ? (const void *)((const float *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE) : (const void *)((const short *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE);
-        int rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, nf, p, is_float, pcm_stride, b->d_an_state, d_features + (size_t)f0 * feat_stride,
+        int rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->active, nf, p, is_float, pcm_stride, b->d_an_state, d_features + (size_t)f0 * feat_stride,
                                               feat_stride, feat_stream_stride, b->d_an_resid, b->d_an_xc, b->d_an_fw, g_err, sizeof(g_err));
         if (rc) return rc;
     }
@@ -62,9 +63,10 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
 extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, int pcm_is_float, float *features, int feat_stride, int n_frames)
 {
     if (!pcm || !features || n_frames < 1 || feat_stride < LPCN_AN_NB_FEATURES) { snprintf(g_err, sizeof(g_err), "bad analysis arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));
-    const size_t nfeat = (size_t)b->n * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
+    const size_t npcm = (size_t)b->active * n_frames * LPCN_FRAME_SIZE * (pcm_is_float ? sizeof(float) : sizeof(short));      // (the active streams' rows lead the arrays)
+    const size_t nfeat = (size_t)b->active * n_frames * LPCN_AN_NB_FEATURES;      // (staged densely; the caller's stride is applied by the copy out)
     int rc = b->d_an_pcm.reserve(b, npcm);
     if (!rc) rc = b->d_an_feat.reserve(b, nfeat);
     if (rc) return rc;
@@ -75,7 +77,7 @@ extern "C" int lpcn_batch_dev_analyze_host(lpcn_batch_dev *b, const void *pcm, i
     rc = lpcn_batch_dev_analyze(b, b->d_an_pcm.p, pcm_is_float, b->d_an_feat, LPCN_AN_NB_FEATURES, n_frames, st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(features, (size_t)feat_stride * sizeof(float), b->d_an_feat, LPCN_AN_NB_FEATURES * sizeof(float),
-                             LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->n * n_frames, hipMemcpyDeviceToHost, st));
+                             LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->active * n_frames, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -134,6 +136,7 @@ static int encode_impl(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_p
         return LPCN_E_ARG;
     }
     if (d_packets && !b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     const int want = encode_chunk_for(b, n_packets);
@@ -153,11 +156,11 @@ static int encode_impl(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_p
         const short *p = d_pcm + (size_t)p0 * 4 * LPCN_FRAME_SIZE;
         int rc;
         if (d_packets)
-            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->n, np, p, pcm_stride, b->d_an_state, b->d_enc_feat, LPCN_AN_NB_FEATURES,
+            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->active, np, p, pcm_stride, b->d_an_state, b->d_enc_feat, LPCN_AN_NB_FEATURES,
                                             (size_t)np * 4 * LPCN_AN_NB_FEATURES, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_enc_vq_mem, b->d_enc_qf3, b->d_enc_pk,
                                             d_packets + (size_t)p0 * 8, n_packets, g_err, sizeof(g_err));
         else
-            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->n, np, p, pcm_stride, b->d_an_state, d_features + (size_t)p0 * 4 * feat_stride, feat_stride,
+            rc = lpcn_launch_encode_kernels(b->e->fmodel, b->e->enc, st, b->active, np, p, pcm_stride, b->d_an_state, d_features + (size_t)p0 * 4 * feat_stride, feat_stride,
                                             (size_t)n_packets * 4 * feat_stride, b->d_an_resid, b->d_an_xc, b->d_an_fw, b->d_enc_vq_mem, b->d_enc_qf3, b->d_enc_pk,
                                             nullptr, n_packets, g_err, sizeof(g_err));
         if (rc) return rc;
@@ -183,9 +186,10 @@ extern "C" int lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, u
         return LPCN_E_ARG;
     }
     if (packets && !b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE * sizeof(short);
-    const size_t nfeat = packets ? 0 : (size_t)b->n * n_packets * 4 * LPCN_AN_NB_FEATURES, nbytes = packets ? (size_t)b->n * n_packets * 8 : 0;
+    const size_t npcm = (size_t)b->active * n_packets * 4 * LPCN_FRAME_SIZE * sizeof(short);
+    const size_t nfeat = packets ? 0 : (size_t)b->active * n_packets * 4 * LPCN_AN_NB_FEATURES, nbytes = packets ? (size_t)b->active * n_packets * 8 : 0;
     int rc = b->d_an_pcm.reserve(b, npcm);
     if (!rc) rc = b->d_an_feat.reserve(b, nfeat);
     if (!rc) rc = b->d_packets.reserve(b, nbytes);
@@ -200,7 +204,7 @@ extern "C" int lpcn_batch_dev_encode_host(lpcn_batch_dev *b, const short *pcm, u
         HIP_TRY(hipMemcpyAsync(packets, b->d_packets, nbytes, hipMemcpyDeviceToHost, st));
     else
         HIP_TRY(hipMemcpy2DAsync(features, (size_t)feat_stride * sizeof(float), b->d_an_feat, LPCN_AN_NB_FEATURES * sizeof(float),
-                                 LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->n * n_packets * 4, hipMemcpyDeviceToHost, st));
+                                 LPCN_AN_NB_FEATURES * sizeof(float), (size_t)b->active * n_packets * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -169,6 +169,8 @@ struct lpcn_plc_host {
 struct lpcn_batch_dev {
     lpcn_engine *e = nullptr;
     int n = 0, max_chunk = 0, S = 0, frame_len = LPCN_FRAME_SIZE;
+    int active = 0;                    // the active prefix (lpcn_batch_dev_set_active; default n): every call that advances streams works on streams [0, active).
+                                       //   Launch sizes and copy lengths take it; allocation sizes and range checks keep n
     bool S_auto = true;                // streams per workgroup are chosen by the engine (measured on this batch, see autotune_streams_per_wg)
     bool tuned = false;                // ... and have been measured for the current arithmetic flavour
     bool pack2 = false;                // 128-VGPR variant: two workgroups per CU (int8, <= 32 items per lane, more workgroups than CUs)
@@ -217,6 +219,10 @@ struct lpcn_batch_dev {
     Event ev_last;
     hipStream_t last_stream = nullptr;
     bool pending = false;
+    DevBuf<int> d_pairs;               // lpcn_batch_dev_copy_streams (engine_roster.hip): the (src, dst) list of a call, [2 n] ...
+    PinBuf h_pairs;                    //   ... its pinned source ...
+    Event ev_pairs;                    //   ... and "the previous call's list has left it"
+    bool pairs_pending = false;
     std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
     PinBuf h_pin;                      // pinned host staging of the single-stream fast path and the combined pass: each reserves what it lays out
     bool timing = false;
@@ -261,7 +267,8 @@ inline bool x3_available(const lpcn_batch_dev *b) { return x2_available(b) && !b
 bool stream_is_capturing(hipStream_t st);
 int order_begin(lpcn_batch_dev *b, hipStream_t st);
 int order_end(lpcn_batch_dev *b, hipStream_t st);
-void forget_keep(lpcn_batch_dev *b);
+void forget_keep(lpcn_batch_dev *b);           // the ACTIVE streams' kept frame products are stale (a call advanced them) ...
+void forget_keep_all(lpcn_batch_dev *b);       // ... every stream's (a maintenance call rewrote states)
 int check_range(const lpcn_batch_dev *b, int first, int count, const char *what);
 int device_cus(const lpcn_engine *e);
 bool use_pack2(const lpcn_batch_dev *b, int n, int S);
@@ -274,6 +281,8 @@ int launch_frames(lpcn_batch_dev *b, const LaunchShape &sh, hipStream_t st, cons
 int lpcn_launch_frame_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const float *d_feat,
                               int feat_stride, size_t feat_stream_stride, lpcn_stream_state *d_state, int *d_fc_base,
                               float *d_cond, float *d_cond_a, float *d_cond_b, float *d_lpc, char *err, size_t errlen);
+// engine_plc.hip: the buffers of the compacted groups, with every stream's kept frame products
+int group_alloc(lpcn_batch_dev *b);
 // engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)
 int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
                                  size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride,

@@ -8,7 +8,7 @@
 // the launch runs on those in the batch's form -- or, under the group schedule, the cost table's form for the group's size (group_shape) -- and
 // the results are scattered back by the same map: the hot kernels stay untouched.  A group runs the sample kernel far below its throughput.
 // the buffers every group uses: the compacted states, features and PCM, and every stream's most recent frame products (zero until a stream has some)
-static int group_alloc(lpcn_batch_dev *b)
+int group_alloc(lpcn_batch_dev *b)
 {
     if (b->d_keep_lpc) return 0;      // (the last one allocated)
     const size_t n = (size_t)b->n;
@@ -162,7 +162,8 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
                                         const int *n_samples, const int *preload, const int *mode)
 {
     if (!features || !pcm || !n_samples || !preload || !mode || feat_stride < LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "bad step arguments"); return LPCN_E_ARG; }
-    for (int s = 0; s < b->n; ++s) {
+    const int na = b->active;          // (the arguments of the streams beyond the active prefix are not looked at: those streams are left alone, like mode 0)
+    for (int s = 0; s < na; ++s) {
         if (mode[s] < 0 || mode[s] > 2) { snprintf(g_err, sizeof(g_err), "stream %d: mode must be 0, 1 or 2", s); return LPCN_E_ARG; }
         if (mode[s] && (n_samples[s] < 1 || n_samples[s] > LPCN_FRAME_SIZE || preload[s] < 0 || preload[s] > n_samples[s])) {
             snprintf(g_err, sizeof(g_err), "stream %d: n_samples must be 1..160 and preload 0..n_samples", s); return LPCN_E_ARG;
@@ -172,13 +173,14 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
     // whatever the last run_frame_network left in the state, but this engine keeps frame products per stream only for
     // steps that went through this call -- a stream advanced by the ordinary synthesize / decode calls has none
     if (b->keep_ok.size() != (size_t)b->n) b->keep_ok.assign((size_t)b->n, 0);
-    for (int s = 0; s < b->n; ++s)
+    for (int s = 0; s < na; ++s)
         if (mode[s] == 2 && !b->keep_ok[s]) {
             snprintf(g_err, sizeof(g_err), "stream %d: a tail-only step (mode 2) needs a preceding frame step (mode 1) of lpcnet_batch_synthesize_step", s);
             return LPCN_E_ARG;
         }
+    if (!na) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t nfeat = (size_t)(b->n - 1) * feat_stride + LPCN_NB_FEAT, npcm = (size_t)b->n * LPCN_FRAME_SIZE;
+    const size_t nfeat = (size_t)(na - 1) * feat_stride + LPCN_NB_FEAT, npcm = (size_t)na * LPCN_FRAME_SIZE;
     int rc = ensure_staging(b, nfeat, npcm);
     if (!rc) rc = group_alloc(b);
     if (rc) return rc;
@@ -188,11 +190,11 @@ extern "C" int lpcn_batch_dev_step_host(lpcn_batch_dev *b, const float *features
     struct Group { int off, cnt, mode, N, preload; };      // (off: the group's place in `map`, which holds every group's streams)
     std::vector<Group> groups;
     std::vector<int> map;
-    std::vector<char> done((size_t)b->n, 0);
-    for (int s0 = 0; s0 < b->n; ++s0) {
+    std::vector<char> done((size_t)na, 0);
+    for (int s0 = 0; s0 < na; ++s0) {
         if (done[s0] || mode[s0] == 0) continue;
         const int off = (int)map.size();
-        for (int s = s0; s < b->n; ++s)
+        for (int s = s0; s < na; ++s)
             if (!done[s] && mode[s] == mode[s0] && n_samples[s] == n_samples[s0] && preload[s] == preload[s0]) { map.push_back(s); done[s] = 1; }
         groups.push_back({off, (int)map.size() - off, mode[s0], n_samples[s0], preload[s0]});
     }
@@ -327,9 +329,11 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
     if (stream_is_capturing(st)) {
         snprintf(g_err, sizeof(g_err), "a PLC step cannot be captured: its launch sequence depends on the loss flags"); return LPCN_E_ARG;
     }
+    if (!b->active) return 0;
     { int rco = order_begin(b, st); if (rco) return rco; }
     if (p->ctl_pending) { HIP_TRY(hipEventSynchronize(p->ev_ctl)); p->ctl_pending = false; }      // (the previous step's lists have left the pinned buffer: long done)
-    int rc = plc_plan(p->options, b->n, p->ctl.data(), lost, p->plan, nullptr, g_err, sizeof(g_err), b->sched_lanes);
+    // (the planner and its lists run over the active prefix: the control state of the other streams does not move)
+    int rc = plc_plan(p->options, b->active, p->ctl.data(), lost, p->plan, nullptr, g_err, sizeof(g_err), b->sched_lanes);
     if (rc) return rc;
     const PlcPlan &P = p->plan;
     if (P.ctl.size() > p->d_ctl.cap) { snprintf(g_err, sizeof(g_err), "PLC step: control lists exceed their buffer"); return LPCN_E_HIP; }
@@ -363,7 +367,7 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             if ((rc = run_group(b, st, plc_group(p, L, d_pcm)))) { (void)lanes_join(b, ln); return rc; }
             break;
         case PLC_T_ANALYSIS:
-            if ((rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->n, 1, d_pcm, 0, (size_t)LPCN_FRAME_SIZE, b->d_an_state, p->D.an, LPCN_AN_NB_FEATURES,
+            if ((rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->active, 1, d_pcm, 0, (size_t)LPCN_FRAME_SIZE, b->d_an_state, p->D.an, LPCN_AN_NB_FEATURES,
                                                    (size_t)LPCN_AN_NB_FEATURES, b->d_an_resid, b->d_an_xc, b->d_an_fw, g_err, sizeof(g_err)))) return rc;
             break;
         }
@@ -383,7 +387,8 @@ extern "C" int lpcn_batch_dev_plc_step_host(lpcn_batch_dev *b, short *pcm, const
     int rc = order_begin(b, st);
     if (rc) return rc;
     if ((rc = tune_if_due(b, st))) return rc;
-    const size_t bytes = sizeof(short) * (size_t)b->n * LPCN_FRAME_SIZE;
+    if (!b->active) return 0;
+    const size_t bytes = sizeof(short) * (size_t)b->active * LPCN_FRAME_SIZE;
     HIP_TRY(hipMemcpyAsync(p->d_pcm, pcm, bytes, hipMemcpyHostToDevice, st));
     if ((rc = lpcn_batch_dev_plc_step(b, p->d_pcm, lost, st))) return rc;
     HIP_TRY(hipMemcpyAsync(pcm, p->d_pcm, bytes, hipMemcpyDeviceToHost, st));
@@ -437,6 +442,11 @@ extern "C" int lpcn_batch_dev_plc_fec_feed(lpcn_batch_dev *b, const float *d_fea
     bool vectors = false;
     for (int s = 0; count && s < b->n; ++s) vectors |= count[s] > 0;
     if (!count || (vectors && !d_features)) { snprintf(g_err, sizeof(g_err), "bad FEC feed arguments"); return LPCN_E_ARG; }
+    // (a stream beyond the active prefix takes no vectors -- rows of the packed array for it would make every later stream's rows ambiguous -- and its
+    // skip and clear are ignored: its ring does not move)
+    for (int s = b->active; s < b->n; ++s) if (count[s] != 0) { snprintf(g_err, sizeof(g_err), "FEC feed: stream %d is not active and has a count", s); return LPCN_E_ARG; }
+    for (int s = b->active; dropped && s < b->n; ++s) dropped[s] = 0;
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     lpcn_plc_host *p = b->plc.get();
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
@@ -445,7 +455,7 @@ extern "C" int lpcn_batch_dev_plc_fec_feed(lpcn_batch_dev *b, const float *d_fea
     }
     if (p->feed_pending) { HIP_TRY(hipEventSynchronize(p->ev_feed)); p->feed_pending = false; }      // (the previous feed's records have left the pinned buffer)
     int *h_rec = (int *)p->h_ctl.p + p->d_ctl.cap, any = 0;
-    const int n_rec = plc_fec_feed_plan(b->n, p->ctl.data(), count, skip, clear, h_rec, dropped, &any, g_err, sizeof(g_err));
+    const int n_rec = plc_fec_feed_plan(b->active, p->ctl.data(), count, skip, clear, h_rec, dropped, &any, g_err, sizeof(g_err));
     if (n_rec < 0) return n_rec;
     if (any) snprintf(g_err, sizeof(g_err), "FEC buffer full");      // (the reference prints this and drops the vector)
     if (n_rec == 0) return any;
@@ -466,6 +476,7 @@ extern "C" int lpcn_batch_dev_plc_fec_feed_host(lpcn_batch_dev *b, const float *
     size_t total = 0;
     for (int s = 0; s < b->n; ++s) {
         if (count[s] < 0) { snprintf(g_err, sizeof(g_err), "FEC feed: stream %d has a negative count", s); return LPCN_E_ARG; }
+        if (count[s] && s >= b->active) { snprintf(g_err, sizeof(g_err), "FEC feed: stream %d is not active and has a count", s); return LPCN_E_ARG; }
         total += (size_t)count[s];
     }
     if (total && !features) { snprintf(g_err, sizeof(g_err), "bad FEC feed arguments"); return LPCN_E_ARG; }
@@ -531,7 +542,9 @@ extern "C" int lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, f
 {
     NEED_PLC(b);
     if (!x || !ceps36) { snprintf(g_err, sizeof(g_err), "bad arguments"); return LPCN_E_ARG; }
-    const size_t count = (size_t)b->n * LPCN_FRAME_SIZE;
+    const int na = b->active;
+    if (!na) return 0;
+    const size_t count = (size_t)na * LPCN_FRAME_SIZE;
     std::vector<short> pc(count);
     for (size_t i = 0; i < count; ++i) {
         if (!(x[i] >= -32768.f && x[i] <= 32767.f) || x[i] != (float)(int)x[i]) { snprintf(g_err, sizeof(g_err), "plc_burg: samples must be integers of the int16 range"); return LPCN_E_ARG; }
@@ -542,10 +555,10 @@ extern "C" int lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, f
     lpcn_plc_host *p = b->plc.get();
     hipStream_t st = b->e->stream;
     HIP_TRY(hipMemcpy(p->d_pcm, pc.data(), sizeof(short) * count, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(b->n), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, (const int *)p->d_ident, b->n, p->d_pcm, p->D, 0);
+    hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(na), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, (const int *)p->d_ident, na, p->d_pcm, p->D, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(ceps36, p->burg, sizeof(float) * (size_t)b->n * 2 * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ceps36, p->burg, sizeof(float) * (size_t)na * 2 * LPCN_NB_BANDS, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -554,13 +567,15 @@ extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57
 {
     NEED_PLC(b);
     if (!in57 || !out20) { snprintf(g_err, sizeof(g_err), "bad arguments"); return LPCN_E_ARG; }
+    const int na = b->active;
+    if (!na) return 0;
     DeviceGuard guard(b->e->device);
     { int rcw = wait_all(b); if (rcw) return rcw; }
     lpcn_plc_host *p = b->plc.get();
     hipStream_t st = b->e->stream;
-    std::vector<int> recs((size_t)b->n * lpcn::PLC_PRED_REC, 0);
+    std::vector<int> recs((size_t)na * lpcn::PLC_PRED_REC, 0);
     if (recs.size() > p->d_ctl.cap) { snprintf(g_err, sizeof(g_err), "plc_pred: control buffer"); return LPCN_E_HIP; }
-    for (int s = 0; s < b->n; ++s) {
+    for (int s = 0; s < na; ++s) {
         const float *in = in57 + (size_t)s * LPCN_PLC_IN;
         int *r = &recs[(size_t)s * lpcn::PLC_PRED_REC];
         r[0] = s; r[1] = lpcn::PLC_F_COMPUTE | lpcn::PLC_F_RAW; r[3] = float_bits(in[LPCN_PLC_IN - 1]);
@@ -568,9 +583,9 @@ extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57
         HIP_TRY(hipMemcpy(p->an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(p->d_ctl, recs.data(), sizeof(int) * recs.size(), hipMemcpyHostToDevice));
-    launch_plc_pred(b, st, p->d_ctl, b->n, b->d_gfeat.p);
+    launch_plc_pred(b, st, p->d_ctl, na, b->d_gfeat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(out20, b->d_gfeat, sizeof(float) * (size_t)b->n * LPCN_NB_FEAT, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out20, b->d_gfeat, sizeof(float) * (size_t)na * LPCN_NB_FEAT, hipMemcpyDeviceToHost));
     return 0;
 }

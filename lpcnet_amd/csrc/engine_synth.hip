@@ -22,7 +22,15 @@ extern "C" int lpcn_launch_sample_x2f(int nw, int grid, int lds, hipStream_t st,
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
 extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout)
 
-static LaunchShape whole_batch(const lpcn_batch_dev *b) { return {b->n, b->frame_len, b->d_state, b->S, b->pack2, b->x3}; }
+// What a whole-batch call launches: every stream in the batch's form -- or, on an active prefix shorter than the batch, streams [0, active) in a
+// pinned form, else the cost table's form for that many streams (as a compacted group gets: a table look-up, never a measurement), never on twelve
+// waves.  PARITY gives the same bits in every form; FAST output is that of a batch of `active` streams with the same switches.
+static LaunchShape whole_batch(const lpcn_batch_dev *b)
+{
+    if (b->active == b->n) return {b->n, b->frame_len, b->d_state, b->S, b->pack2, b->x3};
+    const int S = b->S_auto ? auto_streams_per_wg(b, b->active) : b->S;
+    return {b->active, b->frame_len, b->d_state, S, use_pack2(b, b->active, S), false};
+}
 
 SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_frames)
 {
@@ -168,13 +176,15 @@ extern "C" int lpcn_batch_dev_tune(lpcn_batch_dev *b)
 // host-pointer entry points call it, on the engine's own stream, and BEFORE they make their launch shape, so that the measuring call itself
 // runs on the measured value; the enqueue-only device-pointer entry points never do, whichever stream they name (a NULL hip_stream
 // used to select the engine's own stream AND the measurement).
-int tune_if_due(lpcn_batch_dev *b, hipStream_t st) { return (b->S_auto && !b->tuned) ? autotune_streams_per_wg(b, st) : 0; }
+// (never on an active prefix shorter than the batch: nothing is measured inside such a call, lpcn_batch_dev_tune measures the full capacity)
+int tune_if_due(lpcn_batch_dev *b, hipStream_t st) { return (b->S_auto && !b->tuned && b->active == b->n) ? autotune_streams_per_wg(b, st) : 0; }
 
 static int run_impl(lpcn_batch_dev *b, const LaunchShape &sh, const float *d_features, int feat_stride, short *d_pcm, int n_frames, int preload, void *hip_stream)
 {
     if (n_frames <= 0 || feat_stride < LPCN_NB_FEAT || preload < 0 || preload > LPCN_FRAME_SIZE) {
         snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG;
     }
+    if (sh.n < 1) return 0;            // (no active stream: nothing to launch)
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     float tf = 0.f, ts = 0.f;
@@ -218,8 +228,9 @@ extern "C" int lpcn_batch_dev_run_host(lpcn_batch_dev *b, const float *features,
                                        short *pcm, int n_frames, int preload)
 {
     if (n_frames <= 0) { snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t nfeat = (size_t)b->n * n_frames * feat_stride, npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE;
+    const size_t nfeat = (size_t)b->active * n_frames * feat_stride, npcm = (size_t)b->active * n_frames * LPCN_FRAME_SIZE;      // (the active streams' rows lead the arrays)
     int rc = ensure_staging(b, nfeat, npcm);
     if (rc) return rc;
     hipStream_t st = b->e->stream;
@@ -350,6 +361,7 @@ static int decode_impl(lpcn_batch_dev *b, const unsigned char *d_packets, short 
     forget_keep(b);
     if (n_packets <= 0) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
     if (!b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
     const int T = 4 * n_packets;
@@ -358,7 +370,7 @@ static int decode_impl(lpcn_batch_dev *b, const unsigned char *d_packets, short 
         if (rc) return rc;
         if ((rc = order_begin(b, st))) return rc;
     }
-    hipLaunchKernelGGL(lpcn::decode_kernel, dim3((b->n + 1) / 2), dim3(64), 0, st, b->e->dec, d_packets, b->n, n_packets, b->d_vq_mem,
+    hipLaunchKernelGGL(lpcn::decode_kernel, dim3((b->active + 1) / 2), dim3(64), 0, st, b->e->dec, d_packets, b->active, n_packets, b->d_vq_mem,
                        b->d_feat, LPCN_NB_FEAT);
     HIP_TRY(hipGetLastError());
     if (may_tune) { int rct = tune_if_due(b, st); if (rct) return rct; }      // (decode_host only: the engine's own stream)
@@ -372,8 +384,9 @@ extern "C" int lpcn_batch_dev_decode(lpcn_batch_dev *b, const unsigned char *d_p
 extern "C" int lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char *packets, short *pcm, int n_packets)
 {
     if (n_packets <= 0) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t nbytes = (size_t)b->n * n_packets * 8, npcm = (size_t)b->n * n_packets * 4 * LPCN_FRAME_SIZE;
+    const size_t nbytes = (size_t)b->active * n_packets * 8, npcm = (size_t)b->active * n_packets * 4 * LPCN_FRAME_SIZE;
     int rc = b->d_packets.reserve(b, nbytes);
     if (rc) return rc;
     if ((rc = ensure_staging(b, 0, npcm))) return rc;
@@ -392,8 +405,9 @@ extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond
 {
     forget_keep(b);
     if (n_frames <= 0 || preload < 0 || preload > LPCN_FRAME_SIZE) { snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t npcm = (size_t)b->n * n_frames * LPCN_FRAME_SIZE;
+    const size_t npcm = (size_t)b->active * n_frames * LPCN_FRAME_SIZE;
     int rc = ensure_staging(b, 0, npcm);
     if (rc) return rc;
     hipStream_t st = b->e->stream;
@@ -404,11 +418,11 @@ extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond
         const int nf = n_frames - f0 < b->max_chunk ? n_frames - f0 : b->max_chunk;
         // gather the chunk [stream][f0..f0+nf) into the dense chunk buffers
         HIP_TRY(hipMemcpy2DAsync(b->d_cond_a, (size_t)nf * LPCN_ROWS_A * 4, cond_a + (size_t)f0 * LPCN_ROWS_A, (size_t)n_frames * LPCN_ROWS_A * 4,
-                                 (size_t)nf * LPCN_ROWS_A * 4, b->n, hipMemcpyHostToDevice, st));
+                                 (size_t)nf * LPCN_ROWS_A * 4, b->active, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpy2DAsync(b->d_cond_b, (size_t)nf * LPCN_ROWS_B * 4, cond_b + (size_t)f0 * LPCN_ROWS_B, (size_t)n_frames * LPCN_ROWS_B * 4,
-                                 (size_t)nf * LPCN_ROWS_B * 4, b->n, hipMemcpyHostToDevice, st));
+                                 (size_t)nf * LPCN_ROWS_B * 4, b->active, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpy2DAsync(b->d_lpc, (size_t)nf * LPCN_LPC_ORDER * 4, lpc + (size_t)f0 * LPCN_LPC_ORDER, (size_t)n_frames * LPCN_LPC_ORDER * 4,
-                                 (size_t)nf * LPCN_LPC_ORDER * 4, b->n, hipMemcpyHostToDevice, st));
+                                 (size_t)nf * LPCN_LPC_ORDER * 4, b->active, hipMemcpyHostToDevice, st));
         if (b->timing) HIP_TRY(hipEventRecord(b->ev[1], st));
         rc = launch_sample(b, whole_batch(b), st, b->d_pcm + (size_t)f0 * LPCN_FRAME_SIZE, (size_t)n_frames * LPCN_FRAME_SIZE, nf, preload, false);
         if (rc) return rc;
@@ -429,8 +443,9 @@ extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *fe
 {
     forget_keep(b);
     if (n_frames <= 0 || feat_stride < LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "bad run arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
-    const size_t nfeat = (size_t)b->n * n_frames * feat_stride;
+    const size_t nfeat = (size_t)b->active * n_frames * feat_stride;
     int rc = ensure_staging(b, nfeat, 0);
     if (rc) return rc;
     hipStream_t st = b->e->stream;
@@ -441,11 +456,11 @@ extern "C" int lpcn_batch_dev_run_frames_host(lpcn_batch_dev *b, const float *fe
         rc = launch_frames(b, whole_batch(b), st, b->d_feat + (size_t)f0 * feat_stride, feat_stride, (size_t)n_frames * feat_stride, nf);
         if (rc) return rc;
         if (cond_a) HIP_TRY(hipMemcpy2DAsync(cond_a + (size_t)f0 * LPCN_ROWS_A, (size_t)n_frames * LPCN_ROWS_A * 4, b->d_cond_a, (size_t)nf * LPCN_ROWS_A * 4,
-                                             (size_t)nf * LPCN_ROWS_A * 4, b->n, hipMemcpyDeviceToHost, st));
+                                             (size_t)nf * LPCN_ROWS_A * 4, b->active, hipMemcpyDeviceToHost, st));
         if (cond_b) HIP_TRY(hipMemcpy2DAsync(cond_b + (size_t)f0 * LPCN_ROWS_B, (size_t)n_frames * LPCN_ROWS_B * 4, b->d_cond_b, (size_t)nf * LPCN_ROWS_B * 4,
-                                             (size_t)nf * LPCN_ROWS_B * 4, b->n, hipMemcpyDeviceToHost, st));
+                                             (size_t)nf * LPCN_ROWS_B * 4, b->active, hipMemcpyDeviceToHost, st));
         if (lpc) HIP_TRY(hipMemcpy2DAsync(lpc + (size_t)f0 * LPCN_LPC_ORDER, (size_t)n_frames * LPCN_LPC_ORDER * 4, b->d_lpc, (size_t)nf * LPCN_LPC_ORDER * 4,
-                                          (size_t)nf * LPCN_LPC_ORDER * 4, b->n, hipMemcpyDeviceToHost, st));
+                                          (size_t)nf * LPCN_LPC_ORDER * 4, b->active, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;

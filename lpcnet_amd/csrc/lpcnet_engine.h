@@ -227,6 +227,18 @@ typedef struct lpcn_batch_dev lpcn_batch_dev;
 int  lpcn_batch_dev_create(lpcn_batch_dev **out, lpcn_engine *e, int n_streams, int max_chunk_frames);
 void lpcn_batch_dev_destroy(lpcn_batch_dev *b);
 int  lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count);           /* lpcnet_reset   */
+/* The active prefix (include/lpcnet_batch.h: lpcnet_batch_set_active): every call that advances streams works on streams [0, active) of the batch;
+ * the arrays keep their [n_streams][...] layout and the rows of the other streams are neither read nor written.  Host-only, no wait. */
+int  lpcn_batch_dev_set_active(lpcn_batch_dev *b, int active);                /* 0 .. n_streams (the default) */
+int  lpcn_batch_dev_active(const lpcn_batch_dev *b);
+/* Stream src[i] -> stream dst[i], i < m, on the device: everything the batch keeps per stream that is allocated now (engine_roster.hip).  One upload
+ * of the pair list and one launch, enqueued on hip_stream (NULL = the engine's own; not a capturing one); the host halves (the PLC's control state,
+ * the kept products' flag) are copied now.  The lists must be valid (api_roster.h: roster_check): this function checks the range only. */
+int  lpcn_batch_dev_copy_streams(lpcn_batch_dev *b, const int *src, const int *dst, int m, void *hip_stream);
+/* ... and across batches, through the host: synchronises both (an occasional operation) */
+int  lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int src, lpcn_batch_dev *to, int dst);
+int  lpcn_batch_dev_get_decoder_vq_mem(lpcn_batch_dev *b, int stream, float *out18);
+int  lpcn_batch_dev_set_decoder_vq_mem(lpcn_batch_dev *b, int stream, const float *in18);
 int  lpcn_batch_dev_get_state(lpcn_batch_dev *b, int stream, lpcn_stream_state *host);
 /* k independent streams with their callers' POD states in ONE pass and one synchronisation (engine_synth.hip): frame network + samples,
  * samples from the callers' frame products, or the frame network alone */
