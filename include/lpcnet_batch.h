@@ -247,6 +247,52 @@ LPCNET_EXPORT int lpcnet_hip_plc_fec_feed_plan(int n, int *ctl, const int *count
  * `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
 LPCNET_EXPORT int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info);
 
+/* The DRED decoder on the device, bit-identical to the reference's generic-C float build: per stream s,
+ *   DRED_rdovae_decode_all(model, features[s], state[s], latents[s], count[s])      (src/dred_rdovae.c:38-52, src/dred_rdovae_dec.c:37-98)
+ * -- the producer of the vectors plc_fec_feed consumes: one redundancy packet (an initial state, then one latent per 40 ms) becomes four
+ * 20-float feature frames per latent, the newest first.  One launch per shard decodes every active stream's whole latent chain.
+ * The decoder comes from the same blob as the LPCNet model, as write_lpcnet_weights.c:72-75 appends it: arrays state{1,2,3}_*, dec_dense{1..8}_*,
+ * dec_final_* (torch/rdovae/export_rdovae_weights.py, training_tf2/dump_rdovae.py).  Its widths are read from the bias lengths (each up to 256),
+ * the latent and state dimensions from dec_dense1_weights / state1_weights; dec_final has 80 outputs.  Float arrays beside a float LPCNet model
+ * are served.
+ * dred_enable uploads the decoder and sizes the scratch for calls of up to max_latents latents per stream.  int8 (DOT_PROD) decoder arrays, a
+ *   mix of float and int8 ones, incomplete or inconsistent arrays and a blob without any return LPCNET_HIP_E_MODEL with a message; so does every
+ *   other call below before dred_enable.
+ * dred_decode takes host pointers: state [n][state_dim], latents [n][max_latents][latent_dim], count [n] (each 0 .. max_latents), features
+ *   [n][4 max_latents][20].  Rows 4 count[s] and beyond of a stream are not written.  It copies in, runs, copies out and synchronises (one
+ *   host thread per shard).  dred_decode_device* takes device pointers and only enqueues on `hip_stream` (NULL = the batch's own) under the
+ *   ordering rules of lpcnet_batch_analyze_device; `count` is a host array, read before the call returns.  The launch depends on it, so on a
+ *   stream that is being captured the call returns LPCNET_HIP_E_ARG and enqueues nothing.
+ * dred_decode_packed_device* decodes the same values and writes rows first[s] .. first[s] + take[s] - 1 of stream s's decoded frames (host
+ *   arrays) in REVERSE row order -- the oldest frame first -- into one packed array [sum(take)][20], stream 0's vectors first: the layout
+ *   lpcnet_batch_plc_fec_feed_device reads, so redundancy goes from the decoder to the FEC rings without a host hop.  A permutation of
+ *   dred_decode's output and nothing else.
+ * A count outside 0 .. max_latents, first / take outside the stream's 4 count[s] decoded rows, and a non-zero count on a stream beyond its
+ *   shard's active prefix return LPCNET_HIP_E_ARG with nothing written; the rows of inactive streams are untouched.  The _shard forms cover
+ *   that shard's streams, in arrays and packing.
+ * No per-stream state: a call keeps nothing between calls (decode_all semantics; the incremental init_states / decode_qframe pair is not
+ *   exposed), so lpcnet_batch_copy_streams, the roster and the state snapshots are unaffected.  lpcnet_batch_set_fast does not change this kernel.
+ * dred_set_form pins the streams one workgroup carries (1, 2, 4, 8; 0 = the engine's table) for tests and tools: the output bits are the same in
+ *   every form.  dred_get_form: what a launch over n_streams streams runs with.
+ * dred_info: info[3] = {max_latents, latent dimension, state dimension}: the row lengths of the arrays above. */
+LPCNET_EXPORT int lpcnet_batch_dred_enable(LPCNetBatch *b, int max_latents);
+LPCNET_EXPORT int lpcnet_batch_dred_decode(LPCNetBatch *b, const float *state, const float *latents, const int *count, float *features);
+LPCNET_EXPORT int lpcnet_batch_dred_decode_device(LPCNetBatch *b, const float *d_state, const float *d_latents, const int *count, float *d_features,
+                                                  void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_decode_device_shard(LPCNetBatch *b, int shard, const float *d_state, const float *d_latents, const int *count,
+                                                        float *d_features, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_decode_packed_device(LPCNetBatch *b, const float *d_state, const float *d_latents, const int *count,
+                                                         const int *first, const int *take, float *d_packed, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_decode_packed_device_shard(LPCNetBatch *b, int shard, const float *d_state, const float *d_latents, const int *count,
+                                                               const int *first, const int *take, float *d_packed, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_info(const LPCNetBatch *b, int *info);
+LPCNET_EXPORT int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S);
+LPCNET_EXPORT int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams);
+/* a blob's DRED decoder as the loader sees it, no device: info[12] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
+ * inconsistent), servable (dred_enable accepts the blob), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.  Returns 0,
+ * LPCNET_HIP_E_ARG without `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
+LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len, int *info);
+
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);
 LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st);

@@ -196,6 +196,16 @@ def load_library():
     L.lpcnet_batch_group_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_last_groups.argtypes = [vp, vp, C.c_int]
     L.lpcnet_hip_plc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.lpcnet_hip_dred_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_decode.argtypes = [vp, _f32p, _f32p, vp, _f32p]
+    L.lpcnet_batch_dred_decode_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_dred_decode_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_dred_decode_packed_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_dred_decode_packed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_dred_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -258,6 +268,15 @@ def plc_model_info(blob: bytes):
     if load_library().lpcnet_hip_plc_model_info(blob, len(blob), info) != 0:
         raise LPCNetError("plc_model_info: " + last_error())
     return dict(zip(("present", "servable", "d1", "g1", "g2", "nb1", "nb2"), list(info)))
+
+
+def dred_model_info(blob: bytes):
+    """Host-only view of a blob's DRED decoder: dict(present, servable, latent_dim, state_dim, widths[8]); see include/lpcnet_batch.h."""
+    info = (C.c_int * 12)()
+    if load_library().lpcnet_hip_dred_model_info(blob, len(blob), info) != 0:
+        raise LPCNetError("dred_model_info: " + last_error())
+    v = list(info)
+    return dict(present=v[0], servable=v[1], latent_dim=v[2], state_dim=v[3], widths=v[4:12])
 
 
 def x3_image_info(blob: bytes):
@@ -633,6 +652,64 @@ class LPCNetBatch:
         if rc < 0:
             self._chk(rc, "plc_fec_feed_device")
         return dropped
+
+    # ---- DRED decoder (DRED_rdovae_decode_all per stream; include/lpcnet_batch.h) ----
+    def dred_enable(self, max_latents: int):
+        """upload the blob's DRED decoder and size the scratch for calls of up to max_latents latents per stream"""
+        self._chk(self.L.lpcnet_batch_dred_enable(self.p, max_latents), "dred_enable")
+
+    def dred_info(self):
+        """(max_latents, latent_dim, state_dim): the row lengths of dred_decode's arrays"""
+        info = (C.c_int * 3)()
+        self._chk(self.L.lpcnet_batch_dred_info(self.p, info), "dred_info")
+        return tuple(info)
+
+    def dred_form(self, S=None, n_streams=None) -> int:
+        """S given: pin the streams a workgroup carries (1, 2, 4, 8; 0 = the engine's table).  Returns what a launch over n_streams (default: the
+        batch's) streams runs with; the output bits are the same in every form"""
+        if S is not None:
+            self._chk(self.L.lpcnet_batch_dred_set_form(self.p, S), "dred_form")
+        rc = self.L.lpcnet_batch_dred_get_form(self.p, self.n if n_streams is None else n_streams)
+        if rc < 0:
+            self._chk(rc, "dred_form")
+        return rc
+
+    def dred_decode(self, state: np.ndarray, latents: np.ndarray, count, features: np.ndarray | None = None) -> np.ndarray:
+        """state (n, state_dim), latents (n, max_latents, latent_dim) float32, count [n] -> features (n, 4 * max_latents, 20) float32: stream s's rows
+        [0, 4 * count[s]) are DRED_rdovae_decode_all's output, the newest frame first; its other rows keep what `features` held (zeros without it)"""
+        ml, ld, sd = self.dred_info()
+        st, la = np.ascontiguousarray(state, np.float32), np.ascontiguousarray(latents, np.float32)
+        count = np.ascontiguousarray(count, np.int32)
+        assert st.shape == (self.n, sd) and la.shape == (self.n, ml, ld) and count.shape == (self.n,)
+        out = np.zeros((self.n, 4 * ml, 20), np.float32) if features is None else features
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (self.n, 4 * ml, 20)
+        self._chk(self.L.lpcnet_batch_dred_decode(self.p, st.reshape(-1), la.reshape(-1), count.ctypes.data, out.reshape(-1)), "dred_decode")
+        return out
+
+    def dred_decode_device(self, d_state_ptr: int, d_latents_ptr: int, count, d_features_ptr: int, hip_stream: int = 0, shard=None):
+        """enqueue only: device pointers laid out as dred_decode's arrays; count stays a host array (of the shard's streams with shard=k)"""
+        n = self.n if shard is None else self.shards[shard][1]
+        count = np.ascontiguousarray(count, np.int32)
+        assert count.shape == (n,)
+        args = (d_state_ptr, d_latents_ptr, count.ctypes.data, d_features_ptr, hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_decode_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_decode_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_decode_device")
+
+    def dred_decode_packed(self, d_state_ptr: int, d_latents_ptr: int, count, first, take, hip_stream: int = 0, shard=None):
+        """enqueue only: decode as dred_decode_device does and write rows first[s] .. first[s] + take[s] - 1 of every stream, the oldest frame first,
+        into one packed [sum(take)][20] float32 array on the device -- a torch tensor, returned, whose data_ptr() plc_fec_feed_device takes with
+        count = take.  count, first, take stay host arrays (of the shard's streams with shard=k)"""
+        import torch
+        n = self.n if shard is None else self.shards[shard][1]
+        count, first, take = (np.ascontiguousarray(x, np.int32) for x in (count, first, take))
+        assert count.shape == first.shape == take.shape == (n,)
+        device = self.shards[0 if shard is None else shard][2]
+        rows = int(take.clip(min=0).sum())                # (a negative take is the C call's to refuse)
+        out = torch.empty((max(rows, 1), 20), dtype=torch.float32, device="cuda:%d" % device)[:rows]
+        args = (d_state_ptr, d_latents_ptr, count.ctypes.data, first.ctypes.data, take.ctypes.data, out.data_ptr(), hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_decode_packed_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_decode_packed_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_decode_packed")
+        return out
 
     def get_plc_state(self, stream: int) -> bytes:
         buf = C.create_string_buffer(self.L.lpcnet_batch_plc_state_size())

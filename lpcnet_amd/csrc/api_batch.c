@@ -344,6 +344,72 @@ int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20)
     if (!in57 || !out20) { set_err("lpcnet_batch_plc_pred: bad arguments"); return LPCN_E_ARG; }
     EACH_SHARD(lpcn_batch_dev_plc_pred_host(s->dev, in57 + (size_t)at.first * LPCN_PLC_IN, out20 + (size_t)at.first * LPCN_NB_FEAT));
 }
+/* ---- DRED decoder (DRED_rdovae_decode_all per stream; include/lpcnet_batch.h) ---- */
+#define NEED_DRED_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_dred_enabled((b)->sh[0].dev)) { set_err("the DRED decoder is not enabled on this batch (lpcnet_batch_dred_enable)"); return LPCN_E_MODEL; } } while (0)
+int lpcnet_batch_dred_enable(LPCNetBatch *b, int max_latents) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_dred_enable(s->dev, max_latents)); }
+int lpcnet_batch_dred_info(const LPCNetBatch *b, int *info)
+{
+    NEED_DRED_ON(b);
+    if (!info) { set_err("lpcnet_batch_dred_info: bad arguments"); return LPCN_E_ARG; }
+    info[0] = lpcn_batch_dev_dred_enabled(b->sh[0].dev);
+    FWD(lpcn_batch_dev_dred_dims(b->sh[0].dev, &info[1], &info[2]));
+}
+int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S) { NEED_DRED_ON(b); EACH_SHARD(lpcn_batch_dev_dred_set_form(s->dev, S)); }
+int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams)
+{
+    NEED_DRED_ON(b);
+    const int rc = lpcn_batch_dev_dred_form(b->sh[0].dev, n_streams);
+    if (rc < 0) take_engine_err();
+    return rc;
+}
+typedef struct { LPCNetBatch *b; const float *state, *latents; const int *count; float *features; int max_latents, latent_dim, state_dim; } dred_args;
+static int dred_shard(void *args, int k)
+{
+    const dred_args *a = (const dred_args *)args;
+    const size_t f = (size_t)a->b->at[k].first;
+    return lpcn_batch_dev_dred_decode_host(a->b->sh[k].dev, a->state + f * a->state_dim, a->latents + f * a->max_latents * a->latent_dim, a->count + f,
+                                           a->features + f * LPCN_DRED_FRAMES * a->max_latents * LPCN_NB_FEAT);
+}
+int lpcnet_batch_dred_decode(LPCNetBatch *b, const float *state, const float *latents, const int *count, float *features)
+{
+    NEED_DRED_ON(b);
+    if (!state || !latents || !count || !features) { set_err("lpcnet_batch_dred_decode: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard writes) */
+        const int rc = lpcn_batch_dev_dred_check(b->sh[k].dev, count + b->at[k].first, NULL, NULL, NULL);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    dred_args a = {b, state, latents, count, features, lpcn_batch_dev_dred_enabled(b->sh[0].dev), 0, 0};
+    lpcn_batch_dev_dred_dims(b->sh[0].dev, &a.latent_dim, &a.state_dim);
+    return run_shards(b, dred_shard, &a);
+}
+int lpcnet_batch_dred_decode_device_shard(LPCNetBatch *b, int shard, const float *d_state, const float *d_latents, const int *count, float *d_features,
+                                          void *hip_stream)
+{
+    NEED_DRED_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !count) { set_err("lpcnet_batch_dred_decode_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_decode(b->sh[shard].dev, d_state, d_latents, count, d_features, hip_stream));
+}
+int lpcnet_batch_dred_decode_device(LPCNetBatch *b, const float *d_state, const float *d_latents, const int *count, float *d_features, void *hip_stream)
+{
+    NEED_DRED_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_decode_device");
+    return lpcnet_batch_dred_decode_device_shard(b, 0, d_state, d_latents, count, d_features, hip_stream);
+}
+int lpcnet_batch_dred_decode_packed_device_shard(LPCNetBatch *b, int shard, const float *d_state, const float *d_latents, const int *count, const int *first,
+                                                 const int *take, float *d_packed, void *hip_stream)
+{
+    NEED_DRED_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !count || !first || !take) { set_err("lpcnet_batch_dred_decode_packed_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_decode_packed(b->sh[shard].dev, d_state, d_latents, count, first, take, d_packed, hip_stream));
+}
+int lpcnet_batch_dred_decode_packed_device(LPCNetBatch *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take,
+                                           float *d_packed, void *hip_stream)
+{
+    NEED_DRED_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_decode_packed_device");
+    return lpcnet_batch_dred_decode_packed_device_shard(b, 0, d_state, d_latents, count, first, take, d_packed, hip_stream);
+}
+
 /* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */
 typedef struct { LPCNetBatch *b; const void *pcm; int is_float; float *features; int feat_stride, n_frames; } analyze_args;
 static int analyze_shard(void *args, int k)

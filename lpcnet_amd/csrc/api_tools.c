@@ -102,6 +102,21 @@ int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info)
     return 0;
 }
 
+/* Host-only view of a blob's DRED decoder (no GPU needed): info[0..11] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
+ * inconsistent), servable (lpcnet_batch_dred_enable accepts the blob), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.
+ * Returns 0, LPCN_E_ARG without `info`, LPCN_E_MODEL when the blob does not load as an LPCNet model at all. */
+int lpcnet_hip_dred_model_info(const unsigned char *data, int len, int *info)
+{
+    lpcn_model_host m;
+    if (!info) { set_err("lpcnet_hip_dred_model_info: bad arguments"); return LPCN_E_ARG; }
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return LPCN_E_MODEL; }
+    info[0] = m.dred.present; info[1] = lpcn_dred_servable(&m);
+    info[2] = m.dred.latent_dim; info[3] = m.dred.state_dim;
+    for (int k = 0; k < 8; k++) info[4 + k] = m.dred.width[k];
+    lpcn_model_release(&m);
+    return 0;
+}
+
 /* Host-only model check (no GPU needed): parses the blob with the loader's rules, builds the device
  * packings and verifies them.  info[0..5] = {is_int8, blocks GRU-A, blocks GRU-B, items per lane,
  * padded GRU-B blocks, selftest code}.  Returns 0 if the blob is loadable by the engine (float or

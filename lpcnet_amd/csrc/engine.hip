@@ -340,6 +340,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     e->plc_present = m->plc.present;
     e->plc_servable = lpcn_plc_servable(m) != 0;
     if (e->plc_servable && (rc = m->is_int8 ? plc_upload_net_i8(e, &m->plc) : plc_upload_net(e, &m->plc))) return fail(rc);
+    if ((rc = dred_engine_init(e, m))) return fail(rc);
     *out = e;
     return 0;
 }

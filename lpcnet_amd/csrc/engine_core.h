@@ -121,6 +121,14 @@ struct X2WideHost {
     ~X2WideHost() { if (packed) lpcn_model_release(&mx); }
 };
 
+// The blob's DRED decoder as copied when the engine was created (the blob is the caller's), on the host until a batch asks for it:
+// lpcn_batch_dev_dred_enable uploads it and drops this.  `m` points into the two arenas.
+struct DredHostModel {
+    lpcn_dred_model m{};
+    std::vector<float> f;
+    std::vector<int> i;
+};
+
 struct lpcn_engine {
     int device = 0;
     int nw = 0, nb_b = 0;
@@ -141,6 +149,11 @@ struct lpcn_engine {
     lpcn::PlcNetQ plcq{};          //   ... an int8 blob's (plc_pred_i8_kernel)
     int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
     bool plc_servable = false;     //   ... and whether it is in the blob's own flavour (lpcn_plc_servable): uploaded only then
+    lpcn::DredNet dred{};          // DRED decoder (engine_dred.hip): the blob's decoder on the device, once a batch has enabled it ...
+    const lpcn::DredNet *d_dred = nullptr;        //   ... and the device copy of this block, which the kernel walks
+    int dred_present = 0;          //   ... lpcn_dred_model.present of the blob
+    bool dred_servable = false;    //   ... float arrays beside a float LPCNet model (lpcn_dred_servable)
+    std::unique_ptr<DredHostModel> dred_host;     //   ... not uploaded yet
 };
 
 // packet-loss concealment of a batch (lpcn_batch_dev_plc_enable): the control state on the host, the data on the device
@@ -164,6 +177,18 @@ struct lpcn_plc_host {
     Event ev_feed;                                  //   and a step never wait for each other's upload) and "the previous feed's have left it"
     bool feed_pending = false;
     DevBuf<float> d_feed_src;                       //   ... and the host-pointer call's packed vectors, grown to the largest call
+};
+
+// DRED decoding of a batch (lpcn_batch_dev_dred_enable): no per-stream state, only the scratch of a call
+struct lpcn_dred_host {
+    int max_latents = 0, cus = 0;                   // (cus: the device's compute units, for the form table)
+    int form = 0;                                   // streams per workgroup pinned by lpcn_batch_dev_dred_set_form (0: the table's choice)
+    DevBuf<int> d_rec;                              // a call's per-stream records (dred_kernels.hip.h: DRED_REC) ...
+    PinBuf h_rec;                                   // ... their pinned source ...
+    Event ev_rec;                                   // ... and "the previous call's have left it"
+    bool rec_pending = false;
+    DevBuf<float> d_state, d_latents, d_feat;       // staging of the host-pointer call
+    PinBuf h_feat;                                  //   ... whose output comes down whole and goes to the caller row by row (rows past a stream's count stay)
 };
 
 struct lpcn_batch_dev {
@@ -224,6 +249,7 @@ struct lpcn_batch_dev {
     Event ev_pairs;                    //   ... and "the previous call's list has left it"
     bool pairs_pending = false;
     std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
+    std::unique_ptr<lpcn_dred_host> dred;         // DRED decoding (lpcn_batch_dev_dred_enable)
     PinBuf h_pin;                      // pinned host staging of the single-stream fast path and the combined pass: each reserves what it lays out
     bool timing = false;
     float ms_sample = 0.f, ms_frame = 0.f;
@@ -283,6 +309,8 @@ int lpcn_launch_frame_kernels(const LpcnFrameModel &M, hipStream_t st, int n, in
                               float *d_cond, float *d_cond_a, float *d_cond_b, float *d_lpc, char *err, size_t errlen);
 // engine_plc.hip: the buffers of the compacted groups, with every stream's kept frame products
 int group_alloc(lpcn_batch_dev *b);
+// engine_dred.hip: the host copy of the blob's DRED decoder, taken when the engine is created
+int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m);
 // engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)
 int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
                                  size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride,

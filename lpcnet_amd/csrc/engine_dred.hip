@@ -1,0 +1,278 @@
+// Device runtime, DRED unit: the decoder's upload, a batch's scratch and the one launch that decodes every active stream's latent chain
+// (dred_kernels.hip.h).  The call keeps nothing per stream between calls, so resets, stream copies and state snapshots do not
+// know about it.
+#include "engine_core.h"
+#include "dred_kernels.hip.h"
+#include "lpcnet_tables_gen.h"
+#include <mutex>
+
+// ---- the engine's part: a host copy of the blob's arrays now, the upload when a batch first enables the decoder
+int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
+{
+    e->dred_present = m->dred.present;
+    e->dred_servable = lpcn_dred_servable(m) != 0;
+    if (!e->dred_servable) return 0;
+    auto h = std::make_unique<DredHostModel>();
+    h->m = m->dred;
+    lpcn_dred_model &d = h->m;
+    lpcn_dred_dense *dense[9] = {&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final};
+    size_t nf = 0, ni = 0;
+    std::vector<size_t> idx_len(3);
+    for (lpcn_dred_dense *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
+    for (int g = 0; g < 3; ++g) {
+        const lpcn_dred_gru &G = d.gru[g];
+        idx_len[g] = (size_t)(3 * G.n / 8) + G.nb;
+        nf += 32 * (size_t)G.nb + 3 * (size_t)G.n * G.n + 6 * (size_t)G.n;
+        ni += idx_len[g];
+    }
+    h->f.resize(nf);
+    h->i.resize(ni);
+    float *fp = h->f.data();
+    int *ip = h->i.data();
+    auto take = [&](const float *&src, size_t count) { memcpy(fp, src, sizeof(float) * count); src = fp; fp += count; };
+    for (lpcn_dred_dense *q : dense) { take(q->w, (size_t)q->n_in * q->n_out); take(q->b, q->n_out); }
+    for (int g = 0; g < 3; ++g) {
+        lpcn_dred_gru &G = d.gru[g];
+        take(G.w, 32 * (size_t)G.nb); take(G.rec, 3 * (size_t)G.n * G.n); take(G.bias, 6 * (size_t)G.n);
+        memcpy(ip, G.idx, sizeof(int) * idx_len[g]); G.idx = ip; ip += idx_len[g];
+    }
+    e->dred_host = std::move(h);
+    return 0;
+}
+
+template <typename T>
+static int dred_upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
+{
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, count * sizeof(T) ? count * sizeof(T) : 16));
+    e->allocs.push_back(p);          // (freed with the engine)
+    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = (const T *)p;
+    return 0;
+}
+
+// the arrays as they are; for each sparse GRU input matrix the first block of every 8-row group and the blocks' input positions (as the PLC
+// network's); then the block itself, which the kernel reads from device memory
+static int dred_upload_net(lpcn_engine *e)
+{
+    const lpcn_dred_model &d = e->dred_host->m;
+    lpcn::DredNet n{};
+    int rc = 0, off[9] = {0};
+    n.latent_dim = d.latent_dim; n.state_dim = d.state_dim;
+    for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + d.width[k];
+    n.total = off[8];
+    auto up_dense = [&](const lpcn_dred_dense &s, lpcn::DredStep &o, int x, int out) {
+        o.gru = 0; o.n_in = s.n_in; o.n_out = s.n_out; o.x = x; o.out = out;
+        int r = dred_upload<float>(e, &o.w, s.w, (size_t)s.n_in * s.n_out);
+        return r ? r : dred_upload<float>(e, &o.b, s.b, s.n_out);
+    };
+    static const int dense_at[5] = {0, 2, 4, 6, 7}, gru_at[3] = {1, 3, 5};
+    for (int k = 0; k < 3; ++k) if ((rc = up_dense(d.state[k], n.init[k], -1, off[gru_at[k]]))) return rc;
+    for (int k = 0; k < 5; ++k) if ((rc = up_dense(d.dense[k], n.step[dense_at[k]], dense_at[k] ? off[dense_at[k] - 1] : -1, off[dense_at[k]]))) return rc;
+    for (int g = 0; g < 3; ++g) {
+        const lpcn_dred_gru &G = d.gru[g];
+        lpcn::DredStep &o = n.step[gru_at[g]];
+        o.gru = 1; o.n_in = G.n_in; o.n_out = G.n; o.x = off[gru_at[g] - 1]; o.out = off[gru_at[g]];
+        n.max_gru = G.n > n.max_gru ? G.n : n.max_gru;
+        const int groups = 3 * G.n / 8;
+        const int *idx = G.idx;
+        std::vector<int> start(groups + 1, 0), pos;
+        for (int r = 0; r < groups; ++r) {
+            const int cnt = *idx++;
+            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++);
+            start[r + 1] = (int)pos.size();
+        }
+        if ((rc = dred_upload<float>(e, &o.w, G.w, 32 * (size_t)G.nb)) || (rc = dred_upload<float>(e, &o.rec, G.rec, 3 * (size_t)G.n * G.n)) ||
+            (rc = dred_upload<float>(e, &o.b, G.bias, 6 * (size_t)G.n)) || (rc = dred_upload<int>(e, &o.start, start.data(), start.size())) ||
+            (rc = dred_upload<int>(e, &o.pos, pos.data(), pos.size()))) return rc;
+    }
+    if ((rc = dred_upload<float>(e, &n.final_w, d.final.w, (size_t)n.total * LPCN_DRED_OUT)) || (rc = dred_upload<float>(e, &n.final_b, d.final.b, LPCN_DRED_OUT)) ||
+        (rc = dred_upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
+    if ((rc = dred_upload<lpcn::DredNet>(e, &e->d_dred, &n, 1))) return rc;
+    e->dred = n;
+    e->dred_host.reset();
+    return 0;
+}
+
+extern "C" int lpcn_engine_dred_present(const lpcn_engine *e) { return e->dred_present; }
+extern "C" int lpcn_batch_dev_dred_enabled(const lpcn_batch_dev *b) { return b->dred ? b->dred->max_latents : 0; }
+
+extern "C" int lpcn_batch_dev_dred_enable(lpcn_batch_dev *b, int max_latents)
+{
+    lpcn_engine *e = b->e;
+    if (e->dred_present == 0) { snprintf(g_err, sizeof(g_err), "the model blob has no DRED decoder (state1..3_*, dec_dense1..8_*, dec_final_*)"); return LPCN_E_MODEL; }
+    if (e->dred_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder is int8 (DOT_PROD): only float decoder arrays are served"); return LPCN_E_MODEL; }
+    if (e->dred_present != 1) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder arrays are incomplete, mix float and int8, or do not fit together (widths up to %d, dec_final with %d outputs)", LPCN_DRED_MAX_UNITS, LPCN_DRED_OUT); return LPCN_E_MODEL; }
+    if (!e->dred_servable) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder is float but its LPCNet model is int8: float decoder arrays are served beside a float model"); return LPCN_E_MODEL; }
+    if (max_latents < 1 || (long long)max_latents * LPCN_DRED_FRAMES * b->n > 0x7fffffffLL / LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "DRED: max_latents must be at least 1 (and the batch's rows fit an int)"); return LPCN_E_ARG; }
+    DeviceGuard guard(e->device);
+    int rc = wait_all(b);
+    if (rc) return rc;
+    if (e->dred_host && (rc = dred_upload_net(e))) return rc;
+    if ((size_t)lpcn::dred_lds_floats(e->dred, 1) * sizeof(float) > 160 * 1024) { snprintf(g_err, sizeof(g_err), "DRED: the decoder's buffers do not fit the LDS"); return LPCN_E_MODEL; }
+    if (!b->dred) {
+        auto p = std::make_unique<lpcn_dred_host>();
+        if ((rc = p->d_rec.alloc((size_t)lpcn::DRED_REC * b->n)) || (rc = p->h_rec.reserve(sizeof(int) * lpcn::DRED_REC * (size_t)b->n))) return rc;
+        if (hipEventCreateWithFlags(&p->ev_rec.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED: hipEventCreate failed"); return LPCN_E_HIP; }
+        b->dred = std::move(p);
+    }
+    b->dred->max_latents = max_latents;
+    b->dred->cus = device_cus(e);
+    return 0;
+}
+#define NEED_DRED(b) do { if (!(b)->dred) { snprintf(g_err, sizeof(g_err), "the DRED decoder is not enabled on this batch (lpcnet_batch_dred_enable)"); return LPCN_E_MODEL; } } while (0)
+
+extern "C" int lpcn_batch_dev_dred_dims(const lpcn_batch_dev *b, int *latent_dim, int *state_dim)
+{
+    NEED_DRED(b);
+    if (latent_dim) *latent_dim = b->e->dred.latent_dim;
+    if (state_dim) *state_dim = b->e->dred.state_dim;
+    return 0;
+}
+
+// ---- streams per workgroup.  A workgroup's time per latent is set by its dependent add chains, not by how many streams it carries: measured on one
+// MI355X at width 256 and 25 latents (profiles/dred_rate.json), 256 streams take 6.61 / 6.71 / 6.92 / 7.67 ms at 1 / 2 / 4 / 8 streams per
+// workgroup -- one workgroup per CU or fewer, so the fewest streams win -- and 2 048 streams 52.8 / 27.3 / 14.2 / 7.78 ms, 8 192 streams 210.9 / 109.1 /
+// 56.4 / 31.0 ms: the time follows the number of workgroups.  The table: the fewest streams per workgroup that still put the streams on the CUs in one
+// round, eight beyond that.
+static bool dred_form_fits(const lpcn_engine *e, int S) { return (size_t)lpcn::dred_lds_floats(e->dred, S) * sizeof(float) <= 160 * 1024; }
+extern "C" int lpcn_batch_dev_dred_form(const lpcn_batch_dev *b, int n)
+{
+    NEED_DRED(b);
+    int S = b->dred->form;
+    if (!S) {
+        const int cus = b->dred->cus;
+        for (S = 1; S < 8 && (n + S - 1) / S > cus; S *= 2) {}
+    }
+    while (S > 1 && !dred_form_fits(b->e, S)) S /= 2;      // (widths the widest form's buffers do not fit)
+    return S;
+}
+extern "C" int lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S)
+{
+    NEED_DRED(b);
+    if (S != 0 && S != 1 && S != 2 && S != 4 && S != 8) { snprintf(g_err, sizeof(g_err), "DRED form: 1, 2, 4 or 8 streams per workgroup, 0 = the table's choice"); return LPCN_E_ARG; }
+    b->dred->form = S;
+    return 0;
+}
+
+// count in 0 .. max_latents and zero beyond the active prefix; the packed form's first / take inside the decoded rows
+extern "C" int lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *count, const int *first, const int *take, long long *rows)
+{
+    NEED_DRED(b);
+    if (!count || (first != nullptr) != (take != nullptr)) { snprintf(g_err, sizeof(g_err), "bad DRED decode arguments"); return LPCN_E_ARG; }
+    long long total = 0;
+    for (int s = 0; s < b->n; ++s) {
+        if (count[s] < 0 || count[s] > b->dred->max_latents) { snprintf(g_err, sizeof(g_err), "DRED decode: stream %d has a count outside 0 .. %d", s, b->dred->max_latents); return LPCN_E_ARG; }
+        if (s >= b->active && count[s] != 0) { snprintf(g_err, sizeof(g_err), "DRED decode: stream %d is not active and has a count", s); return LPCN_E_ARG; }
+        if (first && s < b->active) {
+            if (first[s] < 0 || take[s] < 0 || (long long)first[s] + take[s] > (long long)LPCN_DRED_FRAMES * count[s]) { snprintf(g_err, sizeof(g_err), "DRED decode: stream %d selects rows outside its %d decoded ones", s, LPCN_DRED_FRAMES * count[s]); return LPCN_E_ARG; }
+            total += take[s];
+        }
+    }
+    if (total > 0x7fffffffLL / LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "DRED decode: too many packed rows"); return LPCN_E_ARG; }
+    if (rows) *rows = total;
+    return 0;
+}
+
+template <int S>
+static int dred_launch_form(const lpcn::DredNet *P, int grid, int lds, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state,
+                            const float *d_latents, float *d_out)
+{
+    // the dynamic-LDS limit of a form is raised once per (device, size), not at every launch
+    static std::mutex mu;
+    static int limit[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (dev < 0 || dev >= 64 || limit[dev] < lds) {
+            HIP_TRY(hipFuncSetAttribute((const void *)lpcn::dred_decode_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            if (dev >= 0 && dev < 64) limit[dev] = lds;
+        }
+    }
+    hipLaunchKernelGGL(lpcn::dred_decode_kernel<S>, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, P, n, max_latents, d_rec, d_state, d_latents, d_out);
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED decode: kernel launch failed"); return LPCN_E_HIP; }
+    return 0;
+}
+
+// checks, the records' upload through the pinned buffer, one launch.  first == NULL: the plain layout
+static int dred_enqueue(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take, float *d_out,
+                        hipStream_t st)
+{
+    int rc = lpcn_batch_dev_dred_check(b, count, first, take, nullptr);
+    if (rc) return rc;
+    bool any = false;
+    for (int s = 0; s < b->active; ++s) any |= count[s] > 0;
+    if (!any) return 0;
+    if (!d_state || !d_latents || !d_out) { snprintf(g_err, sizeof(g_err), "bad DRED decode arguments"); return LPCN_E_ARG; }
+    if (stream_is_capturing(st)) { snprintf(g_err, sizeof(g_err), "a DRED decode cannot be captured: its launch depends on the host's count array"); return LPCN_E_ARG; }
+    lpcn_dred_host *p = b->dred.get();
+    if (p->rec_pending) { HIP_TRY(hipEventSynchronize(p->ev_rec)); p->rec_pending = false; }      // (the previous call's records have left the pinned buffer)
+    int *h = (int *)p->h_rec.p, row = 0;
+    for (int s = 0; s < b->active; ++s) {
+        int *q = h + (size_t)s * lpcn::DRED_REC;
+        q[0] = count[s]; q[1] = first ? first[s] : -1; q[2] = first ? take[s] : 0; q[3] = row;
+        if (first) row += take[s];
+    }
+    const int S = lpcn_batch_dev_dred_form(b, b->active);
+    const int grid = (b->active + S - 1) / S, lds = lpcn::dred_lds_floats(b->e->dred, S) * (int)sizeof(float);
+    if ((rc = order_begin(b, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_rec, h, sizeof(int) * lpcn::DRED_REC * (size_t)b->active, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(p->ev_rec, st));
+    p->rec_pending = true;
+    const lpcn::DredNet *P = b->e->d_dred;
+    switch (S) {
+    case 1: rc = dred_launch_form<1>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
+    case 2: rc = dred_launch_form<2>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
+    case 4: rc = dred_launch_form<4>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
+    default: rc = dred_launch_form<8>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
+    }
+    if (rc) return rc;
+    return order_end(b, st);
+}
+
+extern "C" int lpcn_batch_dev_dred_decode(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, float *d_features, void *hip_stream)
+{
+    NEED_DRED(b);
+    DeviceGuard guard(b->e->device);
+    return dred_enqueue(b, d_state, d_latents, count, nullptr, nullptr, d_features, hip_stream ? (hipStream_t)hip_stream : b->e->stream);
+}
+
+extern "C" int lpcn_batch_dev_dred_decode_packed(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first,
+                                                 const int *take, float *d_packed, void *hip_stream)
+{
+    NEED_DRED(b);
+    if (!first || !take) { snprintf(g_err, sizeof(g_err), "bad DRED decode arguments"); return LPCN_E_ARG; }
+    long long rows = 0;
+    int rc = lpcn_batch_dev_dred_check(b, count, first, take, &rows);
+    if (rc) return rc;
+    if (!rows) return 0;
+    DeviceGuard guard(b->e->device);
+    return dred_enqueue(b, d_state, d_latents, count, first, take, d_packed, hip_stream ? (hipStream_t)hip_stream : b->e->stream);
+}
+
+// host pointers: the active streams' rows in, one launch, the output down whole and out to the caller row by row
+extern "C" int lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *state, const float *latents, const int *count, float *features)
+{
+    NEED_DRED(b);
+    int rc = lpcn_batch_dev_dred_check(b, count, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (!state || !latents || !features) { snprintf(g_err, sizeof(g_err), "bad DRED decode arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
+    DeviceGuard guard(b->e->device);
+    lpcn_dred_host *p = b->dred.get();
+    const lpcn::DredNet &P = b->e->dred;
+    hipStream_t st = b->e->stream;
+    const size_t n = (size_t)b->active, per_s = (size_t)P.state_dim, per_l = (size_t)p->max_latents * P.latent_dim,
+                 per_f = (size_t)LPCN_DRED_FRAMES * p->max_latents * LPCN_NB_FEAT;
+    if ((rc = p->d_state.reserve(b, (size_t)b->n * per_s)) || (rc = p->d_latents.reserve(b, (size_t)b->n * per_l)) || (rc = p->d_feat.reserve(b, (size_t)b->n * per_f)) ||
+        (rc = p->h_feat.reserve(sizeof(float) * (size_t)b->n * per_f))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_state, state, sizeof(float) * n * per_s, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->d_latents, latents, sizeof(float) * n * per_l, hipMemcpyHostToDevice, st));
+    if ((rc = dred_enqueue(b, p->d_state, p->d_latents, count, nullptr, nullptr, p->d_feat, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->h_feat.p, p->d_feat, sizeof(float) * n * per_f, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t s = 0; s < n; ++s)
+        memcpy(features + s * per_f, (const float *)p->h_feat.p + s * per_f, sizeof(float) * LPCN_DRED_FRAMES * LPCN_NB_FEAT * (size_t)count[s]);
+    return 0;
+}

@@ -69,6 +69,22 @@ struct PlcNetQ {
     const float *tansig;
 };
 
+// the DRED decoder on the device (dred_decode_kernel), a device-resident block the kernel walks step by step: three dense layers from the initial
+// state to the GRU states, the eight layers of a latent, dec_final.  The blob's arrays as they are, the sparse GRU input matrices with per-row-group
+// starts like the PLC network's.  x / out: where a step reads and writes in the concatenated buffer, in cells of S floats (x < 0: the input vector)
+struct DredStep {
+    int gru;                         // 0: dense, tanh; 1: GRU (out = its state's segment)
+    int n_in, n_out, x, out;
+    const float *w, *b, *rec;        // dense [n_in][n_out], [n_out]; GRU blocks [nb][4][8], bias [2][3 n_out], recurrent [n_out][3 n_out]
+    const int *start, *pos;          // GRU: [3 n_out / 8 + 1] first block of a row group, [blocks] input position of a block
+};
+struct DredNet {
+    int latent_dim, state_dim, max_gru, total;       // (total: the buffer's length = dec_final's inputs)
+    DredStep init[3], step[8];
+    const float *final_w, *final_b;                  // [total][80], [80]
+    const float *tansig;
+};
+
 // a compacted group's rows in and out (group_gather_kernel, group_scatter_kernel)
 struct GroupRows {
     const int *map;

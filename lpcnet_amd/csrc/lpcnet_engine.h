@@ -98,6 +98,25 @@ typedef struct lpcn_plc_model {
     const float *out_w, *out_b;                  /* [g2][20], [20] */
 } lpcn_plc_model;
 
+/* ---- the DRED decoder of the same blob (DRED_rdovae_decode_all, src/dred_rdovae.c:38-52; src/dred_rdovae_dec.c:37-98): three dense layers that turn the
+ * initial state into the GRU states, then per latent dense 1 -> GRU 2 -> dense 3 -> GRU 4 -> dense 5 -> GRU 6 -> dense 7 -> dense 8, every output appended
+ * to one buffer, and a linear layer over the whole buffer that gives four 20-float frames.  Bound by the names torch/rdovae/export_rdovae_weights.py and
+ * training_tf2/dump_rdovae.py emit; the widths are read from the bias lengths, the latent and state dimensions from the first matrices. */
+#define LPCN_DRED_MAX_UNITS 256      /* most units of a layer, and most inputs of the first layers (latent, initial state) */
+#define LPCN_DRED_FRAMES    4        /* frames per latent */
+#define LPCN_DRED_OUT       (LPCN_DRED_FRAMES * LPCN_NB_FEAT)
+typedef struct lpcn_dred_dense { const float *w, *b; int n_in, n_out; } lpcn_dred_dense;                      /* [n_in][n_out], [n_out] */
+typedef struct lpcn_dred_gru { const float *w, *rec, *bias; const int *idx; int n_in, n, nb; } lpcn_dred_gru;  /* blocks [nb][4][8], [n][3 n], [2][3 n] */
+typedef struct lpcn_dred_model {
+    int present;                 /* 0: the blob has none of the decoder's arrays; 1: float arrays; 2: int8 GRU arrays (DOT_PROD); -1: incomplete or inconsistent */
+    int latent_dim, state_dim;
+    int width[8];                /* dec_dense1 .. dec_dense8 */
+    lpcn_dred_dense state[3];    /* state1 .. state3: tanh */
+    lpcn_dred_dense dense[5];    /* dec_dense1, 3, 5, 7, 8: tanh */
+    lpcn_dred_gru gru[3];        /* dec_dense2, 4, 6 */
+    lpcn_dred_dense final;       /* dec_final: [sum of the widths][80], linear */
+} lpcn_dred_model;
+
 typedef struct lpcn_model_host {
     int is_int8;                 /* blob flavour: 0 = float qweights (DISABLE_DOT_PROD), 1 = int8 (DOT_PROD)  */
     int b_dense;                 /* GRU-B input matrix lists every input block for every row group */
@@ -134,6 +153,7 @@ typedef struct lpcn_model_host {
     uint8_t *pk_b_blk;    /* [nb_b] input block index per block                                */
     float   *pk_emb[3];   /* sig/pred/exc tables re-ordered to [256][3 slots][512 threads] */
     lpcn_plc_model plc;   /* the PLC network of the same blob, when it has one (pointers into the blob) */
+    lpcn_dred_model dred; /* the DRED decoder of the same blob, when it has one (pointers into the blob) */
 } lpcn_model_host;
 
 /* GRU-A dealt to the twelve waves of sample_kernel_x3 (float blobs).  A wave holds LPCN_X3_NW items per lane: segment 0 -- the HEAD of a candidate
@@ -166,6 +186,7 @@ int  lpcn_x3_image_selftest(const lpcn_model_host *m, const lpcn_x3_image *im); 
 /* re-expand the packings and compare them with the blob (0 = consistent) */
 int  lpcn_model_selftest(const lpcn_model_host *m);
 int  lpcn_plc_servable(const lpcn_model_host *m);                           /* 1: the blob's PLC network is in the blob's own flavour (float / int8) */
+int  lpcn_dred_servable(const lpcn_model_host *m);                          /* 1: the blob's DRED decoder is float beside a float LPCNet model */
 void lpcn_plc_pack_rec_i8(const signed char *rec, int N, int32_t *out);     /* int8 recurrent weights of a PLC GRU, one dword per (row, block): out [N / 4][3 N] */
 
 /* ---- per-stream state as the device keeps it (AoS, one record per stream) ------------------ */
@@ -380,6 +401,23 @@ int  lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int stream, lpcn_plc_state_
 int  lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int stream, const lpcn_plc_state_rec *host);
 int  lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, float *ceps36);
 int  lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57, float *out20);
+
+/* DRED decoder (DRED_rdovae_decode_all per stream, dred_kernels.hip.h): one launch decodes every active stream's whole latent chain.
+ * Nothing is kept per stream between calls.  state [n][state_dim], latents [n][max_latents][latent_dim], count [n] (host, 0 .. max_latents),
+ * features [n][4 max_latents][20]: rows 4 count[s] and beyond of a stream are not written.  The device forms only enqueue (not on a capturing stream:
+ * the launch depends on the host arrays); the packed form writes rows first[s] .. first[s] + take[s] - 1 of every stream in reverse order into one
+ * [sum(take)][20] array, stream 0's first -- the layout lpcn_batch_dev_plc_fec_feed reads. */
+int  lpcn_engine_dred_present(const lpcn_engine *e);          /* lpcn_dred_model.present of the engine's blob */
+int  lpcn_batch_dev_dred_enable(lpcn_batch_dev *b, int max_latents);
+int  lpcn_batch_dev_dred_enabled(const lpcn_batch_dev *b);    /* max_latents, 0 before lpcn_batch_dev_dred_enable */
+int  lpcn_batch_dev_dred_dims(const lpcn_batch_dev *b, int *latent_dim, int *state_dim);
+int  lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S);  /* streams per workgroup: 1, 2, 4, 8; 0 = the table's choice */
+int  lpcn_batch_dev_dred_form(const lpcn_batch_dev *b, int n);/* what a launch over n streams runs with */
+int  lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *count, const int *first, const int *take, long long *rows);   /* the argument checks alone; *rows = sum(take) */
+int  lpcn_batch_dev_dred_decode(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, float *d_features, void *hip_stream);
+int  lpcn_batch_dev_dred_decode_packed(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take,
+                                       float *d_packed, void *hip_stream);
+int  lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *state, const float *latents, const int *count, float *features);
 
 /* Timing of the most recent run: kernel-only milliseconds measured with HIP events on the
  * stream the kernels were launched on (sample kernel, frame kernels). */

@@ -549,6 +549,84 @@ int lpcn_plc_servable(const lpcn_model_host *m)
     return (m->plc.present == 1 && !m->is_int8) || (m->plc.present == 2 && m->is_int8);
 }
 
+/* The DRED decoder of the blob, bound by the names write_lpcnet_weights.c:72-75 appends (rdovae_dec_arrays: state1..3, dec_dense1..8, dec_final).  The
+ * widths come from the bias lengths, the latent and state dimensions from dec_dense1_weights / state1_weights.  None of its arrays: present = 0 and
+ * success.  Some but not all, sizes that do not fit together, a width beyond LPCN_DRED_MAX_UNITS, float and int8 GRUs mixed: -1. */
+static int parse_dred_dense(const blob_rec *rec, int n, const char *name, int n_in, lpcn_dred_dense *d)
+{
+    char key[64];
+    snprintf(key, sizeof(key), "%s_bias", name);
+    const blob_rec *b = blob_find(rec, n, key);
+    if (!b || b->size <= 0 || b->size % (int)sizeof(float)) return -1;
+    d->n_out = b->size / (int)sizeof(float);
+    d->b = (const float *)b->data;
+    snprintf(key, sizeof(key), "%s_weights", name);
+    const blob_rec *w = blob_find(rec, n, key);
+    if (!w || w->size <= 0) return -1;
+    if (n_in <= 0) {                                      /* (the first layers: the input dimension is the matrix's) */
+        if (w->size % (d->n_out * (int)sizeof(float))) return -1;
+        n_in = w->size / (d->n_out * (int)sizeof(float));
+    }
+    if ((size_t)w->size != sizeof(float) * (size_t)n_in * d->n_out) return -1;
+    d->n_in = n_in;
+    d->w = (const float *)w->data;
+    return 0;
+}
+
+static int dred_array_name(const char *s)
+{
+    return !strncmp(s, "dec_dense", 9) || !strncmp(s, "dec_final_", 10) || !strncmp(s, "state1_", 7) || !strncmp(s, "state2_", 7) || !strncmp(s, "state3_", 7);
+}
+
+static int parse_dred(lpcn_dred_model *p, const blob_rec *rec, int n)
+{
+    static const char *dense_name[5] = {"dec_dense1", "dec_dense3", "dec_dense5", "dec_dense7", "dec_dense8"};
+    static const char *gru_name[3] = {"dec_dense2", "dec_dense4", "dec_dense6"};
+    static const char *state_name[3] = {"state1", "state2", "state3"};
+    static const int dense_at[5] = {0, 2, 4, 6, 7}, gru_at[3] = {1, 3, 5};
+    memset(p, 0, sizeof(*p));
+    int any = 0;
+    for (int i = 0; i < n; i++) any |= dred_array_name(rec[i].name);
+    if (!any) return 0;
+    int i8 = -1, total = 0, prev = 0;      /* (prev = 0: dec_dense1's input dimension is read from its matrix) */
+    for (int k = 0; k < 8; k++) {
+        int d = -1, g = -1;
+        for (int q = 0; q < 5; q++) if (dense_at[q] == k) d = q;
+        for (int q = 0; q < 3; q++) if (gru_at[q] == k) g = q;
+        if (d >= 0) {
+            if (parse_dred_dense(rec, n, dense_name[d], prev, &p->dense[d])) return -1;
+            p->width[k] = p->dense[d].n_out;
+        } else {
+            lpcn_dred_gru *G = &p->gru[g];
+            int q8 = 0;
+            if (parse_plc_gru(rec, n, gru_name[g], prev, &G->n, &G->nb, &G->w, &G->idx, &G->rec, &G->bias, &q8)) return -1;
+            if (i8 >= 0 && i8 != q8) return -1;
+            i8 = q8;
+            G->n_in = prev;
+            p->width[k] = G->n;
+        }
+        if (p->width[k] > LPCN_DRED_MAX_UNITS) return -1;
+        prev = p->width[k];
+        total += prev;
+    }
+    p->latent_dim = p->dense[0].n_in;
+    for (int k = 0; k < 3; k++) {
+        if (parse_dred_dense(rec, n, state_name[k], k ? p->state_dim : 0, &p->state[k])) return -1;
+        if (!k) p->state_dim = p->state[0].n_in;
+        if (p->state[k].n_out != p->gru[k].n) return -1;
+    }
+    if (p->latent_dim > LPCN_DRED_MAX_UNITS || p->state_dim > LPCN_DRED_MAX_UNITS) return -1;
+    if (parse_dred_dense(rec, n, "dec_final", total, &p->final) || p->final.n_out != LPCN_DRED_OUT) return -1;
+    p->present = i8 ? 2 : 1;
+    return 0;
+}
+
+/* Float decoder arrays beside a float LPCNet model are served; int8 (DOT_PROD) GRU arrays are not. */
+int lpcn_dred_servable(const lpcn_model_host *m)
+{
+    return m->dred.present == 1 && !m->is_int8;
+}
+
 /* int8 recurrent weights of a PLC GRU for plc_pred_i8_kernel: the blob has [3 N / 8 row groups][N / 4 blocks][8 rows][4 cols]
  * (src/vec.h:274-304), so the four weights of (row, block) are one dword already; the kernel walks a row's blocks with one lane per
  * row, so the dwords go block-major, out [N / 4][3 N]: a wave's lanes read consecutive dwords. */
@@ -563,11 +641,11 @@ void lpcn_plc_pack_rec_i8(const signed char *rec, int N, int32_t *out)
 
 int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
 {
-    blob_rec rec[64];
+    blob_rec rec[256];                                   /* (a blob with the PLC network and both DRED halves has about 120 arrays) */
     memset(m, 0, sizeof(*m));
     m->lpc_gamma = 1.0f;
     if (!blob || len <= 0) return -1;
-    int n = blob_walk(blob, len, rec, 64);
+    int n = blob_walk(blob, len, rec, 256);
     if (n <= 0) return -1;
 
 #define NEED_F(field, name, count) \
@@ -615,6 +693,7 @@ int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
 
     if (pack_gru_a(m, 0) || pack_gru_b(m)) { lpcn_model_release(m); return -1; }
     if (parse_plc(&m->plc, rec, n)) { memset(&m->plc, 0, sizeof(m->plc)); m->plc.present = -1; }      /* (the LPCNet model loads as before; lpcnet_batch_plc_enable reports it) */
+    if (parse_dred(&m->dred, rec, n)) { memset(&m->dred, 0, sizeof(m->dred)); m->dred.present = -1; }   /* (likewise: lpcnet_batch_dred_enable reports it) */
     return 0;
 }
 

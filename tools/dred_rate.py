@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Device time of one DRED decode (lpcnet_batch_dred_decode_device) of a large batch, in every form of the kernel.
+
+    python tools/dred_rate.py OUT.json [latents]       (profiles/dred_rate.json when run for the record)
+
+For 256, 2 048 and 8 192 streams, 25 latents each (one second of redundancy) at the exported width of 256: the time of one call (HIP events
+around the enqueue-only device-pointer call, on a caller's stream) with the streams per workgroup pinned to 1, 2, 4, 8 and left to the engine's
+table.  The forms alternate call by call inside one process and one batch, so that every form sees the same clocks; per form two warm-up calls,
+then the median, the extremes and the 10th / 90th percentiles of at least 20 timed calls.  `spread_ms` of a stream count is the widest
+10th-to-90th range among its forms: what a difference between two medians has to beat.  Every form's output is compared with form 1's, bit for
+bit.  Where oracle/_ref exists the tool also times one stream on the reference's AVX2 + FMA float build (liblpcnet_ref_af.so), the decoder
+chained from its layer functions as tests/tools/make_golden_dred.py chains it, on one core: the CPU yardstick.  One process; the tool stops at
+the first failure.  Run it under a time limit:
+    timeout -k 10 600 python tools/dred_rate.py profiles/dred_rate.json
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+
+FORMS = (1, 2, 4, 8, 0)
+STREAMS = (256, 2048, 8192)
+TIMED, WARMUP = 20, 2
+
+
+def cpu_yardstick(blob, state, latents):
+    """one stream's chain on the reference's af build, best of three: ms per latent"""
+    path = os.path.join(ROOT, "oracle", "_ref", "liblpcnet_ref_af.so")
+    if not os.path.exists(path):
+        return None
+    import make_golden_dred as mg
+    dec = mg.RefDecoder(mg.load_ref(path), blob)
+    best = None
+    for _ in range(3):
+        t0 = time.perf_counter()
+        dec.decode(state, latents, latents.shape[0])
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    return dict(build="af (AVX2 + FMA, float)", latents=int(latents.shape[0]), ms_per_latent=1e3 * best / latents.shape[0],
+                note="one stream, one core, through ctypes: two calls per layer")
+
+
+def measure(out_path, n_latents=25):
+    import torch
+    import dred_model as dm
+    from lpcnet_amd import api
+    dev = torch.device("cuda:0")
+    blob = dm.set_blob("w256")
+    info = api.dred_model_info(blob)
+    base_state, base_lat = dm.inputs(info["latent_dim"], 64, n_latents, seed=0x2A7E)
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), widths=info["widths"], latent_dim=info["latent_dim"], latents=n_latents,
+                  timed_calls=TIMED, warmup_calls=WARMUP, note="forms alternate call by call in one process and batch; ms of one decode call by HIP events", streams=[])
+    s = torch.cuda.Stream()
+    for n in STREAMS:
+        b = api.LPCNetBatch(n, blob)
+        b.dred_enable(n_latents)
+        reps = n // 64 + 1
+        d_state = torch.from_numpy(np.ascontiguousarray(np.tile(base_state, (reps, 1))[:n])).to(dev)
+        d_lat = torch.from_numpy(np.ascontiguousarray(np.tile(base_lat, (reps, 1, 1))[:n])).to(dev)
+        d_out = torch.zeros((n, 4 * n_latents, 20), dtype=torch.float32, device=dev)
+        count = np.full(n, n_latents, np.int32)
+        torch.cuda.synchronize()
+        ms = {f: [] for f in FORMS}
+        runs = {}
+        want = None
+        with torch.cuda.stream(s):
+            for k in range(WARMUP + TIMED):
+                for f in FORMS:
+                    runs[f] = b.dred_form(f)
+                    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(s)
+                    b.dred_decode_device(d_state.data_ptr(), d_lat.data_ptr(), count, d_out.data_ptr(), hip_stream=s.cuda_stream)
+                    e.record(s)
+                    e.synchronize()
+                    if k >= WARMUP:
+                        ms[f].append(a.elapsed_time(e))
+                    elif k == 0:
+                        got = d_out.clone()
+                        if want is None:
+                            want = got
+                        elif not torch.equal(got.view(torch.int32), want.view(torch.int32)):
+                            raise SystemExit("form %d differs from form 1 at %d streams" % (f, n))
+        b.dred_form(0)
+        b.close()
+        row = dict(streams=n, table_form=runs[0], forms=[])
+        for f in FORMS:
+            v = np.array(ms[f])
+            row["forms"].append(dict(form=f, streams_per_workgroup=runs[f], median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()),
+                                     p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)),
+                                     us_per_stream_latent=float(1e3 * np.median(v) / (n * n_latents))))
+        pinned = [r for r in row["forms"] if r["form"]]
+        best = min(pinned, key=lambda r: r["median_ms"])
+        row["spread_ms"] = max(r["p90_ms"] - r["p10_ms"] for r in row["forms"])
+        row["best_pinned_form"] = best["form"]
+        row["table_within_spread_of_best"] = bool(row["forms"][-1]["median_ms"] <= best["median_ms"] + row["spread_ms"])
+        row["best_wide_form_gain_over_one_ms"] = float(pinned[0]["median_ms"] - min(r["median_ms"] for r in pinned[1:]))
+        print(json.dumps(row), flush=True)
+        result["streams"].append(row)
+    result["cpu_reference"] = cpu_yardstick(blob, base_state[0], base_lat[0])
+    print(json.dumps(dict(cpu_reference=result["cpu_reference"])), flush=True)
+    with open(out_path, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if not args:
+        raise SystemExit(__doc__)
+    measure(args[0], int(args[1]) if len(args) > 1 else 25)
