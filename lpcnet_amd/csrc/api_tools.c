@@ -97,7 +97,7 @@ int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info)
     if (!info) { set_err("lpcnet_hip_plc_model_info: bad arguments"); return LPCN_E_ARG; }
     if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return LPCN_E_MODEL; }
     info[0] = m.plc.present; info[1] = lpcn_plc_servable(&m);
-    info[2] = m.plc.d1; info[3] = m.plc.g1; info[4] = m.plc.g2; info[5] = m.plc.nb1; info[6] = m.plc.nb2;
+    info[2] = m.plc.dense1.n_out; info[3] = m.plc.gru[0].n; info[4] = m.plc.gru[1].n; info[5] = m.plc.gru[0].nb; info[6] = m.plc.gru[1].nb;
     lpcn_model_release(&m);
     return 0;
 }

@@ -40,17 +40,6 @@ int wait_all(lpcn_batch_dev *b)
     return 0;
 }
 
-template <typename T>
-static int upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
-{
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, count * sizeof(T) ? count * sizeof(T) : 16));
-    e->allocs.push_back(p);
-    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (const T *)p;
-    return 0;
-}
-
 // compiled item counts per lane (sample_variants.h), zero-terminated: fp32 items are 4 VGPRs each, int8 items 1 VGPR
 #define LPCN_LIST_ITEM(n) n,
 static const int variants_f32[] = {LPCN_VARIANTS_F32(LPCN_LIST_ITEM) 0};
@@ -61,65 +50,18 @@ static const int variants_x2w[] = {LPCN_VARIANTS_X2W(LPCN_LIST_ITEM) 0};
 // the smallest compiled variant that holds nw items per lane (0: none does)
 static int round_up_variant(const int *v, int nw) { for (; *v; ++v) if (nw <= *v) return *v; return 0; }
 
-// the PLC network: the blob's arrays as they are, and for each sparse GRU input matrix the first block of every 8-row group plus the
-// blocks' input positions (the index stream {count, pos...} of src/vec.h:347-360 without its counts)
-static int plc_upload_net(lpcn_engine *e, const lpcn_plc_model *p)
+// the PLC network in the blob's flavour: the dense layers as they are, the two GRUs through upload_gru (engine_core.h)
+template <typename W>
+static int plc_upload_net(lpcn_engine *e, const lpcn_plc_model *p, lpcn::PlcNetT<W> &n)
 {
-    lpcn::PlcNet &n = e->plc;
-    n.d1 = p->d1; n.g1 = p->g1; n.g2 = p->g2;
+    n.d1 = p->dense1.n_out;
     int rc = 0;
 #define UPP(field, src, count) if ((rc = upload<float>(e, &n.field, src, (size_t)(count)))) return rc
-    UPP(dense1_w, p->dense1_w, LPCN_PLC_IN * p->d1); UPP(dense1_b, p->dense1_b, p->d1);
-    UPP(gru1_w, p->gru1_w, 32 * (size_t)p->nb1); UPP(gru1_rec, p->gru1_rec, 3 * (size_t)p->g1 * p->g1); UPP(gru1_bias, p->gru1_bias, 6 * p->g1);
-    UPP(gru2_w, p->gru2_w, 32 * (size_t)p->nb2); UPP(gru2_rec, p->gru2_rec, 3 * (size_t)p->g2 * p->g2); UPP(gru2_bias, p->gru2_bias, 6 * p->g2);
-    UPP(out_w, p->out_w, LPCN_NB_FEAT * p->g2); UPP(out_b, p->out_b, LPCN_NB_FEAT);
+    UPP(dense1_w, p->dense1.w, LPCN_PLC_IN * n.d1); UPP(dense1_b, p->dense1.b, n.d1);
+    UPP(out_w, p->out.w, LPCN_NB_FEAT * p->out.n_in); UPP(out_b, p->out.b, LPCN_NB_FEAT);
     UPP(tansig, lpcn_tansig, 201);
 #undef UPP
-    for (int g = 0; g < 2; ++g) {
-        const int *idx = g ? p->gru2_idx : p->gru1_idx;
-        const int groups = 3 * (g ? p->g2 : p->g1) / 8;
-        std::vector<int> start(groups + 1, 0), pos;
-        for (int r = 0; r < groups; ++r) {
-            const int cnt = *idx++;
-            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++);
-            start[r + 1] = (int)pos.size();
-        }
-        if ((rc = upload<int>(e, g ? &n.gru2_start : &n.gru1_start, start.data(), start.size()))) return rc;
-        if ((rc = upload<int>(e, g ? &n.gru2_pos : &n.gru1_pos, pos.data(), pos.size()))) return rc;
-    }
-    return 0;
-}
-
-// the int8 PLC network (plc_pred_i8_kernel): the float arrays as they are (`bias` -- the generic-C build never reads `subias`), the GRU input
-// blocks as the blob has them -- [block][8 rows][4 cols] int8 is one dword per (row, block) already -- with the row groups' first blocks and the
-// blocks' input dwords, and the recurrent weights block-major (model_pack.c: lpcn_plc_pack_rec_i8)
-static int plc_upload_net_i8(lpcn_engine *e, const lpcn_plc_model *p)
-{
-    lpcn::PlcNetQ &n = e->plcq;
-    n.d1 = e->plc.d1 = p->d1; n.g1 = e->plc.g1 = p->g1; n.g2 = e->plc.g2 = p->g2;
-    int rc = 0;
-#define UPP(field, src, count) if ((rc = upload<float>(e, &n.field, src, (size_t)(count)))) return rc
-    UPP(dense1_w, p->dense1_w, LPCN_PLC_IN * p->d1); UPP(dense1_b, p->dense1_b, p->d1);
-    UPP(gru1_bias, p->gru1_bias, 6 * p->g1); UPP(gru2_bias, p->gru2_bias, 6 * p->g2);
-    UPP(out_w, p->out_w, LPCN_NB_FEAT * p->g2); UPP(out_b, p->out_b, LPCN_NB_FEAT);
-    UPP(tansig, lpcn_tansig, 201);
-#undef UPP
-    for (int g = 0; g < 2; ++g) {
-        const int *idx = g ? p->gru2_idx : p->gru1_idx;
-        const int N = g ? p->g2 : p->g1, nb = g ? p->nb2 : p->nb1, groups = 3 * N / 8;
-        std::vector<int> start(groups + 1, 0), pos;
-        for (int r = 0; r < groups; ++r) {
-            const int cnt = *idx++;
-            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++ >> 2);
-            start[r + 1] = (int)pos.size();
-        }
-        std::vector<int32_t> rec((size_t)3 * N * N / 4);
-        lpcn_plc_pack_rec_i8((const signed char *)(g ? p->gru2_rec : p->gru1_rec), N, rec.data());
-        if ((rc = upload<int>(e, g ? &n.gru2_w : &n.gru1_w, g ? p->gru2_w : p->gru1_w, (size_t)8 * nb))) return rc;      // (32 bytes per block)
-        if ((rc = upload<int>(e, g ? &n.gru2_rec : &n.gru1_rec, rec.data(), rec.size()))) return rc;
-        if ((rc = upload<int>(e, g ? &n.gru2_start : &n.gru1_start, start.data(), start.size()))) return rc;
-        if ((rc = upload<int>(e, g ? &n.gru2_pos : &n.gru1_pos, pos.data(), pos.size()))) return rc;
-    }
+    for (int g = 0; g < 2; ++g) if ((rc = upload_gru(e, n.gru[g], p->gru[g]))) return rc;
     return 0;
 }
 
@@ -339,7 +281,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     fm.end2end = 0;
     e->plc_present = m->plc.present;
     e->plc_servable = lpcn_plc_servable(m) != 0;
-    if (e->plc_servable && (rc = m->is_int8 ? plc_upload_net_i8(e, &m->plc) : plc_upload_net(e, &m->plc))) return fail(rc);
+    if (e->plc_servable && (rc = m->is_int8 ? plc_upload_net(e, &m->plc, e->plcq) : plc_upload_net(e, &m->plc, e->plc))) return fail(rc);
     if ((rc = dred_engine_init(e, m))) return fail(rc);
     *out = e;
     return 0;

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <memory>
+#include <type_traits>
 #include <vector>
 #include "lpcnet_engine.h"
 #include "sample_kernel.hip.h"
@@ -145,8 +146,8 @@ struct lpcn_engine {
     lpcn::DecodeTables dec{};      // codec path: VQ codebooks + pitch table (set by lpcn_engine_set_codebooks)
     bool has_codebooks = false;
     lpcn::EncodeTables enc{};      // encoder: the same codebooks and their transposed copies, refreshed together
-    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network (float blobs; int8 blobs: its widths only)
-    lpcn::PlcNetQ plcq{};          //   ... an int8 blob's (plc_pred_i8_kernel)
+    lpcn::PlcNet plc{};            // packet-loss concealment: the blob's PLC network, a float blob's (plc_pred_kernel) ...
+    lpcn::PlcNetQ plcq{};          //   ... or an int8 blob's (plc_pred_i8_kernel)
     int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
     bool plc_servable = false;     //   ... and whether it is in the blob's own flavour (lpcn_plc_servable): uploaded only then
     lpcn::DredNet dred{};          // DRED decoder (engine_dred.hip): the blob's decoder on the device, once a batch has enabled it ...
@@ -155,6 +156,51 @@ struct lpcn_engine {
     bool dred_servable = false;    //   ... float arrays beside a float LPCNet model (lpcn_dred_servable)
     std::unique_ptr<DredHostModel> dred_host;     //   ... not uploaded yet
 };
+
+// width of GRU g (0, 1) of the engine's PLC network, read from the net that was uploaded: a stream's network state is four copies of g1 + g2 floats
+inline int plc_units(const lpcn_engine *e, int g) { return e->is_int8 ? e->plcq.gru[g].n : e->plc.gru[g].n; }
+
+// ---- model upload.  A device copy of `count` elements that is freed with the engine
+template <typename T>
+int upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
+{
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, count * sizeof(T) ? count * sizeof(T) : 16));
+    e->allocs.push_back(p);
+    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = (const T *)p;
+    return 0;
+}
+// A GRU-B layer of a frame-rate network (kernel_params.h: GruLayer).  The bias as it is (`bias` -- the generic-C build never reads `subias`); the sparse
+// input matrix's index stream {count, pos...} (src/vec.h:347-360) split into the first block of every 8-row group and the blocks' input positions; the
+// weights per flavour.  W = float: the blob's arrays as they are.  W = int, an int8 layer: one dword per (row, block) -- the input blocks [block][8 rows]
+// [4 cols] are that already, the positions become input dwords, the recurrent weights go block-major (model_pack.c: lpcn_plc_pack_rec_i8)
+template <typename W>
+int upload_gru(lpcn_engine *e, lpcn::GruLayer<W> &o, const lpcn_gru_layer &g)
+{
+    constexpr bool q8 = !std::is_same<W, float>::value;
+    const int groups = 3 * g.n / 8;
+    const int *idx = g.idx;
+    std::vector<int> start(groups + 1, 0), pos;
+    for (int r = 0; r < groups; ++r) {
+        const int cnt = *idx++;
+        for (int k = 0; k < cnt; ++k) pos.push_back(*idx++ >> (q8 ? 2 : 0));
+        start[r + 1] = (int)pos.size();
+    }
+    o.n_in = g.n_in; o.n = g.n;
+    int rc = 0;
+    if ((rc = upload<float>(e, &o.bias, g.bias, 6 * (size_t)g.n)) || (rc = upload<int>(e, &o.start, start.data(), start.size())) ||
+        (rc = upload<int>(e, &o.pos, pos.data(), pos.size()))) return rc;
+    if constexpr (q8) {
+        std::vector<int32_t> rec((size_t)3 * g.n * g.n / 4);
+        lpcn_plc_pack_rec_i8((const signed char *)g.rec, g.n, rec.data());
+        if ((rc = upload<int>(e, &o.w, g.w, (size_t)8 * g.nb))) return rc;      // (32 bytes per block)
+        return upload<int>(e, &o.rec, rec.data(), rec.size());
+    } else {
+        if ((rc = upload<float>(e, &o.w, g.w, 32 * (size_t)g.nb))) return rc;
+        return upload<float>(e, &o.rec, g.rec, 3 * (size_t)g.n * g.n);
+    }
+}
 
 // packet-loss concealment of a batch (lpcn_batch_dev_plc_enable): the control state on the host, the data on the device
 struct lpcn_plc_host {

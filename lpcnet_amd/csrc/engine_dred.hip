@@ -15,12 +15,12 @@ int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     auto h = std::make_unique<DredHostModel>();
     h->m = m->dred;
     lpcn_dred_model &d = h->m;
-    lpcn_dred_dense *dense[9] = {&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final};
+    lpcn_dense_layer *dense[9] = {&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final};
     size_t nf = 0, ni = 0;
     std::vector<size_t> idx_len(3);
-    for (lpcn_dred_dense *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
+    for (lpcn_dense_layer *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
     for (int g = 0; g < 3; ++g) {
-        const lpcn_dred_gru &G = d.gru[g];
+        const lpcn_gru_layer &G = d.gru[g];
         idx_len[g] = (size_t)(3 * G.n / 8) + G.nb;
         nf += 32 * (size_t)G.nb + 3 * (size_t)G.n * G.n + 6 * (size_t)G.n;
         ni += idx_len[g];
@@ -30,9 +30,9 @@ int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     float *fp = h->f.data();
     int *ip = h->i.data();
     auto take = [&](const float *&src, size_t count) { memcpy(fp, src, sizeof(float) * count); src = fp; fp += count; };
-    for (lpcn_dred_dense *q : dense) { take(q->w, (size_t)q->n_in * q->n_out); take(q->b, q->n_out); }
+    for (lpcn_dense_layer *q : dense) { take(q->w, (size_t)q->n_in * q->n_out); take(q->b, q->n_out); }
     for (int g = 0; g < 3; ++g) {
-        lpcn_dred_gru &G = d.gru[g];
+        lpcn_gru_layer &G = d.gru[g];
         take(G.w, 32 * (size_t)G.nb); take(G.rec, 3 * (size_t)G.n * G.n); take(G.bias, 6 * (size_t)G.n);
         memcpy(ip, G.idx, sizeof(int) * idx_len[g]); G.idx = ip; ip += idx_len[g];
     }
@@ -40,19 +40,8 @@ int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     return 0;
 }
 
-template <typename T>
-static int dred_upload(lpcn_engine *e, const T **dst, const void *src, size_t count)
-{
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, count * sizeof(T) ? count * sizeof(T) : 16));
-    e->allocs.push_back(p);          // (freed with the engine)
-    if (count) HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    *dst = (const T *)p;
-    return 0;
-}
-
-// the arrays as they are; for each sparse GRU input matrix the first block of every 8-row group and the blocks' input positions (as the PLC
-// network's); then the block itself, which the kernel reads from device memory
+// the arrays as they are, the GRUs through upload_gru (engine_core.h) like the PLC network's; then the block itself, which the kernel reads from
+// device memory
 static int dred_upload_net(lpcn_engine *e)
 {
     const lpcn_dred_model &d = e->dred_host->m;
@@ -61,34 +50,26 @@ static int dred_upload_net(lpcn_engine *e)
     n.latent_dim = d.latent_dim; n.state_dim = d.state_dim;
     for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + d.width[k];
     n.total = off[8];
-    auto up_dense = [&](const lpcn_dred_dense &s, lpcn::DredStep &o, int x, int out) {
+    auto up_dense = [&](const lpcn_dense_layer &s, lpcn::DredStep &o, int x, int out) {
         o.gru = 0; o.n_in = s.n_in; o.n_out = s.n_out; o.x = x; o.out = out;
-        int r = dred_upload<float>(e, &o.w, s.w, (size_t)s.n_in * s.n_out);
-        return r ? r : dred_upload<float>(e, &o.b, s.b, s.n_out);
+        int r = upload<float>(e, &o.w, s.w, (size_t)s.n_in * s.n_out);
+        return r ? r : upload<float>(e, &o.b, s.b, s.n_out);
     };
     static const int dense_at[5] = {0, 2, 4, 6, 7}, gru_at[3] = {1, 3, 5};
     for (int k = 0; k < 3; ++k) if ((rc = up_dense(d.state[k], n.init[k], -1, off[gru_at[k]]))) return rc;
     for (int k = 0; k < 5; ++k) if ((rc = up_dense(d.dense[k], n.step[dense_at[k]], dense_at[k] ? off[dense_at[k] - 1] : -1, off[dense_at[k]]))) return rc;
     for (int g = 0; g < 3; ++g) {
-        const lpcn_dred_gru &G = d.gru[g];
+        const lpcn_gru_layer &G = d.gru[g];
         lpcn::DredStep &o = n.step[gru_at[g]];
-        o.gru = 1; o.n_in = G.n_in; o.n_out = G.n; o.x = off[gru_at[g] - 1]; o.out = off[gru_at[g]];
+        lpcn::GruLayer<float> L{};
+        if ((rc = upload_gru(e, L, G))) return rc;
+        o.gru = 1; o.n_in = L.n_in; o.n_out = L.n; o.x = off[gru_at[g] - 1]; o.out = off[gru_at[g]];
+        o.w = L.w; o.rec = L.rec; o.b = L.bias; o.start = L.start; o.pos = L.pos;
         n.max_gru = G.n > n.max_gru ? G.n : n.max_gru;
-        const int groups = 3 * G.n / 8;
-        const int *idx = G.idx;
-        std::vector<int> start(groups + 1, 0), pos;
-        for (int r = 0; r < groups; ++r) {
-            const int cnt = *idx++;
-            for (int k = 0; k < cnt; ++k) pos.push_back(*idx++);
-            start[r + 1] = (int)pos.size();
-        }
-        if ((rc = dred_upload<float>(e, &o.w, G.w, 32 * (size_t)G.nb)) || (rc = dred_upload<float>(e, &o.rec, G.rec, 3 * (size_t)G.n * G.n)) ||
-            (rc = dred_upload<float>(e, &o.b, G.bias, 6 * (size_t)G.n)) || (rc = dred_upload<int>(e, &o.start, start.data(), start.size())) ||
-            (rc = dred_upload<int>(e, &o.pos, pos.data(), pos.size()))) return rc;
     }
-    if ((rc = dred_upload<float>(e, &n.final_w, d.final.w, (size_t)n.total * LPCN_DRED_OUT)) || (rc = dred_upload<float>(e, &n.final_b, d.final.b, LPCN_DRED_OUT)) ||
-        (rc = dred_upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
-    if ((rc = dred_upload<lpcn::DredNet>(e, &e->d_dred, &n, 1))) return rc;
+    if ((rc = upload<float>(e, &n.final_w, d.final.w, (size_t)n.total * LPCN_DRED_OUT)) || (rc = upload<float>(e, &n.final_b, d.final.b, LPCN_DRED_OUT)) ||
+        (rc = upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
+    if ((rc = upload<lpcn::DredNet>(e, &e->d_dred, &n, 1))) return rc;
     e->dred = n;
     e->dred_host.reset();
     return 0;

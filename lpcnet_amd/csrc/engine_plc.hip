@@ -251,7 +251,7 @@ static void launch_plc_pred(lpcn_batch_dev *b, hipStream_t st, const int *ctl, i
     if (b->e->is_int8) hipLaunchKernelGGL(lpcn::plc_pred_i8_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plcq, ctl, cnt, b->plc->D, raw_out);
     else hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, cnt, b->plc->D, raw_out);
 }
-static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(b->e->plc.g1 + b->e->plc.g2); }
+static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(plc_units(b->e, 0) + plc_units(b->e, 1)); }
 // lpcnet_plc_reset (src/lpcnet_plc.c:46-60) on streams [first, first + count): the PLC's own fields, the synthesis state, the analysis state
 static int plc_reset_range(lpcn_batch_dev *b, int first, int count)
 {
@@ -495,7 +495,7 @@ extern "C" int lpcn_batch_dev_plc_fec_feed_host(lpcn_batch_dev *b, const float *
 static int plc_state_copy(lpcn_batch_dev *b, int s, lpcn_plc_state_rec *h, bool up)
 {
     lpcn_plc_host *p = b->plc.get();
-    const size_t i = (size_t)s, G = (size_t)(b->e->plc.g1 + b->e->plc.g2);
+    const size_t i = (size_t)s, G = (size_t)(plc_units(b->e, 0) + plc_units(b->e, 1));
     const struct { void *dev, *host; size_t bytes; } fields[] = {
         {p->delta + i, &h->delta, sizeof(int)}, {p->dc + 2 * i, h->dc, sizeof(h->dc)}, {p->q + i * LPCN_PLC_QUEUE, h->q, sizeof(h->q)},
         {p->feat + i * LPCN_NB_FEAT, h->feat, sizeof(h->feat)},
@@ -516,7 +516,7 @@ extern "C" int lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int s, lpcn_plc_s
     NEED_PLC(b);
     if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
     memset(h, 0, sizeof(*h));
-    h->ctl = b->plc->ctl[s]; h->g1 = b->e->plc.g1; h->g2 = b->e->plc.g2;
+    h->ctl = b->plc->ctl[s]; h->g1 = plc_units(b->e, 0); h->g2 = plc_units(b->e, 1);
     return plc_state_copy(b, s, h, false);
 }
 
@@ -524,7 +524,7 @@ extern "C" int lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int s, const lpcn
 {
     NEED_PLC(b);
     if (s < 0 || s >= b->n || !h) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
-    const int g1 = b->e->plc.g1, g2 = b->e->plc.g2;
+    const int g1 = plc_units(b->e, 0), g2 = plc_units(b->e, 1);
     if (h->g1 != g1 || h->g2 != g2) { snprintf(g_err, sizeof(g_err), "PLC state of a %d / %d network on a %d / %d network", h->g1, h->g2, g1, g2); return LPCN_E_ARG; }
     {   // (the planner's own consistency check, on a copy)
         lpcn_plc_ctl c = h->ctl;

@@ -13,7 +13,7 @@ static void each_stream_array(lpcn_batch_dev *b, F fn)
     if (b->d_enc_vq_mem) fn(b->d_enc_vq_mem, (size_t)LPCN_NB_BANDS);
     if (b->d_keep_lpc) { fn(b->d_keep_a, (size_t)LPCN_ROWS_A); fn(b->d_keep_b, (size_t)LPCN_ROWS_B); fn(b->d_keep_lpc, (size_t)LPCN_LPC_ORDER); }
     if (lpcn_plc_host *p = b->plc.get()) {
-        fn(p->q, (size_t)LPCN_PLC_QUEUE); fn(p->feat, (size_t)LPCN_NB_FEAT); fn(p->net, 4 * (size_t)(b->e->plc.g1 + b->e->plc.g2)); fn(p->dc, (size_t)2);
+        fn(p->q, (size_t)LPCN_PLC_QUEUE); fn(p->feat, (size_t)LPCN_NB_FEAT); fn(p->net, 4 * (size_t)(plc_units(b->e, 0) + plc_units(b->e, 1))); fn(p->dc, (size_t)2);
         fn(p->delta, (size_t)1); fn(p->fec, (size_t)LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); fn(p->fbuf, (size_t)LPCN_PLC_FBUF * LPCN_NB_FEAT);
         fn(p->lp, (size_t)LPCN_FRAME_SIZE); fn(p->burg, (size_t)2 * LPCN_NB_BANDS); fn(p->an, (size_t)LPCN_AN_NB_FEATURES);
     }
@@ -76,7 +76,7 @@ extern "C" int lpcn_batch_dev_copy_streams(lpcn_batch_dev *b, const int *src, co
 extern "C" int lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int s, lpcn_batch_dev *to, int d)
 {
     if (!from || !to || from == to || s < 0 || s >= from->n || d < 0 || d >= to->n) { snprintf(g_err, sizeof(g_err), "copy_streams: bad cross-shard pair"); return LPCN_E_ARG; }
-    if ((from->plc != nullptr) != (to->plc != nullptr) || (from->plc && (from->plc->options != to->plc->options || from->e->plc.g1 != to->e->plc.g1 || from->e->plc.g2 != to->e->plc.g2))) {
+    if ((from->plc != nullptr) != (to->plc != nullptr) || (from->plc && (from->plc->options != to->plc->options || plc_units(from->e, 0) != plc_units(to->e, 0) || plc_units(from->e, 1) != plc_units(to->e, 1)))) {
         snprintf(g_err, sizeof(g_err), "copy_streams: the shards' packet-loss concealment differs"); return LPCN_E_MODEL;
     }
     int rc = 0;
@@ -104,7 +104,7 @@ extern "C" int lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int s, lp
     }
     if (lpcn_plc_host *p = from->plc.get()) {
         lpcn_plc_host *q = to->plc.get();
-        const size_t G4 = 4 * (size_t)(from->e->plc.g1 + from->e->plc.g2);
+        const size_t G4 = 4 * (size_t)(plc_units(from->e, 0) + plc_units(from->e, 1));
         add(p->q.p, q->q.p, sizeof(short) * LPCN_PLC_QUEUE); add(p->feat.p, q->feat.p, sizeof(float) * LPCN_NB_FEAT); add(p->net.p, q->net.p, sizeof(float) * G4);
         add(p->dc.p, q->dc.p, sizeof(double) * 2); add(p->delta.p, q->delta.p, sizeof(int)); add(p->fec.p, q->fec.p, sizeof(float) * LPCN_PLC_MAX_FEC * LPCN_NB_FEAT);
         add(p->fbuf.p, q->fbuf.p, sizeof(float) * LPCN_PLC_FBUF * LPCN_NB_FEAT); add(p->lp.p, q->lp.p, sizeof(short) * LPCN_FRAME_SIZE);

@@ -29,17 +29,30 @@ struct EncodeTables {
     const float *cbd_t;                        // [4][18][1024]: quarter q holds entries 1024 q ..
 };
 
-// the PLC network on the device (widths from the blob; the sparse GRU input matrices as the blob has them plus per-row-group starts)
-struct PlcNet {
-    int d1, g1, g2;
+// A GRU-B layer on the device: the blob's arrays plus, for the sparse input matrix, the first block of every 8-row group and the blocks' input positions
+// (the index stream {count, pos...} of src/vec.h:347-360 without its counts).  W = float: blocks [nb][4][8], recurrent [n][3 n], pos = the input position
+// of a block (gru_b, frame_nets.hip.h).  W = int, an int8 (DOT_PROD) layer: one dword holds the four int8 weights of (row, block) -- blocks [nb][8 rows],
+// recurrent block-major [n / 4][3 n] -- and pos = the input DWORD (position / 4) of a block (plc_gru_i8).
+template <typename W>
+struct GruLayer {
+    int n_in, n;
+    const W *w, *rec;
+    const float *bias;                           // [2][3 n]
+    const int *start, *pos;                      // [3 n / 8 + 1], [blocks]
+};
+
+// the PLC network on the device, widths from the blob: dense 57 -> d1 tanh, GRU d1 -> g1, GRU g1 -> g2, dense g2 -> 20 linear.  The dense layers are
+// float in both flavours; PlcNet is a float blob's (plc_pred_kernel), PlcNetQ an int8 blob's (plc_pred_i8_kernel)
+template <typename W>
+struct PlcNetT {
+    int d1;
     const float *dense1_w, *dense1_b;
-    const float *gru1_w, *gru1_rec, *gru1_bias;
-    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input position of a block
-    const float *gru2_w, *gru2_rec, *gru2_bias;
-    const int *gru2_start, *gru2_pos;
+    GruLayer<W> gru[2];
     const float *out_w, *out_b;
     const float *tansig;
 };
+using PlcNet = PlcNetT<float>;
+using PlcNetQ = PlcNetT<int>;
 
 // per-stream PLC data (the fields of LPCNetPLCState that hold samples, features and network state; src/lpcnet_private.h:79-105)
 struct PlcData {
@@ -55,23 +68,9 @@ struct PlcData {
     float *an;           // [n][36]  analysis of the step's frame
 };
 
-// ... of an int8 blob (plc_pred_i8_kernel)
-struct PlcNetQ {
-    int d1, g1, g2;
-    const float *dense1_w, *dense1_b;
-    const int *gru1_w, *gru1_rec;                // [blocks][8 rows] and [g1 / 4][3 g1] dwords: the four int8 weights of (row, block)
-    const float *gru1_bias;
-    const int *gru1_start, *gru1_pos;            // [3 g1 / 8 + 1] first block of a row group, [blocks] input DWORD (position / 4) of a block
-    const int *gru2_w, *gru2_rec;
-    const float *gru2_bias;
-    const int *gru2_start, *gru2_pos;
-    const float *out_w, *out_b;
-    const float *tansig;
-};
-
 // the DRED decoder on the device (dred_decode_kernel), a device-resident block the kernel walks step by step: three dense layers from the initial
 // state to the GRU states, the eight layers of a latent, dec_final.  The blob's arrays as they are, the sparse GRU input matrices with per-row-group
-// starts like the PLC network's.  x / out: where a step reads and writes in the concatenated buffer, in cells of S floats (x < 0: the input vector)
+// starts (GruLayer).  x / out: where a step reads and writes in the concatenated buffer, in cells of S floats (x < 0: the input vector)
 struct DredStep {
     int gru;                         // 0: dense, tanh; 1: GRU (out = its state's segment)
     int n_in, n_out, x, out;

@@ -85,17 +85,17 @@ extern "C" {
 #define LPCN_PLC_BUF_SIZE  (LPCN_FEATURES_DELAY * LPCN_FRAME_SIZE + 80)      /* PLC_BUF_SIZE, src/lpcnet_private.h:77 */
 #define LPCN_PLC_QUEUE     (LPCN_PLC_BUF_SIZE + LPCN_FRAME_SIZE)
 #define LPCN_PLC_FBUF      4        /* MAX_FEATURE_BUFFER_SIZE, src/lpcnet_private.h:26 */
+/* One layer of a frame-rate network as the blob has it (pointers into the blob): what the PLC network and the DRED decoder are built from.  The widths
+ * are read from the bias lengths; `idx` is the index stream {count, pos...} per 8-row group (src/vec.h:347-360), `nb` its 8x4 blocks.  An int8 (DOT_PROD)
+ * GRU has signed char behind `w` and `rec`: blocks [nb][8][4] and [3 n / 8][n / 4][8][4]. */
+typedef struct lpcn_dense_layer { const float *w, *b; int n_in, n_out; } lpcn_dense_layer;                      /* [n_in][n_out], [n_out] */
+typedef struct lpcn_gru_layer { const float *w, *rec, *bias; const int *idx; int n_in, n, nb; } lpcn_gru_layer;  /* blocks [nb][4][8], [n][3 n], [2][3 n] */
 typedef struct lpcn_plc_model {
-    int present;                 /* 0: the blob has no plc_* arrays; 1: float arrays; 2: int8 arrays (DOT_PROD: GRU weights signed char, blocks [8][4]); -1: incomplete or
+    int present;                 /* 0: the blob has no plc_* arrays; 1: float arrays; 2: int8 arrays (DOT_PROD GRUs); -1: incomplete or
                                   * inconsistent arrays.  Served in the blob's own flavour only (lpcn_plc_servable) */
-    int d1, g1, g2;              /* dense1 width, GRU widths */
-    int nb1, nb2;                /* 8x4 blocks of the two GRU input matrices */
-    const float *dense1_w, *dense1_b;            /* [57][d1], [d1] */
-    const float *gru1_w, *gru1_rec, *gru1_bias;  /* blocks [nb1][4][8], [g1][3 g1], [2][3 g1]; present == 2: signed char blocks [nb1][8][4], [3 g1 / 8][g1 / 4][8][4] */
-    const int *gru1_idx;
-    const float *gru2_w, *gru2_rec, *gru2_bias;
-    const int *gru2_idx;
-    const float *out_w, *out_b;                  /* [g2][20], [20] */
+    lpcn_dense_layer dense1;     /* [57][d1], tanh */
+    lpcn_gru_layer gru[2];       /* d1 -> g1, g1 -> g2 */
+    lpcn_dense_layer out;        /* [g2][20], linear */
 } lpcn_plc_model;
 
 /* ---- the DRED decoder of the same blob (DRED_rdovae_decode_all, src/dred_rdovae.c:38-52; src/dred_rdovae_dec.c:37-98): three dense layers that turn the
@@ -105,16 +105,14 @@ typedef struct lpcn_plc_model {
 #define LPCN_DRED_MAX_UNITS 256      /* most units of a layer, and most inputs of the first layers (latent, initial state) */
 #define LPCN_DRED_FRAMES    4        /* frames per latent */
 #define LPCN_DRED_OUT       (LPCN_DRED_FRAMES * LPCN_NB_FEAT)
-typedef struct lpcn_dred_dense { const float *w, *b; int n_in, n_out; } lpcn_dred_dense;                      /* [n_in][n_out], [n_out] */
-typedef struct lpcn_dred_gru { const float *w, *rec, *bias; const int *idx; int n_in, n, nb; } lpcn_dred_gru;  /* blocks [nb][4][8], [n][3 n], [2][3 n] */
 typedef struct lpcn_dred_model {
     int present;                 /* 0: the blob has none of the decoder's arrays; 1: float arrays; 2: int8 GRU arrays (DOT_PROD); -1: incomplete or inconsistent */
     int latent_dim, state_dim;
     int width[8];                /* dec_dense1 .. dec_dense8 */
-    lpcn_dred_dense state[3];    /* state1 .. state3: tanh */
-    lpcn_dred_dense dense[5];    /* dec_dense1, 3, 5, 7, 8: tanh */
-    lpcn_dred_gru gru[3];        /* dec_dense2, 4, 6 */
-    lpcn_dred_dense final;       /* dec_final: [sum of the widths][80], linear */
+    lpcn_dense_layer state[3];    /* state1 .. state3: tanh */
+    lpcn_dense_layer dense[5];    /* dec_dense1, 3, 5, 7, 8: tanh */
+    lpcn_gru_layer gru[3];        /* dec_dense2, 4, 6 */
+    lpcn_dense_layer final;       /* dec_final: [sum of the widths][80], linear */
 } lpcn_dred_model;
 
 typedef struct lpcn_model_host {

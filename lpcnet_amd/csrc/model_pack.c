@@ -494,8 +494,7 @@ static int pack_gru_b(lpcn_model_host *m)
 /* The PLC network of the blob, bound like the reference's init_plc_model binds it (dense_init / gru_init of
  * src/parse_lpcnet_weights.c:124-220 with the names training_tf2/dump_plc.py emits) except that the widths come from the bias
  * lengths.  No plc_* array at all: present = 0 and success.  Some but not all, or sizes that do not fit together: -1 (the caller sets present = -1). */
-static int parse_plc_gru(const blob_rec *rec, int n, const char *name, int n_in, int *units, int *nb, const float **w, const int **idx,
-                         const float **rw, const float **bias, int *is_int8)
+static int parse_gru_layer(const blob_rec *rec, int n, const char *name, int n_in, lpcn_gru_layer *g, int *is_int8)
 {
     char key[64];
     snprintf(key, sizeof(key), "%s_bias", name);
@@ -503,20 +502,20 @@ static int parse_plc_gru(const blob_rec *rec, int n, const char *name, int n_in,
     if (!b || b->size <= 0 || b->size % (6 * 8 * (int)sizeof(float))) return -1;      /* [2][3 N] floats, N a multiple of 8 */
     const int N = b->size / (6 * (int)sizeof(float));
     if (N > LPCN_PLC_MAX_UNITS || (n_in & 3)) return -1;
-    *units = N; *bias = (const float *)b->data;
+    g->n_in = n_in; g->n = N; g->bias = (const float *)b->data;
     snprintf(key, sizeof(key), "%s_subias", name);
     if (!blob_need(rec, n, key, sizeof(float) * 6 * (size_t)N)) return -1;
     snprintf(key, sizeof(key), "%s_weights_idx", name);
-    if (!(*idx = blob_need_idx(rec, n, key, n_in, 3 * N, nb))) return -1;
+    if (!(g->idx = blob_need_idx(rec, n, key, n_in, 3 * N, &g->nb))) return -1;
     snprintf(key, sizeof(key), "%s_weights", name);
     const blob_rec *q = blob_find(rec, n, key);
     if (!q) return -1;
-    if ((size_t)q->size == sizeof(float) * 32 * (size_t)*nb) *is_int8 = 0;
-    else if (q->size == 32 * *nb) *is_int8 = 1;
+    if ((size_t)q->size == sizeof(float) * 32 * (size_t)g->nb) *is_int8 = 0;
+    else if (q->size == 32 * g->nb) *is_int8 = 1;
     else return -1;
-    *w = (const float *)q->data;
+    g->w = (const float *)q->data;
     snprintf(key, sizeof(key), "%s_recurrent_weights", name);
-    if (!(*rw = (const float *)blob_need(rec, n, key, (*is_int8 ? 1 : sizeof(float)) * 3 * (size_t)N * N))) return -1;
+    if (!(g->rec = (const float *)blob_need(rec, n, key, (*is_int8 ? 1 : sizeof(float)) * 3 * (size_t)N * N))) return -1;
     return 0;
 }
 
@@ -528,16 +527,18 @@ static int parse_plc(lpcn_plc_model *p, const blob_rec *rec, int n)
     if (!any) return 0;
     const blob_rec *b1 = blob_find(rec, n, "plc_dense1_bias");
     if (!b1 || b1->size <= 0 || b1->size % (4 * (int)sizeof(float))) return -1;
-    p->d1 = b1->size / (int)sizeof(float);
-    if (p->d1 > LPCN_PLC_MAX_UNITS) return -1;
-    p->dense1_b = (const float *)b1->data;
-    if (!(p->dense1_w = (const float *)blob_need(rec, n, "plc_dense1_weights", sizeof(float) * LPCN_PLC_IN * (size_t)p->d1))) return -1;
+    const int d1 = b1->size / (int)sizeof(float);
+    if (d1 > LPCN_PLC_MAX_UNITS) return -1;
+    p->dense1.n_in = LPCN_PLC_IN; p->dense1.n_out = d1;
+    p->dense1.b = (const float *)b1->data;
+    if (!(p->dense1.w = (const float *)blob_need(rec, n, "plc_dense1_weights", sizeof(float) * LPCN_PLC_IN * (size_t)d1))) return -1;
     int i8a = 0, i8b = 0;
-    if (parse_plc_gru(rec, n, "plc_gru1", p->d1, &p->g1, &p->nb1, &p->gru1_w, &p->gru1_idx, &p->gru1_rec, &p->gru1_bias, &i8a)) return -1;
-    if (parse_plc_gru(rec, n, "plc_gru2", p->g1, &p->g2, &p->nb2, &p->gru2_w, &p->gru2_idx, &p->gru2_rec, &p->gru2_bias, &i8b)) return -1;
+    if (parse_gru_layer(rec, n, "plc_gru1", d1, &p->gru[0], &i8a)) return -1;
+    if (parse_gru_layer(rec, n, "plc_gru2", p->gru[0].n, &p->gru[1], &i8b)) return -1;
     if (i8a != i8b) return -1;
-    if (!(p->out_w = (const float *)blob_need(rec, n, "plc_out_weights", sizeof(float) * LPCN_NB_FEAT * (size_t)p->g2))) return -1;
-    if (!(p->out_b = (const float *)blob_need(rec, n, "plc_out_bias", sizeof(float) * LPCN_NB_FEAT))) return -1;
+    p->out.n_in = p->gru[1].n; p->out.n_out = LPCN_NB_FEAT;
+    if (!(p->out.w = (const float *)blob_need(rec, n, "plc_out_weights", sizeof(float) * LPCN_NB_FEAT * (size_t)p->out.n_in))) return -1;
+    if (!(p->out.b = (const float *)blob_need(rec, n, "plc_out_bias", sizeof(float) * LPCN_NB_FEAT))) return -1;
     p->present = i8a ? 2 : 1;
     return 0;
 }
@@ -552,7 +553,7 @@ int lpcn_plc_servable(const lpcn_model_host *m)
 /* The DRED decoder of the blob, bound by the names write_lpcnet_weights.c:72-75 appends (rdovae_dec_arrays: state1..3, dec_dense1..8, dec_final).  The
  * widths come from the bias lengths, the latent and state dimensions from dec_dense1_weights / state1_weights.  None of its arrays: present = 0 and
  * success.  Some but not all, sizes that do not fit together, a width beyond LPCN_DRED_MAX_UNITS, float and int8 GRUs mixed: -1. */
-static int parse_dred_dense(const blob_rec *rec, int n, const char *name, int n_in, lpcn_dred_dense *d)
+static int parse_dred_dense(const blob_rec *rec, int n, const char *name, int n_in, lpcn_dense_layer *d)
 {
     char key[64];
     snprintf(key, sizeof(key), "%s_bias", name);
@@ -597,13 +598,11 @@ static int parse_dred(lpcn_dred_model *p, const blob_rec *rec, int n)
             if (parse_dred_dense(rec, n, dense_name[d], prev, &p->dense[d])) return -1;
             p->width[k] = p->dense[d].n_out;
         } else {
-            lpcn_dred_gru *G = &p->gru[g];
             int q8 = 0;
-            if (parse_plc_gru(rec, n, gru_name[g], prev, &G->n, &G->nb, &G->w, &G->idx, &G->rec, &G->bias, &q8)) return -1;
+            if (parse_gru_layer(rec, n, gru_name[g], prev, &p->gru[g], &q8)) return -1;
             if (i8 >= 0 && i8 != q8) return -1;
             i8 = q8;
-            G->n_in = prev;
-            p->width[k] = G->n;
+            p->width[k] = p->gru[g].n;
         }
         if (p->width[k] > LPCN_DRED_MAX_UNITS) return -1;
         prev = p->width[k];

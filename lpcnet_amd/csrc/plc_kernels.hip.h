@@ -6,7 +6,7 @@
 //   plc_burg_kernel   DC removal (src/lpcnet_plc.c:196-205) and burg_cepstral_analysis (src/freq.c:156-199) of a received frame
 //   plc_pred_kernel   compute_plc_pred (src/lpcnet_plc.c:135-146) with its input selection (get_fec_or_pred :148-168), the rotation and
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
-//   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs
+//   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs: one body (plc_pred_body), two flavours
 //   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
 //   group_gather_kernel, group_scatter_kernel   everything a compacted group of streams takes in and gives back, in one launch each: the group
 //                     runs through the ordinary frame and sample kernels
@@ -14,6 +14,7 @@
 #pragma once
 #include "spectral.hip.h"
 #include "lpcnet_log10.h"
+#include "frame_nets.hip.h"         // dense, gru_b: the float layers, shared with the DRED decoder
 #include "quant_i8.hip.h"           // quant_s8, QS, QS1: the int8 arithmetic's quantisation and scales
 #include "lpcnet_plc_tables_gen.h"
 #include "plc_burg.h"
@@ -140,128 +141,6 @@ __global__ __launch_bounds__(PLC_BURG_THREADS) void plc_burg_kernel(LpcnFrameMod
     }
 }
 
-// compute_gruB with a zero condition (src/nnet.c:326-372, float build: sparse_sgemv_accum8x4 src/vec.h:347-403, sgemv_accum src/nnet.c:73-86):
-// lane = row, columns in the reference's order.  x [n_in] and hs [N] (the state, replaced) in LDS; zrh / recur [3 N] LDS scratch.
-__device__ __forceinline__ void plc_gru(const int N, const float *W, const int *start, const int *pos, const float *R, const float *bias,
-                                        const float *x, float *hs, float *zrh, float *recur, const float *tansig)
-{
-    const int rows = 3 * N;
-    for (int row = threadIdx.x; row < rows; row += blockDim.x) {
-        float z = bias[row] + 0.f;
-        const int grp = row >> 3, r = row & 7;
-        for (int blk = start[grp]; blk < start[grp + 1]; ++blk) {
-            const float *w = W + (size_t)blk * 32 + r;
-            const float *xp = x + pos[blk];
-            z = z + w[0] * xp[0];
-            z = z + w[8] * xp[1];
-            z = z + w[16] * xp[2];
-            z = z + w[24] * xp[3];
-        }
-        zrh[row] = z;
-        float rc = bias[rows + row];
-        for (int j = 0; j < N; ++j) rc = rc + R[(size_t)j * rows + row] * hs[j];
-        recur[row] = rc;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * N; i += blockDim.x) zrh[i] = lpcn_sigmoid(zrh[i] + recur[i], tansig);
-    __syncthreads();
-    float hn[(LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS];
-#pragma unroll
-    for (int t = 0; t < (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS; ++t) {
-        const int i = threadIdx.x + t * PLC_PRED_THREADS;
-        hn[t] = 0.f;
-        if (i < N) {
-            float hh = zrh[2 * N + i] + recur[2 * N + i] * zrh[N + i];
-            hh = lpcn_tanh(hh, tansig);
-            const float z = zrh[i];
-            hn[t] = z * hs[i] + (1.f - z) * hh;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1) / PLC_PRED_THREADS; ++t) {
-        const int i = threadIdx.x + t * PLC_PRED_THREADS;
-        if (i < N) hs[i] = hn[t];
-    }
-    __syncthreads();
-}
-
-// One workgroup per record.  flags: PLC_F_ROT rotate plc_copy and store plc_net in plc_copy[0]; restore k (1, 2): plc_net = plc_copy[k];
-// PLC_F_COMPUTE run the network on the selected input; PLC_F_KEEP features = its output (FEC input: features = the FEC vector, the
-// output is discarded); PLC_F_ATT features[0] = MAX16(-10, features[0] + a1 - a2).  PLC_F_RAW (the parity seam): the input is
-// [burg36, an20, a1] as given and the output goes to raw_out [n][20].
-__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, const int *ctl, int cnt, PlcData D, float *raw_out)
-{
-    __shared__ float in[LPCN_PLC_IN + 3];
-    __shared__ float d1[LPCN_PLC_MAX_UNITS], h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
-    __shared__ float zrh[3 * LPCN_PLC_MAX_UNITS], recur[3 * LPCN_PLC_MAX_UNITS];
-    __shared__ float out[LPCN_NB_FEAT];
-    if ((int)blockIdx.x >= cnt) return;
-    const int *rec = ctl + (size_t)blockIdx.x * PLC_PRED_REC;
-    const int s = rec[0], flags = rec[1], fec_row = rec[2];
-    const float a1 = __int_as_float(rec[3]), a2 = __int_as_float(rec[4]);
-    const int G = P.g1 + P.g2;
-    float *net = D.net + (size_t)s * 4 * G;
-    const int restore = (flags >> PLC_F_RESTORE_SHIFT) & 3, input = (flags >> PLC_F_INPUT_SHIFT) & 3;
-    for (int t = threadIdx.x; t < G; t += blockDim.x) {
-        float v0 = net[t];
-        if (flags & PLC_F_ROT) {
-            const float v1 = net[G + t], v2 = net[2 * G + t];
-            net[G + t] = v0; net[2 * G + t] = v1; net[3 * G + t] = v2;
-        }
-        if (restore) { v0 = net[(restore + 1) * G + t]; net[t] = v0; }
-        if (t < P.g1) h1[t] = v0; else h2[t - P.g1] = v0;
-    }
-    if (!(flags & PLC_F_COMPUTE)) return;
-    float *feat = D.feat + (size_t)s * LPCN_NB_FEAT;
-    const float *fec = D.fec + ((size_t)s * LPCN_PLC_MAX_FEC + fec_row) * LPCN_NB_FEAT;
-    if (threadIdx.x < LPCN_PLC_IN) {
-        const int j = threadIdx.x;
-        float v = 0.f;
-        if (input >= PLC_IN_BURG && j < 2 * LPCN_NB_BANDS) v = D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j];
-        if (j >= 2 * LPCN_NB_BANDS && j < LPCN_PLC_IN - 1) {
-            if (input == PLC_IN_FEC) v = fec[j - 2 * LPCN_NB_BANDS];
-            if (input == PLC_IN_BURG_FEAT) v = D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS];
-        }
-        if (j == LPCN_PLC_IN - 1) v = input == PLC_IN_FEC ? -1.f : input == PLC_IN_ZEROS ? 0.f : 1.f;
-        if (flags & PLC_F_RAW) v = j < 2 * LPCN_NB_BANDS ? D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j] : j < LPCN_PLC_IN - 1 ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS] : a1;
-        in[j] = v;
-    }
-    __syncthreads();
-    // _lpcnet_compute_dense (src/nnet.c:122-135), tanh
-    for (int i = threadIdx.x; i < P.d1; i += blockDim.x) {
-        float acc = P.dense1_b[i];
-        for (int j = 0; j < LPCN_PLC_IN; ++j) acc = acc + P.dense1_w[(size_t)j * P.d1 + i] * in[j];
-        d1[i] = lpcn_tanh(acc, P.tansig);
-    }
-    __syncthreads();
-    plc_gru(P.g1, P.gru1_w, P.gru1_start, P.gru1_pos, P.gru1_rec, P.gru1_bias, d1, h1, zrh, recur, P.tansig);
-    plc_gru(P.g2, P.gru2_w, P.gru2_start, P.gru2_pos, P.gru2_rec, P.gru2_bias, h1, h2, zrh, recur, P.tansig);
-    if (threadIdx.x < LPCN_NB_FEAT) {
-        const int i = threadIdx.x;
-        float acc = P.out_b[i];
-        for (int j = 0; j < P.g2; ++j) acc = acc + P.out_w[(size_t)j * LPCN_NB_FEAT + i] * h2[j];
-        if (i == LPCN_NB_FEAT - 1) { const float v = acc + .1f; acc = .5f < v ? .5f : v; }      // MIN16(.5f, out[19]+.1f)
-        out[i] = acc;
-    }
-    for (int t = threadIdx.x; t < G; t += blockDim.x) net[t] = t < P.g1 ? h1[t] : h2[t - P.g1];
-    __syncthreads();
-    if (threadIdx.x < LPCN_NB_FEAT) {
-        const int i = threadIdx.x;
-        float v = 0.f;
-        bool write = false;
-        if (input == PLC_IN_FEC) { v = fec[i]; write = true; }
-        else if (flags & PLC_F_KEEP) { v = out[i]; write = true; }
-        if (write && i == 0 && (flags & PLC_F_ATT)) {
-            v = v + a1;
-            v = v - a2;
-            v = -10.f > v ? -10.f : v;
-        }
-        if (write) feat[i] = v;
-        if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = out[i];
-    }
-}
-
 // ---- the int8 (DOT_PROD) PLC network: compute_plc_pred of the reference's generic-C int8 build.  The dense layers are float there too; the GRUs
 // run sparse_sgemv_accum8x4 / sgemv_accum8x4 of src/vec.h:274-339 (USE_SU_BIAS undefined: they start from `bias`): per row out *= 128*127, then for
 // each 8x4 block in list order the exact integer sum of four int8 products is added with ONE rounded float add, then out *= 1/128/127.  The inputs
@@ -272,10 +151,9 @@ constexpr int PLC_Q_UNITS_PER_LANE = (LPCN_PLC_MAX_UNITS + PLC_PRED_THREADS - 1)
 // leaves the lane -- the input product row after row (each row group has its own block list), the recurrent product as three independent add chains
 // on one LDS dword per block.  Units beyond the workgroup size take a second pass (t = 1).  xq [M / 4] and sq [N / 4]: the input and the old state as packed int8, four per dword; hs [N] the
 // state (replaced); nq (may be null) receives the new state quantised, the next layer's input.  All in LDS.
-__device__ __forceinline__ void plc_gru_i8(const int N, const int *W, const int *start, const int *pos, const int *R, const float *bias,
-                                           const int *xq, const int *sq, float *hs, unsigned char *nq, const float *tansig)
+__device__ __forceinline__ void plc_gru_i8(const GruLayer<int> &g, const int *xq, const int *sq, float *hs, unsigned char *nq, const float *tansig)
 {
-    const int rows = 3 * N, nblk = N >> 2;
+    const int N = g.n, rows = 3 * N, nblk = N >> 2;
     float hn[PLC_Q_UNITS_PER_LANE];
 #pragma unroll
     for (int t = 0; t < PLC_Q_UNITS_PER_LANE; ++t) {
@@ -284,18 +162,18 @@ __device__ __forceinline__ void plc_gru_i8(const int N, const int *W, const int 
         if (i < N) {
             float zrh[3], rc[3];
 #pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                const int row = g * N + i, grp = row >> 3, r = row & 7;
-                float a = bias[row] + 0.f;
+            for (int k = 0; k < 3; ++k) {
+                const int row = k * N + i, grp = row >> 3, r = row & 7;
+                float a = g.bias[row] + 0.f;
                 a = a * QS;
-                for (int blk = start[grp]; blk < start[grp + 1]; ++blk)
-                    a = a + (float)__builtin_amdgcn_sdot4(W[(size_t)blk * 8 + r], xq[pos[blk]], 0, false);
-                zrh[g] = a * QS1;
-                rc[g] = bias[rows + row] * QS;
+                for (int blk = g.start[grp]; blk < g.start[grp + 1]; ++blk)
+                    a = a + (float)__builtin_amdgcn_sdot4(g.w[(size_t)blk * 8 + r], xq[g.pos[blk]], 0, false);
+                zrh[k] = a * QS1;
+                rc[k] = g.bias[rows + row] * QS;
             }
             for (int j = 0; j < nblk; ++j) {
                 const int x = sq[j];
-                const int *w = R + (size_t)j * rows + i;
+                const int *w = g.rec + (size_t)j * rows + i;
                 rc[0] = rc[0] + (float)__builtin_amdgcn_sdot4(w[0], x, 0, false);
                 rc[1] = rc[1] + (float)__builtin_amdgcn_sdot4(w[N], x, 0, false);
                 rc[2] = rc[2] + (float)__builtin_amdgcn_sdot4(w[2 * N], x, 0, false);
@@ -319,19 +197,55 @@ __device__ __forceinline__ void plc_gru_i8(const int N, const int *W, const int 
     __syncthreads();
 }
 
-// plc_pred_kernel for an int8 PLC network: the same records, flags and per-stream data (the network state is float in both builds); only the two
-// GRUs differ.  The control parts repeat plc_pred_kernel's, which stays as it is.
-__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P, const int *ctl, int cnt, PlcData D, float *raw_out)
+// What the two flavours of the predictor do differently: the LDS block (the 57 inputs, both GRU states as floats and the 20 outputs in either; then
+// whatever the GRUs read and scratch), how a restored state value and a dense1 output are staged for the GRUs, and the two GRU calls.
+struct PlcFloat {
+    using Net = PlcNet;
+    struct alignas(16) Lds {
+        float in[LPCN_PLC_IN + 3];
+        float d1[LPCN_PLC_MAX_UNITS], h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
+        float zrh[3 * LPCN_PLC_MAX_UNITS], recur[3 * LPCN_PLC_MAX_UNITS];
+        float out[LPCN_NB_FEAT];
+    };
+    static __device__ __forceinline__ void stage_state(Lds &, int, int, float) {}      // (the float state is all the GRUs read)
+    static __device__ __forceinline__ void stage_dense1(Lds &L, int i, float v) { L.d1[i] = v; }
+    static __device__ __forceinline__ void grus(const Net &P, Lds &L)
+    {
+        gru_b<1, PLC_PRED_THREADS, false>(P.gru[0], L.d1, L.h1, L.zrh, L.recur, P.tansig, nullptr);
+        gru_b<1, PLC_PRED_THREADS, false>(P.gru[1], L.h1, L.h2, L.zrh, L.recur, P.tansig, nullptr);
+    }
+};
+struct PlcInt8 {
+    using Net = PlcNetQ;
+    struct alignas(16) Lds {
+        float h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
+        int xq[LPCN_PLC_MAX_UNITS / 4], sq[2][LPCN_PLC_MAX_UNITS / 4];      // a layer's input, the two old states: packed int8
+        float in[LPCN_PLC_IN + 3];
+        float out[LPCN_NB_FEAT];
+    };
+    static __device__ __forceinline__ void stage_state(Lds &L, int layer, int i, float v) { ((unsigned char *)L.sq[layer])[i] = (unsigned char)quant_s8(v); }
+    static __device__ __forceinline__ void stage_dense1(Lds &L, int i, float v) { ((unsigned char *)L.xq)[i] = (unsigned char)quant_s8(v); }      // (read as GRU 1's quantised input only)
+    static __device__ __forceinline__ void grus(const Net &P, Lds &L)
+    {
+        plc_gru_i8(P.gru[0], L.xq, L.sq[0], L.h1, (unsigned char *)L.xq, P.tansig);
+        plc_gru_i8(P.gru[1], L.xq, L.sq[1], L.h2, nullptr, P.tansig);
+    }
+};
+
+// One workgroup per record.  flags: PLC_F_ROT rotate plc_copy and store plc_net in plc_copy[0]; restore k (1, 2): plc_net = plc_copy[k];
+// PLC_F_COMPUTE run the network on the selected input; PLC_F_KEEP features = its output (FEC input: features = the FEC vector, the
+// output is discarded); PLC_F_ATT features[0] = MAX16(-10, features[0] + a1 - a2).  PLC_F_RAW (the parity seam): the input is
+// [burg36, an20, a1] as given and the output goes to raw_out [n][20].  The records, flags and per-stream data are the same for both flavours (the
+// network state is float in both builds), and so is everything here but the GRUs.
+template <typename F>
+__device__ __forceinline__ void plc_pred_body(const typename F::Net &P, const int *ctl, int cnt, const PlcData &D, float *raw_out)
 {
-    __shared__ float in[LPCN_PLC_IN + 3];
-    __shared__ float h1[LPCN_PLC_MAX_UNITS], h2[LPCN_PLC_MAX_UNITS];
-    __shared__ int xq[LPCN_PLC_MAX_UNITS / 4], s1q[LPCN_PLC_MAX_UNITS / 4], s2q[LPCN_PLC_MAX_UNITS / 4];      // a layer's input, the two old states: packed int8
-    __shared__ float out[LPCN_NB_FEAT];
+    __shared__ typename F::Lds L;
     if ((int)blockIdx.x >= cnt) return;
     const int *rec = ctl + (size_t)blockIdx.x * PLC_PRED_REC;
     const int s = rec[0], flags = rec[1], fec_row = rec[2];
     const float a1 = __int_as_float(rec[3]), a2 = __int_as_float(rec[4]);
-    const int G = P.g1 + P.g2;
+    const int g1 = P.gru[0].n, g2 = P.gru[1].n, G = g1 + g2;
     float *net = D.net + (size_t)s * 4 * G;
     const int restore = (flags >> PLC_F_RESTORE_SHIFT) & 3, input = (flags >> PLC_F_INPUT_SHIFT) & 3;
     for (int t = threadIdx.x; t < G; t += blockDim.x) {
@@ -341,8 +255,8 @@ __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P
             net[G + t] = v0; net[2 * G + t] = v1; net[3 * G + t] = v2;
         }
         if (restore) { v0 = net[(restore + 1) * G + t]; net[t] = v0; }
-        if (t < P.g1) { h1[t] = v0; ((unsigned char *)s1q)[t] = (unsigned char)quant_s8(v0); }
-        else { h2[t - P.g1] = v0; ((unsigned char *)s2q)[t - P.g1] = (unsigned char)quant_s8(v0); }
+        if (t < g1) { L.h1[t] = v0; F::stage_state(L, 0, t, v0); }
+        else { L.h2[t - g1] = v0; F::stage_state(L, 1, t - g1, v0); }
     }
     if (!(flags & PLC_F_COMPUTE)) return;
     float *feat = D.feat + (size_t)s * LPCN_NB_FEAT;
@@ -357,41 +271,45 @@ __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P
         }
         if (j == LPCN_PLC_IN - 1) v = input == PLC_IN_FEC ? -1.f : input == PLC_IN_ZEROS ? 0.f : 1.f;
         if (flags & PLC_F_RAW) v = j < 2 * LPCN_NB_BANDS ? D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j] : j < LPCN_PLC_IN - 1 ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS] : a1;
-        in[j] = v;
+        L.in[j] = v;
     }
     __syncthreads();
-    // _lpcnet_compute_dense (src/nnet.c:122-135), tanh: float in both builds; its output is read as GRU 1's quantised input only
-    for (int i = threadIdx.x; i < P.d1; i += blockDim.x) {
-        float acc = P.dense1_b[i];
-        for (int j = 0; j < LPCN_PLC_IN; ++j) acc = acc + P.dense1_w[(size_t)j * P.d1 + i] * in[j];
-        ((unsigned char *)xq)[i] = (unsigned char)quant_s8(lpcn_tanh(acc, P.tansig));
-    }
+    // (dense1's 57 columns by three, 19 rounds and no remainder loop: by four, or rolled, the int8 step measures slower -- EXPERIMENTS.md)
+    dense<1, 1, PLC_PRED_THREADS, 3>(LPCN_PLC_IN, P.d1, P.dense1_w, P.dense1_b, L.in, [&](int i, int, const float (&acc)[1]) { F::stage_dense1(L, i, lpcn_tanh(acc[0], P.tansig)); });
     __syncthreads();
-    plc_gru_i8(P.g1, P.gru1_w, P.gru1_start, P.gru1_pos, P.gru1_rec, P.gru1_bias, xq, s1q, h1, (unsigned char *)xq, P.tansig);
-    plc_gru_i8(P.g2, P.gru2_w, P.gru2_start, P.gru2_pos, P.gru2_rec, P.gru2_bias, xq, s2q, h2, nullptr, P.tansig);
-    if (threadIdx.x < LPCN_NB_FEAT) {
-        const int i = threadIdx.x;
-        float acc = P.out_b[i];
-        for (int j = 0; j < P.g2; ++j) acc = acc + P.out_w[(size_t)j * LPCN_NB_FEAT + i] * h2[j];
+    F::grus(P, L);
+    dense<1, 1, PLC_PRED_THREADS, 4>(g2, LPCN_NB_FEAT, P.out_w, P.out_b, L.h2, [&](int i, int, const float (&sum)[1]) {
+        float acc = sum[0];
         if (i == LPCN_NB_FEAT - 1) { const float v = acc + .1f; acc = .5f < v ? .5f : v; }      // MIN16(.5f, out[19]+.1f)
-        out[i] = acc;
-    }
-    for (int t = threadIdx.x; t < G; t += blockDim.x) net[t] = t < P.g1 ? h1[t] : h2[t - P.g1];
+        L.out[i] = acc;
+    });
+    for (int t = threadIdx.x; t < G; t += blockDim.x) net[t] = t < g1 ? L.h1[t] : L.h2[t - g1];
     __syncthreads();
     if (threadIdx.x < LPCN_NB_FEAT) {
         const int i = threadIdx.x;
         float v = 0.f;
         bool write = false;
         if (input == PLC_IN_FEC) { v = fec[i]; write = true; }
-        else if (flags & PLC_F_KEEP) { v = out[i]; write = true; }
+        else if (flags & PLC_F_KEEP) { v = L.out[i]; write = true; }
         if (write && i == 0 && (flags & PLC_F_ATT)) {
             v = v + a1;
             v = v - a2;
             v = -10.f > v ? -10.f : v;
         }
         if (write) feat[i] = v;
-        if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = out[i];
+        if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = L.out[i];
     }
+}
+
+// the float network: both GRUs are gru_b (frame_nets.hip.h) ...
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    plc_pred_body<PlcFloat>(P, ctl, cnt, D, raw_out);
+}
+// ... and an int8 blob's: plc_gru_i8
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    plc_pred_body<PlcInt8>(P, ctl, cnt, D, raw_out);
 }
 
 // Element-wise per-stream operations.  One workgroup per record {stream, a, b}; pcm [n][160] is the call's frame, gpcm the compacted

@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HEADERS = ["kernel_params.h", "spectral.hip.h", "engine_core.h", "plc_plan.h", "plc_records.h",
-           "frame_kernels.hip.h", "decode_kernel.hip.h", "analysis_kernels.hip.h", "encode_kernels.hip.h", "plc_kernels.hip.h"]
+           "frame_kernels.hip.h", "decode_kernel.hip.h", "analysis_kernels.hip.h", "encode_kernels.hip.h", "plc_kernels.hip.h",
+           "frame_nets.hip.h", "dred_kernels.hip.h", "roster_kernels.hip.h"]
 
 
 @pytest.mark.parametrize("header", HEADERS)
