@@ -85,10 +85,15 @@ LPCNET_EXPORT int lpcnet_batch_decode(LPCNetBatch *b, const unsigned char *packe
  * run in a device kernel; the per-stream VQ memory lives on the device and is cleared by lpcnet_batch_reset */
 /* LPC_GAMMA (bandwidth expansion of the LPC filter, lpc_weighting src/freq.c:299-308) is a compile-time constant of the
  * reference's generated nnet_data.h, not part of the weight blob; models trained with --lpc-gamma != 1 set it after
- * lpcnet_batch_load_model.  gamma in (0, 1], default 1. */
+ * lpcnet_batch_load_model.  gamma in (0, 1], default 1; any other value (NaN included) returns LPCNET_HIP_E_ARG and leaves the batch as it
+ * was.  The value reaches every shard's engine.  It weights the coefficients the synthesis filter CONSUMES (synthesize*, decode*, the PLC's
+ * frame networks); the stored delay line stays unweighted, and analysis and the encoder, which the reference never weights, are unaffected.
+ * lpcnet_batch_load_model builds new engines: a later call of it puts gamma back to 1 (set it again).  Without a model: LPCNET_HIP_E_MODEL. */
 LPCNET_EXPORT int lpcnet_batch_set_lpc_gamma(LPCNetBatch *b, float gamma);
 /* END2END models: the reference's compile-time END2END (src/lpcnet.c:56-80,107-108) -- the LPC filter comes from the
- * first 16 conditioning outputs (reflection coefficients, rc2lpc) instead of the cepstrum; set after lpcnet_batch_load_model */
+ * first 16 conditioning outputs (reflection coefficients, rc2lpc) instead of the cepstrum, weighted by LPC_GAMMA like the cepstral ones and
+ * without the two-frame delay line, which is left alone; set after lpcnet_batch_load_model.  Default off; lpcnet_batch_load_model builds new
+ * engines, so a later call of it switches END2END off again (set it again).  Without a model: LPCNET_HIP_E_MODEL. */
 LPCNET_EXPORT int lpcnet_batch_set_end2end(LPCNetBatch *b, int on);
 /* Arithmetic flavour of the sample loop.  0 = PARITY (default): every product and sum rounded like the reference's
  * generic-C build, results bit-identical to it.  1 = FAST: the arithmetic of the reference's own SIMD builds -- fused

@@ -662,6 +662,8 @@ void orc_get_signal_state(const orc_state *st, float *last_sig, int *last_exc, f
     memcpy(rng4, st->rng, sizeof(st->rng));
 }
 void orc_force_frame_count(orc_state *st, int fc) { st->frame_count = fc; }
+/* the LPC delay line as stored: unweighted, [0] = the newest frame (untouched under END2END) */
+void orc_get_old_lpc(const orc_state *st, float *old_lpc) { memcpy(old_lpc, st->old_lpc, sizeof(st->old_lpc)); }
 
 /* ======================================================================================
  * LPC from cepstrum (100 Hz): src/freq.c:310-320 -> idct :230, lpc_from_bands :275-297

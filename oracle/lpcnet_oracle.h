@@ -65,6 +65,7 @@ void orc_get_frame_products(const orc_state *st, float *lpc, float *cond_a, floa
 void orc_get_signal_state(const orc_state *st, float *last_sig, int *last_exc, float *deemph_mem,
                           int *frame_count, unsigned *rng4);
 void orc_force_frame_count(orc_state *st, int frame_count);
+void orc_get_old_lpc(const orc_state *st, float *old_lpc /*[ORC_FEATURES_DELAY][16], unweighted, [0] = newest*/);
 
 /* layer-level hooks */
 void orc_gru_a_input(const orc_model *m, float *out, const float *cond, int sig, int pred, int exc);

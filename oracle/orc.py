@@ -59,6 +59,8 @@ def lib():
     L.orc_get_signal_state.argtypes = [vp, _f32p, C.POINTER(C.c_int), C.POINTER(C.c_float),
                                        C.POINTER(C.c_int), _u32p]
     L.orc_force_frame_count.argtypes = [vp, C.c_int]
+    L.orc_get_old_lpc.argtypes = [vp, _f32p]
+    L.orc_get_old_lpc.restype = None
     L.orc_gru_a_input.argtypes = [vp, _f32p, _f32p, C.c_int, C.c_int, C.c_int]
     L.orc_sparse_gru_a.argtypes = [vp, _f32p, _f32p]
     L.orc_gru_b.argtypes = [vp, _f32p, _f32p, _f32p]
@@ -162,6 +164,12 @@ class OracleState:
         gb = np.zeros(16, np.float32)
         self.L.orc_get_nnet_state(self.p, c1, c2, ga, gb)
         return c1, c2, ga, gb
+
+    def old_lpc(self):
+        """the LPC delay line as stored, (2, 16): unweighted, row 0 the newest frame"""
+        out = np.zeros((2, 16), np.float32)
+        self.L.orc_get_old_lpc(self.p, out)
+        return out
 
     def signal_state(self):
         ls = np.zeros(16, np.float32)

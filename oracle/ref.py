@@ -18,12 +18,16 @@ _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 
 
+# the variant flavours of oracle/Makefile: name -> (LPC_GAMMA, END2END) the library was compiled with
+VARIANTS = {"gg": (0.9, False), "ge": (1.0, True), "gx": (0.95, True)}
+
+
 def available(flavour="gf") -> bool:
     return os.path.exists(os.path.join(REF_DIR, f"liblpcnet_ref_{flavour}.so"))
 
 
 class RefLib:
-    """One loaded flavour of the compiled reference (gf, gi, af, ai)."""
+    """One loaded flavour of the compiled reference (gf, gi, af, ai, or a variant build: gg, ge, gx)."""
 
     def __init__(self, flavour="gf"):
         path = os.path.join(REF_DIR, f"liblpcnet_ref_{flavour}.so")

@@ -199,6 +199,22 @@ def test_end2end_variant_matches_reference(blob_f32):
     assert not np.array_equal(got, orc.OracleModel(blob_f32).new_state().synthesize(f))
 
 
+@pytest.mark.skipif(not ref.available("gx"), reason="oracle/_ref END2END + gamma flavour not built (needs /root/reference)")
+def test_end2end_with_lpc_gamma_matches_reference(blob_f32):
+    """END2END and LPC_GAMMA 0.95 in one build, the operating point of real END2END models: rc2lpc, then lpc_weighting (src/lpcnet.c:107-118).
+    With gamma 1 (the `ge` test above) the synthetic model's filter is unstable and a quarter of that run's live samples sit at +-32767; this run
+    stays inside the range, which is asserted so that the pin cannot silently become a saturated one."""
+    gamma, e2e = ref.VARIANTS["gx"]
+    assert (gamma, e2e) == (0.95, True)
+    f = synth.make_features(4321, 40)
+    want = ref.RefLib("gx").new_state(blob_f32).synthesize(f)
+    got = orc.OracleModel(blob_f32, lpc_gamma=gamma, end2end=e2e).new_state().synthesize(f)
+    assert np.array_equal(got, want)
+    assert not np.array_equal(got, orc.OracleModel(blob_f32).new_state().synthesize(f))
+    assert not np.array_equal(got, orc.OracleModel(blob_f32, end2end=True).new_state().synthesize(f))
+    assert np.abs(want.astype(np.int32)).max() < 32767 and np.any(want[320:] != 0)
+
+
 def test_fp16_restatement_rounds_like_ieee_binary16():
     """the oracle-side statement of the engine's fp16 dual-FC option rounds to binary16 exactly like IEEE (numpy float16):
     normals, subnormals, ties, overflow"""
