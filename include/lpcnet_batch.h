@@ -360,11 +360,20 @@ LPCNET_EXPORT const char *lpcnet_batch_last_error(void);
 
 /* Parity seams used by the test-suite (SURVEY.md §7 hard part 9): the two halves of the path alone.
  *   tail:   sample loop only, frame products given: cond_a [n][T][1152], cond_b [n][T][48], lpc [n][T][16]
- *   frames: frame network + LPC only, products returned in the same layouts (any may be NULL) */
+ *   frames: frame network + LPC only, products returned in the same layouts (any may be NULL)
+ *   decode: the packet unpacker only (decode_packet + the double interpolation), launched as lpcnet_batch_decode launches it: packets
+ *           [n][n_packets][8] -> features [n][4 n_packets][20] (the row stride is fixed at 20: cepstrum [0..17], pitch [18], correlation [19]).
+ *           Advances the decoder's VQ memory and nothing else: the synthesis state, the kept frame products and whether they exist stay as they
+ *           were.  LPCNET_HIP_E_ARG for n_packets <= 0 or a NULL pointer, LPCNET_HIP_E_MODEL without a model or without codebooks. */
 LPCNET_EXPORT int lpcnet_batch_run_tail(LPCNetBatch *b, const float *cond_a, const float *cond_b, const float *lpc,
                                         short *pcm, int n_frames, int preload);
 LPCNET_EXPORT int lpcnet_batch_run_frames(LPCNetBatch *b, const float *features, int feat_stride,
                                           float *cond_a, float *cond_b, float *lpc, int n_frames);
+LPCNET_EXPORT int lpcnet_batch_run_decode(LPCNetBatch *b, const unsigned char *packets, float *features, int n_packets);
+/* tools: the single-stream unpacker on the host (what lpcnet_decode runs before it synthesises; no device work): one 8-byte packet and the
+ * stream's VQ memory [18] (in and out) -> features [4][36] with the installed codebooks.  LPCNET_HIP_E_ARG for a NULL pointer,
+ * LPCNET_HIP_E_MODEL without codebooks. */
+LPCNET_EXPORT int lpcnet_hip_packet_features(const unsigned char *buf8, float *vq_mem18, float *features4x36);
 /* tools: GRU-A row dealing of a blob (out[65]: items per lane, then per wave bound[4] + candidate-only flags[3], then
  * per wave the number of early head items of slot 0) */
 LPCNET_EXPORT int lpcnet_hip_model_layout(const unsigned char *data, int len, int *out);
@@ -389,7 +398,7 @@ LPCNET_EXPORT int lpcnet_hip_quant_sweep_device(unsigned long long *out3);
  *   LPCNET_HIP_E_ARG and no shard has changed.  get_active returns the number of shards, active_streams the sum of the counts.
  * Which calls follow the prefix: every call that ADVANCES streams acts on the active streams only -- the host-pointer, device-pointer and _shard
  *   forms of synthesize, synthesize_preload, synthesize_step, decode, analyze(_float), encode, compute_features, plc_step and plc_fec_feed, and
- *   the parity seams run_tail / run_frames / plc_burg / plc_pred.  Array layouts do not change: host arrays stay [n_streams][...], a shard's device
+ *   the parity seams run_tail / run_frames / run_decode / plc_burg / plc_pred.  Array layouts do not change: host arrays stay [n_streams][...], a shard's device
  *   arrays [count_k][...]; the rows of inactive streams are neither read nor written, and every byte of an inactive stream's states stays as it
  *   was (synthesis, decoder VQ, analysis, encoder VQ and PLC states, the PLC's control state, the kept frame products and whether they exist).
  *   lost[s], clear[s], skip[s] and mode[s] / n_samples[s] / preload[s] of an inactive stream are ignored; dropped[s] is written 0; a non-zero

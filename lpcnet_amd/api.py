@@ -238,6 +238,8 @@ def load_library():
     L.lpcnet_batch_last_error.restype = C.c_char_p
     L.lpcnet_batch_run_tail.argtypes = [vp, _f32p, _f32p, _f32p, _i16p, C.c_int, C.c_int]
     L.lpcnet_batch_run_frames.argtypes = [vp, _f32p, C.c_int, vp, vp, vp, C.c_int]
+    L.lpcnet_batch_run_decode.argtypes = [vp, _u8p, _f32p, C.c_int]
+    L.lpcnet_hip_packet_features.argtypes = [_u8p, _f32p, _f32p]
     L.lpcnet_batch_state_size.restype = C.c_int
     L.lpcnet_batch_get_raw_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_raw_state.argtypes = [vp, C.c_int, vp]
@@ -277,6 +279,16 @@ def dred_model_info(blob: bytes):
         raise LPCNetError("dred_model_info: " + last_error())
     v = list(info)
     return dict(present=v[0], servable=v[1], latent_dim=v[2], state_dim=v[3], widths=v[4:12])
+
+
+def packet_features(packet: np.ndarray, vq_mem: np.ndarray) -> np.ndarray:
+    """Host-only: lpcnet_decode's unpacker on one 8-byte packet; vq_mem (18,) float32 advances in place; returns features (4, 36)."""
+    assert vq_mem.dtype == np.float32 and vq_mem.shape == (18,) and vq_mem.flags.c_contiguous
+    feat = np.zeros((4, NB_TOTAL_FEATURES), np.float32)
+    rc = load_library().lpcnet_hip_packet_features(np.ascontiguousarray(packet, np.uint8).reshape(8), vq_mem, feat.reshape(-1))
+    if rc:
+        raise LPCNetError("packet_features failed (%d): %s" % (rc, last_error()))
+    return feat
 
 
 def x3_image_info(blob: bytes):
@@ -856,6 +868,16 @@ class LPCNetBatch:
         self._chk(self.L.lpcnet_batch_run_frames(self.p, np.ascontiguousarray(features, np.float32).reshape(-1), stride,
                                                  ca.ctypes.data, cb.ctypes.data, lpc.ctypes.data, T), "run_frames")
         return ca, cb, lpc
+
+    def run_decode(self, packets: np.ndarray, out: np.ndarray | None = None) -> np.ndarray:
+        """parity seam: the packet unpacker alone, packets (n, P, 8) uint8 -> features (n, 4P, 20) float32; only the decoder's VQ memory advances.
+        `out` (C-contiguous float32, at least n * 4P * 20 floats) receives the rows instead of a fresh array: the rows of inactive streams stay"""
+        n, P, _ = packets.shape
+        assert n == self.n
+        feat = np.zeros((n, 4 * P, NB_FEATURES), np.float32) if out is None else out
+        assert feat.dtype == np.float32 and feat.flags.c_contiguous and feat.size >= n * 4 * P * NB_FEATURES
+        self._chk(self.L.lpcnet_batch_run_decode(self.p, np.ascontiguousarray(packets, np.uint8).reshape(-1), feat.reshape(-1), P), "run_decode")
+        return feat
 
     def get_state(self, stream: int) -> StreamState:
         st = StreamState()

@@ -670,6 +670,17 @@ int lpcnet_batch_run_frames(LPCNetBatch *b, const float *features, int feat_stri
                                               cond_b ? cond_b + at.first * per * LPCN_ROWS_B : NULL, lpc ? lpc + at.first * per * LPCN_LPC_ORDER : NULL, n_frames));
 }
 
+/* the unpacker alone: packets [n][n_packets][8] -> features [n][4 n_packets][20]; only the decoder's VQ memory advances */
+int lpcnet_batch_run_decode(LPCNetBatch *b, const unsigned char *packets, float *features, int n_packets)
+{
+    NEED_MODEL(b);
+    if (n_packets <= 0 || !packets || !features) { set_err("lpcnet_batch_run_decode: bad arguments"); return LPCN_E_ARG; }
+    const int rc = batch_codebooks(b);
+    if (rc) return rc;
+    const size_t per = (size_t)n_packets;               /* (per stream: packets) */
+    EACH_SHARD(lpcn_batch_dev_run_decode_host(s->dev, packets + at.first * per * 8, features + at.first * per * 4 * LPCN_NB_FEAT, n_packets));
+}
+
 int lpcnet_batch_state_size(void) { return (int)sizeof(lpcn_stream_state); }
 int lpcnet_batch_get_raw_state(LPCNetBatch *b, int stream, void *out)
 {

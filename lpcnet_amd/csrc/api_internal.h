@@ -77,6 +77,9 @@ unsigned char *read_file(const char *path, long *len);
 const float *const *codebooks_rdlock(int *version);
 void codebooks_unlock(void);
 
+/* lpcnet_decode's unpacker (api_stream.c): one packet and the stream's VQ memory -> 4 feature vectors; -1 when cb[0] is NULL */
+int packet_to_features(const float *const *cb, float feat[4][NB_TOTAL_FEATURES], float *vq_mem, const unsigned char *buf);
+
 /* device of the single-stream API: lpcnet_hip_set_device(), $LPCNET_HIP_DEVICE, else 0 (api_stream.c) */
 int single_stream_device(void);
 #pragma GCC visibility pop

@@ -36,8 +36,8 @@ static void band_interp(float *x, const float *left, const float *right, int mod
         x[i] = mode == 0 ? .5f * (left[i] + right[i]) : (mode == 1 ? left[i] : right[i]);
 }
 
-/* (cb: the codebooks, read-locked by codebooks_rdlock() -- another thread may replace them) */
-static int packet_to_features(const float *const *cb, float feat[4][NB_TOTAL_FEATURES], float *vq_mem, const unsigned char *buf)
+/* (cb: the codebooks, read-locked by codebooks_rdlock() -- another thread may replace them; api_tools.c calls it too) */
+int packet_to_features(const float *const *cb, float feat[4][NB_TOTAL_FEATURES], float *vq_mem, const unsigned char *buf)
 {
     if (!cb[0]) return -1;
     int pos = 0;

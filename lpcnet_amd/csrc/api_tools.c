@@ -51,6 +51,17 @@ int lpcnet_hip_plc_fec_feed_plan(int n, int *ctl, const int *count, const int *s
     return rc;
 }
 
+/* tools (include/lpcnet_batch.h): lpcnet_decode's unpacker alone, on the host, under the codebooks' read lock (no device) */
+int lpcnet_hip_packet_features(const unsigned char *buf8, float *vq_mem18, float *features4x36)
+{
+    if (!buf8 || !vq_mem18 || !features4x36) { set_err("lpcnet_hip_packet_features: bad arguments"); return LPCN_E_ARG; }
+    const float *const *cb = codebooks_rdlock(NULL);
+    const int rc = packet_to_features(cb, (float (*)[NB_TOTAL_FEATURES])features4x36, vq_mem18, buf8);
+    codebooks_unlock();
+    if (rc) { set_err("lpcnet_hip_packet_features: no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    return 0;
+}
+
 /* tools: how GRU-A's rows were dealt to the 8 waves of the sample kernel: out[0] = items per lane, then per wave
  * {bound[0..3], allh[0..2]} (item index where each slot starts / slot holds only candidate rows), then out[57 + wave] =
  * items of slot 0's chains computed one sample ahead (stored end-aligned, [nw - head, nw)) */

@@ -400,6 +400,30 @@ extern "C" int lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char
     return 0;
 }
 
+// Parity seam: the unpacker alone.  decode_kernel launched as decode_impl launches it (stride LPCN_NB_FEAT, two streams per workgroup, the active
+// count), the staging rows copied back: features [active][4 n_packets][20].  Only the decoder's VQ memory advances: no frame network runs, so the
+// synthesis state, the kept frame products and their flag stay (no forget_keep).
+extern "C" int lpcn_batch_dev_run_decode_host(lpcn_batch_dev *b, const unsigned char *packets, float *features, int n_packets)
+{
+    if (n_packets <= 0 || !packets || !features) { snprintf(g_err, sizeof(g_err), "bad decode arguments"); return LPCN_E_ARG; }
+    if (!b->e->has_codebooks) { snprintf(g_err, sizeof(g_err), "no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
+    if (!b->active) return 0;
+    DeviceGuard guard(b->e->device);
+    const size_t nbytes = (size_t)b->active * n_packets * 8, nfeat = (size_t)b->active * n_packets * 4 * LPCN_NB_FEAT;
+    int rc = b->d_packets.reserve(b, nbytes);
+    if (rc) return rc;
+    if ((rc = ensure_staging(b, nfeat, 0))) return rc;
+    hipStream_t st = b->e->stream;
+    if ((rc = order_begin(b, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->d_packets, packets, nbytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(lpcn::decode_kernel, dim3((b->active + 1) / 2), dim3(64), 0, st, b->e->dec, b->d_packets, b->active, n_packets, b->d_vq_mem,
+                       b->d_feat, LPCN_NB_FEAT);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(features, b->d_feat, nfeat * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" int lpcn_batch_dev_run_tail_host(lpcn_batch_dev *b, const float *cond_a, const float *cond_b,
                                             const float *lpc, short *pcm, int n_frames, int preload)
 {

@@ -305,6 +305,8 @@ int  lpcn_engine_set_lpc_gamma(lpcn_engine *e, float gamma);     /* LPC_GAMMA of
 int  lpcn_engine_set_fast(lpcn_engine *e, int on);                /* FAST arithmetic (not bit-exact; default off = PARITY) */
 int  lpcn_batch_dev_decode(lpcn_batch_dev *b, const unsigned char *d_packets, short *d_pcm, int n_packets, void *hip_stream);
 int  lpcn_batch_dev_decode_host(lpcn_batch_dev *b, const unsigned char *packets, short *pcm, int n_packets);
+/* Parity seam: the unpacker alone (host pointers): packets [n][n_packets][8] -> features [n][4 n_packets][20].  Advances the VQ memory only. */
+int  lpcn_batch_dev_run_decode_host(lpcn_batch_dev *b, const unsigned char *packets, float *features, int n_packets);
 
 /* Parity seam (SURVEY.md §7 hard part 9): run only the sample loop with caller-provided frame
  * products (host pointers): cond_a [n][f][1152], cond_b [n][f][48], lpc [n][f][16]. */
