@@ -298,6 +298,53 @@ LPCNET_EXPORT int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams
  * LPCNET_HIP_E_ARG without `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
 LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len, int *info);
 
+/* The DRED encoder on the device, bit-identical to the reference's generic-C float build: per stream s and double frame d < count[s],
+ *   DRED_rdovae_encode_dframe(enc_state[s], model, latents[s][d], initial_state[s][d], features[s][2 d .. 2 d + 1])
+ *                                                                                 (src/dred_rdovae.c:102-105, src/dred_rdovae_enc.c:38-95)
+ * -- the producer of the latents and initial states dred_decode consumes: two consecutive 20-float feature frames (20 ms) become one latent vector
+ * and one initial state.  Quantisation and entropy coding of the latents are not part of it.  One launch per shard encodes every active stream's
+ * double frames of a call.
+ * The encoder comes from the same blob, found by name wherever its arrays stand: enc_dense{1..8}_*, bits_dense_*, gdense{1,2}_*.  Its widths are read
+ * from the bias lengths (each up to 256), the latent dimension from bits_dense_bias, the taps K of the conv1d bits_dense from bits_dense_weights
+ * ([K x sum of the widths][latent], oldest tap first, 1 <= K <= 8), the state dimension from gdense2_bias; enc_dense1 has 2 x 20 inputs.  Float arrays
+ * beside a float LPCNet model are served.
+ * dred_enc_enable uploads the encoder, allocates every stream's state as DRED_rdovae_init_encoder leaves it (zero) -- a later call keeps the states --
+ *   and sizes the calls to up to max_dframes double frames per stream.  int8 (DOT_PROD) encoder arrays, a mix of float and int8 ones, incomplete or
+ *   inconsistent arrays and a blob without any return LPCNET_HIP_E_MODEL with a message; so does every other call below before dred_enc_enable.
+ * dred_encode takes host pointers: features [n][2 max_dframes][stride] with stride >= 20 -- only the first 20 floats of a row are read, so the
+ *   36-float rows of lpcnet_batch_analyze go in as they are --, count [n] (each 0 .. max_dframes), latents [n][max_dframes][latent] and initial_state
+ *   [n][max_dframes][state].  Rows count[s] and beyond of a stream are not written, and a stream with count 0 keeps its state.  It copies in, runs,
+ *   copies out and synchronises (one host thread per shard).
+ * dred_encode_device* takes device pointers and only enqueues on `hip_stream` (NULL = the batch's own) under the ordering rules of
+ *   lpcnet_batch_analyze_device.  `count` is a host array read before the call returns; the launch depends on it, so on a stream that is being
+ *   captured the call returns LPCNET_HIP_E_ARG and enqueues nothing.  With count = NULL every active stream encodes n_dframes double frames: that
+ *   launch depends on nothing on the host and is accepted on a capturing stream (n_dframes is ignored when count is given).
+ * A count outside 0 .. max_dframes, a non-zero count on a stream beyond its shard's active prefix and a stride below 20 return LPCNET_HIP_E_ARG with
+ *   nothing written and no state changed; inactive streams are untouched.  The _shard forms cover that shard's streams.
+ * Per-stream state: the three GRU states and the conv memory of (K - 1) x sum-of-the-widths floats.  lpcnet_batch_reset zeroes it for the streams it
+ *   names, lpcnet_batch_copy_streams carries it.  dred_enc_get_state / _set_state move one stream's state in the reference's member order
+ *   (RDOVAEEncState): dense2_state, dense4_state, dense6_state, then bits_dense_state, the oldest tap first -- info[6] floats.
+ *   lpcnet_batch_set_fast does not change this kernel.
+ * dred_enc_set_form pins the streams one workgroup carries (1, 2, 4, 8; 0 = the engine's table) for tests and tools -- a form whose buffers do not
+ *   fit a workgroup's LDS returns LPCNET_HIP_E_ARG -- and the output bits are the same in every form.  dred_enc_get_form: what a launch over n_streams
+ *   streams runs with.
+ * dred_enc_info: info[7] = {max_dframes, 40, latent dimension, state dimension, K, sum of the widths, floats of one stream's state}. */
+LPCNET_EXPORT int lpcnet_batch_dred_enc_enable(LPCNetBatch *b, int max_dframes);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_info(const LPCNetBatch *b, int *info);
+LPCNET_EXPORT int lpcnet_batch_dred_encode(LPCNetBatch *b, const float *features, int stride, const int *count, float *latents, float *initial_state);
+LPCNET_EXPORT int lpcnet_batch_dred_encode_device(LPCNetBatch *b, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents,
+                                                  float *d_initial_state, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_encode_device_shard(LPCNetBatch *b, int shard, const float *d_features, int stride, const int *count, int n_dframes,
+                                                        float *d_latents, float *d_initial_state, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_get_state(LPCNetBatch *b, int stream, float *out);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_set_state(LPCNetBatch *b, int stream, const float *in);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_set_form(LPCNetBatch *b, int S);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams);
+/* a blob's DRED encoder as the loader sees it, no device: info[15] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or inconsistent),
+ * servable (dred_enc_enable accepts the blob), latent dimension, state dimension, K, width of gdense1, floats of one stream's state, the widths of
+ * enc_dense1 .. enc_dense8}.  Returns like lpcnet_hip_dred_model_info */
+LPCNET_EXPORT int lpcnet_hip_dred_enc_model_info(const unsigned char *data, int len, int *info);
+
 /* State interchange with the single-stream API (PLC-style snapshot / rollback). */
 LPCNET_EXPORT int lpcnet_batch_export_state(LPCNetBatch *b, int stream, LPCNetState *st);
 LPCNET_EXPORT int lpcnet_batch_import_state(LPCNetBatch *b, int stream, const LPCNetState *st);

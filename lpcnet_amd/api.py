@@ -206,6 +206,16 @@ def load_library():
     L.lpcnet_batch_dred_info.argtypes = [vp, C.POINTER(C.c_int)]
     L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
+    L.lpcnet_hip_dred_enc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_enc_enable.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_enc_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_encode.argtypes = [vp, _f32p, C.c_int, vp, _f32p, _f32p]
+    L.lpcnet_batch_dred_encode_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.lpcnet_batch_dred_encode_device_shard.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.lpcnet_batch_dred_enc_get_state.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_dred_enc_set_state.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_dred_enc_set_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_enc_get_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -279,6 +289,16 @@ def dred_model_info(blob: bytes):
         raise LPCNetError("dred_model_info: " + last_error())
     v = list(info)
     return dict(present=v[0], servable=v[1], latent_dim=v[2], state_dim=v[3], widths=v[4:12])
+
+
+def dred_enc_model_info(blob: bytes):
+    """Host-only view of a blob's DRED encoder: dict(present, servable, latent_dim, state_dim, taps, gdense1, state_floats, widths[8]); see
+    include/lpcnet_batch.h."""
+    info = (C.c_int * 15)()
+    if load_library().lpcnet_hip_dred_enc_model_info(blob, len(blob), info) != 0:
+        raise LPCNetError("dred_enc_model_info: " + last_error())
+    v = list(info)
+    return dict(present=v[0], servable=v[1], latent_dim=v[2], state_dim=v[3], taps=v[4], gdense1=v[5], state_floats=v[6], widths=v[7:15])
 
 
 def packet_features(packet: np.ndarray, vq_mem: np.ndarray) -> np.ndarray:
@@ -722,6 +742,67 @@ class LPCNetBatch:
         rc = self.L.lpcnet_batch_dred_decode_packed_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_decode_packed_device_shard(self.p, shard, *args)
         self._chk(rc, "dred_decode_packed")
         return out
+
+    # ---- DRED encoder (DRED_rdovae_encode_dframe per stream and double frame; include/lpcnet_batch.h) ----
+    def dred_enc_enable(self, max_dframes: int):
+        """upload the blob's DRED encoder, allocate every stream's state (zero) and size the calls to up to max_dframes double frames per stream"""
+        self._chk(self.L.lpcnet_batch_dred_enc_enable(self.p, max_dframes), "dred_enc_enable")
+
+    def dred_enc_info(self):
+        """(max_dframes, 40, latent_dim, state_dim, taps, sum of the widths, floats of one stream's state)"""
+        info = (C.c_int * 7)()
+        self._chk(self.L.lpcnet_batch_dred_enc_info(self.p, info), "dred_enc_info")
+        return tuple(info)
+
+    def dred_enc_form(self, S=None, n_streams=None) -> int:
+        """S given: pin the streams a workgroup carries (1, 2, 4, 8 where the buffers fit; 0 = the engine's table).  Returns what a launch over
+        n_streams (default: the batch's) streams runs with; the output bits are the same in every form"""
+        if S is not None:
+            self._chk(self.L.lpcnet_batch_dred_enc_set_form(self.p, S), "dred_enc_form")
+        rc = self.L.lpcnet_batch_dred_enc_get_form(self.p, self.n if n_streams is None else n_streams)
+        if rc < 0:
+            self._chk(rc, "dred_enc_form")
+        return rc
+
+    def dred_encode(self, features: np.ndarray, count, latents: np.ndarray | None = None, initial_state: np.ndarray | None = None):
+        """features (n, 2 * max_dframes, stride >= 20) float32, count [n] -> (latents (n, max_dframes, latent_dim), initial_state (n, max_dframes,
+        state_dim)): stream s's rows [0, count[s]) are DRED_rdovae_encode_dframe's outputs for its double frames in order; its other rows keep what
+        the given arrays held (zeros without them).  Every stream's encoder state advances by its count"""
+        md, _, ld, sd = self.dred_enc_info()[:4]
+        f = np.ascontiguousarray(features, np.float32)
+        count = np.ascontiguousarray(count, np.int32)
+        assert f.ndim == 3 and f.shape[:2] == (self.n, 2 * md) and count.shape == (self.n,)
+        lat = np.zeros((self.n, md, ld), np.float32) if latents is None else latents
+        ini = np.zeros((self.n, md, sd), np.float32) if initial_state is None else initial_state
+        for a, shape in ((lat, (self.n, md, ld)), (ini, (self.n, md, sd))):
+            assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape
+        self._chk(self.L.lpcnet_batch_dred_encode(self.p, f.reshape(-1), f.shape[2], count.ctypes.data, lat.reshape(-1), ini.reshape(-1)), "dred_encode")
+        return lat, ini
+
+    def dred_encode_device(self, d_features_ptr: int, stride: int, count, d_latents_ptr: int, d_initial_ptr: int, hip_stream: int = 0, shard=None):
+        """enqueue only: device pointers laid out as dred_encode's arrays.  count: a host array (of the shard's streams with shard=k), or an int:
+        that many double frames for every active stream -- the form a graph capture accepts"""
+        n = self.n if shard is None else self.shards[shard][1]
+        if isinstance(count, (int, np.integer)):
+            cp, nd = None, int(count)
+        else:
+            count = np.ascontiguousarray(count, np.int32)
+            assert count.shape == (n,)
+            cp, nd = count.ctypes.data, 0
+        args = (d_features_ptr, stride, cp, nd, d_latents_ptr, d_initial_ptr, hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_encode_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_encode_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_encode_device")
+
+    def get_dred_enc_state(self, stream: int) -> np.ndarray:
+        """one stream's encoder state: dense2_state, dense4_state, dense6_state, bits_dense_state (oldest tap first)"""
+        out = np.zeros(self.dred_enc_info()[6], np.float32)
+        self._chk(self.L.lpcnet_batch_dred_enc_get_state(self.p, stream, out), "get_dred_enc_state")
+        return out
+
+    def set_dred_enc_state(self, stream: int, state: np.ndarray):
+        st = np.ascontiguousarray(state, np.float32)
+        assert st.shape == (self.dred_enc_info()[6],)
+        self._chk(self.L.lpcnet_batch_dred_enc_set_state(self.p, stream, st), "set_dred_enc_state")
 
     def get_plc_state(self, stream: int) -> bytes:
         buf = C.create_string_buffer(self.L.lpcnet_batch_plc_state_size())

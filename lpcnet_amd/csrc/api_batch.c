@@ -410,6 +410,72 @@ int lpcnet_batch_dred_decode_packed_device(LPCNetBatch *b, const float *d_state,
     return lpcnet_batch_dred_decode_packed_device_shard(b, 0, d_state, d_latents, count, first, take, d_packed, hip_stream);
 }
 
+/* ---- DRED encoder (DRED_rdovae_encode_dframe per stream and double frame; include/lpcnet_batch.h) ---- */
+#define NEED_DENC_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_dred_enc_enabled((b)->sh[0].dev)) { set_err("the DRED encoder is not enabled on this batch (lpcnet_batch_dred_enc_enable)"); return LPCN_E_MODEL; } } while (0)
+int lpcnet_batch_dred_enc_enable(LPCNetBatch *b, int max_dframes) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_dred_enc_enable(s->dev, max_dframes)); }
+int lpcnet_batch_dred_enc_info(const LPCNetBatch *b, int *info)
+{
+    NEED_DENC_ON(b);
+    if (!info) { set_err("lpcnet_batch_dred_enc_info: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_enc_info(b->sh[0].dev, info));
+}
+int lpcnet_batch_dred_enc_set_form(LPCNetBatch *b, int S) { NEED_DENC_ON(b); EACH_SHARD(lpcn_batch_dev_dred_enc_set_form(s->dev, S)); }
+int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams)
+{
+    NEED_DENC_ON(b);
+    const int rc = lpcn_batch_dev_dred_enc_form(b->sh[0].dev, n_streams);
+    if (rc < 0) take_engine_err();
+    return rc;
+}
+typedef struct { LPCNetBatch *b; const float *features; int stride; const int *count; float *latents, *initial; int info[7]; } denc_args;
+static int denc_shard(void *args, int k)
+{
+    const denc_args *a = (const denc_args *)args;
+    const size_t f = (size_t)a->b->at[k].first, md = (size_t)a->info[0];
+    return lpcn_batch_dev_dred_encode_host(a->b->sh[k].dev, a->features + f * 2 * md * a->stride, a->stride, a->count + f, a->latents + f * md * a->info[2],
+                                           a->initial + f * md * a->info[3]);
+}
+int lpcnet_batch_dred_encode(LPCNetBatch *b, const float *features, int stride, const int *count, float *latents, float *initial_state)
+{
+    NEED_DENC_ON(b);
+    if (!features || !count || !latents || !initial_state) { set_err("lpcnet_batch_dred_encode: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard writes or advances) */
+        const int rc = lpcn_batch_dev_dred_enc_check(b->sh[k].dev, count + b->at[k].first, 0, stride);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    denc_args a = {b, features, stride, count, latents, initial_state, {0}};
+    lpcn_batch_dev_dred_enc_info(b->sh[0].dev, a.info);
+    return run_shards(b, denc_shard, &a);
+}
+int lpcnet_batch_dred_encode_device_shard(LPCNetBatch *b, int shard, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents,
+                                          float *d_initial_state, void *hip_stream)
+{
+    NEED_DENC_ON(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("lpcnet_batch_dred_encode_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_encode(b->sh[shard].dev, d_features, stride, count, n_dframes, d_latents, d_initial_state, hip_stream));
+}
+int lpcnet_batch_dred_encode_device(LPCNetBatch *b, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents, float *d_initial_state,
+                                    void *hip_stream)
+{
+    NEED_DENC_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_encode_device");
+    return lpcnet_batch_dred_encode_device_shard(b, 0, d_features, stride, count, n_dframes, d_latents, d_initial_state, hip_stream);
+}
+int lpcnet_batch_dred_enc_get_state(LPCNetBatch *b, int stream, float *out)
+{
+    NEED_DENC_ON(b);
+    if (!out) { set_err("lpcnet_batch_dred_enc_get_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_dred_enc_get_state(s->dev, i, out));
+}
+int lpcnet_batch_dred_enc_set_state(LPCNetBatch *b, int stream, const float *in)
+{
+    NEED_DENC_ON(b);
+    if (!in) { set_err("lpcnet_batch_dred_enc_set_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_dred_enc_set_state(s->dev, i, in));
+}
+
 /* ---- feature analysis (lpcnet_compute_single_frame_features per stream and frame; include/lpcnet_batch.h) ---- */
 typedef struct { LPCNetBatch *b; const void *pcm; int is_float; float *features; int feat_stride, n_frames; } analyze_args;
 static int analyze_shard(void *args, int k)

@@ -128,6 +128,25 @@ int lpcnet_hip_dred_model_info(const unsigned char *data, int len, int *info)
     return 0;
 }
 
+/* Host-only view of a blob's DRED encoder (no GPU needed): info[0..14] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
+ * inconsistent), servable (lpcnet_batch_dred_enc_enable accepts the blob), latent dimension, state dimension, taps of bits_dense, width of gdense1,
+ * floats of one stream's state, the widths of enc_dense1 .. enc_dense8}.  Returns like lpcnet_hip_dred_model_info. */
+int lpcnet_hip_dred_enc_model_info(const unsigned char *data, int len, int *info)
+{
+    lpcn_model_host m;
+    if (!info) { set_err("lpcnet_hip_dred_enc_model_info: bad arguments"); return LPCN_E_ARG; }
+    if (lpcn_model_parse(&m, data, len) != 0) { set_err("malformed or incomplete DNNw weight blob"); return LPCN_E_MODEL; }
+    const lpcn_dred_enc_model *p = &m.dred_enc;
+    int total = 0;
+    for (int k = 0; k < 8; k++) total += p->width[k];
+    info[0] = p->present; info[1] = lpcn_dred_enc_servable(&m);
+    info[2] = p->latent_dim; info[3] = p->state_dim; info[4] = p->taps; info[5] = p->gdense1;
+    info[6] = p->present > 0 ? p->width[1] + p->width[3] + p->width[5] + (p->taps - 1) * total : 0;
+    for (int k = 0; k < 8; k++) info[7 + k] = p->width[k];
+    lpcn_model_release(&m);
+    return 0;
+}
+
 /* Host-only model check (no GPU needed): parses the blob with the loader's rules, builds the device
  * packings and verifies them.  info[0..5] = {is_int8, blocks GRU-A, blocks GRU-B, items per lane,
  * padded GRU-B blocks, selftest code}.  Returns 0 if the blob is loadable by the engine (float or

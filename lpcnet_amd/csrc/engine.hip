@@ -283,6 +283,7 @@ extern "C" int lpcn_engine_create(lpcn_engine **out, int device, const lpcn_mode
     e->plc_servable = lpcn_plc_servable(m) != 0;
     if (e->plc_servable && (rc = m->is_int8 ? plc_upload_net(e, &m->plc, e->plcq) : plc_upload_net(e, &m->plc, e->plc))) return fail(rc);
     if ((rc = dred_engine_init(e, m))) return fail(rc);
+    if ((rc = denc_engine_init(e, m))) return fail(rc);
     *out = e;
     return 0;
 }
@@ -493,6 +494,10 @@ extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
     { int rcw = wait_all(b); if (rcw) return rcw; }
     HIP_TRY(hipMemcpy(b->d_state + first, h.data(), sizeof(lpcn_stream_state) * count, hipMemcpyHostToDevice));
     if (count) HIP_TRY(hipMemset(b->d_vq_mem + (size_t)first * LPCN_NB_BANDS, 0, sizeof(float) * (size_t)count * LPCN_NB_BANDS));
+    if (count && b->denc) {            // (DRED_rdovae_init_encoder; done before the call returns: the next encode may go to any stream)
+        HIP_TRY(hipMemsetAsync(b->denc->state + (size_t)first * b->denc->rec, 0, sizeof(float) * (size_t)count * b->denc->rec, b->e->stream));
+        HIP_TRY(hipStreamSynchronize(b->e->stream));
+    }
     return 0;
 }
 

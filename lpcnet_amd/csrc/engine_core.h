@@ -122,12 +122,44 @@ struct X2WideHost {
     ~X2WideHost() { if (packed) lpcn_model_release(&mx); }
 };
 
-// The blob's DRED decoder as copied when the engine was created (the blob is the caller's), on the host until a batch asks for it:
-// lpcn_batch_dev_dred_enable uploads it and drops this.  `m` points into the two arenas.
-struct DredHostModel {
-    lpcn_dred_model m{};
+// A host copy of the arrays of a frame-rate network's layers (the blob is the caller's): take() copies every array into the two arenas and points
+// the layer records at the copies
+struct LayerArena {
     std::vector<float> f;
     std::vector<int> i;
+    void take(const std::vector<lpcn_dense_layer *> &dense, lpcn_gru_layer *gru, int n_gru)
+    {
+        size_t nf = 0, ni = 0;
+        std::vector<size_t> idx_len(n_gru);
+        for (lpcn_dense_layer *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
+        for (int g = 0; g < n_gru; ++g) {
+            const lpcn_gru_layer &G = gru[g];
+            idx_len[g] = (size_t)(3 * G.n / 8) + G.nb;
+            nf += 32 * (size_t)G.nb + 3 * (size_t)G.n * G.n + 6 * (size_t)G.n;
+            ni += idx_len[g];
+        }
+        f.resize(nf);
+        i.resize(ni);
+        float *fp = f.data();
+        int *ip = i.data();
+        auto copy = [&](const float *&src, size_t count) { memcpy(fp, src, sizeof(float) * count); src = fp; fp += count; };
+        for (lpcn_dense_layer *q : dense) { copy(q->w, (size_t)q->n_in * q->n_out); copy(q->b, q->n_out); }
+        for (int g = 0; g < n_gru; ++g) {
+            lpcn_gru_layer &G = gru[g];
+            copy(G.w, 32 * (size_t)G.nb); copy(G.rec, 3 * (size_t)G.n * G.n); copy(G.bias, 6 * (size_t)G.n);
+            memcpy(ip, G.idx, sizeof(int) * idx_len[g]); G.idx = ip; ip += idx_len[g];
+        }
+    }
+};
+// The blob's DRED decoder as copied when the engine was created, on the host until a batch asks for it: lpcn_batch_dev_dred_enable uploads it and
+// drops this.  `m` points into the arena.  The encoder likewise (lpcn_batch_dev_dred_enc_enable).
+struct DredHostModel {
+    lpcn_dred_model m{};
+    LayerArena a;
+};
+struct DredEncHostModel {
+    lpcn_dred_enc_model m{};
+    LayerArena a;
 };
 
 struct lpcn_engine {
@@ -155,6 +187,11 @@ struct lpcn_engine {
     int dred_present = 0;          //   ... lpcn_dred_model.present of the blob
     bool dred_servable = false;    //   ... float arrays beside a float LPCNet model (lpcn_dred_servable)
     std::unique_ptr<DredHostModel> dred_host;     //   ... not uploaded yet
+    lpcn::DredEncNet denc{};       // DRED encoder (engine_dred_enc.hip), the same five: the block, its device copy, ...
+    const lpcn::DredEncNet *d_denc = nullptr;
+    int denc_present = 0;          //   ... lpcn_dred_enc_model.present of the blob, lpcn_dred_enc_servable, ...
+    bool denc_servable = false;
+    std::unique_ptr<DredEncHostModel> denc_host;  //   ... not uploaded yet
 };
 
 // width of GRU g (0, 1) of the engine's PLC network, read from the net that was uploaded: a stream's network state is four copies of g1 + g2 floats
@@ -237,6 +274,20 @@ struct lpcn_dred_host {
     PinBuf h_feat;                                  //   ... whose output comes down whole and goes to the caller row by row (rows past a stream's count stay)
 };
 
+// DRED encoding of a batch (lpcn_batch_dev_dred_enc_enable): every stream's state record (rdovae_enc_kernels.hip.h) and the scratch of a call
+struct lpcn_denc_host {
+    int max_dframes = 0, cus = 0;                   // (cus: the device's compute units, for the form table)
+    int form = 0;                                   // streams per workgroup pinned by lpcn_batch_dev_dred_enc_set_form (0: the table's choice)
+    size_t rec = 0;                                 // floats of a stream's record
+    DevBuf<float> state;                            // [n][rec]: GRU states, the conv memory as a ring, the ring's head
+    DevBuf<int> d_cnt;                              // a call's per-stream counts ...
+    PinBuf h_cnt;                                   // ... their pinned source ...
+    Event ev_cnt;                                   // ... and "the previous call's have left it"
+    bool cnt_pending = false;
+    DevBuf<float> d_feat, d_lat, d_init;            // staging of the host-pointer call
+    PinBuf h_out;                                   //   ... whose outputs come down whole and go to the caller row by row (rows past a stream's count stay)
+};
+
 struct lpcn_batch_dev {
     lpcn_engine *e = nullptr;
     int n = 0, max_chunk = 0, S = 0, frame_len = LPCN_FRAME_SIZE;
@@ -296,6 +347,7 @@ struct lpcn_batch_dev {
     bool pairs_pending = false;
     std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
     std::unique_ptr<lpcn_dred_host> dred;         // DRED decoding (lpcn_batch_dev_dred_enable)
+    std::unique_ptr<lpcn_denc_host> denc;         // DRED encoding (lpcn_batch_dev_dred_enc_enable)
     PinBuf h_pin;                      // pinned host staging of the single-stream fast path and the combined pass: each reserves what it lays out
     bool timing = false;
     float ms_sample = 0.f, ms_frame = 0.f;
@@ -357,6 +409,8 @@ int lpcn_launch_frame_kernels(const LpcnFrameModel &M, hipStream_t st, int n, in
 int group_alloc(lpcn_batch_dev *b);
 // engine_dred.hip: the host copy of the blob's DRED decoder, taken when the engine is created
 int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m);
+// engine_dred_enc.hip: the same for the blob's DRED encoder
+int denc_engine_init(lpcn_engine *e, const lpcn_model_host *m);
 // engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)
 int lpcn_launch_analysis_kernels(const LpcnFrameModel &M, hipStream_t st, int n, int n_frames, const void *d_pcm, int is_float,
                                  size_t pcm_stream_stride, lpcn_analysis_state *d_state, float *d_feat, int feat_stride,

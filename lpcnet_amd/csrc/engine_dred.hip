@@ -15,27 +15,7 @@ int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     auto h = std::make_unique<DredHostModel>();
     h->m = m->dred;
     lpcn_dred_model &d = h->m;
-    lpcn_dense_layer *dense[9] = {&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final};
-    size_t nf = 0, ni = 0;
-    std::vector<size_t> idx_len(3);
-    for (lpcn_dense_layer *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
-    for (int g = 0; g < 3; ++g) {
-        const lpcn_gru_layer &G = d.gru[g];
-        idx_len[g] = (size_t)(3 * G.n / 8) + G.nb;
-        nf += 32 * (size_t)G.nb + 3 * (size_t)G.n * G.n + 6 * (size_t)G.n;
-        ni += idx_len[g];
-    }
-    h->f.resize(nf);
-    h->i.resize(ni);
-    float *fp = h->f.data();
-    int *ip = h->i.data();
-    auto take = [&](const float *&src, size_t count) { memcpy(fp, src, sizeof(float) * count); src = fp; fp += count; };
-    for (lpcn_dense_layer *q : dense) { take(q->w, (size_t)q->n_in * q->n_out); take(q->b, q->n_out); }
-    for (int g = 0; g < 3; ++g) {
-        lpcn_gru_layer &G = d.gru[g];
-        take(G.w, 32 * (size_t)G.nb); take(G.rec, 3 * (size_t)G.n * G.n); take(G.bias, 6 * (size_t)G.n);
-        memcpy(ip, G.idx, sizeof(int) * idx_len[g]); G.idx = ip; ip += idx_len[g];
-    }
+    h->a.take({&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final}, d.gru, 3);
     e->dred_host = std::move(h);
     return 0;
 }

@@ -17,6 +17,7 @@ static void each_stream_array(lpcn_batch_dev *b, F fn)
         fn(p->delta, (size_t)1); fn(p->fec, (size_t)LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); fn(p->fbuf, (size_t)LPCN_PLC_FBUF * LPCN_NB_FEAT);
         fn(p->lp, (size_t)LPCN_FRAME_SIZE); fn(p->burg, (size_t)2 * LPCN_NB_BANDS); fn(p->an, (size_t)LPCN_AN_NB_FEATURES);
     }
+    if (lpcn_denc_host *p = b->denc.get()) fn(p->state, p->rec);
 }
 static int roster_table(lpcn_batch_dev *b, lpcn::RosterTable &T)
 {
@@ -85,6 +86,7 @@ extern "C" int lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int s, lp
         if (from->d_an_state && !to->d_an_state && (rc = lpcn_batch_dev_analysis_enable(to, 1))) return rc;
         if (from->d_enc_vq_mem && !to->d_enc_vq_mem && (rc = lpcn_batch_dev_encoder_enable(to, 1))) return rc;
         if (from->d_keep_lpc && !to->d_keep_lpc && (rc = group_alloc(to))) return rc;
+        if (from->denc && !to->denc && (rc = lpcn_batch_dev_dred_enc_enable(to, from->denc->max_dframes))) return rc;
         if ((rc = wait_all(to))) return rc;
     }
     struct Part { const char *src; char *dst; size_t bytes; };
@@ -110,6 +112,7 @@ extern "C" int lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int s, lp
         add(p->fbuf.p, q->fbuf.p, sizeof(float) * LPCN_PLC_FBUF * LPCN_NB_FEAT); add(p->lp.p, q->lp.p, sizeof(short) * LPCN_FRAME_SIZE);
         add(p->burg.p, q->burg.p, sizeof(float) * 2 * LPCN_NB_BANDS); add(p->an.p, q->an.p, sizeof(float) * LPCN_AN_NB_FEATURES);
     }
+    if (to->denc) add(from->denc ? from->denc->state.p : nullptr, to->denc->state.p, sizeof(float) * to->denc->rec);
     char *pin = nullptr;
     {
         DeviceGuard guard(from->e->device);

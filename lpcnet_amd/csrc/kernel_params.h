@@ -84,6 +84,19 @@ struct DredNet {
     const float *tansig;
 };
 
+// the DRED encoder on the device (rdovae_enc_kernel), walked like the decoder's block: the eight layers of a double frame, gdense1 (from the buffer's
+// start to the cells behind it), then the two layers that read no DredStep cell range: bits_dense over the window and gdense2, straight to the outputs.
+// A stream's state record in global memory: the three GRU states (gru_floats, at gru_off[g] of the buffer), the conv memory as a ring of taps - 1
+// slots of `total` floats, and the ring's head (int): the slot of the oldest tap
+struct DredEncNet {
+    int latent_dim, state_dim, max_gru, total, taps, gd1, gru_floats;
+    int gru_off[3], gru_n[3];
+    DredStep step[9];                                // (step[8]: gdense1)
+    const float *bits_w, *bits_b;                    // [taps total][latent], [latent]
+    const float *g2_w, *g2_b;                        // [gd1][state], [state]
+    const float *tansig;
+};
+
 // a compacted group's rows in and out (group_gather_kernel, group_scatter_kernel)
 struct GroupRows {
     const int *map;

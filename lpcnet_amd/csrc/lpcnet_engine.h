@@ -115,6 +115,22 @@ typedef struct lpcn_dred_model {
     lpcn_dense_layer final;       /* dec_final: [sum of the widths][80], linear */
 } lpcn_dred_model;
 
+/* ---- the DRED encoder of the same blob (DRED_rdovae_encode_dframe, src/dred_rdovae.c:102-105; src/dred_rdovae_enc.c:38-95): per double frame (two 20-float
+ * feature frames, 40 inputs) dense 1 -> GRU 2 -> dense 3 -> GRU 4 -> dense 5 -> GRU 6 -> dense 7 -> dense 8, every output appended to one buffer; the
+ * latents are the conv1d bits_dense over the last `taps` buffers (linear), the initial state is gdense2(gdense1(buffer)), both tanh.  The widths are read
+ * from the bias lengths, the taps from bits_dense_weights: [taps * sum of the widths][latent], oldest tap first. */
+#define LPCN_DRED_ENC_IN       (2 * LPCN_NB_FEAT)
+#define LPCN_DRED_ENC_MAX_TAPS 8
+typedef struct lpcn_dred_enc_model {
+    int present;                 /* 0: the blob has none of the encoder's arrays; 1: float arrays; 2: int8 GRU arrays (DOT_PROD); -1: incomplete or inconsistent */
+    int latent_dim, state_dim, taps, gdense1;
+    int width[8];                /* enc_dense1 .. enc_dense8 */
+    lpcn_dense_layer dense[5];    /* enc_dense1, 3, 5, 7, 8: tanh */
+    lpcn_gru_layer gru[3];        /* enc_dense2, 4, 6 */
+    lpcn_dense_layer bits;        /* bits_dense: [taps * sum of the widths][latent], linear */
+    lpcn_dense_layer gdense[2];   /* gdense1: [sum of the widths][gdense1], gdense2: [gdense1][state], tanh */
+} lpcn_dred_enc_model;
+
 typedef struct lpcn_model_host {
     int is_int8;                 /* blob flavour: 0 = float qweights (DISABLE_DOT_PROD), 1 = int8 (DOT_PROD)  */
     int b_dense;                 /* GRU-B input matrix lists every input block for every row group */
@@ -152,6 +168,7 @@ typedef struct lpcn_model_host {
     float   *pk_emb[3];   /* sig/pred/exc tables re-ordered to [256][3 slots][512 threads] */
     lpcn_plc_model plc;   /* the PLC network of the same blob, when it has one (pointers into the blob) */
     lpcn_dred_model dred; /* the DRED decoder of the same blob, when it has one (pointers into the blob) */
+    lpcn_dred_enc_model dred_enc;   /* the DRED encoder of the same blob, when it has one (pointers into the blob) */
 } lpcn_model_host;
 
 /* GRU-A dealt to the twelve waves of sample_kernel_x3 (float blobs).  A wave holds LPCN_X3_NW items per lane: segment 0 -- the HEAD of a candidate
@@ -185,6 +202,7 @@ int  lpcn_x3_image_selftest(const lpcn_model_host *m, const lpcn_x3_image *im); 
 int  lpcn_model_selftest(const lpcn_model_host *m);
 int  lpcn_plc_servable(const lpcn_model_host *m);                           /* 1: the blob's PLC network is in the blob's own flavour (float / int8) */
 int  lpcn_dred_servable(const lpcn_model_host *m);                          /* 1: the blob's DRED decoder is float beside a float LPCNet model */
+int  lpcn_dred_enc_servable(const lpcn_model_host *m);                      /* 1: the blob's DRED encoder is float beside a float LPCNet model */
 void lpcn_plc_pack_rec_i8(const signed char *rec, int N, int32_t *out);     /* int8 recurrent weights of a PLC GRU, one dword per (row, block): out [N / 4][3 N] */
 
 /* ---- per-stream state as the device keeps it (AoS, one record per stream) ------------------ */
@@ -418,6 +436,24 @@ int  lpcn_batch_dev_dred_decode(lpcn_batch_dev *b, const float *d_state, const f
 int  lpcn_batch_dev_dred_decode_packed(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take,
                                        float *d_packed, void *hip_stream);
 int  lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *state, const float *latents, const int *count, float *features);
+
+/* DRED encoder (DRED_rdovae_encode_dframe per stream and double frame, rdovae_enc_kernels.hip.h): one launch encodes every active
+ * stream's double frames of a call.  Per stream the batch keeps the three GRU states and the conv memory: zero when the encoder is enabled, zeroed by
+ * lpcn_batch_dev_reset, carried by the stream copies.  features [n][2 max_dframes][stride] (stride >= 20: the first 20 floats of a row are read),
+ * count [n] (host, 0 .. max_dframes; NULL: n_dframes for every active stream), latents [n][max_dframes][latent_dim], initial [n][max_dframes]
+ * [state_dim]: rows count[s] and beyond of a stream are not written, and a stream with count 0 keeps its state.  The device form only enqueues; with a
+ * count array not on a capturing stream (the launch depends on it). */
+int  lpcn_batch_dev_dred_enc_enable(lpcn_batch_dev *b, int max_dframes);
+int  lpcn_batch_dev_dred_enc_enabled(const lpcn_batch_dev *b);/* max_dframes, 0 before lpcn_batch_dev_dred_enc_enable */
+int  lpcn_batch_dev_dred_enc_info(const lpcn_batch_dev *b, int *info7);        /* {max_dframes, 40, latent, state, taps, sum of the widths, floats of a stream's state} */
+int  lpcn_batch_dev_dred_enc_set_form(lpcn_batch_dev *b, int S);      /* streams per workgroup: 1, 2, 4, 8 where the buffers fit the LDS; 0 = the table's choice */
+int  lpcn_batch_dev_dred_enc_form(const lpcn_batch_dev *b, int n);    /* what a launch over n streams runs with */
+int  lpcn_batch_dev_dred_enc_check(const lpcn_batch_dev *b, const int *count, int n_dframes, int stride);      /* the argument checks alone */
+int  lpcn_batch_dev_dred_encode(lpcn_batch_dev *b, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents, float *d_initial,
+                                void *hip_stream);
+int  lpcn_batch_dev_dred_encode_host(lpcn_batch_dev *b, const float *features, int stride, const int *count, float *latents, float *initial);
+int  lpcn_batch_dev_dred_enc_get_state(lpcn_batch_dev *b, int stream, float *out);      /* dense2_state, dense4_state, dense6_state, bits_dense_state (oldest tap first) */
+int  lpcn_batch_dev_dred_enc_set_state(lpcn_batch_dev *b, int stream, const float *in);
 
 /* Timing of the most recent run: kernel-only milliseconds measured with HIP events on the
  * stream the kernels were launched on (sample kernel, frame kernels). */

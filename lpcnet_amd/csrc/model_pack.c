@@ -626,6 +626,63 @@ int lpcn_dred_servable(const lpcn_model_host *m)
     return m->dred.present == 1 && !m->is_int8;
 }
 
+/* The DRED encoder of the blob, bound by the names of rdovae_enc_arrays (enc_dense1..8, bits_dense, gdense1, gdense2), wherever they stand.  The
+ * widths come from the bias lengths, the latent dimension from bits_dense_bias, the taps from bits_dense_weights / (sum of the widths x latent), the
+ * state dimension from gdense2_bias; enc_dense1 has 2 x 20 inputs.  None of its arrays: present = 0 and success.  Some but not all, sizes that do
+ * not fit together, a width beyond LPCN_DRED_MAX_UNITS, taps outside 1 .. LPCN_DRED_ENC_MAX_TAPS, float and int8 GRUs mixed: -1. */
+static int dred_enc_array_name(const char *s)
+{
+    return !strncmp(s, "enc_dense", 9) || !strncmp(s, "bits_dense_", 11) || !strncmp(s, "gdense1_", 8) || !strncmp(s, "gdense2_", 8);
+}
+
+static int parse_dred_enc(lpcn_dred_enc_model *p, const blob_rec *rec, int n)
+{
+    static const char *dense_name[5] = {"enc_dense1", "enc_dense3", "enc_dense5", "enc_dense7", "enc_dense8"};
+    static const char *gru_name[3] = {"enc_dense2", "enc_dense4", "enc_dense6"};
+    static const int dense_at[5] = {0, 2, 4, 6, 7}, gru_at[3] = {1, 3, 5};
+    memset(p, 0, sizeof(*p));
+    int any = 0;
+    for (int i = 0; i < n; i++) any |= dred_enc_array_name(rec[i].name);
+    if (!any) return 0;
+    int i8 = -1, total = 0, prev = LPCN_DRED_ENC_IN;
+    for (int k = 0; k < 8; k++) {
+        int d = -1, g = -1;
+        for (int q = 0; q < 5; q++) if (dense_at[q] == k) d = q;
+        for (int q = 0; q < 3; q++) if (gru_at[q] == k) g = q;
+        if (d >= 0) {
+            if (parse_dred_dense(rec, n, dense_name[d], prev, &p->dense[d])) return -1;
+            p->width[k] = p->dense[d].n_out;
+        } else {
+            int q8 = 0;
+            if (parse_gru_layer(rec, n, gru_name[g], prev, &p->gru[g], &q8)) return -1;
+            if (i8 >= 0 && i8 != q8) return -1;
+            i8 = q8;
+            p->width[k] = p->gru[g].n;
+        }
+        if (p->width[k] > LPCN_DRED_MAX_UNITS) return -1;
+        prev = p->width[k];
+        total += prev;
+    }
+    if (parse_dred_dense(rec, n, "bits_dense", 0, &p->bits)) return -1;      /* (n_in = 0: the window's length is read from the matrix) */
+    p->latent_dim = p->bits.n_out;
+    if (p->latent_dim > LPCN_DRED_MAX_UNITS || p->bits.n_in % total) return -1;
+    p->taps = p->bits.n_in / total;
+    if (p->taps < 1 || p->taps > LPCN_DRED_ENC_MAX_TAPS) return -1;
+    if (parse_dred_dense(rec, n, "gdense1", total, &p->gdense[0])) return -1;
+    p->gdense1 = p->gdense[0].n_out;
+    if (p->gdense1 > LPCN_DRED_MAX_UNITS || parse_dred_dense(rec, n, "gdense2", p->gdense1, &p->gdense[1])) return -1;
+    p->state_dim = p->gdense[1].n_out;
+    if (p->state_dim > LPCN_DRED_MAX_UNITS) return -1;
+    p->present = i8 ? 2 : 1;
+    return 0;
+}
+
+/* Float encoder arrays beside a float LPCNet model are served; int8 (DOT_PROD) GRU arrays are not. */
+int lpcn_dred_enc_servable(const lpcn_model_host *m)
+{
+    return m->dred_enc.present == 1 && !m->is_int8;
+}
+
 /* int8 recurrent weights of a PLC GRU for plc_pred_i8_kernel: the blob has [3 N / 8 row groups][N / 4 blocks][8 rows][4 cols]
  * (src/vec.h:274-304), so the four weights of (row, block) are one dword already; the kernel walks a row's blocks with one lane per
  * row, so the dwords go block-major, out [N / 4][3 N]: a wave's lanes read consecutive dwords. */
@@ -693,6 +750,7 @@ int lpcn_model_parse(lpcn_model_host *m, const unsigned char *blob, int len)
     if (pack_gru_a(m, 0) || pack_gru_b(m)) { lpcn_model_release(m); return -1; }
     if (parse_plc(&m->plc, rec, n)) { memset(&m->plc, 0, sizeof(m->plc)); m->plc.present = -1; }      /* (the LPCNet model loads as before; lpcnet_batch_plc_enable reports it) */
     if (parse_dred(&m->dred, rec, n)) { memset(&m->dred, 0, sizeof(m->dred)); m->dred.present = -1; }   /* (likewise: lpcnet_batch_dred_enable reports it) */
+    if (parse_dred_enc(&m->dred_enc, rec, n)) { memset(&m->dred_enc, 0, sizeof(m->dred_enc)); m->dred_enc.present = -1; }   /* (lpcnet_batch_dred_enc_enable) */
     return 0;
 }
 

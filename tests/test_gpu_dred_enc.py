@@ -1,0 +1,411 @@
+"""The DRED encoder on the device (lpcnet_batch_dred_enc_* / lpcnet_batch_dred_encode*: DRED_rdovae_encode_dframe for every stream in one launch
+per shard) against the reference (tests/golden/golden_dred_enc_v1.npz, made by tests/tools/make_golden_dred_enc.py from the reference's generic-C
+float build): three width sets in every form of the kernel, the state across calls, a long run, the device forms, the way from the analysis and
+into the decoder, moving and clearing state, a captured step, and the refusals.  All comparisons on bit patterns."""
+import os
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import dred_enc_model as em  # noqa: E402
+import plc_model as pm  # noqa: E402
+from lpcnet_amd import api  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+N, MD = em.N_STREAMS, em.N_DFRAMES
+SENTINEL = np.float32(-12345.678)
+FORMS = (1, 2, 4, 8, 0)          # nine streams: a full workgroup and one stream at 8, two full and one at 4; 0 = the table's form
+LDS_BYTES = 160 * 1024
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden_dred_enc_v1.npz"))
+
+
+@pytest.fixture(scope="module")
+def feat(gold):
+    f = em.inputs()
+    assert np.uint32(zlib.crc32(f.tobytes())) == gold["in_crc"]
+    return f
+
+
+@pytest.fixture(scope="module")
+def cases(gold, hip_lib):
+    """per width set: the blob and the reference's results, made once and left unchanged"""
+    out = {}
+    for name in em.SETS:
+        blob = em.set_blob(name)
+        assert np.uint32(zlib.crc32(blob)) == gold["blob_crc_" + name]
+        out[name] = dict(blob=blob, lat=gold["lat_" + name], init=gold["init_" + name], gru=gold["gru_" + name], mem_crc=gold["mem_crc_" + name],
+                         mem_full=gold["mem_full_" + name], gruf=gold["gru_" + name].shape[1])
+    return out
+
+
+@pytest.fixture(scope="module")
+def batches(cases):
+    """one nine-stream batch per width set, shared by the tests; each resets it first and leaves form 0 and every stream active"""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = api.LPCNetBatch(N, cases[name]["blob"])
+            made[name].dred_enc_enable(MD)
+        made[name].reset()
+        return made[name]
+    yield get
+    for b in made.values():
+        b.close()
+
+
+def fresh(case, n=N, md=MD):
+    return np.full((n, md, case["lat"].shape[2]), SENTINEL, np.float32), np.full((n, md, case["init"].shape[2]), SENTINEL, np.float32)
+
+
+def assert_rows(got, case, count, what="", src=None, first=None):
+    """rows below count[s] of (latents, initial states) equal the reference's rows first[s] .. of stream src[s]; the others still hold the sentinel"""
+    for g, want in zip(got, (case["lat"], case["init"])):
+        for s in range(g.shape[0]):
+            k, f, r = int(count[s]), 0 if first is None else int(first[s]), s if src is None else int(src[s])
+            assert np.array_equal(bits(g[s, :k]), bits(want[r, f:f + k])), (what, s, np.argwhere(bits(g[s, :k]) != bits(want[r, f:f + k]))[:4].tolist())
+            assert (bits(g[s, k:]) == bits(SENTINEL)).all(), (what, s, "rows past the count were written")
+
+
+def assert_final_states(b, case, what=""):
+    """every stream's state read back equals the fixture's: the GRU states, the conv memory by CRC and stream 0's in full"""
+    states = [b.get_dred_enc_state(s) for s in range(N)]
+    for s, st in enumerate(states):
+        assert np.array_equal(bits(st[:case["gruf"]]), bits(case["gru"][s])), (what, s)
+    assert em.mem_crc(states, case["gruf"]).tolist() == case["mem_crc"].tolist(), what
+    assert np.array_equal(bits(states[0][case["gruf"]:]), bits(case["mem_full"])), what
+
+
+def chunk(feat, first, count, md=MD, stride=20):
+    """the call's feature array: stream s's double frames first[s] .. first[s] + count[s] - 1 at rows 0 .., the rest poisoned"""
+    out = np.full((feat.shape[0], 2 * md, stride), np.float32(3e4), np.float32)
+    for s in range(feat.shape[0]):
+        out[s, :2 * int(count[s]), :20] = feat[s, 2 * int(first[s]):2 * int(first[s] + count[s])]
+    return out
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("name", list(em.SETS))
+def test_encode_equals_the_reference_in_every_form(name, form, cases, batches, feat):
+    case, s = cases[name], em.SETS[name]
+    b = batches(name)
+    info = b.dred_enc_info()
+    assert info == (MD, 40, s["latent_dim"], s["state_dim"], s["taps"], sum(s["widths"]), case["gruf"] + (s["taps"] - 1) * sum(s["widths"]))
+    fits = 4 * max(form, 1) * (sum(s["widths"]) + s["gdense1"] + 40 + 6 * max(s["widths"][k] for k in em.GRU_AT)) <= LDS_BYTES
+    if not fits:                                          # (no set of the fixture reaches this: widths up to 256 fit every form)
+        with pytest.raises(api.LPCNetError, match=r"\(-4\).*LDS"):
+            b.dred_enc_form(form)
+        return
+    assert b.dred_enc_form(form) == (form if form else 1)          # (nine streams fit the CUs one to a workgroup)
+    try:
+        got = b.dred_encode(feat, em.COUNT, *fresh(case))
+    finally:
+        b.dred_enc_form(0)
+    assert_rows(got, case, em.COUNT, (name, form))
+    assert_final_states(b, case, (name, form))
+    assert np.abs(case["lat"]).max() > 1
+
+
+@pytest.mark.parametrize("name", ["narrow", "tf"])
+def test_state_carries_from_call_to_call(name, cases, batches, feat):
+    """the 7 double frames as calls of 3 + 1 + 3 equal one call of 7"""
+    case = cases[name]
+    b = batches(name)
+    done = np.zeros(N, np.int32)
+    lat, init = fresh(case)
+    for k in (3, 1, 3):
+        cnt = np.clip(em.COUNT - done, 0, k).astype(np.int32)
+        l, i = b.dred_encode(chunk(feat, done, cnt), cnt, *fresh(case))
+        assert_rows((l, i), case, cnt, (name, k), first=done)
+        for s in range(N):
+            lat[s, done[s]:done[s] + cnt[s]], init[s, done[s]:done[s] + cnt[s]] = l[s, :cnt[s]], i[s, :cnt[s]]
+        done += cnt
+    assert_rows((lat, init), case, em.COUNT, name)
+    assert_final_states(b, case, name)
+
+
+@pytest.mark.parametrize("form", [8, 1])
+def test_a_long_run_equals_the_reference(form, cases, gold):
+    f = em.long_inputs()
+    assert np.uint32(zlib.crc32(f.tobytes())) == gold["long_in_crc"]
+    b = api.LPCNetBatch(em.LONG_STREAMS, cases["tf"]["blob"])
+    b.dred_enc_enable(em.LONG_DFRAMES)
+    assert b.dred_enc_form(form) == form
+    lat, init = b.dred_encode(f, em.LONG_COUNT)
+    states = [b.get_dred_enc_state(s) for s in range(em.LONG_STREAMS)]
+    b.close()
+    s, gruf = em.LONG_FULL_STREAM, cases["tf"]["gruf"]
+    assert np.array_equal(bits(lat[s]), bits(gold["long_lat"])) and np.array_equal(bits(init[s]), bits(gold["long_init"]))
+    assert em.rows_crc(lat, init, em.LONG_COUNT).tolist() == gold["long_crc"].tolist()
+    assert [zlib.crc32(st[:gruf].tobytes()) for st in states] == gold["long_gru_crc"].tolist()
+    assert em.mem_crc(states, gruf).tolist() == gold["long_mem_crc"].tolist()
+
+
+def test_device_forms_two_shards_and_stride_36_equal_the_host_form(cases, batches, feat):
+    import torch
+    case = cases["tf"]
+    dev = torch.device("cuda:0")
+    d_feat = torch.from_numpy(em.strided(feat, 36)).to(dev)
+    poisoned = lambda: tuple(torch.from_numpy(x).to(dev) for x in fresh(case))
+    down = lambda pair: tuple(x.cpu().numpy() for x in pair)
+    b = batches("tf")
+    # on the batch's own stream, then on a caller's
+    out = poisoned()
+    torch.cuda.synchronize()
+    b.dred_encode_device(d_feat.data_ptr(), 36, em.COUNT, out[0].data_ptr(), out[1].data_ptr())
+    b.sync()
+    assert_rows(down(out), case, em.COUNT, "own stream")
+    assert_final_states(b, case, "own stream")
+    b.reset()
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        out2 = poisoned()
+        b.dred_encode_device(d_feat.data_ptr(), 36, em.COUNT, out2[0].data_ptr(), out2[1].data_ptr(), hip_stream=st.cuda_stream)
+        got = down(out2)
+    assert_rows(got, case, em.COUNT, "caller's stream")
+    # a capture does not take the per-stream form: the launch depends on the host's counts
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=st):
+        cs = torch.cuda.current_stream().cuda_stream
+        with pytest.raises(api.LPCNetError, match=r"\(-4\).*captur"):
+            b.dred_encode_device(d_feat.data_ptr(), 36, em.COUNT, out2[0].data_ptr(), out2[1].data_ptr(), hip_stream=cs)
+        out2[0].add_(0)                                   # (the capture stays usable and is not empty)
+    b.sync()
+    # the uniform form outside a capture, on the active prefix of six: the inactive streams' rows and states stay
+    b.reset()
+    before = [b.get_dred_enc_state(s) for s in range(6, N)]
+    b.active = 6
+    try:
+        out3 = poisoned()
+        torch.cuda.synchronize()
+        b.dred_encode_device(d_feat.data_ptr(), 36, 2, out3[0].data_ptr(), out3[1].data_ptr())
+        b.sync()
+    finally:
+        b.active = N
+    got = down(out3)
+    two = np.array([2] * 6 + [0] * 3, np.int32)
+    for g_, want in zip(got, (case["lat"], case["init"])):
+        for s in range(6):
+            k = min(2, int(em.COUNT[s]))                 # (the fixture has a stream's first COUNT[s] double frames)
+            assert np.array_equal(bits(g_[s, :k]), bits(want[s, :k])), ("uniform", s)
+        assert (bits(g_[np.arange(MD)[None, :] >= two[:, None]]) == bits(SENTINEL)).all()
+    assert all(np.array_equal(bits(x), bits(b.get_dred_enc_state(6 + k))) for k, x in enumerate(before))
+    # two unequal shards on one device: the host form, then every shard's device form
+    sb = api.LPCNetBatch(N, case["blob"], devices=[0, 0])
+    assert [x[:2] for x in sb.shards] == [(0, 5), (5, 4)]
+    sb.dred_enc_enable(MD)
+    assert_rows(sb.dred_encode(em.strided(feat, 36), em.COUNT, *fresh(case)), case, em.COUNT, "sharded host form")
+    assert_final_states(sb, case, "sharded host form")
+    sb.reset()
+    out4 = poisoned()
+    torch.cuda.synchronize()
+    for k, (first, cnt, _) in enumerate(sb.shards):
+        sl = slice(first, first + cnt)
+        sb.dred_encode_device(d_feat[sl].data_ptr(), 36, em.COUNT[sl], out4[0][sl].data_ptr(), out4[1][sl].data_ptr(), shard=k)
+    sb.sync()
+    assert_rows(down(out4), case, em.COUNT, "device shards")
+    with pytest.raises(api.LPCNetError, match=r"\(-4\).*shard"):
+        sb.dred_encode_device(d_feat.data_ptr(), 36, em.COUNT, out4[0].data_ptr(), out4[1].data_ptr())
+    sb.close()
+
+
+def test_the_analysis_output_goes_straight_into_the_encoder(cases):
+    """analyze_device's 36-float rows are the encoder's input as they are: equal to analyze -> dred_encode through the host on the same PCM"""
+    import torch
+    n, D = 3, 3
+    pcm = np.stack([pm.stream_pcm(s, 2 * D) for s in range(n)]).reshape(n, -1)
+    dev = torch.device("cuda:0")
+    a = api.LPCNetBatch(n, cases["narrow"]["blob"])
+    a.dred_enc_enable(D)
+    a.analysis_enable(2 * D)
+    d_pcm = torch.from_numpy(pcm).to(dev)
+    d_feat = torch.zeros((n, 2 * D, 36), dtype=torch.float32, device=dev)
+    ld, sd = a.dred_enc_info()[2:4]
+    d_lat, d_init = torch.zeros((n, D, ld), dtype=torch.float32, device=dev), torch.zeros((n, D, sd), dtype=torch.float32, device=dev)
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        a.analyze_device(d_pcm.data_ptr(), False, d_feat.data_ptr(), 36, 2 * D, hip_stream=st.cuda_stream)
+        a.dred_encode_device(d_feat.data_ptr(), 36, D, d_lat.data_ptr(), d_init.data_ptr(), hip_stream=st.cuda_stream)
+    a.sync()
+    st.synchronize()
+    a.close()
+    h = api.LPCNetBatch(n, cases["narrow"]["blob"])
+    h.dred_enc_enable(D)
+    f = h.analyze(pcm)
+    lat, init = h.dred_encode(f, np.full(n, D, np.int32))
+    h.close()
+    assert np.array_equal(bits(d_feat.cpu().numpy()), bits(f))
+    assert np.array_equal(bits(d_lat.cpu().numpy()), bits(lat)) and np.array_equal(bits(d_init.cpu().numpy()), bits(init))
+    assert np.abs(lat).max() > 0 and np.isfinite(lat).all()
+
+
+@pytest.mark.parametrize("name", ["narrow", "tf"])
+def test_moving_and_clearing_state(name, cases, feat):
+    case = cases[name]
+    sb = api.LPCNetBatch(N, case["blob"], devices=[0, 0])          # shards (0, 5) and (5, 4)
+    sb.dred_enc_enable(MD)
+    zero = np.zeros(N, np.int32)
+    c1 = np.minimum(em.COUNT, 3).astype(np.int32)
+    assert_rows(sb.dred_encode(chunk(feat, zero, c1), c1, *fresh(case)), case, c1, "first three")
+    # the read-back view is the reference's whatever the ring's head: streams 1 and 3 are through (1 and 2 double frames)
+    for s in (1, 3):
+        st = sb.get_dred_enc_state(s)
+        assert np.array_equal(bits(st[:case["gruf"]]), bits(case["gru"][s])) and zlib.crc32(st[case["gruf"]:].tobytes()) == case["mem_crc"][s]
+    # set_state(get_state) is the identity, also where it turns the ring (stream 8: three double frames in, one to go)
+    st8 = sb.get_dred_enc_state(8)
+    sb.set_dred_enc_state(8, st8)
+    assert np.array_equal(bits(sb.get_dred_enc_state(8)), bits(st8))
+    # stream 0 -> slot 2 within shard 0, stream 4 -> slot 7 across the shards; then four more double frames on the new slots, one on stream 8
+    st0 = sb.get_dred_enc_state(0)
+    sb.copy_streams([0, 4], [2, 7])
+    assert np.array_equal(bits(sb.get_dred_enc_state(2)), bits(st0)) and np.array_equal(bits(sb.get_dred_enc_state(0)), bits(st0))
+    src, first, cnt = np.arange(N), np.zeros(N, np.int32), np.zeros(N, np.int32)
+    src[2], src[7] = 0, 4
+    first[[2, 7, 8]], cnt[[2, 7, 8]] = 3, (4, 4, 1)
+    got = sb.dred_encode(chunk(feat[src], first, cnt), cnt, *fresh(case))
+    assert_rows(got, case, cnt, "after the copies", src=src, first=first)
+    assert np.array_equal(bits(sb.get_dred_enc_state(2)[:case["gruf"]]), bits(case["gru"][0]))
+    assert zlib.crc32(sb.get_dred_enc_state(7)[case["gruf"]:].tobytes()) == case["mem_crc"][4]
+    # reset(first, count) returns those streams to double frame 0 and leaves their neighbours alone
+    keep = {s: sb.get_dred_enc_state(s) for s in (1, 3, 6, 8)}
+    sb.reset(2, 1)
+    sb.reset(7, 1)
+    assert not sb.get_dred_enc_state(2).any() and not sb.get_dred_enc_state(7).any()
+    assert all(np.array_equal(bits(sb.get_dred_enc_state(s)), bits(v)) for s, v in keep.items())
+    cnt[:] = 0
+    cnt[[2, 7]] = 3
+    got = sb.dred_encode(chunk(feat[src], zero, cnt), cnt, *fresh(case))
+    assert_rows(got, case, cnt, "after the reset", src=src)
+    sb.close()
+
+
+def test_encoder_output_decodes_on_the_device_without_a_host_copy(cases, gold, feat):
+    """encode_device -> dred_decode_device on one stream: the newest double frame's initial state, the latents newest first (dred_enc_model.py)"""
+    import torch
+    blob = em.set_blob("tf", with_dec=True)
+    assert np.uint32(zlib.crc32(blob)) == gold["blob_crc_rt"]
+    dev = torch.device("cuda:0")
+    b = api.LPCNetBatch(N, blob)
+    b.dred_enc_enable(MD)
+    b.dred_enable(MD)
+    assert b.dred_info()[1:] == b.dred_enc_info()[2:4]
+    dcount = np.zeros(N, np.int32)
+    dcount[list(em.RT_STREAMS)] = MD
+    st = torch.cuda.Stream()
+    d_feat = torch.from_numpy(feat).to(dev)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        d_lat = torch.zeros((N, MD, 80), dtype=torch.float32, device=dev)
+        d_init = torch.zeros((N, MD, 24), dtype=torch.float32, device=dev)
+        d_out = torch.zeros((N, 4 * MD, 20), dtype=torch.float32, device=dev)
+        b.dred_encode_device(d_feat.data_ptr(), 20, em.COUNT, d_lat.data_ptr(), d_init.data_ptr(), hip_stream=st.cuda_stream)
+        d_state = d_init[:, MD - 1].contiguous()
+        d_rev = d_lat.flip(1).contiguous()
+        b.dred_decode_device(d_state.data_ptr(), d_rev.data_ptr(), dcount, d_out.data_ptr(), hip_stream=st.cuda_stream)
+        out = d_out.cpu().numpy()
+    b.close()
+    assert all(em.COUNT[s] == MD for s in em.RT_STREAMS)
+    assert np.array_equal(bits(out[list(em.RT_STREAMS)]), bits(gold["rt_feat"]))
+
+
+def test_the_uniform_step_is_captured_and_replayed(cases, batches, feat):
+    """count = NULL, one double frame per call: captured once with torch.cuda.graph, replayed double frame after double frame"""
+    import torch
+    case = cases["tf"]
+    dev = torch.device("cuda:0")
+    b = api.LPCNetBatch(N, case["blob"])
+    b.dred_enc_enable(1)
+    d_feat = torch.zeros((N, 2, 20), dtype=torch.float32, device=dev)
+    d_lat = torch.zeros((N, 1, 80), dtype=torch.float32, device=dev)
+    d_init = torch.zeros((N, 1, 24), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    b.dred_encode_device(d_feat.data_ptr(), 20, 1, d_lat.data_ptr(), d_init.data_ptr())          # (a first launch outside the capture)
+    b.sync()
+    b.reset()
+    g = torch.cuda.CUDAGraph()
+    st = torch.cuda.Stream()
+    with torch.cuda.graph(g, stream=st):
+        b.dred_encode_device(d_feat.data_ptr(), 20, 1, d_lat.data_ptr(), d_init.data_ptr(), hip_stream=torch.cuda.current_stream().cuda_stream)
+    assert not b.get_dred_enc_state(0).any()              # (the capture ran nothing)
+    lat, init = fresh(case)
+    for d in range(MD):
+        d_feat.copy_(torch.from_numpy(feat[:, 2 * d:2 * d + 2]))
+        g.replay()
+        torch.cuda.synchronize()
+        lat[:, d], init[:, d] = d_lat.cpu().numpy()[:, 0], d_init.cpu().numpy()[:, 0]
+    b.close()
+    for s in range(N):                                    # (every stream ran all seven; the fixture has a stream's first COUNT[s])
+        k = int(em.COUNT[s])
+        assert np.array_equal(bits(lat[s, :k]), bits(case["lat"][s, :k])) and np.array_equal(bits(init[s, :k]), bits(case["init"][s, :k])), s
+
+
+def test_refusals(cases, batches, feat, blob_f32):
+    case = cases["narrow"]
+    # before dred_enc_enable; a blob without the encoder's arrays; int8 encoder arrays
+    b = api.LPCNetBatch(N, case["blob"])
+    for call in (lambda: b.dred_encode(feat, em.COUNT), lambda: b.dred_encode_device(0, 20, em.COUNT, 0, 0), lambda: b.dred_encode_device(0, 20, 1, 0, 0),
+                 lambda: b.dred_enc_form(8), lambda: b.dred_enc_info(), lambda: b.get_dred_enc_state(0)):
+        with pytest.raises(api.LPCNetError, match=r"\(-5\).*enabled"):
+            call()
+    b.close()
+    nb = api.LPCNetBatch(2, blob_f32)
+    with pytest.raises(api.LPCNetError, match=r"\(-5\).*no DRED encoder"):
+        nb.dred_enc_enable(4)
+    nb.close()
+    s = em.SETS["narrow"]
+    kw = dict(taps=s["taps"], latent_dim=s["latent_dim"], gdense1=s["gdense1"], state_dim=s["state_dim"])
+    nb = api.LPCNetBatch(2, em.blob_enc(s["widths"], gru_flavour="int8", **kw))
+    with pytest.raises(api.LPCNetError, match=r"\(-5\).*int8"):
+        nb.dred_enc_enable(4)
+    nb.close()
+    b = batches("narrow")
+    c3 = np.minimum(em.COUNT, 3).astype(np.int32)
+    b.dred_encode(chunk(feat, np.zeros(N, np.int32), c3), c3)
+    before = [b.get_dred_enc_state(s) for s in range(N)]
+    unchanged = lambda: all(np.array_equal(bits(x), bits(b.get_dred_enc_state(s))) for s, x in enumerate(before))
+    # counts outside 0 .. max_dframes, a stride below 20, a form that does not exist: nothing written, no state changed
+    for bad in (-1, MD + 1):
+        count = em.COUNT.copy()
+        count[5] = bad
+        out = fresh(case)
+        with pytest.raises(api.LPCNetError, match=r"\(-4\).*count"):
+            b.dred_encode(feat, count, *out)
+        assert all((bits(x) == bits(SENTINEL)).all() for x in out) and unchanged()
+    out = fresh(case)
+    with pytest.raises(api.LPCNetError, match=r"\(-4\).*stride"):
+        b.dred_encode(np.ascontiguousarray(feat[:, :, :19]), em.COUNT, *out)
+    with pytest.raises(api.LPCNetError, match=r"\(-4\).*count"):
+        b.dred_encode_device(0, 20, MD + 1, 0, 0)
+    with pytest.raises(api.LPCNetError, match=r"\(-4\)"):
+        b.dred_enc_form(3)
+    assert all((bits(x) == bits(SENTINEL)).all() for x in out) and unchanged()
+    # the active prefix: a count on an inactive stream is refused; with zero there, the inactive rows and states stay and the active ones encode
+    b.active = 6
+    try:
+        with pytest.raises(api.LPCNetError, match=r"\(-4\).*not active"):
+            b.dred_encode(feat, em.COUNT, *out)
+        assert all((bits(x) == bits(SENTINEL)).all() for x in out) and unchanged()
+        b.reset()
+        count = em.COUNT.copy()
+        count[6:] = 0
+        got = b.dred_encode(feat, count, *out)
+        assert_rows(got, case, count, "prefix of six")
+        assert count[:6].sum() > 0 and not any(b.get_dred_enc_state(s).any() for s in range(6, N))
+    finally:
+        b.active = N
+    b.reset()
+    assert_rows(b.dred_encode(feat, em.COUNT, *fresh(case)), case, em.COUNT, "whole batch again")
