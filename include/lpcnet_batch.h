@@ -252,17 +252,19 @@ LPCNET_EXPORT int lpcnet_hip_plc_fec_feed_plan(int n, int *ctl, const int *count
  * `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
 LPCNET_EXPORT int lpcnet_hip_plc_model_info(const unsigned char *data, int len, int *info);
 
-/* The DRED decoder on the device, bit-identical to the reference's generic-C float build: per stream s,
+/* The DRED decoder on the device, bit-identical to the reference's generic-C build of the blob's flavour (float, or int8 / DOT_PROD): per stream s,
  *   DRED_rdovae_decode_all(model, features[s], state[s], latents[s], count[s])      (src/dred_rdovae.c:38-52, src/dred_rdovae_dec.c:37-98)
  * -- the producer of the vectors plc_fec_feed consumes: one redundancy packet (an initial state, then one latent per 40 ms) becomes four
  * 20-float feature frames per latent, the newest first.  One launch per shard decodes every active stream's whole latent chain.
  * The decoder comes from the same blob as the LPCNet model, as write_lpcnet_weights.c:72-75 appends it: arrays state{1,2,3}_*, dec_dense{1..8}_*,
  * dec_final_* (torch/rdovae/export_rdovae_weights.py, training_tf2/dump_rdovae.py).  Its widths are read from the bias lengths (each up to 256),
- * the latent and state dimensions from dec_dense1_weights / state1_weights; dec_final has 80 outputs.  Float arrays beside a float LPCNet model
- * are served.
- * dred_enable uploads the decoder and sizes the scratch for calls of up to max_latents latents per stream.  int8 (DOT_PROD) decoder arrays, a
- *   mix of float and int8 ones, incomplete or inconsistent arrays and a blob without any return LPCNET_HIP_E_MODEL with a message; so does every
- *   other call below before dred_enable.
+ * the latent and state dimensions from dec_dense1_weights / state1_weights; dec_final has 80 outputs.  The decoder is served in its blob's own
+ * flavour: float arrays beside a float LPCNet model, int8 (DOT_PROD) GRU arrays -- dec_dense2 / 4 / 6; the dense layers are float in that build too --
+ * beside an int8 one.
+ * dred_enable uploads the decoder and sizes the scratch for calls of up to max_latents latents per stream.  Decoder arrays of the other flavour
+ *   than the LPCNet model's (int8 beside float, float beside int8), a mix of float and int8 GRUs, incomplete or inconsistent arrays and a blob
+ *   without any return LPCNET_HIP_E_MODEL with a message; so does every other call below before dred_enable.
+ * dred_flavour: 0 the float decoder runs, 1 the int8 one.
  * dred_decode takes host pointers: state [n][state_dim], latents [n][max_latents][latent_dim], count [n] (each 0 .. max_latents), features
  *   [n][4 max_latents][20].  Rows 4 count[s] and beyond of a stream are not written.  It copies in, runs, copies out and synchronises (one
  *   host thread per shard).  dred_decode_device* takes device pointers and only enqueues on `hip_stream` (NULL = the batch's own) under the
@@ -291,14 +293,16 @@ LPCNET_EXPORT int lpcnet_batch_dred_decode_packed_device(LPCNetBatch *b, const f
 LPCNET_EXPORT int lpcnet_batch_dred_decode_packed_device_shard(LPCNetBatch *b, int shard, const float *d_state, const float *d_latents, const int *count,
                                                                const int *first, const int *take, float *d_packed, void *hip_stream);
 LPCNET_EXPORT int lpcnet_batch_dred_info(const LPCNetBatch *b, int *info);
+LPCNET_EXPORT int lpcnet_batch_dred_flavour(const LPCNetBatch *b);     /* 0: the float decoder runs, 1: the int8 one; LPCNET_HIP_E_MODEL before dred_enable */
 LPCNET_EXPORT int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams);
 /* a blob's DRED decoder as the loader sees it, no device: info[12] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
- * inconsistent), servable (dred_enable accepts the blob), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.  Returns 0,
+ * inconsistent), servable (dred_enable accepts the blob: the arrays are in the LPCNet model's own flavour), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.  Returns 0,
  * LPCNET_HIP_E_ARG without `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
 LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len, int *info);
 
-/* The DRED encoder on the device, bit-identical to the reference's generic-C float build: per stream s and double frame d < count[s],
+/* The DRED encoder on the device, bit-identical to the reference's generic-C build of the blob's flavour (float, or int8 / DOT_PROD): per stream s and
+ * double frame d < count[s],
  *   DRED_rdovae_encode_dframe(enc_state[s], model, latents[s][d], initial_state[s][d], features[s][2 d .. 2 d + 1])
  *                                                                                 (src/dred_rdovae.c:102-105, src/dred_rdovae_enc.c:38-95)
  * -- the producer of the latents and initial states dred_decode consumes: two consecutive 20-float feature frames (20 ms) become one latent vector
@@ -306,11 +310,13 @@ LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len,
  * double frames of a call.
  * The encoder comes from the same blob, found by name wherever its arrays stand: enc_dense{1..8}_*, bits_dense_*, gdense{1,2}_*.  Its widths are read
  * from the bias lengths (each up to 256), the latent dimension from bits_dense_bias, the taps K of the conv1d bits_dense from bits_dense_weights
- * ([K x sum of the widths][latent], oldest tap first, 1 <= K <= 8), the state dimension from gdense2_bias; enc_dense1 has 2 x 20 inputs.  Float arrays
- * beside a float LPCNet model are served.
+ * ([K x sum of the widths][latent], oldest tap first, 1 <= K <= 8), the state dimension from gdense2_bias; enc_dense1 has 2 x 20 inputs.  The encoder
+ * is served in its blob's own flavour: float arrays beside a float LPCNet model, int8 (DOT_PROD) GRU arrays (enc_dense2 / 4 / 6) beside an int8 one; the
+ * per-stream state is float in both.
  * dred_enc_enable uploads the encoder, allocates every stream's state as DRED_rdovae_init_encoder leaves it (zero) -- a later call keeps the states --
- *   and sizes the calls to up to max_dframes double frames per stream.  int8 (DOT_PROD) encoder arrays, a mix of float and int8 ones, incomplete or
- *   inconsistent arrays and a blob without any return LPCNET_HIP_E_MODEL with a message; so does every other call below before dred_enc_enable.
+ *   and sizes the calls to up to max_dframes double frames per stream.  Encoder arrays of the other flavour than the LPCNet model's, a mix of float and
+ *   int8 GRUs, incomplete or inconsistent arrays and a blob without any return LPCNET_HIP_E_MODEL with a message; so does every other call below
+ *   before dred_enc_enable.  dred_enc_flavour: 0 the float encoder runs, 1 the int8 one.
  * dred_encode takes host pointers: features [n][2 max_dframes][stride] with stride >= 20 -- only the first 20 floats of a row are read, so the
  *   36-float rows of lpcnet_batch_analyze go in as they are --, count [n] (each 0 .. max_dframes), latents [n][max_dframes][latent] and initial_state
  *   [n][max_dframes][state].  Rows count[s] and beyond of a stream are not written, and a stream with count 0 keeps its state.  It copies in, runs,
@@ -331,6 +337,7 @@ LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len,
  * dred_enc_info: info[7] = {max_dframes, 40, latent dimension, state dimension, K, sum of the widths, floats of one stream's state}. */
 LPCNET_EXPORT int lpcnet_batch_dred_enc_enable(LPCNetBatch *b, int max_dframes);
 LPCNET_EXPORT int lpcnet_batch_dred_enc_info(const LPCNetBatch *b, int *info);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_flavour(const LPCNetBatch *b);     /* 0: the float encoder runs, 1: the int8 one; LPCNET_HIP_E_MODEL before dred_enc_enable */
 LPCNET_EXPORT int lpcnet_batch_dred_encode(LPCNetBatch *b, const float *features, int stride, const int *count, float *latents, float *initial_state);
 LPCNET_EXPORT int lpcnet_batch_dred_encode_device(LPCNetBatch *b, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents,
                                                   float *d_initial_state, void *hip_stream);
@@ -341,7 +348,7 @@ LPCNET_EXPORT int lpcnet_batch_dred_enc_set_state(LPCNetBatch *b, int stream, co
 LPCNET_EXPORT int lpcnet_batch_dred_enc_set_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams);
 /* a blob's DRED encoder as the loader sees it, no device: info[15] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or inconsistent),
- * servable (dred_enc_enable accepts the blob), latent dimension, state dimension, K, width of gdense1, floats of one stream's state, the widths of
+ * servable (dred_enc_enable accepts the blob: the arrays are in the LPCNet model's own flavour), latent dimension, state dimension, K, width of gdense1, floats of one stream's state, the widths of
  * enc_dense1 .. enc_dense8}.  Returns like lpcnet_hip_dred_model_info */
 LPCNET_EXPORT int lpcnet_hip_dred_enc_model_info(const unsigned char *data, int len, int *info);
 

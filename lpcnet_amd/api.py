@@ -204,11 +204,13 @@ def load_library():
     L.lpcnet_batch_dred_decode_packed_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_decode_packed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_flavour.argtypes = [vp]
     L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
     L.lpcnet_hip_dred_enc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_batch_dred_enc_enable.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_enc_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_enc_flavour.argtypes = [vp]
     L.lpcnet_batch_dred_encode.argtypes = [vp, _f32p, C.c_int, vp, _f32p, _f32p]
     L.lpcnet_batch_dred_encode_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.lpcnet_batch_dred_encode_device_shard.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp]
@@ -687,8 +689,16 @@ class LPCNetBatch:
 
     # ---- DRED decoder (DRED_rdovae_decode_all per stream; include/lpcnet_batch.h) ----
     def dred_enable(self, max_latents: int):
-        """upload the blob's DRED decoder and size the scratch for calls of up to max_latents latents per stream"""
+        """upload the blob's DRED decoder and size the scratch for calls of up to max_latents latents per stream.  The decoder is served in its
+        blob's own flavour: float arrays beside a float LPCNet model, int8 GRU arrays beside an int8 one"""
         self._chk(self.L.lpcnet_batch_dred_enable(self.p, max_latents), "dred_enable")
+
+    def dred_flavour(self) -> int:
+        """0: the float DRED decoder runs, 1: the int8 one (the flavour of the batch's blob)"""
+        rc = self.L.lpcnet_batch_dred_flavour(self.p)
+        if rc < 0:
+            self._chk(rc, "dred_flavour")
+        return rc
 
     def dred_info(self):
         """(max_latents, latent_dim, state_dim): the row lengths of dred_decode's arrays"""
@@ -745,8 +755,16 @@ class LPCNetBatch:
 
     # ---- DRED encoder (DRED_rdovae_encode_dframe per stream and double frame; include/lpcnet_batch.h) ----
     def dred_enc_enable(self, max_dframes: int):
-        """upload the blob's DRED encoder, allocate every stream's state (zero) and size the calls to up to max_dframes double frames per stream"""
+        """upload the blob's DRED encoder, allocate every stream's state (zero) and size the calls to up to max_dframes double frames per stream.
+        The encoder is served in its blob's own flavour, like the decoder"""
         self._chk(self.L.lpcnet_batch_dred_enc_enable(self.p, max_dframes), "dred_enc_enable")
+
+    def dred_enc_flavour(self) -> int:
+        """0: the float DRED encoder runs, 1: the int8 one (the flavour of the batch's blob)"""
+        rc = self.L.lpcnet_batch_dred_enc_flavour(self.p)
+        if rc < 0:
+            self._chk(rc, "dred_enc_flavour")
+        return rc
 
     def dred_enc_info(self):
         """(max_dframes, 40, latent_dim, state_dim, taps, sum of the widths, floats of one stream's state)"""

@@ -354,6 +354,11 @@ int lpcnet_batch_dred_info(const LPCNetBatch *b, int *info)
     info[0] = lpcn_batch_dev_dred_enabled(b->sh[0].dev);
     FWD(lpcn_batch_dev_dred_dims(b->sh[0].dev, &info[1], &info[2]));
 }
+int lpcnet_batch_dred_flavour(const LPCNetBatch *b)
+{
+    NEED_DRED_ON(b);
+    FWD(lpcn_batch_dev_dred_flavour(b->sh[0].dev));
+}
 int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S) { NEED_DRED_ON(b); EACH_SHARD(lpcn_batch_dev_dred_set_form(s->dev, S)); }
 int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams)
 {
@@ -418,6 +423,11 @@ int lpcnet_batch_dred_enc_info(const LPCNetBatch *b, int *info)
     NEED_DENC_ON(b);
     if (!info) { set_err("lpcnet_batch_dred_enc_info: bad arguments"); return LPCN_E_ARG; }
     FWD(lpcn_batch_dev_dred_enc_info(b->sh[0].dev, info));
+}
+int lpcnet_batch_dred_enc_flavour(const LPCNetBatch *b)
+{
+    NEED_DENC_ON(b);
+    FWD(lpcn_batch_dev_dred_enc_flavour(b->sh[0].dev));
 }
 int lpcnet_batch_dred_enc_set_form(LPCNetBatch *b, int S) { NEED_DENC_ON(b); EACH_SHARD(lpcn_batch_dev_dred_enc_set_form(s->dev, S)); }
 int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams)

@@ -11,29 +11,49 @@
 // A = S: every recurrent weight is read once per workgroup and latent.  The dense layers have few rows (dec_final: 80), so their streams are dealt
 // over lanes instead (A < S): their matrices are small and stay in L2.  The GRU states are their segments of the concatenated buffer: nothing of
 // the chain goes to global memory but the features.
+//
+// An int8 (DOT_PROD) blob's decoder is the same walk, bit for bit like the reference's generic-C int8 build: that build's dense layers run on float
+// weights too, so only the three GRUs differ (gru_b_i8, frame_nets.hip.h).  One body, two kernels: dred_decode_kernel<S> for a float
+// block, dred_decode_i8_kernel<S> for an int8 one.
 #pragma once
-#include "frame_nets.hip.h"      // dense, gru_b: the layers, shared with the PLC predictor
+#include "frame_nets.hip.h"      // dense, gru_b, gru_b_i8: the layers, shared with the PLC predictor
+#include <type_traits>
 
 namespace lpcn {
 
 constexpr int DRED_THREADS = 1024;
 constexpr int DRED_REC = 4;            // per-stream record {count, first, take, first packed row}: first < 0 = the plain layout
 
-// floats of dynamic LDS a workgroup of S streams needs: the concatenated buffer, the input vector, the GRUs' two scratch arrays
-__host__ __device__ inline int dred_lds_floats(const DredNet &P, int S)
+// the widest input of a block's three GRUs (steps 1, 3, 5 of either half): the quantised input cells of an int8 block
+template <typename Step>
+__host__ __device__ inline int dred_gru_in(const Step *step)
 {
-    const int in = P.latent_dim > P.state_dim ? P.latent_dim : P.state_dim;
-    return S * (P.total + in + 6 * P.max_gru);
+    const int a = step[1].n_in, b = step[3].n_in, c = step[5].n_in;
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
-// one step of the decoder's block (kernel_params.h: DredStep): the whole workgroup takes the same branch
-template <int S>
-__device__ __forceinline__ void dred_step(const DredStep *q, float *buf, const float *xin, float *zrh, float *recur, const float *tansig, const int *live)
+// floats of dynamic LDS a workgroup of S streams needs: the concatenated buffer, the input vector, the GRUs' two scratch arrays -- and for an int8
+// block the GRUs' quantised input and old state, four int8 per dword
+template <typename W>
+__host__ __device__ inline int dred_lds_floats(const DredNetT<W> &P, int S)
+{
+    const int in = P.latent_dim > P.state_dim ? P.latent_dim : P.state_dim;
+    const int q = std::is_same<W, float>::value ? 0 : (dred_gru_in(P.step) + P.max_gru) / 4;
+    return S * (P.total + in + 6 * P.max_gru + q);
+}
+
+// one step of the decoder's block (kernel_params.h: DredStepT): the whole workgroup takes the same branch.  xq: an int8 block's quantised cells (the
+// widest GRU input's, then the widest GRU's), not read by a float block
+template <int S, typename W>
+__device__ __forceinline__ void dred_step(const DredStepT<W> *q, float *buf, const float *xin, float *zrh, float *recur, int *xq, int gru_in, const float *tansig,
+                                          const int *live)
 {
     constexpr int AD = S >= 8 ? 2 : 1;      // streams per lane in the dense layers: up to 256 rows x S / AD groups fill the workgroup
     const float *x = q->x < 0 ? xin : buf + S * q->x;
     if (q->gru) {
-        gru_b<S, DRED_THREADS, true>(GruLayer<float>{q->n_in, q->n_out, q->w, q->rec, q->b, q->start, q->pos}, x, buf + S * q->out, zrh, recur, tansig, live);
+        const GruLayer<W> g{q->n_in, q->n_out, q->gw, q->rec, q->b, q->start, q->pos};
+        if constexpr (std::is_same<W, float>::value) gru_b<S, DRED_THREADS, true>(g, x, buf + S * q->out, zrh, recur, tansig, live);
+        else gru_b_i8<S, DRED_THREADS, true>(g, x, buf + S * q->out, zrh, recur, xq, xq + S * (gru_in >> 2), tansig, live);
     } else {
         float *out = buf + S * q->out;
         dense<S, AD, DRED_THREADS, 4>(q->n_in, q->n_out, q->w, q->b, x, [&](int row, int a0, const float (&acc)[AD]) {
@@ -48,9 +68,10 @@ __device__ __forceinline__ void dred_step(const DredStep *q, float *buf, const f
 // latents [n][max_latents][latent_dim].  first < 0: features [n][4 max_latents][20], rows below 4 count written.  Else `features` is the packed array
 // and decoded row r of the stream, first <= r < first + take, goes to packed row (first packed row) + first + take - 1 - r: the oldest frame first.
 // A stream whose count is below its workgroup's largest neither writes nor advances once its own latents are through.
-template <int S>
-__global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet *P, int n, int max_latents, const int *rec, const float *state,
-                                                                    const float *latents, float *features)
+// The body of both flavours: W = float a float blob's kernel, W = int an int8 blob's, which differ in the GRUs alone (dred_step).
+template <int S, typename W>
+__device__ __forceinline__ void dred_decode_body(const DredNetT<W> *P, int n, int max_latents, const int *rec, const float *state, const float *latents,
+                                                 float *features)
 {
     extern __shared__ float4 dred_lds[];
     __shared__ int cnt[S], live[S];
@@ -60,6 +81,8 @@ __global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet
     float *xin = buf + S * total;
     float *zrh = xin + S * (latent_dim > state_dim ? latent_dim : state_dim);
     float *recur = zrh + S * 3 * P->max_gru;
+    int *xq = nullptr, gru_in = 0;
+    if constexpr (!std::is_same<W, float>::value) { xq = (int *)(recur + S * 3 * P->max_gru); gru_in = dred_gru_in(P->step); }
     const int s0 = blockIdx.x * S, t = threadIdx.x;
     if (t < S) { cnt[t] = s0 + t < n ? rec[(size_t)(s0 + t) * DRED_REC] : 0; live[t] = 1; }
     __syncthreads();
@@ -74,7 +97,7 @@ __global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet
     __syncthreads();
     // dred_rdovae_dec_init_states (src/dred_rdovae_dec.c:37-47): the GRU states are the GRUs' segments of the buffer
 #pragma unroll 1
-    for (int k = 0; k < 3; ++k) dred_step<S>(&P->init[k], buf, xin, zrh, recur, tansig, live);
+    for (int k = 0; k < 3; ++k) dred_step<S, W>(&P->init[k], buf, xin, zrh, recur, xq, gru_in, tansig, live);
     for (int l = 0; l < maxc; ++l) {
         if (t < S) live[t] = l < cnt[t];
         for (int e = t; e < S * latent_dim; e += DRED_THREADS) {
@@ -84,7 +107,7 @@ __global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet
         __syncthreads();
         // dred_rdovae_decode_qframe (src/dred_rdovae_dec.c:50-98): dense 1, GRU 2, dense 3, GRU 4, dense 5, GRU 6, dense 7, dense 8
 #pragma unroll 1
-        for (int k = 0; k < 8; ++k) dred_step<S>(&P->step[k], buf, xin, zrh, recur, tansig, live);
+        for (int k = 0; k < 8; ++k) dred_step<S, W>(&P->step[k], buf, xin, zrh, recur, xq, gru_in, tansig, live);
         // dec_final over the whole buffer, linear: one lane per (output, stream); straight to the output
         dense<S, 1, DRED_THREADS, 8>(total, LPCN_DRED_OUT, P->final_w, P->final_b, buf, [&](int i, int a, const float (&sum)[1]) {
             const float acc = sum[0];
@@ -97,6 +120,20 @@ __global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet
         });
         __syncthreads();
     }
+}
+
+template <int S>
+__global__ __launch_bounds__(DRED_THREADS) void dred_decode_kernel(const DredNet *P, int n, int max_latents, const int *rec, const float *state,
+                                                                    const float *latents, float *features)
+{
+    dred_decode_body<S, float>(P, n, max_latents, rec, state, latents, features);
+}
+// ... and an int8 (DOT_PROD) blob's: the dense layers float, the GRUs compute_gruB of the reference's generic-C int8 build (gru_b_i8)
+template <int S>
+__global__ __launch_bounds__(DRED_THREADS) void dred_decode_i8_kernel(const DredNetQ *P, int n, int max_latents, const int *rec, const float *state,
+                                                                       const float *latents, float *features)
+{
+    dred_decode_body<S, int>(P, n, max_latents, rec, state, latents, features);
 }
 
 }  // namespace lpcn

@@ -123,19 +123,20 @@ struct X2WideHost {
 };
 
 // A host copy of the arrays of a frame-rate network's layers (the blob is the caller's): take() copies every array into the two arenas and points
-// the layer records at the copies
+// the layer records at the copies.  q8: the GRUs are int8 layers, whose two weight arrays hold a byte per weight (a multiple of four)
 struct LayerArena {
     std::vector<float> f;
     std::vector<int> i;
-    void take(const std::vector<lpcn_dense_layer *> &dense, lpcn_gru_layer *gru, int n_gru)
+    void take(const std::vector<lpcn_dense_layer *> &dense, lpcn_gru_layer *gru, int n_gru, bool q8 = false)
     {
         size_t nf = 0, ni = 0;
+        const size_t per = q8 ? 4 : 1;      // weights per float-sized cell
         std::vector<size_t> idx_len(n_gru);
         for (lpcn_dense_layer *q : dense) nf += (size_t)q->n_in * q->n_out + q->n_out;
         for (int g = 0; g < n_gru; ++g) {
             const lpcn_gru_layer &G = gru[g];
             idx_len[g] = (size_t)(3 * G.n / 8) + G.nb;
-            nf += 32 * (size_t)G.nb + 3 * (size_t)G.n * G.n + 6 * (size_t)G.n;
+            nf += 32 * (size_t)G.nb / per + 3 * (size_t)G.n * G.n / per + 6 * (size_t)G.n;
             ni += idx_len[g];
         }
         f.resize(nf);
@@ -146,7 +147,7 @@ struct LayerArena {
         for (lpcn_dense_layer *q : dense) { copy(q->w, (size_t)q->n_in * q->n_out); copy(q->b, q->n_out); }
         for (int g = 0; g < n_gru; ++g) {
             lpcn_gru_layer &G = gru[g];
-            copy(G.w, 32 * (size_t)G.nb); copy(G.rec, 3 * (size_t)G.n * G.n); copy(G.bias, 6 * (size_t)G.n);
+            copy(G.w, 32 * (size_t)G.nb / per); copy(G.rec, 3 * (size_t)G.n * G.n / per); copy(G.bias, 6 * (size_t)G.n);
             memcpy(ip, G.idx, sizeof(int) * idx_len[g]); G.idx = ip; ip += idx_len[g];
         }
     }
@@ -182,13 +183,17 @@ struct lpcn_engine {
     lpcn::PlcNetQ plcq{};          //   ... or an int8 blob's (plc_pred_i8_kernel)
     int plc_present = 0;           //   ... lpcn_plc_model.present of the blob
     bool plc_servable = false;     //   ... and whether it is in the blob's own flavour (lpcn_plc_servable): uploaded only then
-    lpcn::DredNet dred{};          // DRED decoder (engine_dred.hip): the blob's decoder on the device, once a batch has enabled it ...
+    lpcn::DredNet dred{};          // DRED decoder (engine_dred.hip): the blob's decoder on the device, once a batch has enabled it: a float blob's ...
+    lpcn::DredNetQ dredq{};        //   ... or an int8 blob's (dred_decode_i8_kernel) ...
     const lpcn::DredNet *d_dred = nullptr;        //   ... and the device copy of this block, which the kernel walks
+    const lpcn::DredNetQ *d_dredq = nullptr;
     int dred_present = 0;          //   ... lpcn_dred_model.present of the blob
-    bool dred_servable = false;    //   ... float arrays beside a float LPCNet model (lpcn_dred_servable)
+    bool dred_servable = false;    //   ... and whether it is in the blob's own flavour (lpcn_dred_servable)
     std::unique_ptr<DredHostModel> dred_host;     //   ... not uploaded yet
-    lpcn::DredEncNet denc{};       // DRED encoder (engine_dred_enc.hip), the same five: the block, its device copy, ...
+    lpcn::DredEncNet denc{};       // DRED encoder (engine_dred_enc.hip), the same: the block of either flavour, its device copy, ...
+    lpcn::DredEncNetQ dencq{};
     const lpcn::DredEncNet *d_denc = nullptr;
+    const lpcn::DredEncNetQ *d_dencq = nullptr;
     int denc_present = 0;          //   ... lpcn_dred_enc_model.present of the blob, lpcn_dred_enc_servable, ...
     bool denc_servable = false;
     std::unique_ptr<DredEncHostModel> denc_host;  //   ... not uploaded yet

@@ -15,22 +15,23 @@ int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     auto h = std::make_unique<DredHostModel>();
     h->m = m->dred;
     lpcn_dred_model &d = h->m;
-    h->a.take({&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final}, d.gru, 3);
+    h->a.take({&d.state[0], &d.state[1], &d.state[2], &d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.final}, d.gru, 3, m->dred.present == 2);
     e->dred_host = std::move(h);
     return 0;
 }
 
-// the arrays as they are, the GRUs through upload_gru (engine_core.h) like the PLC network's; then the block itself, which the kernel reads from
-// device memory
-static int dred_upload_net(lpcn_engine *e)
+// the arrays as they are, the GRUs through upload_gru (engine_core.h) like the PLC network's, in the blob's flavour (W = int: an int8 blob's); then
+// the block itself, which the kernel reads from device memory
+template <typename W>
+static int dred_upload_net(lpcn_engine *e, lpcn::DredNetT<W> &net, const lpcn::DredNetT<W> **d_net)
 {
     const lpcn_dred_model &d = e->dred_host->m;
-    lpcn::DredNet n{};
+    lpcn::DredNetT<W> n{};
     int rc = 0, off[9] = {0};
     n.latent_dim = d.latent_dim; n.state_dim = d.state_dim;
     for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + d.width[k];
     n.total = off[8];
-    auto up_dense = [&](const lpcn_dense_layer &s, lpcn::DredStep &o, int x, int out) {
+    auto up_dense = [&](const lpcn_dense_layer &s, lpcn::DredStepT<W> &o, int x, int out) {
         o.gru = 0; o.n_in = s.n_in; o.n_out = s.n_out; o.x = x; o.out = out;
         int r = upload<float>(e, &o.w, s.w, (size_t)s.n_in * s.n_out);
         return r ? r : upload<float>(e, &o.b, s.b, s.n_out);
@@ -40,20 +41,24 @@ static int dred_upload_net(lpcn_engine *e)
     for (int k = 0; k < 5; ++k) if ((rc = up_dense(d.dense[k], n.step[dense_at[k]], dense_at[k] ? off[dense_at[k] - 1] : -1, off[dense_at[k]]))) return rc;
     for (int g = 0; g < 3; ++g) {
         const lpcn_gru_layer &G = d.gru[g];
-        lpcn::DredStep &o = n.step[gru_at[g]];
-        lpcn::GruLayer<float> L{};
+        lpcn::DredStepT<W> &o = n.step[gru_at[g]];
+        lpcn::GruLayer<W> L{};
         if ((rc = upload_gru(e, L, G))) return rc;
         o.gru = 1; o.n_in = L.n_in; o.n_out = L.n; o.x = off[gru_at[g] - 1]; o.out = off[gru_at[g]];
-        o.w = L.w; o.rec = L.rec; o.b = L.bias; o.start = L.start; o.pos = L.pos;
+        o.gw = L.w; o.rec = L.rec; o.b = L.bias; o.start = L.start; o.pos = L.pos;
         n.max_gru = G.n > n.max_gru ? G.n : n.max_gru;
     }
     if ((rc = upload<float>(e, &n.final_w, d.final.w, (size_t)n.total * LPCN_DRED_OUT)) || (rc = upload<float>(e, &n.final_b, d.final.b, LPCN_DRED_OUT)) ||
         (rc = upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
-    if ((rc = upload<lpcn::DredNet>(e, &e->d_dred, &n, 1))) return rc;
-    e->dred = n;
+    if ((rc = upload<lpcn::DredNetT<W>>(e, d_net, &n, 1))) return rc;
+    net = n;
     e->dred_host.reset();
     return 0;
 }
+// the uploaded block's figures, whichever flavour it is (a served decoder is in the blob's own)
+static int dred_lds_bytes(const lpcn_engine *e, int S) { return (e->is_int8 ? lpcn::dred_lds_floats(e->dredq, S) : lpcn::dred_lds_floats(e->dred, S)) * (int)sizeof(float); }
+static int dred_latent_dim(const lpcn_engine *e) { return e->is_int8 ? e->dredq.latent_dim : e->dred.latent_dim; }
+static int dred_state_dim(const lpcn_engine *e) { return e->is_int8 ? e->dredq.state_dim : e->dred.state_dim; }
 
 extern "C" int lpcn_engine_dred_present(const lpcn_engine *e) { return e->dred_present; }
 extern "C" int lpcn_batch_dev_dred_enabled(const lpcn_batch_dev *b) { return b->dred ? b->dred->max_latents : 0; }
@@ -62,15 +67,15 @@ extern "C" int lpcn_batch_dev_dred_enable(lpcn_batch_dev *b, int max_latents)
 {
     lpcn_engine *e = b->e;
     if (e->dred_present == 0) { snprintf(g_err, sizeof(g_err), "the model blob has no DRED decoder (state1..3_*, dec_dense1..8_*, dec_final_*)"); return LPCN_E_MODEL; }
-    if (e->dred_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder is int8 (DOT_PROD): only float decoder arrays are served"); return LPCN_E_MODEL; }
-    if (e->dred_present != 1) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder arrays are incomplete, mix float and int8, or do not fit together (widths up to %d, dec_final with %d outputs)", LPCN_DRED_MAX_UNITS, LPCN_DRED_OUT); return LPCN_E_MODEL; }
+    if (e->dred_present != 1 && e->dred_present != 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder arrays are incomplete, mix float and int8, or do not fit together (widths up to %d, dec_final with %d outputs)", LPCN_DRED_MAX_UNITS, LPCN_DRED_OUT); return LPCN_E_MODEL; }
+    if (!e->dred_servable && e->dred_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder is int8 (DOT_PROD) but its LPCNet model is float: int8 decoder arrays are served beside an int8 model"); return LPCN_E_MODEL; }
     if (!e->dred_servable) { snprintf(g_err, sizeof(g_err), "the blob's DRED decoder is float but its LPCNet model is int8: float decoder arrays are served beside a float model"); return LPCN_E_MODEL; }
     if (max_latents < 1 || (long long)max_latents * LPCN_DRED_FRAMES * b->n > 0x7fffffffLL / LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "DRED: max_latents must be at least 1 (and the batch's rows fit an int)"); return LPCN_E_ARG; }
     DeviceGuard guard(e->device);
     int rc = wait_all(b);
     if (rc) return rc;
-    if (e->dred_host && (rc = dred_upload_net(e))) return rc;
-    if ((size_t)lpcn::dred_lds_floats(e->dred, 1) * sizeof(float) > 160 * 1024) { snprintf(g_err, sizeof(g_err), "DRED: the decoder's buffers do not fit the LDS"); return LPCN_E_MODEL; }
+    if (e->dred_host && (rc = e->is_int8 ? dred_upload_net<int>(e, e->dredq, &e->d_dredq) : dred_upload_net<float>(e, e->dred, &e->d_dred))) return rc;
+    if ((size_t)dred_lds_bytes(e, 1) > 160 * 1024) { snprintf(g_err, sizeof(g_err), "DRED: the decoder's buffers do not fit the LDS"); return LPCN_E_MODEL; }
     if (!b->dred) {
         auto p = std::make_unique<lpcn_dred_host>();
         if ((rc = p->d_rec.alloc((size_t)lpcn::DRED_REC * b->n)) || (rc = p->h_rec.reserve(sizeof(int) * lpcn::DRED_REC * (size_t)b->n))) return rc;
@@ -86,17 +91,24 @@ extern "C" int lpcn_batch_dev_dred_enable(lpcn_batch_dev *b, int max_latents)
 extern "C" int lpcn_batch_dev_dred_dims(const lpcn_batch_dev *b, int *latent_dim, int *state_dim)
 {
     NEED_DRED(b);
-    if (latent_dim) *latent_dim = b->e->dred.latent_dim;
-    if (state_dim) *state_dim = b->e->dred.state_dim;
+    if (latent_dim) *latent_dim = dred_latent_dim(b->e);
+    if (state_dim) *state_dim = dred_state_dim(b->e);
     return 0;
+}
+extern "C" int lpcn_batch_dev_dred_flavour(const lpcn_batch_dev *b)
+{
+    NEED_DRED(b);
+    return b->e->is_int8 ? 1 : 0;
 }
 
 // ---- streams per workgroup.  A workgroup's time per latent is set by its dependent add chains, not by how many streams it carries: measured on one
 // MI355X at width 256 and 25 latents (profiles/dred_rate.json), 256 streams take 6.61 / 6.71 / 6.92 / 7.67 ms at 1 / 2 / 4 / 8 streams per
 // workgroup -- one workgroup per CU or fewer, so the fewest streams win -- and 2 048 streams 52.8 / 27.3 / 14.2 / 7.78 ms, 8 192 streams 210.9 / 109.1 /
 // 56.4 / 31.0 ms: the time follows the number of workgroups.  The table: the fewest streams per workgroup that still put the streams on the CUs in one
-// round, eight beyond that.
-static bool dred_form_fits(const lpcn_engine *e, int S) { return (size_t)lpcn::dred_lds_floats(e->dred, S) * sizeof(float) <= 160 * 1024; }
+// round, eight beyond that.  An int8 blob's decoder shares the table: measured beside the float one (profiles/dred_i8_rate.json) it
+// takes 2.78 / 2.82 / 3.11 / 4.86 ms at 256 streams, 21.1 / 10.9 / 6.25 / 4.91 ms at 2 048 and 83.7 / 43.0 / 24.4 / 19.3 ms at 8 192, and the table's
+// form is within the run's spread of the best pinned one in every row.
+static bool dred_form_fits(const lpcn_engine *e, int S) { return (size_t)dred_lds_bytes(e, S) <= 160 * 1024; }
 extern "C" int lpcn_batch_dev_dred_form(const lpcn_batch_dev *b, int n)
 {
     NEED_DRED(b);
@@ -135,25 +147,38 @@ extern "C" int lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *cou
     return 0;
 }
 
-template <int S>
-static int dred_launch_form(const lpcn::DredNet *P, int grid, int lds, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state,
+template <int S, typename W>
+static int dred_launch_form(const lpcn::DredNetT<W> *P, int grid, int lds, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state,
                             const float *d_latents, float *d_out)
 {
     // the dynamic-LDS limit of a form is raised once per (device, size), not at every launch
     static std::mutex mu;
     static int limit[64];
+    const auto kernel = [] { if constexpr (std::is_same<W, float>::value) return lpcn::dred_decode_kernel<S>; else return lpcn::dred_decode_i8_kernel<S>; }();
     int dev = 0;
     (void)hipGetDevice(&dev);
     {
         std::lock_guard<std::mutex> g(mu);
         if (dev < 0 || dev >= 64 || limit[dev] < lds) {
-            HIP_TRY(hipFuncSetAttribute((const void *)lpcn::dred_decode_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             if (dev >= 0 && dev < 64) limit[dev] = lds;
         }
     }
-    hipLaunchKernelGGL(lpcn::dred_decode_kernel<S>, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, P, n, max_latents, d_rec, d_state, d_latents, d_out);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, P, n, max_latents, d_rec, d_state, d_latents, d_out);
     if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED decode: kernel launch failed"); return LPCN_E_HIP; }
     return 0;
+}
+
+template <typename W>
+static int dred_launch(const lpcn::DredNetT<W> *P, int S, int grid, int lds, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state,
+                       const float *d_latents, float *d_out)
+{
+    switch (S) {
+    case 1: return dred_launch_form<1>(P, grid, lds, st, n, max_latents, d_rec, d_state, d_latents, d_out);
+    case 2: return dred_launch_form<2>(P, grid, lds, st, n, max_latents, d_rec, d_state, d_latents, d_out);
+    case 4: return dred_launch_form<4>(P, grid, lds, st, n, max_latents, d_rec, d_state, d_latents, d_out);
+    default: return dred_launch_form<8>(P, grid, lds, st, n, max_latents, d_rec, d_state, d_latents, d_out);
+    }
 }
 
 // checks, the records' upload through the pinned buffer, one launch.  first == NULL: the plain layout
@@ -176,18 +201,13 @@ static int dred_enqueue(lpcn_batch_dev *b, const float *d_state, const float *d_
         if (first) row += take[s];
     }
     const int S = lpcn_batch_dev_dred_form(b, b->active);
-    const int grid = (b->active + S - 1) / S, lds = lpcn::dred_lds_floats(b->e->dred, S) * (int)sizeof(float);
+    const int grid = (b->active + S - 1) / S, lds = dred_lds_bytes(b->e, S);
     if ((rc = order_begin(b, st))) return rc;
     HIP_TRY(hipMemcpyAsync(p->d_rec, h, sizeof(int) * lpcn::DRED_REC * (size_t)b->active, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->ev_rec, st));
     p->rec_pending = true;
-    const lpcn::DredNet *P = b->e->d_dred;
-    switch (S) {
-    case 1: rc = dred_launch_form<1>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
-    case 2: rc = dred_launch_form<2>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
-    case 4: rc = dred_launch_form<4>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
-    default: rc = dred_launch_form<8>(P, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out); break;
-    }
+    rc = b->e->is_int8 ? dred_launch(b->e->d_dredq, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out)
+                       : dred_launch(b->e->d_dred, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out);
     if (rc) return rc;
     return order_end(b, st);
 }
@@ -222,9 +242,8 @@ extern "C" int lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *s
     if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     lpcn_dred_host *p = b->dred.get();
-    const lpcn::DredNet &P = b->e->dred;
     hipStream_t st = b->e->stream;
-    const size_t n = (size_t)b->active, per_s = (size_t)P.state_dim, per_l = (size_t)p->max_latents * P.latent_dim,
+    const size_t n = (size_t)b->active, per_s = (size_t)dred_state_dim(b->e), per_l = (size_t)p->max_latents * dred_latent_dim(b->e),
                  per_f = (size_t)LPCN_DRED_FRAMES * p->max_latents * LPCN_NB_FEAT;
     if ((rc = p->d_state.reserve(b, (size_t)b->n * per_s)) || (rc = p->d_latents.reserve(b, (size_t)b->n * per_l)) || (rc = p->d_feat.reserve(b, (size_t)b->n * per_f)) ||
         (rc = p->h_feat.reserve(sizeof(float) * (size_t)b->n * per_f))) return rc;

@@ -16,21 +16,23 @@ int denc_engine_init(lpcn_engine *e, const lpcn_model_host *m)
     auto h = std::make_unique<DredEncHostModel>();
     h->m = m->dred_enc;
     lpcn_dred_enc_model &d = h->m;
-    h->a.take({&d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.bits, &d.gdense[0], &d.gdense[1]}, d.gru, 3);
+    h->a.take({&d.dense[0], &d.dense[1], &d.dense[2], &d.dense[3], &d.dense[4], &d.bits, &d.gdense[0], &d.gdense[1]}, d.gru, 3, m->dred_enc.present == 2);
     e->denc_host = std::move(h);
     return 0;
 }
 
-// the arrays as they are, the GRUs through upload_gru (engine_core.h); then the block itself, which the kernel reads from device memory
-static int denc_upload_net(lpcn_engine *e)
+// the arrays as they are, the GRUs through upload_gru (engine_core.h) in the blob's flavour (W = int: an int8 blob's); then the block itself, which the
+// kernel reads from device memory
+template <typename W>
+static int denc_upload_net(lpcn_engine *e, lpcn::DredEncNetT<W> &net, const lpcn::DredEncNetT<W> **d_net)
 {
     const lpcn_dred_enc_model &d = e->denc_host->m;
-    lpcn::DredEncNet n{};
+    lpcn::DredEncNetT<W> n{};
     int rc = 0, off[9] = {0};
     n.latent_dim = d.latent_dim; n.state_dim = d.state_dim; n.taps = d.taps; n.gd1 = d.gdense1;
     for (int k = 0; k < 8; ++k) off[k + 1] = off[k] + d.width[k];
     n.total = off[8];
-    auto up_dense = [&](const lpcn_dense_layer &s, lpcn::DredStep &o, int x, int out) {
+    auto up_dense = [&](const lpcn_dense_layer &s, lpcn::DredStepT<W> &o, int x, int out) {
         o.gru = 0; o.n_in = s.n_in; o.n_out = s.n_out; o.x = x; o.out = out;
         int r = upload<float>(e, &o.w, s.w, (size_t)s.n_in * s.n_out);
         return r ? r : upload<float>(e, &o.b, s.b, s.n_out);
@@ -39,11 +41,11 @@ static int denc_upload_net(lpcn_engine *e)
     for (int k = 0; k < 5; ++k) if ((rc = up_dense(d.dense[k], n.step[dense_at[k]], dense_at[k] ? off[dense_at[k] - 1] : -1, off[dense_at[k]]))) return rc;
     for (int g = 0; g < 3; ++g) {
         const lpcn_gru_layer &G = d.gru[g];
-        lpcn::DredStep &o = n.step[gru_at[g]];
-        lpcn::GruLayer<float> L{};
+        lpcn::DredStepT<W> &o = n.step[gru_at[g]];
+        lpcn::GruLayer<W> L{};
         if ((rc = upload_gru(e, L, G))) return rc;
         o.gru = 1; o.n_in = L.n_in; o.n_out = L.n; o.x = off[gru_at[g] - 1]; o.out = off[gru_at[g]];
-        o.w = L.w; o.rec = L.rec; o.b = L.bias; o.start = L.start; o.pos = L.pos;
+        o.gw = L.w; o.rec = L.rec; o.b = L.bias; o.start = L.start; o.pos = L.pos;
         n.max_gru = G.n > n.max_gru ? G.n : n.max_gru;
         n.gru_off[g] = off[gru_at[g]]; n.gru_n[g] = G.n; n.gru_floats += G.n;
     }
@@ -51,20 +53,31 @@ static int denc_upload_net(lpcn_engine *e)
     if ((rc = upload<float>(e, &n.bits_w, d.bits.w, (size_t)d.bits.n_in * d.bits.n_out)) || (rc = upload<float>(e, &n.bits_b, d.bits.b, d.bits.n_out)) ||
         (rc = upload<float>(e, &n.g2_w, d.gdense[1].w, (size_t)d.gdense1 * d.state_dim)) || (rc = upload<float>(e, &n.g2_b, d.gdense[1].b, d.state_dim)) ||
         (rc = upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
-    if ((rc = upload<lpcn::DredEncNet>(e, &e->d_denc, &n, 1))) return rc;
-    e->denc = n;
+    if ((rc = upload<lpcn::DredEncNetT<W>>(e, d_net, &n, 1))) return rc;
+    net = n;
     e->denc_host.reset();
     return 0;
 }
 
-static bool denc_form_fits(const lpcn_engine *e, int S) { return (size_t)lpcn::rdovae_enc_lds_floats(e->denc, S) * sizeof(float) <= DENC_LDS_MAX; }
+// the uploaded block's figures, whichever flavour it is (a served encoder is in the blob's own): everything but the weights is the same in both
+static size_t denc_lds_bytes(const lpcn_engine *e, int S) { return (size_t)(e->is_int8 ? lpcn::rdovae_enc_lds_floats(e->dencq, S) : lpcn::rdovae_enc_lds_floats(e->denc, S)) * sizeof(float); }
+struct DencDims { int latent_dim, state_dim, taps, total, gru_floats, rec; };
+static DencDims denc_dims(const lpcn_engine *e)
+{
+    if (e->is_int8) return {e->dencq.latent_dim, e->dencq.state_dim, e->dencq.taps, e->dencq.total, e->dencq.gru_floats, lpcn::rdovae_enc_rec_floats(e->dencq)};
+    return {e->denc.latent_dim, e->denc.state_dim, e->denc.taps, e->denc.total, e->denc.gru_floats, lpcn::rdovae_enc_rec_floats(e->denc)};
+}
+static bool denc_form_fits(const lpcn_engine *e, int S) { return denc_lds_bytes(e, S) <= DENC_LDS_MAX; }
+template <int S, typename W>
+static auto denc_kernel() { if constexpr (std::is_same<W, float>::value) return lpcn::rdovae_enc_kernel<S>; else return lpcn::rdovae_enc_i8_kernel<S>; }
 
 // the dynamic-LDS limit of a form, raised when a batch enables the encoder: a launch sets nothing, so it can be captured
 template <int S>
 static int denc_prepare_form(const lpcn_engine *e)
 {
     if (!denc_form_fits(e, S)) return 0;
-    HIP_TRY(hipFuncSetAttribute((const void *)lpcn::rdovae_enc_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, lpcn::rdovae_enc_lds_floats(e->denc, S) * (int)sizeof(float)));
+    const void *kernel = e->is_int8 ? (const void *)denc_kernel<S, int>() : (const void *)denc_kernel<S, float>();
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)denc_lds_bytes(e, S)));
     return 0;
 }
 
@@ -74,19 +87,19 @@ extern "C" int lpcn_batch_dev_dred_enc_enable(lpcn_batch_dev *b, int max_dframes
 {
     lpcn_engine *e = b->e;
     if (e->denc_present == 0) { snprintf(g_err, sizeof(g_err), "the model blob has no DRED encoder (enc_dense1..8_*, bits_dense_*, gdense1_*, gdense2_*)"); return LPCN_E_MODEL; }
-    if (e->denc_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED encoder is int8 (DOT_PROD): only float encoder arrays are served"); return LPCN_E_MODEL; }
-    if (e->denc_present != 1) { snprintf(g_err, sizeof(g_err), "the blob's DRED encoder arrays are incomplete, mix float and int8, or do not fit together (widths up to %d, enc_dense1 with %d inputs, 1 to %d taps of bits_dense)", LPCN_DRED_MAX_UNITS, LPCN_DRED_ENC_IN, LPCN_DRED_ENC_MAX_TAPS); return LPCN_E_MODEL; }
+    if (e->denc_present != 1 && e->denc_present != 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED encoder arrays are incomplete, mix float and int8, or do not fit together (widths up to %d, enc_dense1 with %d inputs, 1 to %d taps of bits_dense)", LPCN_DRED_MAX_UNITS, LPCN_DRED_ENC_IN, LPCN_DRED_ENC_MAX_TAPS); return LPCN_E_MODEL; }
+    if (!e->denc_servable && e->denc_present == 2) { snprintf(g_err, sizeof(g_err), "the blob's DRED encoder is int8 (DOT_PROD) but its LPCNet model is float: int8 encoder arrays are served beside an int8 model"); return LPCN_E_MODEL; }
     if (!e->denc_servable) { snprintf(g_err, sizeof(g_err), "the blob's DRED encoder is float but its LPCNet model is int8: float encoder arrays are served beside a float model"); return LPCN_E_MODEL; }
     if (max_dframes < 1 || (long long)max_dframes * 2 * b->n > 0x7fffffffLL / 256) { snprintf(g_err, sizeof(g_err), "DRED encoder: max_dframes must be at least 1 (and the batch's rows fit an int)"); return LPCN_E_ARG; }
     DeviceGuard guard(e->device);
     int rc = wait_all(b);
     if (rc) return rc;
-    if (e->denc_host && (rc = denc_upload_net(e))) return rc;
+    if (e->denc_host && (rc = e->is_int8 ? denc_upload_net<int>(e, e->dencq, &e->d_dencq) : denc_upload_net<float>(e, e->denc, &e->d_denc))) return rc;
     if (!denc_form_fits(e, 1)) { snprintf(g_err, sizeof(g_err), "DRED encoder: the encoder's buffers do not fit the LDS"); return LPCN_E_MODEL; }
     if ((rc = denc_prepare_form<1>(e)) || (rc = denc_prepare_form<2>(e)) || (rc = denc_prepare_form<4>(e)) || (rc = denc_prepare_form<8>(e))) return rc;
     if (!b->denc) {
         auto p = std::make_unique<lpcn_denc_host>();
-        p->rec = (size_t)lpcn::rdovae_enc_rec_floats(e->denc);
+        p->rec = (size_t)denc_dims(e).rec;
         if ((rc = p->state.alloc(p->rec * b->n)) || (rc = p->d_cnt.alloc((size_t)b->n)) || (rc = p->h_cnt.reserve(sizeof(int) * (size_t)b->n))) return rc;
         HIP_TRY(hipMemsetAsync(p->state, 0, sizeof(float) * p->rec * b->n, e->stream));      // (DRED_rdovae_init_encoder; done before the call returns: the first
         HIP_TRY(hipStreamSynchronize(e->stream));                                            //  encode may go to any stream)
@@ -99,10 +112,16 @@ extern "C" int lpcn_batch_dev_dred_enc_enable(lpcn_batch_dev *b, int max_dframes
 }
 #define NEED_DENC(b) do { if (!(b)->denc) { snprintf(g_err, sizeof(g_err), "the DRED encoder is not enabled on this batch (lpcnet_batch_dred_enc_enable)"); return LPCN_E_MODEL; } } while (0)
 
+extern "C" int lpcn_batch_dev_dred_enc_flavour(const lpcn_batch_dev *b)
+{
+    NEED_DENC(b);
+    return b->e->is_int8 ? 1 : 0;
+}
+
 extern "C" int lpcn_batch_dev_dred_enc_info(const lpcn_batch_dev *b, int *info)
 {
     NEED_DENC(b);
-    const lpcn::DredEncNet &P = b->e->denc;
+    const DencDims P = denc_dims(b->e);
     info[0] = b->denc->max_dframes; info[1] = LPCN_DRED_ENC_IN; info[2] = P.latent_dim; info[3] = P.state_dim; info[4] = P.taps; info[5] = P.total;
     info[6] = P.gru_floats + (P.taps - 1) * P.total;
     return 0;
@@ -110,7 +129,8 @@ extern "C" int lpcn_batch_dev_dred_enc_info(const lpcn_batch_dev *b, int *info)
 
 // ---- streams per workgroup.  The table is the decoder's (engine_dred.hip): a workgroup's time per double frame is set by its dependent add chains, not
 // by how many streams it carries, so the fewest streams per workgroup that still put the streams on the CUs in one round, eight beyond that -- among
-// the forms whose buffers fit the LDS.  Measured in profiles/dred_enc_rate.json.
+// the forms whose buffers fit the LDS.  Measured in profiles/dred_enc_rate.json, and for an int8 blob's encoder, which shares the
+// table, in profiles/dred_enc_i8_rate.json (§4.8).
 extern "C" int lpcn_batch_dev_dred_enc_form(const lpcn_batch_dev *b, int n)
 {
     NEED_DENC(b);
@@ -126,7 +146,7 @@ extern "C" int lpcn_batch_dev_dred_enc_set_form(lpcn_batch_dev *b, int S)
 {
     NEED_DENC(b);
     if (S != 0 && S != 1 && S != 2 && S != 4 && S != 8) { snprintf(g_err, sizeof(g_err), "DRED encoder form: 1, 2, 4 or 8 streams per workgroup, 0 = the table's choice"); return LPCN_E_ARG; }
-    if (S && !denc_form_fits(b->e, S)) { snprintf(g_err, sizeof(g_err), "DRED encoder form: the buffers of %d streams (%zu bytes) do not fit a workgroup's LDS", S, (size_t)lpcn::rdovae_enc_lds_floats(b->e->denc, S) * sizeof(float)); return LPCN_E_ARG; }
+    if (S && !denc_form_fits(b->e, S)) { snprintf(g_err, sizeof(g_err), "DRED encoder form: the buffers of %d streams (%zu bytes) do not fit a workgroup's LDS", S, denc_lds_bytes(b->e, S)); return LPCN_E_ARG; }
     b->denc->form = S;
     return 0;
 }
@@ -150,9 +170,13 @@ extern "C" int lpcn_batch_dev_dred_enc_check(const lpcn_batch_dev *b, const int 
 template <int S>
 static void denc_launch_form(const lpcn_batch_dev *b, hipStream_t st, const int *d_cnt, int uniform, const float *d_feat, int stride, float *d_lat, float *d_init)
 {
-    const int grid = (b->active + S - 1) / S, lds = lpcn::rdovae_enc_lds_floats(b->e->denc, S) * (int)sizeof(float);
-    hipLaunchKernelGGL(lpcn::rdovae_enc_kernel<S>, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, b->e->d_denc, b->active, b->denc->max_dframes, d_cnt, uniform,
-                       d_feat, stride, (float *)b->denc->state, d_lat, d_init);
+    const int grid = (b->active + S - 1) / S, lds = (int)denc_lds_bytes(b->e, S);
+    if (b->e->is_int8)
+        hipLaunchKernelGGL(lpcn::rdovae_enc_i8_kernel<S>, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, b->e->d_dencq, b->active, b->denc->max_dframes, d_cnt,
+                           uniform, d_feat, stride, (float *)b->denc->state, d_lat, d_init);
+    else
+        hipLaunchKernelGGL(lpcn::rdovae_enc_kernel<S>, dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, b->e->d_denc, b->active, b->denc->max_dframes, d_cnt, uniform,
+                           d_feat, stride, (float *)b->denc->state, d_lat, d_init);
 }
 
 // checks, the counts' upload through the pinned buffer (none for the uniform form), one launch
@@ -204,7 +228,7 @@ extern "C" int lpcn_batch_dev_dred_encode_host(lpcn_batch_dev *b, const float *f
     if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     lpcn_denc_host *p = b->denc.get();
-    const lpcn::DredEncNet &P = b->e->denc;
+    const DencDims P = denc_dims(b->e);
     hipStream_t st = b->e->stream;
     const size_t n = (size_t)b->active, per_f = 2 * (size_t)p->max_dframes * stride, per_l = (size_t)p->max_dframes * P.latent_dim,
                  per_i = (size_t)p->max_dframes * P.state_dim;
@@ -230,7 +254,7 @@ extern "C" int lpcn_batch_dev_dred_enc_get_state(lpcn_batch_dev *b, int s, float
 {
     NEED_DENC(b);
     lpcn_denc_host *p = b->denc.get();
-    const lpcn::DredEncNet &P = b->e->denc;
+    const DencDims P = denc_dims(b->e);
     if (!out) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
     std::vector<float> r(p->rec);
     int rc = stream_rec(b, s, p->state, p->rec, r.data(), nullptr);

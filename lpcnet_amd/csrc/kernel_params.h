@@ -70,32 +70,48 @@ struct PlcData {
 
 // the DRED decoder on the device (dred_decode_kernel), a device-resident block the kernel walks step by step: three dense layers from the initial
 // state to the GRU states, the eight layers of a latent, dec_final.  The blob's arrays as they are, the sparse GRU input matrices with per-row-group
-// starts (GruLayer).  x / out: where a step reads and writes in the concatenated buffer, in cells of S floats (x < 0: the input vector)
-struct DredStep {
+// starts (GruLayer).  x / out: where a step reads and writes in the concatenated buffer, in cells of S floats (x < 0: the input vector).  W = float:
+// a float blob's (DredStep, DredNet); W = int: an int8 (DOT_PROD) blob's, whose dense layers are float too and whose GRUs are GruLayer<int>'s
+// (dred_decode_i8_kernel).  The float record's layout is the same in both
+template <typename W>
+struct DredStepT {
     int gru;                         // 0: dense, tanh; 1: GRU (out = its state's segment)
     int n_in, n_out, x, out;
-    const float *w, *b, *rec;        // dense [n_in][n_out], [n_out]; GRU blocks [nb][4][8], bias [2][3 n_out], recurrent [n_out][3 n_out]
-    const int *start, *pos;          // GRU: [3 n_out / 8 + 1] first block of a row group, [blocks] input position of a block
+    union {
+        const float *w;              // dense [n_in][n_out]
+        const W *gw;                 // GRU blocks: float [nb][4][8], int [nb][8 rows]
+    };
+    const float *b;                  // dense [n_out]; GRU bias [2][3 n_out]
+    const W *rec;                    // GRU recurrent: float [n_out][3 n_out], int block-major [n_out / 4][3 n_out]
+    const int *start, *pos;          // GRU: [3 n_out / 8 + 1] first block of a row group, [blocks] input position (int: input dword) of a block
 };
-struct DredNet {
+using DredStep = DredStepT<float>;
+template <typename W>
+struct DredNetT {
     int latent_dim, state_dim, max_gru, total;       // (total: the buffer's length = dec_final's inputs)
-    DredStep init[3], step[8];
+    DredStepT<W> init[3], step[8];
     const float *final_w, *final_b;                  // [total][80], [80]
     const float *tansig;
 };
+using DredNet = DredNetT<float>;
+using DredNetQ = DredNetT<int>;
 
 // the DRED encoder on the device (rdovae_enc_kernel), walked like the decoder's block: the eight layers of a double frame, gdense1 (from the buffer's
 // start to the cells behind it), then the two layers that read no DredStep cell range: bits_dense over the window and gdense2, straight to the outputs.
 // A stream's state record in global memory: the three GRU states (gru_floats, at gru_off[g] of the buffer), the conv memory as a ring of taps - 1
-// slots of `total` floats, and the ring's head (int): the slot of the oldest tap
-struct DredEncNet {
+// slots of `total` floats, and the ring's head (int): the slot of the oldest tap.  W as in DredNetT (int: rdovae_enc_i8_kernel); the state record is
+// float in both
+template <typename W>
+struct DredEncNetT {
     int latent_dim, state_dim, max_gru, total, taps, gd1, gru_floats;
     int gru_off[3], gru_n[3];
-    DredStep step[9];                                // (step[8]: gdense1)
+    DredStepT<W> step[9];                            // (step[8]: gdense1)
     const float *bits_w, *bits_b;                    // [taps total][latent], [latent]
     const float *g2_w, *g2_b;                        // [gd1][state], [state]
     const float *tansig;
 };
+using DredEncNet = DredEncNetT<float>;
+using DredEncNetQ = DredEncNetT<int>;
 
 // a compacted group's rows in and out (group_gather_kernel, group_scatter_kernel)
 struct GroupRows {

@@ -429,6 +429,7 @@ int  lpcn_engine_dred_present(const lpcn_engine *e);          /* lpcn_dred_model
 int  lpcn_batch_dev_dred_enable(lpcn_batch_dev *b, int max_latents);
 int  lpcn_batch_dev_dred_enabled(const lpcn_batch_dev *b);    /* max_latents, 0 before lpcn_batch_dev_dred_enable */
 int  lpcn_batch_dev_dred_dims(const lpcn_batch_dev *b, int *latent_dim, int *state_dim);
+int  lpcn_batch_dev_dred_flavour(const lpcn_batch_dev *b);    /* 0 float decoder, 1 int8; LPCN_E_MODEL before dred_enable */
 int  lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S);  /* streams per workgroup: 1, 2, 4, 8; 0 = the table's choice */
 int  lpcn_batch_dev_dred_form(const lpcn_batch_dev *b, int n);/* what a launch over n streams runs with */
 int  lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *count, const int *first, const int *take, long long *rows);   /* the argument checks alone; *rows = sum(take) */
@@ -445,6 +446,7 @@ int  lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *state, cons
  * count array not on a capturing stream (the launch depends on it). */
 int  lpcn_batch_dev_dred_enc_enable(lpcn_batch_dev *b, int max_dframes);
 int  lpcn_batch_dev_dred_enc_enabled(const lpcn_batch_dev *b);/* max_dframes, 0 before lpcn_batch_dev_dred_enc_enable */
+int  lpcn_batch_dev_dred_enc_flavour(const lpcn_batch_dev *b);                /* 0 float encoder, 1 int8; LPCN_E_MODEL before dred_enc_enable */
 int  lpcn_batch_dev_dred_enc_info(const lpcn_batch_dev *b, int *info7);        /* {max_dframes, 40, latent, state, taps, sum of the widths, floats of a stream's state} */
 int  lpcn_batch_dev_dred_enc_set_form(lpcn_batch_dev *b, int S);      /* streams per workgroup: 1, 2, 4, 8 where the buffers fit the LDS; 0 = the table's choice */
 int  lpcn_batch_dev_dred_enc_form(const lpcn_batch_dev *b, int n);    /* what a launch over n streams runs with */

@@ -620,10 +620,11 @@ static int parse_dred(lpcn_dred_model *p, const blob_rec *rec, int n)
     return 0;
 }
 
-/* Float decoder arrays beside a float LPCNet model are served; int8 (DOT_PROD) GRU arrays are not. */
+/* The decoder is served in its blob's own flavour, like the PLC network: float arrays beside a float LPCNet model, int8 (DOT_PROD) GRU arrays beside an
+ * int8 one. */
 int lpcn_dred_servable(const lpcn_model_host *m)
 {
-    return m->dred.present == 1 && !m->is_int8;
+    return (m->dred.present == 1 && !m->is_int8) || (m->dred.present == 2 && m->is_int8);
 }
 
 /* The DRED encoder of the blob, bound by the names of rdovae_enc_arrays (enc_dense1..8, bits_dense, gdense1, gdense2), wherever they stand.  The
@@ -677,10 +678,10 @@ static int parse_dred_enc(lpcn_dred_enc_model *p, const blob_rec *rec, int n)
     return 0;
 }
 
-/* Float encoder arrays beside a float LPCNet model are served; int8 (DOT_PROD) GRU arrays are not. */
+/* The encoder is served in its blob's own flavour too. */
 int lpcn_dred_enc_servable(const lpcn_model_host *m)
 {
-    return m->dred_enc.present == 1 && !m->is_int8;
+    return (m->dred_enc.present == 1 && !m->is_int8) || (m->dred_enc.present == 2 && m->is_int8);
 }
 
 /* int8 recurrent weights of a PLC GRU for plc_pred_i8_kernel: the blob has [3 N / 8 row groups][N / 4 blocks][8 rows][4 cols]

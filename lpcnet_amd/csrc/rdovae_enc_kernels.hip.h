@@ -10,6 +10,10 @@
 // the conv memory -- the taps - 1 earlier buffers -- stays in the record, a ring of taps - 1 slots that the window's sum reads from global memory (it is
 // read once per double frame and lies in L2), so the LDS holds one buffer per stream whatever the taps.  A lane of the window's sum owns one (output,
 // stream): one add chain of taps x total terms, the longest of a double frame.
+//
+// An int8 (DOT_PROD) blob's encoder is the same walk, bit for bit like the reference's generic-C int8 build: its dense layers, its conv1d and its state
+// are float, only the three GRUs differ (gru_b_i8, frame_nets.hip.h).  One body, two kernels: rdovae_enc_kernel<S> for a float block,
+// rdovae_enc_i8_kernel<S> for an int8 one.
 #pragma once
 #include "dred_kernels.hip.h"      // dred_step: the walk over DredStep records, shared with the decoder
 
@@ -18,17 +22,25 @@ namespace lpcn {
 constexpr int RDOVAE_ENC_IN = LPCN_DRED_ENC_IN;
 
 // floats of one stream's record: the GRU states, the ring, its head
-__host__ __device__ inline int rdovae_enc_rec_floats(const DredEncNet &P) { return P.gru_floats + (P.taps - 1) * P.total + 1; }
-// floats of dynamic LDS a workgroup of S streams needs: the buffer with gdense1's output behind it, the input vector, the GRUs' two scratch arrays
-__host__ __device__ inline int rdovae_enc_lds_floats(const DredEncNet &P, int S) { return S * (P.total + P.gd1 + RDOVAE_ENC_IN + 6 * P.max_gru); }
+template <typename W>
+__host__ __device__ inline int rdovae_enc_rec_floats(const DredEncNetT<W> &P) { return P.gru_floats + (P.taps - 1) * P.total + 1; }
+// floats of dynamic LDS a workgroup of S streams needs: the buffer with gdense1's output behind it, the input vector, the GRUs' two scratch arrays --
+// and for an int8 block the GRUs' quantised input and old state, four int8 per dword
+template <typename W>
+__host__ __device__ inline int rdovae_enc_lds_floats(const DredEncNetT<W> &P, int S)
+{
+    const int q = std::is_same<W, float>::value ? 0 : (dred_gru_in(P.step) + P.max_gru) / 4;
+    return S * (P.total + P.gd1 + RDOVAE_ENC_IN + 6 * P.max_gru + q);
+}
 
 // Workgroup w encodes streams [w S, w S + S) of the n active ones.  count [n] double frames per stream, or NULL: `uniform` for every one.  features
 // [n][2 max_dframes][stride], the first 20 floats of a row read; state [n][rdovae_enc_rec_floats]; latents [n][max_dframes][latent_dim], initial
 // [n][max_dframes][state_dim], rows below a stream's count written.  A stream whose count is below its workgroup's largest neither writes nor advances
 // once its own double frames are through; one with count 0 is not touched at all.
-template <int S>
-__global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_kernel(const DredEncNet *P, int n, int max_dframes, const int *count, int uniform,
-                                                                   const float *features, int stride, float *state, float *latents, float *initial)
+// The body of both flavours: W = float a float blob's kernel, W = int an int8 blob's, which differ in the GRUs alone (dred_step).
+template <int S, typename W>
+__device__ __forceinline__ void rdovae_enc_body(const DredEncNetT<W> *P, int n, int max_dframes, const int *count, int uniform, const float *features,
+                                                int stride, float *state, float *latents, float *initial)
 {
     extern __shared__ float4 rdovae_enc_lds[];
     __shared__ int cnt[S], live[S], head[S];
@@ -39,6 +51,8 @@ __global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_kernel(const DredEncN
     float *xin = buf + S * (total + P->gd1);
     float *zrh = xin + S * RDOVAE_ENC_IN;
     float *recur = zrh + S * 3 * P->max_gru;
+    int *xq = nullptr, gru_in = 0;
+    if constexpr (!std::is_same<W, float>::value) { xq = (int *)(recur + S * 3 * P->max_gru); gru_in = dred_gru_in(P->step); }
     const int s0 = blockIdx.x * S, t = threadIdx.x;
     if (t < S) {
         const int c = s0 + t < n ? (count ? count[s0 + t] : uniform) : 0, rec = rdovae_enc_rec_floats(*P);
@@ -68,7 +82,7 @@ __global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_kernel(const DredEncN
         // dred_rdovae_encode_dframe (src/dred_rdovae_enc.c:52-84): dense 1, GRU 2, dense 3, GRU 4, dense 5, GRU 6, dense 7, dense 8 -- and gdense1
         // behind the buffer (:91), which the window's sum does not read
 #pragma unroll 1
-        for (int k = 0; k < 9; ++k) dred_step<S>(&P->step[k], buf, xin, zrh, recur, tansig, live);
+        for (int k = 0; k < 9; ++k) dred_step<S, W>(&P->step[k], buf, xin, zrh, recur, xq, gru_in, tansig, live);
         // bits_dense over the window (:87), linear: one lane per (output, stream), the earlier buffers from the stream's ring, this one from LDS
         {
             const int latent_dim = P->latent_dim, taps = P->taps;
@@ -119,6 +133,20 @@ __global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_kernel(const DredEncN
         }
     }
     if (t < S && cnt[t] > 0) { const int rec = rdovae_enc_rec_floats(*P); ((int *)(state + (size_t)(s0 + t) * rec))[rec - 1] = head[t]; }
+}
+
+template <int S>
+__global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_kernel(const DredEncNet *P, int n, int max_dframes, const int *count, int uniform,
+                                                                   const float *features, int stride, float *state, float *latents, float *initial)
+{
+    rdovae_enc_body<S, float>(P, n, max_dframes, count, uniform, features, stride, state, latents, initial);
+}
+// ... and an int8 (DOT_PROD) blob's: the dense layers and the state record float, the GRUs compute_gruB of the reference's generic-C int8 build
+template <int S>
+__global__ __launch_bounds__(DRED_THREADS) void rdovae_enc_i8_kernel(const DredEncNetQ *P, int n, int max_dframes, const int *count, int uniform,
+                                                                      const float *features, int stride, float *state, float *latents, float *initial)
+{
+    rdovae_enc_body<S, int>(P, n, max_dframes, count, uniform, features, stride, state, latents, initial);
 }
 
 }  // namespace lpcn

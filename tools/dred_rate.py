@@ -2,6 +2,7 @@
 """Device time of one DRED decode (lpcnet_batch_dred_decode_device) of a large batch, in every form of the kernel.
 
     python tools/dred_rate.py OUT.json [latents]       (profiles/dred_rate.json when run for the record)
+    python tools/dred_rate.py --int8 OUT.json [latents]       (profiles/dred_i8_rate.json: the int8 decoder beside the float one)
 
 For 256, 2 048 and 8 192 streams, 25 latents each (one second of redundancy) at the exported width of 256: the time of one call (HIP events
 around the enqueue-only device-pointer call, on a caller's stream) with the streams per workgroup pinned to 1, 2, 4, 8 and left to the engine's
@@ -10,7 +11,11 @@ then the median, the extremes and the 10th / 90th percentiles of at least 20 tim
 10th-to-90th range among its forms: what a difference between two medians has to beat.  Every form's output is compared with form 1's, bit for
 bit.  Where oracle/_ref exists the tool also times one stream on the reference's AVX2 + FMA float build (liblpcnet_ref_af.so), the decoder
 chained from its layer functions as tests/tools/make_golden_dred.py chains it, on one core: the CPU yardstick.  One process; the tool stops at
-the first failure.  Run it under a time limit:
+the first failure.
+--int8: the same blob widths as an int8 (DOT_PROD) blob (tests/tools/dred_i8_model.py) on a second batch beside the float one; flavours and forms
+alternate call by call in the one process, so that int8 and float see the same clocks.  `streams` holds the int8 rows, `float_streams` the float
+rows of the same session, `int8_over_float` the ratio of the medians per stream count at the table's form and at each flavour's best pinned form;
+the CPU yardstick is the reference's AVX2 int8 build (liblpcnet_ref_ai.so).  Run it under a time limit:
     timeout -k 10 600 python tools/dred_rate.py profiles/dred_rate.json
 """
 import json
@@ -29,9 +34,9 @@ STREAMS = (256, 2048, 8192)
 TIMED, WARMUP = 20, 2
 
 
-def cpu_yardstick(blob, state, latents):
-    """one stream's chain on the reference's af build, best of three: ms per latent"""
-    path = os.path.join(ROOT, "oracle", "_ref", "liblpcnet_ref_af.so")
+def cpu_yardstick(blob, state, latents, int8=False):
+    """one stream's chain on the reference's af build (int8: ai), best of three: ms per latent"""
+    path = os.path.join(ROOT, "oracle", "_ref", "liblpcnet_ref_ai.so" if int8 else "liblpcnet_ref_af.so")
     if not os.path.exists(path):
         return None
     import make_golden_dred as mg
@@ -42,68 +47,92 @@ def cpu_yardstick(blob, state, latents):
         dec.decode(state, latents, latents.shape[0])
         dt = time.perf_counter() - t0
         best = dt if best is None else min(best, dt)
-    return dict(build="af (AVX2 + FMA, float)", latents=int(latents.shape[0]), ms_per_latent=1e3 * best / latents.shape[0],
+    return dict(build="ai (AVX2, int8 GRUs)" if int8 else "af (AVX2 + FMA, float)", latents=int(latents.shape[0]), ms_per_latent=1e3 * best / latents.shape[0],
                 note="one stream, one core, through ctypes: two calls per layer")
 
 
-def measure(out_path, n_latents=25):
+def form_rows(n, n_latents, ms, runs):
+    """one stream count's row from the timed calls of every form"""
+    row = dict(streams=n, table_form=runs[0], forms=[])
+    for f in FORMS:
+        v = np.array(ms[f])
+        row["forms"].append(dict(form=f, streams_per_workgroup=runs[f], median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()),
+                                 p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)),
+                                 us_per_stream_latent=float(1e3 * np.median(v) / (n * n_latents))))
+    pinned = [r for r in row["forms"] if r["form"]]
+    best = min(pinned, key=lambda r: r["median_ms"])
+    row["spread_ms"] = max(r["p90_ms"] - r["p10_ms"] for r in row["forms"])
+    row["best_pinned_form"] = best["form"]
+    row["table_within_spread_of_best"] = bool(row["forms"][-1]["median_ms"] <= best["median_ms"] + row["spread_ms"])
+    row["best_wide_form_gain_over_one_ms"] = float(pinned[0]["median_ms"] - min(r["median_ms"] for r in pinned[1:]))
+    return row
+
+
+def measure(out_path, n_latents=25, int8=False):
     import torch
     import dred_model as dm
     from lpcnet_amd import api
     dev = torch.device("cuda:0")
-    blob = dm.set_blob("w256")
-    info = api.dred_model_info(blob)
+    blobs = {"float": dm.set_blob("w256")}
+    if int8:
+        import dred_i8_model as di
+        blobs["int8"] = di.blob_dec("w256")
+    main = "int8" if int8 else "float"
+    info = api.dred_model_info(blobs[main])
     base_state, base_lat = dm.inputs(info["latent_dim"], 64, n_latents, seed=0x2A7E)
-    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), widths=info["widths"], latent_dim=info["latent_dim"], latents=n_latents,
-                  timed_calls=TIMED, warmup_calls=WARMUP, note="forms alternate call by call in one process and batch; ms of one decode call by HIP events", streams=[])
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), flavour=main, widths=info["widths"], latent_dim=info["latent_dim"],
+                  latents=n_latents, timed_calls=TIMED, warmup_calls=WARMUP,
+                  note="forms%s alternate call by call in one process; ms of one decode call by HIP events" % (" and flavours" if int8 else ""), streams=[])
+    if int8:
+        result["float_streams"], result["int8_over_float"] = [], []
     s = torch.cuda.Stream()
     for n in STREAMS:
-        b = api.LPCNetBatch(n, blob)
-        b.dred_enable(n_latents)
+        batch = {}
+        for fl, blob in blobs.items():
+            batch[fl] = api.LPCNetBatch(n, blob)
+            batch[fl].dred_enable(n_latents)
+            assert batch[fl].dred_flavour() == (fl == "int8")
         reps = n // 64 + 1
         d_state = torch.from_numpy(np.ascontiguousarray(np.tile(base_state, (reps, 1))[:n])).to(dev)
         d_lat = torch.from_numpy(np.ascontiguousarray(np.tile(base_lat, (reps, 1, 1))[:n])).to(dev)
         d_out = torch.zeros((n, 4 * n_latents, 20), dtype=torch.float32, device=dev)
         count = np.full(n, n_latents, np.int32)
         torch.cuda.synchronize()
-        ms = {f: [] for f in FORMS}
-        runs = {}
-        want = None
+        ms = {fl: {f: [] for f in FORMS} for fl in blobs}
+        runs = {fl: {} for fl in blobs}
+        want = {fl: None for fl in blobs}
         with torch.cuda.stream(s):
             for k in range(WARMUP + TIMED):
                 for f in FORMS:
-                    runs[f] = b.dred_form(f)
-                    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record(s)
-                    b.dred_decode_device(d_state.data_ptr(), d_lat.data_ptr(), count, d_out.data_ptr(), hip_stream=s.cuda_stream)
-                    e.record(s)
-                    e.synchronize()
-                    if k >= WARMUP:
-                        ms[f].append(a.elapsed_time(e))
-                    elif k == 0:
-                        got = d_out.clone()
-                        if want is None:
-                            want = got
-                        elif not torch.equal(got.view(torch.int32), want.view(torch.int32)):
-                            raise SystemExit("form %d differs from form 1 at %d streams" % (f, n))
-        b.dred_form(0)
-        b.close()
-        row = dict(streams=n, table_form=runs[0], forms=[])
-        for f in FORMS:
-            v = np.array(ms[f])
-            row["forms"].append(dict(form=f, streams_per_workgroup=runs[f], median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()),
-                                     p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)),
-                                     us_per_stream_latent=float(1e3 * np.median(v) / (n * n_latents))))
-        pinned = [r for r in row["forms"] if r["form"]]
-        best = min(pinned, key=lambda r: r["median_ms"])
-        row["spread_ms"] = max(r["p90_ms"] - r["p10_ms"] for r in row["forms"])
-        row["best_pinned_form"] = best["form"]
-        row["table_within_spread_of_best"] = bool(row["forms"][-1]["median_ms"] <= best["median_ms"] + row["spread_ms"])
-        row["best_wide_form_gain_over_one_ms"] = float(pinned[0]["median_ms"] - min(r["median_ms"] for r in pinned[1:]))
-        print(json.dumps(row), flush=True)
-        result["streams"].append(row)
-    result["cpu_reference"] = cpu_yardstick(blob, base_state[0], base_lat[0])
-    print(json.dumps(dict(cpu_reference=result["cpu_reference"])), flush=True)
+                    for fl, b in batch.items():
+                        runs[fl][f] = b.dred_form(f)
+                        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record(s)
+                        b.dred_decode_device(d_state.data_ptr(), d_lat.data_ptr(), count, d_out.data_ptr(), hip_stream=s.cuda_stream)
+                        e.record(s)
+                        e.synchronize()
+                        if k >= WARMUP:
+                            ms[fl][f].append(a.elapsed_time(e))
+                        elif k == 0:
+                            got = d_out.clone()
+                            if want[fl] is None:
+                                want[fl] = got
+                            elif not torch.equal(got.view(torch.int32), want[fl].view(torch.int32)):
+                                raise SystemExit("%s: form %d differs from form 1 at %d streams" % (fl, f, n))
+        for b in batch.values():
+            b.dred_form(0)
+            b.close()
+        rows = {fl: form_rows(n, n_latents, ms[fl], runs[fl]) for fl in blobs}
+        print(json.dumps(rows), flush=True)
+        result["streams"].append(rows[main])
+        if int8:
+            result["float_streams"].append(rows["float"])
+            med = lambda row, form: [r for r in row["forms"] if r["form"] == form][0]["median_ms"]
+            result["int8_over_float"].append(dict(streams=n, table_form=med(rows["int8"], 0) / med(rows["float"], 0),
+                                                  best_pinned_form=med(rows["int8"], rows["int8"]["best_pinned_form"]) / med(rows["float"], rows["float"]["best_pinned_form"]),
+                                                  spread_ms=max(rows["int8"]["spread_ms"], rows["float"]["spread_ms"])))
+    result["cpu_reference"] = cpu_yardstick(blobs[main], base_state[0], base_lat[0], int8)
+    print(json.dumps(dict(cpu_reference=result["cpu_reference"], int8_over_float=result.get("int8_over_float"))), flush=True)
     with open(out_path, "w") as fh:
         json.dump(result, fh, indent=1)
         fh.write("\n")
@@ -113,4 +142,4 @@ if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if not args:
         raise SystemExit(__doc__)
-    measure(args[0], int(args[1]) if len(args) > 1 else 25)
+    measure(args[0], int(args[1]) if len(args) > 1 else 25, int8="--int8" in sys.argv[1:])
