@@ -231,6 +231,14 @@ LPCNET_EXPORT int lpcnet_batch_set_plc_state(LPCNetBatch *b, int stream, const v
  * them -> ceps36 [n][36]; compute_plc_pred (src/lpcnet_plc.c:135-146) on every stream's network state (which advances): in57 [n][57] -> out20 [n][20] */
 LPCNET_EXPORT int lpcnet_batch_plc_burg(LPCNetBatch *b, const float *x, float *ceps36);
 LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20);
+/* The PLC network runs with 1, 2, 4 or 8 streams per workgroup: a workgroup loads a weight once for all its streams, and every stream's flags and
+ * output bits are what they are at one stream per workgroup.  plc_set_pred_form pins S (0 = the engine's table; anything else is LPCNET_HIP_E_ARG)
+ * on every shard, for tests and tools; plc_get_pred_form: what a prediction launch over n_streams streams runs with on shard 0 -- the pinned or the
+ * table's value, halved until the form's LDS fits the network's widths.  lpcnet_hip_plc_pred_form is that rule alone, no device: n_records records
+ * on a device of `cus` compute units, a network of widths d1 / g1 / g2, int8 != 0 for an int8 blob, pinned as above -> S, or LPCNET_HIP_E_ARG. */
+LPCNET_EXPORT int lpcnet_batch_plc_set_pred_form(LPCNetBatch *b, int S);
+LPCNET_EXPORT int lpcnet_batch_plc_get_pred_form(const LPCNetBatch *b, int n_streams);
+LPCNET_EXPORT int lpcnet_hip_plc_pred_form(int n_records, int cus, int d1, int g1, int g2, int int8, int pinned);
 /* the host planner alone, no device (tests): ctl [n][9] ints in and out, fec_op [n] or NULL (1 vector added, 2 NULL skip, 3 clear, 4 two vectors
  * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
  * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */

@@ -51,6 +51,17 @@ def plc_plan(options: int, ctl: np.ndarray, lost, fec_op=None):
     return out
 
 
+def plc_pred_form_table(n_records: int, cus: int, d1: int, g1: int, g2: int, int8: bool = False, pinned: int = 0) -> int:
+    """The PLC prediction kernels' form rule alone (no device): the streams per workgroup (1, 2, 4, 8) a launch over n_records records runs with on a
+    device of `cus` compute units, for a network of widths d1 / g1 / g2 (float or int8).  pinned = 0: the table's choice, else the pinned value;
+    either way halved until the form's LDS fits"""
+    L = load_library()
+    rc = L.lpcnet_hip_plc_pred_form(n_records, cus, d1, g1, g2, 1 if int8 else 0, pinned)
+    if rc < 0:
+        raise LPCNetError("plc_pred_form_table failed (%d): %s" % (rc, last_error()))
+    return rc
+
+
 PLC_LANES_REC = 10
 
 
@@ -205,6 +216,9 @@ def load_library():
     L.lpcnet_batch_dred_decode_packed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_info.argtypes = [vp, C.POINTER(C.c_int)]
     L.lpcnet_batch_dred_flavour.argtypes = [vp]
+    L.lpcnet_batch_plc_set_pred_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_plc_get_pred_form.argtypes = [vp, C.c_int]
+    L.lpcnet_hip_plc_pred_form.argtypes = [C.c_int] * 7
     L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
     L.lpcnet_hip_dred_enc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
@@ -846,6 +860,16 @@ class LPCNetBatch:
         out = np.empty((self.n, 20), np.float32)
         self._chk(self.L.lpcnet_batch_plc_pred(self.p, x, out), "plc_pred")
         return out
+
+    def plc_pred_form(self, S=None, n_streams=None) -> int:
+        """S given: pin the streams a workgroup of the PLC network's kernels carries (1, 2, 4, 8; 0 = the engine's table).  Returns what a prediction
+        launch over n_streams (default: the batch's) streams runs with; the output bits are the same in every form"""
+        if S is not None:
+            self._chk(self.L.lpcnet_batch_plc_set_pred_form(self.p, S), "plc_pred_form")
+        rc = self.L.lpcnet_batch_plc_get_pred_form(self.p, self.n if n_streams is None else n_streams)
+        if rc < 0:
+            self._chk(rc, "plc_pred_form")
+        return rc
 
     def encode(self, pcm: np.ndarray) -> np.ndarray:
         """pcm (n, P*640) int16 -> packets (n, P, 8) uint8: lpcnet_encode per stream and packet (codebooks: set_codebooks)"""

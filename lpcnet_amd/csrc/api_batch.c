@@ -344,6 +344,14 @@ int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float *out20)
     if (!in57 || !out20) { set_err("lpcnet_batch_plc_pred: bad arguments"); return LPCN_E_ARG; }
     EACH_SHARD(lpcn_batch_dev_plc_pred_host(s->dev, in57 + (size_t)at.first * LPCN_PLC_IN, out20 + (size_t)at.first * LPCN_NB_FEAT));
 }
+int lpcnet_batch_plc_set_pred_form(LPCNetBatch *b, int S) { NEED_PLC_ON(b); EACH_SHARD(lpcn_batch_dev_plc_pred_set_form(s->dev, S)); }
+int lpcnet_batch_plc_get_pred_form(const LPCNetBatch *b, int n_streams)
+{
+    NEED_PLC_ON(b);
+    const int rc = lpcn_batch_dev_plc_pred_form(b->sh[0].dev, n_streams);
+    if (rc < 0) take_engine_err();
+    return rc;
+}
 /* ---- DRED decoder (DRED_rdovae_decode_all per stream; include/lpcnet_batch.h) ---- */
 #define NEED_DRED_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_dred_enabled((b)->sh[0].dev)) { set_err("the DRED decoder is not enabled on this batch (lpcnet_batch_dred_enable)"); return LPCN_E_MODEL; } } while (0)
 int lpcnet_batch_dred_enable(LPCNetBatch *b, int max_latents) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_dred_enable(s->dev, max_latents)); }

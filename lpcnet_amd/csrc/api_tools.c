@@ -41,6 +41,13 @@ int lpcnet_hip_plc_plan_lanes(int options, int n, int lanes, int *ctl, const uns
     free(before);
     return rc;
 }
+/* the prediction kernels' form rule alone (no device): include/lpcnet_batch.h */
+int lpcnet_hip_plc_pred_form(int n_records, int cus, int d1, int g1, int g2, int int8, int pinned)
+{
+    const int rc = lpcn_plc_pred_form(n_records, cus, d1, g1, g2, int8, pinned);
+    if (rc < 0) set_err("lpcnet_hip_plc_pred_form: pinned must be 0, 1, 2, 4 or 8, n_records at least 0, cus and the widths at least 1");
+    return rc;
+}
 /* the FEC feed's planner alone (no device): ctl as above, count [n], skip / clear [n] or NULL, rec [n][8] out (one record per stream that stores
  * something: stream, first source row, rows a, their ring row, move-from row, rows moved, rows b, their ring row), dropped [n] or NULL.  Returns
  * the number of records. */

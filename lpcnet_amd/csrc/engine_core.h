@@ -248,6 +248,8 @@ int upload_gru(lpcn_engine *e, lpcn::GruLayer<W> &o, const lpcn_gru_layer &g)
 struct lpcn_plc_host {
     int options = 0;
     bool remove_dc = false;
+    int cus = 0;                                    // the device's compute units, for the prediction kernels' form table
+    int pred_form = 0;                              // records per workgroup pinned by lpcn_batch_dev_plc_pred_set_form (0: the table's choice)
     std::vector<lpcn_plc_ctl> ctl;
     DevBuf<short> q, lp;                            // the arrays of lpcn::PlcData (kernel_params.h) ...
     DevBuf<float> feat, net, fec, fbuf, burg, an;

@@ -1,6 +1,7 @@
 // Compacted groups, their lanes and schedule, the per-stream step, packet-loss concealment and its FEC feed.  Owns plc_kernels.hip.h.
 #include "engine_core.h"
 #include "plc_kernels.hip.h"
+#include <mutex>
 
 // ---- compacted groups: a subset of the batch's streams through the ordinary frame and sample kernels (the per-stream-arguments step below
 // and the packet-loss concealment, whose streams take different branches in one step).  The streams of a group are named by an index map on
@@ -246,10 +247,66 @@ extern "C" int lpcn_batch_dev_plc_flavour(const lpcn_batch_dev *b)
     return b->e->is_int8 ? 1 : 0;
 }
 // compute_plc_pred in the flavour of the engine's blob: the same records and data, the float or the int8 network
-static void launch_plc_pred(lpcn_batch_dev *b, hipStream_t st, const int *ctl, int cnt, float *raw_out)
+// ---- records per workgroup.  One workgroup per record reads the whole network through L2 for its one stream; the forms with S = 2, 4, 8 records per
+// workgroup (plc_pred_s_kernel<S>) load a weight once for S streams.  The rule and the measurements behind it: plc_plan.cpp: lpcn_plc_pred_form,
+// DESIGN.md §4.4.
+static int plc_pred_d1(const lpcn_engine *e) { return e->is_int8 ? e->plcq.d1 : e->plc.d1; }
+extern "C" int lpcn_batch_dev_plc_pred_form(const lpcn_batch_dev *b, int n)
 {
-    if (b->e->is_int8) hipLaunchKernelGGL(lpcn::plc_pred_i8_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plcq, ctl, cnt, b->plc->D, raw_out);
-    else hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, b->e->plc, ctl, cnt, b->plc->D, raw_out);
+    if (!b->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; }
+    if (n < 0) { snprintf(g_err, sizeof(g_err), "PLC prediction form: a negative number of records"); return LPCN_E_ARG; }
+    return lpcn_plc_pred_form(n, b->plc->cus, plc_pred_d1(b->e), plc_units(b->e, 0), plc_units(b->e, 1), b->e->is_int8 ? 1 : 0, b->plc->pred_form);
+}
+extern "C" int lpcn_batch_dev_plc_pred_set_form(lpcn_batch_dev *b, int S)
+{
+    if (!b->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; }
+    if (S != 0 && S != 1 && S != 2 && S != 4 && S != 8) { snprintf(g_err, sizeof(g_err), "PLC prediction form: 1, 2, 4 or 8 records per workgroup, 0 = the table's choice"); return LPCN_E_ARG; }
+    b->plc->pred_form = S;
+    return 0;
+}
+template <int S, typename Net>
+static int plc_pred_launch_form(const Net &P, int grid, int lds, hipStream_t st, const int *ctl, int cnt, const lpcn::PlcData &D, float *raw_out)
+{
+    // the dynamic-LDS limit of a form is raised once per (device, size), not at every launch
+    static std::mutex mu;
+    static int limit[64];
+    const auto kernel = [] { if constexpr (std::is_same<Net, lpcn::PlcNet>::value) return lpcn::plc_pred_s_kernel<S>; else return lpcn::plc_pred_s_int8_kernel<S>; }();
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (dev < 0 || dev >= 64 || limit[dev] < lds) {
+            HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            if (dev >= 0 && dev < 64) limit[dev] = lds;
+        }
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(lpcn::PLC_PRED_THREADS), lds, st, P, ctl, cnt, D, raw_out);
+    return 0;
+}
+template <typename Net>
+static int plc_pred_launch(const Net &P, int S, int lds, hipStream_t st, const int *ctl, int cnt, const lpcn::PlcData &D, float *raw_out)
+{
+    const int grid = (cnt + S - 1) / S;
+    switch (S) {
+    case 2: return plc_pred_launch_form<2>(P, grid, lds, st, ctl, cnt, D, raw_out);
+    case 4: return plc_pred_launch_form<4>(P, grid, lds, st, ctl, cnt, D, raw_out);
+    default: return plc_pred_launch_form<8>(P, grid, lds, st, ctl, cnt, D, raw_out);
+    }
+}
+// compute_plc_pred in the flavour of the engine's blob: the same records and data, the float or the int8 network, in the form for `cnt` records.  The
+// single launch site: the step's prediction phases and the parity seam.
+static int launch_plc_pred(lpcn_batch_dev *b, hipStream_t st, const int *ctl, int cnt, float *raw_out)
+{
+    const lpcn_engine *e = b->e;
+    const int S = lpcn_batch_dev_plc_pred_form(b, cnt);
+    if (S < 0) return S;
+    if (S > 1) {
+        const int lds = lpcn::plc_pred_lds_bytes(S, plc_pred_d1(e), plc_units(e, 0), plc_units(e, 1), e->is_int8 ? 1 : 0);
+        return e->is_int8 ? plc_pred_launch(e->plcq, S, lds, st, ctl, cnt, b->plc->D, raw_out) : plc_pred_launch(e->plc, S, lds, st, ctl, cnt, b->plc->D, raw_out);
+    }
+    if (e->is_int8) hipLaunchKernelGGL(lpcn::plc_pred_i8_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, e->plcq, ctl, cnt, b->plc->D, raw_out);
+    else hipLaunchKernelGGL(lpcn::plc_pred_kernel, dim3(cnt), dim3(lpcn::PLC_PRED_THREADS), 0, st, e->plc, ctl, cnt, b->plc->D, raw_out);
+    return 0;
 }
 static size_t plc_net_floats(const lpcn_batch_dev *b) { return 4 * (size_t)(plc_units(b->e, 0) + plc_units(b->e, 1)); }
 // lpcnet_plc_reset (src/lpcnet_plc.c:46-60) on streams [first, first + count): the PLC's own fields, the synthesis state, the analysis state
@@ -298,6 +355,7 @@ extern "C" int lpcn_batch_dev_plc_enable(lpcn_batch_dev *b, int options)
         b->plc = std::move(p);
     }
     b->plc->options = options; b->plc->remove_dc = (options & 4) != 0;
+    b->plc->cus = device_cus(b->e);
     return plc_reset_range(b, 0, b->n);
 }
 #define NEED_PLC(b) do { if (!(b)->plc) { snprintf(g_err, sizeof(g_err), "packet-loss concealment is not enabled on this batch (lpcnet_batch_plc_enable)"); return LPCN_E_MODEL; } } while (0)
@@ -358,7 +416,7 @@ extern "C" int lpcn_batch_dev_plc_step(lpcn_batch_dev *b, short *d_pcm, const un
             hipLaunchKernelGGL(lpcn::plc_burg_kernel, dim3(L.cnt), dim3(lpcn::PLC_BURG_THREADS), 0, st, b->e->fmodel, ctl, L.cnt, d_pcm, p->D, p->remove_dc ? 1 : 0);
             break;
         case PLC_T_PRED:
-            launch_plc_pred(b, st, ctl, L.cnt, nullptr);
+            if ((rc = launch_plc_pred(b, st, ctl, L.cnt, nullptr))) { (void)lanes_join(b, ln); return rc; }
             break;
         case PLC_T_MIX:
             hipLaunchKernelGGL(lpcn::plc_mix_kernel, dim3(L.cnt), dim3(lpcn::PLC_MIX_THREADS), 0, st, L.op, ctl, L.cnt, d_pcm, (const short *)b->d_gpcm + (size_t)L.slot * LPCN_FRAME_SIZE, p->D, b->d_state);
@@ -583,7 +641,7 @@ extern "C" int lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57
         HIP_TRY(hipMemcpy(p->an + (size_t)s * LPCN_AN_NB_FEATURES, in + 2 * LPCN_NB_BANDS, sizeof(float) * LPCN_NB_FEAT, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(p->d_ctl, recs.data(), sizeof(int) * recs.size(), hipMemcpyHostToDevice));
-    launch_plc_pred(b, st, p->d_ctl, na, b->d_gfeat.p);
+    { int rcl = launch_plc_pred(b, st, p->d_ctl, na, b->d_gfeat.p); if (rcl) return rcl; }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(out20, b->d_gfeat, sizeof(float) * (size_t)na * LPCN_NB_FEAT, hipMemcpyDeviceToHost));

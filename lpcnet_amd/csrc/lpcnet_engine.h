@@ -419,6 +419,12 @@ int  lpcn_batch_dev_get_plc_state(lpcn_batch_dev *b, int stream, lpcn_plc_state_
 int  lpcn_batch_dev_set_plc_state(lpcn_batch_dev *b, int stream, const lpcn_plc_state_rec *host);
 int  lpcn_batch_dev_plc_burg_host(lpcn_batch_dev *b, const float *x, float *ceps36);
 int  lpcn_batch_dev_plc_pred_host(lpcn_batch_dev *b, const float *in57, float *out20);
+/* Records per workgroup of the prediction kernels (plc_kernels.hip.h: plc_pred_kernel at 1, plc_pred_s_kernel<S> at 2, 4, 8; the output bits are the
+ * same in every form).  set_form pins it (0 = the table's choice); form: what a launch over n records runs with -- the pinned or the table's value,
+ * halved until its LDS fits.  lpcn_plc_pred_form is that rule alone (plc_plan.cpp, no device): LPCN_E_ARG for a pinned value other than 0, 1, 2, 4, 8. */
+int  lpcn_batch_dev_plc_pred_set_form(lpcn_batch_dev *b, int S);
+int  lpcn_batch_dev_plc_pred_form(const lpcn_batch_dev *b, int n);
+int  lpcn_plc_pred_form(int n_records, int cus, int d1, int g1, int g2, int int8, int pinned);
 
 /* DRED decoder (DRED_rdovae_decode_all per stream, dred_kernels.hip.h): one launch decodes every active stream's whole latent chain.
  * Nothing is kept per stream between calls.  state [n][state_dim], latents [n][max_latents][latent_dim], count [n] (host, 0 .. max_latents),

@@ -7,6 +7,7 @@
 //   plc_pred_kernel   compute_plc_pred (src/lpcnet_plc.c:135-146) with its input selection (get_fec_or_pred :148-168), the rotation and
 //                     restoring of plc_copy (:215, :238, :305-306) and the attenuation of features[0] (:323-324)
 //   plc_pred_i8_kernel  the same with the int8 GRUs of the DOT_PROD build (src/vec.h:274-339), for int8 blobs: one body (plc_pred_body), two flavours
+//   plc_pred_s_kernel<S>, plc_pred_s_int8_kernel<S>  either flavour at S = 2, 4 or 8 records per workgroup, bit for bit like the two above
 //   plc_mix_kernel    the PCM queue, the deferred feature queue, the cross-fade, lpcnet_reset_signal, DC restore
 //   group_gather_kernel, group_scatter_kernel   everything a compacted group of streams takes in and gives back, in one launch each: the group
 //                     runs through the ordinary frame and sample kernels
@@ -19,6 +20,7 @@
 #include "lpcnet_plc_tables_gen.h"
 #include "plc_burg.h"
 #include "plc_records.h"      // record sizes, flags and operation codes of the control lists (shared with the host planner)
+#include <type_traits>
 
 namespace lpcn {
 
@@ -310,6 +312,134 @@ __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_kernel(PlcNet P, co
 __global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_i8_kernel(PlcNetQ P, const int *ctl, int cnt, PlcData D, float *raw_out)
 {
     plc_pred_body<PlcInt8>(P, ctl, cnt, D, raw_out);
+}
+
+// ---- S = 2, 4 or 8 records per workgroup: workgroup w takes the records [w S, min(cnt, w S + S)), so a weight read through L2 serves S streams.  The same
+// records, flags and arithmetic as plc_pred_body, stream by stream: each of the S streams keeps its own flags, so the rotation, the restore, the input
+// selection and what becomes of the output are decided per stream; a stream without PLC_F_COMPUTE -- or a slot past the last record -- is not live in
+// the layers, which leave its state alone (gru_b's LIVE mask), and has zeros where the layers read.  The activations lie [j][S] in dynamic LDS
+// (plc_records.h: plc_pred_lds_bytes, sized by the blob's widths), so the S values of an input are one broadcast read of 4 S bytes that every lane of
+// the wave makes at the same address: no bank conflict at any S.  The GRUs are the shared S-stream layers (frame_nets.hip.h): lane = gate row, all S
+// streams; dense1 gives a lane S / 2 streams, so 128 rows fill the 256 lanes at every S, the output layer one (row, stream).
+template <int S, typename W>
+__device__ __forceinline__ void plc_pred_s_body(const PlcNetT<W> &P, const int *ctl, int cnt, const PlcData &D, float *raw_out)
+{
+    extern __shared__ float4 plc_pred_lds[];
+    constexpr bool Q = !std::is_same<W, float>::value;
+    constexpr int AD = S / 2;
+    const int d1 = P.d1, g1 = P.gru[0].n, g2 = P.gru[1].n, G = g1 + g2, mg = plc_pred_max(g1, g2);
+    float *in = (float *)plc_pred_lds;
+    float *x1 = in + S * PLC_PRED_IN_PAD;
+    float *h1 = x1 + S * d1, *h2 = h1 + S * g1;
+    float *zrh = h2 + S * g2, *recur = zrh + S * 3 * mg;
+    float *out = recur + S * 3 * mg;
+    int *xq = (int *)(out + S * LPCN_NB_FEAT), *sq = xq + S * (plc_pred_max(d1, g1) >> 2);      // (an int8 blob's cells; else none)
+    int *rec = Q ? sq + S * (mg >> 2) : xq;                                                       // [S][PLC_PRED_REC]: stream (-1: no record), flags, ...
+    int *live = rec + S * PLC_PRED_REC;
+    const int r0 = blockIdx.x * S, t = threadIdx.x;
+    if (r0 >= cnt) return;
+    if (t < S * PLC_PRED_REC) {
+        const bool have = r0 + t / PLC_PRED_REC < cnt;
+        rec[t] = have ? ctl[(size_t)r0 * PLC_PRED_REC + t] : t % PLC_PRED_REC == 0 ? -1 : 0;
+    }
+    __syncthreads();
+    if (t < S) live[t] = rec[t * PLC_PRED_REC] >= 0 && (rec[t * PLC_PRED_REC + 1] & PLC_F_COMPUTE) ? 1 : 0;
+    bool any = false;
+#pragma unroll
+    for (int a = 0; a < S; ++a) {
+        const int s = rec[a * PLC_PRED_REC], flags = rec[a * PLC_PRED_REC + 1];
+        const bool lv = s >= 0 && (flags & PLC_F_COMPUTE);
+        any |= lv;
+        float *net = D.net + (size_t)(s < 0 ? 0 : s) * 4 * G;
+        const int restore = (flags >> PLC_F_RESTORE_SHIFT) & 3;
+        for (int k = t; k < G; k += PLC_PRED_THREADS) {
+            float v0 = 0.f;
+            if (s >= 0) {
+                v0 = net[k];
+                if (flags & PLC_F_ROT) {
+                    const float v1 = net[G + k], v2 = net[2 * G + k];
+                    net[G + k] = v0; net[2 * G + k] = v1; net[3 * G + k] = v2;
+                }
+                if (restore) { v0 = net[(restore + 1) * G + k]; net[k] = v0; }
+            }
+            if (!lv) v0 = 0.f;
+            if (k < g1) h1[k * S + a] = v0;
+            else h2[(k - g1) * S + a] = v0;
+        }
+    }
+    if (!any) return;                       // (the whole workgroup)
+    for (int e = t; e < LPCN_PLC_IN * S; e += PLC_PRED_THREADS) {
+        const int j = e / S, a = e % S;
+        const int s = rec[a * PLC_PRED_REC], flags = rec[a * PLC_PRED_REC + 1];
+        const int input = (flags >> PLC_F_INPUT_SHIFT) & 3;
+        float v = 0.f;
+        if (s >= 0 && (flags & PLC_F_COMPUTE)) {
+            const float *fec = D.fec + ((size_t)s * LPCN_PLC_MAX_FEC + rec[a * PLC_PRED_REC + 2]) * LPCN_NB_FEAT;
+            if (input >= PLC_IN_BURG && j < 2 * LPCN_NB_BANDS) v = D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j];
+            if (j >= 2 * LPCN_NB_BANDS && j < LPCN_PLC_IN - 1) {
+                if (input == PLC_IN_FEC) v = fec[j - 2 * LPCN_NB_BANDS];
+                if (input == PLC_IN_BURG_FEAT) v = D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS];
+            }
+            if (j == LPCN_PLC_IN - 1) v = input == PLC_IN_FEC ? -1.f : input == PLC_IN_ZEROS ? 0.f : 1.f;
+            if (flags & PLC_F_RAW) v = j < 2 * LPCN_NB_BANDS ? D.burg[(size_t)s * 2 * LPCN_NB_BANDS + j] : j < LPCN_PLC_IN - 1 ? D.an[(size_t)s * LPCN_AN_NB_FEATURES + j - 2 * LPCN_NB_BANDS] : __int_as_float(rec[a * PLC_PRED_REC + 3]);
+        }
+        in[e] = v;
+    }
+    __syncthreads();
+    dense<S, AD, PLC_PRED_THREADS, 3>(LPCN_PLC_IN, d1, P.dense1_w, P.dense1_b, in, [&](int i, int a0, const float (&acc)[AD]) {
+#pragma unroll
+        for (int a = 0; a < AD; ++a) x1[i * S + a0 + a] = lpcn_tanh(acc[a], P.tansig);
+    });
+    __syncthreads();
+    if constexpr (Q) {
+        gru_b_i8<S, PLC_PRED_THREADS, true>(P.gru[0], x1, h1, zrh, recur, xq, sq, P.tansig, live);
+        gru_b_i8<S, PLC_PRED_THREADS, true>(P.gru[1], h1, h2, zrh, recur, xq, sq, P.tansig, live);
+    } else {
+        gru_b<S, PLC_PRED_THREADS, true>(P.gru[0], x1, h1, zrh, recur, P.tansig, live);
+        gru_b<S, PLC_PRED_THREADS, true>(P.gru[1], h1, h2, zrh, recur, P.tansig, live);
+    }
+    dense<S, 1, PLC_PRED_THREADS, 4>(g2, LPCN_NB_FEAT, P.out_w, P.out_b, h2, [&](int i, int a, const float (&sum)[1]) {
+        float acc = sum[0];
+        if (i == LPCN_NB_FEAT - 1) { const float v = acc + .1f; acc = .5f < v ? .5f : v; }      // MIN16(.5f, out[19]+.1f)
+        out[i * S + a] = acc;
+    });
+#pragma unroll
+    for (int a = 0; a < S; ++a) {
+        if (!live[a]) continue;
+        float *net = D.net + (size_t)rec[a * PLC_PRED_REC] * 4 * G;
+        for (int k = t; k < G; k += PLC_PRED_THREADS) net[k] = k < g1 ? h1[k * S + a] : h2[(k - g1) * S + a];
+    }
+    __syncthreads();
+    if (t < LPCN_NB_FEAT * S) {
+        const int i = t / S, a = t % S;
+        if (live[a]) {
+            const int s = rec[a * PLC_PRED_REC], flags = rec[a * PLC_PRED_REC + 1];
+            const int input = (flags >> PLC_F_INPUT_SHIFT) & 3;
+            float v = 0.f;
+            bool write = false;
+            if (input == PLC_IN_FEC) { v = D.fec[((size_t)s * LPCN_PLC_MAX_FEC + rec[a * PLC_PRED_REC + 2]) * LPCN_NB_FEAT + i]; write = true; }
+            else if (flags & PLC_F_KEEP) { v = out[i * S + a]; write = true; }
+            if (write && i == 0 && (flags & PLC_F_ATT)) {
+                v = v + __int_as_float(rec[a * PLC_PRED_REC + 3]);
+                v = v - __int_as_float(rec[a * PLC_PRED_REC + 4]);
+                v = -10.f > v ? -10.f : v;
+            }
+            if (write) D.feat[(size_t)s * LPCN_NB_FEAT + i] = v;
+            if ((flags & PLC_F_RAW) && raw_out) raw_out[(size_t)s * LPCN_NB_FEAT + i] = out[i * S + a];
+        }
+    }
+}
+
+template <int S>
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_s_kernel(PlcNet P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    plc_pred_s_body<S, float>(P, ctl, cnt, D, raw_out);
+}
+// ... and an int8 blob's, with gru_b_i8.  (Named _int8: every *_i8_kernel<int> of the engine is a DRED kernel to the DRED resource tests.)
+template <int S>
+__global__ __launch_bounds__(PLC_PRED_THREADS) void plc_pred_s_int8_kernel(PlcNetQ P, const int *ctl, int cnt, PlcData D, float *raw_out)
+{
+    plc_pred_s_body<S, int>(P, ctl, cnt, D, raw_out);
 }
 
 // Element-wise per-stream operations.  One workgroup per record {stream, a, b}; pcm [n][160] is the call's frame, gpcm the compacted

@@ -309,3 +309,28 @@ extern "C" int lpcn_plc_plan_lanes(int options, int n, int lanes, lpcn_plc_ctl *
     if (!P.ctl.empty()) memcpy(lists, P.ctl.data(), sizeof(int) * P.ctl.size());
     return (int)P.launches.size();
 }
+
+// Records per workgroup of a prediction launch over n_records records on a device of `cus` compute units (engine_plc.hip: launch_plc_pred), for a PLC
+// network of widths d1 / g1 / g2, float or int8.  pinned: 1, 2, 4 or 8, or 0 for the table.  Either way halved until the form's LDS (plc_records.h:
+// plc_pred_lds_bytes) fits a CU's.  LPCN_E_ARG for anything else.
+// The table, as measured on one MI355X (profiles/plc_pred_forms.json) -- it is NOT the DRED kernels' rule.  A workgroup is four waves,
+// one per SIMD, and its time is that of its dependent add chains, so a CU has to hold several workgroups to be busy: a form pays while four of its
+// workgroups still share a CU's LDS (40 KB each) and there are records enough to fill those four places on every CU: the table is the largest such
+// form, else one record per workgroup.  On 256 CUs that is 1 below 2 K records (measured at 256, 512 and 1 024: the fastest or within the run's
+// spread of it), 2 from 2 K (measured at 2 048: the fastest in every row), and from 4 K and 8 K on also 4 and 8 where the LDS allows: at 8 192 records 8 at
+// widths 128 / 16 / 16, 4 at 128 / 256 / 256 and 2 at 512 / 512 / 512, each the fastest pinned form of its row.
+constexpr int PLC_PRED_FORM_SHARE = 4;
+extern "C" int lpcn_plc_pred_form(int n_records, int cus, int d1, int g1, int g2, int int8, int pinned)
+{
+    if (pinned != 0 && pinned != 1 && pinned != 2 && pinned != 4 && pinned != 8) return LPCN_E_ARG;
+    if (n_records < 0 || cus < 1 || d1 < 1 || g1 < 1 || g2 < 1) return LPCN_E_ARG;
+    int S = pinned;
+    if (!S) {
+        S = 1;
+        for (int k = 2; k <= 8; k *= 2)
+            if (plc_pred_lds_bytes(k, d1, g1, g2, int8 != 0) <= PLC_PRED_FORM_LDS_LIMIT / PLC_PRED_FORM_SHARE && (n_records + k - 1) / k >= (long long)PLC_PRED_FORM_SHARE * cus) S = k;
+    }
+    while (S > 1 && plc_pred_lds_bytes(S, d1, g1, g2, int8 != 0) > PLC_PRED_FORM_LDS_LIMIT) S /= 2;
+    return S;
+}
+

@@ -27,6 +27,14 @@ process, the schedule switched between blocks of steps -- off, then each --sched
 every variant sees the same clocks, the same state history and the same loss flags' statistics.  Per loss pattern (0 %, 5 %, 20 % random loss, the
 outage and its recovery) it prints every variant's median over all its blocks, the medians of its single blocks, and the ratio to the off median;
 the spread between the off blocks' medians is the noise a ratio has to beat.  The steps are timed like the runs above.
+
+    python tools/plc_rate.py [--widths D1,G1,G2]... [--pred-form S]... [--loss P]... --forms OUT.json [streams[,streams...]]       (profiles/plc_pred_forms.json)
+
+The PLC network's kernels at 1, 2, 4, 8 streams per workgroup (LPCNetBatch.plc_pred_form).  --widths D1,G1,G2 gives the blob a PLC network of those
+widths (tests/tools/plc_model.blob_widths) and --pred-form S pins the form, for the first run above too.  --forms compares: for the float and the
+int8 model, each --widths and each number of streams, one batch whose form is switched between blocks of steps -- the table's choice, 1, 2, 4, 8,
+or the --pred-form values given -- at each --loss P (default 0: the step of a call without loss).  Run on a build without the forms it measures
+that build alone, as "parent".
 """
 import json
 import os
@@ -126,17 +134,87 @@ def measure_ab(out_path, n, schedules, int8=False, rounds=4, block=12):
         f.write("\n")
 
 
-def measure(out_path, n, int8=False, schedule=None):
-    import torch
+def plc_blob(int8, widths=None):
+    """the test model with the 128 / 16 / 16 PLC network, or (--widths) with one of the given widths (tests/tools/plc_model.blob_widths)"""
+    import plc_model
     import plc_synth
+    from lpcnet_amd import synth
+    if widths:
+        return plc_model.blob_widths(*widths, "int8" if int8 else "float")
+    return synth.blob_bytes(plc_synth.make_model_with_plc(flavour="int8" if int8 else "float"))
+
+
+def measure_forms(out_path, streams, widths_list, losses, pinned=None, rounds=3, block=8):
+    """The prediction kernels' forms side by side: per (flavour, widths, streams, loss) ONE batch, the form switched between blocks of steps -- the
+    table's choice, then 1, 2, 4, 8 pinned (or the --pred-form values alone), round after round -- so that every form sees the same clocks and the
+    same history.  A library without the forms (the parent build) runs as the single variant "parent".  Per variant: the median over all its
+    steps, its blocks' medians and the form a launch over all streams runs with; spread = (largest - smallest block median) / median of the
+    first variant, the noise a difference between variants has to beat."""
+    import torch
     from lpcnet_amd import api, synth
     dev = torch.device("cuda:0")
-    b = api.LPCNetBatch(n, synth.blob_bytes(plc_synth.make_model_with_plc(flavour="int8" if int8 else "float")))
+    has_forms = hasattr(api.LPCNetBatch, "plc_pred_form")
+    variants = ["parent"] if not has_forms else list(pinned) if pinned else [0, 1, 2, 4, 8]
+    T = 100
+    base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), options="LPCNET_PLC_CAUSAL", rounds=rounds, steps_per_block=block,
+                  note="one batch per row, one process; the form alternates between blocks of steps; variant 0 = the table's choice", rows=[])
+    s = torch.cuda.Stream()
+    for int8 in (False, True):
+        for widths in widths_list:
+            blob = plc_blob(int8, widths)
+            for n in streams:
+                b = api.LPCNetBatch(n, blob)
+                b.plc_enable(api.PLC_CAUSAL)
+                frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
+                d = torch.zeros((n, 160), dtype=torch.int16, device=dev)
+                with torch.cuda.stream(s):
+                    for p in losses:
+                        rng = np.random.default_rng(7)
+                        b.plc_reset()
+                        t = 0
+                        for _ in range(20):
+                            d.copy_(frames[t % T]); step_ms(torch, b, d, (rng.uniform(size=n) < p).astype(np.uint8), s); t += 1
+                        blocks = {v: [] for v in variants}
+                        forms = {}
+                        for _ in range(rounds):
+                            for v in variants:
+                                if has_forms:
+                                    forms[v] = b.plc_pred_form(v)
+                                ms = []
+                                for _ in range(block):
+                                    d.copy_(frames[t % T]); ms.append(step_ms(torch, b, d, (rng.uniform(size=n) < p).astype(np.uint8), s)); t += 1
+                                blocks[v].append(ms)
+                        first = float(np.median(np.concatenate(blocks[variants[0]])))
+                        bm0 = [float(np.median(x)) for x in blocks[variants[0]]]
+                        row = dict(flavour="int8" if int8 else "float", widths=list(widths or (128, 16, 16)), streams=n, loss=p, spread=(max(bm0) - min(bm0)) / first, variants=[])
+                        for v in variants:
+                            row["variants"].append(dict(pinned=v, form=forms.get(v), median_ms=float(np.median(np.concatenate(blocks[v]))),
+                                                        block_medians_ms=[float(np.median(x)) for x in blocks[v]]))
+                        print(json.dumps(row), flush=True)
+                        result["rows"].append(row)
+                if has_forms:
+                    b.plc_pred_form(0)
+                b.sync()
+                b.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+def measure(out_path, n, int8=False, schedule=None, widths=None, pred_form=None):
+    import torch
+    from lpcnet_amd import api, synth
+    dev = torch.device("cuda:0")
+    b = api.LPCNetBatch(n, plc_blob(int8, widths))
     b.plc_enable(api.PLC_CAUSAL)
     assert b.plc_flavour() == int(int8)
     b.tune()
     if schedule:
         b.group_schedule = schedule
+    if pred_form is not None:
+        b.plc_pred_form(pred_form)
     T = 100
     base = np.stack([synth.make_pcm(700 + k, T).reshape(T, 160) for k in range(64)])
     frames = [torch.from_numpy(np.ascontiguousarray(np.tile(base[:, t], (n // 64 + 1, 1))[:n])).to(dev) for t in range(T)]
@@ -145,7 +223,8 @@ def measure(out_path, n, int8=False, schedule=None):
     s = torch.cuda.Stream()
     rng = np.random.default_rng(7)
     result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), streams=n, options="LPCNET_PLC_CAUSAL", flavour="int8" if int8 else "float",
-                  streams_per_workgroup=b.L.lpcnet_batch_get_streams_per_workgroup(b.p), group_schedule=list(b.group_schedule), random_loss=[], burst=None)
+                  streams_per_workgroup=b.L.lpcnet_batch_get_streams_per_workgroup(b.p), group_schedule=list(b.group_schedule),
+                  plc_widths=list(widths or (128, 16, 16)), pred_form=b.plc_pred_form(), random_loss=[], burst=None)
     with torch.cuda.stream(s):
         for p in (0.0, 0.05, 0.20):
             b.plc_reset()
@@ -272,7 +351,16 @@ def measure_fec(out_path, n, K, loop=False, int8=False, schedule=None):
 
 
 if __name__ == "__main__":
-    args = [x for x in sys.argv[1:] if x not in ("--int8", "--fec-loop", "--ab")]
+    args = [x for x in sys.argv[1:] if x not in ("--int8", "--fec-loop", "--ab", "--forms")]
+    widths_list, pred_forms, losses = [], [], []
+    for opt, dest, conv in (("--widths", widths_list, lambda x: tuple(int(v) for v in x.split(","))), ("--pred-form", pred_forms, int), ("--loss", losses, float)):
+        while opt in args:
+            i = args.index(opt)
+            dest.append(conv(args[i + 1]))
+            del args[i:i + 2]
+    if "--forms" in sys.argv[1:]:
+        measure_forms(args[0], [int(x) for x in args[1].split(",")] if len(args) > 1 else [8192], widths_list or [None], losses or [0.0], pinned=pred_forms)
+        sys.exit(0)
     schedules = []
     while "--schedule" in args:
         i = args.index("--schedule")
@@ -289,4 +377,5 @@ if __name__ == "__main__":
         del args[i:i + 2]
         measure_fec(args[0], int(args[1]) if len(args) > 1 else 8192, K, loop="--fec-loop" in sys.argv[1:], int8="--int8" in sys.argv[1:], schedule=schedule)
         sys.exit(0)
-    measure(args[0], int(args[1]) if len(args) > 1 else 8192, int8="--int8" in sys.argv[1:], schedule=schedule)
+    measure(args[0], int(args[1]) if len(args) > 1 else 8192, int8="--int8" in sys.argv[1:], schedule=schedule, widths=widths_list[-1] if widths_list else None,
+            pred_form=pred_forms[-1] if pred_forms else None)
