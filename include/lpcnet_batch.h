@@ -156,6 +156,7 @@ LPCNET_EXPORT int lpcnet_batch_set_analysis_state(LPCNetBatch *b, int stream, co
  * lpcnet_batch_analysis_reset (lpcnet_encoder_init) clears it as well, lpcnet_batch_reset touches neither; a snapshot of a stream is its
  * analysis state plus its vq_mem.
  * Codebooks: as for lpcnet_batch_decode (lpcnet_hip_set_codebooks or the default file); without them encode returns what decode returns.
+ * Codebooks installed while a batch exists reach its device tables with the batch's next encode or decode call.
  * compute_features needs none.  A batch without a model returns LPCNET_HIP_E_MODEL.  Host-pointer calls copy in, run, copy out and
  * synchronise (one host thread per shard); device-pointer calls only enqueue on `hip_stream` (NULL = the batch's own) under the ordering
  * and capture rules of lpcnet_batch_analyze_device: on a stream that is being captured nothing is executed, allocated or synchronised,
@@ -239,6 +240,15 @@ LPCNET_EXPORT int lpcnet_batch_plc_pred(LPCNetBatch *b, const float *in57, float
 LPCNET_EXPORT int lpcnet_batch_plc_set_pred_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_plc_get_pred_form(const LPCNetBatch *b, int n_streams);
 LPCNET_EXPORT int lpcnet_hip_plc_pred_form(int n_records, int cus, int d1, int g1, int g2, int int8, int pinned);
+/* How one lpcnet_batch_encode* call (analysis == 0, count packets) or one lpcnet_batch_analyze* call (analysis != 0, count frames) is cut into
+ * launches on a shard of capacity n of whose streams the first `active` run, by the engine's own rules and without a device.  A call runs in
+ * chunks that keep capacity x frames within 65 536 (the chunk follows the capacity, not the active count, and is at least one packet / one
+ * frame); per chunk the two VQ kernels of the encoder give a wavefront 1 .. 4 (vq_end) and 1 .. 2 (vq_mid) of the chunk's active x packets items,
+ * more than one from 8 192 items; a workgroup has eight wavefronts.  out [cap][8] receives per launch {packets or frames, items, items per
+ * wavefront of vq_end, of vq_mid, workgroups of vq_end, items in its last workgroup, workgroups of vq_mid, items in its last workgroup} (the
+ * last six are 0 for the analysis; lpcnet_batch_compute_features* runs the encoder's chunks without the VQ kernels).  Returns the number of
+ * launches (records beyond `cap` are not written), 0 when no stream is active, LPCNET_HIP_E_ARG for n < 1, active outside 0 .. n, count < 1. */
+LPCNET_EXPORT int lpcnet_hip_encode_plan(int n, int active, int count, int analysis, int *out, int cap);
 /* the host planner alone, no device (tests): ctl [n][9] ints in and out, fec_op [n] or NULL (1 vector added, 2 NULL skip, 3 clear, 4 two vectors
  * added, before the step), summary [n][10] out: {lost, flushed deferred features, queue rounds, their samples, FEC vectors used, first frame after a
  * loss (1 cross-fade, 2 codec restore), queue operation (1 tail, 2 append, 3 push), prediction kept, deferred features appended, loss_count} */

@@ -62,6 +62,23 @@ def plc_pred_form_table(n_records: int, cus: int, d1: int, g1: int, g2: int, int
     return rc
 
 
+def encode_plan(n: int, active: int, count: int, analysis: bool = False):
+    """The launches of one encode call of `count` packets (or, analysis=True, one analyze call of `count` frames) on a batch of capacity n with
+    `active` streams running, by the engine's own chunk and items-per-wavefront rules (no device): a list with one dict per launch -- packets (or
+    frames), items, and for the encoder ipw_end, ipw_mid, wg_end, last_end, wg_mid, last_mid (workgroups of either VQ kernel and the items in the
+    last one).  compute_features runs the encoder's chunks without the VQ kernels"""
+    L = load_library()
+    k = L.lpcnet_hip_encode_plan(n, active, count, 1 if analysis else 0, None, 0)
+    if k < 0:
+        raise LPCNetError("encode_plan failed (%d): %s" % (k, last_error()))
+    out = np.zeros((max(k, 1), 8), np.int32)
+    k = L.lpcnet_hip_encode_plan(n, active, count, 1 if analysis else 0, out.ctypes.data, out.shape[0])
+    if analysis:
+        return [dict(frames=int(r[0]), items=int(r[1])) for r in out[:k]]
+    names = ("packets", "items", "ipw_end", "ipw_mid", "wg_end", "last_end", "wg_mid", "last_mid")
+    return [dict(zip(names, (int(x) for x in r))) for r in out[:k]]
+
+
 PLC_LANES_REC = 10
 
 
@@ -219,6 +236,7 @@ def load_library():
     L.lpcnet_batch_plc_set_pred_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_plc_get_pred_form.argtypes = [vp, C.c_int]
     L.lpcnet_hip_plc_pred_form.argtypes = [C.c_int] * 7
+    L.lpcnet_hip_encode_plan.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int]
     L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
     L.lpcnet_hip_dred_enc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]

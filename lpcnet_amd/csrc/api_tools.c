@@ -2,6 +2,7 @@
  * weight blob, the PLC planners without a device, and the device probes of the arithmetic. */
 #include "api_internal.h"
 #include "sample_variants.h"
+#include "encode_plan.h"
 
 /* what the caller did to each stream's FEC ring before the step: fec_op [n] (may be NULL): 1 = a vector was added, 2 = a NULL skip, 3 = fec_clear,
  * 4 = two vectors */
@@ -67,6 +68,31 @@ int lpcnet_hip_packet_features(const unsigned char *buf8, float *vq_mem18, float
     codebooks_unlock();
     if (rc) { set_err("lpcnet_hip_packet_features: no VQ codebooks installed (lpcnet_hip_set_codebooks)"); return LPCN_E_MODEL; }
     return 0;
+}
+
+/* tools (include/lpcnet_batch.h): the launches of one lpcnet_batch_encode / lpcnet_batch_analyze call by the engine's own rules (encode_plan.h), no device */
+int lpcnet_hip_encode_plan(int n, int active, int count, int analysis, int *out, int cap)
+{
+    if (n < 1 || active < 0 || active > n || count < 1 || cap < 0 || (cap && !out)) { set_err("lpcnet_hip_encode_plan: bad arguments"); return LPCN_E_ARG; }
+    const int chunk = analysis ? lpcn_analysis_chunk(n, count) : lpcn_encode_chunk(n, count);
+    int k = 0;
+    for (int c0 = 0; active && c0 < count; c0 += chunk, k++) {
+        if (k >= cap) continue;
+        int *r = out + 8 * k;
+        const size_t items = (size_t)active * (count - c0 < chunk ? count - c0 : chunk);
+        memset(r, 0, sizeof(int) * 8);
+        r[0] = count - c0 < chunk ? count - c0 : chunk;
+        r[1] = (int)items;
+        if (analysis) continue;
+        r[2] = lpcn_encode_ipw(items, LPCN_ENC_END_IPW);
+        r[3] = lpcn_encode_ipw(items, LPCN_ENC_MID_IPW);
+        for (int v = 0; v < 2; v++) {
+            const size_t per = (size_t)LPCN_ENC_VQ_WAVES * r[2 + v], wg = (items + per - 1) / per;
+            r[4 + 2 * v] = (int)wg;
+            r[5 + 2 * v] = (int)(items - (wg - 1) * per);
+        }
+    }
+    return k;
 }
 
 /* tools: how GRU-A's rows were dealt to the 8 waves of the sample kernel: out[0] = items per lane, then per wave

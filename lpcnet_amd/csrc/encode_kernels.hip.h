@@ -17,16 +17,17 @@
 // features of the quantised path (:686-690, :720-723) are not part of a packet and are not computed.
 #pragma once
 #include "analysis_kernels.hip.h"
+#include "encode_plan.h"
 
 namespace lpcn {
 
 constexpr int ENC_NB1 = LPCN_NB_BANDS - 1;     // NB_BANDS_1: the 17 coefficients of the three-stage VQ
 constexpr int ENC_CB = 1024;                   // entries of a stage codebook, and of one quarter of ceps_codebook_diff4
 constexpr int ENC_SURV = 5;                    // SURVIVORS
-constexpr int ENC_VQ_WAVES = 8;
+constexpr int ENC_VQ_WAVES = LPCN_ENC_VQ_WAVES;
 constexpr int ENC_VQ_THREADS = 64 * ENC_VQ_WAVES;
-constexpr int ENC_END_IPW = 4;                 // (stream, packet) items per wavefront, at most: vq_end (77 KB of LDS: two workgroups per CU)
-constexpr int ENC_MID_IPW = 2;                 //   ... vq_mid (78 KB)
+constexpr int ENC_END_IPW = LPCN_ENC_END_IPW;  // (stream, packet) items per wavefront, at most (encode_plan.h: lpcn_encode_ipw)
+constexpr int ENC_MID_IPW = LPCN_ENC_MID_IPW;
 constexpr int ENC_PK = 4;                      // ints per packet of the scratch record: [0] pitch | modulation | corr_id (11 bits), [1] c0_id + 64, [2] vq_end (30 bits)
 
 // (int)v as the reference's x86 build converts (cvttsd2si): out of range and NaN give INT_MIN
@@ -459,13 +460,6 @@ __global__ __launch_bounds__(ENC_VQ_THREADS) void encode_vq_mid_kernel(EncodeTab
 }
 
 }  // namespace lpcn
-
-// items per wavefront of a VQ kernel: enough workgroups for two per CU before a workgroup takes more items per staged codebook
-static inline int lpcn_encode_ipw(size_t items, int ipw_max)
-{
-    const size_t want = items / ((size_t)lpcn::ENC_VQ_WAVES * 512);
-    return want < 1 ? 1 : (want > (size_t)ipw_max ? ipw_max : (int)want);
-}
 
 // the launches of one chunk of n_packets packets (4 * n_packets <= the analysis scratch's frames).  d_packets != NULL: lpcnet_encode, five
 // launches, cepstrum / LPC into the scratch rows d_feat (stride 36); else lpcnet_compute_features, three launches, d_feat is the caller's.

@@ -3,14 +3,7 @@
 #include "encode_kernels.hip.h"
 
 // ------------------------------------------------------------------------------- feature analysis -----
-// (stream, frame) items per launch of the analysis kernels: bounds their scratch (2.7 KB per item) at 176 MB
-#define LPCN_AN_ITEMS_MAX 65536
-static int analysis_chunk_for(const lpcn_batch_dev *b, int n_frames)
-{
-    int cap = LPCN_AN_ITEMS_MAX / b->n;
-    if (cap < 1) cap = 1;
-    return n_frames < cap ? n_frames : cap;
-}
+// A call runs in chunks of lpcn_analysis_chunk frames (encode_plan.h), which bounds the kernels' scratch.
 
 // the analysis state (if absent) and the kernels' scratch for `chunk` frames per launch
 static int analysis_alloc(lpcn_batch_dev *b, int chunk)
@@ -29,7 +22,7 @@ extern "C" int lpcn_batch_dev_analysis_enable(lpcn_batch_dev *b, int max_frames)
 {
     if (max_frames < 1) { snprintf(g_err, sizeof(g_err), "analysis: bad frame count"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
-    return analysis_alloc(b, analysis_chunk_for(b, max_frames));
+    return analysis_alloc(b, lpcn_analysis_chunk(b->n, max_frames));
 }
 
 extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int pcm_is_float, float *d_features, int feat_stride, int n_frames,
@@ -39,7 +32,7 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
     if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
-    if (!b->d_an_state || analysis_chunk_for(b, n_frames) > b->an_chunk) {
+    if (!b->d_an_state || lpcn_analysis_chunk(b->n, n_frames) > b->an_chunk) {
         if (stream_is_capturing(st)) {      // (a capture executes nothing and allocates nothing)
             snprintf(g_err, sizeof(g_err), "analysis state / scratch for %d frames per call must exist before a capture: call lpcnet_batch_analysis_enable first", n_frames);
             return LPCN_E_ARG;
@@ -50,8 +43,9 @@ extern "C" int lpcn_batch_dev_analyze(lpcn_batch_dev *b, const void *d_pcm, int 
     { int rco = order_begin(b, st); if (rco) return rco; }
     const int is_float = pcm_is_float ? 1 : 0;
     const size_t pcm_stride = (size_t)n_frames * LPCN_FRAME_SIZE, feat_stream_stride = (size_t)n_frames * feat_stride;
-    for (int f0 = 0; f0 < n_frames; f0 += b->an_chunk) {
-        const int nf = n_frames - f0 < b->an_chunk ? n_frames - f0 : b->an_chunk;
+    const int chunk = lpcn_analysis_chunk(b->n, n_frames);      // (<= b->an_chunk: the scratch may be larger than this call needs)
+    for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
         const void *p = is_float ? (const void *)((const float *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE) : (const void *)((const short *)d_pcm + (size_t)f0 * LPCN_FRAME_SIZE);
         int rc = lpcn_launch_analysis_kernels(b->e->fmodel, st, b->active, nf, p, is_float, pcm_stride, b->d_an_state, d_features + (size_t)f0 * feat_stride,
                                               feat_stride, feat_stream_stride, b->d_an_resid, b->d_an_xc, b->d_an_fw, g_err, sizeof(g_err));
@@ -103,19 +97,12 @@ extern "C" int lpcn_batch_dev_set_analysis_state(lpcn_batch_dev *b, int s, const
 
 // ------------------------------------------------------------------------------- encoder -----
 // lpcnet_encode / lpcnet_compute_features per stream and packet (encode_kernels.hip.h).  A chunk is a whole number of packets within the
-// analysis scratch's item bound (at least one packet, whatever the batch size).
-static int encode_chunk_for(const lpcn_batch_dev *b, int n_packets)
-{
-    int cap = LPCN_AN_ITEMS_MAX / b->n / 4;
-    if (cap < 1) cap = 1;
-    return n_packets < cap ? n_packets : cap;
-}
-
+// analysis scratch's item bound (at least one packet, whatever the batch size): lpcn_encode_chunk (encode_plan.h).
 extern "C" int lpcn_batch_dev_encoder_enable(lpcn_batch_dev *b, int max_packets)
 {
     if (max_packets < 1) { snprintf(g_err, sizeof(g_err), "encoder: bad packet count"); return LPCN_E_ARG; }
     DeviceGuard guard(b->e->device);
-    const int chunk = encode_chunk_for(b, max_packets);
+    const int chunk = lpcn_encode_chunk(b->n, max_packets);
     int rc = analysis_alloc(b, 4 * chunk);
     if (rc) return rc;
     if (!b->d_enc_vq_mem && (rc = b->d_enc_vq_mem.alloc(LPCN_NB_BANDS * (size_t)b->n, true))) return rc;
@@ -139,7 +126,7 @@ static int encode_impl(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_p
     if (!b->active) return 0;
     DeviceGuard guard(b->e->device);
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : b->e->stream;
-    const int want = encode_chunk_for(b, n_packets);
+    const int want = lpcn_encode_chunk(b->n, n_packets);
     if (!b->d_an_state || !b->d_enc_vq_mem || want > b->enc_chunk || 4 * want > b->an_chunk) {
         if (stream_is_capturing(st)) {      // (a capture executes nothing and allocates nothing)
             snprintf(g_err, sizeof(g_err), "encoder state / scratch for %d packets per call must exist before a capture: call lpcnet_batch_encoder_enable first", n_packets);
@@ -149,7 +136,7 @@ static int encode_impl(lpcn_batch_dev *b, const short *d_pcm, unsigned char *d_p
         if (rc) return rc;
     }
     { int rco = order_begin(b, st); if (rco) return rco; }
-    const int chunk = b->enc_chunk < b->an_chunk / 4 ? b->enc_chunk : b->an_chunk / 4;
+    const int chunk = want;      // (<= b->enc_chunk, b->an_chunk / 4: the scratch may be larger than this call needs)
     const size_t pcm_stride = (size_t)n_packets * 4 * LPCN_FRAME_SIZE;
     for (int p0 = 0; p0 < n_packets; p0 += chunk) {
         const int np = n_packets - p0 < chunk ? n_packets - p0 : chunk;

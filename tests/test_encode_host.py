@@ -12,7 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import kernel_resources  # noqa: E402
+import encode_ties  # noqa: E402
 import make_golden_encode as mge  # noqa: E402
+import make_golden_encode_ties as mget  # noqa: E402
 from lpcnet_amd import api  # noqa: E402
 
 CSRC = os.path.join(ROOT, "lpcnet_amd", "csrc")
@@ -59,6 +61,42 @@ def test_the_fixture_regenerates_identically_from_the_compiled_reference():
     if not os.path.exists(REF_LIB):
         pytest.skip("compiled reference absent (make -C oracle ref)")
     g, fresh = np.load(mge.PATH), mge.generate()
+    assert sorted(g.files) == sorted(fresh)
+    for k in g.files:
+        a, b = np.asarray(g[k]), np.asarray(fresh[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
+def test_the_tie_fixture_shows_the_reference_deciding_every_tie_by_the_lower_index():
+    """tests/golden/golden_encode_ties_v1.npz (codebooks of tests/tools/encode_ties.py): the conditions its generator refuses to write without.
+    Recorded, not required: a zero row of ceps_codebook_diff4 never won; in 251 of the 384 packets double_interp_search passed over the forbidden
+    id 7 although it was the nearest (recomputed by encode_ties.interp_census, which reproduces every interp id of the fixture)"""
+    g = np.load(mget.PATH)
+    S, P = g["packets"].shape[:2]
+    assert (S, P) == (6, 64) and g["packets"].dtype == np.uint8 and g["vq_mem"].shape == (S, 18) and g["vq_mem"].dtype == np.float32
+    assert int(g["codebook_seed"]) == encode_ties.SEED and g["seeds"].tolist() == list(mget.SEEDS)
+    ties = encode_ties.make(int(g["codebook_seed"]))
+    for s in range(3):                                                           # every vector at four positions
+        cb, group = ties["cbs"][s], ties["groups"][s]
+        assert cb.shape == (1024, 17) and all(len({cb[i].tobytes() for i in np.flatnonzero(group == k)}) == 1 for k in range(256))
+        assert len({cb[i].tobytes() for i in range(1024)}) == 256
+        assert all(v >= 40 for v in encode_ties.placement_census(group).values())
+    c = encode_ties.census(g["packets"], ties)
+    assert encode_ties.conditions(c) == [], c
+    assert c["packets"] == S * P and all(v >= 10 for v in c["kinds"].values()) and c["mid_first_of_equal_pair"] >= 10
+    assert c["mid_zero_row"] == int(g["zero_row_winners"]) == 0 and c["interp_ids"] == list(range(8))
+    assert int(g["forbidden_id7"]) == 251
+    # the final vq_mem is the last packet's quantised frame 3
+    f = mge.packet_fields(g["packets"][:, -1])
+    cb1, cb2, cb3, _ = ties["cbs"]
+    assert np.array_equal(g["vq_mem"][:, 0], ((f["c0"] - 64) / 4.0).astype(np.float32))
+    assert np.array_equal(g["vq_mem"][:, 1:], (cb1[f["e0"]] + cb2[f["e1"]]) + cb3[f["e2"]])
+
+
+def test_the_tie_fixture_regenerates_identically_from_the_compiled_reference():
+    if not os.path.exists(REF_LIB):
+        pytest.skip("compiled reference absent (make -C oracle ref)")
+    g, fresh = np.load(mget.PATH), mget.generate()
     assert sorted(g.files) == sorted(fresh)
     for k in g.files:
         a, b = np.asarray(g[k]), np.asarray(fresh[k])
