@@ -128,13 +128,18 @@ static int autotune_streams_per_wg(lpcn_batch_dev *b, hipStream_t st)
     int best = b->S;
     bool best_x3 = false;
     float best_ms = -1.f;
-    // the candidates: S = 1, 2, 4, 8 and -- where the model has the image, the choice is the engine's and the batch has more than four streams per CU --
-    // eight on twelve waves (both forms of the two-group kernel produce the same bits: the choice cannot change a result)
+    // the candidates: S = 1, 2, 4, 8 and -- where eight has won, the model has the image, the choice is the engine's and the batch has more than four streams
+    // per CU -- eight on twelve waves (both forms of the two-group kernel produce the same bits: the choice cannot change a result)
     const bool try_x3 = x3_available(b) && b->x3_mode < 0 && b->n > 4 * device_cus(b->e);
     for (int c = 0; c < 5; ++c) {
         const int S = c < 4 ? 1 << c : 8;
         if (S == 8 && (!x2_available(b) || b->n <= 4)) break;
-        if (c == 4 && !try_x3) break;
+        // The twelve-wave form competes with the eight-wave form only, where that one has won: the two share everything this measurement does not see.
+        // What is timed is live frames in steady state; the two-group kernels run a call's silent start-up frames at full price, the others do not.  At
+        // 2 560 streams (320 workgroups in two rounds against 640 in three) the twelve-wave form ties with four streams per workgroup on live frames
+        // (0.3 - 0.8 % apart, inside the spread) and takes 1.42 x the time on a call of 6 frames from reset (21.5 against 15.1 ms): as one more candidate
+        // among all it was taken from batch to batch (round 13), with a margin of 2 % still now and then.
+        if (c == 4 && (!try_x3 || best != 8)) break;
         const LaunchShape sh = {b->n, b->frame_len, b->d_state, S, use_pack2(b, b->n, S), c == 4 || (S == 8 && b->x3_mode == 1)};
         float ms = -1.f, ms1 = 0.f;
         for (int pass = 0; pass < 7 && !rc; ++pass) {          // warm-up (1 frame), then three pairs of (1 frame, nf frames): the smallest difference

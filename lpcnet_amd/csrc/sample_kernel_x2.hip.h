@@ -49,7 +49,7 @@ struct LdsX2 {
     static constexpr int g_hB    = g_prec + NA * S * 4;             // [4][16]
     static constexpr int g_idx   = g_hB + S * NB * 4;               // [4] packed indices, [4] live flags
     static constexpr int g_thr   = g_idx + S * 16;                  // [4][8]
-    static constexpr int g_mask  = g_thr + S * 32;                  // [4] i32: the streams' walked tree values (the region keeps the size of the [4][8] u64 ballots the twelve-wave kernel stores here)
+    static constexpr int g_mask  = g_thr + S * 32;                  // [4] i32: the streams' walked tree values (the region keeps the size of the [4][8] u64 ballots both forms stored here until they walked the tree in stages)
     static constexpr int g_pfx   = g_mask + S * 4;                  // [4] i32: (sample sequence number << LPCN_TREE_TOP) | stage 1's walk, published by the streams' chain waves for the stage-2 wave
     static constexpr int g_lead  = g_mask + S * 64;                 // [4][8]
     static constexpr int g_flag  = g_lead + S * 32;                 // [4] i32

@@ -5,9 +5,11 @@
 // what.  With two waves per SIMD every interval of that kernel is a chain of latency-bound links on each wave, and only the partner wave can fill
 // them; here a SIMD carries one chain wave and two row waves, in 168 VGPRs each:
 //
-//      waves 0..3    GRU-B's chain of one stream of group Q (grub_lds_loop_s4_v168.inc: the same loop in v128..v167), then their P1 segments of P
+//      waves 0..3    GRU-B's chain of one stream of group Q (grub_lds_loop_s4_v168.inc: the same loop in v128..v167), stage 1 of that stream's tree
+//                    (tree_stages.h) behind the gates, then their P1 segments of P
 //      waves 4..11   the candidate heads of Q in the chains' shadow, the start-value pass ("P0") of P -- 2.25 rounds of 512 rows instead of 4.5 of
-//                    256, two rounds in flight --, their P1 segments of P, and Q's tree (256 nodes x 2 channels = 512 lanes)
+//                    256, two rounds in flight --, their P1 segments of P; they evaluate no tree nodes
+//      wave LPCN_X3_S2W   stage 2 of the four streams' trees in one packed pass, behind its P1 segments
 //
 // A lane holds 16 items (64 weight VGPRs) instead of 30, so a candidate slot of more than 16 items is cut: its head -- blocks 0..15, from
 // bias + diag*h -- runs one sample ahead on a row wave and parks its partial sums in the rows' pre-activation cells, its tail goes on adding
@@ -22,7 +24,8 @@ namespace lpcn {
 
 #define LPCN_X3_TW 1            // the wave that draws the KISS99 thresholds: a chain wave on another SIMD than the leader's (waves w, w + 4, w + 8 share one: tools/ubench/hwid.hip)
 #define LPCN_X3_HG 6            // head items a row wave runs before it polls the leader's indices for the start-value pass
-#define LPCN_X3_TREE_FIRST 4    // waves 4..11 evaluate the tree: the chain waves, the longest link of an interval, go straight to the barrier
+#define LPCN_X3_S2W 11          // the wave that runs stage 2 of the four streams' trees in one pass: any but the leader's.  Row wave 9 / 11, chain wave 0 / 2 / 3: 177.8 / 180.6 / 176.8 / 176.9 / 172.7 M (round 13; the eight-wave form 175.6 M, this kernel with round 6's tree 163.0 M)
+#define LPCN_X3_S2_LEAD 2       // ... and how many of its P1 items from the end it polls the streams' prefixes and issues the loads of its rows (on wave 11, 1 / 2 / 4: 180.8 / 180.6 / 180.6 M, a tie; at least 1)
 
 __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const LpcnSampleArgs *__restrict__ Ap)
 {
@@ -110,7 +113,8 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             unsigned char *gb = smem + g * L::G_SZ;
             stage_leader_record({(float *)(gb + L::g_lead), (int *)(gb + L::g_idx), nullptr, nullptr}, s, &states[stream_of(tid)]);
         }
-        if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; fl[2] = 0; }
+        if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; }
+        if (tid < 2 * S) ((int *)(smem + (tid >> 2) * L::G_SZ + L::g_pfx))[tid & 3] = 0;      // (no sample has sequence number 0)
     }
     __syncthreads();
 
@@ -126,7 +130,6 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
     bool liveP = false, liveQ = false;                       // per lane: leader lanes (their stream), threshold lanes
     int live_maskP = 0, live_maskQ = 0;                      // bit s: stream s of the group produces samples in its current frame
     int seqP = 0, seqQ = 0;                                  // samples opened so far, per group (identical in every wave)
-    int chnP = 0, chnQ = 0;                                  // GRU-B phases run so far, per group
     int smpP = 0, smpQ = 0, fP = 0, fQ = 0;                  // position of the group's NEXT P1 sample: sample within the frame, frame
     float lpc_tap = 0.f, prod_old = 0.f;                     // leader lanes: computed behind the tree of a group, used when its sample is finished
 
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             const int lrow = (t_ & 63) >> 4, tap = t_ & 15;
             float pcm, deemph;
             int exc;
-            draw_sample(cells_p, (const unsigned long long *)(gp + L::g_mask) + lrow * 8, sm_ulaw, lrow, tap, liveP, smp_done, preload, histP, pcm, deemph, exc);
+            draw_sample_walked(cells_p, (const int *)(gp + L::g_mask) + lrow, sm_ulaw, lrow, tap, liveP, smp_done, preload, histP, pcm, deemph, exc);
             // the next sample's indices first (wave LW publishes them through idx_p + flag_p): the row waves are waiting for them
             if (more) { open_sample<S>(cells_p, tid0, liveP, pcm, tap == 0 ? pcm * lpc_tap : prod_old, exc, false); lds_publish(flag_p, seqP); }
             __builtin_amdgcn_s_setprio(0);
@@ -224,7 +227,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
         // ================================================================ interval A ===========
         // ---- shared pieces of the item chains (P1 of group P, candidate heads of group Q)
         float acc[S] = {};
-        constexpr int PF = 1;                                // state blocks fetched one item ahead (two, the eight-wave kernel's value, costs four VGPRs that the 168 do not have: a weight tuple is spilled)
+        constexpr int PF = 1;                                // state blocks fetched one item ahead (two, the eight-wave kernel's value, costs four VGPRs that the 168 do not have: a weight tuple is spilled; measured again in round 13 with the tree off the row waves: 177.8 against 177.8 M on wave 9, a tie, not kept)
         float4 hq[PF + 1] = {};
         const unsigned char *hA_cur = gp + L::g_hA;           // state blocks of the group whose items are running
         auto fetch_h = [&](const int j) __attribute__((always_inline)) {
@@ -265,24 +268,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             return (float *)(r < 2 * NA ? smem + L::pre_ur + r * (S * 4) : gb + L::g_prec + (r - 2 * NA) * (S * 4));
         };
 
-        const int lane = tid0 & 63;
         const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-        // this lane's dual-FC row (node = tid >> 1, channel = tid & 1) for group Q's tree, fetched behind the wave's items of P (it lands while the slots are closed)
-        float fcw[NB], fcb = 0.f, fcf = 0.f;
-        auto load_fc = [&]() __attribute__((always_inline)) {
-            int t_ = tid0;
-            LPCN_REMAT_V(t_);
-            t_ -= 64 * LPCN_X3_TREE_FIRST;
-            const int node_ = t_ >> 1, chan_ = t_ & 1;
-            const auto *fcw_ptr = fc_w_s + node_ * 2 * NB + chan_ * NB;
-#pragma unroll
-            for (int j = 0; j < NB; ++j) fcw[j] = fcw_ptr[j];
-            fcb = fc_b_s[chan_ * 256 + node_]; fcf = fc_f_s[chan_ * 256 + node_];
-        };
-        const bool tree_wave = wave >= LPCN_X3_TREE_FIRST;     // (wave-uniform)
-        const uint32_t chcnt_q = lds_addr(gq + L::g_flag) + 8;   // arrival counter of Q's GRU-B chains (the tree of a wave must not start before all four have written their state)
-        if (q_chain) ++chnQ;
-
         // Order of an interval on one wave (round 6, third form.  The first ran P3 of Q, then all of P1 of P, and every wave then sat ~4 k clk behind
         // its own embedding gather; the second issued each wave's gather before Q's chain / heads and the 60 values in flight pushed GRU-A's weights
         // into scratch -- profiles/r06_x2_phase_v1.txt):
@@ -398,6 +384,9 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
                     : [z] "+v"(zrh), [wp] "+v"(wp32), [hp] "+v"(hp32) : : LPCN_GRUB_LDS168_CLOBBERS);
                 __builtin_amdgcn_s_setprio(0);
                 LPCN_X2_PROF(1);
+                // P4 of stream s, stage 1: the rows of the tree's top levels are the same every sample; fetched here, behind the assembly block (its
+                // v128..v167 are dead, nothing extra is live across it), they land under the gates
+                const TreeRow top = tree_row_load<0>(fc_w_s, fc_b_s, fc_f_s, ln_, 0);
                 // gates: rows [0,16) update, [16,32) reset, [32,48) candidate (src/nnet.c:362-371)
                 const int ln = ln_ & 15;
                 const float sg = lpcn_sigmoid(zrh + rec, sm_tansig);
@@ -409,8 +398,16 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
                     const float hnew = sg * hold + (1.f - sg) * hc_i;
                     if ((live_maskQ >> s) & 1) hB_q[s * NB + ln_] = hnew;
                 }
-                lds_arrive(chcnt_q);                         // (behind the state store)
                 LPCN_X2_PROF(2);
+                // ---- P4 of group Q, stage 1: the top five levels of stream s's tree on the wave that has just produced its state, as on the eight-wave
+                // kernel (sample_kernel_x2.hip.h): the state is read back from the cells this wave has just written (a wave's LDS operations complete in
+                // order: no counter, no wait for another stream's chain), the five decided bits are published under the sample's sequence number behind
+                // the state stores.  Until round 13 waves 4..11 evaluated all 255 nodes x 2 channels of the four streams behind their P1, behind a poll for
+                // the SLOWEST chain: a serial link of a whole tree evaluation on every half-step, and eight waves' worth of issue slots.
+                const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
+                const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
+                if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
+                LPCN_X2_PROF(9);                             // (slot 9 = the tree, as on the eight-wave kernel: a chain wave's stage 1 here plus whatever it runs between the close of its P1 and barrier 1 -- the stage-2 pass where it hosts it, else next to nothing)
             }
             // (Round 6 also gave these waves a share of P's start-value pass -- a round of update / reset rows and one of candidate inputs, or the candidate
             // inputs alone, issued above the gates: 144.0 / 145.7 vs 147.0 M.  With only the barrier waits instrumented the chain waves have 1.3-2.2 k clk
@@ -460,6 +457,27 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             LPCN_X2_PROF(3);
         }
 
+        // ---------------------------------------------------------------- P4 of group Q, stage 2, first part (wave LPCN_X3_S2W) ----
+        // Four streams in one pass: lane 16 f + l is local lane l of stream f (tree_stages.h, packed mapping).  Each lane reads its stream's cell until all
+        // four carry this sample's sequence number, then fetches the row of its node in the subtree its stream's prefix names.  This happens
+        // LPCN_X3_S2_LEAD items before the end of the wave's P1 segments: the rows land under those, and the chains have published by then.
+        static_assert(LPCN_X3_S2W != LPCN_X3_LW && LPCN_X3_S2W >= 0 && LPCN_X3_S2W < LPCN_X3_WAVES && LPCN_TREE_FIELDS == S && LPCN_X3_S2_LEAD >= 1, "stage 2 runs on any wave but the leader's, one field per stream");
+        const bool s2_wave = q_chain && wave == LPCN_X3_S2W;      // (wave-uniform)
+        TreeRow sub = {};
+        int pfx = 0;
+        auto s2_open = [&]() __attribute__((always_inline)) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            const uint32_t cell = lds_addr(gq + L::g_pfx) + (uint32_t)lpcn_tree_packed_field(t_ & 63) * 4u;
+            do {
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pfx) : "v"(cell) : "memory");
+            } while (__ballot((pfx >> LPCN_TREE_TOP) != seqQ) != 0ull);
+            pfx &= (1 << LPCN_TREE_TOP) - 1;
+            sub = tree_row_load_packed(fc_w_s, fc_b_s, fc_f_s, t_ & 63, pfx);
+        };
+        const bool s2_in_items = s2_wave && p_active && b4 > 0;      // (a wave without items, a half-step without P1: in front of the barrier's work)
+        if (s2_wave && !s2_in_items) s2_open();
+
         // ---------------------------------------------------------------- 5: P1 of group P ----
         if (p_active) {
             hA_cur = gp + L::g_hA;
@@ -507,17 +525,22 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             LPCN_REMAT_S(b3);
             LPCN_REMAT_S(b4);
             // All tests below are wave-uniform scalar branches; an ordinary item falls through every one of them.
+            int s2_at = s2_in_items ? (jend > LPCN_X3_S2_LEAD ? jend - LPCN_X3_S2_LEAD : 0) : NW + 1;      // stage 2 of Q's trees opens in front of this item
+            LPCN_REMAT_S(s2_at);
             int nextb = b1;
+            if (s2_at < nextb) nextb = s2_at;
             LPCN_REMAT_S(nextb);
             auto item = [&](const int j) __attribute__((always_inline)) -> bool {           // false: this wave has no more items
                 if (__builtin_expect(j >= jend, 0)) return false;
                 if (j + PF < NW) fetch_h(j + PF);
-                if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty): ONE compare per item against the next one
+                if (__builtin_expect(j == nextb, 0)) {       // slot boundaries (a slot may be empty) and the stage-2 wave's opening: ONE compare per item against the next one
                     if (j == b1) row_swap(1, 2);
                     if (j == b2) row_swap(2, 3);
                     if (j == b3) row_swap(3, 4);
+                    if (j == s2_at) s2_open();
                     __builtin_amdgcn_s_waitcnt(0xC07F);
                     nextb = b1 > j ? b1 : (b2 > j ? b2 : (b3 > j ? b3 : NW));
+                    if (s2_at > j && s2_at < nextb) nextb = s2_at;
                 }
                 mac(j);
                 return true;
@@ -530,7 +553,6 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
                 }
             };
             run_items(run_items, std::integral_constant<int, 0>{});
-            if (q_chain && tree_wave) load_fc();
             LPCN_X2_PROF(5);
             // close whichever slot is still open; slots that start exactly at the end have no items
             if (b1 >= jend) {
@@ -546,69 +568,27 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             row_store(4);
             LPCN_X2_PROF(6);
         }
-        // ------------------------------------------------------------ P4 of group Q: dual-FC tree, all nodes at once (src/nnet.c:163-214) --
-        // Round 6: the tree runs on each wave BEHIND its own part of interval A, in front of the barrier -- a wave that is done early evaluates its nodes
-        // while others are still in their (latency-bound) items, instead of all eight saturating the vector units at once behind the barrier.
-        if (q_chain && tree_wave) {
-            if (!p_active) load_fc();
-            lds_poll_until<false>(chcnt_q, chnQ * S);
-            int tid = tid0;
-            LPCN_REMAT_V(tid);
-            const int twave = wave - LPCN_X3_TREE_FIRST;     // word of the ballot masks this wave fills
-            const int node = (tid - 64 * LPCN_X3_TREE_FIRST) >> 1;
-            const int node_level = node > 0 ? 31 - __clz(node) : 0;
-            const float *const thr_q = (const float *)(gq + L::g_thr);
-            unsigned long long *const mask_q = (unsigned long long *)(gq + L::g_mask);
-            // the node's 16 products for all four streams from the matrix pipe, four columns at a time, like a GRU-A item: lane k of a quad holds stream k's
-            // state, v_mfma_f32_4x4x1 with C = -0.0 returns (stream k's value) x (this lane's weight) in register k, rounded once; the sums stay in the
-            // reference's order as packed adds over stream pairs (src/nnet.c:194-199) -- 16 MFMA + 32 packed adds instead of 64 multiplies + 64 adds
-            // (146.7 -> 148.3 M samples/s)
-            float sums[S];
-            {
-                typedef float f4 __attribute__((ext_vector_type(4)));
-                typedef float f2 __attribute__((ext_vector_type(2)));
-                float hs[NB];
-                const float4 *hp = (const float4 *)(hB_q + (tid & 3) * NB);
+        // ---------------------------------------------------------------- P4 of group Q, stage 2, second part ----
+        // Behind the close of the segments: the state and the thresholds of the lane's stream, one 64-bit ballot, four three-level walks over its 16-bit
+        // fields (scalar); lane 16 f stores stream f's 8 bits for the leader, which reads them behind barriers 1 and 2.  In a group with fewer than four
+        // streams the unused fields belong to clamped copies: valid rows, values nobody reads.
+        if (s2_wave) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            const int ln = t_ & 63, f = lpcn_tree_packed_field(ln);
+            const unsigned long long m = tree_node_ballot(sub, hB_q + f * NB, (const float *)(gq + L::g_thr) + f * 8 + lpcn_tree_packed_level(ln), sm_tansig) & lpcn_tree_packed_mask();
+            int walks = 0;
 #pragma unroll
-                for (int qd = 0; qd < NB / 4; ++qd) { const float4 v4 = hp[qd]; hs[4 * qd] = v4.x; hs[4 * qd + 1] = v4.y; hs[4 * qd + 2] = v4.z; hs[4 * qd + 3] = v4.w; }
-                load_negz();
-                f2 s01 = {fcb, fcb}, s23 = {fcb, fcb};
-#pragma unroll
-                for (int jb = 0; jb < NB; jb += 4) {
-                    f4 pv[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) pv[c] = __builtin_amdgcn_mfma_f32_4x4x1f32(hs[jb + c], fcw[jb + c], negz, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        s01 = s01 + __builtin_shufflevector(pv[c], pv[c], 0, 1);
-                        s23 = s23 + __builtin_shufflevector(pv[c], pv[c], 2, 3);
-                    }
-                }
-                sums[0] = s01[0]; sums[1] = s01[1]; sums[2] = s23[0]; sums[3] = s23[1];
-            }
-            // the four streams stage by stage -- four table lookups in flight, the masks stored at the end (a store per stream makes every stream a basic block
-            // of its own, and the compiler then runs them one behind the other)
-            float vq[S], thq[S];
-            unsigned long long mq[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) { vq[s] = lpcn_tanh(sums[s], sm_tansig); thq[s] = thr_q[s * 8 + node_level]; }
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-                const float v = fcf * vq[s];
-                const float vo = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-                const float lg = v + vo;
-                mq[s] = __ballot(thq[s] < lg) & (twave == 0 ? 0x5555555555555554ull : 0x5555555555555555ull);
-            }
-            if (lane == 0) {
-#pragma unroll
-                for (int s = 0; s < S; ++s) mask_q[s * 8 + twave] = mq[s];
-            }
-            // wave LW: the prediction terms of Q's next sample that do not involve the sample about to be drawn (src/lpcnet.c:252,262)
-            if (is_lw) {
-                lpc_tap = ((const float *)(gq + L::g_lpc))[tid & 63];
-                prod_old = row_shr1(histQ, 0.f) * lpc_tap;
-            }
+            for (int k = 0; k < S; ++k) walks |= lpcn_tree_packed_walk(m, k) << (8 * k);
+            if ((ln & (LPCN_TREE_FIELD_LANES - 1)) == 0)
+                ((int *)(gq + L::g_mask))[f] = (pfx << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) | ((walks >> (8 * f)) & ((1 << (LPCN_TREE_LEVELS - LPCN_TREE_TOP)) - 1));
+        }
+        // wave LW: the prediction terms of Q's next sample that do not involve the sample about to be drawn (src/lpcnet.c:252,262)
+        if (q_chain && is_lw) {
+            int t_ = tid0;
+            LPCN_REMAT_V(t_);
+            lpc_tap = ((const float *)(gq + L::g_lpc))[t_ & 63];
+            prod_old = row_shr1(histQ, 0.f) * lpc_tap;
         }
         LPCN_X2_PROF(9);
         __syncthreads();                                                       // B1
@@ -660,7 +640,6 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
         { const bool t = liveP; liveP = liveQ; liveQ = t; }
         { const int t = live_maskP; live_maskP = live_maskQ; live_maskQ = t; }
         { const int t = seqP; seqP = seqQ; seqQ = t; }
-        { const int t = chnP; chnP = chnQ; chnQ = t; }
         { const int t = smpP; smpP = smpQ; smpQ = t; }
         { const int t = fP; fP = fQ; fQ = t; }
         asm volatile("; LPCN_SAMPLE_LOOP_END" ::: "memory");
