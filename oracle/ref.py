@@ -75,6 +75,24 @@ class RefLib:
         lib.ref_lpc_from_cepstrum.restype = C.c_float
         lib.ref_lpc_weighting.argtypes = [_f32p, C.c_float]
         lib.ref_decode_packet.argtypes = [_f32p, _f32p, _u8p]
+        if hasattr(lib, "ref_plc_get_state"):            # (absent from a library built before the PLC accessors existed)
+            lib.lpcnet_plc_create.restype = vp
+            lib.lpcnet_plc_create.argtypes = [C.c_int]
+            lib.lpcnet_plc_destroy.argtypes = [vp]
+            lib.lpcnet_plc_load_model.argtypes = [vp, C.c_char_p, C.c_int]
+            lib.lpcnet_plc_update.argtypes = [vp, _i16p]
+            lib.lpcnet_plc_conceal.argtypes = [vp, _i16p]
+            lib.lpcnet_plc_fec_add.argtypes = [vp, vp]
+            lib.lpcnet_plc_fec_clear.argtypes = [vp]
+            lib.ref_plc_lpcnet.restype = vp
+            lib.ref_plc_lpcnet.argtypes = [vp]
+            lib.ref_plc_enc.restype = vp
+            lib.ref_plc_enc.argtypes = [vp]
+            lib.ref_plc_net_units.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            lib.ref_plc_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+            lib.ref_get_deferred_state.argtypes = [vp, _f32p, _f32p]
+            lib.ref_enc_get_state.argtypes = [vp, vp]
+            lib.ref_enc_get_state.restype = C.c_int
         lib.kiss99_srand.argtypes = [_u32p, C.c_char_p, C.c_int]
         lib.kiss99_rand.argtypes = [_u32p]
         lib.kiss99_rand.restype = C.c_uint32
@@ -143,3 +161,75 @@ class RefState:
         rng = np.zeros(4, np.uint32)
         self.lib.ref_get_signal_state(self.p, ls, C.byref(le), C.byref(dm), C.byref(fc), rng)
         return ls, le.value, dm.value, fc.value, rng
+
+
+class _LpcnetView(RefState):
+    """the LPCNetState embedded in an LPCNetPLCState: RefState's readers on a pointer this object does not own"""
+
+    def __init__(self, lib, p):
+        self.lib, self.p = lib, p
+
+    def __del__(self):
+        pass
+
+
+class RefPlc:
+    """One LPCNetPLCState of the compiled reference (lpcnet_plc_create / _load_model / _update / _conceal / _fec_add / _fec_clear), with the
+    accessors of oracle/ref_harness.c: ctl() the nine control ints, snapshot() every member a stream's state is made of."""
+
+    def __init__(self, ref: RefLib, blob: bytes, options: int):
+        self.lib = ref.lib
+        self._blob = C.create_string_buffer(blob, len(blob))   # must outlive the state
+        self.p = self.lib.lpcnet_plc_create(options)
+        if self.lib.lpcnet_plc_load_model(self.p, self._blob, len(blob)) != 0:
+            raise RuntimeError("reference lpcnet_plc_load_model failed")
+        g1, g2 = C.c_int(), C.c_int()
+        self.lib.ref_plc_net_units(C.byref(g1), C.byref(g2))
+        self.g = (g1.value, g2.value)
+        self.lpcnet = _LpcnetView(self.lib, self.lib.ref_plc_lpcnet(self.p))
+
+    def __del__(self):
+        try:
+            self.lib.lpcnet_plc_destroy(self.p)
+        except Exception:
+            pass
+
+    def fec_add(self, features=None):
+        if features is None:
+            self.lib.lpcnet_plc_fec_add(self.p, None)
+        else:
+            v = np.ascontiguousarray(features, np.float32)
+            assert v.shape == (20,)
+            self.lib.lpcnet_plc_fec_add(self.p, v.ctypes.data)
+
+    def fec_clear(self):
+        self.lib.lpcnet_plc_fec_clear(self.p)
+
+    def step(self, frame: np.ndarray, lost) -> np.ndarray:
+        """one frame: lpcnet_plc_conceal when lost (the input is ignored), else lpcnet_plc_update -> the frame as the reference leaves it"""
+        out = np.zeros(160, np.int16) if lost else np.ascontiguousarray(frame, np.int16).copy()
+        (self.lib.lpcnet_plc_conceal if lost else self.lib.lpcnet_plc_update)(self.p, out)
+        return out
+
+    def ctl(self) -> np.ndarray:
+        c = np.zeros(9, np.int32)
+        self.lib.ref_plc_get_state(self.p, c.ctypes.data, None, None, None, None, None)
+        return c
+
+    def snapshot(self) -> dict:
+        """every member of the state, as the reference's own arrays (the names of tests/tools/plc_state_map.SNAP_FIELDS)"""
+        s = dict(ctl=np.zeros(9, np.int32), pcm=np.zeros(560, np.int16), features=np.zeros(20, np.float32),
+                 net=np.zeros((4, sum(self.g)), np.float32), dc=np.zeros(2, np.float64), fec=np.zeros((100, 20), np.float32))
+        self.lib.ref_plc_get_state(self.p, *(s[k].ctypes.data for k in ("ctl", "pcm", "features", "net", "dc", "fec")))
+        s["conv1"], s["conv2"], s["gru_a"], s["gru_b"] = self.lpcnet.nnet_state()
+        ls, le, dm, fc, rng = self.lpcnet.signal_state()
+        s.update(last_sig=ls, last_exc=np.int32(le), deemph_mem=np.float32(dm), frame_count=np.int32(fc), rng=rng)
+        s["lpc"], s["cond_a"], s["cond_b"] = self.lpcnet.frame_products()
+        s["old_lpc"], s["feature_buffer"] = np.zeros((2, 16), np.float32), np.zeros(80, np.float32)
+        self.lib.ref_get_deferred_state(self.lpcnet.p, s["old_lpc"], s["feature_buffer"])
+        enc = self.lib.ref_plc_enc(self.p)
+        buf = C.create_string_buffer(self.lib.ref_enc_get_state(enc, None))
+        self.lib.ref_enc_get_state(enc, buf)
+        s["enc"] = np.frombuffer(buf.raw, np.uint8).copy()
+        s["g"] = np.array(self.g, np.int32)
+        return s

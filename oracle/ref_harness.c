@@ -144,3 +144,72 @@ void  ref_decode_packet(float *features4x36, float *vq_mem, const unsigned char 
 {
     decode_packet((float (*)[NB_TOTAL_FEATURES])features4x36, vq_mem, buf);
 }
+
+/* ---- packet-loss concealment: the state of an LPCNetPLCState (src/lpcnet_private.h:78-106), copied out field by field -------- */
+LPCNetState    *ref_plc_lpcnet(LPCNetPLCState *st) { return &st->lpcnet; }
+LPCNetEncState *ref_plc_enc(LPCNetPLCState *st)    { return &st->enc; }
+
+/* widths of the PLC network's two GRU states as this build has them (generated plc_data.h) */
+void ref_plc_net_units(int *g1, int *g2)
+{
+    *g1 = (int)(sizeof(((PLCNetState *)0)->plc_gru1_state)/sizeof(float));
+    *g2 = (int)(sizeof(((PLCNetState *)0)->plc_gru2_state)/sizeof(float));
+}
+
+static float *put_net(float *out, const PLCNetState *n)
+{
+    memcpy(out, n->plc_gru1_state, sizeof(n->plc_gru1_state)); out += sizeof(n->plc_gru1_state)/sizeof(float);
+    memcpy(out, n->plc_gru2_state, sizeof(n->plc_gru2_state)); out += sizeof(n->plc_gru2_state)/sizeof(float);
+    return out;
+}
+
+/* ctl9 = {pcm_fill, skip_analysis, blend, loss_count, fec_fill_pos, fec_keep_pos, fec_read_pos, fec_skip, lpcnet.feature_buffer_fill};
+ * any of the array arguments may be NULL.  net = plc_net, plc_copy[0..2], each gru1 then gru2 state; dc2 = {dc_mem, syn_dc} */
+void ref_plc_get_state(const LPCNetPLCState *st, int *ctl9, short *pcm560, float *features20, float *net, double *dc2, float *fec100x20)
+{
+    int i;
+    if (ctl9) {
+        ctl9[0] = st->pcm_fill; ctl9[1] = st->skip_analysis; ctl9[2] = st->blend; ctl9[3] = st->loss_count;
+        ctl9[4] = st->fec_fill_pos; ctl9[5] = st->fec_keep_pos; ctl9[6] = st->fec_read_pos; ctl9[7] = st->fec_skip;
+        ctl9[8] = st->lpcnet.feature_buffer_fill;
+    }
+    if (pcm560) memcpy(pcm560, st->pcm, sizeof(st->pcm));
+    if (features20) memcpy(features20, st->features, sizeof(float)*NB_FEATURES);
+    if (net) {
+        net = put_net(net, &st->plc_net);
+        for (i=0;i<FEATURES_DELAY+1;i++) net = put_net(net, &st->plc_copy[i]);
+    }
+    if (dc2) { dc2[0] = st->dc_mem; dc2[1] = st->syn_dc; }
+    if (fec100x20) memcpy(fec100x20, st->fec, sizeof(st->fec));
+}
+
+/* the members of LPCNetState that ref_get_nnet_state / ref_get_signal_state / ref_get_frame_products do not return */
+void ref_get_deferred_state(const LPCNetState *st, float *old_lpc2x16, float *feature_buffer80)
+{
+    memcpy(old_lpc2x16, st->old_lpc, sizeof(st->old_lpc));
+    memcpy(feature_buffer80, st->feature_buffer, sizeof(st->feature_buffer));
+}
+
+/* LPCNetEncState (src/lpcnet_private.h:55-75) in the order of the engine's analysis-state record: analysis_mem[160], mem_preemph, pcount,
+ * pitch_mem[16], pitch_filt, exc_buf[576], pitch_max_path[0][0..224) (the rows the pitch search reads), pitch_max_path_all, best_i:
+ * 981 four-byte cells.  Returns the number of bytes written (out == NULL: just the size). */
+int ref_enc_get_state(const LPCNetEncState *st, void *out)
+{
+    char *p = (char *)out;
+    const int paths = PITCH_MAX_PERIOD-PITCH_MIN_PERIOD;
+    const int size = (int)(sizeof(st->analysis_mem) + sizeof(st->mem_preemph) + sizeof(st->pcount) + sizeof(st->pitch_mem) + sizeof(st->pitch_filt)
+                     + sizeof(st->exc_buf) + sizeof(float)*paths + sizeof(st->pitch_max_path_all) + sizeof(st->best_i));
+    if (!out) return size;
+#define PUT(src, n) do { memcpy(p, src, n); p += n; } while (0)
+    PUT(st->analysis_mem, sizeof(st->analysis_mem));
+    PUT(&st->mem_preemph, sizeof(st->mem_preemph));
+    PUT(&st->pcount, sizeof(st->pcount));
+    PUT(st->pitch_mem, sizeof(st->pitch_mem));
+    PUT(&st->pitch_filt, sizeof(st->pitch_filt));
+    PUT(st->exc_buf, sizeof(st->exc_buf));
+    PUT(st->pitch_max_path[0], sizeof(float)*paths);
+    PUT(&st->pitch_max_path_all, sizeof(st->pitch_max_path_all));
+    PUT(&st->best_i, sizeof(st->best_i));
+#undef PUT
+    return size;
+}
