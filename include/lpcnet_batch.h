@@ -489,8 +489,8 @@ LPCNET_EXPORT int lpcnet_hip_quant_sweep_device(unsigned long long *out3);
  *   every index inside the capacity: else LPCNET_HIP_E_ARG and nothing has changed.  Pairs inside one shard: one upload of the pair list and ONE
  *   launch per shard, only enqueued on hip_stream (NULL = the batch's own; on a sharded batch it must be NULL) under the ordering rules of
  *   lpcnet_batch_analyze_device; LPCNET_HIP_E_ARG on a capturing stream.  The host halves (PLC control state, the products' flag) are copied
- *   when the call is made, which is when the planners of the steps run too: call order is the order.  Pairs ACROSS shards go through pinned
- *   host memory and synchronise both shards: an occasional operation, not one for every step.
+ *   when the call is made, which is when the planners of the steps run too: call order is the order.  Pairs ACROSS shards are grouped by
+ *   (source shard, destination shard) and move like copy_streams_to below: one gather, one transfer and one scatter per shard pair, only enqueued.
  * A stream leaves by copying the last active stream of its shard into its slot and lowering the count; a stream joins by reset (and
  *   analysis_reset / plc_reset where used) of the slot at the count and raising it.  lpcnet_amd/roster.py (StreamRoster) keeps that book. */
 LPCNET_EXPORT int lpcnet_batch_set_active(LPCNetBatch *b, const int *active, int n_shards);
@@ -500,6 +500,79 @@ LPCNET_EXPORT int lpcnet_batch_copy_streams(LPCNetBatch *b, const int *src, cons
 /* the decoder's per-stream VQ memory (float[18]; zero after lpcnet_batch_reset): with it a per-stream snapshot covers every state of a stream */
 LPCNET_EXPORT int lpcnet_batch_get_decoder_vq_mem(LPCNetBatch *b, int stream, float *out18);
 LPCNET_EXPORT int lpcnet_batch_set_decoder_vq_mem(LPCNetBatch *b, int stream, const float *in18);
+/* Stream snapshots: m streams' complete records to or from one contiguous buffer, in one launch per shard.
+ * A RECORD is everything copy_streams moves, laid end to end: every per-stream array that is allocated at the time of the call is one SECTION, in
+ *   the order of the ids below, each on a 16-byte boundary, its bytes the device array's; the PLC's control ints (LPCNET_SNAP_PLC_CTL, 9 ints, with
+ *   PLC enabled) and the kept products' flag (LPCNET_SNAP_KEEP_FLAG, 1 int, always) are sections too.  The record length is a multiple of 16.
+ * snapshot_layout: the batch's present section table, sections [k][3] = {id, bytes per stream, offset in the record} (entries beyond `cap` rows are
+ *   not written) and the record length; returns k.  snapshot_bytes: the size of a host blob of m streams with that layout (0 without a model).
+ * snapshot: the records of streams[0 .. m) (distinct, any stream of the capacity) as a host BLOB: header ("LPCS", version, m), the layout -- record
+ *   length, sections, the blob's flavour, the PLC options and widths, the DRED encoder's record length, this library's state_size /
+ *   analysis_state_size / plc_state_size and a 64-bit hash of the model blob (information only) --, meta [m][LPCNET_SNAP_META] ints (the host halves),
+ *   m records.  Copies out and synchronises; LPCNET_HIP_E_ARG when cap is below snapshot_bytes(b, m).  buf must be 4-byte aligned.
+ * restore: record i of the blob -> stream streams[i], i < m (m at most the blob's count: the first m records; streams distinct).  The blob's layout
+ *   must MATCH the batch: a section on both sides has equal bytes; another flavour, PLC on one side only or with other options or widths, and a blob
+ *   of a build with other struct sizes are LPCNET_HIP_E_MODEL with a message that names the section; a section only the snapshot has makes the host
+ *   form enable that subsystem in the batch first (analysis, encoder, kept products, DRED encoder -- as copy_streams across shards does); a section
+ *   only the batch has receives a fresh stream's record (zeros, a reset control state, flag 0).  A NULL, truncated or inconsistent blob is
+ *   LPCNET_HIP_E_ARG.  On any refusal nothing has changed.  On a sharded batch both host forms run one host thread per shard.
+ * snapshot_device / restore_device: the same on device memory, ONE upload of the list and ONE launch, only enqueued on hip_stream (NULL = the batch's
+ *   own) under the ordering rules of lpcnet_batch_analyze_device; LPCNET_HIP_E_ARG on a capturing stream.  d_records holds m records of the batch's
+ *   present layout (16-byte aligned); meta [m][LPCNET_SNAP_META] is a HOST array: snapshot_device has filled it when it returns, restore_device reads
+ *   it when it is called -- the host halves move when the call is made, which is when the planners of the steps run too: call order is the order, as
+ *   for copy_streams.  restore_device takes the section table the records were written with ([n_sections][3]); flavour and PLC options do not travel
+ *   in it, and a section only the snapshot has is LPCNET_HIP_E_MODEL here (nothing is allocated).  Neither call allocates after the batch's first
+ *   snapshot or copy, waits for enqueued work or changes the active counts.  The forms without _shard need a batch of one shard.
+ * copy_streams_to: stream src[i] of `from` -> stream dst[i] of `to`, i < m (src distinct, dst distinct; the two batches differ): a snapshot of
+ *   `from` and a restore into `to` through staging buffers the library owns, shard pair by shard pair.  On one device: a gather on the source's
+ *   stream, a scatter on the destination's behind an event -- no host hop, no wait.  On two devices: gather, one device-to-device copy (one bounce
+ *   of the whole buffer through pinned host memory where the devices cannot reach each other), scatter.  Only enqueued; `from` is unchanged; missing
+ *   subsystems are enabled in `to` as restore does.  Ordering as copy_streams: the host halves move when the call is made. */
+#define LPCNET_SNAP_SYNTH      1
+#define LPCNET_SNAP_DEC_VQ     2
+#define LPCNET_SNAP_AN         3
+#define LPCNET_SNAP_ENC_VQ     4
+#define LPCNET_SNAP_KEEP_A     5
+#define LPCNET_SNAP_KEEP_B     6
+#define LPCNET_SNAP_KEEP_LPC   7
+#define LPCNET_SNAP_KEEP_FLAG  8
+#define LPCNET_SNAP_PLC_Q      9
+#define LPCNET_SNAP_PLC_FEAT  10
+#define LPCNET_SNAP_PLC_NET   11
+#define LPCNET_SNAP_PLC_DC    12
+#define LPCNET_SNAP_PLC_DELTA 13
+#define LPCNET_SNAP_PLC_FEC   14
+#define LPCNET_SNAP_PLC_FBUF  15
+#define LPCNET_SNAP_PLC_LP    16
+#define LPCNET_SNAP_PLC_BURG  17
+#define LPCNET_SNAP_PLC_AN    18
+#define LPCNET_SNAP_PLC_CTL   19
+#define LPCNET_SNAP_DRED_ENC  20
+#define LPCNET_SNAP_META      10      /* ints of a stream's host halves: the PLC's nine control ints (zero without PLC), the kept products' flag */
+#define LPCNET_SNAP_CONFIG    10      /* ints of a configuration, below */
+#define LPCNET_SNAP_LAYOUT_INTS 92    /* the most ints a layout has: 14 head fields and 26 sections */
+LPCNET_EXPORT int    lpcnet_batch_snapshot_layout(const LPCNetBatch *b, int *sections, int cap, int *record_bytes);
+LPCNET_EXPORT size_t lpcnet_batch_snapshot_bytes(const LPCNetBatch *b, int m);
+LPCNET_EXPORT int    lpcnet_batch_snapshot(LPCNetBatch *b, const int *streams, int m, void *buf, size_t cap);
+LPCNET_EXPORT int    lpcnet_batch_restore(LPCNetBatch *b, const int *streams, int m, const void *buf, size_t len);
+LPCNET_EXPORT int    lpcnet_batch_snapshot_device(LPCNetBatch *b, const int *streams, int m, void *d_records, int *meta, void *hip_stream);
+LPCNET_EXPORT int    lpcnet_batch_restore_device(LPCNetBatch *b, const int *streams, int m, const void *d_records, const int *meta,
+                                                 const int *sections, int n_sections, void *hip_stream);
+/* ... on ONE shard of a sharded batch: the shard's own stream indices, pointers on the shard's device */
+LPCNET_EXPORT int    lpcnet_batch_snapshot_device_shard(LPCNetBatch *b, int shard, const int *streams, int m, void *d_records, int *meta, void *hip_stream);
+LPCNET_EXPORT int    lpcnet_batch_restore_device_shard(LPCNetBatch *b, int shard, const int *streams, int m, const void *d_records, const int *meta,
+                                                       const int *sections, int n_sections, void *hip_stream);
+LPCNET_EXPORT int    lpcnet_batch_copy_streams_to(LPCNetBatch *from, const int *src, LPCNetBatch *to, const int *dst, int m);
+/* Without a device.  snapshot_layout: config [LPCNET_SNAP_CONFIG] = {int8 blob, analysis, encoder, kept products, PLC, PLC options, PLC widths g1, g2,
+ * floats of the DRED encoder's record (0: not enabled), its max_dframes} -> out [k][3] as above, then the record length in out[3 k] where cap (ints)
+ * allows; returns k.  snapshot_info: a blob's header and layout, info = {version, m, record bytes, sections k, flavour, PLC, PLC options, g1, g2,
+ * DRED encoder floats, its max_dframes, state_size, analysis_state_size, plc_state_size, hash low, hash high, k x {id, bytes, offset}}; returns the
+ * ints written (at most cap), LPCNET_HIP_E_ARG for a NULL, truncated, wrong-magic or wrong-version buffer or one whose lengths do not add up.
+ * snapshot_match: would a snapshot of config_snap restore into a batch of config_batch?  0 yes; 1 yes in the host form, which enables the missing
+ * subsystem first (with enqueue_only != 0 that is a refusal); LPCNET_HIP_E_MODEL no, *section (may be NULL) the section the message names. */
+LPCNET_EXPORT int    lpcnet_hip_snapshot_layout(const int *config, int *out, int cap);
+LPCNET_EXPORT int    lpcnet_hip_snapshot_info(const void *buf, size_t len, int *info, int cap);
+LPCNET_EXPORT int    lpcnet_hip_snapshot_match(const int *config_snap, const int *config_batch, int enqueue_only, int *section);
 /* raw per-stream state record (layout = struct lpcn_stream_state in lpcnet_amd/csrc/lpcnet_engine.h) */
 LPCNET_EXPORT int lpcnet_batch_state_size(void);
 LPCNET_EXPORT int lpcnet_batch_get_raw_state(LPCNetBatch *b, int stream, void *out);

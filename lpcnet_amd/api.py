@@ -128,6 +128,65 @@ def _feed_args(n, count, skip, clear):
     return count, skip, clear
 
 
+# ---- stream snapshots (include/lpcnet_batch.h: lpcnet_batch_snapshot) ----
+SNAP_META = 10
+SNAP_SECTIONS = ("SYNTH", "DEC_VQ", "AN", "ENC_VQ", "KEEP_A", "KEEP_B", "KEEP_LPC", "KEEP_FLAG", "PLC_Q", "PLC_FEAT", "PLC_NET", "PLC_DC", "PLC_DELTA",
+                 "PLC_FEC", "PLC_FBUF", "PLC_LP", "PLC_BURG", "PLC_AN", "PLC_CTL", "DRED_ENC")
+SNAP = {name: i + 1 for i, name in enumerate(SNAP_SECTIONS)}      # section ids (LPCNET_SNAP_*)
+_SNAP_LAYOUT_INTS = 92
+
+
+def _snap_config(config):
+    """a configuration as the ten ints of LPCNET_SNAP_CONFIG, from a dict (missing keys: off / 0) or a sequence"""
+    if isinstance(config, dict):
+        keys = ("int8", "analysis", "encoder", "keep", "plc", "plc_options", "g1", "g2", "dred_enc_floats", "dred_enc_dframes")
+        unknown = set(config) - set(keys)
+        if unknown:
+            raise ValueError(f"unknown configuration keys {sorted(unknown)}")
+        config = [int(config.get(k, 0)) for k in keys]
+    cfg = np.ascontiguousarray(config, np.int32)
+    assert cfg.shape == (10,)
+    return cfg
+
+
+def snapshot_layout(config):
+    """The snapshot record of a configuration, without a device: config = dict(int8, analysis, encoder, keep, plc, plc_options, g1, g2,
+    dred_enc_floats, dred_enc_dframes) -> dict(sections [(id, bytes per stream, offset)], record_bytes)."""
+    L = load_library()
+    cfg = _snap_config(config)
+    out = np.zeros(_SNAP_LAYOUT_INTS, np.int32)
+    k = L.lpcnet_hip_snapshot_layout(cfg.ctypes.data, out.ctypes.data, out.size)
+    if k < 0:
+        raise LPCNetError("snapshot_layout failed (%d): %s" % (k, last_error()))
+    return dict(sections=[tuple(int(x) for x in out[3 * i:3 * i + 3]) for i in range(k)], record_bytes=int(out[3 * k]))
+
+
+def snapshot_info(blob: bytes):
+    """The header and layout of a snapshot blob: dict(version, m, record_bytes, int8, plc, plc_options, g1, g2, dred_enc_floats, dred_enc_dframes,
+    state_size, analysis_state_size, plc_state_size, model_hash, sections [(id, bytes, offset)]).  LPCNetError for anything that is not a blob."""
+    L = load_library()
+    info = np.zeros(4 + _SNAP_LAYOUT_INTS, np.int32)
+    n = L.lpcnet_hip_snapshot_info(bytes(blob), len(blob), info.ctypes.data, info.size)
+    if n < 0:
+        raise LPCNetError("snapshot_info failed (%d): %s" % (n, last_error()))
+    keys = ("version", "m", "record_bytes", "n_sections", "int8", "plc", "plc_options", "g1", "g2", "dred_enc_floats", "dred_enc_dframes", "state_size",
+            "analysis_state_size", "plc_state_size")
+    d = {k: int(v) for k, v in zip(keys, info)}
+    d["model_hash"] = (int(info[14]) & 0xffffffff) | ((int(info[15]) & 0xffffffff) << 32)
+    d["sections"] = [tuple(int(x) for x in info[16 + 3 * i:19 + 3 * i]) for i in range(d.pop("n_sections"))]
+    return d
+
+
+def snapshot_match(config_snap, config_batch, enqueue_only: bool = False):
+    """Would a snapshot of one configuration restore into a batch of another?  (code, section id): 0 yes, 1 yes in the host form (which enables the
+    missing subsystem first), LPCNET_HIP_E_MODEL (-5) no -- last_error() says why and the section is the one it names."""
+    L = load_library()
+    a, b = _snap_config(config_snap), _snap_config(config_batch)
+    sec = C.c_int(0)
+    rc = L.lpcnet_hip_snapshot_match(a.ctypes.data, b.ctypes.data, 1 if enqueue_only else 0, C.byref(sec))
+    return rc, sec.value
+
+
 def load_library():
     """dlopen liblpcnet_hip.so (built by `python -m lpcnet_amd.build`).  Raises if it is absent:
     the product path never falls back to a CPU implementation."""
@@ -264,6 +323,19 @@ def load_library():
     L.lpcnet_batch_get_active.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
     L.lpcnet_batch_active_streams.argtypes = [vp]
     L.lpcnet_batch_copy_streams.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.lpcnet_batch_snapshot_layout.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.lpcnet_batch_snapshot_bytes.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_snapshot_bytes.restype = C.c_size_t
+    L.lpcnet_batch_snapshot.argtypes = [vp, vp, C.c_int, vp, C.c_size_t]
+    L.lpcnet_batch_restore.argtypes = [vp, vp, C.c_int, C.c_char_p, C.c_size_t]
+    L.lpcnet_batch_snapshot_device.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.lpcnet_batch_restore_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.lpcnet_batch_snapshot_device_shard.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.lpcnet_batch_restore_device_shard.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    L.lpcnet_batch_copy_streams_to.argtypes = [vp, vp, vp, vp, C.c_int]
+    L.lpcnet_hip_snapshot_layout.argtypes = [vp, vp, C.c_int]
+    L.lpcnet_hip_snapshot_info.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_int]
+    L.lpcnet_hip_snapshot_match.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_batch_export_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_import_state.argtypes = [vp, C.c_int, vp]
     L.lpcnet_batch_set_streams_per_workgroup.argtypes = [vp, C.c_int]
@@ -969,10 +1041,59 @@ class LPCNetBatch:
 
     def copy_streams(self, src, dst, hip_stream: int = 0):
         """stream src[i] -> stream dst[i]: everything the batch keeps per stream, on the device (one launch per shard, only enqueued; pairs across
-        shards go through the host and synchronise).  All dst distinct, no stream in both lists"""
+        shards: a gather, a transfer and a scatter per shard pair, only enqueued too).  All dst distinct, no stream in both lists"""
         src, dst = np.ascontiguousarray(src, np.int32).reshape(-1), np.ascontiguousarray(dst, np.int32).reshape(-1)
         assert src.size == dst.size
         self._chk(self.L.lpcnet_batch_copy_streams(self.p, src.ctypes.data, dst.ctypes.data, int(src.size), hip_stream or None), "copy_streams")
+
+    # ---- stream snapshots (include/lpcnet_batch.h: lpcnet_batch_snapshot) ----
+    def snapshot_layout(self):
+        """the batch's present record: dict(sections [(id, bytes per stream, offset)], record_bytes)"""
+        sec = np.zeros((_SNAP_LAYOUT_INTS // 3, 3), np.int32)
+        rb = C.c_int(0)
+        k = self.L.lpcnet_batch_snapshot_layout(self.p, sec.ctypes.data, sec.shape[0], C.byref(rb))
+        if k < 0:
+            self._chk(k, "snapshot_layout")
+        return dict(sections=[tuple(int(x) for x in row) for row in sec[:k]], record_bytes=rb.value)
+
+    def snapshot(self, streams) -> bytes:
+        """the complete records of `streams` (distinct, any stream of the capacity) as one blob; copies out and synchronises"""
+        st = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        buf = np.zeros((self.L.lpcnet_batch_snapshot_bytes(self.p, int(st.size)) + 3) // 4, np.int32)      # (4-byte aligned)
+        self._chk(self.L.lpcnet_batch_snapshot(self.p, st.ctypes.data, int(st.size), buf.ctypes.data, buf.nbytes), "snapshot")
+        return buf.tobytes()
+
+    def restore(self, streams, blob: bytes):
+        """record i of the blob -> stream streams[i] (the first len(streams) records); the blob's layout must match the batch"""
+        st = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        self._chk(self.L.lpcnet_batch_restore(self.p, st.ctypes.data, int(st.size), bytes(blob), len(blob)), "restore")
+
+    def snapshot_device(self, streams, d_records_ptr: int, hip_stream: int = 0, shard=None) -> np.ndarray:
+        """enqueue only: the records of `streams` to device memory (len(streams) * record_bytes, 16-byte aligned).  Returns meta (m, 10) int32: the
+        host halves, taken when the call is made.  shard: the shard's own indices and device"""
+        st = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        meta = np.zeros((st.size, SNAP_META), np.int32)
+        args = (st.ctypes.data, int(st.size), d_records_ptr, meta.ctypes.data, hip_stream or None)
+        rc = self.L.lpcnet_batch_snapshot_device(self.p, *args) if shard is None else self.L.lpcnet_batch_snapshot_device_shard(self.p, shard, *args)
+        self._chk(rc, "snapshot_device")
+        return meta
+
+    def restore_device(self, streams, d_records_ptr: int, meta, sections, hip_stream: int = 0, shard=None):
+        """enqueue only: record i at d_records_ptr -> stream streams[i]; meta as snapshot_device returned it, sections as snapshot_layout()["sections"]
+        of the batch the records came from"""
+        st = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        meta = np.ascontiguousarray(meta, np.int32)
+        sec = np.ascontiguousarray(sections, np.int32).reshape(-1, 3)
+        assert meta.shape == (st.size, SNAP_META)
+        args = (st.ctypes.data, int(st.size), d_records_ptr, meta.ctypes.data, sec.ctypes.data, sec.shape[0], hip_stream or None)
+        rc = self.L.lpcnet_batch_restore_device(self.p, *args) if shard is None else self.L.lpcnet_batch_restore_device_shard(self.p, shard, *args)
+        self._chk(rc, "restore_device")
+
+    def copy_streams_to(self, src, other: "LPCNetBatch", dst):
+        """stream src[i] of this batch -> stream dst[i] of `other`: gather, transfer, scatter on the device, only enqueued; this batch is unchanged"""
+        src, dst = np.ascontiguousarray(src, np.int32).reshape(-1), np.ascontiguousarray(dst, np.int32).reshape(-1)
+        assert src.size == dst.size
+        self._chk(self.L.lpcnet_batch_copy_streams_to(self.p, src.ctypes.data, other.p, dst.ctypes.data, int(src.size)), "copy_streams_to")
 
     def set_lpc_gamma(self, gamma: float):
         self._chk(self.L.lpcnet_batch_set_lpc_gamma(self.p, gamma), "set_lpc_gamma")

@@ -25,7 +25,7 @@ C_FLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-std=gnu11", "-Wall", "-fvisibi
 CXX_FLAGS = ["-std=c++17" if x == "-std=gnu11" else x for x in C_FLAGS]      # host C++ (plc_plan.cpp: the PLC planner, no device code)
 
 # The engine's host runtime, one unit per subsystem (engine_core.h is what they share; each kernel header belongs to one unit) ...
-ENGINE_UNITS = ("engine", "engine_synth", "engine_codec", "engine_plc", "engine_probe", "engine_roster", "engine_dred", "engine_dred_enc")
+ENGINE_UNITS = ("engine", "engine_synth", "engine_codec", "engine_plc", "engine_probe", "engine_roster", "engine_snapshot", "engine_dred", "engine_dred_enc")
 # ... the C host shell, one unit per API surface (api_internal.h / api_shards.h are what they share); api_stream holds the model registry ...
 API_UNITS = ("api_core", "api_stream", "api_batch", "api_tools")
 REGISTRY_UNIT = "api_stream"

@@ -2,6 +2,7 @@
  * device runtime declared in lpcnet_engine.h.  Which streams a shard owns and how one call fans out over the shards is api_shards.h. */
 #include "api_internal.h"
 #include "api_roster.h"
+#include "snapshot_plan.h"
 
 LPCNetBatch *lpcnet_batch_create_sharded(int n_streams, const int *devices, int n_devices)
 {
@@ -68,6 +69,8 @@ int lpcnet_batch_load_model(LPCNetBatch *b, const unsigned char *data, int len)
         if (b->sh[k].engine) lpcn_engine_destroy(b->sh[k].engine);
         b->sh[k].engine = e[k]; b->sh[k].dev = d[k]; b->sh[k].cb_version = 0;
     }
+    b->model_hash = 14695981039346656037ull;             /* (taken once, here: a snapshot's layout carries it) */
+    for (int i = 0; i < len; i++) b->model_hash = (b->model_hash ^ data[i]) * 1099511628211ull;
     return 0;
 }
 
@@ -657,6 +660,7 @@ int lpcnet_batch_active_streams(const LPCNetBatch *b)
     for (int k = 0; k < b->n_shards; k++) sum += lpcn_batch_dev_active(b->sh[k].dev);
     return sum;
 }
+static int copy_pairs_between(LPCNetBatch *from, const int *src, LPCNetBatch *to, const int *dst, int m);
 int lpcnet_batch_copy_streams(LPCNetBatch *b, const int *src, const int *dst, int m, void *hip_stream)
 {
     NEED_MODEL(b);
@@ -677,14 +681,203 @@ int lpcnet_batch_copy_streams(LPCNetBatch *b, const int *src, const int *dst, in
     const int nx = roster_split(b->at, b->n_shards, src, dst, m, first, lsrc, ldst, xsrc, xdst);
     for (int k = 0; k < b->n_shards && !rc; k++)         /* one upload and one launch per shard, only enqueued */
         if (first[k + 1] > first[k]) rc = lpcn_batch_dev_copy_streams(b->sh[k].dev, lsrc + first[k], ldst + first[k], first[k + 1] - first[k], hip_stream);
-    for (int i = 0; i < nx && !rc; i++) {                /* across shards: through the host, both shards synchronised */
-        int ls = 0, ld = 0;
-        const int ks = shard_of(b->at, b->n_shards, xsrc[i], &ls), kd = shard_of(b->at, b->n_shards, xdst[i], &ld);
-        rc = lpcn_batch_dev_copy_stream_across(b->sh[ks].dev, ls, b->sh[kd].dev, ld);
-    }
     if (rc) take_engine_err();
+    else if (nx) rc = copy_pairs_between(b, xsrc, b, xdst, nx);      /* across shards: one gather, one transfer and one scatter per shard pair, only enqueued */
     free(mark);
     return rc;
+}
+
+/* ---- stream snapshots (include/lpcnet_batch.h; the record, its layout and the blob are snapshot_plan.h) ---- */
+/* the batch's present layout: shard 0's with the model's hash; every shard must have the same sections (a copy across shards can enable a
+ * subsystem in one shard alone: such a batch is brought level with the lpcnet_batch_*_enable calls) */
+static int batch_layout(const LPCNetBatch *b, int *lay)
+{
+    int other[LPCN_SNAP_LAYOUT_MAX];
+    int n = lpcn_batch_dev_snapshot_layout(b->sh[0].dev, lay);
+    if (n < 0) { take_engine_err(); return n; }
+    for (int k = 1; k < b->n_shards; k++) {
+        const int nk = lpcn_batch_dev_snapshot_layout(b->sh[k].dev, other);
+        if (nk < 0) { take_engine_err(); return nk; }
+        if (nk != n || memcmp(other, lay, sizeof(int) * (size_t)n)) { set_err("snapshot: the shards of the batch have different subsystems enabled"); return LPCN_E_MODEL; }
+    }
+    lay[SNAP_L_HASH_LO] = (int)(unsigned)(b->model_hash & 0xffffffffu); lay[SNAP_L_HASH_HI] = (int)(unsigned)(b->model_hash >> 32);
+    return n;
+}
+int lpcnet_batch_snapshot_layout(const LPCNetBatch *b, int *sections, int cap, int *record_bytes)
+{
+    NEED_MODEL(b);
+    int lay[LPCN_SNAP_LAYOUT_MAX];
+    if (cap < 0 || (cap && !sections)) { set_err("lpcnet_batch_snapshot_layout: bad arguments"); return LPCN_E_ARG; }
+    const int n = batch_layout(b, lay);
+    if (n < 0) return n;
+    for (int k = 0; k < lay[SNAP_L_SECTIONS] && k < cap; k++) memcpy(sections + 3 * k, snap_section(lay, k), sizeof(int) * 3);
+    if (record_bytes) *record_bytes = lay[SNAP_L_RECORD];
+    return lay[SNAP_L_SECTIONS];
+}
+size_t lpcnet_batch_snapshot_bytes(const LPCNetBatch *b, int m)
+{
+    int lay[LPCN_SNAP_LAYOUT_MAX];
+    if (!b || !b->n_shards || !b->sh[0].dev || m < 0 || batch_layout(b, lay) < 0) return 0;
+    return snap_blob_bytes(lay, m);
+}
+/* a list of the batch's streams, distinct: the streams of shard k in the shard's own indices at ls [first[k], first[k + 1]) with the list entry each
+ * came from in pos; ls and pos hold m ints each, mark one byte per stream of the batch.  0, or -1 - i with i the first bad entry */
+static int snapshot_split(const LPCNetBatch *b, const int *streams, int m, int *first, int *ls, int *pos, unsigned char *mark)
+{
+    int fill[LPCN_MAX_SHARDS], local = 0;
+    memset(mark, 0, (size_t)b->n);
+    for (int k = 0; k <= b->n_shards; k++) first[k] = 0;
+    for (int i = 0; i < m; i++) {
+        const int k = shard_of(b->at, b->n_shards, streams[i], &local);
+        if (k < 0 || mark[streams[i]]) return -1 - i;
+        mark[streams[i]] = 1;
+        first[k + 1]++;
+    }
+    for (int k = 0; k < b->n_shards; k++) { first[k + 1] += first[k]; fill[k] = first[k]; }
+    for (int i = 0; i < m; i++) {
+        const int k = shard_of(b->at, b->n_shards, streams[i], &local);
+        ls[fill[k]] = local; pos[fill[k]++] = i;
+    }
+    return 0;
+}
+typedef struct { LPCNetBatch *b; const int *first, *ls, *pos; char *records; int *meta; const char *in_records; const int *in_meta, *layout; } snap_args;
+static int snapshot_shard(void *args, int k)
+{
+    const snap_args *a = (const snap_args *)args;
+    const int f = a->first[k], cnt = a->first[k + 1] - f;
+    if (!cnt) return 0;
+    if (a->layout) return lpcn_batch_dev_restore_host(a->b->sh[k].dev, a->ls + f, a->pos + f, cnt, a->in_records, a->in_meta, a->layout);
+    return lpcn_batch_dev_snapshot_host(a->b->sh[k].dev, a->ls + f, a->pos + f, cnt, a->records, a->meta);
+}
+/* the split of a list for the host forms, in one allocation: *scratch is the caller's to free */
+static int snapshot_lists(LPCNetBatch *b, const int *streams, int m, int *first, int **ls, int **pos, void **scratch, const char *what)
+{
+    char msg[160];
+    if (m < 0 || m > b->n || (m && !streams)) { snprintf(msg, sizeof(msg), "%s: bad arguments", what); set_err(msg); return LPCN_E_ARG; }
+    int *mem = (int *)malloc(2 * (size_t)(m + 1) * sizeof(int) + (size_t)b->n);
+    if (!mem) { set_err("snapshot: out of memory"); return LPCN_E_ARG; }
+    *ls = mem; *pos = mem + m + 1; *scratch = mem;
+    const int bad = snapshot_split(b, streams, m, first, *ls, *pos, (unsigned char *)(mem + 2 * (m + 1)));
+    if (bad) {
+        snprintf(msg, sizeof(msg), "%s: entry %d (stream %d) lies outside the batch's %d streams or is listed twice", what, -1 - bad, streams[-1 - bad], b->n);
+        set_err(msg); free(mem); return LPCN_E_ARG;
+    }
+    return 0;
+}
+int lpcnet_batch_snapshot(LPCNetBatch *b, const int *streams, int m, void *buf, size_t cap)
+{
+    NEED_MODEL(b);
+    int lay[LPCN_SNAP_LAYOUT_MAX], first[LPCN_MAX_SHARDS + 1], *ls, *pos, *meta;
+    void *scratch;
+    char *records;
+    int rc = batch_layout(b, lay);
+    if (rc < 0) return rc;
+    if ((rc = snapshot_lists(b, streams, m, first, &ls, &pos, &scratch, "lpcnet_batch_snapshot"))) return rc;
+    if (snap_blob_begin(buf, cap, lay, m, &meta, &records)) { set_err("lpcnet_batch_snapshot: the buffer is NULL, not 4-byte aligned or smaller than lpcnet_batch_snapshot_bytes"); free(scratch); return LPCN_E_ARG; }
+    snap_args a = {b, first, ls, pos, records, meta, NULL, NULL, NULL};
+    rc = run_shards(b, snapshot_shard, &a);
+    free(scratch);
+    return rc;
+}
+int lpcnet_batch_restore(LPCNetBatch *b, const int *streams, int m, const void *buf, size_t len)
+{
+    NEED_MODEL(b);
+    int lay[LPCN_SNAP_LAYOUT_MAX], first[LPCN_MAX_SHARDS + 1], *ls, *pos, have = 0, need = 0;
+    const int *meta;
+    const char *records;
+    void *scratch;
+    if (snap_blob_parse(buf, len, &have, lay, &meta, &records)) { set_err("lpcnet_batch_restore: not a snapshot blob (NULL, truncated, wrong magic or version, or lengths that do not add up)"); return LPCN_E_ARG; }
+    if (m > have) { set_err("lpcnet_batch_restore: the blob holds fewer records"); return LPCN_E_ARG; }
+    int rc = snapshot_lists(b, streams, m, first, &ls, &pos, &scratch, "lpcnet_batch_restore");
+    if (rc) return rc;
+    for (int k = 0; k < b->n_shards && rc >= 0; k++) {   /* (every shard is asked before any shard changes) */
+        rc = lpcn_batch_dev_snapshot_match(b->sh[k].dev, lay, 0);
+        if (rc > 0) need = 1;
+    }
+    if (rc < 0) { take_engine_err(); free(scratch); return rc; }
+    for (int k = 0; need && k < b->n_shards; k++)
+        if ((rc = lpcn_batch_dev_snapshot_enable(b->sh[k].dev, lay))) { take_engine_err(); free(scratch); return rc; }
+    snap_args a = {b, first, ls, pos, NULL, NULL, records, meta, lay};
+    rc = run_shards(b, snapshot_shard, &a);
+    free(scratch);
+    return rc;
+}
+int lpcnet_batch_snapshot_device_shard(LPCNetBatch *b, int shard, const int *streams, int m, void *d_records, int *meta, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_snapshot(b->sh[shard].dev, streams, m, d_records, meta, hip_stream));
+}
+int lpcnet_batch_snapshot_device(LPCNetBatch *b, const int *streams, int m, void *d_records, int *meta, void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_snapshot_device");
+    return lpcnet_batch_snapshot_device_shard(b, 0, streams, m, d_records, meta, hip_stream);
+}
+int lpcnet_batch_restore_device_shard(LPCNetBatch *b, int shard, const int *streams, int m, const void *d_records, const int *meta,
+                                      const int *sections, int n_sections, void *hip_stream)
+{
+    NEED_MODEL(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("shard index"); return LPCN_E_ARG; }
+    int lay[LPCN_SNAP_LAYOUT_MAX];
+    if (!sections || n_sections < 1 || n_sections > LPCN_SNAP_MAX_SECTIONS) { set_err("lpcnet_batch_restore_device: bad section table"); return LPCN_E_ARG; }
+    /* the head fields do not travel in a section table: the batch's own stand in, and the sections decide */
+    if (lpcn_batch_dev_snapshot_layout(b->sh[shard].dev, lay) < 0) { take_engine_err(); return LPCN_E_HIP; }
+    memcpy(lay + SNAP_L_HEAD, sections, sizeof(int) * 3 * (size_t)n_sections);
+    lay[SNAP_L_SECTIONS] = n_sections;
+    lay[SNAP_L_RECORD] = (sections[3 * (n_sections - 1) + 1] + sections[3 * (n_sections - 1) + 2] + 15) / 16 * 16;
+    if (!snap_layout_valid(lay, SNAP_L_HEAD + 3 * n_sections)) { set_err("lpcnet_batch_restore_device: bad section table"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_restore(b->sh[shard].dev, streams, m, d_records, meta, lay, hip_stream));
+}
+int lpcnet_batch_restore_device(LPCNetBatch *b, const int *streams, int m, const void *d_records, const int *meta, const int *sections, int n_sections,
+                                void *hip_stream)
+{
+    NEED_MODEL(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_restore_device");
+    return lpcnet_batch_restore_device_shard(b, 0, streams, m, d_records, meta, sections, n_sections, hip_stream);
+}
+/* Pairs between two batches (or two shards of one), shard pair by shard pair: the pairs from shard ks of `from` to shard kd of `to` are one gather,
+ * one transfer and one scatter (lpcn_batch_dev_copy_streams_to).  The indices are the batches' own and lie inside them. */
+static int copy_pairs_between(LPCNetBatch *from, const int *src, LPCNetBatch *to, const int *dst, int m)
+{
+    int first[LPCN_MAX_SHARDS * LPCN_MAX_SHARDS + 1] = {0}, fill[LPCN_MAX_SHARDS * LPCN_MAX_SHARDS], ls = 0, ld = 0, rc = 0;
+    const int K = to->n_shards, keys = from->n_shards * K;
+    int *psrc = (int *)malloc(2 * (size_t)(m + 1) * sizeof(int)), *pdst = psrc ? psrc + m + 1 : NULL;
+    if (!psrc) { set_err("copy_streams: out of memory"); return LPCN_E_ARG; }
+    for (int i = 0; i < m; i++) first[shard_of(from->at, from->n_shards, src[i], &ls) * K + shard_of(to->at, K, dst[i], &ld) + 1]++;
+    for (int k = 0; k < keys; k++) { first[k + 1] += first[k]; fill[k] = first[k]; }
+    for (int i = 0; i < m; i++) {
+        const int key = shard_of(from->at, from->n_shards, src[i], &ls) * K + shard_of(to->at, K, dst[i], &ld);
+        psrc[fill[key]] = ls; pdst[fill[key]++] = ld;
+    }
+    for (int key = 0; key < keys && !rc; key++)
+        if (first[key + 1] > first[key]) rc = lpcn_batch_dev_copy_streams_to(from->sh[key / K].dev, psrc + first[key], to->sh[key % K].dev, pdst + first[key], first[key + 1] - first[key]);
+    if (rc) take_engine_err();
+    free(psrc);
+    return rc;
+}
+int lpcnet_batch_copy_streams_to(LPCNetBatch *from, const int *src, LPCNetBatch *to, const int *dst, int m)
+{
+    NEED_MODEL(from);
+    NEED_MODEL(to);
+    if (from == to || m < 0 || m > to->n || (m && (!src || !dst))) { set_err("lpcnet_batch_copy_streams_to: two batches, and at most as many pairs as the destination has streams"); return LPCN_E_ARG; }
+    int lay[LPCN_SNAP_LAYOUT_MAX], need = 0, rc = 0;
+    unsigned char *mark = (unsigned char *)calloc((size_t)to->n, 1);
+    if (!mark) { set_err("lpcnet_batch_copy_streams_to: out of memory"); return LPCN_E_ARG; }
+    for (int i = 0; i < m && !rc; i++) {
+        if (src[i] < 0 || src[i] >= from->n || dst[i] < 0 || dst[i] >= to->n || mark[dst[i]]) rc = LPCN_E_ARG; else mark[dst[i]] = 1;
+    }
+    free(mark);
+    if (rc) { set_err("lpcnet_batch_copy_streams_to: every index must lie inside its batch and all destinations be distinct"); return rc; }
+    if ((rc = batch_layout(from, lay)) < 0) return rc;
+    for (int k = 0; k < to->n_shards && rc >= 0; k++) {  /* (every destination shard is asked before anything changes) */
+        rc = lpcn_batch_dev_snapshot_match(to->sh[k].dev, lay, 0);
+        if (rc > 0) need = 1;
+    }
+    if (rc < 0) { take_engine_err(); return rc; }
+    for (int k = 0; need && k < to->n_shards; k++)
+        if ((rc = lpcn_batch_dev_snapshot_enable(to->sh[k].dev, lay))) { take_engine_err(); return rc; }
+    return copy_pairs_between(from, src, to, dst, m);
 }
 
 int lpcnet_batch_set_streams_per_workgroup(LPCNetBatch *b, int spw) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_set_streams_per_wg(s->dev, spw)); }

@@ -60,6 +60,7 @@ struct LPCNetBatch {
     int n, n_shards;
     shard_span at[LPCN_MAX_SHARDS];   /* the streams of shard k ... */
     batch_shard sh[LPCN_MAX_SHARDS];  /* ... and where they live */
+    unsigned long long model_hash;    /* FNV-1a of the model blob (lpcnet_batch_load_model): travels in a snapshot's layout, for information */
 };
 
 #pragma GCC visibility push(hidden)

@@ -3,6 +3,7 @@
 #include "api_internal.h"
 #include "sample_variants.h"
 #include "encode_plan.h"
+#include "snapshot_plan.h"
 
 /* what the caller did to each stream's FEC ring before the step: fec_op [n] (may be NULL): 1 = a vector was added, 2 = a NULL skip, 3 = fec_clear,
  * 4 = two vectors */
@@ -93,6 +94,36 @@ int lpcnet_hip_encode_plan(int n, int active, int count, int analysis, int *out,
         }
     }
     return k;
+}
+
+/* stream snapshots without a device (include/lpcnet_batch.h; snapshot_plan.h): the layout of a configuration, a blob's header, the match rule */
+int lpcnet_hip_snapshot_layout(const int *config, int *out, int cap)
+{
+    int lay[LPCN_SNAP_LAYOUT_MAX];
+    if (!config || cap < 0 || (cap && !out) || snap_layout_build(config, 0, lay) < 0) { set_err("lpcnet_hip_snapshot_layout: bad configuration"); return LPCN_E_ARG; }
+    const int k = lay[SNAP_L_SECTIONS];
+    for (int i = 0; i < 3 * k && i < cap; i++) out[i] = lay[SNAP_L_HEAD + i];
+    if (cap > 3 * k) out[3 * k] = lay[SNAP_L_RECORD];
+    return k;
+}
+int lpcnet_hip_snapshot_info(const void *buf, size_t len, int *info, int cap)
+{
+    int lay[LPCN_SNAP_LAYOUT_MAX], m = 0, n = 0;
+    if (cap < 0 || (cap && !info)) { set_err("lpcnet_hip_snapshot_info: bad arguments"); return LPCN_E_ARG; }
+    if (snap_blob_parse(buf, len, &m, lay, NULL, NULL)) { set_err("lpcnet_hip_snapshot_info: not a snapshot blob (NULL, truncated, wrong magic or version, or lengths that do not add up)"); return LPCN_E_ARG; }
+    const int head[4] = {LPCN_SNAP_VERSION, m, lay[SNAP_L_RECORD], lay[SNAP_L_SECTIONS]};
+    for (int i = 0; i < 4 && n < cap; i++) info[n++] = head[i];
+    for (int i = SNAP_L_FLAVOUR; i < snap_layout_ints(lay) && n < cap; i++) info[n++] = lay[i];
+    return n;
+}
+int lpcnet_hip_snapshot_match(const int *config_snap, const int *config_batch, int enqueue_only, int *section)
+{
+    int snap[LPCN_SNAP_LAYOUT_MAX], mine[LPCN_SNAP_LAYOUT_MAX];
+    char msg[400];
+    if (!config_snap || !config_batch || snap_layout_build(config_snap, 0, snap) < 0 || snap_layout_build(config_batch, 0, mine) < 0) { set_err("lpcnet_hip_snapshot_match: bad configuration"); return LPCN_E_ARG; }
+    const int fit = snap_layout_match(snap, mine, enqueue_only, section, msg, sizeof(msg));
+    if (fit < 0) { set_err(msg); return LPCN_E_MODEL; }
+    return fit;
 }
 
 /* tools: how GRU-A's rows were dealt to the 8 waves of the sample kernel: out[0] = items per lane, then per wave

@@ -13,6 +13,7 @@
 #include "sample_kernel.hip.h"
 #include "kernel_params.h"
 #include "plc_plan.h"
+#include "snapshot_plan.h"
 
 // The calling thread's last error message (engine.hip; lpcn_last_error).  __thread: no dynamic initialiser, so every unit reaches it directly; a
 // thread_local declared extern goes through the C++ wrapper and its weak init hook, whose address test fails in a shared library.
@@ -348,10 +349,14 @@ struct lpcn_batch_dev {
     Event ev_last;
     hipStream_t last_stream = nullptr;
     bool pending = false;
-    DevBuf<int> d_pairs;               // lpcn_batch_dev_copy_streams (engine_roster.hip): the (src, dst) list of a call, [2 n] ...
+    DevBuf<int> d_pairs;               // lpcn_batch_dev_copy_streams (engine_roster.hip): the (src, dst) list of a call, or a snapshot's streams and meta rows, [11 n] ...
     PinBuf h_pairs;                    //   ... its pinned source ...
     Event ev_pairs;                    //   ... and "the previous call's list has left it"
     bool pairs_pending = false;
+    DevBuf<char> d_snap;               // stream snapshots (engine_snapshot.hip): the records of a host-form call or of a copy to another batch, grown to the largest ...
+    PinBuf h_snap;                     //   ... their pinned copy (host forms; the bounce between devices that cannot reach each other) ...
+    std::vector<int> snap_meta;        //   ... the meta rows of a copy to another batch ...
+    std::vector<unsigned char> snap_mark;         //   ... and one mark per stream for the check of a list
     std::unique_ptr<lpcn_plc_host> plc;           // packet-loss concealment (lpcn_batch_dev_plc_enable): host control state and device data
     std::unique_ptr<lpcn_dred_host> dred;         // DRED decoding (lpcn_batch_dev_dred_enable)
     std::unique_ptr<lpcn_denc_host> denc;         // DRED encoding (lpcn_batch_dev_dred_enc_enable)
@@ -359,6 +364,24 @@ struct lpcn_batch_dev {
     bool timing = false;
     float ms_sample = 0.f, ms_frame = 0.f;
 };
+
+// engine_roster.hip, engine_snapshot.hip: every per-stream array of the batch that is allocated now, as (base, bytes per stream).  `fn(buffer, elements per stream)`.
+template <typename F>
+void each_stream_array(lpcn_batch_dev *b, F fn)
+{
+    fn(b->d_state, (size_t)1);
+    fn(b->d_vq_mem, (size_t)LPCN_NB_BANDS);
+    if (b->d_an_state) fn(b->d_an_state, (size_t)1);
+    if (b->d_enc_vq_mem) fn(b->d_enc_vq_mem, (size_t)LPCN_NB_BANDS);
+    if (b->d_keep_lpc) { fn(b->d_keep_a, (size_t)LPCN_ROWS_A); fn(b->d_keep_b, (size_t)LPCN_ROWS_B); fn(b->d_keep_lpc, (size_t)LPCN_LPC_ORDER); }
+    if (lpcn_plc_host *p = b->plc.get()) {
+        fn(p->q, (size_t)LPCN_PLC_QUEUE); fn(p->feat, (size_t)LPCN_NB_FEAT); fn(p->net, 4 * (size_t)(plc_units(b->e, 0) + plc_units(b->e, 1))); fn(p->dc, (size_t)2);
+        fn(p->delta, (size_t)1); fn(p->fec, (size_t)LPCN_PLC_MAX_FEC * LPCN_NB_FEAT); fn(p->fbuf, (size_t)LPCN_PLC_FBUF * LPCN_NB_FEAT);
+        fn(p->lp, (size_t)LPCN_FRAME_SIZE); fn(p->burg, (size_t)2 * LPCN_NB_BANDS); fn(p->an, (size_t)LPCN_AN_NB_FEATURES);
+    }
+    if (lpcn_denc_host *p = b->denc.get()) fn(p->state, p->rec);
+}
+int stream_list_buffers(lpcn_batch_dev *b);      // engine_roster.hip: d_pairs / h_pairs / ev_pairs, on first use
 
 // What a launch works on and the batch does not own for good: a call on part of the batch, on other states or with another S passes another
 // shape; nothing overwrites the batch's settings to steer a launch.

@@ -272,8 +272,21 @@ int  lpcn_batch_dev_active(const lpcn_batch_dev *b);
  * of the pair list and one launch, enqueued on hip_stream (NULL = the engine's own; not a capturing one); the host halves (the PLC's control state,
  * the kept products' flag) are copied now.  The lists must be valid (api_roster.h: roster_check): this function checks the range only. */
 int  lpcn_batch_dev_copy_streams(lpcn_batch_dev *b, const int *src, const int *dst, int m, void *hip_stream);
-/* ... and across batches, through the host: synchronises both (an occasional operation) */
-int  lpcn_batch_dev_copy_stream_across(lpcn_batch_dev *from, int src, lpcn_batch_dev *to, int dst);
+/* Stream snapshots (include/lpcnet_batch.h: lpcnet_batch_snapshot; engine_snapshot.hip, snapshot_plan.h).  A layout is LPCNET_SNAP_LAYOUT_INTS ints at
+ * most; snapshot_layout writes the batch's present one (model hash 0: the shell knows it) and returns its ints.  snapshot / restore: one upload of the
+ * list and one launch, enqueued on hip_stream (NULL = the engine's own; not a capturing one); they check the list (inside the capacity, distinct), meta
+ * [m][LPCNET_SNAP_META] is a host array written / read before the call returns, d_records is 16-byte aligned.  restore refuses a layout that does not
+ * match with nothing allocated (LPCN_E_MODEL); snapshot_match is that check alone (0, 1 = fits once snapshot_enable has allocated the subsystems only
+ * the snapshot has, LPCN_E_MODEL).  The _host forms move records [.][record bytes] and meta rows of a blob: entry j of the list is record pos[j]
+ * (NULL: j); they synchronise.  copy_streams_to: gather, transfer, scatter between two batches, only enqueued. */
+int  lpcn_batch_dev_snapshot_layout(const lpcn_batch_dev *b, int *layout);
+int  lpcn_batch_dev_snapshot(lpcn_batch_dev *b, const int *streams, int m, void *d_records, int *meta, void *hip_stream);
+int  lpcn_batch_dev_restore(lpcn_batch_dev *b, const int *streams, int m, const void *d_records, const int *meta, const int *layout, void *hip_stream);
+int  lpcn_batch_dev_snapshot_match(const lpcn_batch_dev *b, const int *layout, int enqueue_only);
+int  lpcn_batch_dev_snapshot_enable(lpcn_batch_dev *b, const int *layout);
+int  lpcn_batch_dev_snapshot_host(lpcn_batch_dev *b, const int *streams, const int *pos, int m, void *records, int *meta);
+int  lpcn_batch_dev_restore_host(lpcn_batch_dev *b, const int *streams, const int *pos, int m, const void *records, const int *meta, const int *layout);
+int  lpcn_batch_dev_copy_streams_to(lpcn_batch_dev *from, const int *src, lpcn_batch_dev *to, const int *dst, int m);
 int  lpcn_batch_dev_get_decoder_vq_mem(lpcn_batch_dev *b, int stream, float *out18);
 int  lpcn_batch_dev_set_decoder_vq_mem(lpcn_batch_dev *b, int stream, const float *in18);
 int  lpcn_batch_dev_get_state(lpcn_batch_dev *b, int stream, lpcn_stream_state *host);

@@ -89,3 +89,32 @@ class StreamRoster:
                 self.batch.copy_streams([p[0] for p in pairs], [p[1] for p in pairs])
             self._push()
         return pairs, list(new_active)
+
+    def migrate(self, idents, other: "StreamRoster"):
+        """the streams `idents` move to `other`'s batch: they join `other` on its least-loaded shards (no reset: the records arrive whole), one
+        copy_streams_to carries them, then they leave this roster with the usual swap-remove.  Returns {id: slot in other}."""
+        idents = list(idents)
+        if len(set(idents)) != len(idents) or any(i not in self._slot for i in idents):
+            raise ValueError("migrate: ids must be distinct streams of this roster")
+        if any(i in other._slot for i in idents):
+            raise ValueError("migrate: an id is in the other roster already")
+        load = list(other.active)
+        dst = []
+        for _ in idents:                  # (planned before either book changes)
+            free = [k for k, (_, c) in enumerate(other.spans) if load[k] < c]
+            if not free:
+                raise RuntimeError("the other batch is full")
+            k = min(free, key=lambda k: (load[k], k))
+            dst.append(other.spans[k][0] + load[k])
+            load[k] += 1
+        src = [self._slot[i] for i in idents]
+        if self.batch is not None and other.batch is not None and idents:
+            self.batch.copy_streams_to(src, other.batch, dst)
+        for i, d in zip(idents, dst):
+            other._slot[i] = d
+            other._id[d] = i
+        other.active = load
+        if other.batch is not None:
+            other._push()
+        self.leave(idents)
+        return dict(zip(idents, dst))

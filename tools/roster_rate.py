@@ -16,6 +16,18 @@ Then lpcnet_batch_copy_streams on a batch of the same capacity with the packet-l
 rows of the copy table): 1, 64 and 1 024 pairs inside the one shard, HIP events around the enqueue-only call, median of 20 calls, with the
 bytes a pair moves.  One process; the tool stops at the first failure.  Run it under a time limit:
     timeout -k 10 600 python tools/roster_rate.py profiles/roster_rate.json
+
+    python tools/roster_rate.py --snapshot OUT.json [capacity] [--parent-lib PATH]       (profiles/snapshot_rate.json)
+
+Stream snapshots (lpcnet_batch_snapshot_device / _restore_device) and the copy across shards, for m = 1, 64, 1 024 and the capacity, on batches with
+the packet-loss concealment and the encoder enabled.  Every figure is host wall time from the call to the end of the work (the call, then a wait for
+the stream or the batch), the median of a few repetitions after two that do not count:
+  a  snapshot_device + restore_device of m streams of one batch on a caller's stream, with the HIP-event time between the two records beside it
+     (gb_per_s: the records' bytes, once gathered and once scattered, over that time);
+  b  lpcnet_batch_copy_streams of m pairs that all cross the two shards of a batch of 2 x capacity streams on one device, then lpcnet_batch_sync;
+  c  the same call on the library of the parent commit (--parent-lib: built beside this one from a checkout of that commit), the two
+     alternating call by call so that both see the same clocks.  Without --parent-lib the series is left out and the file says so.
+The file also holds the record's bytes and the spread (max - min) / median of each series' repetitions, the margin a comparison has to beat.
 """
 import json
 import os
@@ -53,7 +65,122 @@ def side(blocks):
                 block_device_ms_medians=[float(np.median(blk[0])) for blk in blocks], steps=len(dev))
 
 
+class ParentLib:
+    """the few calls series c needs, on another build of the library (ctypes, beside the one lpcnet_amd.api has loaded)"""
+
+    def __init__(self, path, n, devices, blob, options):
+        import ctypes as C
+        self.C, self.L = C, C.CDLL(path)
+        vp = C.c_void_p
+        self.L.lpcnet_batch_create_sharded.restype = vp
+        self.L.lpcnet_batch_create_sharded.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int]
+        self.L.lpcnet_batch_load_model.argtypes = [vp, C.c_char_p, C.c_int]
+        self.L.lpcnet_batch_plc_enable.argtypes = [vp, C.c_int]
+        self.L.lpcnet_batch_encoder_enable.argtypes = [vp, C.c_int]
+        self.L.lpcnet_batch_copy_streams.argtypes = [vp, vp, vp, C.c_int, vp]
+        self.L.lpcnet_batch_sync.argtypes = [vp]
+        self.L.lpcnet_batch_destroy.argtypes = [vp]
+        self.L.lpcnet_batch_last_error.restype = C.c_char_p
+        self.p = self.L.lpcnet_batch_create_sharded(n, (C.c_int * len(devices))(*devices), len(devices))
+        self.chk(0 if self.p else -1)
+        self.chk(self.L.lpcnet_batch_load_model(self.p, blob, len(blob)))
+        self.chk(self.L.lpcnet_batch_plc_enable(self.p, options))
+        self.chk(self.L.lpcnet_batch_encoder_enable(self.p, 1))
+
+    def chk(self, rc):
+        if rc:
+            raise RuntimeError("parent library: %d %s" % (rc, self.L.lpcnet_batch_last_error().decode()))
+
+    def copy_streams(self, src, dst):
+        self.chk(self.L.lpcnet_batch_copy_streams(self.p, src.ctypes.data, dst.ctypes.data, int(src.size), None))
+
+    def sync(self):
+        self.chk(self.L.lpcnet_batch_sync(self.p))
+
+    def close(self):
+        self.L.lpcnet_batch_destroy(self.p)
+
+
+def series(ms):
+    return dict(wall_ms_median=float(np.median(ms)), wall_ms_min=float(np.min(ms)), wall_ms_max=float(np.max(ms)), calls=len(ms),
+                spread=float((np.max(ms) - np.min(ms)) / np.median(ms)))
+
+
+def snapshot_main(argv):
+    import torch
+    import plc_synth
+    from lpcnet_amd import api, synth
+    parent = None
+    if "--parent-lib" in argv:
+        i = argv.index("--parent-lib")
+        parent = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    out_path = argv[0]
+    cap = int(argv[1]) if len(argv) > 1 else 8192
+    s = torch.cuda.Stream()
+    blob = synth.blob_bytes(plc_synth.make_model_with_plc())
+    opt = api.PLC_CODEC | api.PLC_DC_FILTER
+    one = api.LPCNetBatch(cap, blob)
+    one.plc_enable(opt)
+    one.encoder_enable(1)
+    lay = one.snapshot_layout()
+    rb = lay["record_bytes"]
+    two = api.LPCNetBatch(2 * cap, blob, devices=[0, 0])
+    two.plc_enable(opt)
+    two.encoder_enable(1)
+    old = ParentLib(parent, 2 * cap, [0, 0], blob, opt) if parent else None
+    rec = torch.zeros(cap * rb, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    result = dict(capacity=cap, build=api.build_info(), device=torch.cuda.get_device_name(0), record_bytes=rb, sections=len(lay["sections"]),
+                  parent_library=bool(parent), a_snapshot_restore=[], b_copy_across_shards=[], c_copy_across_shards_parent=[])
+    if not parent:
+        result["c_note"] = "no --parent-lib given: series c was not measured"
+
+    def timed(call, wait):
+        w0 = time.perf_counter()
+        call()
+        wait()
+        return (time.perf_counter() - w0) * 1e3
+
+    for m in sorted({1, min(64, cap), min(1024, cap), cap}):
+        streams = np.arange(m, dtype=np.int32)
+        src, dst = np.arange(m, dtype=np.int32), np.arange(cap, cap + m, dtype=np.int32)      # shard 0 -> shard 1
+        reps = 9 if m <= 1024 else 5
+        wa, da, wb, wc = [], [], [], []
+        for r in range(reps + 2):
+            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+            def both():
+                a.record(s)
+                meta = one.snapshot_device(streams, rec.data_ptr(), s.cuda_stream)
+                one.restore_device(streams, rec.data_ptr(), meta, lay["sections"], s.cuda_stream)
+                e.record(s)
+            wa.append(timed(both, e.synchronize))
+            da.append(a.elapsed_time(e))
+            wb.append(timed(lambda: two.copy_streams(src, dst), two.sync))
+            if old:
+                wc.append(timed(lambda: old.copy_streams(src, dst), old.sync))
+        ra = dict(series(wa[2:]), m=m, device_ms_median=float(np.median(da[2:])), gb_per_s=2e-6 * rb * m / float(np.median(da[2:])))
+        rbb = dict(series(wb[2:]), m=m)
+        print(json.dumps(dict(a=ra, b=rbb)), flush=True)
+        result["a_snapshot_restore"].append(ra)
+        result["b_copy_across_shards"].append(rbb)
+        if old:
+            rc = dict(series(wc[2:]), m=m, ratio_b_over_c=rbb["wall_ms_median"] / float(np.median(wc[2:])))
+            print(json.dumps(dict(c=rc)), flush=True)
+            result["c_copy_across_shards_parent"].append(rc)
+    one.close(); two.close()
+    if old:
+        old.close()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
 def main():
+    if "--snapshot" in sys.argv:
+        return snapshot_main([x for x in sys.argv[1:] if x != "--snapshot"])
     import torch
     import plc_synth
     from lpcnet_amd import api, synth
