@@ -296,7 +296,17 @@ LPCNET_EXPORT int lpcnet_hip_plc_model_info(const unsigned char *data, int len, 
  *   shard's active prefix return LPCNET_HIP_E_ARG with nothing written; the rows of inactive streams are untouched.  The _shard forms cover
  *   that shard's streams, in arrays and packing.
  * No per-stream state: a call keeps nothing between calls (decode_all semantics; the incremental init_states / decode_qframe pair is not
- *   exposed), so lpcnet_batch_copy_streams, the roster and the state snapshots are unaffected.  lpcnet_batch_set_fast does not change this kernel.
+ *   exposed), so lpcnet_batch_copy_streams, the roster and the state snapshots are unaffected.  lpcnet_batch_set_fast does not change this kernel; its
+ *   own switch is dred_set_fast.
+ * dred_set_fast(mode) selects the arithmetic of the float decoder, per batch, off by default: 0 = PARITY, the bits above; 1 = FAST with the engine's
+ *   choice of tile; 16 or 32 = FAST pinned to a tile of that many streams per workgroup (the tiles that are built; for tests and tools).  FAST is the arithmetic
+ *   of the reference's AVX2+FMA float build: every sum one fma chain from its bias in ascending input order (sgemv_accum16 and sparse_sgemv_accum8x4
+ *   of src/vec_avx.h), computed on the fp32 matrix pipe with the streams of a workgroup as columns; exp / rcp based activations.  Its output
+ *   deviates from PARITY's no more than that build's does on the same inputs, and a stream's bits do not depend on the tile, on the streams that
+ *   share it, on their counts, on the active prefix or on the shards.  Every decode call follows the switch; signatures, layouts, refusals and
+ *   the absence of per-stream state are the same.  Any other mode returns LPCNET_HIP_E_ARG; on an int8 decoder a non-zero mode returns
+ *   LPCNET_HIP_E_MODEL (the int8 decoder has no FAST form yet) and nothing changes.  dred_get_fast: the mode that is set.  dred_set_form /
+ *   dred_get_form describe the PARITY forms only.
  * dred_set_form pins the streams one workgroup carries (1, 2, 4, 8; 0 = the engine's table) for tests and tools: the output bits are the same in
  *   every form.  dred_get_form: what a launch over n_streams streams runs with.
  * dred_info: info[3] = {max_latents, latent dimension, state dimension}: the row lengths of the arrays above. */
@@ -314,6 +324,8 @@ LPCNET_EXPORT int lpcnet_batch_dred_info(const LPCNetBatch *b, int *info);
 LPCNET_EXPORT int lpcnet_batch_dred_flavour(const LPCNetBatch *b);     /* 0: the float decoder runs, 1: the int8 one; LPCNET_HIP_E_MODEL before dred_enable */
 LPCNET_EXPORT int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams);
+LPCNET_EXPORT int lpcnet_batch_dred_set_fast(LPCNetBatch *b, int mode);
+LPCNET_EXPORT int lpcnet_batch_dred_get_fast(const LPCNetBatch *b);
 /* a blob's DRED decoder as the loader sees it, no device: info[12] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
  * inconsistent), servable (dred_enable accepts the blob: the arrays are in the LPCNet model's own flavour), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.  Returns 0,
  * LPCNET_HIP_E_ARG without `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */

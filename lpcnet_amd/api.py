@@ -298,6 +298,8 @@ def load_library():
     L.lpcnet_hip_encode_plan.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int]
     L.lpcnet_batch_dred_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_get_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_set_fast.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_get_fast.argtypes = [vp]
     L.lpcnet_hip_dred_enc_model_info.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     L.lpcnet_batch_dred_enc_enable.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_enc_info.argtypes = [vp, C.POINTER(C.c_int)]
@@ -819,6 +821,20 @@ class LPCNetBatch:
         if rc < 0:
             self._chk(rc, "dred_form")
         return rc
+
+    @property
+    def dred_fast(self) -> int:
+        """the DRED decoder's arithmetic: 0 PARITY (the default: the bits of the reference's generic-C build), 1 FAST at the engine's tile, 16 or 32 FAST
+        pinned to that many streams per workgroup (the same bits in either).  FAST is the fma-chain arithmetic of the reference's AVX2 float build on the fp32 matrix pipe; every
+        dred_decode* call follows the switch.  Float decoders only"""
+        rc = self.L.lpcnet_batch_dred_get_fast(self.p)
+        if rc < 0:
+            self._chk(rc, "dred_fast")
+        return rc
+
+    @dred_fast.setter
+    def dred_fast(self, mode):
+        self._chk(self.L.lpcnet_batch_dred_set_fast(self.p, int(mode)), "dred_fast")
 
     def dred_decode(self, state: np.ndarray, latents: np.ndarray, count, features: np.ndarray | None = None) -> np.ndarray:
         """state (n, state_dim), latents (n, max_latents, latent_dim) float32, count [n] -> features (n, 4 * max_latents, 20) float32: stream s's rows

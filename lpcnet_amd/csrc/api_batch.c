@@ -378,6 +378,26 @@ int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams)
     if (rc < 0) take_engine_err();
     return rc;
 }
+/* all shards or none: a shard that refuses puts the earlier ones back, so that a sharded batch never decodes in two arithmetics */
+int lpcnet_batch_dred_set_fast(LPCNetBatch *b, int mode)
+{
+    NEED_DRED_ON(b);
+    const int before = lpcn_batch_dev_dred_get_fast(b->sh[0].dev);
+    for (int k = 0; k < b->n_shards; k++) {
+        const int rc = lpcn_batch_dev_dred_set_fast(b->sh[k].dev, mode);
+        if (rc) {
+            take_engine_err();
+            while (k-- > 0) lpcn_batch_dev_dred_set_fast(b->sh[k].dev, before);
+            return rc;
+        }
+    }
+    return 0;
+}
+int lpcnet_batch_dred_get_fast(const LPCNetBatch *b)
+{
+    NEED_DRED_ON(b);
+    FWD(lpcn_batch_dev_dred_get_fast(b->sh[0].dev));
+}
 typedef struct { LPCNetBatch *b; const float *state, *latents; const int *count; float *features; int max_latents, latent_dim, state_dim; } dred_args;
 static int dred_shard(void *args, int k)
 {

@@ -159,6 +159,12 @@ struct DredHostModel {
     lpcn_dred_model m{};
     LayerArena a;
 };
+// What the FAST flavour's image is packed from (dred_fast_pack.h): the three GRUs' sparse input matrices and their index streams, nothing else
+struct DredFastHost {
+    std::vector<float> w[3];
+    std::vector<int> idx[3];
+    int n_in[3] = {0, 0, 0}, n[3] = {0, 0, 0};
+};
 struct DredEncHostModel {
     lpcn_dred_enc_model m{};
     LayerArena a;
@@ -191,6 +197,8 @@ struct lpcn_engine {
     int dred_present = 0;          //   ... lpcn_dred_model.present of the blob
     bool dred_servable = false;    //   ... and whether it is in the blob's own flavour (lpcn_dred_servable)
     std::unique_ptr<DredHostModel> dred_host;     //   ... not uploaded yet
+    std::unique_ptr<DredFastHost> dred_fast_host;   //   ... a float decoder's GRU input matrices, kept from the upload until the FAST image is packed from them
+    const lpcn::DredFastImage *d_dred_fast = nullptr;   //   ... the FAST flavour's image of the GRU input matrices, once a batch has asked for FAST
     lpcn::DredEncNet denc{};       // DRED encoder (engine_dred_enc.hip), the same: the block of either flavour, its device copy, ...
     lpcn::DredEncNetQ dencq{};
     const lpcn::DredEncNet *d_denc = nullptr;
@@ -274,6 +282,7 @@ struct lpcn_plc_host {
 struct lpcn_dred_host {
     int max_latents = 0, cus = 0;                   // (cus: the device's compute units, for the form table)
     int form = 0;                                   // streams per workgroup pinned by lpcn_batch_dev_dred_set_form (0: the table's choice)
+    int fast = 0;                                   // lpcn_batch_dev_dred_set_fast: 0 PARITY, 1 FAST at the engine's tile, else FAST at that tile
     DevBuf<int> d_rec;                              // a call's per-stream records (dred_kernels.hip.h: DRED_REC) ...
     PinBuf h_rec;                                   // ... their pinned source ...
     Event ev_rec;                                   // ... and "the previous call's have left it"

@@ -3,6 +3,8 @@
 // know about it.
 #include "engine_core.h"
 #include "dred_kernels.hip.h"
+#include "dred_fast_kernels.hip.h"
+#include "dred_fast_pack.h"
 #include "lpcnet_tables_gen.h"
 #include <mutex>
 
@@ -52,6 +54,16 @@ static int dred_upload_net(lpcn_engine *e, lpcn::DredNetT<W> &net, const lpcn::D
         (rc = upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
     if ((rc = upload<lpcn::DredNetT<W>>(e, d_net, &n, 1))) return rc;
     net = n;
+    if constexpr (std::is_same<W, float>::value) {       // (what the FAST image is packed from outlives the host copy: dred_fast_upload)
+        auto f = std::make_unique<DredFastHost>();
+        for (int g = 0; g < 3; ++g) {
+            const lpcn_gru_layer &G = d.gru[g];
+            f->w[g].assign(G.w, G.w + 32 * (size_t)G.nb);
+            f->idx[g].assign(G.idx, G.idx + 3 * G.n / 8 + G.nb);
+            f->n_in[g] = G.n_in; f->n[g] = G.n;
+        }
+        e->dred_fast_host = std::move(f);
+    }
     e->dred_host.reset();
     return 0;
 }
@@ -128,6 +140,65 @@ extern "C" int lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S)
     return 0;
 }
 
+// ---- the FAST flavour (dred_fast_kernels.hip.h): the float decoder in the arithmetic of the reference's AVX2+FMA build, the streams of a workgroup on
+// the columns of an fp32 MFMA.  Its image of the GRUs' sparse input matrices is packed on the host (dred_fast_pack.h) and uploaded when a batch first
+// asks for FAST; the host copy of those matrices goes then.  The other arrays are the PARITY block's.
+static int dred_fast_upload(lpcn_engine *e)
+{
+    if (e->d_dred_fast) return 0;
+    if (!e->dred_fast_host) { snprintf(g_err, sizeof(g_err), "DRED FAST: the decoder's host arrays are gone"); return LPCN_E_MODEL; }
+    lpcn::DredFastImage im{};
+    for (int g = 0; g < 3; ++g) {
+        const DredFastHost &F = *e->dred_fast_host;
+        lpcn_dred_fast_gru pk;
+        const int prc = lpcn_dred_fast_pack(F.w[g].data(), F.idx[g].data(), F.n_in[g], F.n[g], &pk);
+        if (prc) {
+            snprintf(g_err, sizeof(g_err), prc == -1 ? "DRED FAST: out of memory" : "DRED FAST: GRU %d's block lists are not ascending: no FAST image", g);
+            return prc == -1 ? LPCN_E_HIP : LPCN_E_MODEL;
+        }
+        const size_t blocks = (size_t)pk.start[3 * pk.tiles];
+        int rc = upload<int>(e, &im.gru[g].start, pk.start, 3 * (size_t)pk.tiles + 1);
+        if (!rc) rc = upload<int>(e, &im.gru[g].pos, pk.pos, blocks);
+        if (!rc) rc = upload<float>(e, &im.gru[g].w, pk.w, blocks * 128);
+        lpcn_dred_fast_release(&pk);
+        if (rc) return rc;
+    }
+    int rc = upload<lpcn::DredFastImage>(e, &e->d_dred_fast, &im, 1);
+    if (rc) return rc;
+    e->dred_fast_host.reset();
+    return 0;
+}
+// The tile a FAST launch over n streams runs with: the pinned one, or the engine's choice (mode 1).  The rule is read off
+// profiles/dred_fast_rate.json (one MI355X, width 256, 25 latents): a tile's chain takes the same time however many tiles run in
+// one round -- T = 16: 4.68 / 4.28 ms for 16 / 128 tiles and 8.62 ms for 512 (two rounds); T = 32: 8.31 / 7.79 / 7.54 ms for 8 / 64 / 256 tiles;
+// PARITY's table form 6.66 / 7.87 / 30.90 ms at those 256 / 2 048 / 8 192 streams -- so T = 16 while its tiles fit the CUs in one round, 32 beyond.
+// The bits of a stream are the same in both
+static int dred_fast_tile(const lpcn_dred_host *p, int n)
+{
+    if (p->fast != 1) return p->fast;
+    return (n + 15) / 16 <= p->cus ? 16 : 32;
+}
+extern "C" int lpcn_batch_dev_dred_get_fast(const lpcn_batch_dev *b)
+{
+    NEED_DRED(b);
+    return b->dred->fast;
+}
+extern "C" int lpcn_batch_dev_dred_set_fast(lpcn_batch_dev *b, int mode)
+{
+    NEED_DRED(b);
+    lpcn_engine *e = b->e;
+    if (mode != 0 && mode != 1 && mode != 16 && mode != 32) { snprintf(g_err, sizeof(g_err), "DRED FAST: 0 = off, 1 = the engine's tile, 16 or 32 = that many streams per workgroup (the tiles that are built)"); return LPCN_E_ARG; }
+    if (e->is_int8 && mode) { snprintf(g_err, sizeof(g_err), "DRED FAST: the int8 decoder has no FAST form yet"); return LPCN_E_MODEL; }
+    if (mode) {
+        if ((size_t)lpcn::dred_fast_lds_floats(e->dred, mode == 16 ? 16 : 32) * sizeof(float) > 160 * 1024 - 1024) { snprintf(g_err, sizeof(g_err), "DRED FAST: the decoder's tile does not fit the LDS"); return LPCN_E_MODEL; }
+        DeviceGuard guard(e->device);
+        int rc = wait_all(b);
+        if (rc || (rc = dred_fast_upload(e))) return rc;
+    }
+    b->dred->fast = mode;
+    return 0;
+}
+
 // count in 0 .. max_latents and zero beyond the active prefix; the packed form's first / take inside the decoded rows
 extern "C" int lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *count, const int *first, const int *take, long long *rows)
 {
@@ -169,6 +240,28 @@ static int dred_launch_form(const lpcn::DredNetT<W> *P, int grid, int lds, hipSt
     return 0;
 }
 
+// the FAST launch: T streams per workgroup, U steps of weights in flight per wave (the smaller tile's accumulators leave registers for twice as many)
+template <int T, int U>
+static int dred_fast_launch(const lpcn_engine *e, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state, const float *d_latents, float *d_out)
+{
+    static std::mutex mu;
+    static int limit[64];
+    const auto kernel = lpcn::dred_fast_kernel<T, U>;
+    const int lds = lpcn::dred_fast_lds_floats(e->dred, T) * (int)sizeof(float);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (dev < 0 || dev >= 64 || limit[dev] < lds) {
+            HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            if (dev >= 0 && dev < 64) limit[dev] = lds;
+        }
+    }
+    hipLaunchKernelGGL(kernel, dim3((n + T - 1) / T), dim3(lpcn::DRED_FAST_THREADS), lds, st, e->d_dred, e->d_dred_fast, n, max_latents, d_rec, d_state, d_latents, d_out);
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED decode: kernel launch failed"); return LPCN_E_HIP; }
+    return 0;
+}
+
 template <typename W>
 static int dred_launch(const lpcn::DredNetT<W> *P, int S, int grid, int lds, hipStream_t st, int n, int max_latents, const int *d_rec, const float *d_state,
                        const float *d_latents, float *d_out)
@@ -200,14 +293,19 @@ static int dred_enqueue(lpcn_batch_dev *b, const float *d_state, const float *d_
         q[0] = count[s]; q[1] = first ? first[s] : -1; q[2] = first ? take[s] : 0; q[3] = row;
         if (first) row += take[s];
     }
-    const int S = lpcn_batch_dev_dred_form(b, b->active);
-    const int grid = (b->active + S - 1) / S, lds = dred_lds_bytes(b->e, S);
     if ((rc = order_begin(b, st))) return rc;
     HIP_TRY(hipMemcpyAsync(p->d_rec, h, sizeof(int) * lpcn::DRED_REC * (size_t)b->active, hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(p->ev_rec, st));
     p->rec_pending = true;
-    rc = b->e->is_int8 ? dred_launch(b->e->d_dredq, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out)
-                       : dred_launch(b->e->d_dred, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out);
+    if (p->fast) {
+        rc = dred_fast_tile(p, b->active) == 16 ? dred_fast_launch<16, 16>(b->e, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out)
+                                                : dred_fast_launch<32, 8>(b->e, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out);
+    } else {
+        const int S = lpcn_batch_dev_dred_form(b, b->active);
+        const int grid = (b->active + S - 1) / S, lds = dred_lds_bytes(b->e, S);
+        rc = b->e->is_int8 ? dred_launch(b->e->d_dredq, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out)
+                           : dred_launch(b->e->d_dred, S, grid, lds, st, b->active, p->max_latents, p->d_rec, d_state, d_latents, d_out);
+    }
     if (rc) return rc;
     return order_end(b, st);
 }

@@ -95,6 +95,10 @@ struct DredNetT {
 };
 using DredNet = DredNetT<float>;
 using DredNetQ = DredNetT<int>;
+// the FAST decoder's image of the three GRUs' sparse input matrices (dred_fast_kernel; dred_fast_pack.h): per (unit tile of 32, gate) the union of the
+// tile's row groups' blocks.  start [3 tiles + 1], pos [blocks], w [blocks][4][32].  A device-resident block beside the DredNet, which FAST reads too
+struct DredFastGru { const int *start, *pos; const float *w; };
+struct DredFastImage { DredFastGru gru[3]; };
 
 // the DRED encoder on the device (rdovae_enc_kernel), walked like the decoder's block: the eight layers of a double frame, gdense1 (from the buffer's
 // start to the cells behind it), then the two layers that read no DredStep cell range: bits_dense over the window and gdense2, straight to the outputs.

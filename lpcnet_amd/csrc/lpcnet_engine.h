@@ -451,6 +451,8 @@ int  lpcn_batch_dev_dred_dims(const lpcn_batch_dev *b, int *latent_dim, int *sta
 int  lpcn_batch_dev_dred_flavour(const lpcn_batch_dev *b);    /* 0 float decoder, 1 int8; LPCN_E_MODEL before dred_enable */
 int  lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S);  /* streams per workgroup: 1, 2, 4, 8; 0 = the table's choice */
 int  lpcn_batch_dev_dred_form(const lpcn_batch_dev *b, int n);/* what a launch over n streams runs with */
+int  lpcn_batch_dev_dred_set_fast(lpcn_batch_dev *b, int mode);   /* 0 PARITY, 1 FAST at the engine's tile, 16 / 32 FAST at that tile; LPCN_E_MODEL on an int8 decoder */
+int  lpcn_batch_dev_dred_get_fast(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_dred_check(const lpcn_batch_dev *b, const int *count, const int *first, const int *take, long long *rows);   /* the argument checks alone; *rows = sum(take) */
 int  lpcn_batch_dev_dred_decode(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, float *d_features, void *hip_stream);
 int  lpcn_batch_dev_dred_decode_packed(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take,

@@ -3,6 +3,7 @@
 
     python tools/dred_rate.py OUT.json [latents]       (profiles/dred_rate.json when run for the record)
     python tools/dred_rate.py --int8 OUT.json [latents]       (profiles/dred_i8_rate.json: the int8 decoder beside the float one)
+    python tools/dred_rate.py --fast OUT.json [latents]       (profiles/dred_fast_rate.json: the FAST flavour beside PARITY)
 
 For 256, 2 048 and 8 192 streams, 25 latents each (one second of redundancy) at the exported width of 256: the time of one call (HIP events
 around the enqueue-only device-pointer call, on a caller's stream) with the streams per workgroup pinned to 1, 2, 4, 8 and left to the engine's
@@ -15,7 +16,10 @@ the first failure.
 --int8: the same blob widths as an int8 (DOT_PROD) blob (tests/tools/dred_i8_model.py) on a second batch beside the float one; flavours and forms
 alternate call by call in the one process, so that int8 and float see the same clocks.  `streams` holds the int8 rows, `float_streams` the float
 rows of the same session, `int8_over_float` the ratio of the medians per stream count at the table's form and at each flavour's best pinned form;
-the CPU yardstick is the reference's AVX2 int8 build (liblpcnet_ref_ai.so).  Run it under a time limit:
+the CPU yardstick is the reference's AVX2 int8 build (liblpcnet_ref_ai.so).
+--fast (profiles/dred_fast_rate.json): PARITY at the table's form beside the FAST flavour (lpcnet_batch_dred_set_fast) pinned to every tile that is
+built and at the engine's choice (mode 1), alternating call by call on one batch; the same protocol and stream counts.  FAST's output is compared with
+the pinned tile's bit for bit and its largest deviation from PARITY's is recorded.  Run it under a time limit:
     timeout -k 10 600 python tools/dred_rate.py profiles/dred_rate.json
 """
 import json
@@ -138,8 +142,74 @@ def measure(out_path, n_latents=25, int8=False):
         fh.write("\n")
 
 
+FAST_TILES = (16, 32)           # every tile that is built (lpcnet_batch_dred_set_fast)
+
+
+def measure_fast(out_path, n_latents=25):
+    import torch
+    import dred_model as dm
+    from lpcnet_amd import api
+    dev = torch.device("cuda:0")
+    blob = dm.set_blob("w256")
+    info = api.dred_model_info(blob)
+    base_state, base_lat = dm.inputs(info["latent_dim"], 64, n_latents, seed=0x2A7E)
+    modes = [("parity", 0)] + [("fast_T%d" % t, t) for t in FAST_TILES] + [("fast", 1)]
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), widths=info["widths"], latent_dim=info["latent_dim"], latents=n_latents,
+                  timed_calls=TIMED, warmup_calls=WARMUP, note="PARITY (table form) and FAST alternate call by call in one process; ms of one decode call by HIP events",
+                  streams=[])
+    s = torch.cuda.Stream()
+    for n in STREAMS:
+        b = api.LPCNetBatch(n, blob)
+        b.dred_enable(n_latents)
+        reps = n // 64 + 1
+        d_state = torch.from_numpy(np.ascontiguousarray(np.tile(base_state, (reps, 1))[:n])).to(dev)
+        d_lat = torch.from_numpy(np.ascontiguousarray(np.tile(base_lat, (reps, 1, 1))[:n])).to(dev)
+        d_out = torch.zeros((n, 4 * n_latents, 20), dtype=torch.float32, device=dev)
+        count = np.full(n, n_latents, np.int32)
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _ in modes}
+        first = {}
+        with torch.cuda.stream(s):
+            for k in range(WARMUP + TIMED):
+                for name, mode in modes:
+                    b.dred_fast = mode
+                    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(s)
+                    b.dred_decode_device(d_state.data_ptr(), d_lat.data_ptr(), count, d_out.data_ptr(), hip_stream=s.cuda_stream)
+                    e.record(s)
+                    e.synchronize()
+                    if k >= WARMUP:
+                        ms[name].append(a.elapsed_time(e))
+                    elif k == 0:
+                        first[name] = d_out.clone()
+        table_form = b.dred_form()
+        b.dred_fast = 0
+        b.close()
+        for name, mode in modes[2:]:
+            if not torch.equal(first[name].view(torch.int32), first[modes[1][0]].view(torch.int32)):
+                raise SystemExit("%s differs from %s at %d streams" % (name, modes[1][0], n))
+        row = dict(streams=n, parity_table_form=table_form, max_abs_fast_minus_parity=float((first["fast"] - first["parity"]).abs().max()), modes=[])
+        for name, mode in modes:
+            v = np.array(ms[name])
+            row["modes"].append(dict(mode=name, set_fast=mode, median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()),
+                                     p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)),
+                                     us_per_stream_latent=float(1e3 * np.median(v) / (n * n_latents))))
+        med = {r["mode"]: r["median_ms"] for r in row["modes"]}
+        row["spread_ms"] = max(r["p90_ms"] - r["p10_ms"] for r in row["modes"])
+        row["fast_gain_over_parity_ms"] = med["parity"] - med["fast"]
+        row["fast_beats_parity_by_more_than_the_spread"] = bool(row["fast_gain_over_parity_ms"] > row["spread_ms"])
+        print(json.dumps(row), flush=True)
+        result["streams"].append(row)
+    with open(out_path, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if not args:
         raise SystemExit(__doc__)
-    measure(args[0], int(args[1]) if len(args) > 1 else 25, int8="--int8" in sys.argv[1:])
+    if "--fast" in sys.argv[1:]:
+        measure_fast(args[0], int(args[1]) if len(args) > 1 else 25)
+    else:
+        measure(args[0], int(args[1]) if len(args) > 1 else 25, int8="--int8" in sys.argv[1:])
