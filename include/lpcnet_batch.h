@@ -360,7 +360,18 @@ LPCNET_EXPORT int lpcnet_hip_dred_model_info(const unsigned char *data, int len,
  * Per-stream state: the three GRU states and the conv memory of (K - 1) x sum-of-the-widths floats.  lpcnet_batch_reset zeroes it for the streams it
  *   names, lpcnet_batch_copy_streams carries it.  dred_enc_get_state / _set_state move one stream's state in the reference's member order
  *   (RDOVAEEncState): dense2_state, dense4_state, dense6_state, then bits_dense_state, the oldest tap first -- info[6] floats.
- *   lpcnet_batch_set_fast does not change this kernel.
+ *   lpcnet_batch_set_fast and dred_set_fast do not change this kernel; its own switch is dred_enc_set_fast.
+ * dred_enc_set_fast(mode) selects the arithmetic of the float encoder, per batch, off by default: 0 = PARITY, the bits above; 1 = FAST with the
+ *   engine's choice of tile; 16 or 32 = FAST pinned to a tile of that many streams per workgroup (the tiles that are built; for tests and tools).
+ *   FAST is the arithmetic dred_set_fast gives the decoder: every sum one fma chain from its bias in ascending input order on the fp32 matrix pipe
+ *   -- bits_dense one chain over its whole window, the oldest tap first -- and exp / rcp based activations.  Its outputs and states deviate from
+ *   PARITY's no more than the reference's AVX2+FMA float build's do on the same inputs, and a stream's bits do not depend on the tile, on the streams
+ *   that share it, on their counts, on the active prefix, on the shards or on how a run of double frames is cut into calls.  Every encode call
+ *   follows the switch; signatures, layouts, refusals and the per-stream state record are the same, so a batch may change the mode between calls,
+ *   and reset, copy_streams, the snapshots and dred_enc_get_state / _set_state work as before.  Any other mode returns LPCNET_HIP_E_ARG; on an int8
+ *   encoder a non-zero mode returns LPCNET_HIP_E_MODEL (the int8 encoder has no FAST form yet), and so does a tile whose buffers do not fit a
+ *   workgroup (mode 1 takes 16 streams where 32 do not fit); nothing changes then.  dred_enc_get_fast: the mode that is set.  dred_enc_set_form /
+ *   dred_enc_get_form describe the PARITY forms only.
  * dred_enc_set_form pins the streams one workgroup carries (1, 2, 4, 8; 0 = the engine's table) for tests and tools -- a form whose buffers do not
  *   fit a workgroup's LDS returns LPCNET_HIP_E_ARG -- and the output bits are the same in every form.  dred_enc_get_form: what a launch over n_streams
  *   streams runs with.
@@ -377,6 +388,8 @@ LPCNET_EXPORT int lpcnet_batch_dred_enc_get_state(LPCNetBatch *b, int stream, fl
 LPCNET_EXPORT int lpcnet_batch_dred_enc_set_state(LPCNetBatch *b, int stream, const float *in);
 LPCNET_EXPORT int lpcnet_batch_dred_enc_set_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_set_fast(LPCNetBatch *b, int mode);
+LPCNET_EXPORT int lpcnet_batch_dred_enc_get_fast(const LPCNetBatch *b);
 /* a blob's DRED encoder as the loader sees it, no device: info[15] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or inconsistent),
  * servable (dred_enc_enable accepts the blob: the arrays are in the LPCNet model's own flavour), latent dimension, state dimension, K, width of gdense1, floats of one stream's state, the widths of
  * enc_dense1 .. enc_dense8}.  Returns like lpcnet_hip_dred_model_info */

@@ -311,6 +311,8 @@ def load_library():
     L.lpcnet_batch_dred_enc_set_state.argtypes = [vp, C.c_int, _f32p]
     L.lpcnet_batch_dred_enc_set_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_dred_enc_get_form.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_enc_set_fast.argtypes = [vp, C.c_int]
+    L.lpcnet_batch_dred_enc_get_fast.argtypes = [vp]
     L.lpcnet_batch_encode.argtypes = [vp, _i16p, _u8p, C.c_int]
     L.lpcnet_batch_encode_device.argtypes = [vp, vp, vp, C.c_int, vp]
     L.lpcnet_batch_encode_device_shard.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -901,6 +903,20 @@ class LPCNetBatch:
         if rc < 0:
             self._chk(rc, "dred_enc_form")
         return rc
+
+    @property
+    def dred_enc_fast(self) -> int:
+        """the DRED encoder's arithmetic: 0 PARITY (the default: the bits of the reference's generic-C build), 1 FAST at the engine's tile, 16 or 32 FAST
+        pinned to that many streams per workgroup (the same bits in either).  FAST is the fma-chain arithmetic of the reference's AVX2 float build on the
+        fp32 matrix pipe; every dred_encode* call follows the switch, and the per-stream state is the same record in both.  Float encoders only"""
+        rc = self.L.lpcnet_batch_dred_enc_get_fast(self.p)
+        if rc < 0:
+            self._chk(rc, "dred_enc_fast")
+        return rc
+
+    @dred_enc_fast.setter
+    def dred_enc_fast(self, mode):
+        self._chk(self.L.lpcnet_batch_dred_enc_set_fast(self.p, int(mode)), "dred_enc_fast")
 
     def dred_encode(self, features: np.ndarray, count, latents: np.ndarray | None = None, initial_state: np.ndarray | None = None):
         """features (n, 2 * max_dframes, stride >= 20) float32, count [n] -> (latents (n, max_dframes, latent_dim), initial_state (n, max_dframes,

@@ -468,6 +468,26 @@ int lpcnet_batch_dred_enc_get_form(const LPCNetBatch *b, int n_streams)
     if (rc < 0) take_engine_err();
     return rc;
 }
+/* all shards or none, like the decoder's switch: a sharded batch never encodes in two arithmetics */
+int lpcnet_batch_dred_enc_set_fast(LPCNetBatch *b, int mode)
+{
+    NEED_DENC_ON(b);
+    const int before = lpcn_batch_dev_dred_enc_get_fast(b->sh[0].dev);
+    for (int k = 0; k < b->n_shards; k++) {
+        const int rc = lpcn_batch_dev_dred_enc_set_fast(b->sh[k].dev, mode);
+        if (rc) {
+            take_engine_err();
+            while (k-- > 0) lpcn_batch_dev_dred_enc_set_fast(b->sh[k].dev, before);
+            return rc;
+        }
+    }
+    return 0;
+}
+int lpcnet_batch_dred_enc_get_fast(const LPCNetBatch *b)
+{
+    NEED_DENC_ON(b);
+    FWD(lpcn_batch_dev_dred_enc_get_fast(b->sh[0].dev));
+}
 typedef struct { LPCNetBatch *b; const float *features; int stride; const int *count; float *latents, *initial; int info[7]; } denc_args;
 static int denc_shard(void *args, int k)
 {

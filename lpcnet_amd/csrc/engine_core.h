@@ -206,6 +206,8 @@ struct lpcn_engine {
     int denc_present = 0;          //   ... lpcn_dred_enc_model.present of the blob, lpcn_dred_enc_servable, ...
     bool denc_servable = false;
     std::unique_ptr<DredEncHostModel> denc_host;  //   ... not uploaded yet
+    std::unique_ptr<DredFastHost> denc_fast_host;   //   ... a float encoder's GRU input matrices, kept from the upload until its FAST image is packed from them
+    const lpcn::DredFastImage *d_denc_fast = nullptr;   //   ... the encoder's FAST image (rdovae_enc_fast_kernel), once a batch has asked for FAST
 };
 
 // width of GRU g (0, 1) of the engine's PLC network, read from the net that was uploaded: a stream's network state is four copies of g1 + g2 floats
@@ -295,6 +297,7 @@ struct lpcn_dred_host {
 struct lpcn_denc_host {
     int max_dframes = 0, cus = 0;                   // (cus: the device's compute units, for the form table)
     int form = 0;                                   // streams per workgroup pinned by lpcn_batch_dev_dred_enc_set_form (0: the table's choice)
+    int fast = 0;                                   // lpcn_batch_dev_dred_enc_set_fast: 0 PARITY, 1 FAST at the engine's tile, else FAST at that tile
     size_t rec = 0;                                 // floats of a stream's record
     DevBuf<float> state;                            // [n][rec]: GRU states, the conv memory as a ring, the ring's head
     DevBuf<int> d_cnt;                              // a call's per-stream counts ...
@@ -448,6 +451,8 @@ int lpcn_launch_frame_kernels(const LpcnFrameModel &M, hipStream_t st, int n, in
 int group_alloc(lpcn_batch_dev *b);
 // engine_dred.hip: the host copy of the blob's DRED decoder, taken when the engine is created
 int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m);
+// engine_dred.hip: a FAST image packed from `F` (dred_fast_pack.h) and uploaded; `what` names the half in the messages ("DRED FAST", "DRED encoder FAST")
+int dred_fast_image_upload(lpcn_engine *e, const DredFastHost &F, const lpcn::DredFastImage **dst, const char *what);
 // engine_dred_enc.hip: the same for the blob's DRED encoder
 int denc_engine_init(lpcn_engine *e, const lpcn_model_host *m);
 // engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)

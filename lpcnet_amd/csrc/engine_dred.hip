@@ -143,17 +143,15 @@ extern "C" int lpcn_batch_dev_dred_set_form(lpcn_batch_dev *b, int S)
 // ---- the FAST flavour (dred_fast_kernels.hip.h): the float decoder in the arithmetic of the reference's AVX2+FMA build, the streams of a workgroup on
 // the columns of an fp32 MFMA.  Its image of the GRUs' sparse input matrices is packed on the host (dred_fast_pack.h) and uploaded when a batch first
 // asks for FAST; the host copy of those matrices goes then.  The other arrays are the PARITY block's.
-static int dred_fast_upload(lpcn_engine *e)
+int dred_fast_image_upload(lpcn_engine *e, const DredFastHost &F, const lpcn::DredFastImage **dst, const char *what)
 {
-    if (e->d_dred_fast) return 0;
-    if (!e->dred_fast_host) { snprintf(g_err, sizeof(g_err), "DRED FAST: the decoder's host arrays are gone"); return LPCN_E_MODEL; }
     lpcn::DredFastImage im{};
     for (int g = 0; g < 3; ++g) {
-        const DredFastHost &F = *e->dred_fast_host;
         lpcn_dred_fast_gru pk;
         const int prc = lpcn_dred_fast_pack(F.w[g].data(), F.idx[g].data(), F.n_in[g], F.n[g], &pk);
         if (prc) {
-            snprintf(g_err, sizeof(g_err), prc == -1 ? "DRED FAST: out of memory" : "DRED FAST: GRU %d's block lists are not ascending: no FAST image", g);
+            if (prc == -1) snprintf(g_err, sizeof(g_err), "%s: out of memory", what);
+            else snprintf(g_err, sizeof(g_err), "%s: GRU %d's block lists are not ascending: no FAST image", what, g);
             return prc == -1 ? LPCN_E_HIP : LPCN_E_MODEL;
         }
         const size_t blocks = (size_t)pk.start[3 * pk.tiles];
@@ -163,7 +161,13 @@ static int dred_fast_upload(lpcn_engine *e)
         lpcn_dred_fast_release(&pk);
         if (rc) return rc;
     }
-    int rc = upload<lpcn::DredFastImage>(e, &e->d_dred_fast, &im, 1);
+    return upload<lpcn::DredFastImage>(e, dst, &im, 1);
+}
+static int dred_fast_upload(lpcn_engine *e)
+{
+    if (e->d_dred_fast) return 0;
+    if (!e->dred_fast_host) { snprintf(g_err, sizeof(g_err), "DRED FAST: the decoder's host arrays are gone"); return LPCN_E_MODEL; }
+    const int rc = dred_fast_image_upload(e, *e->dred_fast_host, &e->d_dred_fast, "DRED FAST");
     if (rc) return rc;
     e->dred_fast_host.reset();
     return 0;

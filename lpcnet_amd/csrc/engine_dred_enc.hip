@@ -3,6 +3,7 @@
 // copies (engine_roster.hip) treat them like the others.
 #include "engine_core.h"
 #include "rdovae_enc_kernels.hip.h"
+#include "rdovae_enc_fast_kernels.hip.h"
 #include "lpcnet_tables_gen.h"
 
 static constexpr size_t DENC_LDS_MAX = 160 * 1024;
@@ -55,6 +56,16 @@ static int denc_upload_net(lpcn_engine *e, lpcn::DredEncNetT<W> &net, const lpcn
         (rc = upload<float>(e, &n.tansig, lpcn_tansig, 201))) return rc;
     if ((rc = upload<lpcn::DredEncNetT<W>>(e, d_net, &n, 1))) return rc;
     net = n;
+    if constexpr (std::is_same<W, float>::value) {       // (what the FAST image is packed from outlives the host copy: denc_fast_upload)
+        auto f = std::make_unique<DredFastHost>();
+        for (int g = 0; g < 3; ++g) {
+            const lpcn_gru_layer &G = d.gru[g];
+            f->w[g].assign(G.w, G.w + 32 * (size_t)G.nb);
+            f->idx[g].assign(G.idx, G.idx + 3 * G.n / 8 + G.nb);
+            f->n_in[g] = G.n_in; f->n[g] = G.n;
+        }
+        e->denc_fast_host = std::move(f);
+    }
     e->denc_host.reset();
     return 0;
 }
@@ -151,6 +162,76 @@ extern "C" int lpcn_batch_dev_dred_enc_set_form(lpcn_batch_dev *b, int S)
     return 0;
 }
 
+// ---- the FAST flavour (rdovae_enc_fast_kernels.hip.h): the float encoder in the arithmetic of the reference's AVX2+FMA build, the
+// streams of a workgroup on the columns of an fp32 MFMA.  Its image of the GRUs' sparse input matrices is the decoder's format, packed on the host
+// (dred_fast_pack.h) and uploaded when a batch first asks for FAST; the host copy of those matrices goes then.  The other arrays are the PARITY block's.
+static int denc_fast_upload(lpcn_engine *e)
+{
+    if (e->d_denc_fast) return 0;
+    if (!e->denc_fast_host) { snprintf(g_err, sizeof(g_err), "DRED encoder FAST: the encoder's host arrays are gone"); return LPCN_E_MODEL; }
+    const int rc = dred_fast_image_upload(e, *e->denc_fast_host, &e->d_denc_fast, "DRED encoder FAST");
+    if (rc) return rc;
+    e->denc_fast_host.reset();
+    return 0;
+}
+// (a kilobyte is left to the kernel's static LDS)
+static bool denc_fast_fits(const lpcn_engine *e, int T)
+{
+    return lpcn::rdovae_enc_fast_tiles_fit(e->denc) && (size_t)lpcn::rdovae_enc_fast_lds_floats(e->denc, T) * sizeof(float) <= DENC_LDS_MAX - 1024;
+}
+// The tile a FAST launch over n streams runs with: the pinned one, or the engine's choice (mode 1).  The rule is read off
+// profiles/dred_enc_fast_rate.json, and it is the decoder's: a tile's chain takes the same time whether it carries 16 or 32 streams,
+// so T = 16 while its tiles fit the CUs in one round and T = 32 beyond -- among the tiles whose buffers fit the LDS.  The bits of a stream are the
+// same in both
+static int denc_fast_tile(const lpcn_batch_dev *b, int n)
+{
+    const lpcn_denc_host *p = b->denc.get();
+    if (p->fast != 1) return p->fast;
+    const int T = (n + 15) / 16 <= p->cus ? 16 : 32;
+    return denc_fast_fits(b->e, T) ? T : 16;
+}
+template <int T, int U>
+static int denc_fast_prepare(const lpcn_engine *e)
+{
+    if (!denc_fast_fits(e, T)) return 0;
+    HIP_TRY(hipFuncSetAttribute((const void *)lpcn::rdovae_enc_fast_kernel<T, U>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lpcn::rdovae_enc_fast_lds_floats(e->denc, T) * (int)sizeof(float)));
+    return 0;
+}
+extern "C" int lpcn_batch_dev_dred_enc_get_fast(const lpcn_batch_dev *b)
+{
+    NEED_DENC(b);
+    return b->denc->fast;
+}
+extern "C" int lpcn_batch_dev_dred_enc_set_fast(lpcn_batch_dev *b, int mode)
+{
+    NEED_DENC(b);
+    lpcn_engine *e = b->e;
+    if (mode != 0 && mode != 1 && mode != 16 && mode != 32) { snprintf(g_err, sizeof(g_err), "DRED encoder FAST: 0 = off, 1 = the engine's tile, 16 or 32 = that many streams per workgroup (the tiles that are built)"); return LPCN_E_ARG; }
+    if (e->is_int8 && mode) { snprintf(g_err, sizeof(g_err), "DRED encoder FAST: the int8 encoder has no FAST form yet"); return LPCN_E_MODEL; }
+    if (mode) {
+        // a pinned tile must fit; mode 1 falls back to 16 streams where 32 do not fit
+        if (!denc_fast_fits(e, mode == 32 ? 32 : 16)) {
+            snprintf(g_err, sizeof(g_err), "DRED encoder FAST: the encoder's tile of %d streams (%zu bytes, bits_dense and gdense1 in at most %d tiles of 32 rows) does not fit a workgroup",
+                     mode == 32 ? 32 : 16, (size_t)lpcn::rdovae_enc_fast_lds_floats(e->denc, mode == 32 ? 32 : 16) * sizeof(float), lpcn::ENC_FAST_TRAIL_WAVES * lpcn::ENC_FAST_SLOTS);
+            return LPCN_E_MODEL;
+        }
+        DeviceGuard guard(e->device);
+        int rc = wait_all(b);
+        // (the dynamic-LDS limits are raised here, not at a launch: a launch sets nothing, so it can be captured)
+        if (rc || (rc = denc_fast_upload(e)) || (rc = denc_fast_prepare<16, 16>(e)) || (rc = denc_fast_prepare<32, 8>(e))) return rc;
+    }
+    b->denc->fast = mode;
+    return 0;
+}
+template <int T, int U>
+static void denc_fast_launch(const lpcn_batch_dev *b, hipStream_t st, const int *d_cnt, int uniform, const float *d_feat, int stride, float *d_lat, float *d_init)
+{
+    const int lds = lpcn::rdovae_enc_fast_lds_floats(b->e->denc, T) * (int)sizeof(float);
+    hipLaunchKernelGGL((lpcn::rdovae_enc_fast_kernel<T, U>), dim3((b->active + T - 1) / T), dim3(lpcn::ENC_FAST_THREADS), lds, st, b->e->d_denc, b->e->d_denc_fast, b->active,
+                       b->denc->max_dframes, d_cnt, uniform, d_feat, stride, (float *)b->denc->state, d_lat, d_init);
+}
+
 // count in 0 .. max_dframes and zero beyond the active prefix (count == NULL: n_dframes for every active stream); stride >= 20
 extern "C" int lpcn_batch_dev_dred_enc_check(const lpcn_batch_dev *b, const int *count, int n_dframes, int stride)
 {
@@ -199,7 +280,10 @@ static int denc_enqueue(lpcn_batch_dev *b, const float *d_feat, int stride, cons
         p->cnt_pending = true;
     }
     const int *d_cnt = count ? (const int *)p->d_cnt : nullptr;
-    switch (lpcn_batch_dev_dred_enc_form(b, b->active)) {
+    if (p->fast) {
+        if (denc_fast_tile(b, b->active) == 16) denc_fast_launch<16, 16>(b, st, d_cnt, n_dframes, d_feat, stride, d_lat, d_init);
+        else denc_fast_launch<32, 8>(b, st, d_cnt, n_dframes, d_feat, stride, d_lat, d_init);
+    } else switch (lpcn_batch_dev_dred_enc_form(b, b->active)) {
     case 1: denc_launch_form<1>(b, st, d_cnt, n_dframes, d_feat, stride, d_lat, d_init); break;
     case 2: denc_launch_form<2>(b, st, d_cnt, n_dframes, d_feat, stride, d_lat, d_init); break;
     case 4: denc_launch_form<4>(b, st, d_cnt, n_dframes, d_feat, stride, d_lat, d_init); break;

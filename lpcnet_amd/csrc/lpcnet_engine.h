@@ -471,6 +471,8 @@ int  lpcn_batch_dev_dred_enc_flavour(const lpcn_batch_dev *b);                /*
 int  lpcn_batch_dev_dred_enc_info(const lpcn_batch_dev *b, int *info7);        /* {max_dframes, 40, latent, state, taps, sum of the widths, floats of a stream's state} */
 int  lpcn_batch_dev_dred_enc_set_form(lpcn_batch_dev *b, int S);      /* streams per workgroup: 1, 2, 4, 8 where the buffers fit the LDS; 0 = the table's choice */
 int  lpcn_batch_dev_dred_enc_form(const lpcn_batch_dev *b, int n);    /* what a launch over n streams runs with */
+int  lpcn_batch_dev_dred_enc_set_fast(lpcn_batch_dev *b, int mode);   /* 0 PARITY, 1 FAST at the engine's tile, 16 / 32 FAST at that tile; LPCN_E_MODEL on an int8 encoder */
+int  lpcn_batch_dev_dred_enc_get_fast(const lpcn_batch_dev *b);
 int  lpcn_batch_dev_dred_enc_check(const lpcn_batch_dev *b, const int *count, int n_dframes, int stride);      /* the argument checks alone */
 int  lpcn_batch_dev_dred_encode(lpcn_batch_dev *b, const float *d_features, int stride, const int *count, int n_dframes, float *d_latents, float *d_initial,
                                 void *hip_stream);

@@ -3,6 +3,7 @@
 
     python tools/dred_enc_rate.py OUT.json       (profiles/dred_enc_rate.json when run for the record)
     python tools/dred_enc_rate.py --int8 OUT.json       (profiles/dred_enc_i8_rate.json: the int8 encoder beside the float one)
+    python tools/dred_enc_rate.py --fast OUT.json       (profiles/dred_enc_fast_rate.json: the FAST flavour beside PARITY)
 
 For 256, 2 048 and 8 192 streams at the widths of the training defaults, at two operating points -- one double frame per call (two 10-ms
 frames: the 20-ms real-time step) and 50 double frames per call (one second) -- the time of one call (HIP events around the enqueue-only device-pointer call in its uniform form, on
@@ -17,6 +18,10 @@ time limit.
 alternate call by call in the one process, so that int8 and float see the same clocks.  `rows` holds the int8 rows, `float_rows` the float rows
 of the same session, `int8_over_float` the ratio of the medians per row at the table's form and at each flavour's best pinned form; the CPU
 yardstick is the reference's AVX2 int8 build (liblpcnet_ref_ai.so).
+--fast (profiles/dred_enc_fast_rate.json): PARITY at the table's form beside the FAST flavour (lpcnet_batch_dred_enc_set_fast) pinned to every tile
+that is built and at the engine's tile (mode 1), on one batch: the four alternate call by call in rotating order, the same protocol and rows.  A
+row's `spread_ms` is the widest 10th-to-90th range among its four columns; the three FAST columns' outputs from a freshly reset state are compared bit
+for bit, and the largest |FAST - PARITY| is recorded.
     timeout -k 10 600 python tools/dred_enc_rate.py profiles/dred_enc_rate.json
 """
 import json
@@ -144,8 +149,78 @@ def measure(out_path, int8=False):
         fh.write("\n")
 
 
+FAST_TILES = (16, 32)           # every tile that is built (lpcnet_batch_dred_enc_set_fast)
+
+
+def measure_fast(out_path):
+    import torch
+    import dred_enc_model as em
+    from lpcnet_amd import api
+    dev = torch.device("cuda:0")
+    blob = em.set_blob("tf")
+    info = api.dred_enc_model_info(blob)
+    base = em.inputs(64, max(DFRAMES), seed=0x2A7F)
+    modes = [("parity", 0)] + [("fast_T%d" % t, t) for t in FAST_TILES] + [("fast", 1)]
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), widths=info["widths"], latent_dim=info["latent_dim"], taps=info["taps"],
+                  timed_calls=TIMED, warmup_calls=WARMUP,
+                  note="PARITY (table form) and FAST alternate call by call, in rotating order, in one process; ms of one encode call by HIP events", rows=[])
+    s = torch.cuda.Stream()
+    for n in STREAMS:
+        for nd in DFRAMES:
+            b = api.LPCNetBatch(n, blob)
+            b.dred_enc_enable(nd)
+            d_feat = torch.from_numpy(np.ascontiguousarray(np.tile(base[:, :2 * nd], (n // 64 + 1, 1, 1))[:n])).to(dev)
+            d_lat = torch.zeros((n, nd, info["latent_dim"]), dtype=torch.float32, device=dev)
+            d_init = torch.zeros((n, nd, info["state_dim"]), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            ms = {name: [] for name, _ in modes}
+            first = {}
+            with torch.cuda.stream(s):
+                for k in range(WARMUP + TIMED):
+                    for name, mode in modes[k % len(modes):] + modes[:k % len(modes)]:      # (rotated: every column follows every other one equally often)
+                        b.dred_enc_fast = mode
+                        if k == 0:
+                            b.reset()
+                        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record(s)
+                        b.dred_encode_device(d_feat.data_ptr(), 20, nd, d_lat.data_ptr(), d_init.data_ptr(), hip_stream=s.cuda_stream)
+                        e.record(s)
+                        e.synchronize()
+                        if k >= WARMUP:
+                            ms[name].append(a.elapsed_time(e))
+                        elif k == 0:
+                            first[name] = torch.cat([d_lat.reshape(n, -1), d_init.reshape(n, -1)], 1).clone()
+            tile = 16 if (n + 15) // 16 <= torch.cuda.get_device_properties(0).multi_processor_count else 32      # (the engine's rule for mode 1)
+            b.dred_enc_fast = 0
+            table_form = b.dred_enc_form()
+            b.close()
+            for name, mode in modes[2:]:
+                if not torch.equal(first[name].view(torch.int32), first[modes[1][0]].view(torch.int32)):
+                    raise SystemExit("%s differs from %s at %d streams" % (name, modes[1][0], n))
+            row = dict(streams=n, dframes=nd, parity_table_form=table_form, mode1_tile=tile,
+                       max_abs_fast_minus_parity=float((first["fast"] - first["parity"]).abs().max()), modes=[])
+            for name, mode in modes:
+                v = np.array(ms[name])
+                row["modes"].append(dict(mode=name, set_fast=mode, median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()),
+                                         p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)),
+                                         us_per_stream_dframe=float(1e3 * np.median(v) / (n * nd))))
+            med = {r["mode"]: r["median_ms"] for r in row["modes"]}
+            spr = {r["mode"]: r["p90_ms"] - r["p10_ms"] for r in row["modes"]}
+            row["spread_ms"] = max(spr.values())
+            row["fast_gain_over_parity_ms"] = med["parity"] - med["fast"]
+            row["fast_beats_parity_by_more_than_the_two_spreads"] = bool(row["fast_gain_over_parity_ms"] > spr["parity"] + spr["fast"])
+            print(json.dumps(row), flush=True)
+            result["rows"].append(row)
+    with open(out_path, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if not args:
         raise SystemExit(__doc__)
-    measure(args[0], int8="--int8" in sys.argv[1:])
+    if "--fast" in sys.argv[1:]:
+        measure_fast(args[0])
+    else:
+        measure(args[0], int8="--int8" in sys.argv[1:])
