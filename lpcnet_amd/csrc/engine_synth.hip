@@ -20,7 +20,8 @@ extern "C" int lpcn_launch_sample_x2(int nw, int grid, int lds, hipStream_t st, 
 extern "C" int lpcn_launch_sample_x2w(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);     // sample_x2w.hip: its streamed variants (more than 32 items per lane)
 extern "C" int lpcn_launch_sample_x2f(int nw, int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);     // sample_x2f.hip: its register-resident variants with FAST fp32 arithmetic
 extern "C" int lpcn_x2_lds_bytes(int nb_b);
-extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout)
+extern "C" int lpcn_launch_sample_x3(int grid, int lds, hipStream_t st, const LpcnSampleArgs *d_args);      // sample_x3.hip: the same on twelve waves (same LDS layout, its own cells behind it)
+extern "C" int lpcn_x3_lds_bytes(int nb_b);
 
 // What a whole-batch call launches: every stream in the batch's form -- or, on an active prefix shorter than the batch, streams [0, active) in a
 // pinned form, else the cost table's form for that many streams (as a compacted group gets: a table look-up, never a measurement), never on twelve
@@ -43,7 +44,7 @@ SamplePlan plan_sample(const lpcn_batch_dev *b, const LaunchShape &sh, int n_fra
     if (sh.S == 8 && (!x2_available(b) || (unsigned long long)sh.n * (unsigned long long)n_frames * LPCN_ROWS_A * 4ull >= (1ull << 32))) { p.S = 4; p.pack2 = false; }
     p.x3 = p.S == 8 && sh.x3 && x3_available(b);
     p.image = p.x3 ? &e->image[IMG_X3] : &gru_a_image(e, p.S);
-    p.lds = p.S == 8 ? lpcn_x2_lds_bytes(e->nb_b) : p.S == 1 ? lpcn::Lds<1>::total(e->nb_b, e->is_int8) : p.S == 2 ? lpcn::Lds<2>::total(e->nb_b, e->is_int8) : lpcn::Lds<4>::total(e->nb_b, e->is_int8);
+    p.lds = p.x3 ? lpcn_x3_lds_bytes(e->nb_b) : p.S == 8 ? lpcn_x2_lds_bytes(e->nb_b) : p.S == 1 ? lpcn::Lds<1>::total(e->nb_b, e->is_int8) : p.S == 2 ? lpcn::Lds<2>::total(e->nb_b, e->is_int8) : lpcn::Lds<4>::total(e->nb_b, e->is_int8);
     p.grid = (sh.n + p.S - 1) / p.S;
     return p;
 }

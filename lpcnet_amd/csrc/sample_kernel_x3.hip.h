@@ -5,10 +5,11 @@
 // what.  With two waves per SIMD every interval of that kernel is a chain of latency-bound links on each wave, and only the partner wave can fill
 // them; here a SIMD carries one chain wave and two row waves, in 168 VGPRs each:
 //
-//      waves 0..3    GRU-B's chain of one stream of group Q (grub_lds_loop_s4_v168.inc: the same loop in v128..v167), stage 1 of that stream's tree
-//                    (tree_stages.h) behind the gates, then their P1 segments of P
+//      waves 0..3    GRU-B's chain of one stream of group Q (grub_lds_loop_s4_v168.inc: the same loop in v128..v167) and its gates, then their P1
+//                    segments of P
 //      waves 4..11   the candidate heads of Q in the chains' shadow, the start-value pass ("P0") of P -- 2.25 rounds of 512 rows instead of 4.5 of
-//                    256, two rounds in flight --, their P1 segments of P; they evaluate no tree nodes
+//                    256, two rounds in flight --, their P1 segments of P
+//      LPCN_X3_HELPERS   four of the row waves, one per stream: stage 1 of that stream's tree (tree_stages.h) on the state its chain wave has stored
 //      wave LPCN_X3_S2W   stage 2 of the four streams' trees in one packed pass, behind its P1 segments
 //
 // A lane holds 16 items (64 weight VGPRs) instead of 30, so a candidate slot of more than 16 items is cut: its head -- blocks 0..15, from
@@ -25,7 +26,33 @@ namespace lpcn {
 #define LPCN_X3_TW 1            // the wave that draws the KISS99 thresholds: a chain wave on another SIMD than the leader's (waves w, w + 4, w + 8 share one: tools/ubench/hwid.hip)
 #define LPCN_X3_HG 6            // head items a row wave runs before it polls the leader's indices for the start-value pass
 #define LPCN_X3_S2W 11          // the wave that runs stage 2 of the four streams' trees in one pass: any but the leader's.  Row wave 9 / 11, chain wave 0 / 2 / 3: 177.8 / 180.6 / 176.8 / 176.9 / 172.7 M (round 13; the eight-wave form 175.6 M, this kernel with round 6's tree 163.0 M)
+#define LPCN_X3_HELPERS 0xA865u  // nibble s: the HELPER wave of stream s, which runs stage 1 of that stream's tree -- row waves 5, 6, 8, 10: none on its stream's chain SIMD, none on the stage-2 wave's.  184.9 M against 180.2 M with stage 1 on the chain waves; {8,5,6,7}, each helper on its chain's SIMD: 180.5 M, a tie (round 14; the other maps in EXPERIMENTS.md)
 #define LPCN_X3_S2_LEAD 2       // ... and how many of its P1 items from the end it polls the streams' prefixes and issues the loads of its rows (on wave 11, 1 / 2 / 4: 180.8 / 180.6 / 180.6 M, a tie; at least 1)
+
+// The twelve-wave form's own LDS cells, behind everything LdsX2 lays out (no LdsX2 offset moves): per group one word per stream, the sequence number
+// of the sample whose GRU-B state the stream's chain wave has stored.
+struct LdsX3 {
+    static constexpr int g_seq  = 0;                                // [4] i32
+    static constexpr int G_SZ   = 16;
+    static constexpr int total(int nb_b) { return LdsX2::total(nb_b) + 2 * G_SZ; }
+};
+// the helper wave of stream s / the stream a wave helps (-1: none)
+constexpr int lpcn_x3_helper_wave(const int s) { return (int)((LPCN_X3_HELPERS >> (4 * s)) & 15u); }
+__host__ __device__ constexpr int lpcn_x3_helper_stream(const int wave)
+{
+    for (int s = 0; s < 4; ++s) if ((int)((LPCN_X3_HELPERS >> (4 * s)) & 15u) == wave) return s;
+    return -1;
+}
+constexpr bool lpcn_x3_helpers_ok()
+{
+    for (int s = 0; s < 4; ++s) {
+        const int w = lpcn_x3_helper_wave(s);
+        if (w < LPCN_X3_CHAIN_WAVES || w >= LPCN_X3_WAVES || w == LPCN_X3_LW || w == LPCN_X3_S2W) return false;
+        for (int t = 0; t < s; ++t) if (lpcn_x3_helper_wave(t) == w) return false;
+    }
+    return true;
+}
+static_assert(lpcn_x3_helpers_ok(), "four distinct helper waves among the row waves, never the leader's or the stage-2 wave");
 
 __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const LpcnSampleArgs *__restrict__ Ap)
 {
@@ -90,6 +117,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
     const LPCN_GLOBAL float *cond_a_s = as_global(Ap->cond_a);
     asm volatile("" : "+s"(cond_a_s));
     const int hl = __builtin_amdgcn_readfirstlane(as_global(Ap->a_head)[tid0 >> 6]);      // items of this wave's head, at [NW - hl, NW)
+    const bool p1_wave = __builtin_amdgcn_readfirstlane(b4 > 0 ? 1 : 0) != 0;      // wave-uniform: this wave has P1 items
     const bool early_wave = __builtin_amdgcn_readfirstlane(__ballot(row_reg[0] >= 0) != 0ull ? 1 : 0) != 0;      // wave-uniform: this wave computes a head (rows without blocks: bias + diag*h alone) one sample ahead
 
     // ------------------------------------------------------------------ LDS residents -------
@@ -115,6 +143,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
         }
         if (tid < 2) { int *fl = (int *)(smem + tid * L::G_SZ + L::g_flag); fl[0] = 0; fl[1] = 0; }
         if (tid < 2 * S) ((int *)(smem + (tid >> 2) * L::G_SZ + L::g_pfx))[tid & 3] = 0;      // (no sample has sequence number 0)
+        if (tid < 2 * S) ((int *)(smem + L::total(Ap->nb_b) + (tid >> 2) * LdsX3::G_SZ + LdsX3::g_seq))[tid & 3] = 0;
     }
     __syncthreads();
 
@@ -134,6 +163,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
     float lpc_tap = 0.f, prod_old = 0.f;                     // leader lanes: computed behind the tree of a group, used when its sample is finished
 
     const int T = n_frames * frame_len;                      // samples per stream in this launch
+    const int x3_cells = __builtin_amdgcn_readfirstlane(L::total(Ap->nb_b));
 #if LPCN_ENABLE_PROF
     // per-phase shader-clock accounting of workgroup 0 (profiling builds only): the slots and LPCN_X2_PROF of sample_kernel_x2.hip.h, waves 0..7
     unsigned long long *const prof = Ap->prof;
@@ -158,6 +188,7 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
         short *const pcm_p = (short *)(gp + L::g_pcm);
         const LeaderCells cells_p = {(float *)(gp + L::g_lead), idx_p, (float *)(gp + L::g_thr), pcm_p};      // group P's leader cells (sample_common.hip.h)
         const uint32_t flag_p = lds_addr(gp + L::g_flag);
+        unsigned char *const xq = smem + x3_cells + q * LdsX3::G_SZ;      // group Q's sequence words (LdsX3)
 
         // ------------------------------------------------ the leader finishes group P's previous sample --
         if (more) ++seqP;
@@ -384,9 +415,6 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
                     : [z] "+v"(zrh), [wp] "+v"(wp32), [hp] "+v"(hp32) : : LPCN_GRUB_LDS168_CLOBBERS);
                 __builtin_amdgcn_s_setprio(0);
                 LPCN_X2_PROF(1);
-                // P4 of stream s, stage 1: the rows of the tree's top levels are the same every sample; fetched here, behind the assembly block (its
-                // v128..v167 are dead, nothing extra is live across it), they land under the gates
-                const TreeRow top = tree_row_load<0>(fc_w_s, fc_b_s, fc_f_s, ln_, 0);
                 // gates: rows [0,16) update, [16,32) reset, [32,48) candidate (src/nnet.c:362-371)
                 const int ln = ln_ & 15;
                 const float sg = lpcn_sigmoid(zrh + rec, sm_tansig);
@@ -399,15 +427,10 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
                     if ((live_maskQ >> s) & 1) hB_q[s * NB + ln_] = hnew;
                 }
                 LPCN_X2_PROF(2);
-                // ---- P4 of group Q, stage 1: the top five levels of stream s's tree on the wave that has just produced its state, as on the eight-wave
-                // kernel (sample_kernel_x2.hip.h): the state is read back from the cells this wave has just written (a wave's LDS operations complete in
-                // order: no counter, no wait for another stream's chain), the five decided bits are published under the sample's sequence number behind
-                // the state stores.  Until round 13 waves 4..11 evaluated all 255 nodes x 2 channels of the four streams behind their P1, behind a poll for
-                // the SLOWEST chain: a serial link of a whole tree evaluation on every half-step, and eight waves' worth of issue slots.
-                const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
-                const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
-                if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
-                LPCN_X2_PROF(9);                             // (slot 9 = the tree, as on the eight-wave kernel: a chain wave's stage 1 here plus whatever it runs between the close of its P1 and barrier 1 -- the stage-2 pass where it hosts it, else next to nothing)
+                // The state is stored: the sample's sequence number goes out behind the stores (a wave's LDS operations complete in order), and this wave
+                // goes on to its P1 items -- 15 or 16 of them on the benchmark model, the longest path of interval A.  Stage 1 of the stream's tree, which
+                // ran here until round 14, is the helper wave's (below): a clamped copy's chain publishes like any other.
+                lds_publish(lds_addr(xq + LdsX3::g_seq) + s * 4, seqQ);
             }
             // (Round 6 also gave these waves a share of P's start-value pass -- a round of update / reset rows and one of candidate inputs, or the candidate
             // inputs alone, issued above the gates: 144.0 / 145.7 vs 147.0 M.  With only the barrier waits instrumented the chain waves have 1.3-2.2 k clk
@@ -479,7 +502,8 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
         if (s2_wave && !s2_in_items) s2_open();
 
         // ---------------------------------------------------------------- 5: P1 of group P ----
-        if (p_active) {
+        if (p_active && p1_wave) {                           // (wave-uniform.  A wave without P1 items has no rows to start or to close and nothing of P0's to wait for; until round 14 it polled
+                                                             // the arrival counter and swapped three absent rows all the same, which on a helper wave stands in front of the tree)
             hA_cur = gp + L::g_hA;
             load_negz();
             lds_poll_until<false>(p0cnt_p, seqP * NP0);       // the start values of the update / reset rows and the candidate inputs come from P0
@@ -567,6 +591,24 @@ __global__ __launch_bounds__(LPCN_X3_THREADS, 1) void sample_kernel_x3(const Lpc
             }
             row_store(4);
             LPCN_X2_PROF(6);
+        }
+        // ---------------------------------------------------------------- P4 of group Q, stage 1 (the streams' helper waves) ----
+        // The top five levels of stream s's tree on a ROW wave (LPCN_X3_HELPERS), behind the close of its P1 segments -- none on the benchmark model --:
+        // the rows of the top levels are the same every sample and are fetched before the poll; the wave then reads the stream's sequence word until
+        // the chain wave has published this sample's number behind its state stores, evaluates the 31 nodes on that state and publishes the five
+        // decided bits under the same number for the stage-2 wave.  Every half-step with a chain has a publisher for every stream (clamped copies
+        // included) and none without one polls: a launch of one sample runs this once per group.
+        const int hs = lpcn_x3_helper_stream(wave);           // (wave-uniform)
+        if (q_chain && hs >= 0) {
+            const int s = hs;
+            int ln_ = tid0;
+            LPCN_REMAT_V(ln_);
+            ln_ &= 63;
+            const TreeRow top = tree_row_load<0>(fc_w_s, fc_b_s, fc_f_s, ln_, 0);
+            lds_poll_until<false>(lds_addr(xq + LdsX3::g_seq) + s * 4, seqQ);
+            const float *const thr_s = (const float *)(gq + L::g_thr) + s * 8;
+            const int val = tree_stage_walk<0>(top, hB_q + s * NB, thr_s, sm_tansig, ln_);
+            if (ln_ == 0) lds_publish(lds_addr(gq + L::g_pfx) + s * 4, (seqQ << LPCN_TREE_TOP) | val);
         }
         // ---------------------------------------------------------------- P4 of group Q, stage 2, second part ----
         // Behind the close of the segments: the state and the thresholds of the lane's stream, one 64-bit ballot, four three-level walks over its 16-bit
