@@ -295,8 +295,10 @@ LPCNET_EXPORT int lpcnet_hip_plc_model_info(const unsigned char *data, int len, 
  * A count outside 0 .. max_latents, first / take outside the stream's 4 count[s] decoded rows, and a non-zero count on a stream beyond its
  *   shard's active prefix return LPCNET_HIP_E_ARG with nothing written; the rows of inactive streams are untouched.  The _shard forms cover
  *   that shard's streams, in arrays and packing.
- * No per-stream state: a call keeps nothing between calls (decode_all semantics; the incremental init_states / decode_qframe pair is not
- *   exposed), so lpcnet_batch_copy_streams, the roster and the state snapshots are unaffected.  lpcnet_batch_set_fast does not change this kernel; its
+ * No per-stream state in dred_decode*: a call keeps nothing between calls (decode_all semantics), and lpcnet_batch_copy_streams, the roster and
+ *   the state snapshots do not see it.
+ *   The incremental pair underneath, init_states / decode_qframe on a per-stream state, is dred_init / dred_step below.
+ *   Which arithmetic runs is the batch's own choice, call by call: lpcnet_batch_set_fast does not change this kernel; its
  *   own switch is dred_set_fast.
  * dred_set_fast(mode) selects the arithmetic of the float decoder, per batch, off by default: 0 = PARITY, the bits above; 1 = FAST with the engine's
  *   choice of tile; 16 or 32 = FAST pinned to a tile of that many streams per workgroup (the tiles that are built; for tests and tools).  FAST is the arithmetic
@@ -326,6 +328,47 @@ LPCNET_EXPORT int lpcnet_batch_dred_set_form(LPCNetBatch *b, int S);
 LPCNET_EXPORT int lpcnet_batch_dred_get_form(const LPCNetBatch *b, int n_streams);
 LPCNET_EXPORT int lpcnet_batch_dred_set_fast(LPCNetBatch *b, int mode);
 LPCNET_EXPORT int lpcnet_batch_dred_get_fast(const LPCNetBatch *b);
+/* The DRED decoder as a per-stream state: DRED_rdovae_dec_init_states and DRED_rdovae_decode_qframe on an RDOVAEDecState (include/dred_rdovae.h;
+ * src/dred_rdovae_dec.c:37-98), the pair DRED_rdovae_decode_all is made of.  With consecutive ranges that partition [0, c[s]) for every stream,
+ *   dred_init(state, NULL); dred_step(latents, a_0, c_0, features); ... dred_step(latents, a_k, c_k, features)
+ * leaves in `features` exactly the bits dred_decode(state, latents, c, features) writes -- in every flavour, mode, form, tile, shard layout and
+ * active prefix -- so a receiver decodes as far back as the gap it knows and pays only for the latents a longer gap adds.
+ * dred_state_enable, after dred_enable (LPCNET_HIP_E_MODEL before it), allocates one float record per stream: dense2_state, dense4_state,
+ *   dense6_state in the reference's member order at their own widths, padded to whole 16 bytes; all zero is DRED_rdovae_init_decoder.  The record
+ *   is float for float and int8 blobs, PARITY and FAST: dred_set_fast may change between calls.  It is one of the batch's per-stream arrays:
+ *   lpcnet_batch_reset clears it, lpcnet_batch_copy_streams / _copy_streams_to and the roster carry it, snapshots hold it as section
+ *   LPCNET_SNAP_DRED_DEC.  Batches that never call it allocate nothing.  Every call below returns LPCNET_HIP_E_MODEL before it.
+ * dred_dec_state_size: floats of one stream's three states; get_ / set_dred_dec_state move them in that order.
+ * dred_init(state [n][state_dim], which [n] | NULL): init_states into the record of every active stream with which[s] != 0 (NULL: every active
+ *   stream); the other records keep their bits.
+ * dred_step(latents [n][max_latents][latent_dim], start [n], count [n], features [n][4 max_latents][20]): stream s runs decode_qframe on latents
+ *   start[s] .. start[s] + count[s] - 1 from its record, writes rows 4 start[s] .. 4 (start[s] + count[s]) - 1 of its features and stores the
+ *   record back.  count[s] == 0: no row written, the record untouched.  The arrays are dred_decode's own.
+ * The host forms copy in, run, copy out and synchronise (one host thread per shard).  The _device forms take device pointers and only enqueue on
+ *   `hip_stream` (NULL = the batch's own) under the ordering rules of lpcnet_batch_analyze_device; which / start / count are host arrays, read
+ *   before the call returns, and with them a capturing stream is refused (LPCNET_HIP_E_ARG).  The UNIFORM forms -- which == NULL; start == count
+ *   == NULL with first_latent / n_latents for every active stream -- depend on nothing on the host and are accepted on a capturing stream under
+ *   the rules lpcnet_batch_synthesize_device states.
+ * dred_step_packed_device* has dred_decode_packed_device's selection and layout (the oldest row first, what lpcnet_batch_plc_fec_feed_device
+ *   reads); first / take are in the stream's own (global) row numbers and lie inside the rows this call decodes.
+ * start[s] < 0, count[s] < 0, start[s] + count[s] > max_latents, a count or a `which` flag beyond the active prefix and first / take outside the
+ *   call's rows return LPCNET_HIP_E_ARG with nothing written.  The _shard forms cover that shard's streams, in arrays and packing. */
+LPCNET_EXPORT int lpcnet_batch_dred_state_enable(LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_dred_dec_state_size(const LPCNetBatch *b);
+LPCNET_EXPORT int lpcnet_batch_get_dred_dec_state(LPCNetBatch *b, int stream, float *out);
+LPCNET_EXPORT int lpcnet_batch_set_dred_dec_state(LPCNetBatch *b, int stream, const float *in);
+LPCNET_EXPORT int lpcnet_batch_dred_init(LPCNetBatch *b, const float *state, const int *which);
+LPCNET_EXPORT int lpcnet_batch_dred_init_device(LPCNetBatch *b, const float *d_state, const int *which, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_init_device_shard(LPCNetBatch *b, int shard, const float *d_state, const int *which, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_step(LPCNetBatch *b, const float *latents, const int *start, const int *count, float *features);
+LPCNET_EXPORT int lpcnet_batch_dred_step_device(LPCNetBatch *b, const float *d_latents, const int *start, const int *count, int first_latent, int n_latents,
+                                                float *d_features, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_step_device_shard(LPCNetBatch *b, int shard, const float *d_latents, const int *start, const int *count, int first_latent,
+                                                      int n_latents, float *d_features, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_step_packed_device(LPCNetBatch *b, const float *d_latents, const int *start, const int *count, const int *first,
+                                                       const int *take, float *d_packed, void *hip_stream);
+LPCNET_EXPORT int lpcnet_batch_dred_step_packed_device_shard(LPCNetBatch *b, int shard, const float *d_latents, const int *start, const int *count,
+                                                             const int *first, const int *take, float *d_packed, void *hip_stream);
 /* a blob's DRED decoder as the loader sees it, no device: info[12] = {present (0 none, 1 float arrays, 2 int8 arrays, -1 incomplete or
  * inconsistent), servable (dred_enable accepts the blob: the arrays are in the LPCNet model's own flavour), latent dimension, state dimension, the widths of dec_dense1 .. dec_dense8}.  Returns 0,
  * LPCNET_HIP_E_ARG without `info`, LPCNET_HIP_E_MODEL when the blob does not load as an LPCNet model at all */
@@ -538,7 +581,8 @@ LPCNET_EXPORT int lpcnet_batch_set_decoder_vq_mem(LPCNetBatch *b, int stream, co
  * restore: record i of the blob -> stream streams[i], i < m (m at most the blob's count: the first m records; streams distinct).  The blob's layout
  *   must MATCH the batch: a section on both sides has equal bytes; another flavour, PLC on one side only or with other options or widths, and a blob
  *   of a build with other struct sizes are LPCNET_HIP_E_MODEL with a message that names the section; a section only the snapshot has makes the host
- *   form enable that subsystem in the batch first (analysis, encoder, kept products, DRED encoder -- as copy_streams across shards does); a section
+ *   form enable that subsystem in the batch first (analysis, encoder, kept products, DRED encoder, the DRED decoder's record in a batch that has
+ *   dred_enable'd -- one that has not is LPCNET_HIP_E_MODEL: max_latents is the batch's to say -- as copy_streams across shards does); a section
  *   only the batch has receives a fresh stream's record (zeros, a reset control state, flag 0).  A NULL, truncated or inconsistent blob is
  *   LPCNET_HIP_E_ARG.  On any refusal nothing has changed.  On a sharded batch both host forms run one host thread per shard.
  * snapshot_device / restore_device: the same on device memory, ONE upload of the list and ONE launch, only enqueued on hip_stream (NULL = the batch's
@@ -573,6 +617,7 @@ LPCNET_EXPORT int lpcnet_batch_set_decoder_vq_mem(LPCNetBatch *b, int stream, co
 #define LPCNET_SNAP_PLC_AN    18
 #define LPCNET_SNAP_PLC_CTL   19
 #define LPCNET_SNAP_DRED_ENC  20
+#define LPCNET_SNAP_DRED_DEC  21      /* the DRED decoder's per-stream record (lpcnet_batch_dred_state_enable): present when the batch has it */
 #define LPCNET_SNAP_META      10      /* ints of a stream's host halves: the PLC's nine control ints (zero without PLC), the kept products' flag */
 #define LPCNET_SNAP_CONFIG    10      /* ints of a configuration, below */
 #define LPCNET_SNAP_LAYOUT_INTS 92    /* the most ints a layout has: 14 head fields and 26 sections */
@@ -590,7 +635,8 @@ LPCNET_EXPORT int    lpcnet_batch_restore_device_shard(LPCNetBatch *b, int shard
 LPCNET_EXPORT int    lpcnet_batch_copy_streams_to(LPCNetBatch *from, const int *src, LPCNetBatch *to, const int *dst, int m);
 /* Without a device.  snapshot_layout: config [LPCNET_SNAP_CONFIG] = {int8 blob, analysis, encoder, kept products, PLC, PLC options, PLC widths g1, g2,
  * floats of the DRED encoder's record (0: not enabled), its max_dframes} -> out [k][3] as above, then the record length in out[3 k] where cap (ints)
- * allows; returns k.  snapshot_info: a blob's header and layout, info = {version, m, record bytes, sections k, flavour, PLC, PLC options, g1, g2,
+ * allows; returns k.  (A configuration describes a batch without the DRED decoder's record: LPCNET_SNAP_DRED_DEC has no field of its own, in a
+ * configuration or in a layout's head -- a batch's own snapshot_layout reports the section, whose size says what it holds.)  snapshot_info: a blob's header and layout, info = {version, m, record bytes, sections k, flavour, PLC, PLC options, g1, g2,
  * DRED encoder floats, its max_dframes, state_size, analysis_state_size, plc_state_size, hash low, hash high, k x {id, bytes, offset}}; returns the
  * ints written (at most cap), LPCNET_HIP_E_ARG for a NULL, truncated, wrong-magic or wrong-version buffer or one whose lengths do not add up.
  * snapshot_match: would a snapshot of config_snap restore into a batch of config_batch?  0 yes; 1 yes in the host form, which enables the missing

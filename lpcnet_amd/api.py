@@ -131,7 +131,7 @@ def _feed_args(n, count, skip, clear):
 # ---- stream snapshots (include/lpcnet_batch.h: lpcnet_batch_snapshot) ----
 SNAP_META = 10
 SNAP_SECTIONS = ("SYNTH", "DEC_VQ", "AN", "ENC_VQ", "KEEP_A", "KEEP_B", "KEEP_LPC", "KEEP_FLAG", "PLC_Q", "PLC_FEAT", "PLC_NET", "PLC_DC", "PLC_DELTA",
-                 "PLC_FEC", "PLC_FBUF", "PLC_LP", "PLC_BURG", "PLC_AN", "PLC_CTL", "DRED_ENC")
+                 "PLC_FEC", "PLC_FBUF", "PLC_LP", "PLC_BURG", "PLC_AN", "PLC_CTL", "DRED_ENC", "DRED_DEC")
 SNAP = {name: i + 1 for i, name in enumerate(SNAP_SECTIONS)}      # section ids (LPCNET_SNAP_*)
 _SNAP_LAYOUT_INTS = 92
 
@@ -291,6 +291,18 @@ def load_library():
     L.lpcnet_batch_dred_decode_packed_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_decode_packed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_info.argtypes = [vp, C.POINTER(C.c_int)]
+    L.lpcnet_batch_dred_state_enable.argtypes = [vp]
+    L.lpcnet_batch_dred_dec_state_size.argtypes = [vp]
+    L.lpcnet_batch_get_dred_dec_state.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_set_dred_dec_state.argtypes = [vp, C.c_int, _f32p]
+    L.lpcnet_batch_dred_init.argtypes = [vp, _f32p, vp]
+    L.lpcnet_batch_dred_init_device.argtypes = [vp, vp, vp, vp]
+    L.lpcnet_batch_dred_init_device_shard.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.lpcnet_batch_dred_step.argtypes = [vp, _f32p, vp, vp, _f32p]
+    L.lpcnet_batch_dred_step_device.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.lpcnet_batch_dred_step_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    L.lpcnet_batch_dred_step_packed_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lpcnet_batch_dred_step_packed_device_shard.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.lpcnet_batch_dred_flavour.argtypes = [vp]
     L.lpcnet_batch_plc_set_pred_form.argtypes = [vp, C.c_int]
     L.lpcnet_batch_plc_get_pred_form.argtypes = [vp, C.c_int]
@@ -873,6 +885,98 @@ class LPCNetBatch:
         args = (d_state_ptr, d_latents_ptr, count.ctypes.data, first.ctypes.data, take.ctypes.data, out.data_ptr(), hip_stream or None)
         rc = self.L.lpcnet_batch_dred_decode_packed_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_decode_packed_device_shard(self.p, shard, *args)
         self._chk(rc, "dred_decode_packed")
+        return out
+
+    # ---- the DRED decoder as a per-stream state (DRED_rdovae_dec_init_states / DRED_rdovae_decode_qframe per stream; include/lpcnet_batch.h) ----
+    def dred_state_enable(self):
+        """after dred_enable: allocate every stream's decoder record (dense2_state, dense4_state, dense6_state; all zero is DRED_rdovae_init_decoder).
+        reset clears it, copy_streams / copy_streams_to / the roster carry it, snapshots hold it as section DRED_DEC"""
+        self._chk(self.L.lpcnet_batch_dred_state_enable(self.p), "dred_state_enable")
+
+    def dred_dec_state_size(self) -> int:
+        """floats of one stream's three decoder states"""
+        rc = self.L.lpcnet_batch_dred_dec_state_size(self.p)
+        if rc < 0:
+            self._chk(rc, "dred_dec_state_size")
+        return rc
+
+    def get_dred_dec_state(self, stream: int) -> np.ndarray:
+        """one stream's decoder state in the reference's member order: dense2_state, dense4_state, dense6_state"""
+        out = np.zeros(self.dred_dec_state_size(), np.float32)
+        self._chk(self.L.lpcnet_batch_get_dred_dec_state(self.p, stream, out), "get_dred_dec_state")
+        return out
+
+    def set_dred_dec_state(self, stream: int, state: np.ndarray):
+        st = np.ascontiguousarray(state, np.float32)
+        assert st.shape == (self.dred_dec_state_size(),)
+        self._chk(self.L.lpcnet_batch_set_dred_dec_state(self.p, stream, st), "set_dred_dec_state")
+
+    def _dred_flags(self, which, n):
+        if which is None:
+            return None
+        which = np.ascontiguousarray(which, np.int32)
+        assert which.shape == (n,)
+        return which
+
+    def dred_init(self, state: np.ndarray, which=None):
+        """state (n, state_dim) float32: dred_rdovae_dec_init_states into the record of every active stream with which[s] != 0 (None: every active
+        stream); the other records keep their bits"""
+        sd = self.dred_info()[2]
+        st = np.ascontiguousarray(state, np.float32)
+        assert st.shape == (self.n, sd)
+        which = self._dred_flags(which, self.n)
+        self._chk(self.L.lpcnet_batch_dred_init(self.p, st.reshape(-1), None if which is None else which.ctypes.data), "dred_init")
+
+    def dred_init_device(self, d_state_ptr: int, which=None, hip_stream: int = 0, shard=None):
+        """enqueue only: a device pointer laid out as dred_init's state; which stays a host array (of the shard's streams with shard=k) or None, the
+        uniform form, which a capturing stream accepts"""
+        n = self.n if shard is None else self.shards[shard][1]
+        which = self._dred_flags(which, n)
+        args = (d_state_ptr, None if which is None else which.ctypes.data, hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_init_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_init_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_init_device")
+
+    def dred_step(self, latents: np.ndarray, start, count, features: np.ndarray | None = None) -> np.ndarray:
+        """latents (n, max_latents, latent_dim) float32, start [n], count [n] -> features (n, 4 * max_latents, 20): stream s runs decode_qframe on
+        latents start[s] .. start[s] + count[s] - 1 from its record and writes rows [4 * start[s], 4 * (start[s] + count[s])); its other rows keep
+        what `features` held (zeros without it)"""
+        ml, ld, _ = self.dred_info()
+        la = np.ascontiguousarray(latents, np.float32)
+        start, count = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(count, np.int32)
+        assert la.shape == (self.n, ml, ld) and start.shape == count.shape == (self.n,)
+        out = np.zeros((self.n, 4 * ml, 20), np.float32) if features is None else features
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (self.n, 4 * ml, 20)
+        self._chk(self.L.lpcnet_batch_dred_step(self.p, la.reshape(-1), start.ctypes.data, count.ctypes.data, out.reshape(-1)), "dred_step")
+        return out
+
+    def dred_step_device(self, d_latents_ptr: int, start, count, d_features_ptr: int, hip_stream: int = 0, shard=None, first_latent: int = 0, n_latents: int = 0):
+        """enqueue only: device pointers laid out as dred_step's arrays; start / count stay host arrays (of the shard's streams with shard=k).
+        start=None, count=None: the uniform form -- latents first_latent .. first_latent + n_latents - 1 of every active stream -- which depends
+        on nothing on the host and which a capturing stream accepts"""
+        n = self.n if shard is None else self.shards[shard][1]
+        assert (start is None) == (count is None)
+        if start is not None:
+            start, count = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(count, np.int32)
+            assert start.shape == count.shape == (n,)
+        args = (d_latents_ptr, None if start is None else start.ctypes.data, None if count is None else count.ctypes.data, int(first_latent), int(n_latents),
+                d_features_ptr, hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_step_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_step_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_step_device")
+
+    def dred_step_packed(self, d_latents_ptr: int, start, count, first, take, hip_stream: int = 0, shard=None):
+        """enqueue only: step as dred_step_device does and write rows first[s] .. first[s] + take[s] - 1 of every stream -- the stream's own row
+        numbers, inside the rows this call decodes -- the oldest frame first, into one packed [sum(take)][20] float32 array on the device: a torch
+        tensor, returned, whose data_ptr() plc_fec_feed_device takes with count = take"""
+        import torch
+        n = self.n if shard is None else self.shards[shard][1]
+        start, count, first, take = (np.ascontiguousarray(x, np.int32) for x in (start, count, first, take))
+        assert start.shape == count.shape == first.shape == take.shape == (n,)
+        device = self.shards[0 if shard is None else shard][2]
+        rows = int(take.clip(min=0).sum())                # (a negative take is the C call's to refuse)
+        out = torch.empty((max(rows, 1), 20), dtype=torch.float32, device="cuda:%d" % device)[:rows]
+        args = (d_latents_ptr, start.ctypes.data, count.ctypes.data, first.ctypes.data, take.ctypes.data, out.data_ptr(), hip_stream or None)
+        rc = self.L.lpcnet_batch_dred_step_packed_device(self.p, *args) if shard is None else self.L.lpcnet_batch_dred_step_packed_device_shard(self.p, shard, *args)
+        self._chk(rc, "dred_step_packed")
         return out
 
     # ---- DRED encoder (DRED_rdovae_encode_dframe per stream and double frame; include/lpcnet_batch.h) ----

@@ -446,6 +446,107 @@ int lpcnet_batch_dred_decode_packed_device(LPCNetBatch *b, const float *d_state,
     return lpcnet_batch_dred_decode_packed_device_shard(b, 0, d_state, d_latents, count, first, take, d_packed, hip_stream);
 }
 
+/* ---- the DRED decoder as a per-stream state (DRED_rdovae_dec_init_states / DRED_rdovae_decode_qframe per stream; include/lpcnet_batch.h) ---- */
+#define NEED_DRED_STATE_ON(b) do { NEED_DRED_ON(b); if (!lpcn_batch_dev_dred_state_enabled((b)->sh[0].dev)) { set_err("the DRED decoder's per-stream state is not enabled on this batch (lpcnet_batch_dred_state_enable)"); return LPCN_E_MODEL; } } while (0)
+int lpcnet_batch_dred_state_enable(LPCNetBatch *b) { NEED_DRED_ON(b); EACH_SHARD(lpcn_batch_dev_dred_state_enable(s->dev)); }
+int lpcnet_batch_dred_dec_state_size(const LPCNetBatch *b)
+{
+    NEED_DRED_STATE_ON(b);
+    return lpcn_batch_dev_dred_state_enabled(b->sh[0].dev);
+}
+int lpcnet_batch_get_dred_dec_state(LPCNetBatch *b, int stream, float *out)
+{
+    NEED_DRED_STATE_ON(b);
+    if (!out) { set_err("lpcnet_batch_get_dred_dec_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_dred_get_dec_state(s->dev, i, out));
+}
+int lpcnet_batch_set_dred_dec_state(LPCNetBatch *b, int stream, const float *in)
+{
+    NEED_DRED_STATE_ON(b);
+    if (!in) { set_err("lpcnet_batch_set_dred_dec_state: bad arguments"); return LPCN_E_ARG; }
+    SHARD_OF(s, i, b, stream);
+    FWD(lpcn_batch_dev_dred_set_dec_state(s->dev, i, in));
+}
+typedef struct { LPCNetBatch *b; const float *state, *latents; const int *which, *start, *count; float *features; int max_latents, latent_dim, state_dim; } dred_stream_args;
+static int dred_init_shard(void *args, int k)
+{
+    const dred_stream_args *a = (const dred_stream_args *)args;
+    const size_t f = (size_t)a->b->at[k].first;
+    return lpcn_batch_dev_dred_init_host(a->b->sh[k].dev, a->state + f * a->state_dim, a->which ? a->which + f : NULL);
+}
+static int dred_step_shard(void *args, int k)
+{
+    const dred_stream_args *a = (const dred_stream_args *)args;
+    const size_t f = (size_t)a->b->at[k].first;
+    return lpcn_batch_dev_dred_step_host(a->b->sh[k].dev, a->latents + f * a->max_latents * a->latent_dim, a->start + f, a->count + f,
+                                         a->features + f * LPCN_DRED_FRAMES * a->max_latents * LPCN_NB_FEAT);
+}
+int lpcnet_batch_dred_init(LPCNetBatch *b, const float *state, const int *which)
+{
+    NEED_DRED_STATE_ON(b);
+    if (!state) { set_err("lpcnet_batch_dred_init: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard writes) */
+        const int rc = lpcn_batch_dev_dred_init_check(b->sh[k].dev, which ? which + b->at[k].first : NULL);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    dred_stream_args a = {b, state, NULL, which, NULL, NULL, NULL, 0, 0, 0};
+    lpcn_batch_dev_dred_dims(b->sh[0].dev, &a.latent_dim, &a.state_dim);
+    return run_shards(b, dred_init_shard, &a);
+}
+int lpcnet_batch_dred_step(LPCNetBatch *b, const float *latents, const int *start, const int *count, float *features)
+{
+    NEED_DRED_STATE_ON(b);
+    if (!latents || !start || !count || !features) { set_err("lpcnet_batch_dred_step: bad arguments"); return LPCN_E_ARG; }
+    for (int k = 0; k < b->n_shards; k++) {          /* (checked for the whole batch before any shard writes or advances) */
+        const int rc = lpcn_batch_dev_dred_step_check(b->sh[k].dev, start + b->at[k].first, count + b->at[k].first, 0, 0, NULL, NULL, NULL);
+        if (rc) { take_engine_err(); return rc; }
+    }
+    dred_stream_args a = {b, NULL, latents, NULL, start, count, features, lpcn_batch_dev_dred_enabled(b->sh[0].dev), 0, 0};
+    lpcn_batch_dev_dred_dims(b->sh[0].dev, &a.latent_dim, &a.state_dim);
+    return run_shards(b, dred_step_shard, &a);
+}
+int lpcnet_batch_dred_init_device_shard(LPCNetBatch *b, int shard, const float *d_state, const int *which, void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("lpcnet_batch_dred_init_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_init(b->sh[shard].dev, d_state, which, hip_stream));
+}
+int lpcnet_batch_dred_init_device(LPCNetBatch *b, const float *d_state, const int *which, void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_init_device");
+    return lpcnet_batch_dred_init_device_shard(b, 0, d_state, which, hip_stream);
+}
+int lpcnet_batch_dred_step_device_shard(LPCNetBatch *b, int shard, const float *d_latents, const int *start, const int *count, int first_latent, int n_latents,
+                                        float *d_features, void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    if (shard < 0 || shard >= b->n_shards) { set_err("lpcnet_batch_dred_step_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_step(b->sh[shard].dev, d_latents, start, count, first_latent, n_latents, d_features, hip_stream));
+}
+int lpcnet_batch_dred_step_device(LPCNetBatch *b, const float *d_latents, const int *start, const int *count, int first_latent, int n_latents, float *d_features,
+                                  void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_step_device");
+    return lpcnet_batch_dred_step_device_shard(b, 0, d_latents, start, count, first_latent, n_latents, d_features, hip_stream);
+}
+int lpcnet_batch_dred_step_packed_device_shard(LPCNetBatch *b, int shard, const float *d_latents, const int *start, const int *count, const int *first,
+                                               const int *take, float *d_packed, void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    if (shard < 0 || shard >= b->n_shards || !start || !count || !first || !take) { set_err("lpcnet_batch_dred_step_packed_device: bad arguments"); return LPCN_E_ARG; }
+    FWD(lpcn_batch_dev_dred_step_packed(b->sh[shard].dev, d_latents, start, count, first, take, d_packed, hip_stream));
+}
+int lpcnet_batch_dred_step_packed_device(LPCNetBatch *b, const float *d_latents, const int *start, const int *count, const int *first, const int *take,
+                                         float *d_packed, void *hip_stream)
+{
+    NEED_DRED_STATE_ON(b);
+    NEED_ONE_SHARD(b, "lpcnet_batch_dred_step_packed_device");
+    return lpcnet_batch_dred_step_packed_device_shard(b, 0, d_latents, start, count, first, take, d_packed, hip_stream);
+}
+
 /* ---- DRED encoder (DRED_rdovae_encode_dframe per stream and double frame; include/lpcnet_batch.h) ---- */
 #define NEED_DENC_ON(b) do { NEED_MODEL(b); if (!lpcn_batch_dev_dred_enc_enabled((b)->sh[0].dev)) { set_err("the DRED encoder is not enabled on this batch (lpcnet_batch_dred_enc_enable)"); return LPCN_E_MODEL; } } while (0)
 int lpcnet_batch_dred_enc_enable(LPCNetBatch *b, int max_dframes) { NEED_MODEL(b); EACH_SHARD(lpcn_batch_dev_dred_enc_enable(s->dev, max_dframes)); }

@@ -337,4 +337,197 @@ __global__ __launch_bounds__(DRED_FAST_THREADS) void dred_fast_kernel(const Dred
     }
 }
 
+// ---- the decoder as a per-stream state in FAST arithmetic (dred_stream_kernel of dred_kernels.hip.h is the PARITY one): the tiles,
+// the roles, the chains and the barrier discipline of dred_fast_kernel, with the three LDS state buffers filled from and drained to the streams'
+// records.  Arguments as dred_stream_kernel's.  A record holds a layer's own width: the pad rows of a partial 32-row tile are zero on the way in and
+// stay here on the way out.  What dred_fast_kernel leaves to chance -- a stream whose latents are through goes on advancing its column -- matters
+// here: a GRU's new state is written for the columns whose own latents still run and for no other.
+template <int T, int U>
+__global__ __launch_bounds__(DRED_FAST_THREADS) void dred_stream_fast_kernel(const DredNet *P, const DredFastImage *img, int n, int max_latents, int init,
+                                                                              const int *rec, int u_start, int u_count, const float *state,
+                                                                              const float *latents, float *features, float *dstate, int rec_floats)
+{
+    static_assert(T == 32 || T == 16, "32 streams on the 32x32x2 MFMA, 16 on the 16x16x4");
+    using Acc = DredFastAcc<T>;
+    constexpr int KS = 64 / T, NJ = Acc::NJ, NE = Acc::NE;
+    extern __shared__ float4 dred_fast_lds[];
+    __shared__ int cnt[T], beg[T];
+    const int t = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, col = lane % T;
+    const int latent_dim = P->latent_dim, state_dim = P->state_dim;
+    float *const h0 = (float *)dred_fast_lds, *const h1 = h0 + T * dred_fast_pad(P->step[1].n_out), *const h2 = h1 + T * dred_fast_pad(P->step[3].n_out);
+    float *const act = h2 + T * dred_fast_pad(P->step[5].n_out);
+    const auto h = [&](int g) { return g == 0 ? h0 : g == 1 ? h1 : h2; };
+    const int s0 = blockIdx.x * T;
+    if (t < T) {
+        int c = 0, b = 0;
+        if (s0 + t < n) {
+            const int *q = rec ? rec + (size_t)(s0 + t) * DRED_SREC : nullptr;
+            c = init ? (q ? q[0] != 0 : 1) : (q ? q[2] : u_count);
+            b = q ? q[1] : u_start;
+        }
+        cnt[t] = c; beg[t] = b;
+    }
+    __syncthreads();
+    int maxc = 0;
+    for (int a = 0; a < T; ++a) maxc = cnt[a] > maxc ? cnt[a] : maxc;
+    if (maxc == 0) return;                  // (the whole workgroup)
+    const bool layer_wave = wave < DRED_FAST_LAYER_WAVES;
+    const int ft = wave - DRED_FAST_LAYER_WAVES;                       // dec_final's tile of a final wave
+    const bool final_wave = ft >= 0 && ft < DRED_FAST_FINAL_WAVES;
+    const int i0 = 32 * wave;
+    // the records of the streams that took part, from the state buffers: a layer's own rows
+    const auto store_records = [&]() {
+        for (int g = 0, at = 0; g < 3; ++g) {
+            const int w = P->step[2 * g + 1].n_out;
+            for (int e = t; e < T * w; e += DRED_FAST_THREADS) {
+                const int j = e / T, a = e % T;
+                if (cnt[a] > 0) dstate[(size_t)(s0 + a) * rec_floats + at + j] = h(g)[e];
+            }
+            at += w;
+        }
+    };
+
+    if (init) {
+        for (int e = t; e < T * state_dim; e += DRED_FAST_THREADS) {
+            const int j = e / T, a = e % T;
+            act[e] = cnt[a] > 0 ? state[(size_t)(s0 + a) * state_dim + j] : 0.f;
+        }
+        __syncthreads();
+        // dred_rdovae_dec_init_states (src/dred_rdovae_dec.c:37-47): the GRU states
+        if (layer_wave) {
+#pragma unroll 1
+            for (int g = 0; g < 3; ++g) {
+                const DredStep *q = &P->init[g];
+                if (i0 < q->n_out) {
+                    Acc acc = dred_fast_dense<T, U>(q->b, Acc{}, q->w, q->n_out, i0, q->n_out, q->n_in, act);
+#pragma unroll
+                    for (int e = 0, r0 = dred_fast_row0<T>(); e < NE; ++e) h(g)[(i0 + dred_fast_row<T>(e, r0)) * T + col] = dred_fast_tanh(acc.get(e));
+                }
+            }
+        }
+        __syncthreads();
+        store_records();
+        return;
+    }
+    for (int g = 0, at = 0; g < 3; ++g) {
+        const int w = P->step[2 * g + 1].n_out;
+        for (int e = t; e < T * dred_fast_pad(w); e += DRED_FAST_THREADS) {
+            const int j = e / T, a = e % T;
+            h(g)[e] = j < w && cnt[a] > 0 ? dstate[(size_t)(s0 + a) * rec_floats + at + j] : 0.f;
+        }
+        at += w;
+    }
+    __syncthreads();                        // the GRU states are in LDS
+    // latent l of every stream's range into the activation buffer, by the whole workgroup
+    const auto load_latent = [&](int l) {
+        int tl = t;                         // (opaque: the addresses of a latent's loads are formed per latent, not held in registers)
+        asm volatile("" : "+v"(tl));
+        for (int e = tl; e < T * latent_dim; e += DRED_FAST_THREADS) {
+            const int j = e / T, a = e % T;
+            act[e] = l < cnt[a] ? latents[((size_t)(s0 + a) * max_latents + beg[a] + l) * latent_dim + j] : 0.f;
+        }
+        __syncthreads();
+    };
+    // The two roles run the latent loop apart, as in dred_fast_kernel, and meet at the same barriers: per latent ONE in load_latent, TWO per layer (16
+    // in all) and ONE at the latent's end.  A barrier added or dropped on one side alone hangs the workgroup.
+    if (layer_wave) {
+#pragma unroll 1
+        for (int l = 0; l < maxc; ++l) {
+            load_latent(l);                 // (1 barrier)
+#pragma unroll 1
+            for (int k = 0; k < 8; ++k) {
+                int tk = threadIdx.x;       // (opaque: what a layer derives from the lane is formed per layer, not held in registers across the loops)
+                asm volatile("" : "+v"(tk));
+                const int lane = tk & 63, col = lane % T, kq = lane / T;
+                const DredStep *q = &P->step[k];
+                const int g = k >> 1;       // the GRU of step 1, 3, 5; the state a dense layer 2, 4, 6 reads is GRU g - 1's
+                const int n_out = q->n_out;
+                float *out = q->gru ? h(g) : act;
+                const float *x = k == 0 || q->gru || k == 7 ? act : h(g - 1);
+                Acc res = {};
+                const bool mine = i0 < n_out;
+                if (mine && !q->gru) {
+                    res = dred_fast_dense<T, U>(q->b, res, q->w, n_out, i0, n_out, q->n_in, x);
+#pragma unroll
+                    for (int e = 0; e < NE; ++e) res.set(e, dred_fast_tanh(res.get(e)));
+                } else if (mine) {
+                    // units i0 .. i0 + 31: gate by gate, the input part over the tile's union blocks, the recurrent part over the state
+                    const int N = n_out;
+                    const DredFastGru im = img->gru[g];
+                    const int *start = im.start + 3 * wave;
+                    float *hg = out;
+                    Acc z = {}, r = {};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        asm volatile("" ::: "memory");      // (one chain at a time: two chains' loads in flight together cost their registers)
+                        const int b0 = start[c], nb = start[c + 1] - b0;
+                        const int *pos = dred_fast_uniform(im.pos + b0);
+                        unsigned bidx[NJ], woff[NJ], wlo[NJ];
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+                            const int i = T * j + col;      // the lane's row of row tile j among the wave's 32
+                            bidx[j] = min(i0 + i, N - 1); woff[j] = 32 * kq + i; wlo[j] = i;
+                        }
+                        const Acc in = dred_fast_chain<T, U>(true, Acc{}, q->b + c * N, bidx, im.w + (size_t)b0 * 128, woff, wlo, 32 * KS, 4 * nb, act + col, q->n_in - 1,
+                                                             [&](int s) { return pos[(KS * s) >> 2] + ((KS * s) & 3); });
+                        asm volatile("" ::: "memory");
+                        const Acc rc = dred_fast_dense<T, U>(q->b + 3 * N + c * N, Acc{}, q->rec + c * N, 3 * N, i0, N, N, hg);
+#pragma unroll
+                        for (int e = 0, r0 = dred_fast_row0<T>(); e < NE; ++e) {
+                            if (c == 0) z.set(e, dred_fast_sigmoid(in.get(e) + rc.get(e)));
+                            else if (c == 1) r.set(e, dred_fast_sigmoid(in.get(e) + rc.get(e)));
+                            else {
+                                const float old = hg[(i0 + dred_fast_row<T>(e, r0)) * T + col];
+                                res.set(e, __builtin_fmaf(z.get(e), old, (1.f - z.get(e)) * dred_fast_tanh(__builtin_fmaf(rc.get(e), r.get(e), in.get(e)))));
+                            }
+                        }
+                    }
+                }
+                __syncthreads();            // (2 k + 1) every reader of what layer k overwrites is through
+                if (mine && (!q->gru || l < cnt[col])) {      // (a stream whose own latents are through keeps its state)
+#pragma unroll
+                    for (int e = 0, r0 = dred_fast_row0<T>(); e < NE; ++e) out[(i0 + dred_fast_row<T>(e, r0)) * T + col] = res.get(e);
+                }
+                __syncthreads();            // (2 k + 2) layer k's output is written
+            }
+            __syncthreads();                // (1) dec_final has read the last layer's output: the next latent may overwrite it
+        }
+    } else {
+        const int my_cnt = cnt[col], my_beg = beg[col];
+#pragma unroll 1
+        for (int l = 0; l < maxc; ++l) {
+            load_latent(l);                 // (1 barrier)
+            Acc facc = {};
+            int off = 0;                    // of layer k among dec_final's inputs
+#pragma unroll 1
+            for (int k = 0; k < 8; ++k) {
+                __syncthreads();            // (2 k + 1)
+                __syncthreads();            // (2 k + 2) layer k's output is written
+                const DredStep *q = &P->step[k];
+                if (final_wave) facc = dred_fast_dense<T, U>(k ? nullptr : P->final_b, facc, P->final_w + (size_t)off * LPCN_DRED_OUT, LPCN_DRED_OUT, 32 * ft, LPCN_DRED_OUT, q->n_out, q->gru ? h(k >> 1) : act);
+                off += q->n_out;
+            }
+            if (final_wave && l < my_cnt) {
+                // the lane's outputs are runs of four, and a run lies in one 20-float row: one address per run
+                int first = -1, take = 0, prow = 0;
+                if (rec) { const int *q = rec + (size_t)(s0 + col) * DRED_SREC; first = q[3]; take = q[4]; prow = q[5]; }
+                const int i00 = 32 * ft + dred_fast_row0<T>();
+#pragma unroll
+                for (int run = 0; run < NE / 4; ++run) {
+                    const int i = i00 + Acc::RUN * run, r = LPCN_DRED_FRAMES * (my_beg + l) + i / LPCN_NB_FEAT;
+                    const bool ok = i < LPCN_DRED_OUT && (first < 0 || (r >= first && r < first + take));
+                    const size_t row = first < 0 ? (size_t)(s0 + col) * LPCN_DRED_FRAMES * max_latents + r : (size_t)prow + (first + take - 1 - r);
+                    if (ok) {
+                        float *dst = features + row * LPCN_NB_FEAT + i % LPCN_NB_FEAT;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) dst[e] = facc.get(4 * run + e);
+                    }
+                }
+            }
+            __syncthreads();                // (1) the latent's end
+        }
+    }
+    store_records();                        // (behind the last latent's closing barrier)
+}
+
 }  // namespace lpcn

@@ -498,7 +498,7 @@ extern "C" int lpcn_batch_dev_reset(lpcn_batch_dev *b, int first, int count)
         HIP_TRY(hipMemsetAsync(b->denc->state + (size_t)first * b->denc->rec, 0, sizeof(float) * (size_t)count * b->denc->rec, b->e->stream));
         HIP_TRY(hipStreamSynchronize(b->e->stream));
     }
-    return 0;
+    return dred_state_reset(b, first, count);      // (DRED_rdovae_init_decoder, where the batch keeps the decoder's states)
 }
 
 extern "C" int lpcn_batch_dev_get_state(lpcn_batch_dev *b, int s, lpcn_stream_state *host) { return stream_rec(b, s, b->d_state, 1, host, nullptr); }

@@ -280,7 +280,8 @@ struct lpcn_plc_host {
     DevBuf<float> d_feed_src;                       //   ... and the host-pointer call's packed vectors, grown to the largest call
 };
 
-// DRED decoding of a batch (lpcn_batch_dev_dred_enable): no per-stream state, only the scratch of a call
+// DRED decoding of a batch (lpcn_batch_dev_dred_enable): the scratch of a call, and -- once lpcn_batch_dev_dred_state_enable has run -- every
+// stream's decoder state for the init / step pair
 struct lpcn_dred_host {
     int max_latents = 0, cus = 0;                   // (cus: the device's compute units, for the form table)
     int form = 0;                                   // streams per workgroup pinned by lpcn_batch_dev_dred_set_form (0: the table's choice)
@@ -291,6 +292,12 @@ struct lpcn_dred_host {
     bool rec_pending = false;
     DevBuf<float> d_state, d_latents, d_feat;       // staging of the host-pointer call
     PinBuf h_feat;                                  //   ... whose output comes down whole and goes to the caller row by row (rows past a stream's count stay)
+    size_t st_rec = 0;                              // floats of a stream's decoder record (dred_kernels.hip.h: dred_state_rec_floats); 0: not enabled
+    DevBuf<float> st;                               // [n][st_rec]: dense2_state, dense4_state, dense6_state, padded to 16 bytes
+    DevBuf<int> d_srec;                             // an init's or a step's per-stream records (DRED_SREC) ...
+    PinBuf h_srec;                                  // ... their pinned source ...
+    Event ev_srec;                                  // ... and "the previous call's have left it"
+    bool srec_pending = false;
 };
 
 // DRED encoding of a batch (lpcn_batch_dev_dred_enc_enable): every stream's state record (rdovae_enc_kernels.hip.h) and the scratch of a call
@@ -392,6 +399,7 @@ void each_stream_array(lpcn_batch_dev *b, F fn)
         fn(p->lp, (size_t)LPCN_FRAME_SIZE); fn(p->burg, (size_t)2 * LPCN_NB_BANDS); fn(p->an, (size_t)LPCN_AN_NB_FEATURES);
     }
     if (lpcn_denc_host *p = b->denc.get()) fn(p->state, p->rec);
+    if (lpcn_dred_host *p = b->dred.get()) if (p->st) fn(p->st, p->st_rec);
 }
 int stream_list_buffers(lpcn_batch_dev *b);      // engine_roster.hip: d_pairs / h_pairs / ev_pairs, on first use
 
@@ -453,6 +461,7 @@ int group_alloc(lpcn_batch_dev *b);
 int dred_engine_init(lpcn_engine *e, const lpcn_model_host *m);
 // engine_dred.hip: a FAST image packed from `F` (dred_fast_pack.h) and uploaded; `what` names the half in the messages ("DRED FAST", "DRED encoder FAST")
 int dred_fast_image_upload(lpcn_engine *e, const DredFastHost &F, const lpcn::DredFastImage **dst, const char *what);
+int dred_state_reset(lpcn_batch_dev *b, int first, int count);      // engine_dred.hip: the decoder's per-stream records of a range, zeroed (lpcn_batch_dev_reset)
 // engine_dred_enc.hip: the same for the blob's DRED encoder
 int denc_engine_init(lpcn_engine *e, const lpcn_model_host *m);
 // engine_codec.hip (analysis_kernels.hip.h, encode_kernels.hip.h)

@@ -1,6 +1,6 @@
 // Device runtime, DRED unit: the decoder's upload, a batch's scratch and the one launch that decodes every active stream's latent chain
-// (dred_kernels.hip.h).  The call keeps nothing per stream between calls, so resets, stream copies and state snapshots do not
-// know about it.
+// (dred_kernels.hip.h).  That call keeps nothing per stream between calls.  The init / step pair at the end of the file does
+// (DESIGN.md §4.6b): its record is one of the batch's per-stream arrays, which resets, stream copies and snapshots carry.
 #include "engine_core.h"
 #include "dred_kernels.hip.h"
 #include "dred_fast_kernels.hip.h"
@@ -356,5 +356,256 @@ extern "C" int lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *s
     HIP_TRY(hipStreamSynchronize(st));
     for (size_t s = 0; s < n; ++s)
         memcpy(features + s * per_f, (const float *)p->h_feat.p + s * per_f, sizeof(float) * LPCN_DRED_FRAMES * LPCN_NB_FEAT * (size_t)count[s]);
+    return 0;
+}
+
+// ---- the decoder as a per-stream state (DRED_rdovae_dec_init_states / DRED_rdovae_decode_qframe; dred_stream_kernel, dred_stream_fast_kernel;
+// DESIGN.md §4.6b).  The record is float in every flavour and mode; all zero is DRED_rdovae_init_decoder.
+static int dred_state_floats(const lpcn_engine *e) { return e->is_int8 ? lpcn::dred_state_floats(e->dredq) : lpcn::dred_state_floats(e->dred); }
+template <int S>
+static const void *dred_stream_kernel_of(const lpcn_engine *e)
+{
+    return e->is_int8 ? (const void *)lpcn::dred_stream_kernel<S, true> : (const void *)lpcn::dred_stream_kernel<S, false>;
+}
+// the dynamic-LDS limits are raised here, not at a launch: a launch sets nothing, so the uniform forms can be captured
+template <int S>
+static int dred_stream_prepare(const lpcn_engine *e)
+{
+    if (!dred_form_fits(e, S)) return 0;
+    HIP_TRY(hipFuncSetAttribute(dred_stream_kernel_of<S>(e), hipFuncAttributeMaxDynamicSharedMemorySize, dred_lds_bytes(e, S)));
+    return 0;
+}
+template <int T, int U>
+static int dred_stream_fast_prepare(const lpcn_engine *e)
+{
+    const size_t lds = (size_t)lpcn::dred_fast_lds_floats(e->dred, T) * sizeof(float);
+    if (lds > 160 * 1024 - 1024) return 0;      // (dred_set_fast refuses that tile)
+    HIP_TRY(hipFuncSetAttribute((const void *)lpcn::dred_stream_fast_kernel<T, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return 0;
+}
+
+extern "C" int lpcn_batch_dev_dred_state_enabled(const lpcn_batch_dev *b) { return b->dred && b->dred->st ? dred_state_floats(b->e) : 0; }
+
+extern "C" int lpcn_batch_dev_dred_state_enable(lpcn_batch_dev *b)
+{
+    NEED_DRED(b);
+    lpcn_engine *e = b->e;
+    lpcn_dred_host *p = b->dred.get();
+    if (p->st) return 0;
+    DeviceGuard guard(e->device);
+    int rc = wait_all(b);
+    if (rc || (rc = dred_stream_prepare<1>(e)) || (rc = dred_stream_prepare<2>(e)) || (rc = dred_stream_prepare<4>(e)) || (rc = dred_stream_prepare<8>(e))) return rc;
+    if (!e->is_int8 && ((rc = dred_stream_fast_prepare<16, 16>(e)) || (rc = dred_stream_fast_prepare<32, 8>(e)))) return rc;
+    const size_t per = (size_t)(e->is_int8 ? lpcn::dred_state_rec_floats(e->dredq) : lpcn::dred_state_rec_floats(e->dred));
+    DevBuf<float> st;
+    if ((rc = st.alloc(per * b->n)) || (rc = p->d_srec.alloc((size_t)lpcn::DRED_SREC * b->n)) || (rc = p->h_srec.reserve(sizeof(int) * lpcn::DRED_SREC * (size_t)b->n))) return rc;
+    if (!p->ev_srec.e && hipEventCreateWithFlags(&p->ev_srec.e, hipEventDisableTiming) != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED: hipEventCreate failed"); return LPCN_E_HIP; }
+    HIP_TRY(hipMemsetAsync(st, 0, sizeof(float) * per * b->n, e->stream));      // (DRED_rdovae_init_decoder; done before the call returns: the first
+    HIP_TRY(hipStreamSynchronize(e->stream));                                   //  init may go to any stream)
+    p->st.p = st.p; p->st.cap = st.cap; st.p = nullptr; st.cap = 0;
+    p->st_rec = per;
+    return 0;
+}
+#define NEED_DRED_STATE(b) do { NEED_DRED(b); if (!(b)->dred->st) { snprintf(g_err, sizeof(g_err), "the DRED decoder's per-stream state is not enabled on this batch (lpcnet_batch_dred_state_enable)"); return LPCN_E_MODEL; } } while (0)
+
+// lpcn_batch_dev_reset's part: the records of [first, first + count) as DRED_rdovae_init_decoder leaves them
+int dred_state_reset(lpcn_batch_dev *b, int first, int count)
+{
+    lpcn_dred_host *p = b->dred.get();
+    if (!count || !p || !p->st) return 0;
+    HIP_TRY(hipMemsetAsync(p->st + (size_t)first * p->st_rec, 0, sizeof(float) * (size_t)count * p->st_rec, b->e->stream));
+    HIP_TRY(hipStreamSynchronize(b->e->stream));
+    return 0;
+}
+
+// one stream's three states in the reference's member order: the record without its padding
+extern "C" int lpcn_batch_dev_dred_get_dec_state(lpcn_batch_dev *b, int s, float *out)
+{
+    NEED_DRED_STATE(b);
+    lpcn_dred_host *p = b->dred.get();
+    if (!out) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    std::vector<float> r(p->st_rec);
+    const int rc = stream_rec(b, s, p->st, p->st_rec, r.data(), nullptr);
+    if (!rc) memcpy(out, r.data(), sizeof(float) * (size_t)dred_state_floats(b->e));
+    return rc;
+}
+extern "C" int lpcn_batch_dev_dred_set_dec_state(lpcn_batch_dev *b, int s, const float *in)
+{
+    NEED_DRED_STATE(b);
+    lpcn_dred_host *p = b->dred.get();
+    if (!in) { snprintf(g_err, sizeof(g_err), "stream index"); return LPCN_E_ARG; }
+    std::vector<float> r(p->st_rec, 0.f);
+    memcpy(r.data(), in, sizeof(float) * (size_t)dred_state_floats(b->e));
+    return stream_rec(b, s, p->st, p->st_rec, nullptr, r.data());
+}
+
+// which == NULL: every active stream; else no flag beyond the active prefix
+extern "C" int lpcn_batch_dev_dred_init_check(const lpcn_batch_dev *b, const int *which)
+{
+    NEED_DRED_STATE(b);
+    for (int s = b->active; which && s < b->n; ++s)
+        if (which[s]) { snprintf(g_err, sizeof(g_err), "DRED init: stream %d is not active and is selected", s); return LPCN_E_ARG; }
+    return 0;
+}
+// start == count == NULL: the uniform form, latents u_start .. u_start + u_count - 1 of every active stream.  Else per stream, zero counts beyond the
+// active prefix; the packed form's first / take in the stream's own row numbers, inside the rows this call decodes
+extern "C" int lpcn_batch_dev_dred_step_check(const lpcn_batch_dev *b, const int *start, const int *count, int u_start, int u_count, const int *first,
+                                              const int *take, long long *rows)
+{
+    NEED_DRED_STATE(b);
+    const int ml = b->dred->max_latents;
+    if ((start != nullptr) != (count != nullptr) || (first != nullptr) != (take != nullptr) || (first && !count)) { snprintf(g_err, sizeof(g_err), "bad DRED step arguments"); return LPCN_E_ARG; }
+    if (!count) {
+        if (u_start < 0 || u_count < 0 || (long long)u_start + u_count > ml) { snprintf(g_err, sizeof(g_err), "DRED step: latents %d .. %d + %d outside 0 .. %d", u_start, u_start, u_count, ml); return LPCN_E_ARG; }
+        if (rows) *rows = 0;
+        return 0;
+    }
+    long long total = 0;
+    for (int s = 0; s < b->n; ++s) {
+        if (start[s] < 0 || count[s] < 0 || (long long)start[s] + count[s] > ml) { snprintf(g_err, sizeof(g_err), "DRED step: stream %d has latents outside 0 .. %d (start %d, count %d)", s, ml, start[s], count[s]); return LPCN_E_ARG; }
+        if (s >= b->active && count[s] != 0) { snprintf(g_err, sizeof(g_err), "DRED step: stream %d is not active and has a count", s); return LPCN_E_ARG; }
+        if (first && s < b->active) {
+            const long long lo = (long long)LPCN_DRED_FRAMES * start[s], hi = lo + (long long)LPCN_DRED_FRAMES * count[s];
+            if (take[s] < 0 || (take[s] > 0 && (first[s] < lo || (long long)first[s] + take[s] > hi)) || (take[s] == 0 && first[s] < 0)) {
+                snprintf(g_err, sizeof(g_err), "DRED step: stream %d selects rows outside the %lld .. %lld this call decodes", s, lo, hi - 1);
+                return LPCN_E_ARG;
+            }
+            total += take[s];
+        }
+    }
+    if (total > 0x7fffffffLL / LPCN_NB_FEAT) { snprintf(g_err, sizeof(g_err), "DRED step: too many packed rows"); return LPCN_E_ARG; }
+    if (rows) *rows = total;
+    return 0;
+}
+
+// one launch of the stream kernel in the batch's arithmetic, form and tile.  d_rec == nullptr: the uniform form
+static int dred_stream_launch(lpcn_batch_dev *b, hipStream_t st, int init, const int *d_rec, int u_start, int u_count, const float *d_state, const float *d_latents,
+                              float *d_out)
+{
+    lpcn_engine *e = b->e;
+    lpcn_dred_host *p = b->dred.get();
+    const int n = b->active, ml = p->max_latents, rf = (int)p->st_rec;
+    float *ds = p->st;
+    if (p->fast) {
+        if (dred_fast_tile(p, n) == 16)
+            hipLaunchKernelGGL((lpcn::dred_stream_fast_kernel<16, 16>), dim3((n + 15) / 16), dim3(lpcn::DRED_FAST_THREADS), lpcn::dred_fast_lds_floats(e->dred, 16) * (int)sizeof(float), st,
+                               e->d_dred, e->d_dred_fast, n, ml, init, d_rec, u_start, u_count, d_state, d_latents, d_out, ds, rf);
+        else
+            hipLaunchKernelGGL((lpcn::dred_stream_fast_kernel<32, 8>), dim3((n + 31) / 32), dim3(lpcn::DRED_FAST_THREADS), lpcn::dred_fast_lds_floats(e->dred, 32) * (int)sizeof(float), st,
+                               e->d_dred, e->d_dred_fast, n, ml, init, d_rec, u_start, u_count, d_state, d_latents, d_out, ds, rf);
+    } else {
+        const int S = lpcn_batch_dev_dred_form(b, n);
+        const int grid = (n + S - 1) / S, lds = dred_lds_bytes(e, S);
+        auto go = [&](auto form) {
+            constexpr int F = decltype(form)::value;
+            if (e->is_int8) hipLaunchKernelGGL((lpcn::dred_stream_kernel<F, true>), dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, e->d_dredq, n, ml, init, d_rec, u_start, u_count, d_state, d_latents, d_out, ds, rf);
+            else hipLaunchKernelGGL((lpcn::dred_stream_kernel<F, false>), dim3(grid), dim3(lpcn::DRED_THREADS), lds, st, e->d_dred, n, ml, init, d_rec, u_start, u_count, d_state, d_latents, d_out, ds, rf);
+        };
+        switch (S) {
+        case 1: go(std::integral_constant<int, 1>{}); break;
+        case 2: go(std::integral_constant<int, 2>{}); break;
+        case 4: go(std::integral_constant<int, 4>{}); break;
+        default: go(std::integral_constant<int, 8>{}); break;
+        }
+    }
+    if (hipGetLastError() != hipSuccess) { snprintf(g_err, sizeof(g_err), "DRED %s: kernel launch failed", init ? "init" : "step"); return LPCN_E_HIP; }
+    return 0;
+}
+
+// checks, the records' upload through the pinned buffer (none for the uniform forms), one launch.  init: `flag` is `which`.  first == NULL: the plain layout
+static int dred_stream_enqueue(lpcn_batch_dev *b, int init, const float *d_state, const float *d_latents, const int *flag, const int *start, const int *count, int u_start,
+                               int u_count, const int *first, const int *take, float *d_out, hipStream_t st)
+{
+    long long rows = 0;
+    int rc = init ? lpcn_batch_dev_dred_init_check(b, flag) : lpcn_batch_dev_dred_step_check(b, start, count, u_start, u_count, first, take, &rows);
+    if (rc) return rc;
+    const int *per = init ? flag : count;
+    bool any = !per && b->active > 0 && (init || u_count > 0);
+    for (int s = 0; per && s < b->active; ++s) any |= per[s] != 0;
+    if (!any) return 0;
+    // (a packed step that takes no row still advances its streams)
+    if (init ? !d_state : (!d_latents || (!d_out && (!first || rows)))) { snprintf(g_err, sizeof(g_err), "bad DRED %s arguments", init ? "init" : "step"); return LPCN_E_ARG; }
+    lpcn_dred_host *p = b->dred.get();
+    if (per && stream_is_capturing(st)) { snprintf(g_err, sizeof(g_err), "a DRED %s with host arrays cannot be captured: its launch depends on them (the uniform form can)", init ? "init" : "step"); return LPCN_E_ARG; }
+    if ((rc = order_begin(b, st))) return rc;
+    if (per) {
+        if (p->srec_pending) { HIP_TRY(hipEventSynchronize(p->ev_srec)); p->srec_pending = false; }      // (the previous call's records have left the pinned buffer)
+        int *h = (int *)p->h_srec.p, row = 0;
+        for (int s = 0; s < b->active; ++s) {
+            int *q = h + (size_t)s * lpcn::DRED_SREC;
+            q[0] = init ? flag[s] != 0 : 0; q[1] = init ? 0 : start[s]; q[2] = init ? 0 : count[s];
+            q[3] = first ? first[s] : -1; q[4] = first ? take[s] : 0; q[5] = row; q[6] = q[7] = 0;
+            if (first) row += take[s];
+        }
+        HIP_TRY(hipMemcpyAsync(p->d_srec, h, sizeof(int) * lpcn::DRED_SREC * (size_t)b->active, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(p->ev_srec, st));
+        p->srec_pending = true;
+    }
+    if ((rc = dred_stream_launch(b, st, init, per ? (const int *)p->d_srec : nullptr, u_start, u_count, d_state, d_latents, d_out))) return rc;
+    return order_end(b, st);
+}
+
+extern "C" int lpcn_batch_dev_dred_init(lpcn_batch_dev *b, const float *d_state, const int *which, void *hip_stream)
+{
+    NEED_DRED_STATE(b);
+    DeviceGuard guard(b->e->device);
+    return dred_stream_enqueue(b, 1, d_state, nullptr, which, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : b->e->stream);
+}
+extern "C" int lpcn_batch_dev_dred_step(lpcn_batch_dev *b, const float *d_latents, const int *start, const int *count, int first_latent, int n_latents, float *d_features,
+                                        void *hip_stream)
+{
+    NEED_DRED_STATE(b);
+    DeviceGuard guard(b->e->device);
+    return dred_stream_enqueue(b, 0, nullptr, d_latents, nullptr, start, count, first_latent, n_latents, nullptr, nullptr, d_features, hip_stream ? (hipStream_t)hip_stream : b->e->stream);
+}
+extern "C" int lpcn_batch_dev_dred_step_packed(lpcn_batch_dev *b, const float *d_latents, const int *start, const int *count, const int *first, const int *take,
+                                               float *d_packed, void *hip_stream)
+{
+    NEED_DRED_STATE(b);
+    if (!start || !count || !first || !take) { snprintf(g_err, sizeof(g_err), "bad DRED step arguments"); return LPCN_E_ARG; }
+    DeviceGuard guard(b->e->device);
+    return dred_stream_enqueue(b, 0, nullptr, d_latents, nullptr, start, count, 0, 0, first, take, d_packed, hip_stream ? (hipStream_t)hip_stream : b->e->stream);
+}
+
+// host pointers: the active streams' rows in, one launch, and for a step the output down whole and out to the caller, the rows of this call alone
+extern "C" int lpcn_batch_dev_dred_init_host(lpcn_batch_dev *b, const float *state, const int *which)
+{
+    NEED_DRED_STATE(b);
+    int rc = lpcn_batch_dev_dred_init_check(b, which);
+    if (rc) return rc;
+    if (!state) { snprintf(g_err, sizeof(g_err), "bad DRED init arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
+    DeviceGuard guard(b->e->device);
+    lpcn_dred_host *p = b->dred.get();
+    hipStream_t st = b->e->stream;
+    const size_t per_s = (size_t)dred_state_dim(b->e);
+    if ((rc = p->d_state.reserve(b, (size_t)b->n * per_s))) return rc;
+    if ((rc = order_begin(b, st))) return rc;      // the staging buffer may still be read by work on a caller stream
+    HIP_TRY(hipMemcpyAsync(p->d_state, state, sizeof(float) * (size_t)b->active * per_s, hipMemcpyHostToDevice, st));
+    if ((rc = dred_stream_enqueue(b, 1, p->d_state, nullptr, which, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, st))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int lpcn_batch_dev_dred_step_host(lpcn_batch_dev *b, const float *latents, const int *start, const int *count, float *features)
+{
+    NEED_DRED_STATE(b);
+    if (!start || !count) { snprintf(g_err, sizeof(g_err), "bad DRED step arguments"); return LPCN_E_ARG; }
+    int rc = lpcn_batch_dev_dred_step_check(b, start, count, 0, 0, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (!latents || !features) { snprintf(g_err, sizeof(g_err), "bad DRED step arguments"); return LPCN_E_ARG; }
+    if (!b->active) return 0;
+    DeviceGuard guard(b->e->device);
+    lpcn_dred_host *p = b->dred.get();
+    hipStream_t st = b->e->stream;
+    const size_t n = (size_t)b->active, per_l = (size_t)p->max_latents * dred_latent_dim(b->e), per_f = (size_t)LPCN_DRED_FRAMES * p->max_latents * LPCN_NB_FEAT;
+    if ((rc = p->d_latents.reserve(b, (size_t)b->n * per_l)) || (rc = p->d_feat.reserve(b, (size_t)b->n * per_f)) || (rc = p->h_feat.reserve(sizeof(float) * (size_t)b->n * per_f))) return rc;
+    if ((rc = order_begin(b, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_latents, latents, sizeof(float) * n * per_l, hipMemcpyHostToDevice, st));
+    if ((rc = dred_stream_enqueue(b, 0, nullptr, p->d_latents, nullptr, start, count, 0, 0, nullptr, nullptr, p->d_feat, st))) return rc;
+    HIP_TRY(hipMemcpyAsync(p->h_feat.p, p->d_feat, sizeof(float) * n * per_f, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t row = (size_t)LPCN_DRED_FRAMES * LPCN_NB_FEAT;
+    for (size_t s = 0; s < n; ++s)
+        memcpy(features + s * per_f + row * start[s], (const float *)p->h_feat.p + s * per_f + row * start[s], sizeof(float) * row * (size_t)count[s]);
     return 0;
 }

@@ -13,7 +13,8 @@ extern "C" int lpcn_batch_dev_snapshot_layout(const lpcn_batch_dev *b, int *layo
     cfg[SNAP_C_KEEP] = b->d_keep_lpc.p != nullptr;
     if (const lpcn_plc_host *p = b->plc.get()) { cfg[SNAP_C_PLC] = 1; cfg[SNAP_C_PLC_OPTIONS] = p->options; cfg[SNAP_C_G1] = plc_units(b->e, 0); cfg[SNAP_C_G2] = plc_units(b->e, 1); }
     if (const lpcn_denc_host *p = b->denc.get()) { cfg[SNAP_C_DENC_FLOATS] = (int)p->rec; cfg[SNAP_C_DENC_DFRAMES] = p->max_dframes; }
-    const int n = snap_layout_build(cfg, 0, layout);
+    const int ddec = b->dred && b->dred->st ? (int)b->dred->st_rec : 0;
+    const int n = snap_layout_build_dec(cfg, ddec, 0, layout);
     if (n < 0) { snprintf(g_err, sizeof(g_err), "snapshot: the batch's per-stream arrays have no layout"); return LPCN_E_HIP; }
     return n;
 }
@@ -122,10 +123,13 @@ extern "C" int lpcn_batch_dev_snapshot_enable(lpcn_batch_dev *b, const int *layo
 {
     DeviceGuard guard(b->e->device);
     int rc = 0;
+    // (the one subsystem a snapshot cannot bring along: its max_latents is the batch's to say.  Refused before anything is enabled)
+    if (snap_find(layout, LPCNET_SNAP_DRED_DEC) && !b->dred) { snprintf(g_err, sizeof(g_err), "snapshot: section DRED_DEC needs the DRED decoder enabled on the batch first (lpcnet_batch_dred_enable)"); return LPCN_E_MODEL; }
     if (snap_find(layout, LPCNET_SNAP_AN) && !b->d_an_state && (rc = lpcn_batch_dev_analysis_enable(b, 1))) return rc;
     if (snap_find(layout, LPCNET_SNAP_ENC_VQ) && !b->d_enc_vq_mem && (rc = lpcn_batch_dev_encoder_enable(b, 1))) return rc;
     if (snap_find(layout, LPCNET_SNAP_KEEP_LPC) && !b->d_keep_lpc && (rc = group_alloc(b))) return rc;
     if (snap_find(layout, LPCNET_SNAP_DRED_ENC) && !b->denc && (rc = lpcn_batch_dev_dred_enc_enable(b, layout[SNAP_L_DENC_DFRAMES] > 0 ? layout[SNAP_L_DENC_DFRAMES] : 1))) return rc;
+    if (snap_find(layout, LPCNET_SNAP_DRED_DEC) && !(b->dred && b->dred->st) && (rc = lpcn_batch_dev_dred_state_enable(b))) return rc;      // (after dred_enable alone)
     return 0;
 }
 

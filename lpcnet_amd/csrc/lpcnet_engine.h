@@ -458,6 +458,24 @@ int  lpcn_batch_dev_dred_decode(lpcn_batch_dev *b, const float *d_state, const f
 int  lpcn_batch_dev_dred_decode_packed(lpcn_batch_dev *b, const float *d_state, const float *d_latents, const int *count, const int *first, const int *take,
                                        float *d_packed, void *hip_stream);
 int  lpcn_batch_dev_dred_decode_host(lpcn_batch_dev *b, const float *state, const float *latents, const int *count, float *features);
+/* ... and the decoder as a per-stream state (DRED_rdovae_dec_init_states / DRED_rdovae_decode_qframe): a float record per stream, one
+ * of the batch's per-stream arrays.  init: state -> the records of the selected streams (which == NULL: every active one).  step: latents start ..
+ * start + count - 1 from the record, feature rows 4 start .. 4 (start + count) - 1 (start == count == NULL: first_latent / n_latents for every active
+ * stream -- nothing of the launch depends on the host, so it can be captured). */
+int  lpcn_batch_dev_dred_state_enable(lpcn_batch_dev *b);                     /* after dred_enable; LPCN_E_MODEL before it */
+int  lpcn_batch_dev_dred_state_enabled(const lpcn_batch_dev *b);              /* floats of one stream's three states, 0 before dred_state_enable */
+int  lpcn_batch_dev_dred_get_dec_state(lpcn_batch_dev *b, int stream, float *out);      /* dense2_state, dense4_state, dense6_state */
+int  lpcn_batch_dev_dred_set_dec_state(lpcn_batch_dev *b, int stream, const float *in);
+int  lpcn_batch_dev_dred_init_check(const lpcn_batch_dev *b, const int *which);         /* the argument checks alone */
+int  lpcn_batch_dev_dred_step_check(const lpcn_batch_dev *b, const int *start, const int *count, int first_latent, int n_latents, const int *first, const int *take,
+                                    long long *rows);
+int  lpcn_batch_dev_dred_init(lpcn_batch_dev *b, const float *d_state, const int *which, void *hip_stream);
+int  lpcn_batch_dev_dred_step(lpcn_batch_dev *b, const float *d_latents, const int *start, const int *count, int first_latent, int n_latents, float *d_features,
+                              void *hip_stream);
+int  lpcn_batch_dev_dred_step_packed(lpcn_batch_dev *b, const float *d_latents, const int *start, const int *count, const int *first, const int *take,
+                                     float *d_packed, void *hip_stream);
+int  lpcn_batch_dev_dred_init_host(lpcn_batch_dev *b, const float *state, const int *which);
+int  lpcn_batch_dev_dred_step_host(lpcn_batch_dev *b, const float *latents, const int *start, const int *count, float *features);
 
 /* DRED encoder (DRED_rdovae_encode_dframe per stream and double frame, rdovae_enc_kernels.hip.h): one launch encodes every active
  * stream's double frames of a call.  Per stream the batch keeps the three GRU states and the conv memory: zero when the encoder is enabled, zeroed by

@@ -46,20 +46,21 @@ static inline const int *snap_find(const int *lay, int id)
 static inline const char *snap_section_name(int id)
 {
     static const char *const name[] = {"?", "SYNTH", "DEC_VQ", "AN", "ENC_VQ", "KEEP_A", "KEEP_B", "KEEP_LPC", "KEEP_FLAG", "PLC_Q", "PLC_FEAT", "PLC_NET", "PLC_DC",
-                                       "PLC_DELTA", "PLC_FEC", "PLC_FBUF", "PLC_LP", "PLC_BURG", "PLC_AN", "PLC_CTL", "DRED_ENC"};
-    return id >= 1 && id <= LPCNET_SNAP_DRED_ENC ? name[id] : name[0];
+                                       "PLC_DELTA", "PLC_FEC", "PLC_FBUF", "PLC_LP", "PLC_BURG", "PLC_AN", "PLC_CTL", "DRED_ENC", "DRED_DEC"};
+    return id >= 1 && id <= LPCNET_SNAP_DRED_DEC ? name[id] : name[0];
 }
 static inline int snap_is_plc(int id) { return id >= LPCNET_SNAP_PLC_Q && id <= LPCNET_SNAP_PLC_CTL; }
 static inline int snap_is_host_half(int id) { return id == LPCNET_SNAP_KEEP_FLAG || id == LPCNET_SNAP_PLC_CTL; }
 
 /* The layout of a configuration; the three struct sizes are the library's own.  Returns the layout's ints, or -1 for a configuration that has
- * no layout (negative or odd sizes, PLC widths beyond the engine's). */
-static inline int snap_layout_build(const int *cfg, unsigned long long model_hash, int *lay)
+ * no layout (negative or odd sizes, PLC widths beyond the engine's).  ddec: floats of the DRED decoder's record (0: the batch has none) -- no field
+ * of the public ten-int configuration and none of the head: the section's own size says it, and a configuration describes a batch without it. */
+static inline int snap_layout_build_dec(const int *cfg, int ddec, unsigned long long model_hash, int *lay)
 {
     int k = 0;
     long long off = 0;
     const int plc = cfg[SNAP_C_PLC] != 0, g1 = plc ? cfg[SNAP_C_G1] : 0, g2 = plc ? cfg[SNAP_C_G2] : 0, denc = cfg[SNAP_C_DENC_FLOATS];
-    if (denc < 0 || (plc && (g1 < 1 || g2 < 1 || g1 > LPCN_PLC_MAX_UNITS || g2 > LPCN_PLC_MAX_UNITS))) return -1;
+    if (denc < 0 || ddec < 0 || (plc && (g1 < 1 || g2 < 1 || g1 > LPCN_PLC_MAX_UNITS || g2 > LPCN_PLC_MAX_UNITS))) return -1;
 #define SNAP_ADD(id, nbytes) do { int *s_ = lay + SNAP_L_HEAD + 3 * k++; s_[0] = (id); s_[1] = (int)(nbytes); s_[2] = (int)off; off = (off + s_[1] + 15) / 16 * 16; } while (0)
     SNAP_ADD(LPCNET_SNAP_SYNTH, sizeof(lpcn_stream_state));
     SNAP_ADD(LPCNET_SNAP_DEC_VQ, sizeof(float) * LPCN_NB_BANDS);
@@ -79,6 +80,7 @@ static inline int snap_layout_build(const int *cfg, unsigned long long model_has
         SNAP_ADD(LPCNET_SNAP_PLC_CTL, sizeof(lpcn_plc_ctl));
     }
     if (denc) SNAP_ADD(LPCNET_SNAP_DRED_ENC, sizeof(float) * (size_t)denc);
+    if (ddec) SNAP_ADD(LPCNET_SNAP_DRED_DEC, sizeof(float) * (size_t)ddec);
 #undef SNAP_ADD
     if (off > 0x7ffffff0LL) return -1;
     lay[SNAP_L_RECORD] = (int)off; lay[SNAP_L_SECTIONS] = k;
@@ -88,6 +90,7 @@ static inline int snap_layout_build(const int *cfg, unsigned long long model_has
     lay[SNAP_L_HASH_LO] = (int)(unsigned)(model_hash & 0xffffffffu); lay[SNAP_L_HASH_HI] = (int)(unsigned)(model_hash >> 32);
     return SNAP_L_HEAD + 3 * k;
 }
+static inline int snap_layout_build(const int *cfg, unsigned long long model_hash, int *lay) { return snap_layout_build_dec(cfg, 0, model_hash, lay); }
 
 /* Is this int array of `n` ints a layout?  Known ids in rising order, sizes that are whole ints, every section at the rounded end of the one before it, the record
  * the rounded end of the last. */
@@ -100,7 +103,7 @@ static inline int snap_layout_valid(const int *lay, int n)
     int last = 0;
     for (int i = 0; i < k; i++) {
         const int *s = snap_section(lay, i);
-        if (s[0] <= last || s[0] > LPCNET_SNAP_DRED_ENC || s[1] < 4 || s[1] % 4 || s[2] != end) return 0;
+        if (s[0] <= last || s[0] > LPCNET_SNAP_DRED_DEC || s[1] < 4 || s[1] % 4 || s[2] != end) return 0;
         last = s[0];
         end = ((long long)s[2] + s[1] + 15) / 16 * 16;
     }
@@ -180,6 +183,10 @@ static inline int snap_blob_parse(const void *buf, size_t len, int *m, int *lay,
     if (k < 1 || k > LPCN_SNAP_MAX_SECTIONS || len < sizeof(int) * ((size_t)LPCN_SNAP_BLOB_HEAD + SNAP_L_HEAD + 3 * (size_t)k)) return -1;
     memcpy(lay, (const char *)buf + sizeof(int) * LPCN_SNAP_BLOB_HEAD, sizeof(int) * ((size_t)SNAP_L_HEAD + 3 * (size_t)k));
     if (!snap_layout_valid(lay, SNAP_L_HEAD + 3 * k)) return -1;
+    {   /* a blob's head and sections say the same about the DRED encoder: the section is there with the head's floats, or neither is */
+        const int *d = snap_find(lay, LPCNET_SNAP_DRED_ENC);
+        if (lay[SNAP_L_DENC_FLOATS] ? (!d || d[1] != 4 * lay[SNAP_L_DENC_FLOATS]) : d != NULL) return -1;
+    }
     if ((size_t)h[2] > (len - sizeof(h)) / ((size_t)lay[SNAP_L_RECORD] + sizeof(int) * LPCNET_SNAP_META) || len < snap_blob_bytes(lay, h[2])) return -1;
     *m = h[2];
     if (meta) *meta = (const int *)buf + LPCN_SNAP_BLOB_HEAD + snap_layout_ints(lay);

@@ -4,6 +4,7 @@
     python tools/dred_rate.py OUT.json [latents]       (profiles/dred_rate.json when run for the record)
     python tools/dred_rate.py --int8 OUT.json [latents]       (profiles/dred_i8_rate.json: the int8 decoder beside the float one)
     python tools/dred_rate.py --fast OUT.json [latents]       (profiles/dred_fast_rate.json: the FAST flavour beside PARITY)
+    python tools/dred_rate.py --resume OUT.json [latents]     (profiles/dred_stream_rate.json: init + steps on a kept state beside the one-shot call)
 
 For 256, 2 048 and 8 192 streams, 25 latents each (one second of redundancy) at the exported width of 256: the time of one call (HIP events
 around the enqueue-only device-pointer call, on a caller's stream) with the streams per workgroup pinned to 1, 2, 4, 8 and left to the engine's
@@ -19,7 +20,13 @@ rows of the same session, `int8_over_float` the ratio of the medians per stream 
 the CPU yardstick is the reference's AVX2 int8 build (liblpcnet_ref_ai.so).
 --fast (profiles/dred_fast_rate.json): PARITY at the table's form beside the FAST flavour (lpcnet_batch_dred_set_fast) pinned to every tile that is
 built and at the engine's choice (mode 1), alternating call by call on one batch; the same protocol and stream counts.  FAST's output is compared with
-the pinned tile's bit for bit and its largest deviation from PARITY's is recorded.  Run it under a time limit:
+the pinned tile's bit for bit and its largest deviation from PARITY's is recorded.
+--resume (profiles/dred_stream_rate.json): the decoder as a per-stream state (lpcnet_batch_dred_init / _dred_step) beside the one-shot call, PARITY and
+FAST, at the same stream counts and width: init + 25 uniform steps of one latent against one dred_decode of 25; "5, then 5 more" -- init + step(0, 5),
+then step(5, 5) -- against dred_decode of 5 followed by dred_decode of 10; a captured replay of init + step(5) against the eager pair.  The scenarios
+alternate inside one process and one batch; each is timed by HIP events around all of its calls.  The stepped features are compared with
+dred_decode's bit for bit.  The `decode_25` column is the one-shot call's time in this session: what `--fast` reports as `parity` and `fast`.
+Run it under a time limit:
     timeout -k 10 600 python tools/dred_rate.py profiles/dred_rate.json
 """
 import json
@@ -205,11 +212,119 @@ def measure_fast(out_path, n_latents=25):
         fh.write("\n")
 
 
+def measure_resume(out_path, n_latents=25):
+    import torch
+    import dred_model as dm
+    from lpcnet_amd import api
+    dev = torch.device("cuda:0")
+    blob = dm.set_blob("w256")
+    info = api.dred_model_info(blob)
+    base_state, base_lat = dm.inputs(info["latent_dim"], 64, n_latents, seed=0x2A7E)
+    result = dict(build=api.build_info(), device=torch.cuda.get_device_name(0), widths=info["widths"], latent_dim=info["latent_dim"], latents=n_latents,
+                  timed_calls=TIMED, warmup_calls=WARMUP,
+                  note="scenarios and arithmetics alternate in one process and one batch; ms of all calls of a scenario by HIP events on a caller's stream", streams=[])
+    s = torch.cuda.Stream()
+    for n in STREAMS:
+        b = api.LPCNetBatch(n, blob)
+        b.dred_enable(n_latents)
+        b.dred_state_enable()
+        reps = n // 64 + 1
+        d_state = torch.from_numpy(np.ascontiguousarray(np.tile(base_state, (reps, 1))[:n])).to(dev)
+        d_lat = torch.from_numpy(np.ascontiguousarray(np.tile(base_lat, (reps, 1, 1))[:n])).to(dev)
+        d_out = torch.zeros((n, 4 * n_latents, 20), dtype=torch.float32, device=dev)
+        d_step = torch.zeros((n, 4 * n_latents, 20), dtype=torch.float32, device=dev)
+        full, five, ten = (np.full(n, k, np.int32) for k in (n_latents, 5, 10))
+        sp, lp = d_state.data_ptr(), d_lat.data_ptr()
+        torch.cuda.synchronize()
+
+        def decode(count, out=d_out):
+            b.dred_decode_device(sp, lp, count, out.data_ptr(), hip_stream=s.cuda_stream)
+
+        def init():
+            b.dred_init_device(sp, hip_stream=s.cuda_stream)
+
+        def step(first, k):
+            b.dred_step_device(lp, None, None, d_step.data_ptr(), hip_stream=s.cuda_stream, first_latent=first, n_latents=k)
+
+        def one_by_one():
+            init()
+            for l in range(n_latents):
+                step(l, 1)
+
+        def resume():
+            init()
+            step(0, 5)
+            step(5, 5)
+
+        def again():
+            decode(five)
+            decode(ten)
+
+        def pair():
+            init()
+            step(0, 5)
+
+        graphs = {}
+        row = dict(streams=n, modes=[])
+        with torch.cuda.stream(s):
+            for mode in (0, 1):                        # a graph per arithmetic: the launch is chosen when it is captured
+                b.dred_fast = mode
+                pair()
+                s.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=s):
+                    b.dred_init_device(sp, hip_stream=torch.cuda.current_stream().cuda_stream)
+                    b.dred_step_device(lp, None, None, d_step.data_ptr(), hip_stream=torch.cuda.current_stream().cuda_stream, first_latent=0, n_latents=5)
+                graphs[mode] = g
+            scen = [("decode_25", lambda m: decode(full)), ("init_and_25_steps_of_one", lambda m: one_by_one()), ("decode_5_then_decode_10", lambda m: again()),
+                    ("init_step_5_then_step_5", lambda m: resume()), ("eager_init_step_5", lambda m: pair()), ("captured_init_step_5", lambda m: graphs[m].replay())]
+            ms = {(mode, name): [] for mode in (0, 1) for name, _ in scen}
+            for k in range(WARMUP + TIMED):
+                for mode in (0, 1):
+                    b.dred_fast = mode
+                    for name, fn in scen:
+                        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record(s)
+                        fn(mode)
+                        e.record(s)
+                        e.synchronize()
+                        if k >= WARMUP:
+                            ms[mode, name].append(a.elapsed_time(e))
+                        elif k == 0 and name == "init_and_25_steps_of_one" and not torch.equal(d_step.view(torch.int32), d_out.view(torch.int32)):
+                            raise SystemExit("mode %d: the stepped features differ from dred_decode's at %d streams" % (mode, n))
+                        elif k == 0 and name == "captured_init_step_5":
+                            got = d_step[:, :20].clone()
+                            decode(five, d_step)
+                            s.synchronize()
+                            if not torch.equal(got.view(torch.int32), d_step[:, :20].view(torch.int32)):
+                                raise SystemExit("mode %d: the captured replay differs from dred_decode's at %d streams" % (mode, n))
+        for mode in (0, 1):
+            cols = {}
+            for name, _ in scen:
+                v = np.array(ms[mode, name])
+                cols[name] = dict(median_ms=float(np.median(v)), min_ms=float(v.min()), max_ms=float(v.max()), p10_ms=float(np.percentile(v, 10)), p90_ms=float(np.percentile(v, 90)))
+            spread = max(c["p90_ms"] - c["p10_ms"] for c in cols.values())
+            med = {k: c["median_ms"] for k, c in cols.items()}
+            row["modes"].append(dict(mode="fast" if mode else "parity", set_fast=mode, scenarios=cols, spread_ms=spread,
+                                     steps_of_one_over_decode_25=med["init_and_25_steps_of_one"] / med["decode_25"],
+                                     resume_gain_over_decoding_again_ms=med["decode_5_then_decode_10"] - med["init_step_5_then_step_5"],
+                                     capture_gain_over_eager_ms=med["eager_init_step_5"] - med["captured_init_step_5"]))
+        b.dred_fast = 0
+        b.close()
+        print(json.dumps(row), flush=True)
+        result["streams"].append(row)
+    with open(out_path, "w") as fh:
+        json.dump(result, fh, indent=1)
+        fh.write("\n")
+
+
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     if not args:
         raise SystemExit(__doc__)
-    if "--fast" in sys.argv[1:]:
+    if "--resume" in sys.argv[1:]:
+        measure_resume(args[0], int(args[1]) if len(args) > 1 else 25)
+    elif "--fast" in sys.argv[1:]:
         measure_fast(args[0], int(args[1]) if len(args) > 1 else 25)
     else:
         measure(args[0], int(args[1]) if len(args) > 1 else 25, int8="--int8" in sys.argv[1:])
